@@ -352,6 +352,10 @@ def bench_ec(eng, name, args):
             post = []
             for b in range(count):
                 d_pb = ring_p[b % len(ring_p)]
+                if b >= len(ring_p):
+                    # the box that used this slot last must be absorbed and have its responses out before P(i) of this box
+                    # overwrites its ring_p / d_rr buffers: the throttle below bounds the boxes in flight, not which ones are done
+                    post[b - len(ring_p)].result()[1].result()
                 while len(post) - sum(f.done() for f in post) >= e2e_depth:
                     time.sleep(0.0002)
                 eng.ec_deal_compute(gid, coeff_bytes[b % len(coeff_bytes)], d_pos.data_ptr(), d_pk.data_ptr(), d_wt.data_ptr(), n, d_pb.data_ptr())
@@ -365,7 +369,8 @@ def bench_ec(eng, name, args):
     e2e = deal_e2e(e2e_boxes)
     torch.cuda.synchronize()
     e2e_s = (time.perf_counter() - t_e) / e2e_boxes
-    assert e2e[0][0] == d["digest"] and e2e[0][1] == responses, f"end-to-end dealer ({name}): box 0 differs from the dealer's"
+    assert e2e[0][0] == d["digest"], f"end-to-end dealer ({name}): box 0's digest differs from the dealer's"
+    assert e2e[0][1] == responses, f"end-to-end dealer ({name}): box 0's responses differ from the dealer's"
     ec_call, ec_outputs = eng.ec_deal_call(gid, coeff_bytes[0], positions, pks, b"".join(map(sb, wits)))
     ec_call()                      # (the library call alone over ctypes buffers made once; mean of 3 after a warm call)
     t_one = time.perf_counter()
@@ -620,6 +625,17 @@ class Box:
     pass
 
 
+def dump_outputs(path, last):
+    """--dump-outputs: what a caller of the timed path receives for the last timed step -- the box's verdict and the
+    transcript digest the library hashed from every X_i, Y_i, a1_i, a2_i it computed (one differing bit in any share
+    changes it) -- as float32 arrays.  The inputs come from SEED alone, so runs with the same arguments are comparable."""
+    import numpy as np
+    verdict, digest, _ = last
+    os.makedirs(path, exist_ok=True)
+    np.save(os.path.join(path, "verdict.npy"), np.array([1.0 if verdict else 0.0], dtype=np.float32))
+    np.save(os.path.join(path, "digest.npy"), np.frombuffer(digest, dtype=np.uint8).astype(np.float32))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -650,7 +666,11 @@ def main():
                     "region (0: skip)")
     ap.add_argument("--config-boxes", type=int, default=-1, help="boxes timed for the other BASELINE shapes in `configs` "
                     "(C2 n=4096 t=64, one GPU's slice of C5 n=131072 t=1024; -1: 48 / 6, 0: skip)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned (verdict.npy, digest.npy; float32) into DIR")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     rank = int(os.environ.get("RANK", "0"))
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -1052,6 +1072,8 @@ def main():
     barrier()
     elapsed = time.perf_counter() - t0
     pst = eng.pipeline_stats(reset=True)          # host and kernel accounting of exactly the timed steps
+    if args.dump_outputs and rank == 0:           # before the gate, so that a box that failed to verify is on disk too
+        dump_outputs(args.dump_outputs, results[-1])
     gate(results, "timed steps: a GPU box did not verify")
     if world > 1:
         tt = torch.tensor([elapsed], dtype=torch.float64, device=commdev if smoke_one_gpu else dev)
