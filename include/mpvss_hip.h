@@ -510,6 +510,51 @@ int mpvss_box_parse(const uint8_t* buf, size_t len, mpvss_box_view* view);
 /* verify_distribution_shares of a serialized box in host memory (any of the three groups) */
 int mpvss_box_verify_wire(mpvss_ctx* ctx, const uint8_t* buf, size_t len, int* verdict, uint8_t* digest32_out);
 
+/* ---- MODP groups of a run-time modulus (ModpGroup::init, src/groups/modp.rs:72-84) ---------------------------
+ * A group handle holds an odd modulus q of at most 2048 bits -- ModpGroup::init(length).modulus() or any other -- and
+ * what the kernels need of it (Montgomery constants, the width: 5, 9 or 18 limbs of 29 bits per lane, the smallest with
+ * bits(q) <= 29 * 4 * limbs - 2).  Creating it is host work only (no GPU, no context); it is immutable afterwards and may
+ * be used from any number of contexts and threads at once.  Elements and scalars keep the 256-byte big-endian encoding
+ * of MPVSS_MODP_BYTES; inputs need not be reduced (a value >= q gives what BigInt::modpow / (a * b) % q give, modp.rs:154-156
+ * validates nothing), outputs are canonical (< q).  The group's generators are those of ModpGroup: G = 2, g = G^2 = 4.
+ * Protocol parity (verify_distribution, verify_shares) is specified for safe primes, which is what ModpGroup::init yields.
+ * The entry points below mirror the group-14 ones with the handle added, lock the context like them and are safe for
+ * concurrent callers on one context in the same sense.  Not offered for a run-time group: the block / pipeline forms,
+ * verify_many, key sets, the dealer's one-call deal and the wire format; moduli above 2048 bits (their elements need
+ * more than 256 bytes) are refused with MPVSS_E_INVALID. */
+typedef struct mpvss_modp_group mpvss_modp_group;
+/* q_be: q_len big-endian bytes (leading zeros allowed).  MPVSS_E_INVALID for an even q, q < 5 or q >= 2^2048. */
+int mpvss_modp_group_create(const uint8_t* q_be, size_t q_len, mpvss_modp_group** out);
+void mpvss_modp_group_destroy(mpvss_modp_group* grp);
+/* bit length of q, and the limbs per lane of the width the kernels run at (5, 9 or 18) */
+int mpvss_modp_group_bits(const mpvss_modp_group* grp);
+int mpvss_modp_group_limbs_per_lane(const mpvss_modp_group* grp);
+/* Group::hash_to_scalar: int_BE(SHA256(data)) mod (q-1)/2 as 256-byte big-endian (src/groups/modp.rs:142-148); host only */
+int mpvss_modp_group_hash_to_scalar(const mpvss_modp_group* grp, const uint8_t* data, size_t len, uint8_t out256[256]);
+/* out[i] = bases[i]^exps[i] mod q                                    ModpGroup::exp (src/groups/modp.rs:122-128) */
+int mpvss_modp_group_batch_exp(mpvss_ctx* ctx, const mpvss_modp_group* grp, int space, const uint8_t* bases, const uint8_t* exps,
+                               size_t n, uint8_t* out);
+/* out[i] = a[i] * b[i] mod q                                         ModpGroup::mul (src/groups/modp.rs:130-132) */
+int mpvss_modp_group_batch_mul(mpvss_ctx* ctx, const mpvss_modp_group* grp, int space, const uint8_t* a, const uint8_t* b, size_t n,
+                               uint8_t* out);
+/* X[i] = prod_{j<t} C_j^(positions[i]^j mod (q-1)) mod q           src/participant.rs:423-434 (as mpvss_modp_commit_eval) */
+int mpvss_modp_group_commit_eval(mpvss_ctx* ctx, const mpvss_modp_group* grp, int space, const uint8_t* commitments, size_t t,
+                                 const int64_t* positions, size_t n, uint8_t* x_out);
+/* a1[i] = g1^r[i] h1[i]^c_i, a2[i] = g2[i]^r[i] h2[i]^c_i          src/dleq.rs:66-84 (as mpvss_modp_dleq_commitments) */
+int mpvss_modp_group_dleq_commitments(mpvss_ctx* ctx, const mpvss_modp_group* grp, int space, const uint8_t* g1_host, const uint8_t* h1,
+                                      const uint8_t* g2, const uint8_t* h2, const uint8_t* r, const uint8_t* c, int c_per_share,
+                                      size_t n, uint8_t* a1_out, uint8_t* a2_out);
+/* whole-box verification, src/participant.rs:399-455: same contract as mpvss_modp_verify_distribution (verdict, digest of the
+ * transcript, optional host dumps of X, a1, a2; n == 0 hashes the empty transcript) */
+int mpvss_modp_group_verify_distribution(mpvss_ctx* ctx, const mpvss_modp_group* grp, int space, const uint8_t* commitments, size_t t,
+                                         const int64_t* positions, const uint8_t* pubkeys, const uint8_t* shares,
+                                         const uint8_t* responses, size_t n, const uint8_t* challenge_host, int* verdict,
+                                         uint8_t* digest32_out, uint8_t* x_out_host, uint8_t* a1_out_host, uint8_t* a2_out_host);
+/* n share-box proofs, src/participant.rs:361-386 -> src/dleq.rs:275-302 (as mpvss_modp_verify_shares); products on the GPU, the
+ * per-share hashes on the host */
+int mpvss_modp_group_verify_shares(mpvss_ctx* ctx, const mpvss_modp_group* grp, int space, const uint8_t* pk, const uint8_t* s,
+                                   const uint8_t* y, const uint8_t* c, const uint8_t* r, size_t n, uint8_t* verdicts_host);
+
 /* ---- hashing helpers (host only; Group::hash_to_scalar, src/groups/modp.rs:142-148) ------ */
 
 /* out32 = SHA-256(data) */

@@ -46,6 +46,9 @@ EXPORTED_SYMBOLS = (
     "mpvss_modp_distribute_compute", "mpvss_modp_distribute_absorb",
     "mpvss_process_init", "mpvss_modp_verify_block_compute_flags",
     "mpvss_modp_extract_shares_compute", "mpvss_modp_extract_shares_absorb",
+    "mpvss_modp_group_create", "mpvss_modp_group_destroy", "mpvss_modp_group_bits", "mpvss_modp_group_limbs_per_lane",
+    "mpvss_modp_group_hash_to_scalar", "mpvss_modp_group_batch_exp", "mpvss_modp_group_batch_mul", "mpvss_modp_group_commit_eval",
+    "mpvss_modp_group_dleq_commitments", "mpvss_modp_group_verify_distribution", "mpvss_modp_group_verify_shares",
 )
 
 GROUP_SECP256K1 = 1
@@ -201,6 +204,19 @@ def load_library() -> C.CDLL:
     lib.mpvss_issue_probe.argtypes = [vp, ci, C.c_double, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double)]
     lib.mpvss_modp_extract_shares.argtypes = [vp, ci, u8p, u8p, u8p, u8p, sz, u8p, u8p]
     lib.mpvss_ec_extract_shares.argtypes = [vp, ci, ci, u8p, u8p, u8p, u8p, sz, u8p, u8p]
+    lib.mpvss_modp_group_create.argtypes = [u8p, sz, C.POINTER(vp)]
+    lib.mpvss_modp_group_destroy.argtypes = [vp]
+    lib.mpvss_modp_group_destroy.restype = None
+    lib.mpvss_modp_group_bits.argtypes = [vp]
+    lib.mpvss_modp_group_limbs_per_lane.argtypes = [vp]
+    lib.mpvss_modp_group_hash_to_scalar.argtypes = [vp, u8p, sz, u8p]
+    lib.mpvss_modp_group_batch_exp.argtypes = [vp, vp, ci, u8p, u8p, sz, u8p]
+    lib.mpvss_modp_group_batch_mul.argtypes = [vp, vp, ci, u8p, u8p, sz, u8p]
+    lib.mpvss_modp_group_commit_eval.argtypes = [vp, vp, ci, u8p, sz, i64p, sz, u8p]
+    lib.mpvss_modp_group_dleq_commitments.argtypes = [vp, vp, ci, u8p, u8p, u8p, u8p, u8p, u8p, ci, sz, u8p, u8p]
+    lib.mpvss_modp_group_verify_distribution.argtypes = [vp, vp, ci, u8p, sz, i64p, u8p, u8p, u8p, sz, u8p,
+                                                         C.POINTER(ci), u8p, u8p, u8p, u8p]
+    lib.mpvss_modp_group_verify_shares.argtypes = [vp, vp, ci, u8p, u8p, u8p, u8p, u8p, sz, u8p]
     return lib
 
 
@@ -215,6 +231,51 @@ def _buf(b: Optional[bytes]):
 def _out(nbytes: int):
     arr = (C.c_uint8 * max(nbytes, 1))()
     return arr, C.cast(arr, C.c_void_p)
+
+
+class ModpGroup:
+    """Handle of a run-time MODP group (mpvss_modp_group_create): any odd modulus q of at most 2048 bits, host only --
+    the counterpart of the reference's ModpGroup::init(length) (src/groups/modp.rs:72-84).  Usable with every Engine."""
+
+    def __init__(self, q: int):
+        self.lib = load_library()
+        if q < 0:
+            raise EngineError("modp group: negative modulus")
+        qb = q.to_bytes(max(1, (q.bit_length() + 7) // 8), "big")
+        kq, pq = _buf(qb)
+        h = C.c_void_p()
+        rc = self.lib.mpvss_modp_group_create(pq, len(qb), C.byref(h))
+        if rc != 0:
+            raise EngineError(f"mpvss_modp_group_create failed: rc={rc}")
+        self.handle = h
+        self.q = q
+
+    @property
+    def bits(self) -> int:
+        return self.lib.mpvss_modp_group_bits(self.handle)
+
+    @property
+    def limbs_per_lane(self) -> int:
+        return self.lib.mpvss_modp_group_limbs_per_lane(self.handle)
+
+    def hash_to_scalar(self, data: bytes) -> bytes:
+        kd, pd = _buf(data if data else b"\0")
+        ko, po = _out(EB)
+        rc = self.lib.mpvss_modp_group_hash_to_scalar(self.handle, pd, len(data), po)
+        if rc != 0:
+            raise EngineError(f"mpvss_modp_group_hash_to_scalar failed: rc={rc}")
+        return bytes(ko)[:EB]
+
+    def close(self):
+        if getattr(self, "handle", None):
+            self.lib.mpvss_modp_group_destroy(self.handle)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 class Engine:
@@ -336,6 +397,68 @@ class Engine:
         if dump:
             out.update(X=bytes(kx)[: n * EB], a1=bytes(k1)[: n * EB], a2=bytes(k2)[: n * EB])
         return out
+
+    # ---- run-time MODP groups (ModpGroup handles; include/mpvss_hip.h "MODP groups of a run-time modulus")
+    def group_batch_exp(self, grp: "ModpGroup", bases: bytes, exps: bytes) -> bytes:
+        n = len(bases) // EB
+        ka, pa = _buf(bases); kb, pb = _buf(exps); ko, po = _out(n * EB)
+        self._check(self.lib.mpvss_modp_group_batch_exp(self.ctx, grp.handle, MPVSS_HOST, pa, pb, n, po), "group_batch_exp")
+        return bytes(ko)[: n * EB]
+
+    def group_batch_mul(self, grp: "ModpGroup", a: bytes, b: bytes) -> bytes:
+        n = len(a) // EB
+        ka, pa = _buf(a); kb, pb = _buf(b); ko, po = _out(n * EB)
+        self._check(self.lib.mpvss_modp_group_batch_mul(self.ctx, grp.handle, MPVSS_HOST, pa, pb, n, po), "group_batch_mul")
+        return bytes(ko)[: n * EB]
+
+    def group_commit_eval(self, grp: "ModpGroup", commitments: bytes, positions: Sequence[int]) -> bytes:
+        t = len(commitments) // EB
+        n = len(positions)
+        kc, pc = _buf(commitments)
+        pos = (C.c_int64 * max(n, 1))(*positions)
+        ko, po = _out(n * EB)
+        self._check(self.lib.mpvss_modp_group_commit_eval(self.ctx, grp.handle, MPVSS_HOST, pc, t, C.cast(pos, C.c_void_p), n, po),
+                    "group_commit_eval")
+        return bytes(ko)[: n * EB]
+
+    def group_dleq_commitments(self, grp: "ModpGroup", g1: bytes, h1: bytes, g2: bytes, h2: bytes, r: bytes, c: bytes,
+                               c_per_share: bool) -> Tuple[bytes, bytes]:
+        n = len(h1) // EB
+        k = [_buf(x) for x in (g1, h1, g2, h2, r, c)]
+        k1, p1 = _out(n * EB); k2, p2 = _out(n * EB)
+        self._check(self.lib.mpvss_modp_group_dleq_commitments(self.ctx, grp.handle, MPVSS_HOST, k[0][1], k[1][1], k[2][1], k[3][1],
+                                                               k[4][1], k[5][1], int(c_per_share), n, p1, p2),
+                    "group_dleq_commitments")
+        return bytes(k1)[: n * EB], bytes(k2)[: n * EB]
+
+    def group_verify_distribution(self, grp: "ModpGroup", commitments: bytes, positions: Sequence[int], pubkeys: bytes,
+                                  shares: bytes, responses: bytes, challenge: bytes, dump: bool = False):
+        t = len(commitments) // EB
+        n = len(positions)
+        kc, pc = _buf(commitments or None); ky, py = _buf(pubkeys or None); kY, pY = _buf(shares or None)
+        kr, pr = _buf(responses or None); kch, pch = _buf(challenge)
+        pos = (C.c_int64 * max(n, 1))(*positions)
+        verdict = C.c_int(0)
+        kd, pd = _out(32)
+        kx = k1 = k2 = None
+        px = p1 = p2 = None
+        if dump:
+            kx, px = _out(n * EB); k1, p1 = _out(n * EB); k2, p2 = _out(n * EB)
+        self._check(self.lib.mpvss_modp_group_verify_distribution(
+            self.ctx, grp.handle, MPVSS_HOST, pc, t, C.cast(pos, C.c_void_p), py, pY, pr, n, pch, C.byref(verdict), pd,
+            px, p1, p2), "group_verify_distribution")
+        out = {"verdict": bool(verdict.value), "digest": bytes(kd)[:32]}
+        if dump:
+            out.update(X=bytes(kx)[: n * EB], a1=bytes(k1)[: n * EB], a2=bytes(k2)[: n * EB])
+        return out
+
+    def group_verify_shares(self, grp: "ModpGroup", pk: bytes, s: bytes, y: bytes, c: bytes, r: bytes) -> bytes:
+        n = len(pk) // EB
+        k = [_buf(x) for x in (pk, s, y, c, r)]
+        ko, po = _out(n)
+        self._check(self.lib.mpvss_modp_group_verify_shares(self.ctx, grp.handle, MPVSS_HOST, k[0][1], k[1][1], k[2][1], k[3][1],
+                                                            k[4][1], n, po), "group_verify_shares")
+        return bytes(ko)[:n]
 
     # ---- sharded verification (one engine per GPU; see mpvss_rs_amd/sharding.py)
     def verify_block_compute(self, commitments: bytes, positions: Sequence[int], pubkeys: bytes, shares: bytes,

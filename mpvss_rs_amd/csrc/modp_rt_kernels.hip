@@ -1,0 +1,437 @@
+// Kernels of a run-time MODP group: ModpGroup::init(length) of the reference (src/groups/modp.rs:72-84) -- any odd
+// modulus q of at most 2048 bits, chosen when the program runs.
+//
+//   ModpGroup::exp / ::mul                       (src/groups/modp.rs:122-132)      k_rt_dual_exp, k_rt_mul
+//   DLEQ verifier commitments a = g1^r h1^c      (src/dleq.rs:66-84)               k_rt_dual_exp (two tables)
+//   X_i = prod_j C_j^(i^j mod (q-1))             (src/participant.rs:423-434)      k_rt_commit_eval
+//
+// Layout and program shape are those of the group-14 kernels (modp_kernels.hip): one number per DPP quad, 16 numbers
+// per one-wave workgroup, the second operand of every product staged in LDS, 16-entry window tables in HBM.  The
+// product is bnrt::mont_mul (bn_quad_rt.h): three widths (5, 9, 18 limbs per lane), n0inv a run-time value.
+//
+// Cost follows the operands: the exponent loops run over the wave's largest exponent (4-bit windows), Horner's squarings
+// over the wave's largest reduced position.  Inputs are 256-byte big-endian values of any size: they enter a width by
+// one long product (bnrt::Width::IN_ROWS rows), which reduces them mod q on the way into Montgomery form.
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+#include "bn_quad_rt.h"
+#include "modp_rt_kernels.h"
+
+using namespace bnrt;
+
+#define RT_NUMS 16   // numbers per workgroup (one wave)
+
+namespace {
+
+// occupancy of each width: the 18-limb product wants 3 waves per SIMD like the group-14 kernels (135 VGPRs); the
+// narrower ones fit more
+template <int LPL> struct Occ { static constexpr int waves = 3; };
+template <> struct Occ<9> { static constexpr int waves = 4; };
+template <> struct Occ<5> { static constexpr int waves = 6; };
+
+// limb j (29 bits at bit 29 j) of a 256-byte big-endian integer; 0 above bit 2047
+__device__ __forceinline__ u32 be_limb(const uint8_t* __restrict__ be, int j) {
+  const int o = W * j;
+  const int p = o >> 3, s = o & 7;
+  u64 w = 0;
+#pragma unroll
+  for (int t = 0; t < 5; ++t) {
+    const int idx = 255 - (p + t);
+    if (idx >= 0) w |= (u64)be[idx] << (8 * t);
+  }
+  return (u32)(w >> s) & MASK;
+}
+
+// a = in R mod N (< 2N) for any 256-byte input: the input's 29-bit limbs go to the LDS slot (IN_ROWS of them), and one
+// long product with kin = 2^(29 (IN_ROWS + L)) mod N gives in kin 2^(-29 IN_ROWS) = in R, below N + kin in / 2^(29 IN_ROWS) < 2N.
+template <int LPL>
+__device__ __forceinline__ void to_mont_in(u32 (&a)[LPL], u32* slot, const uint8_t* __restrict__ in_be, const modp_rt_consts* __restrict__ cs,
+                                           const u32 (&n)[LPL], u32 n0inv, const Lane& ln) {
+  constexpr int IN_ROWS = Width<LPL>::IN_ROWS;
+#pragma unroll
+  for (int j = (int)0; j < IN_ROWS; j += 4) {
+    const int jj = j + (int)ln.q;
+    if (jj < IN_ROWS) slot[jj] = be_limb(in_be, jj);
+  }
+  u32 k[LPL];
+  lane_load<LPL>(k, cs->kin, ln);
+  __builtin_amdgcn_wave_barrier();
+  mont_mul<LPL, false, IN_ROWS>(a, k, slot, n, n0inv, ln);
+  __builtin_amdgcn_wave_barrier();
+}
+
+// plain almost-normalised value < 2N -> canonical residue as 256 big-endian bytes (the slot is scratch)
+template <int LPL>
+__device__ __forceinline__ void store_canonical(uint8_t* __restrict__ out, const u32 (&a)[LPL], u32* slot,
+                                                const modp_rt_consts* __restrict__ cs, const Lane& ln, bool write) {
+  constexpr int L = Width<LPL>::L;
+  slot_store<LPL>(slot, a, ln);
+  __builtin_amdgcn_wave_barrier();
+  if (ln.q == 0) {
+    u32 c = 0;
+#pragma nounroll
+    for (int j = 0; j < L; ++j) {
+      const u32 v = slot[j] + c;
+      slot[j] = v & MASK;
+      c = v >> W;
+    }
+    // value < 2N: subtract N once if value >= N
+    int ge = 1;
+#pragma nounroll
+    for (int j = L - 1; j >= 0; --j) {
+      const u32 x = slot[j], y = cs->n[j];
+      if (x != y) { ge = x > y; break; }
+    }
+    if (ge) {
+      u32 borrow = 0;
+#pragma nounroll
+      for (int j = 0; j < L; ++j) {
+        const u32 d = slot[j] - cs->n[j] - borrow;
+        borrow = (d >> 31) & 1;
+        slot[j] = d & MASK;
+      }
+    }
+  }
+  __builtin_amdgcn_wave_barrier();
+  if (write) {
+    // lane q emits little-endian 32-bit words 16q .. 16q+15 (byte-swapped, mirrored position); limbs >= L are zero
+    u32* out32 = reinterpret_cast<u32*>(out);
+#pragma unroll
+    for (int i = 0; i < 16; ++i) {
+      const int wd = (int)ln.q * 16 + i;
+      const int bit = 32 * wd;
+      const int j = bit / W, s = bit % W;
+      u32 v = 0;
+      if (j < L) {
+        u64 two = (u64)slot[j] | ((u64)(j + 1 < L ? slot[j + 1] : 0u) << W);
+        two >>= s;
+        if (2 * W - s < 32) two |= (u64)(j + 2 < L ? slot[j + 2] : 0u) << (2 * W - s);
+        v = (u32)two;
+      }
+      out32[63 - wd] = __builtin_bswap32(v);
+    }
+  }
+  __builtin_amdgcn_wave_barrier();
+}
+
+// bit length of a 256-byte big-endian number, the maximum over the whole wave (every quad: lane q scans bytes 64q .. 64q+63)
+__device__ __forceinline__ int wave_max_bits(const uint8_t* __restrict__ be, const Lane& ln) {
+  const uint4* p = reinterpret_cast<const uint4*>(be + 64 * ln.q);
+  int bl = 0;
+#pragma unroll
+  for (int i = 3; i >= 0; --i) {
+    const uint4 v = p[i];
+    const u32 w4[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+    for (int k = 3; k >= 0; --k) {
+      const u32 word = __builtin_bswap32(w4[k]);       // big-endian word 4 i + k of this lane's quarter
+      if (word != 0) bl = (16 - (4 * i + k)) * 32 - __builtin_clz(word);
+    }
+  }
+  if (bl > 0) bl += (3 - (int)ln.q) * 512;
+#pragma unroll
+  for (int off = 32; off >= 1; off >>= 1) {
+    const int other = __shfl_xor(bl, off);
+    bl = other > bl ? other : bl;
+  }
+  return __builtin_amdgcn_readfirstlane(bl);
+}
+
+__device__ __forceinline__ u32 nibble(const uint8_t* __restrict__ e, int w) {
+  const u32 byte = e[255 - (w >> 1)];
+  return (w & 1) ? (byte >> 4) : (byte & 15u);
+}
+
+}  // namespace
+
+#define RT_KERNEL(LPL) __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(Occ<LPL>::waves, Occ<LPL>::waves)))
+// Horner's kernel holds two slots per number: at 5 limbs per lane its LDS (10 KB per wave) admits 4 waves per SIMD
+#define RT_KERNEL_LDS2(LPL) __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(Occ<LPL>::waves < 4 ? Occ<LPL>::waves : 4, Occ<LPL>::waves < 4 ? Occ<LPL>::waves : 4)))
+
+// ---------------------------------------------------------------------------------------
+// out_m[x] = in[x] R mod N (commitments into Montgomery form)
+// ---------------------------------------------------------------------------------------
+template <int LPL>
+__global__ void RT_KERNEL(LPL) k_rt_to_mont(const uint8_t* __restrict__ in_be, int count, u32* __restrict__ out_m,
+                                            const modp_rt_consts* __restrict__ cs) {
+  constexpr int L = Width<LPL>::L, SLOT = Width<LPL>::SLOT;
+  __shared__ __attribute__((aligned(16))) u32 lds[RT_NUMS * SLOT];
+  const Lane ln = make_lane();
+  const int xi = blockIdx.x * RT_NUMS + (threadIdx.x >> 2);
+  const bool live = xi < count;
+  const int x = live ? xi : count - 1;
+  u32* slot = lds + (threadIdx.x >> 2) * SLOT;
+  const u32 n0inv = cs->n0inv;
+  u32 n[LPL], a[LPL];
+  lane_load<LPL>(n, cs->n, ln);
+  to_mont_in<LPL>(a, slot, in_be + (size_t)x * 256, cs, n, n0inv, ln);
+  if (live) lane_store<LPL>(out_m + (size_t)x * L, a, ln);
+}
+
+// ---------------------------------------------------------------------------------------
+// 16-entry window table of each base: tab[x][d] = base^d R mod N
+// ---------------------------------------------------------------------------------------
+template <int LPL>
+__global__ void RT_KERNEL(LPL) k_rt_table(const uint8_t* __restrict__ base_be, size_t base_stride, int count, u32* __restrict__ tab,
+                                          const modp_rt_consts* __restrict__ cs) {
+  constexpr int L = Width<LPL>::L, SLOT = Width<LPL>::SLOT;
+  __shared__ __attribute__((aligned(16))) u32 lds[RT_NUMS * SLOT];
+  const Lane ln = make_lane();
+  const int xi = blockIdx.x * RT_NUMS + (threadIdx.x >> 2);
+  const bool live = xi < count;
+  const int x = live ? xi : count - 1;
+  u32* slot = lds + (threadIdx.x >> 2) * SLOT;
+  const u32 n0inv = cs->n0inv;
+  u32 n[LPL], b[LPL], acc[LPL];
+  lane_load<LPL>(n, cs->n, ln);
+  to_mont_in<LPL>(b, slot, base_be + (size_t)x * base_stride, cs, n, n0inv, ln);
+  u32* my = tab + (size_t)x * 16 * L;
+  lane_load<LPL>(acc, cs->one_m, ln);
+  if (live) lane_store<LPL>(my, acc, ln);
+  if (live) lane_store<LPL>(my + L, b, ln);
+  slot_store<LPL>(slot, b, ln);
+  __builtin_amdgcn_wave_barrier();
+#pragma unroll
+  for (int k = 0; k < LPL; ++k) acc[k] = b[k];
+  for (int e = 2; e < 16; ++e) {
+    mont_mul<LPL>(acc, acc, slot, n, n0inv, ln);
+    if (live) lane_store<LPL>(my + (size_t)e * L, acc, ln);
+  }
+}
+
+// ---------------------------------------------------------------------------------------
+// out[x] = B1^e1 * B2^e2 mod q (B2 absent when tab2 is null), fixed 4-bit windows from the wave's highest one,
+// squarings shared.  One Montgomery-product site: every step only chooses its LDS operand (own copy = square, a table
+// entry, plain 1 at the end).
+// ---------------------------------------------------------------------------------------
+template <int LPL>
+__global__ void RT_KERNEL(LPL) k_rt_dual_exp(const u32* __restrict__ tab1, size_t tab1_stride, const u32* __restrict__ tab2,
+                                             size_t tab2_stride, const uint8_t* __restrict__ e1_be, size_t e1_stride,
+                                             const uint8_t* __restrict__ e2_be, size_t e2_stride, int count,
+                                             uint8_t* __restrict__ out_be, const modp_rt_consts* __restrict__ cs) {
+  constexpr int L = Width<LPL>::L, SLOT = Width<LPL>::SLOT;
+  __shared__ __attribute__((aligned(16))) u32 lds[RT_NUMS * SLOT];
+  const Lane ln = make_lane();
+  const int xi = blockIdx.x * RT_NUMS + (threadIdx.x >> 2);
+  const bool live = xi < count;
+  const int x = live ? xi : count - 1;
+  u32* slot = lds + (threadIdx.x >> 2) * SLOT;
+  const u32 n0inv = cs->n0inv;
+  const bool has2 = tab2 != nullptr;
+  const u32* t1 = tab1 + (size_t)x * tab1_stride;
+  const u32* t2 = has2 ? tab2 + (size_t)x * tab2_stride : t1;
+  const uint8_t* e1 = e1_be + (size_t)x * e1_stride;
+  const uint8_t* e2 = has2 ? e2_be + (size_t)x * e2_stride : e1;
+  u32 n[LPL], acc[LPL];
+  lane_load<LPL>(n, cs->n, ln);
+  int nb = wave_max_bits(e1, ln);
+  if (has2) {
+    const int nb2 = wave_max_bits(e2, ln);
+    nb = nb2 > nb ? nb2 : nb;
+  }
+  const int nw = (nb + 3) >> 2;
+  // steps: 0..3 square, 4 times tab1[d1], 5 times tab2[d2], 6 next window, 7 final (times plain 1)
+  int w = nw - 1, s;
+  if (nw == 0) {
+    lane_load<LPL>(acc, cs->one_m, ln);
+    s = 7;
+  } else {
+    lane_load<LPL>(acc, t1 + (size_t)nibble(e1, w) * L, ln);
+    s = has2 ? 5 : 6;
+  }
+  while (true) {
+    if (s == 6) {
+      if (w == 0) {
+        s = 7;
+      } else {
+        --w;
+        s = 0;
+      }
+    }
+    if (s == 7) {
+      slot_fill<LPL>(slot, cs->one, ln);
+    } else if (s < 4) {
+      slot_store<LPL>(slot, acc, ln);
+    } else {
+      const u32 d = nibble(s == 4 ? e1 : e2, w);
+      slot_fill<LPL>(slot, (s == 4 ? t1 : t2) + (size_t)d * L, ln);
+    }
+    __builtin_amdgcn_wave_barrier();
+    if (s < 4) mont_mul<LPL, true>(acc, acc, slot, n, n0inv, ln);
+    else mont_mul<LPL>(acc, acc, slot, n, n0inv, ln);
+    __builtin_amdgcn_wave_barrier();
+    if (s == 7) break;
+    ++s;
+    if (s == 5 && !has2) s = 6;
+  }
+  store_canonical<LPL>(out_be + (size_t)x * 256, acc, slot, cs, ln, live);
+}
+
+// ---------------------------------------------------------------------------------------
+// out[x] = a[x] b[x] mod q from a R and b R (k_rt_to_mont): a b R, times plain 1
+// ---------------------------------------------------------------------------------------
+template <int LPL>
+__global__ void RT_KERNEL(LPL) k_rt_mul(const u32* __restrict__ a_m, const u32* __restrict__ b_m, int count,
+                                        uint8_t* __restrict__ out_be, const modp_rt_consts* __restrict__ cs) {
+  constexpr int L = Width<LPL>::L, SLOT = Width<LPL>::SLOT;
+  __shared__ __attribute__((aligned(16))) u32 lds[RT_NUMS * SLOT];
+  const Lane ln = make_lane();
+  const int xi = blockIdx.x * RT_NUMS + (threadIdx.x >> 2);
+  const bool live = xi < count;
+  const int x = live ? xi : count - 1;
+  u32* slot = lds + (threadIdx.x >> 2) * SLOT;
+  const u32 n0inv = cs->n0inv;
+  u32 n[LPL], acc[LPL];
+  lane_load<LPL>(n, cs->n, ln);
+  lane_load<LPL>(acc, a_m + (size_t)x * L, ln);
+#pragma nounroll
+  for (int step = 0; step < 2; ++step) {
+    slot_fill<LPL>(slot, step == 0 ? b_m + (size_t)x * L : cs->one, ln);
+    __builtin_amdgcn_wave_barrier();
+    mont_mul<LPL>(acc, acc, slot, n, n0inv, ln);
+    __builtin_amdgcn_wave_barrier();
+  }
+  store_canonical<LPL>(out_be + (size_t)x * 256, acc, slot, cs, ln, live);
+}
+
+// ---------------------------------------------------------------------------------------
+// X_i by Horner's rule in the exponent, X = (..((C_{t-1})^i' C_{t-2})^i' ..)^i' C_0 with i' = i mod (q-1).
+// For a safe prime q this is the reference's prod_j C_j^(i^j mod (q-1)) for every input: for a unit C_j the
+// exponents agree mod q-1 (Fermat); a C_j = 0 mod q gives 0 on both sides when i' > 0 (every i'^j >= 1) and when
+// i' = 0 the reference's exponents i^j mod (q-1) of j >= 1 are 0 too, so both sides are C_0.
+//   cm : [t][L] commitments in Montgomery form;  squarings run over the wave's largest i'.
+// LDS per wave: operand slot + saved-base slot per number, one slot with R mod N.
+// ---------------------------------------------------------------------------------------
+template <int LPL>
+__global__ void RT_KERNEL_LDS2(LPL) k_rt_commit_eval(const u32* __restrict__ cm, int t, const int64_t* __restrict__ positions, int count,
+                                                uint8_t* __restrict__ x_be, const modp_rt_consts* __restrict__ cs) {
+  constexpr int L = Width<LPL>::L, SLOT = Width<LPL>::SLOT;
+  __shared__ __attribute__((aligned(16))) u32 lds[(2 * RT_NUMS + 1) * SLOT];
+  const Lane ln = make_lane();
+  const int xi = blockIdx.x * RT_NUMS + (threadIdx.x >> 2);
+  const bool live = xi < count;
+  const int x = live ? xi : count - 1;
+  u32* slot = lds + (threadIdx.x >> 2) * SLOT;
+  u32* bslot = lds + (RT_NUMS + (threadIdx.x >> 2)) * SLOT;
+  u32* oneslot = lds + 2 * RT_NUMS * SLOT;
+  const u32 n0inv = cs->n0inv;
+  u32 n[LPL], acc[LPL];
+  lane_load<LPL>(n, cs->n, ln);
+  if (threadIdx.x < 4) slot_fill<LPL>(oneslot, cs->one_m, ln);
+  const u64 qm1 = ((u64)cs->qm1_hi << 32) | cs->qm1_lo;
+  u64 pos = (u64)positions[x];
+  if (qm1 != 0) pos %= qm1;
+  int nb = (pos == 0) ? 0 : 64 - __builtin_clzll(pos);
+#pragma unroll
+  for (int off = 32; off >= 4; off >>= 1) {
+    const int other = __shfl_xor(nb, off);
+    nb = other > nb ? other : nb;
+  }
+  nb = __builtin_amdgcn_readfirstlane(nb);
+  __builtin_amdgcn_wave_barrier();
+
+  lane_load<LPL>(acc, cm + (size_t)(t - 1) * L, ln);
+  //   for j = t-2 .. 0:   base = acc; acc = topbit ? base : one
+  //                       for bit = nb-2 .. 0: SQUARE; CONDMUL (by base or one, skipped if no lane needs it)
+  //                       CMUL (by C_j)
+  //   FINAL (by plain 1)
+  enum { K_SQUARE, K_CONDMUL, K_CMUL, K_FINAL };
+  int j = t - 2, bit = 0, kind = K_FINAL;
+  auto begin_coefficient = [&]() {
+    if (nb == 0) {   // every i' of the wave is 0: acc^0 = 1
+      lane_load<LPL>(acc, cs->one_m, ln);
+      kind = K_CMUL;
+      return;
+    }
+    slot_store<LPL>(bslot, acc, ln);
+    if (!((pos >> (nb - 1)) & 1)) lane_load<LPL>(acc, cs->one_m, ln);
+    bit = nb - 2;
+    kind = (bit >= 0) ? K_SQUARE : K_CMUL;
+  };
+  if (j >= 0) begin_coefficient();
+  while (true) {
+    const u32* bptr = slot;
+    bool skip = false;
+    if (kind == K_SQUARE) {
+      slot_store<LPL>(slot, acc, ln);
+    } else if (kind == K_CONDMUL) {
+      const bool mine = (pos >> bit) & 1;
+      skip = __builtin_amdgcn_ballot_w64(mine) == 0;
+      bptr = mine ? bslot : oneslot;
+    } else if (kind == K_CMUL) {
+      slot_fill<LPL>(slot, cm + (size_t)j * L, ln);
+    } else {
+      slot_fill<LPL>(slot, cs->one, ln);
+    }
+    if (!skip) {
+      __builtin_amdgcn_wave_barrier();
+      if (kind == K_SQUARE) mont_mul<LPL, true>(acc, acc, slot, n, n0inv, ln);
+      else mont_mul<LPL>(acc, acc, bptr, n, n0inv, ln);
+      __builtin_amdgcn_wave_barrier();
+    }
+    if (kind == K_FINAL) break;
+    if (kind == K_SQUARE) {
+      kind = K_CONDMUL;
+    } else if (kind == K_CONDMUL) {
+      --bit;
+      kind = (bit >= 0) ? K_SQUARE : K_CMUL;
+    } else {
+      --j;
+      if (j >= 0) begin_coefficient(); else kind = K_FINAL;
+    }
+  }
+  store_canonical<LPL>(x_be + (size_t)x * 256, acc, slot, cs, ln, live);
+}
+
+// ---------------------------------------------------------------------------------------
+// launchers
+// ---------------------------------------------------------------------------------------
+static inline int rt_grid(int count) { return (count + RT_NUMS - 1) / RT_NUMS; }
+
+#define RT_DISPATCH(lpl, KERNEL, ...)                                                          \
+  do {                                                                                         \
+    if ((lpl) == 5) hipLaunchKernelGGL(KERNEL<5>, __VA_ARGS__);                                \
+    else if ((lpl) == 9) hipLaunchKernelGGL(KERNEL<9>, __VA_ARGS__);                           \
+    else if ((lpl) == 18) hipLaunchKernelGGL(KERNEL<18>, __VA_ARGS__);                         \
+    else return (int)hipErrorInvalidValue;                                                     \
+  } while (0)
+
+extern "C" int modp_rt_in_rows(int lpl) {
+  return lpl == 5 ? Width<5>::IN_ROWS : lpl == 9 ? Width<9>::IN_ROWS : lpl == 18 ? Width<18>::IN_ROWS : -1;
+}
+
+extern "C" int modp_rt_launch_to_mont(int lpl, const uint8_t* in_be, int count, uint32_t* out_m, const modp_rt_consts* cs, hipStream_t s) {
+  if (count <= 0) return 0;
+  RT_DISPATCH(lpl, k_rt_to_mont, dim3(rt_grid(count)), dim3(64), 0, s, in_be, count, out_m, cs);
+  return (int)hipGetLastError();
+}
+
+extern "C" int modp_rt_launch_table(int lpl, const uint8_t* base_be, size_t base_stride, int count, uint32_t* tab,
+                                    const modp_rt_consts* cs, hipStream_t s) {
+  if (count <= 0) return 0;
+  RT_DISPATCH(lpl, k_rt_table, dim3(rt_grid(count)), dim3(64), 0, s, base_be, base_stride, count, tab, cs);
+  return (int)hipGetLastError();
+}
+
+extern "C" int modp_rt_launch_dual_exp(int lpl, const uint32_t* tab1, size_t tab1_stride, const uint32_t* tab2, size_t tab2_stride,
+                                       const uint8_t* e1, size_t e1_stride, const uint8_t* e2, size_t e2_stride, int count, uint8_t* out,
+                                       const modp_rt_consts* cs, hipStream_t s) {
+  if (count <= 0) return 0;
+  RT_DISPATCH(lpl, k_rt_dual_exp, dim3(rt_grid(count)), dim3(64), 0, s, tab1, tab1_stride, tab2, tab2_stride, e1, e1_stride, e2,
+              e2_stride, count, out, cs);
+  return (int)hipGetLastError();
+}
+
+extern "C" int modp_rt_launch_mul(int lpl, const uint32_t* a, const uint32_t* b, int count, uint8_t* out, const modp_rt_consts* cs,
+                                  hipStream_t s) {
+  if (count <= 0) return 0;
+  RT_DISPATCH(lpl, k_rt_mul, dim3(rt_grid(count)), dim3(64), 0, s, a, b, count, out, cs);
+  return (int)hipGetLastError();
+}
+
+extern "C" int modp_rt_launch_commit_eval(int lpl, const uint32_t* cm_m, int t, const int64_t* positions, int count, uint8_t* x_be,
+                                          const modp_rt_consts* cs, hipStream_t s) {
+  if (count <= 0) return 0;
+  RT_DISPATCH(lpl, k_rt_commit_eval, dim3(rt_grid(count)), dim3(64), 0, s, cm_m, t, positions, count, x_be, cs);
+  return (int)hipGetLastError();
+}

@@ -23,6 +23,7 @@
 #include "host_modq.h"
 #include "host_scalar.h"
 #include "modp_kernels.h"
+#include "modp_rt_kernels.h"
 #include "sha256.h"
 #include "verdict_kernels.h"
 
@@ -315,6 +316,12 @@ struct mpvss_ctx {
     unsigned long long blocks = 0;
   } pstats;
   EcWork ecwork;
+  // workspace of the run-time MODP group entry points (capi_modp_rt.inc), used under `mu`
+  DevBuf rt_consts, rt_in[6], rt_out[3], rt_tab1, rt_tab2, rt_tabg, rt_cm, rt_small[2];
+  std::vector<DevBuf*> rt_all() {
+    return {&rt_consts, &rt_in[0], &rt_in[1], &rt_in[2], &rt_in[3], &rt_in[4], &rt_in[5], &rt_out[0], &rt_out[1], &rt_out[2],
+            &rt_tab1, &rt_tab2, &rt_tabg, &rt_cm, &rt_small[0], &rt_small[1]};
+  }
 };
 
 namespace {
@@ -781,6 +788,8 @@ extern "C" void mpvss_ctx_destroy(mpvss_ctx* ctx) {
   for (DevBuf* b : {&ctx->comb[0], &ctx->comb[1], &ctx->comb16[0], &ctx->comb16[1], &ctx->qbounds})
     if (b->p) (void)hipFree(b->p);
   for (DevBuf* b : ctx->ecwork.all())
+    if (b->p) (void)hipFree(b->p);
+  for (DevBuf* b : ctx->rt_all())
     if (b->p) (void)hipFree(b->p);
   for (auto& sl : ctx->slot)
     for (DevBuf* b : sl.ecw.all())
@@ -3703,3 +3712,5 @@ extern "C" int mpvss_modp_extract_shares_absorb(mpvss_ctx* ctx, uint8_t* s_out_h
 #include "capi_scalar.inc"
 // flat wire format of a box
 #include "capi_wire.inc"
+
+#include "capi_modp_rt.inc"

@@ -63,12 +63,22 @@ pub fn flatten(group: &HipModpGroup, bx: &DistributionSharesBox<HipModpGroup>) -
 pub fn verify_distribution_shares(group: &HipModpGroup, bx: &DistributionSharesBox<HipModpGroup>) -> bool {
     let Some(f) = flatten(group, bx) else { return false };
     let mut verdict = 0i32;
-    let rc = unsafe {
-        ffi::mpvss_modp_verify_distribution(
-            group.engine.raw(), ffi::MPVSS_HOST, f.commitments.as_ptr(), bx.commitments.len(), f.positions.as_ptr(),
-            f.pubkeys.as_ptr(), f.shares.as_ptr(), f.responses.as_ptr(), f.positions.len(), f.challenge.as_ptr(),
-            &mut verdict, std::ptr::null_mut(), std::ptr::null_mut(), std::ptr::null_mut(), std::ptr::null_mut(),
-        )
+    let rc = match group.rt_handle() {
+        // a run-time group (HipModpGroup::init / with_modulus): the same contract on modp_rt_kernels.hip
+        Some(h) => unsafe {
+            ffi::mpvss_modp_group_verify_distribution(
+                group.engine.raw(), h, ffi::MPVSS_HOST, f.commitments.as_ptr(), bx.commitments.len(), f.positions.as_ptr(),
+                f.pubkeys.as_ptr(), f.shares.as_ptr(), f.responses.as_ptr(), f.positions.len(), f.challenge.as_ptr(),
+                &mut verdict, std::ptr::null_mut(), std::ptr::null_mut(), std::ptr::null_mut(), std::ptr::null_mut(),
+            )
+        },
+        None => unsafe {
+            ffi::mpvss_modp_verify_distribution(
+                group.engine.raw(), ffi::MPVSS_HOST, f.commitments.as_ptr(), bx.commitments.len(), f.positions.as_ptr(),
+                f.pubkeys.as_ptr(), f.shares.as_ptr(), f.responses.as_ptr(), f.positions.len(), f.challenge.as_ptr(),
+                &mut verdict, std::ptr::null_mut(), std::ptr::null_mut(), std::ptr::null_mut(), std::ptr::null_mut(),
+            )
+        },
     };
     group.engine.expect(rc, "verify_distribution_shares");     // the reference panics on a negative position too
     verdict == 1
@@ -78,6 +88,7 @@ pub fn verify_distribution_shares(group: &HipModpGroup, bx: &DistributionSharesB
 /// transcript hashers).  Boxes with a missing map entry get `false` without touching the GPU.
 pub fn verify_many(group: &HipModpGroup, boxes: &[&DistributionSharesBox<HipModpGroup>], depth: i32, hash_threads: i32)
     -> Result<Vec<bool>, EngineError> {
+    assert!(group.rt.is_none(), "batch::verify_many: RFC 3526 group 14 only (a run-time group offers verify_distribution_shares and verify_shares)");
     let flats: Vec<Option<FlatBox>> = boxes.iter().map(|b| flatten(group, b)).collect();
     let mut descs = Vec::new();
     let mut index = Vec::new();
@@ -129,9 +140,15 @@ pub fn verify_shares(group: &HipModpGroup, share_boxes: &[ShareBox<HipModpGroup>
         }
     }
     let mut verdicts = vec![0u8; live.len()];
-    let rc = unsafe {
-        ffi::mpvss_modp_verify_shares(group.engine.raw(), ffi::MPVSS_HOST, pk.as_ptr(), s.as_ptr(), y.as_ptr(), c.as_ptr(), r.as_ptr(),
-                                      live.len(), verdicts.as_mut_ptr())
+    let rc = match group.rt_handle() {
+        Some(h) => unsafe {
+            ffi::mpvss_modp_group_verify_shares(group.engine.raw(), h, ffi::MPVSS_HOST, pk.as_ptr(), s.as_ptr(), y.as_ptr(), c.as_ptr(),
+                                                r.as_ptr(), live.len(), verdicts.as_mut_ptr())
+        },
+        None => unsafe {
+            ffi::mpvss_modp_verify_shares(group.engine.raw(), ffi::MPVSS_HOST, pk.as_ptr(), s.as_ptr(), y.as_ptr(), c.as_ptr(), r.as_ptr(),
+                                          live.len(), verdicts.as_mut_ptr())
+        },
     };
     group.engine.expect(rc, "verify_shares");
     let mut out = vec![false; share_boxes.len()];
@@ -143,6 +160,7 @@ pub fn verify_shares(group: &HipModpGroup, share_boxes: &[ShareBox<HipModpGroup>
 
 /// Drop-in body of `Participant<ModpGroup>::distribute_secret` (participant.rs:160-286).
 pub fn distribute_secret(group: &HipModpGroup, secret: &BigInt, publickeys: &[BigInt], threshold: u32) -> DistributionSharesBox<HipModpGroup> {
+    assert!(group.rt.is_none(), "batch::distribute_secret: RFC 3526 group 14 only (a run-time group offers verify_distribution_shares and verify_shares)");
     assert!(threshold as usize <= publickeys.len());                                   // participant.rs:166
     let n = publickeys.len();
     let t = threshold as usize;
@@ -200,6 +218,7 @@ pub fn distribute_secret(group: &HipModpGroup, secret: &BigInt, publickeys: &[Bi
 /// n participants decrypt and prove at once (participant.rs:294-353): `witnesses[i]` is the `w` argument of the i-th call.
 pub fn extract_secret_shares(group: &HipModpGroup, bx: &DistributionSharesBox<HipModpGroup>, private_keys: &[BigInt], witnesses: &[BigInt])
     -> Vec<Option<ShareBox<HipModpGroup>>> {
+    assert!(group.rt.is_none(), "batch::extract_secret_shares: RFC 3526 group 14 only (a run-time group offers verify_distribution_shares and verify_shares)");
     assert_eq!(private_keys.len(), witnesses.len());
     let mut idx = Vec::new();
     let (mut pk, mut y, mut xinv, mut w) = (Vec::new(), Vec::new(), Vec::new(), Vec::new());
@@ -232,6 +251,7 @@ pub fn extract_secret_shares(group: &HipModpGroup, bx: &DistributionSharesBox<Hi
 
 /// Drop-in body of `Participant<ModpGroup>::reconstruct` (participant.rs:462-519).
 pub fn reconstruct(group: &HipModpGroup, share_boxes: &[ShareBox<HipModpGroup>], bx: &DistributionSharesBox<HipModpGroup>) -> Option<BigInt> {
+    assert!(group.rt.is_none(), "batch::reconstruct: RFC 3526 group 14 only (a run-time group offers verify_distribution_shares and verify_shares)");
     if share_boxes.len() < bx.commitments.len() {
         return None;
     }

@@ -25,6 +25,11 @@ pub struct mpvss_ctx {
 pub struct mpvss_keyset {
     _private: [u8; 0],
 }
+/// a run-time MODP group (mpvss_modp_group_create): immutable, usable from every context and thread
+#[repr(C)]
+pub struct mpvss_modp_group {
+    _private: [u8; 0],
+}
 #[repr(C)]
 pub struct mpvss_modp_box {
     pub commitments: *const u8,
@@ -227,6 +232,28 @@ unsafe extern "C" {
                                out_cap: usize, out_len: *mut usize) -> c_int;
     pub fn mpvss_box_parse(buf: *const u8, len: usize, view: *mut mpvss_box_view) -> c_int;
     pub fn mpvss_box_verify_wire(ctx: *mut mpvss_ctx, buf: *const u8, len: usize, verdict: *mut c_int, digest32_out: *mut u8) -> c_int;
+    // ---- MODP groups of a run-time modulus (ModpGroup::init)
+    pub fn mpvss_modp_group_create(q_be: *const u8, q_len: usize, out: *mut *mut mpvss_modp_group) -> c_int;
+    pub fn mpvss_modp_group_destroy(grp: *mut mpvss_modp_group);
+    pub fn mpvss_modp_group_bits(grp: *const mpvss_modp_group) -> c_int;
+    pub fn mpvss_modp_group_limbs_per_lane(grp: *const mpvss_modp_group) -> c_int;
+    pub fn mpvss_modp_group_hash_to_scalar(grp: *const mpvss_modp_group, data: *const u8, len: usize, out256: *mut u8) -> c_int;
+    pub fn mpvss_modp_group_batch_exp(ctx: *mut mpvss_ctx, grp: *const mpvss_modp_group, space: c_int, bases: *const u8, exps: *const u8,
+                                      n: usize, out: *mut u8) -> c_int;
+    pub fn mpvss_modp_group_batch_mul(ctx: *mut mpvss_ctx, grp: *const mpvss_modp_group, space: c_int, a: *const u8, b: *const u8, n: usize,
+                                      out: *mut u8) -> c_int;
+    pub fn mpvss_modp_group_commit_eval(ctx: *mut mpvss_ctx, grp: *const mpvss_modp_group, space: c_int, commitments: *const u8, t: usize,
+                                        positions: *const i64, n: usize, x_out: *mut u8) -> c_int;
+    pub fn mpvss_modp_group_dleq_commitments(ctx: *mut mpvss_ctx, grp: *const mpvss_modp_group, space: c_int, g1_host: *const u8,
+                                             h1: *const u8, g2: *const u8, h2: *const u8, r: *const u8, c: *const u8, c_per_share: c_int,
+                                             n: usize, a1_out: *mut u8, a2_out: *mut u8) -> c_int;
+    pub fn mpvss_modp_group_verify_distribution(ctx: *mut mpvss_ctx, grp: *const mpvss_modp_group, space: c_int, commitments: *const u8,
+                                                t: usize, positions: *const i64, pubkeys: *const u8, shares: *const u8,
+                                                responses: *const u8, n: usize, challenge_host: *const u8, verdict: *mut c_int,
+                                                digest32_out: *mut u8, x_out_host: *mut u8, a1_out_host: *mut u8,
+                                                a2_out_host: *mut u8) -> c_int;
+    pub fn mpvss_modp_group_verify_shares(ctx: *mut mpvss_ctx, grp: *const mpvss_modp_group, space: c_int, pk: *const u8, s: *const u8,
+                                          y: *const u8, c: *const u8, r: *const u8, n: usize, verdicts_host: *mut u8) -> c_int;
     // ---- hashing helpers
     pub fn mpvss_sha256(data: *const u8, len: usize, out32: *mut u8);
     pub fn mpvss_modp_hash_to_scalar(data: *const u8, len: usize, out256: *mut u8);

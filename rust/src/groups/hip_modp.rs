@@ -10,10 +10,24 @@ use super::be256;
 use crate::engine::Engine;
 use crate::ffi;
 
+/// Owner of a run-time group handle (mpvss_modp_group_create): the modulus of `ModpGroup::init(length)` or any other odd q
+/// of at most 2048 bits.  The handle is immutable, so sharing it between threads is sound.
+#[derive(Debug)]
+pub(crate) struct RtGroup(pub(crate) *mut ffi::mpvss_modp_group);
+unsafe impl Send for RtGroup {}
+unsafe impl Sync for RtGroup {}
+impl Drop for RtGroup {
+    fn drop(&mut self) {
+        unsafe { ffi::mpvss_modp_group_destroy(self.0) }
+    }
+}
+
 #[derive(Debug, Clone)]
 pub struct HipModpGroup {
     pub(crate) engine: Engine,
-    q: BigInt,         // RFC 3526 group 14 (modp.rs:47-58)
+    /// None: RFC 3526 group 14 (the group-14 kernels); Some: a run-time group (modp_rt_kernels.hip)
+    pub(crate) rt: Option<Arc<RtGroup>>,
+    q: BigInt,         // RFC 3526 group 14 (modp.rs:47-58), or the run-time modulus
     g: BigInt,         // (q - 1) / 2
     order: BigInt,     // q - 1
     gen_main: BigInt,  // 2
@@ -33,6 +47,40 @@ impl HipModpGroup {
         Self::with_engine(Engine::new(device_id).expect("MI355X engine"))
     }
 
+    /// `ModpGroup::init(length)` (modp.rs:72-84): the reference generates the safe prime (num_primes, its own choice of
+    /// prime), the engine runs the group's exp / mul and the batched protocol calls of crate::batch on the GPU.  Moduli above
+    /// 2048 bits have no GPU path and there is no CPU fallback: `init(length > 2048)` panics.
+    pub fn init(length: u32) -> Arc<Self> {
+        assert!(length <= 2048, "HipModpGroup::init({length}): the MI355X engine covers MODP groups of at most 2048 bits and has no CPU fallback");
+        let reference = mpvss_rs::groups::ModpGroup::init(length);
+        Self::with_modulus(reference.modulus())
+    }
+
+    /// A MODP group of any odd modulus q of at most 2048 bits (protocol parity is specified for safe primes); generators 2 and 4
+    /// as in modp.rs:80-82.  Panics for an even q, q < 5 or q >= 2^2048.
+    pub fn with_modulus(q: &BigInt) -> Arc<Self> {
+        let (_, bytes) = q.to_bytes_be();
+        let mut raw: *mut ffi::mpvss_modp_group = std::ptr::null_mut();
+        let rc = unsafe { ffi::mpvss_modp_group_create(bytes.as_ptr(), bytes.len(), &mut raw) };
+        assert!(rc == 0 && !raw.is_null(), "HipModpGroup::with_modulus: not an odd modulus of 5 .. 2048 bits (rc {rc})");
+        let order = q - BigInt::one();
+        let g = &order / BigInt::from(2);
+        Arc::new(HipModpGroup {
+            engine: Engine::shared(),
+            rt: Some(Arc::new(RtGroup(raw))),
+            q: q.clone(),
+            g,
+            order,
+            gen_main: BigInt::from(2),
+            gen_sub: BigInt::from(4).mod_floor(q),
+        })
+    }
+
+    /// the run-time group handle, None for group 14
+    pub(crate) fn rt_handle(&self) -> Option<*const ffi::mpvss_modp_group> {
+        self.rt.as_ref().map(|r| r.0 as *const ffi::mpvss_modp_group)
+    }
+
     fn with_engine(engine: Engine) -> Arc<Self> {
         let q = BigInt::parse_bytes(
             b"ffffffffffffffffc90fdaa22168c234c4c6628b80dc1cd129024e088a67cc74020bbea63b139b22514a08798e3404dd\
@@ -46,7 +94,7 @@ impl HipModpGroup {
         .unwrap();
         let order = &q - BigInt::one();
         let g = &order / BigInt::from(2);
-        Arc::new(HipModpGroup { engine, q, g, order, gen_main: BigInt::from(2), gen_sub: BigInt::from(4) })
+        Arc::new(HipModpGroup { engine, rt: None, q, g, order, gen_main: BigInt::from(2), gen_sub: BigInt::from(4) })
     }
 
     fn from_be256(b: &[u8; 256]) -> BigInt {
@@ -98,7 +146,10 @@ impl Group for HipModpGroup {
     fn exp(&self, base: &BigInt, scalar: &BigInt) -> BigInt {
         let (b, e) = (be256(base), be256(scalar));
         let mut out = [0u8; 256];
-        let rc = unsafe { ffi::mpvss_modp_batch_exp(self.engine.raw(), ffi::MPVSS_HOST, b.as_ptr(), e.as_ptr(), 1, out.as_mut_ptr()) };
+        let rc = match self.rt_handle() {
+            Some(h) => unsafe { ffi::mpvss_modp_group_batch_exp(self.engine.raw(), h, ffi::MPVSS_HOST, b.as_ptr(), e.as_ptr(), 1, out.as_mut_ptr()) },
+            None => unsafe { ffi::mpvss_modp_batch_exp(self.engine.raw(), ffi::MPVSS_HOST, b.as_ptr(), e.as_ptr(), 1, out.as_mut_ptr()) },
+        };
         self.engine.expect(rc, "HipModpGroup::exp");
         Self::from_be256(&out)
     }
@@ -107,7 +158,10 @@ impl Group for HipModpGroup {
     fn mul(&self, a: &BigInt, b: &BigInt) -> BigInt {
         let (x, y) = (be256(a), be256(b));
         let mut out = [0u8; 256];
-        let rc = unsafe { ffi::mpvss_modp_batch_mul(self.engine.raw(), ffi::MPVSS_HOST, x.as_ptr(), y.as_ptr(), 1, out.as_mut_ptr()) };
+        let rc = match self.rt_handle() {
+            Some(h) => unsafe { ffi::mpvss_modp_group_batch_mul(self.engine.raw(), h, ffi::MPVSS_HOST, x.as_ptr(), y.as_ptr(), 1, out.as_mut_ptr()) },
+            None => unsafe { ffi::mpvss_modp_batch_mul(self.engine.raw(), ffi::MPVSS_HOST, x.as_ptr(), y.as_ptr(), 1, out.as_mut_ptr()) },
+        };
         self.engine.expect(rc, "HipModpGroup::mul");
         Self::from_be256(&out)
     }
@@ -139,6 +193,9 @@ impl Group for HipModpGroup {
 
     /// modp.rs:176-178: G^k through the fixed-base comb
     fn generate_public_key(&self, private_key: &BigInt) -> BigInt {
+        if self.rt.is_some() {
+            return self.exp(&self.gen_main, private_key);
+        }
         let (g, e) = (be256(&self.gen_main), be256(private_key));
         let mut out = [0u8; 256];
         let rc = unsafe { ffi::mpvss_modp_batch_exp_fixed_base(self.engine.raw(), ffi::MPVSS_HOST, g.as_ptr(), e.as_ptr(), 1, out.as_mut_ptr()) };
@@ -148,6 +205,9 @@ impl Group for HipModpGroup {
 
     /// modp.rs:180-182
     fn scalar_mul(&self, a: &BigInt, b: &BigInt) -> BigInt {
+        if self.rt.is_some() {
+            return (a * b) % &self.order;
+        }
         let (x, y) = (be256(a), be256(b));
         let mut out = [0u8; 256];
         unsafe { ffi::mpvss_modp_scalar_mul(x.as_ptr(), y.as_ptr(), out.as_mut_ptr()) };
@@ -156,6 +216,10 @@ impl Group for HipModpGroup {
 
     /// modp.rs:184-192
     fn scalar_sub(&self, a: &BigInt, b: &BigInt) -> BigInt {
+        if self.rt.is_some() {
+            let diff = a - b;
+            return if diff < BigInt::zero() { diff + &self.order } else { diff % &self.order };
+        }
         let (x, y) = (be256(a), be256(b));
         let mut out = [0u8; 256];
         unsafe { ffi::mpvss_modp_scalar_sub(x.as_ptr(), y.as_ptr(), out.as_mut_ptr()) };
