@@ -10,8 +10,11 @@ must verify (verdict True) and reproduce the dealer's transcript digest or the r
   python bench.py --gpus 1 --steps K --warmup W
   python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...   (weak scaling:
       the box has N x 65536 participants, rank g holds the contiguous block g)
+  python bench.py --full ...   (also every secondary figure: isolated kernels, steady state, probes,
+      CPU baselines, the other shapes and call forms, the curve groups; several minutes)
 
-Prints ONE JSON line on rank 0.
+Prints ONE JSON line on rank 0.  A plain run measures the headline only: set-up, warm-up, the
+timed steps, --dump-outputs, the line.
 """
 import os as _os
 import sys as _sys
@@ -71,7 +74,6 @@ import collections
 import concurrent.futures
 import ctypes as C
 import json
-import math
 import os
 import random
 import sys
@@ -111,9 +113,9 @@ def fx(v: int) -> bytes:
 
 
 def keygen(rng: random.Random) -> int:
-    while True:                                   # modp.rs:162-174
+    while True:                                   # modp.rs:162-174: k with gcd(k, q-1) == 1
         k = rng.randrange(Q)
-        if math.gcd(k, ORDER) == 1:
+        if k & 1 and k != ORDER // 2:             # q-1 = 2 q' with q' prime (safe prime): the same test as the gcd, 20x faster
             return k
 
 
@@ -668,6 +670,12 @@ def main():
                     "(C2 n=4096 t=64, one GPU's slice of C5 n=131072 t=1024; -1: 48 / 6, 0: skip)")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="write what the last timed step returned (verdict.npy, digest.npy; float32) into DIR")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also measure everything that is not the headline: the lone-box and alone-on-the-chip "
+                         "kernel durations, the steady state, the issue-rate probes, and every secondary leg (verify_share, "
+                         "extract_shares, the dealer, the CPU baselines, the other shapes, strong scaling, host buffers, one_call, "
+                         "drop_in, registered keys, the curve groups).  Without it a run sets up, warms up, times --steps, writes "
+                         "--dump-outputs and prints its line; the options of those legs only act with --full")
     args = ap.parse_args()
     if args.steps < 1:
         ap.error("--steps must be at least 1")
@@ -802,7 +810,9 @@ def main():
     d_pk = dev_u8(pubkeys)
     d_pos = torch.tensor(positions, dtype=torch.int64, device=dev)
     n_distinct = args.distinct_boxes if args.distinct_boxes > 0 else max(1, min(args.steps, 24))
-    boxes = [make_box(0, n, t, positions, pubkeys, wit_bytes, True)]
+    # box 0's scalars from Python integers with --full (the dealer leg checks the C ABI's against them, byte for byte);
+    # a plain run takes the C ABI's, the same bytes in a fraction of the time
+    boxes = [make_box(0, n, t, positions, pubkeys, wit_bytes, args.full)]
     boxes += [make_box(b, n, t, positions, pubkeys, wit_bytes, False) for b in range(1, n_distinct)]
     box0 = boxes[0]
     commitments, shares, responses, challenge, dres = box0.commitments, box0.shares, box0.responses, box0.challenge, box0.dres
@@ -1090,8 +1100,10 @@ def main():
     # Isolated launches: the same box verified alone (one box in flight, nothing else on the GPU) after the timed
     # region -- the duration of a launch that has the chip to itself is what a roofline can be read from; in the timed
     # region up to PIPE_DEPTH boxes share the chip and a launch's wall duration exceeds the step time.
+    # These runs of their own, the steady state and the probes below are --full only: without them `roofline` reads the
+    # overlapped launches of the timed region and `compute` has no probe-weighted figures.
     lone = None
-    if world == 1 and args.lone_boxes > 0:
+    if args.full and world == 1 and args.lone_boxes > 0:
         torch.cuda.synchronize()
         gate(run_steps(args.lone_boxes, depth=1), "lone box")
         lst = eng.pipeline_stats(reset=True)
@@ -1103,7 +1115,7 @@ def main():
     # synchronous entry point (mpvss_modp_dleq_commitments: a1, then the tables of y and Y, then a2 = y^r Y^c -- the same
     # k_modp_dual_exp_w6 launch on the same operands, with nothing beside it; even a lone box runs its X path beside a2)
     alone_ms = None
-    if world == 1 and args.lone_boxes > 0 and keyset[0] is None:
+    if args.full and world == 1 and args.lone_boxes > 0 and keyset[0] is None:
         d_X = dev_u8(dres["X"])
         o1 = torch.empty(n * EB, dtype=torch.uint8, device=dev)
         o2 = torch.empty(n * EB, dtype=torch.uint8, device=dev)
@@ -1118,7 +1130,7 @@ def main():
     # steady state: the same pipeline over many more boxes (the K-step region ends with the boxes in flight finishing together
     # and their hashes running with nothing beside them; over 100 boxes that tail no longer shows)
     steady = None
-    if world == 1 and args.steady_steps > 0:
+    if args.full and world == 1 and args.steady_steps > 0:
         barrier()
         ts0 = time.perf_counter()
         res_ss = run_steps(args.steady_steps)
@@ -1129,7 +1141,7 @@ def main():
         eng.pipeline_stats(reset=True)
     # what this device sustains of the kernels' basic instructions right now (4 waves per SIMD issuing back to back for ~40 ms)
     probe = None
-    if world == 1:
+    if args.full and world == 1:
         p0, p1 = eng.issue_probe(0, 40.0), eng.issue_probe(1, 40.0)
         probe = {"mad64_insts_per_s": p0["insts_per_s"], "mad64_shader_clock_ghz": p0["shader_clock_ghz"],
                  "mad64_cycles_per_inst": 1024 * p0["shader_clock_ghz"] * 1e9 / p0["insts_per_s"] if p0["insts_per_s"] else None,
@@ -1278,11 +1290,10 @@ def main():
         except Exception:
             pass
 
-    # Everything below is secondary to the headline (`value`, `roofline`, `compute` are complete at this point): a failure
-    # there -- an allocation that does not fit, a parity gate of a secondary figure -- must not cost the line; it is
-    # reported in `secondary_error` and the process exits non-zero after printing.
-    secondary_error = None
-    try:
+    # Everything below is secondary to the headline (`value`, `roofline`, `compute` are complete at this point) and runs with
+    # --full only: a failure there -- an allocation that does not fit, a parity gate of a secondary figure -- must not cost
+    # the line; it is reported in `secondary_error` and the process exits non-zero after printing.
+    def secondary_legs():
         # (Order: the Python-driven secondary legs of the MODP group first -- W_B, extract, the dealer --, then the CPU baselines, the
         # other shapes, host buffers, registered keys and the curve groups.  With the CPU legs and the large shapes ahead of them the
         # Python-driven legs read 15-20 % lower in the same process (0.92 against 1.10 M for verify_share; profiles/r04_wb_order.txt):
@@ -1997,11 +2008,15 @@ def main():
         if rank == 0 and world == 1 and args.ec_boxes > 0:
             result["ec"] = {name: bench_ec(eng, name, args) for name in ("secp256k1", "ristretto255")}
 
-    except Exception as exc:      # noqa: BLE001 - reported in the line and through the exit code
-        import traceback
-        secondary_error = "".join(traceback.format_exception_only(type(exc), exc)).strip()
-        result["secondary_error"] = secondary_error
-        traceback.print_exc()
+    secondary_error = None
+    if args.full:
+        try:
+            secondary_legs()
+        except Exception as exc:      # noqa: BLE001 - reported in the line and through the exit code
+            import traceback
+            secondary_error = "".join(traceback.format_exception_only(type(exc), exc)).strip()
+            result["secondary_error"] = secondary_error
+            traceback.print_exc()
     fd_blocks, fd_fallbacks = eng.fd_stats()
     result["compute"]["fd_blocks"] = fd_blocks
     result["compute"]["fd_fallbacks"] = fd_fallbacks          # boxes whose pipeline gave up and were recomputed by Horner

@@ -36,7 +36,7 @@ def _line(out):
     return compact, detail
 
 
-def _run(ranks, steps, n, depth, timeout=900, extra_env=None, config_boxes="0", scaling="weak", threshold="64"):
+def _run(ranks, steps, n, depth, timeout=900, extra_env=None, config_boxes="0", scaling="weak", threshold="64", full=False):
     env = dict(os.environ, MPVSS_BENCH_SMOKE_ONE_GPU="1", MASTER_ADDR="127.0.0.1", **(extra_env or {}))
     if depth is not None:                  # None: the boxes in flight per rank follow bench.py's own formula for that world size
         env["MPVSS_BENCH_DEPTH"] = str(depth)
@@ -46,7 +46,7 @@ def _run(ranks, steps, n, depth, timeout=900, extra_env=None, config_boxes="0", 
            "127.0.0.1", "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"), "--gpus", str(ranks), "--steps",
            str(steps), "--warmup", "1", "--participants", str(n), "--threshold", threshold, "--cpu-sample", "0", "--wb-shares", "0",
            "--registered-keys", "0", "--ec-boxes", "0", "--lone-boxes", "0", "--host-boxes", "0", "--config-boxes", config_boxes,
-           "--scaling", scaling, "--drop-in-threads", "0", "--steady-steps", "0"]
+           "--scaling", scaling, "--drop-in-threads", "0", "--steady-steps", "0"] + (["--full"] if full else [])    # `c5`, `strong`: --full
     return subprocess.run(cmd, capture_output=True, text=True, env=env, timeout=timeout, cwd=ROOT)
 
 
@@ -94,7 +94,7 @@ def test_the_c5_object_of_an_eight_gpu_run_in_small():
     participants per rank, boxes dealt across the ranks (the dealer's transcript chained rank to rank), slots grown in an
     untimed pass, per-box flag gather with re-sized buffers, and the headline figure of the same run untouched."""
     out = _run(2, 3, 8192, 3, extra_env={"MPVSS_BENCH_C5": "1", "MPVSS_BENCH_C5_N": "16384", "MPVSS_BENCH_C5_T": "64"},
-               config_boxes="3")
+               config_boxes="3", full=True)
     assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-4000:]
     _, res = _line(out)
     assert "secondary_error" not in res
@@ -107,7 +107,7 @@ def test_the_c5_object_of_an_eight_gpu_run_in_small():
 def eight_rank_run():
     """ONE eight-rank run for the two tests below: `--scaling both` (the default the driver gets at N > 1), the forced-small `c5` object."""
     out = _run(8, 6, 2048, None, timeout=600, extra_env={"MPVSS_BENCH_C5_N": "4096", "MPVSS_BENCH_C5_T": "64", "OMP_NUM_THREADS": "2"},
-               config_boxes="3", scaling="both")
+               config_boxes="3", scaling="both", full=True)
     assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-4000:]
     return _line(out)
 
@@ -141,7 +141,7 @@ def test_strong_scaling_the_same_box_over_one_and_eight_ranks(eight_rank_run):
     assert st["scaling"] == "strong" and st["n_per_gpu"] == 256 and st["boxes"] == 6 and st["value"] > 0
     assert compact["strong"]["value"] == pytest.approx(st["value"], rel=1e-5)
     assert res["scaling"] == "weak" and res["config"]["n_per_gpu"] == 2048            # `value` is still the weak figure
-    out = _run(1, 6, 2048, 4, timeout=420, scaling="both", extra_env={"MPVSS_BENCH_STRONG_AT_N1": "1"})
+    out = _run(1, 6, 2048, 4, timeout=420, scaling="both", extra_env={"MPVSS_BENCH_STRONG_AT_N1": "1"}, full=True)
     assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-4000:]
     _, one = _line(out)
     assert one["strong"]["n_per_gpu"] == 2048 and one["strong"]["boxes"] == 6

@@ -1,7 +1,7 @@
 #!/bin/bash
 # One A/B line of the headline pipeline per variant (replaces the per-experiment scripts of earlier rounds):
 #   tools/ab_bench.sh OUTFILE [-k STEPS] [-r REPS] [-s STEADY_STEPS] -- NAME1 ENV=VAL ... -- NAME2 ENV=VAL ... 
-# Every variant runs `bench.py --gpus 1 --steps STEPS --warmup 5` with the secondary figures switched off, REPS times, under
+# Every variant runs `bench.py --full --gpus 1 --steps STEPS --warmup 5` with the secondary legs switched off, REPS times, under
 # the given environment, and appends "NAME value ms_per_step a2_alone_ms kernel_ms_sums" to gpurun_out/OUTFILE.
 # Variant libraries (e.g. a kernel built with other -D flags): make -C mpvss_rs_amd/csrc PAIR_EXTRA=... and pass
 # MPVSS_HIP_LIB=/path/to/copy.so as one of the ENV=VAL words.
@@ -30,7 +30,7 @@ for rep in $(seq $REPS); do
   for v in "${!NAMES[@]}"; do
     NAME=${NAMES[$v]}
     # shellcheck disable=SC2086
-    env ${ENVSTR[$v]} MPVSS_BENCH_DETAIL=/tmp/ab_detail.json python3 bench.py --gpus 1 --steps $STEPS --warmup 5 --cpu-sample 0 --wb-shares 0 --registered-keys 0 --ec-boxes 0 \
+    env ${ENVSTR[$v]} MPVSS_BENCH_DETAIL=/tmp/ab_detail.json python3 bench.py --full --gpus 1 --steps $STEPS --warmup 5 --cpu-sample 0 --wb-shares 0 --registered-keys 0 --ec-boxes 0 \
         --host-boxes 0 --config-boxes 0 --lone-boxes 1 --steady-steps $STEADY --drop-in-threads 0 >/dev/null 2>/dev/null
     python3 -c "
 import json
