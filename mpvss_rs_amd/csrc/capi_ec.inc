@@ -633,57 +633,19 @@ int ec_verify_block_compute_locked(mpvss_ctx* ctx, int group, int space, const u
   if (!challenge_host) return fail(ctx, MPVSS_E_INVALID, "ec_verify: null challenge");
   if (n > 0 && (!commitments || !positions || !pubkeys || !shares || !responses || t == 0 || t > 0x7fffffff || n > 0x7fffffff))
     return fail(ctx, MPVSS_E_INVALID, "ec_verify_distribution: bad argument (t must be >= 1)");
-  mpvss_ctx::BlockSlot& sl = ctx->head_slot();
-  if (sl.busy) return fail(ctx, MPVSS_E_INVALID, "ec_verify: every block slot (MPVSS_BLOCK_SLOTS) is in flight, absorb one first");
-  const auto t_enq0 = std::chrono::steady_clock::now();
-  HIPCHK(ctx, hipSetDevice(ctx->device));
-  if (!sl.done) HIPCHK(ctx, hipEventCreateWithFlags(&sl.done, hipEventDisableTiming | hipEventBlockingSync));
-  sl.n = n;
-  sl.kind = 2;
-  sl.dealer = false;
+  BlockEnqueue be(ctx, 2, n, "ec_verify");
+  RET_IF(be.rc);
+  mpvss_ctx::BlockSlot& sl = be.sl;
   sl.group = group;
   sl.t = t;
-  sl.check_positions = false;
-  sl.fd_used = false;
-  sl.fd_chunks = 0;
-  sl.enqueue_ms = 0;
-  if (n == 0) {
-    sl.busy = true;
-    ctx->commit_head(sl);
-    return MPVSS_OK;
-  }
+  if (n == 0) return be.commit_empty();
   if (!scalar_canonical(gi, challenge_host)) return ec_report_bad_scalar(ctx, "challenge", 0);
-  RET_IF(work_init(ctx, sl.work, nullptr));
   const uint32_t* comb;
   RET_IF(ec_comb(ctx, group, &comb));          // before the streams are switched: built once on the context's stream
-  struct Restore {       // also: an early (error) return leaves nothing of this block running on the slot's streams
-    mpvss_ctx* c;
-    hipStream_t a, b;
-    mpvss_ctx::BlockSlot* sl;
-    ~Restore() {
-      if (!sl->busy) {
-        if (sl->work.sa) (void)hipStreamSynchronize(sl->work.sa);
-        if (sl->work.sb) (void)hipStreamSynchronize(sl->work.sb);
-      }
-      c->sp = &c->main_spans; c->w = &c->work0; c->stream = a; c->stream_b = b;
-    }
-  } restore{ctx, ctx->stream, ctx->stream_b, &sl};
-  ctx->w = &sl.work;
-  ctx->stream = sl.work.sa;
-  ctx->stream_b = sl.work.sb;
-  ctx->sp = &sl.spans;
-  spans_reset(ctx);
+  RET_IF(be.enter());
   EcWork& w = sl.ecw;
   const size_t L = gi->enc;
-  const size_t need = ec_staging_out_bytes(n, t, L) + (space == MPVSS_HOST ? 2 * n * L + n * 32 + t * L + n * 8 : 0);
-  if (need > sl.cap) {
-    if (sl.pin) HIPCHK(ctx, hipHostFree(sl.pin));
-    sl.pin = nullptr;
-    sl.cap = 0;
-    hipError_t e = hipHostMalloc(&sl.pin, need, hipHostMallocDefault);
-    if (e != hipSuccess) return fail(ctx, MPVSS_E_NOMEM, "hipHostMalloc(block staging)", e);
-    sl.cap = need;
-  }
+  RET_IF(be.pin(ec_staging_out_bytes(n, t, L) + (space == MPVSS_HOST ? 2 * n * L + n * 32 + t * L + n * 8 : 0)));
   EcStaging st = ec_staging(sl.pin, n, t, L);
   const int64_t* hpos = nullptr;
   if (space == MPVSS_HOST) {       // pinned copies: every transfer is asynchronous, nothing of the caller's is kept
@@ -786,11 +748,7 @@ int ec_verify_block_compute_locked(mpvss_ctx* ctx, int group, int space, const u
   HIPCHK(ctx, hipMemcpyAsync(st.ok, ok, okn, hipMemcpyDeviceToHost, ctx->stream));
   HIPCHK(ctx, hipMemcpyAsync(st.flags + 1, flags + 1, 8, hipMemcpyDeviceToHost, ctx->stream));
   if (gate != nullptr) HIPCHK(ctx, hipMemcpyAsync(st.flags, gate, 4, hipMemcpyDeviceToHost, ctx->stream));
-  HIPCHK(ctx, hipEventRecord(sl.done, ctx->stream));
-  sl.busy = true;
-  sl.enqueue_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_enq0).count();
-  ctx->commit_head(sl);
-  return MPVSS_OK;
+  return be.commit();
 }
 
 int ec_verify_block_absorb_locked(mpvss_ctx* ctx, std::unique_lock<std::mutex>& lk, uint8_t* state, uint8_t* x_out,
@@ -802,31 +760,14 @@ int ec_verify_block_absorb_locked(mpvss_ctx* ctx, std::unique_lock<std::mutex>& 
   mpvss_ctx::BlockSlot& sl = *slp;
   const size_t n = sl.n, t = sl.t;
   const EcInfo* gi = ec_info(sl.group);
-  if (n == 0) {
-    ctx->release(sl);
-    if (sl.gpu_done_ctr) sl.gpu_done_ctr->fetch_add(1);
-    return MPVSS_OK;
-  }
-  sl.absorbing = true;
-  {
-    const hipError_t e_dev = hipSetDevice(ctx->device);
-    if (e_dev != hipSuccess) {               // give the slot back: the block is lost, the ring is not
-      ctx->release(sl);
-      sl.absorbing = false;
-      if (sl.gpu_done_ctr) sl.gpu_done_ctr->fetch_add(1);
-      return fail(ctx, MPVSS_E_DEVICE, "absorb: hipSetDevice", e_dev);
-    }
-  }
-  lk.unlock();
-  const auto t_w0 = std::chrono::steady_clock::now();
-  const hipError_t e = hipEventSynchronize(sl.done);
-  const auto t_w1 = std::chrono::steady_clock::now();
-  if (sl.gpu_done_ctr) sl.gpu_done_ctr->fetch_add(1);
+  const bool dealer = sl.dealer;
   const size_t L = gi->enc;
   const EcStaging st = ec_staging(sl.pin, n, t, L);
   long bad_elem = -1;
   const char* bad_what = "";
-  if (e == hipSuccess) {
+  Absorbed a;
+  RET_IF(absorb_block(ctx, lk, sl, a, [&](bool done) {
+    if (!done) return;
     for (size_t i = 0; i < t + 2 * n && bad_elem < 0; ++i)
       if (!st.ok[i]) {
         bad_elem = i < t ? (long)i : (long)((i - t) % n);
@@ -842,13 +783,9 @@ int ec_verify_block_absorb_locked(mpvss_ctx* ctx, std::unique_lock<std::mutex>& 
       if (a1_out) memcpy(a1_out, st.a1, n * L);
       if (a2_out) memcpy(a2_out, st.a2, n * L);
     }
-  }
-  const auto t_h1 = std::chrono::steady_clock::now();
-  const bool dealer = sl.dealer;
-  lk.lock();
-  ctx->release(sl);
-  sl.absorbing = false;
-  if (e != hipSuccess) return fail(ctx, MPVSS_E_DEVICE, "ec absorb: hipEventSynchronize", e);
+  }));
+  if (!a.waited) return MPVSS_OK;
+  if (a.e != hipSuccess) return fail(ctx, MPVSS_E_DEVICE, "ec absorb: hipEventSynchronize", a.e);
   // the X path's device gate, as the MODP blocks count it (mpvss_fd_stats): 1 = the forward-difference pipelines held, 0 = the
   // gated Horner launch computed every X (a stage gave up, or device-resident positions were not consecutive); -1 = no gate
   if (!dealer && st.flags[0] != -1) {
@@ -859,17 +796,7 @@ int ec_verify_block_absorb_locked(mpvss_ctx* ctx, std::unique_lock<std::mutex>& 
   if (dealer && st.flags[2] != INT_MAX) return ec_report_bad_scalar(ctx, "witnesses", (size_t)st.flags[2]);
   if (bad_elem >= 0) return ec_report_bad_element(ctx, bad_what, (size_t)bad_elem);
   RET_IF(spans_sum(ctx, sl.spans, ctx->kernel_ms));
-  {
-    mpvss_ctx::PipeStats& ps = ctx->pstats;
-    ps.enqueue_ms += sl.enqueue_ms;
-    ps.wait_ms += std::chrono::duration<double, std::milli>(t_w1 - t_w0).count();
-    ps.hash_ms += std::chrono::duration<double, std::milli>(t_h1 - t_w1).count();
-    for (int k = 0; k < 4; ++k) {
-      ps.kernel_ms[k] += ctx->kernel_ms[k];
-      ps.kernel_launches[k] += (unsigned long long)ctx->kernel_launches[k];
-    }
-    ++ps.blocks;
-  }
+  pstats_add(ctx, sl, a, true, 1);
   return MPVSS_OK;
 }
 
@@ -904,57 +831,20 @@ int ec_distribute_compute_locked(mpvss_ctx* ctx, int group, int space, const uin
   if (n > 0 && (!pubkeys || !p_values || !witnesses || n > 0x7fffffff || (commitments && (!positions || t == 0 || t > 0x7fffffff))))
     return fail(ctx, MPVSS_E_INVALID, "ec_distribute: bad argument");
   if (!commitments) t = 0;      // (threshold > n is the whole box's business -- mpvss_ec_distribute checks it; a block may be smaller)
-  mpvss_ctx::BlockSlot& sl = ctx->head_slot();
-  if (sl.busy) return fail(ctx, MPVSS_E_INVALID, "ec_distribute: every block slot (MPVSS_BLOCK_SLOTS) is in flight, absorb one first");
-  const auto t_enq0 = std::chrono::steady_clock::now();
-  HIPCHK(ctx, hipSetDevice(ctx->device));
-  if (!sl.done) HIPCHK(ctx, hipEventCreateWithFlags(&sl.done, hipEventDisableTiming | hipEventBlockingSync));
-  sl.n = n;
-  sl.kind = 2;
+  BlockEnqueue be(ctx, 2, n, "ec_distribute");
+  RET_IF(be.rc);
+  mpvss_ctx::BlockSlot& sl = be.sl;
   sl.dealer = true;
   sl.group = group;
   sl.t = t;
-  sl.check_positions = false;
-  sl.fd_used = false;
-  sl.fd_chunks = 0;
-  sl.enqueue_ms = 0;
-  if (n == 0) {
-    sl.busy = true;
-    ctx->commit_head(sl);
-    return MPVSS_OK;
-  }
-  RET_IF(work_init(ctx, sl.work, nullptr));
+  if (n == 0) return be.commit_empty();
   const uint32_t* comb;
   RET_IF(ec_comb(ctx, group, &comb));
-  struct Restore {       // also: an early (error) return leaves nothing of this block running on the slot's streams
-    mpvss_ctx* c;
-    hipStream_t a, b;
-    mpvss_ctx::BlockSlot* sl;
-    ~Restore() {
-      if (!sl->busy) {
-        if (sl->work.sa) (void)hipStreamSynchronize(sl->work.sa);
-        if (sl->work.sb) (void)hipStreamSynchronize(sl->work.sb);
-      }
-      c->sp = &c->main_spans; c->w = &c->work0; c->stream = a; c->stream_b = b;
-    }
-  } restore{ctx, ctx->stream, ctx->stream_b, &sl};
-  ctx->w = &sl.work;
-  ctx->stream = sl.work.sa;
-  ctx->stream_b = sl.work.sb;
-  ctx->sp = &sl.spans;
-  spans_reset(ctx);
+  RET_IF(be.enter());
   EcWork& w = sl.ecw;
   const size_t L = gi->enc;
-  const size_t need = ec_staging_out_bytes(n, t, L) + (space == MPVSS_HOST ? n * L + 2 * n * 32 + t * L + n * 8 : 0) +
-                      (poly && !poly->coeffs_dev ? poly->t * 32 : 0);
-  if (need > sl.cap) {
-    if (sl.pin) HIPCHK(ctx, hipHostFree(sl.pin));
-    sl.pin = nullptr;
-    sl.cap = 0;
-    hipError_t e = hipHostMalloc(&sl.pin, need, hipHostMallocDefault);
-    if (e != hipSuccess) return fail(ctx, MPVSS_E_NOMEM, "hipHostMalloc(block staging)", e);
-    sl.cap = need;
-  }
+  RET_IF(be.pin(ec_staging_out_bytes(n, t, L) + (space == MPVSS_HOST ? n * L + 2 * n * 32 + t * L + n * 8 : 0) +
+                (poly && !poly->coeffs_dev ? poly->t * 32 : 0)));
   EcStaging st = ec_staging(sl.pin, n, t, L);
   if (poly) {
     // P(i) mod order first, on this block's own stream: the group work below reads it in stream order
@@ -1036,11 +926,7 @@ int ec_distribute_compute_locked(mpvss_ctx* ctx, int group, int space, const uin
     if (a1_dev_out) HIPCHK(ctx, hipMemcpyAsync(a1_dev_out, d1, n * L, hipMemcpyDeviceToDevice, ctx->stream));
     if (a2_dev_out) HIPCHK(ctx, hipMemcpyAsync(a2_dev_out, d2, n * L, hipMemcpyDeviceToDevice, ctx->stream));
   }
-  HIPCHK(ctx, hipEventRecord(sl.done, ctx->stream));
-  sl.busy = true;
-  sl.enqueue_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_enq0).count();
-  ctx->commit_head(sl);
-  return MPVSS_OK;
+  return be.commit();
 }
 }  // namespace
 
@@ -1277,54 +1163,17 @@ int ec_verify_shares_compute_locked(mpvss_ctx* ctx, int group, int space, const 
   const EcInfo* gi = ec_info(group);
   if (!gi) return fail(ctx, MPVSS_E_UNSUPPORTED, "ec_verify_shares: unknown group");
   if (n > 0 && (!pk || !s || !y || !c || !r || n > 0x7fffffff)) return fail(ctx, MPVSS_E_INVALID, "ec_verify_shares: bad argument");
-  mpvss_ctx::BlockSlot& sl = ctx->head_slot();
-  if (sl.busy) return fail(ctx, MPVSS_E_INVALID, "ec_verify_shares: every block slot (MPVSS_BLOCK_SLOTS) is in flight, absorb one first");
-  const auto t_enq0 = std::chrono::steady_clock::now();
-  HIPCHK(ctx, hipSetDevice(ctx->device));
-  if (!sl.done) HIPCHK(ctx, hipEventCreateWithFlags(&sl.done, hipEventDisableTiming | hipEventBlockingSync));
-  sl.n = n;
-  sl.kind = 3;
+  BlockEnqueue be(ctx, 3, n, "ec_verify_shares");
+  RET_IF(be.rc);
+  mpvss_ctx::BlockSlot& sl = be.sl;
   sl.group = group;
-  sl.check_positions = false;
-  sl.fd_used = false;
-  sl.fd_chunks = 0;
-  sl.enqueue_ms = 0;
-  if (n == 0) {
-    sl.busy = true;
-    ctx->commit_head(sl);
-    return MPVSS_OK;
-  }
-  RET_IF(work_init(ctx, sl.work, nullptr));
+  if (n == 0) return be.commit_empty();
   const uint32_t* comb;
   RET_IF(ec_comb(ctx, group, &comb));          // built once, on the context's stream
-  struct Restore {       // also: an early (error) return leaves nothing of this block running on the slot's streams
-    mpvss_ctx* c;
-    hipStream_t a, b;
-    mpvss_ctx::BlockSlot* sl;
-    ~Restore() {
-      if (!sl->busy) {
-        if (sl->work.sa) (void)hipStreamSynchronize(sl->work.sa);
-        if (sl->work.sb) (void)hipStreamSynchronize(sl->work.sb);
-      }
-      c->sp = &c->main_spans; c->w = &c->work0; c->stream = a; c->stream_b = b;
-    }
-  } restore{ctx, ctx->stream, ctx->stream_b, &sl};
-  ctx->w = &sl.work;
-  ctx->stream = sl.work.sa;
-  ctx->stream_b = sl.work.sb;
-  ctx->sp = &sl.spans;
-  spans_reset(ctx);
+  RET_IF(be.enter());
   EcWork& w = sl.ecw;
   const size_t L = gi->enc;
-  const size_t need = 6 * n + (space == MPVSS_HOST ? 3 * n * L + 2 * n * 32 : 0);
-  if (need > sl.cap) {
-    if (sl.pin) HIPCHK(ctx, hipHostFree(sl.pin));
-    sl.pin = nullptr;
-    sl.cap = 0;
-    hipError_t e = hipHostMalloc(&sl.pin, need, hipHostMallocDefault);
-    if (e != hipSuccess) return fail(ctx, MPVSS_E_NOMEM, "hipHostMalloc(block staging)", e);
-    sl.cap = need;
-  }
+  RET_IF(be.pin(6 * n + (space == MPVSS_HOST ? 3 * n * L + 2 * n * 32 : 0)));
   uint8_t* hok = (uint8_t*)sl.pin;
   if (space == MPVSS_HOST) {
     uint8_t* in = hok + 6 * n;
@@ -1359,11 +1208,7 @@ int ec_verify_shares_compute_locked(mpvss_ctx* ctx, int group, int space, const 
                                          (const uint8_t*)dr, (int)n, dv, oksc, ctx->stream));
   HIPCHK(ctx, hipMemcpyAsync(hok, ok, 6 * n, hipMemcpyDeviceToHost, ctx->stream));
   if (verdicts_dev_out) HIPCHK(ctx, hipMemcpyAsync(verdicts_dev_out, dv, n, hipMemcpyDeviceToDevice, ctx->stream));
-  HIPCHK(ctx, hipEventRecord(sl.done, ctx->stream));
-  sl.busy = true;
-  sl.enqueue_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_enq0).count();
-  ctx->commit_head(sl);
-  return MPVSS_OK;
+  return be.commit();
 }
 
 int ec_verify_shares_absorb_locked(mpvss_ctx* ctx, std::unique_lock<std::mutex>& lk, uint8_t* verdicts_host,
@@ -1372,37 +1217,19 @@ int ec_verify_shares_absorb_locked(mpvss_ctx* ctx, std::unique_lock<std::mutex>&
   if (!slp) return MPVSS_E_INVALID;
   mpvss_ctx::BlockSlot& sl = *slp;
   const size_t n = sl.n;
-  if (n == 0) {
-    ctx->release(sl);
-    if (sl.gpu_done_ctr) sl.gpu_done_ctr->fetch_add(1);
-    return MPVSS_OK;
-  }
-  sl.absorbing = true;
-  {
-    const hipError_t e_dev = hipSetDevice(ctx->device);
-    if (e_dev != hipSuccess) {               // give the slot back: the block is lost, the ring is not
-      ctx->release(sl);
-      sl.absorbing = false;
-      if (sl.gpu_done_ctr) sl.gpu_done_ctr->fetch_add(1);
-      return fail(ctx, MPVSS_E_DEVICE, "absorb: hipSetDevice", e_dev);
-    }
-  }
-  lk.unlock();
-  const hipError_t e = hipEventSynchronize(sl.done);
-  if (sl.gpu_done_ctr) sl.gpu_done_ctr->fetch_add(1);
   const uint8_t* hok = (const uint8_t*)sl.pin;
   long bad_scalar = -1, bad_elem = -1;
-  if (e == hipSuccess) {
+  Absorbed a;
+  RET_IF(absorb_block(ctx, lk, sl, a, [&](bool done) {
+    if (!done) return;
     for (size_t i = 0; i < n && bad_scalar < 0; ++i)
       if (!hok[4 * n + i]) bad_scalar = (long)i;
     for (size_t i = 0; i < 4 * n && bad_elem < 0; ++i)
       if (!hok[i]) bad_elem = (long)(i % n);
     if (bad_scalar < 0 && bad_elem < 0 && verdicts_host) memcpy(verdicts_host, hok + 5 * n, n);
-  }
-  lk.lock();
-  ctx->release(sl);
-  sl.absorbing = false;
-  if (e != hipSuccess) return fail(ctx, MPVSS_E_DEVICE, "ec_verify_shares_absorb: hipEventSynchronize", e);
+  }));
+  if (!a.waited) return MPVSS_OK;
+  if (a.e != hipSuccess) return fail(ctx, MPVSS_E_DEVICE, "ec_verify_shares_absorb: hipEventSynchronize", a.e);
   if (bad_scalar >= 0) return ec_report_bad_scalar(ctx, "ec_verify_shares: response or challenge", (size_t)bad_scalar);
   if (bad_elem >= 0) return ec_report_bad_element(ctx, "share boxes", (size_t)bad_elem);
   RET_IF(spans_sum(ctx, sl.spans, ctx->kernel_ms));

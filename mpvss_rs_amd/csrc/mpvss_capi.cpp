@@ -1454,6 +1454,211 @@ extern "C" int mpvss_modp_dleq_commitments(mpvss_ctx* ctx, int space, const uint
   return MPVSS_OK;
 }
 
+// ---- block slots: the life of a block in the ring ---------------------------------------------------------------------
+// Every batched entry point (verify_distribution blocks and groups, verify_shares, distribute / deal, extract_shares; MODP and
+// curve groups) enqueues its GPU work as a block in a slot (BlockEnqueue) and a later absorb call waits for it, takes its
+// results out of the slot's pinned staging and frees the slot (absorb_block).
+namespace {
+
+// Room for `count` more blocks in the ring (context lock held; released while waiting).  Blocks whose consumer is at work -- another
+// thread's one-call entry point, a pipeline, a claimed block -- free their slots by themselves: wait for them.  When only blocks of
+// the explicit block API fill the ring nobody but the caller can absorb them: an error, as it always was.
+int wait_for_room(mpvss_ctx* ctx, std::unique_lock<std::mutex>& lk, unsigned count = 1) {
+  auto room = [&] {
+    if (ctx->free_top < count) return false;
+    for (unsigned k = 0; k < count; ++k)
+      if (ctx->ring[(ctx->head + k) % mpvss_ctx::NSLOT] >= 0) return false;
+    return true;
+  };
+  while (!room()) {
+    if (!ctx->consumers_at_work())
+      return fail(ctx, MPVSS_E_INVALID, "every block slot (MPVSS_BLOCK_SLOTS) is in flight, absorb one first");
+    ctx->slot_cv.wait(lk);
+  }
+  return 0;
+}
+
+// Enqueue side, context lock held.  Construction takes the ring's head slot (refused while every slot is in flight: `rc`) and
+// resets the block's fields to their defaults -- the caller then sets what its kind needs.  enter() moves the context onto the
+// slot's own workspace, stream pair and spans (a separate step: the curve groups first build their comb on the context's
+// stream), pin() grows the slot's pinned staging, commit() / commit_empty() put the fully enqueued block into the ring.  Only a
+// committed block occupies the slot: on any other way out nothing of the block keeps running on the slot's streams, and the
+// context gets its own workspace, streams and spans back.
+struct BlockEnqueue {
+  mpvss_ctx* ctx;
+  mpvss_ctx::BlockSlot& sl;
+  int rc;                                      // non-zero: there is no block (the error is recorded): return it
+  std::chrono::steady_clock::time_point t0;    // start of the enqueue (the block's enqueue_ms)
+  BlockEnqueue(mpvss_ctx* c, int kind, size_t n, const char* who) : ctx(c), sl(c->head_slot()) { rc = start(kind, n, who); }
+  BlockEnqueue(const BlockEnqueue&) = delete;
+  BlockEnqueue& operator=(const BlockEnqueue&) = delete;
+  ~BlockEnqueue() {
+    if (!sl.busy) {
+      if (entered) {
+        (void)hipStreamSynchronize(sl.work.sa);
+        (void)hipStreamSynchronize(sl.work.sb);
+      }
+      sl.nbox = 1;
+    }
+    if (entered) {
+      ctx->sp = &ctx->main_spans;
+      ctx->w = &ctx->work0;
+      ctx->stream = stream0;
+      ctx->stream_b = stream_b0;
+    }
+  }
+  int commit_empty() {      // a block of no shares: nothing runs, its absorb only frees the slot
+    sl.busy = true;
+    ctx->commit_head(sl);
+    return MPVSS_OK;
+  }
+  int enter() {
+    RET_IF(work_init(ctx, sl.work, nullptr));
+    entered = true;
+    stream0 = ctx->stream;
+    stream_b0 = ctx->stream_b;
+    ctx->w = &sl.work;
+    sl.work.fd_used = false;
+    ctx->stream = sl.work.sa;
+    ctx->stream_b = sl.work.sb;
+    ctx->sp = &sl.spans;
+    spans_reset(ctx);
+    return 0;
+  }
+  int pin(size_t need) {
+    if (need > sl.cap) {
+      if (sl.pin) HIPCHK(ctx, hipHostFree(sl.pin));
+      sl.pin = nullptr;
+      sl.cap = 0;
+      hipError_t e = hipHostMalloc(&sl.pin, need, hipHostMallocDefault);
+      if (e != hipSuccess) return fail(ctx, MPVSS_E_NOMEM, "hipHostMalloc(block staging)", e);
+      sl.cap = need;
+    }
+    return 0;
+  }
+  int commit() {
+    HIPCHK(ctx, hipEventRecord(sl.done, ctx->stream));
+    sl.busy = true;
+    sl.enqueue_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    ctx->commit_head(sl);
+    return MPVSS_OK;
+  }
+
+ private:
+  bool entered = false;
+  hipStream_t stream0 = nullptr, stream_b0 = nullptr;
+  int start(int kind, size_t n, const char* who) {
+    if (sl.busy) {
+      char msg[160];
+      snprintf(msg, sizeof(msg), "%s: every block slot (MPVSS_BLOCK_SLOTS) is in flight, absorb one first", who);
+      return fail(ctx, MPVSS_E_INVALID, msg);
+    }
+    t0 = std::chrono::steady_clock::now();
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    if (!sl.done)      // blocking wait: threads that absorb blocks sleep until the GPU is done instead of spinning
+      HIPCHK(ctx, hipEventCreateWithFlags(&sl.done, hipEventDisableTiming | hipEventBlockingSync));
+    sl.n = n;
+    sl.kind = kind;
+    sl.nbox = 1;
+    sl.dealer = false;
+    sl.group = 0;
+    sl.t = 0;
+    sl.check_positions = false;
+    sl.fd_used = false;
+    sl.fd_chunks = 0;
+    sl.enqueue_ms = 0;
+    return 0;
+  }
+};
+
+// Which block an absorb call works on (context lock held).  ticket == null: the oldest block that waits for a FIFO consumer
+// (the explicit block API); ticket + !by_position: the block mpvss_block_claim handed out under this number; ticket +
+// by_position: the caller's OWN block of this number (mpvss_ctx::own_last: the one-call entry points and the library's box
+// pipeline).  `kind` / `kind2`: the slot kinds the calling entry point absorbs.  Returns null with the error recorded.
+mpvss_ctx::BlockSlot* select_block(mpvss_ctx* ctx, const unsigned long long* ticket, bool by_position, int kind, int kind2, const char* who) {
+  char msg[160];
+  auto bad = [&](const char* what) -> mpvss_ctx::BlockSlot* {
+    snprintf(msg, sizeof(msg), "%s: %s", who, what);
+    (void)fail(ctx, MPVSS_E_INVALID, msg);
+    return nullptr;
+  };
+  mpvss_ctx::BlockSlot* sl;
+  if (!ticket) {
+    sl = &ctx->fifo_front();
+    if (!sl->busy) return bad("no block in flight");
+    if (sl->kind != kind && sl->kind != kind2) return bad("the oldest block in flight belongs to another entry point");
+    ++ctx->tail;
+  } else {
+    sl = &ctx->ring_slot((unsigned)*ticket);
+    if (by_position) {
+      if (!sl->busy || !sl->owned || sl->absorbing) return bad("no block of this caller at this position");
+    } else {
+      if (!sl->busy || !sl->claimed) return bad("no block was claimed with this ticket");
+    }
+    if (sl->kind != kind && sl->kind != kind2) return bad("the block belongs to another entry point");
+    sl->claimed = false;
+  }
+  return sl;
+}
+
+// Absorb side: `sl` is the block select_block chose, context lock held through `lk`.  An empty block is freed at once
+// (`waited` stays false: nothing to account).  Otherwise the lock is RELEASED while this thread waits for the block's GPU work
+// and runs host_work(ok) -- ok: that work completed -- so that other host threads can enqueue blocks or absorb the next ones
+// meanwhile (every box has its own transcript; a 65536-share box is 35 ms of SHA-256); the slot is freed under the lock again.
+struct Absorbed {
+  bool waited = false;
+  hipError_t e = hipSuccess;         // status of the block's GPU work
+  double wait_ms = 0, host_ms = 0;   // waiting for the GPU / host_work
+};
+template <class HostWork>
+int absorb_block(mpvss_ctx* ctx, std::unique_lock<std::mutex>& lk, mpvss_ctx::BlockSlot& sl, Absorbed& a, HostWork&& host_work) {
+  auto give_back = [&] {
+    ctx->release(sl);
+    sl.absorbing = false;
+    if (sl.gpu_done_ctr) sl.gpu_done_ctr->fetch_add(1);
+  };
+  if (sl.n == 0) {
+    give_back();
+    return MPVSS_OK;
+  }
+  sl.absorbing = true;
+  const hipError_t e_dev = hipSetDevice(ctx->device);
+  if (e_dev != hipSuccess) {               // give the slot back: the block is lost, the ring is not
+    give_back();
+    return fail(ctx, MPVSS_E_DEVICE, "absorb: hipSetDevice", e_dev);
+  }
+  lk.unlock();
+  const auto t_w0 = std::chrono::steady_clock::now();
+  a.e = hipEventSynchronize(sl.done);
+  const auto t_w1 = std::chrono::steady_clock::now();
+  if (sl.gpu_done_ctr) sl.gpu_done_ctr->fetch_add(1);
+  host_work(a.e == hipSuccess);
+  const auto t_h1 = std::chrono::steady_clock::now();
+  lk.lock();
+  ctx->release(sl);
+  sl.absorbing = false;
+  a.waited = true;
+  a.wait_ms = std::chrono::duration<double, std::milli>(t_w1 - t_w0).count();
+  a.host_ms = std::chrono::duration<double, std::milli>(t_h1 - t_w1).count();
+  return MPVSS_OK;
+}
+
+// One absorbed block in the pipeline's accounting (mpvss_pipeline_stats_get, read by bench.py), after spans_sum has put its
+// kernel times into ctx->kernel_ms: it counts as `blocks`, its host work as hash time when `hash` is set.
+void pstats_add(mpvss_ctx* ctx, const mpvss_ctx::BlockSlot& sl, const Absorbed& a, bool hash, unsigned long long blocks) {
+  mpvss_ctx::PipeStats& ps = ctx->pstats;
+  ps.enqueue_ms += sl.enqueue_ms;
+  ps.wait_ms += a.wait_ms;
+  if (hash) ps.hash_ms += a.host_ms;
+  for (int k = 0; k < 4; ++k) {
+    ps.kernel_ms[k] += ctx->kernel_ms[k];
+    ps.kernel_launches[k] += (unsigned long long)ctx->kernel_launches[k];
+  }
+  ps.blocks += blocks;
+}
+
+}  // namespace
+
 // ---- verify_distribution_shares --------------------------------------------------------------------
 // Split in three so that a box can be sharded over several engines (one per GPU):
 //   compute : GPU work of one contiguous block of shares; X, Y, a1, a2 land in pinned host staging
@@ -1500,59 +1705,19 @@ int verify_block_compute_locked(mpvss_ctx* ctx, int space, const uint8_t* commit
     pubkeys = (const uint8_t*)ks->keys.p + key_offset * EB;
     key_space = MPVSS_DEVICE;
   }
-  mpvss_ctx::BlockSlot& sl = ctx->head_slot();
-  if (sl.busy) return fail(ctx, MPVSS_E_INVALID, "verify: every block slot (MPVSS_BLOCK_SLOTS) is in flight, absorb one first");
-  const auto t_enq0 = std::chrono::steady_clock::now();
-  HIPCHK(ctx, hipSetDevice(ctx->device));
-  if (!sl.done)      // blocking wait: threads that absorb blocks sleep until the GPU is done instead of spinning
-    HIPCHK(ctx, hipEventCreateWithFlags(&sl.done, hipEventDisableTiming | hipEventBlockingSync));
-  sl.n = n;
-  sl.kind = 0;
-  sl.nbox = 1;
-  sl.check_positions = false;
-  sl.fd_used = false;
-  sl.fd_chunks = 0;
-  sl.enqueue_ms = 0;
-  if (n == 0) {
-    sl.busy = true;
-    ctx->commit_head(sl);
-    return MPVSS_OK;
-  }
+  BlockEnqueue be(ctx, 0, n, "verify");
+  RET_IF(be.rc);
+  mpvss_ctx::BlockSlot& sl = be.sl;
+  if (n == 0) return be.commit_empty();
   if (space == MPVSS_HOST) RET_IF(check_positions_host(ctx, positions, n));
   // this block runs in its slot's own workspace and stream pair, so that boxes overlap on the GPU
-  RET_IF(work_init(ctx, sl.work, nullptr));
-  struct Restore {       // also: an early (error) return leaves nothing of this block running on the slot's streams
-    mpvss_ctx* c;
-    hipStream_t a, b;
-    mpvss_ctx::BlockSlot* sl;
-    ~Restore() {
-      if (!sl->busy) {
-        if (sl->work.sa) (void)hipStreamSynchronize(sl->work.sa);
-        if (sl->work.sb) (void)hipStreamSynchronize(sl->work.sb);
-      }
-      c->sp = &c->main_spans; c->w = &c->work0; c->stream = a; c->stream_b = b;
-    }
-  } restore{ctx, ctx->stream, ctx->stream_b, &sl};
-  ctx->w = &sl.work;
-  sl.work.fd_used = false;
-  ctx->stream = sl.work.sa;
-  ctx->stream_b = sl.work.sb;
-  ctx->sp = &sl.spans;
-  spans_reset(ctx);
+  RET_IF(be.enter());
   // Pinned staging of the slot: the outputs X, Y, a1, a2, the positions, one forward-difference flag per chunk and --
   // for callers that hand over host memory -- a copy of the inputs, so that every transfer is asynchronous and
   // nothing of the caller's is referenced after this call returns.
   constexpr size_t FLAGS = 64;                 // chunks per block whose flags are kept (the rest count as held)
   const size_t out_bytes = n * EB * 4 + n * 8 + FLAGS * 4;
-  const size_t need = out_bytes + ((space == MPVSS_HOST && !prestaged) ? 3 * n * EB + t * EB : 0);
-  if (need > sl.cap) {
-    if (sl.pin) HIPCHK(ctx, hipHostFree(sl.pin));
-    sl.pin = nullptr;
-    sl.cap = 0;
-    hipError_t e = hipHostMalloc(&sl.pin, need, hipHostMallocDefault);
-    if (e != hipSuccess) return fail(ctx, MPVSS_E_NOMEM, "hipHostMalloc(block staging)", e);
-    sl.cap = need;
-  }
+  RET_IF(be.pin(out_bytes + ((space == MPVSS_HOST && !prestaged) ? 3 * n * EB + t * EB : 0)));
   uint8_t* hX = (uint8_t*)sl.pin;
   uint8_t* hY = hX + n * EB;
   uint8_t* h1 = hY + n * EB;
@@ -1593,7 +1758,7 @@ int verify_block_compute_locked(mpvss_ctx* ctx, int space, const uint8_t* commit
   static const int trace_enq = fd_env("MPVSS_TRACE_ENQUEUE", 0);
   double marks[8] = {0, 0, 0, 0, 0, 0, 0, 0};
   auto mark = [&](int i) {
-    if (trace_enq) marks[i] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_enq0).count();
+    if (trace_enq) marks[i] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - be.t0).count();
   };
   mark(0);
   RET_IF(stage_commitments(ctx, space, commitments, t));
@@ -1787,14 +1952,11 @@ int verify_block_compute_locked(mpvss_ctx* ctx, int space, const uint8_t* commit
     if (off + MAX_CHUNK < n) HIPCHK(ctx, hipStreamSynchronize(ctx->stream));   // device buffers are reused
   }
   mark(4);
-  HIPCHK(ctx, hipEventRecord(sl.done, ctx->stream));
-  sl.busy = true;      // only a fully enqueued block occupies the slot (an error above leaves it free)
-  sl.enqueue_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_enq0).count();
+  RET_IF(be.commit());
   if (trace_enq && sl.enqueue_ms > 3.0)
     fprintf(stderr, "[mpvss] slow enqueue %.1f ms: staging %.1f | commitments %.1f | tables+a2+g^r %.1f | X path %.1f | a1+copies %.1f | "
             "event %.1f\n", sl.enqueue_ms, marks[0], marks[1] - marks[0], marks[2] - marks[1], marks[3] - marks[2],
             marks[4] - marks[3], sl.enqueue_ms - marks[4]);
-  ctx->commit_head(sl);
   return MPVSS_OK;
 }
 
@@ -1832,52 +1994,17 @@ bool box_groupable(const mpvss_modp_box& bx, size_t n, size_t t, int space) {
 
 int verify_group_compute_locked(mpvss_ctx* ctx, int space, const mpvss_modp_box* boxes, size_t B) {
   const size_t n = boxes[0].n, t = boxes[0].t, N = B * n;
-  mpvss_ctx::BlockSlot& sl = ctx->head_slot();
-  if (sl.busy) return fail(ctx, MPVSS_E_INVALID, "verify: every block slot (MPVSS_BLOCK_SLOTS) is in flight, absorb one first");
-  const auto t_enq0 = std::chrono::steady_clock::now();
-  HIPCHK(ctx, hipSetDevice(ctx->device));
-  if (!sl.done) HIPCHK(ctx, hipEventCreateWithFlags(&sl.done, hipEventDisableTiming | hipEventBlockingSync));
-  sl.n = N;
+  BlockEnqueue be(ctx, 0, N, "verify");
+  RET_IF(be.rc);
+  mpvss_ctx::BlockSlot& sl = be.sl;
   sl.nbox = (unsigned)B;
-  sl.kind = 0;
-  sl.check_positions = false;
-  sl.fd_used = false;
-  sl.fd_chunks = 0;
-  sl.enqueue_ms = 0;
-  RET_IF(work_init(ctx, sl.work, nullptr));
-  struct Restore {       // an early (error) return leaves nothing of this block running on the slot's streams
-    mpvss_ctx* c;
-    hipStream_t a, b;
-    mpvss_ctx::BlockSlot* sl;
-    ~Restore() {
-      if (!sl->busy) {
-        if (sl->work.sa) (void)hipStreamSynchronize(sl->work.sa);
-        if (sl->work.sb) (void)hipStreamSynchronize(sl->work.sb);
-        sl->nbox = 1;
-      }
-      c->sp = &c->main_spans; c->w = &c->work0; c->stream = a; c->stream_b = b;
-    }
-  } restore{ctx, ctx->stream, ctx->stream_b, &sl};
+  RET_IF(be.enter());
   mpvss_ctx::Work& w = sl.work;
-  ctx->w = &w;
-  w.fd_used = false;
-  ctx->stream = w.sa;
-  ctx->stream_b = w.sb;
-  ctx->sp = &sl.spans;
-  spans_reset(ctx);
   // pinned staging as for a lone block (X | Y | a1 | a2 | positions | flags | host inputs), then the boxes' challenges
   constexpr size_t FLAGS = 64;
   const size_t out_bytes = N * EB * 4 + N * 8 + FLAGS * 4;
   const size_t in_bytes = space == MPVSS_HOST ? 3 * N * EB + B * t * EB : 0;
-  const size_t need = out_bytes + in_bytes + B * EB;
-  if (need > sl.cap) {
-    if (sl.pin) HIPCHK(ctx, hipHostFree(sl.pin));
-    sl.pin = nullptr;
-    sl.cap = 0;
-    hipError_t e = hipHostMalloc(&sl.pin, need, hipHostMallocDefault);
-    if (e != hipSuccess) return fail(ctx, MPVSS_E_NOMEM, "hipHostMalloc(block staging)", e);
-    sl.cap = need;
-  }
+  RET_IF(be.pin(out_bytes + in_bytes + B * EB));
   uint8_t* hX = (uint8_t*)sl.pin;
   uint8_t* hY = hX + N * EB;
   uint8_t* h1 = hY + N * EB;
@@ -1984,64 +2111,10 @@ int verify_group_compute_locked(mpvss_ctx* ctx, int space, const mpvss_modp_box*
     HIPCHK(ctx, hipMemcpyAsync(hflags, w.fd_flag.p, 4, hipMemcpyDeviceToHost, ctx->stream));
     sl.fd_chunks = 1;
   }
-  HIPCHK(ctx, hipEventRecord(sl.done, ctx->stream));
-  sl.busy = true;
-  sl.enqueue_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_enq0).count();
-  ctx->commit_head(sl);
-  return MPVSS_OK;
+  return be.commit();
 }
 
-// Room for `count` more blocks in the ring (context lock held; released while waiting).  Blocks whose consumer is at work -- another
-// thread's one-call entry point, a pipeline, a claimed block -- free their slots by themselves: wait for them.  When only blocks of
-// the explicit block API fill the ring nobody but the caller can absorb them: an error, as it always was.
-int wait_for_room(mpvss_ctx* ctx, std::unique_lock<std::mutex>& lk, unsigned count = 1) {
-  auto room = [&] {
-    if (ctx->free_top < count) return false;
-    for (unsigned k = 0; k < count; ++k)
-      if (ctx->ring[(ctx->head + k) % mpvss_ctx::NSLOT] >= 0) return false;
-    return true;
-  };
-  while (!room()) {
-    if (!ctx->consumers_at_work())
-      return fail(ctx, MPVSS_E_INVALID, "every block slot (MPVSS_BLOCK_SLOTS) is in flight, absorb one first");
-    ctx->slot_cv.wait(lk);
-  }
-  return 0;
-}
-
-// Which block an absorb call works on (context lock held).  ticket == null: the oldest block that waits for a FIFO consumer
-// (the explicit block API); ticket + !by_position: the block mpvss_block_claim handed out under this number; ticket +
-// by_position: the caller's OWN block of this number (mpvss_ctx::own_last: the one-call entry points and the library's box
-// pipeline).  `kind` / `kind2`: the slot kinds the calling entry point absorbs.  Returns null with the error recorded.
-mpvss_ctx::BlockSlot* select_block(mpvss_ctx* ctx, const unsigned long long* ticket, bool by_position, int kind, int kind2, const char* who) {
-  char msg[160];
-  auto bad = [&](const char* what) -> mpvss_ctx::BlockSlot* {
-    snprintf(msg, sizeof(msg), "%s: %s", who, what);
-    (void)fail(ctx, MPVSS_E_INVALID, msg);
-    return nullptr;
-  };
-  mpvss_ctx::BlockSlot* sl;
-  if (!ticket) {
-    sl = &ctx->fifo_front();
-    if (!sl->busy) return bad("no block in flight");
-    if (sl->kind != kind && sl->kind != kind2) return bad("the oldest block in flight belongs to another entry point");
-    ++ctx->tail;
-  } else {
-    sl = &ctx->ring_slot((unsigned)*ticket);
-    if (by_position) {
-      if (!sl->busy || !sl->owned || sl->absorbing) return bad("no block of this caller at this position");
-    } else {
-      if (!sl->busy || !sl->claimed) return bad("no block was claimed with this ticket");
-    }
-    if (sl->kind != kind && sl->kind != kind2) return bad("the block belongs to another entry point");
-    sl->claimed = false;
-  }
-  return sl;
-}
-
-// Called with `lk` (the context lock) held.  The lock is RELEASED while this thread waits for the block's GPU work
-// and hashes it, so that other host threads can enqueue blocks or absorb the next ones meanwhile (every box has its
-// own transcript; a 65536-share box is 35 ms of SHA-256).
+// Called with `lk` (the context lock) held; released while this thread waits for the block and hashes it (absorb_block).
 int verify_block_absorb_locked(mpvss_ctx* ctx, std::unique_lock<std::mutex>& lk, uint8_t* state, uint8_t* x_out,
                                uint8_t* a1_out, uint8_t* a2_out, uint8_t* y_out = nullptr,
                                const unsigned long long* ticket = nullptr, bool by_position = false,
@@ -2060,33 +2133,14 @@ int verify_block_absorb_locked(mpvss_ctx* ctx, std::unique_lock<std::mutex>& lk,
   mpvss_ctx::BlockSlot& sl = *slp;
   const size_t n = sl.n;
   const size_t nbox = sl.nbox ? sl.nbox : 1;
-  if (n == 0) {
-    ctx->release(sl);
-    sl.absorbing = false;
-    if (sl.gpu_done_ctr) sl.gpu_done_ctr->fetch_add(1);
-    return MPVSS_OK;
-  }
-  sl.absorbing = true;
-  {
-    const hipError_t e_dev = hipSetDevice(ctx->device);
-    if (e_dev != hipSuccess) {               // give the slot back: the block is lost, the ring is not
-      ctx->release(sl);
-      sl.absorbing = false;
-      if (sl.gpu_done_ctr) sl.gpu_done_ctr->fetch_add(1);
-      return fail(ctx, MPVSS_E_DEVICE, "absorb: hipSetDevice", e_dev);
-    }
-  }
-  lk.unlock();
-  const auto t_w0 = std::chrono::steady_clock::now();
   const uint8_t* hX = (const uint8_t*)sl.pin;
   const uint8_t* hY = hX + n * EB;
   const uint8_t* h1 = hY + n * EB;
   const uint8_t* h2 = h1 + n * EB;
   bool positions_ok = true;
-  const hipError_t e = hipEventSynchronize(sl.done);
-  const auto t_w1 = std::chrono::steady_clock::now();
-  if (sl.gpu_done_ctr) sl.gpu_done_ctr->fetch_add(1);
-  if (e == hipSuccess) {
+  Absorbed a;
+  RET_IF(absorb_block(ctx, lk, sl, a, [&](bool done) {
+    if (!done) return;
     if (sl.check_positions && nbox == 1) {
       const int64_t* pos = (const int64_t*)(h2 + n * EB);
       for (size_t i = 0; i < n && positions_ok; ++i) positions_ok = pos[i] >= 0;
@@ -2122,11 +2176,9 @@ int verify_block_absorb_locked(mpvss_ctx* ctx, std::unique_lock<std::mutex>& lk,
       });
       memcpy(state, &tr, sizeof(tr));
     }
-  }
-  const auto t_h1 = std::chrono::steady_clock::now();
-  lk.lock();
-  ctx->release(sl);
-  sl.absorbing = false;
+  }));
+  if (!a.waited) return MPVSS_OK;
+  const hipError_t e = a.e;
   if (e == hipSuccess && sl.fd_used) {
     const int* hflags = (const int*)(h2 + n * EB + n * 8);
     bool held = true;
@@ -2137,17 +2189,7 @@ int verify_block_absorb_locked(mpvss_ctx* ctx, std::unique_lock<std::mutex>& lk,
   if (e != hipSuccess) return fail(ctx, MPVSS_E_DEVICE, "absorb: hipEventSynchronize", e);
   if (!positions_ok) return fail(ctx, MPVSS_E_INVALID, "negative position (the reference panics: negative exponent)");
   RET_IF(spans_sum(ctx, sl.spans, ctx->kernel_ms));
-  {
-    mpvss_ctx::PipeStats& ps = ctx->pstats;
-    ps.enqueue_ms += sl.enqueue_ms;
-    ps.wait_ms += std::chrono::duration<double, std::milli>(t_w1 - t_w0).count();
-    ps.hash_ms += std::chrono::duration<double, std::milli>(t_h1 - t_w1).count();
-    for (int k = 0; k < 4; ++k) {
-      ps.kernel_ms[k] += ctx->kernel_ms[k];
-      ps.kernel_launches[k] += (unsigned long long)ctx->kernel_launches[k];
-    }
-    ps.blocks += (unsigned long long)nbox;      // a group block counts as its boxes
-  }
+  pstats_add(ctx, sl, a, true, nbox);      // a group block counts as its boxes
   return MPVSS_OK;
 }
 
@@ -2936,50 +2978,13 @@ namespace {
 int verify_shares_compute_locked(mpvss_ctx* ctx, int space, const uint8_t* pk, const uint8_t* s, const uint8_t* y,
                                  const uint8_t* c, const uint8_t* r, size_t n, uint8_t* verdicts_dev_out) {
   if (n > 0 && (!pk || !s || !y || !c || !r || n > 0x7fffffff)) return fail(ctx, MPVSS_E_INVALID, "verify_shares: bad argument");
-  mpvss_ctx::BlockSlot& sl = ctx->head_slot();
-  if (sl.busy) return fail(ctx, MPVSS_E_INVALID, "verify_shares: every block slot (MPVSS_BLOCK_SLOTS) is in flight, absorb one first");
-  const auto t_enq0 = std::chrono::steady_clock::now();
-  HIPCHK(ctx, hipSetDevice(ctx->device));
-  if (!sl.done) HIPCHK(ctx, hipEventCreateWithFlags(&sl.done, hipEventDisableTiming | hipEventBlockingSync));
-  sl.n = n;
-  sl.kind = 1;
-  sl.check_positions = false;
-  sl.fd_used = false;
-  sl.fd_chunks = 0;
-  sl.enqueue_ms = 0;
-  if (n == 0) {
-    sl.busy = true;
-    ctx->commit_head(sl);
-    return MPVSS_OK;
-  }
-  RET_IF(work_init(ctx, sl.work, nullptr));
-  struct Restore {       // also: an early (error) return leaves nothing of this block running on the slot's streams
-    mpvss_ctx* c;
-    hipStream_t a, b;
-    mpvss_ctx::BlockSlot* sl;
-    ~Restore() {
-      if (!sl->busy) {
-        if (sl->work.sa) (void)hipStreamSynchronize(sl->work.sa);
-        if (sl->work.sb) (void)hipStreamSynchronize(sl->work.sb);
-      }
-      c->sp = &c->main_spans; c->w = &c->work0; c->stream = a; c->stream_b = b;
-    }
-  } restore{ctx, ctx->stream, ctx->stream_b, &sl};
-  ctx->w = &sl.work;
-  ctx->stream = sl.work.sa;
-  ctx->stream_b = sl.work.sb;
-  ctx->sp = &sl.spans;
-  spans_reset(ctx);
+  BlockEnqueue be(ctx, 1, n, "verify_shares");
+  RET_IF(be.rc);
+  mpvss_ctx::BlockSlot& sl = be.sl;
+  if (n == 0) return be.commit_empty();
+  RET_IF(be.enter());
   // pinned staging: the verdict bytes and, for host callers, a copy of the five input arrays
-  const size_t need = n + (space == MPVSS_HOST ? 5 * n * EB : 0);
-  if (need > sl.cap) {
-    if (sl.pin) HIPCHK(ctx, hipHostFree(sl.pin));
-    sl.pin = nullptr;
-    sl.cap = 0;
-    hipError_t e = hipHostMalloc(&sl.pin, need, hipHostMallocDefault);
-    if (e != hipSuccess) return fail(ctx, MPVSS_E_NOMEM, "hipHostMalloc(block staging)", e);
-    sl.cap = need;
-  }
+  RET_IF(be.pin(n + (space == MPVSS_HOST ? 5 * n * EB : 0)));
   uint8_t* hv = (uint8_t*)sl.pin;
   if (space == MPVSS_HOST) {
     uint8_t* in = hv + n;
@@ -3033,11 +3038,7 @@ int verify_shares_compute_locked(mpvss_ctx* ctx, int space, const uint8_t* pk, c
   }
   HIPCHK(ctx, hipMemcpyAsync(hv, dv, n, hipMemcpyDeviceToHost, ctx->stream));
   if (verdicts_dev_out) HIPCHK(ctx, hipMemcpyAsync(verdicts_dev_out, dv, n, hipMemcpyDeviceToDevice, ctx->stream));
-  HIPCHK(ctx, hipEventRecord(sl.done, ctx->stream));
-  sl.busy = true;
-  sl.enqueue_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_enq0).count();
-  ctx->commit_head(sl);
-  return MPVSS_OK;
+  return be.commit();
 }
 
 int verify_shares_absorb_locked(mpvss_ctx* ctx, std::unique_lock<std::mutex>& lk, uint8_t* verdicts_host,
@@ -3045,40 +3046,14 @@ int verify_shares_absorb_locked(mpvss_ctx* ctx, std::unique_lock<std::mutex>& lk
   mpvss_ctx::BlockSlot* slp = select_block(ctx, own_pos, own_pos != nullptr, 1, 1, "verify_shares_absorb");
   if (!slp) return MPVSS_E_INVALID;
   mpvss_ctx::BlockSlot& sl = *slp;
-  const size_t n = sl.n;
-  if (n == 0) {
-    ctx->release(sl);
-    if (sl.gpu_done_ctr) sl.gpu_done_ctr->fetch_add(1);
-    return MPVSS_OK;
-  }
-  sl.absorbing = true;
-  {
-    const hipError_t e_dev = hipSetDevice(ctx->device);
-    if (e_dev != hipSuccess) {               // give the slot back: the block is lost, the ring is not
-      ctx->release(sl);
-      sl.absorbing = false;
-      if (sl.gpu_done_ctr) sl.gpu_done_ctr->fetch_add(1);
-      return fail(ctx, MPVSS_E_DEVICE, "absorb: hipSetDevice", e_dev);
-    }
-  }
-  lk.unlock();
-  const auto t_w0 = std::chrono::steady_clock::now();
-  const hipError_t e = hipEventSynchronize(sl.done);
-  const auto t_w1 = std::chrono::steady_clock::now();
-  if (sl.gpu_done_ctr) sl.gpu_done_ctr->fetch_add(1);
-  if (e == hipSuccess && verdicts_host) memcpy(verdicts_host, sl.pin, n);
-  lk.lock();
-  ctx->release(sl);
-  sl.absorbing = false;
-  if (e != hipSuccess) return fail(ctx, MPVSS_E_DEVICE, "verify_shares_absorb: hipEventSynchronize", e);
+  Absorbed a;
+  RET_IF(absorb_block(ctx, lk, sl, a, [&](bool done) {
+    if (done && verdicts_host) memcpy(verdicts_host, sl.pin, sl.n);
+  }));
+  if (!a.waited) return MPVSS_OK;
+  if (a.e != hipSuccess) return fail(ctx, MPVSS_E_DEVICE, "verify_shares_absorb: hipEventSynchronize", a.e);
   RET_IF(spans_sum(ctx, sl.spans, ctx->kernel_ms));
-  ctx->pstats.enqueue_ms += sl.enqueue_ms;
-  ctx->pstats.wait_ms += std::chrono::duration<double, std::milli>(t_w1 - t_w0).count();
-  for (int k = 0; k < 4; ++k) {
-    ctx->pstats.kernel_ms[k] += ctx->kernel_ms[k];
-    ctx->pstats.kernel_launches[k] += (unsigned long long)ctx->kernel_launches[k];
-  }
-  ++ctx->pstats.blocks;
+  pstats_add(ctx, sl, a, false, 1);
   return MPVSS_OK;
 }
 
@@ -3159,55 +3134,16 @@ int distribute_block_compute_locked(mpvss_ctx* ctx, int space, const uint8_t* co
   if (n > 0 && (!pubkeys || !p_values || !witnesses || n > 0x7fffffff || (commitments && (!positions || t == 0 || t > 0x7fffffff))))
     return fail(ctx, MPVSS_E_INVALID, "distribute: bad argument");
   // (threshold > n is the whole box's business -- mpvss_modp_distribute checks it; a block of a box may be smaller)
-  mpvss_ctx::BlockSlot& sl = ctx->head_slot();
-  if (sl.busy) return fail(ctx, MPVSS_E_INVALID, "distribute: every block slot (MPVSS_BLOCK_SLOTS) is in flight, absorb one first");
-  const auto t_enq0 = std::chrono::steady_clock::now();
-  HIPCHK(ctx, hipSetDevice(ctx->device));
-  if (!sl.done) HIPCHK(ctx, hipEventCreateWithFlags(&sl.done, hipEventDisableTiming | hipEventBlockingSync));
-  sl.n = n;
-  sl.kind = 0;                 // absorbed like a verifier's block: same staging layout, same hash
-  sl.nbox = 1;
-  sl.check_positions = false;
-  sl.fd_used = false;
-  sl.fd_chunks = 0;
-  sl.enqueue_ms = 0;
-  if (n == 0) {
-    sl.busy = true;
-    ctx->commit_head(sl);
-    return MPVSS_OK;
-  }
+  BlockEnqueue be(ctx, 0, n, "distribute");       // absorbed like a verifier's block: same staging layout, same hash
+  RET_IF(be.rc);
+  mpvss_ctx::BlockSlot& sl = be.sl;
+  if (n == 0) return be.commit_empty();
   if (commitments && space == MPVSS_HOST) RET_IF(check_positions_host(ctx, positions, n));
-  RET_IF(work_init(ctx, sl.work, nullptr));
-  struct Restore {       // also: an early (error) return leaves nothing of this block running on the slot's streams
-    mpvss_ctx* c;
-    hipStream_t a, b;
-    mpvss_ctx::BlockSlot* sl;
-    ~Restore() {
-      if (!sl->busy) {
-        if (sl->work.sa) (void)hipStreamSynchronize(sl->work.sa);
-        if (sl->work.sb) (void)hipStreamSynchronize(sl->work.sb);
-      }
-      c->sp = &c->main_spans; c->w = &c->work0; c->stream = a; c->stream_b = b;
-    }
-  } restore{ctx, ctx->stream, ctx->stream_b, &sl};
-  ctx->w = &sl.work;
-  sl.work.fd_used = false;
-  ctx->stream = sl.work.sa;
-  ctx->stream_b = sl.work.sb;
-  ctx->sp = &sl.spans;
-  spans_reset(ctx);
+  RET_IF(be.enter());
   constexpr size_t FLAGS = 64;
   const size_t out_bytes = n * EB * 4 + n * 8 + FLAGS * 4;
-  const size_t need = out_bytes + (space == MPVSS_HOST ? 3 * n * EB + (commitments ? t * EB : 0) : 0) +
-                      (poly && !poly->limbs_dev ? poly->t * MODP_L * 4 : 0);
-  if (need > sl.cap) {
-    if (sl.pin) HIPCHK(ctx, hipHostFree(sl.pin));
-    sl.pin = nullptr;
-    sl.cap = 0;
-    hipError_t e = hipHostMalloc(&sl.pin, need, hipHostMallocDefault);
-    if (e != hipSuccess) return fail(ctx, MPVSS_E_NOMEM, "hipHostMalloc(block staging)", e);
-    sl.cap = need;
-  }
+  RET_IF(be.pin(out_bytes + (space == MPVSS_HOST ? 3 * n * EB + (commitments ? t * EB : 0) : 0) +
+                (poly && !poly->limbs_dev ? poly->t * MODP_L * 4 : 0)));
   uint8_t* hX = (uint8_t*)sl.pin;
   uint8_t* hY = hX + n * EB;
   uint8_t* h1 = hY + n * EB;
@@ -3339,11 +3275,7 @@ int distribute_block_compute_locked(mpvss_ctx* ctx, int space, const uint8_t* co
       HIPCHK(ctx, hipStreamSynchronize(ctx->w->sb));
     }
   }
-  HIPCHK(ctx, hipEventRecord(sl.done, ctx->stream));
-  sl.busy = true;
-  sl.enqueue_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_enq0).count();
-  ctx->commit_head(sl);
-  return MPVSS_OK;
+  return be.commit();
 }
 
 }  // namespace
@@ -3555,8 +3487,9 @@ namespace {
 int extract_shares_compute_locked(mpvss_ctx* ctx, const uint8_t* pk, const uint8_t* y, const uint8_t* xinv, const uint8_t* w,
                                   size_t n) {
   if (n == 0 || !pk || !y || !xinv || !w || n > 0x7fffffff) return fail(ctx, MPVSS_E_INVALID, "extract_shares_compute: bad argument");
-  mpvss_ctx::BlockSlot& sl = ctx->head_slot();
-  if (sl.busy) return fail(ctx, MPVSS_E_INVALID, "extract_shares_compute: every block slot (MPVSS_BLOCK_SLOTS) is in flight, absorb one first");
+  BlockEnqueue be(ctx, 4, n, "extract_shares_compute");
+  RET_IF(be.rc);
+  mpvss_ctx::BlockSlot& sl = be.sl;
   if (n > MAX_CHUNK) return fail(ctx, MPVSS_E_UNSUPPORTED, "extract_shares_compute: batch larger than one chunk");
   {
     uint8_t qb[EB];
@@ -3566,43 +3499,9 @@ int extract_shares_compute_locked(mpvss_ctx* ctx, const uint8_t* pk, const uint8
       if (memcmp(y + i * EB, zero, EB) == 0 || memcmp(y + i * EB, qb, EB) == 0)
         return fail(ctx, MPVSS_E_UNSUPPORTED, "extract_shares_compute: an encrypted share is 0 mod q (use mpvss_modp_extract_shares)");
   }
-  const auto t_enq0 = std::chrono::steady_clock::now();
-  HIPCHK(ctx, hipSetDevice(ctx->device));
-  if (!sl.done) HIPCHK(ctx, hipEventCreateWithFlags(&sl.done, hipEventDisableTiming | hipEventBlockingSync));
-  sl.n = n;
-  sl.kind = 4;
-  sl.check_positions = false;
-  sl.fd_used = false;
-  sl.fd_chunks = 0;
-  sl.enqueue_ms = 0;
-  RET_IF(work_init(ctx, sl.work, nullptr));
-  struct Restore {       // also: an early (error) return leaves nothing of this block running on the slot's streams
-    mpvss_ctx* c;
-    hipStream_t a, b;
-    mpvss_ctx::BlockSlot* sl;
-    ~Restore() {
-      if (!sl->busy) {
-        if (sl->work.sa) (void)hipStreamSynchronize(sl->work.sa);
-        if (sl->work.sb) (void)hipStreamSynchronize(sl->work.sb);
-      }
-      c->sp = &c->main_spans; c->w = &c->work0; c->stream = a; c->stream_b = b;
-    }
-  } restore{ctx, ctx->stream, ctx->stream_b, &sl};
-  ctx->w = &sl.work;
-  ctx->stream = sl.work.sa;
-  ctx->stream_b = sl.work.sb;
-  ctx->sp = &sl.spans;
-  spans_reset(ctx);
+  RET_IF(be.enter());
   // pinned staging: outputs S [n][256], c [n][32]; inputs pk, y, xinv, w [n][256] each
-  const size_t need = n * EB + n * 32 + 4 * n * EB;
-  if (need > sl.cap) {
-    if (sl.pin) HIPCHK(ctx, hipHostFree(sl.pin));
-    sl.pin = nullptr;
-    sl.cap = 0;
-    hipError_t e = hipHostMalloc(&sl.pin, need, hipHostMallocDefault);
-    if (e != hipSuccess) return fail(ctx, MPVSS_E_NOMEM, "hipHostMalloc(block staging)", e);
-    sl.cap = need;
-  }
+  RET_IF(be.pin(n * EB + n * 32 + 4 * n * EB));
   uint8_t* hS = (uint8_t*)sl.pin;
   uint8_t* hc = hS + n * EB;
   uint8_t* in = hc + n * 32;
@@ -3648,11 +3547,7 @@ int extract_shares_compute_locked(mpvss_ctx* ctx, const uint8_t* pk, const uint8
   TIMED_LAUNCH(ctx, 0, verdict_launch_modp_challenge((const uint8_t*)dpk, (const uint8_t*)dy, da1, da2, (int)n, dc, ctx->stream));
   HIPCHK(ctx, hipMemcpyAsync(hS, dS, n * EB, hipMemcpyDeviceToHost, ctx->stream));
   HIPCHK(ctx, hipMemcpyAsync(hc, dc, n * 32, hipMemcpyDeviceToHost, ctx->stream));
-  HIPCHK(ctx, hipEventRecord(sl.done, ctx->stream));
-  sl.busy = true;
-  sl.enqueue_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_enq0).count();
-  ctx->commit_head(sl);
-  return MPVSS_OK;
+  return be.commit();
 }
 
 int extract_shares_absorb_locked(mpvss_ctx* ctx, std::unique_lock<std::mutex>& lk, uint8_t* s_out_host, uint8_t* c_out_host) {
@@ -3660,20 +3555,9 @@ int extract_shares_absorb_locked(mpvss_ctx* ctx, std::unique_lock<std::mutex>& l
   if (!slp) return MPVSS_E_INVALID;
   mpvss_ctx::BlockSlot& sl = *slp;
   const size_t n = sl.n;
-  sl.absorbing = true;
-  {
-    const hipError_t e_dev = hipSetDevice(ctx->device);
-    if (e_dev != hipSuccess) {
-      ctx->release(sl);
-      sl.absorbing = false;
-      if (sl.gpu_done_ctr) sl.gpu_done_ctr->fetch_add(1);
-      return fail(ctx, MPVSS_E_DEVICE, "absorb: hipSetDevice", e_dev);
-    }
-  }
-  lk.unlock();
-  const hipError_t e = hipEventSynchronize(sl.done);
-  if (sl.gpu_done_ctr) sl.gpu_done_ctr->fetch_add(1);
-  if (e == hipSuccess) {
+  Absorbed a;
+  RET_IF(absorb_block(ctx, lk, sl, a, [&](bool done) {
+    if (!done) return;
     const uint8_t* hS = (const uint8_t*)sl.pin;
     const uint8_t* hc = hS + n * EB;
     if (s_out_host) memcpy(s_out_host, hS, n * EB);
@@ -3682,11 +3566,9 @@ int extract_shares_absorb_locked(mpvss_ctx* ctx, std::unique_lock<std::mutex>& l
         memset(c_out_host + i * EB, 0, EB - 32);
         memcpy(c_out_host + i * EB + EB - 32, hc + i * 32, 32);
       }
-  }
-  lk.lock();
-  ctx->release(sl);
-  sl.absorbing = false;
-  if (e != hipSuccess) return fail(ctx, MPVSS_E_DEVICE, "extract_shares_absorb: hipEventSynchronize", e);
+  }));
+  if (!a.waited) return MPVSS_OK;
+  if (a.e != hipSuccess) return fail(ctx, MPVSS_E_DEVICE, "extract_shares_absorb: hipEventSynchronize", a.e);
   RET_IF(spans_sum(ctx, sl.spans, ctx->kernel_ms));
   return MPVSS_OK;
 }

@@ -1,6 +1,7 @@
 """Paths the parity tests do not reach by themselves: device-resident buffers (torch tensors' data_ptr), the
 multi-chunk loop, two blocks in flight (pipelining), concurrent host threads on one context, a caller stream."""
 import ctypes as C
+import json
 import os
 import random
 import subprocess
@@ -10,7 +11,7 @@ import threading
 import pytest
 
 import mpvss_oracle as O
-from helpers import EB, cat, make_modp_instance, split
+from helpers import EB, cat, make_modp_instance, modp_keygen, split
 from mpvss_rs_amd import capi
 
 pytestmark = pytest.mark.gpu
@@ -270,3 +271,79 @@ def test_block_wellformedness_bytes(engine):
     assert got == [0, 0, 1, 0, 0, 1, 0, 1, 1] + [1] * 30 + [0]
     ref = engine.verify_distribution(flat["commitments"], flat["positions"], bytes(pk), bytes(sh), bytes(rs), flat["challenge"])
     assert verdict == (ref["verdict"], ref["digest"]) and verdict[0] is False
+
+
+
+def test_pipeline_stats_per_block_kind(engine):
+    """What one compute / absorb pair of each block kind adds to mpvss_pipeline_stats_get (bench.py reads it): a MODP
+    distribution block counts its boxes, with hash time (a group of boxes that verify_many enqueues as one block: one per
+    box); a MODP verify_share batch one block, without hash time; a curve distribution block one, with hash time; curve
+    verify_share batches and extract batches add nothing."""
+    g, privs, pks, coeffs, ws, box = make_modp_instance(12, 4, 41)
+    flat = O.box_to_flat(g, box)
+    n = flat["n"]
+
+    def added(run):
+        engine.pipeline_stats(reset=True)
+        run()
+        st = engine.pipeline_stats(reset=True)
+        return st["blocks"], st["hash_ms"] > 0
+
+    def modp_block():
+        engine.verify_block_compute(flat["commitments"], flat["positions"], flat["publickeys"], flat["shares"],
+                                    flat["responses"], flat["challenge"])
+        st = engine.verify_block_absorb(capi.transcript_init())
+        assert capi.transcript_verdict(st, flat["challenge"]) == (True, box["_digest"])
+    assert added(modp_block) == (1, True)
+
+    def modp_group():
+        one = {"commitments": flat["commitments"], "positions": flat["positions"], "pubkeys": flat["publickeys"],
+               "shares": flat["shares"], "responses": flat["responses"], "challenge": flat["challenge"]}
+        assert engine.verify_many([one] * 3, depth=4, hash_threads=2) == [(True, box["_digest"])] * 3
+    assert added(modp_group) == (3, True)
+
+    rng = random.Random(42)
+    wit = [modp_keygen(g, rng) for _ in privs]
+    pkb, Yb = cat(g, pks), cat(g, [box["shares"][g.element_to_bytes(p)] for p in pks])
+    xinv = cat(g, [O.mod_inverse(x, g.group_order_int()) for x in privs])
+    out = {}
+
+    def extract():
+        assert engine.extract_shares_compute(pkb, Yb, xinv, cat(g, wit)) == n
+        out["S"], out["c"] = engine.extract_shares_absorb(n)
+    assert added(extract) == (0, False)
+    r = cat(g, [O.dleq_response(g, w, x, c) for w, x, c in zip(wit, privs, split(out["c"]))])
+
+    def modp_shares():
+        assert engine.verify_shares_compute(pkb, out["S"], Yb, out["c"], r) == n
+        assert list(engine.verify_shares_absorb(n)) == [1] * n
+    assert added(modp_shares) == (1, False)
+
+    G, gid = O.GROUPS["secp256k1"](), capi.GROUP_SECP256K1
+    fx = json.load(open(os.path.join(ROOT, "tests", "golden", "secp256k1_n8_t4.json")))
+    b = fx["box"]
+    hx = lambda hs: bytes.fromhex("".join(hs))
+
+    def ec_block():
+        engine.ec_verify_block_compute(gid, hx(b["commitments"]), b["positions"], hx(b["publickeys"]), hx(b["shares"]),
+                                       hx(b["responses"]), bytes.fromhex(b["challenge"]))
+        st = engine.ec_verify_block_absorb(capi.transcript_init())
+        assert capi.ec_transcript_verdict(gid, st, bytes.fromhex(b["challenge"])) == \
+            (True, bytes.fromhex(fx["expected"]["transcript_digest"]))
+    assert added(ec_block) == (1, True)
+
+    order = G.group_order_int()
+    ek = [rng.randrange(1, order) for _ in range(6)]
+    epk = [G.generate_public_key(k) for k in ek]
+    ebox = O.distribute_secret(G, 0x1234, epk, 3, [rng.randrange(order) for _ in range(3)],
+                               [rng.randrange(1, order) for _ in range(6)])
+    proofs = [O.extract_secret_share(G, ebox, x, rng.randrange(1, order)) for x in ek]
+    enc = lambda pts: b"".join(G.element_to_bytes(p) for p in pts)
+    sc = lambda ks: b"".join(G.scalar_to_bytes(k) for k in ks)
+    eargs = (enc(epk), enc([e["share"] for e in proofs]), enc([ebox["shares"][G.element_to_bytes(p)] for p in epk]),
+             sc([e["challenge"] for e in proofs]), sc([e["response"] for e in proofs]))
+
+    def ec_shares():
+        assert engine.ec_verify_shares_compute(gid, *eargs) == 6
+        assert list(engine.ec_verify_shares_absorb(6)) == [1] * 6
+    assert added(ec_shares) == (0, False)
