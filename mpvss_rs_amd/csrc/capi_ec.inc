@@ -234,80 +234,131 @@ int ec_dual(mpvss_ctx* ctx, const EcInfo* gi, const EcBase& b1, const uint8_t* k
   return 0;
 }
 
-// X_i for n shares: encodings into dX and, when the forward-difference path runs, internal points in w.pts.
-//   hpos != null : positions known to the host, the choice is made here           -> *gate_out = null
-//   hpos == null : positions are device-resident; a kernel checks them and a device flag (w.flags[0]) gates the two
-//                  paths (no host synchronisation)                                 -> *gate_out = the flag
-// *pts_out = w.pts when the internal points may be valid (always valid if *gate_out == null), else null.
-// MPVSS_EC_FD=0 disables the path.
-int ec_eval_x(mpvss_ctx* ctx, const EcInfo* gi, EcWork& w, size_t t, const int64_t* hpos, const int64_t* dpos, size_t n,
-              uint8_t* dX, const int** gate_out, const uint32_t** pts_out) {
+// may the forward differences serve a curve box of this shape?  MPVSS_EC_FD=0 disables the path.
+bool ec_fd_shape(size_t n, size_t t) {
   static const int fd_on = fd_env("MPVSS_EC_FD", 1);
+  return fd_on && t >= 16 && t <= 256 && n >= 16 * t && n >= 4096;
+}
+
+// S strided chains of chain_len members cover a box's n positions; each chain's t seeds start at member w0 and it steps both ways
+struct EcFdGeometry {
+  int S, chain_len, w0;
+  size_t state_words;       // difference tables of a box: forward and backward per chain, and those of the two-level seeding
+};
+EcFdGeometry ec_fd_geometry(int group, size_t n, size_t t) {
+  EcFdGeometry g;
+  g.S = std::max((int)(4096 / t), 4);
+  const int s_max = (int)(n / (4 * t));
+  if (g.S > s_max) g.S = s_max;
+  if (g.S < 1) g.S = 1;
+  g.chain_len = (int)((n + g.S - 1) / g.S);
+  g.w0 = (g.chain_len - (int)t) / 2;
+  g.state_words = ((size_t)2 * g.S * t + 2 * t) * (size_t)ec_point_words(group);
+  return g;
+}
+
+// What the forward-difference X path of B boxes of one shape works on: box b at b * its stride of every array (sized by the caller
+// from ec_fd_geometry; no stride matters when B = 1).  hand / wtab: the optional buffers of the quad-lane pipelines, sized here.
+struct EcFdBoxes {
+  const uint32_t* cm;       // decoded commitments
+  const int64_t* pos;
+  uint32_t* pts;            // out: internal points
+  uint32_t* state;
+  uint8_t* xenc;            // out: encodings
+  int* flags;               // the boxes' gates
+  const int* ones;          // B ones in PINNED memory: the gates are initialised by an asynchronous copy
+  DevBuf &hand, &wtab;
+  size_t cm_stride, pos_stride, pts_stride, state_stride, enc_stride;
+};
+
+// X of B boxes of one shape (n, t; ec_fd_shape holds) by forward differences on stream s, ONE sequence of launches with the box as
+// the second grid dimension.
+//   device_positions : nobody has looked at the positions: a kernel checks each box's and clears its gate unless they are consecutive
+//   may_quad         : the caller's part of the MPVSS_EC_FD_QUAD = 1 condition (the chip is the boxes' own)
+//   two_level        : the caller's reading of MPVSS_EC_FD_L1
+//   timed            : the launches are spans of ctx's timing (s must be ctx->stream then), else plain launches
+// *gate_out = the gates (box b: + b) when the boxes have them -- then Horner's rule has filled in for every box whose gate
+// was cleared -- or null: the forward differences ran unconditionally.
+#define EC_X_LAUNCH(call)                           \
+  do {                                              \
+    if (timed) TIMED_LAUNCH(ctx, 0, call);          \
+    else LAUNCHCHK(ctx, call);                      \
+  } while (0)
+int ec_fd_x(mpvss_ctx* ctx, const EcInfo* gi, const EcFdBoxes& bx, size_t B, size_t n, size_t t, const EcFdGeometry& g,
+            bool device_positions, bool may_quad, bool two_level, hipStream_t s, bool timed, const int** gate_out) {
   constexpr int split_seeds = 1;     // every seed evaluated by 8 lanes (shorter latency)
   const int group = gi->group;
-  *gate_out = nullptr;
-  *pts_out = nullptr;
-  bool fd = fd_on && t >= 16 && t <= 256 && n >= 16 * t && n >= 4096;
-  if (fd && hpos != nullptr) {
-    fd = hpos[0] >= 0 && hpos[0] < ((int64_t)1 << 61);
-    for (size_t i = 1; i < n && fd; ++i) fd = hpos[i] == hpos[0] + (int64_t)i;
-  }
-  if (!fd) {
-    TIMED_LAUNCH(ctx, 0, ec_launch_commit_eval(group, (const uint32_t*)w.cm.p, (int)t, dpos, (int)n, dX, nullptr, 0, ctx->stream));
-    return 0;
-  }
-  // A call that has the chip to itself steps through pipelines of quad-lane stages (ec_quad.h): a third of the latency per step.
-  // MPVSS_EC_FD_QUAD: 0 never, 1 when no other block is in flight, 2 always; the pipeline may give up, so it always has a gate.
+  const size_t pw = (size_t)ec_point_words(group);
+  // Boxes that have the chip to themselves step through pipelines of quad-lane stages (ec_quad.h): a third of the latency per step.
+  // MPVSS_EC_FD_QUAD: 0 never, 1 when the caller allows it, 2 always; the pipeline may give up, so it always has a gate.
   static const int quad_mode = fd_env("MPVSS_EC_FD_QUAD", 1), quad_fault = fd_env("MPVSS_EC_FD_TEST_FAULT", 0);
   constexpr int quad_seeds = 1;     // its seed kernel: 16 lanes per seed, windowed x^lo
   constexpr int quad_table = 1;     // its difference tables by the same pipeline
   constexpr int quad_oct = 0;       // (secp256k1 with eight lanes per point was built, exact and 4 % slower: profiles/r04_ec_quad_isa.txt)
-  const bool quad = quad_mode >= 2 || (quad_mode == 1 && !ctx->busy_with_others());
+  const bool quad = quad_mode >= 2 || (quad_mode == 1 && may_quad);
   const int* gate = nullptr;
-  if (hpos == nullptr || quad) {       // decide on the device / a flag the stepping pipeline can clear
-    RET_IF(ensure(ctx, w.flags, 64));
-    int* flag = (int*)w.flags.p;
-    ctx->w->root[0].one = 1;     // pinned constant of the current workspace: the copy is asynchronous
-    HIPCHK(ctx, hipMemcpyAsync(flag, &ctx->w->root[0].one, 4, hipMemcpyHostToDevice, ctx->stream));
-    if (hpos == nullptr) LAUNCHCHK(ctx, modp_launch_fd_check_positions(dpos, (int)n, flag, ctx->stream));
-    gate = flag;
+  if (device_positions || quad) {       // every box decides for itself on the device / a flag the stepping pipeline can clear
+    HIPCHK(ctx, hipMemcpyAsync(bx.flags, bx.ones, B * 4, hipMemcpyHostToDevice, s));
+    if (device_positions)
+      for (size_t b = 0; b < B; ++b)
+        LAUNCHCHK(ctx, modp_launch_fd_check_positions(bx.pos + b * bx.pos_stride, (int)n, bx.flags + b, s));
+    gate = bx.flags;
   }
-  int S = std::max((int)(4096 / t), 4);
-  const int s_max = (int)(n / (4 * t));
-  if (S > s_max) S = s_max;
-  if (S < 1) S = 1;
-  const int chain_len = (int)((n + S - 1) / S);
-  const int w0 = (chain_len - (int)t) / 2;
-  const size_t pw = (size_t)ec_point_words(group);
-  RET_IF(ensure(ctx, w.pts, n * pw * 4));
+  EcQuadStepping qs{nullptr, 0, bx.flags, quad_fault};
+  bool use_quad = quad;       // (its hand-over space is a few hundred MB: without it the one-workgroup-per-chain kernels run)
+  if (use_quad) {
+    qs.oct = quad_oct;
+    qs.hand_box_words = ec_fd_quad_hand_words(group, quad_oct, (int)t, g.S, g.w0, g.chain_len);
+    // (a chain of n / S members keeps every handed point: 160 B x 15 x 2 S x its steps -- 177 MB at n = 65536, 2.8 GB at 2^20; beyond
+    // 4 GB the chain kernels run)
+    if (B * qs.hand_box_words * 4 > ((size_t)4 << 30) || !try_ensure(ctx, bx.hand, B * qs.hand_box_words * 4)) use_quad = false;
+    qs.hand = (uint32_t*)bx.hand.p;
+    if (use_quad && quad_seeds) {
+      qs.wtab_box_words = ec_fd_seed_tab_words(group, two_level ? (int)t : g.S * (int)t);
+      if (try_ensure(ctx, bx.wtab, B * qs.wtab_box_words * 4)) qs.wtab = (uint32_t*)bx.wtab.p;
+    }
+    qs.table = quad_table;
+  }
+  uint32_t* st = bx.state;
+  EC_X_LAUNCH(ec_launch_fd_boxes_q(group, bx.cm, (int)t, bx.pos, (int)n, g.S, g.w0, g.chain_len, bx.pts, st, st + (size_t)g.S * t * pw,
+                                   two_level ? st + (size_t)2 * g.S * t * pw : nullptr, bx.xenc, split_seeds, gate, (int)B, bx.cm_stride,
+                                   bx.pos_stride, bx.pts_stride, bx.state_stride, bx.enc_stride, use_quad ? &qs : nullptr, s));
+  if (gate != nullptr)         // fallback per box: Horner's rule when its positions are not consecutive (or its pipeline gave up)
+    EC_X_LAUNCH(ec_launch_commit_eval_boxes(group, bx.cm, (int)t, bx.pos, (int)n, bx.xenc, gate, 0, (int)B, bx.cm_stride, bx.pos_stride,
+                                            bx.enc_stride, s));
+  *gate_out = gate;
+  return 0;
+}
+#undef EC_X_LAUNCH
+
+// X_i for n shares: encodings into dX and, when the forward-difference path runs, internal points in w.pts.
+//   hpos != null : positions known to the host, the choice is made here           -> *gate_out = null unless the quad pipeline runs
+//   hpos == null : positions are device-resident; a kernel checks them and a device flag (w.flags[0]) gates the two
+//                  paths (no host synchronisation)                                 -> *gate_out = the flag
+// *pts_out = w.pts when the internal points may be valid (always valid if *gate_out == null), else null.
+int ec_eval_x(mpvss_ctx* ctx, const EcInfo* gi, EcWork& w, size_t t, const int64_t* hpos, const int64_t* dpos, size_t n,
+              uint8_t* dX, const int** gate_out, const uint32_t** pts_out) {
+  const int group = gi->group;
+  *gate_out = nullptr;
+  *pts_out = nullptr;
+  if (!ec_fd_shape(n, t) || (hpos != nullptr && !positions_consecutive(hpos, n))) {
+    TIMED_LAUNCH(ctx, 0, ec_launch_commit_eval(group, (const uint32_t*)w.cm.p, (int)t, dpos, (int)n, dX, nullptr, 0, ctx->stream));
+    return 0;
+  }
+  const EcFdGeometry g = ec_fd_geometry(group, n, t);
+  RET_IF(ensure(ctx, w.flags, 64));
+  RET_IF(ensure(ctx, w.pts, n * (size_t)ec_point_words(group) * 4));
+  RET_IF(ensure(ctx, w.fdst, g.state_words * 4));
   // Two-level seeding (Horner for t seeds only, the others by a stride-1 chain) removes 37 % of a box's instructions but
   // adds a serial chain to its latency (X path 24 -> 39 ms for a lone secp256k1 box): worth it when other blocks keep the
   // chip busy, not for a call that has the GPU to itself.  MPVSS_EC_FD_L1: 0 never, 1 when blocks are in flight, 2 always.
   static const int l1_mode = fd_env("MPVSS_EC_FD_L1", 1);
   const bool two_level = l1_mode >= 2 || (l1_mode == 1 && ctx->busy_with_others());
-  RET_IF(ensure(ctx, w.fdst, ((size_t)2 * S * t + 2 * t) * pw * 4));
-  uint32_t* st = (uint32_t*)w.fdst.p;
-  EcQuadStepping qs{nullptr, 0, (int*)gate, quad_fault};
-  bool use_quad = quad;       // (its hand-over space is a few hundred MB: without it the one-workgroup-per-chain kernels run)
-  if (use_quad) {
-    qs.oct = quad_oct;
-    qs.hand_box_words = ec_fd_quad_hand_words(group, quad_oct, (int)t, S, w0, chain_len);
-    // (a chain of n / S members keeps every handed point: 160 B x 15 x 2 S x its steps -- 177 MB at n = 65536, 2.8 GB at 2^20; beyond
-    // 4 GB the chain kernels run)
-    if (qs.hand_box_words * 4 > ((size_t)4 << 30) || !try_ensure(ctx, w.hand, qs.hand_box_words * 4)) use_quad = false;
-    qs.hand = (uint32_t*)w.hand.p;
-    if (use_quad && quad_seeds) {
-      qs.wtab_box_words = ec_fd_seed_tab_words(group, two_level ? (int)t : S * (int)t);
-      if (try_ensure(ctx, w.wtab, qs.wtab_box_words * 4)) qs.wtab = (uint32_t*)w.wtab.p;
-    }
-    qs.table = quad_table;
-  }
-  TIMED_LAUNCH(ctx, 0, ec_launch_fd_boxes_q(group, (const uint32_t*)w.cm.p, (int)t, dpos, (int)n, S, w0, chain_len, (uint32_t*)w.pts.p,
-                                            st, st + (size_t)S * t * pw, two_level ? st + (size_t)2 * S * t * pw : nullptr, dX,
-                                            split_seeds, gate, 1, 0, 0, 0, 0, 0, use_quad ? &qs : nullptr, ctx->stream));
-  if (gate != nullptr)         // fallback: Horner's rule when the positions are not consecutive
-    TIMED_LAUNCH(ctx, 0, ec_launch_commit_eval(group, (const uint32_t*)w.cm.p, (int)t, dpos, (int)n, dX, gate, 0, ctx->stream));
-  *gate_out = gate;
+  ctx->w->root[0].one = 1;     // pinned constant of the current workspace: the gate's copy is asynchronous
+  const EcFdBoxes bx{(const uint32_t*)w.cm.p, dpos, (uint32_t*)w.pts.p, (uint32_t*)w.fdst.p, dX, (int*)w.flags.p, &ctx->w->root[0].one,
+                     w.hand, w.wtab, 0, 0, 0, 0, 0};
+  // (the quad pipelines: a call that has the chip to itself, no other block in flight)
+  RET_IF(ec_fd_x(ctx, gi, bx, 1, n, t, g, hpos == nullptr, !ctx->busy_with_others(), two_level, ctx->stream, true, gate_out));
   *pts_out = (const uint32_t*)w.pts.p;
   return 0;
 }
@@ -508,16 +559,9 @@ struct EcPre {
 // may this box's X path join a batch of boxes of shape (n, t)?  (forward differences must apply: the conditions of
 // ec_eval_x; host positions are judged here, device positions by the box's gate on the device)
 bool ec_x_box_batchable(int space, const mpvss_ec_box& bx, size_t n, size_t t) {
-  static const int fd_on = fd_env("MPVSS_EC_FD", 1);
-  if (!fd_on || bx.n != n || bx.t != t || t < 16 || t > 256 || n < 16 * t || n < 4096 || n > 0x7fffffff) return false;
+  if (bx.n != n || bx.t != t || !ec_fd_shape(n, t) || n > 0x7fffffff) return false;
   if (!bx.commitments || !bx.positions) return false;
-  if (space == MPVSS_HOST) {
-    const int64_t* hp = bx.positions;
-    if (hp[0] < 0 || hp[0] >= ((int64_t)1 << 61)) return false;
-    for (size_t i = 1; i < n; ++i)
-      if (hp[i] != hp[0] + (int64_t)i) return false;
-  }
-  return true;
+  return space != MPVSS_HOST || positions_consecutive(bx.positions, n);
 }
 
 // The X paths of B boxes of one shape (same n, t; forward differences apply) by ONE sequence of launches with the box
@@ -527,24 +571,15 @@ bool ec_x_box_batchable(int space, const mpvss_ec_box& bx, size_t n, size_t t) {
 // (the caller then takes the per-box path).
 int ec_x_batch_compute(mpvss_ctx* ctx, const EcInfo* gi, int space, const mpvss_ec_box* bx, size_t B, mpvss_ctx::XBatch& xb,
                        EcPre* pre) {
-  constexpr int split_seeds = 1;
-  static const int two_level = fd_env("MPVSS_EC_FD_L1", 1);
-  // quad-lane stepping pipelines (ec_eval_x) for a batch of one or two boxes with nothing else in flight
-  static const int quad_mode = fd_env("MPVSS_EC_FD_QUAD", 1), quad_fault = fd_env("MPVSS_EC_FD_TEST_FAULT", 0);
-  constexpr int quad_seeds = 1, quad_table = 1, quad_oct = 0;
-  const bool quad = quad_mode >= 2 || (quad_mode == 1 && B <= 2 && !ctx->busy_with_others());
+  static const bool two_level = fd_env("MPVSS_EC_FD_L1", 1) != 0;     // (any setting but 0: a batch does not ask what else is in flight)
+  // quad-lane stepping pipelines (ec_fd_x) for a batch of one or two boxes with nothing else in flight
+  const bool may_quad = B <= 2 && !ctx->busy_with_others();
   const size_t n = bx[0].n, t = bx[0].t, L = gi->enc;
   for (size_t b = 0; b < B; ++b)
     if (!ec_x_box_batchable(space, bx[b], n, t)) return 1;
   const int group = gi->group;
   const size_t pw = (size_t)ec_point_words(group);
-  int S = std::max((int)(4096 / t), 4);
-  const int s_max = (int)(n / (4 * t));
-  if (S > s_max) S = s_max;
-  if (S < 1) S = 1;
-  const int chain_len = (int)((n + S - 1) / S);
-  const int w0 = (chain_len - (int)t) / 2;
-  const size_t state_words = ((size_t)2 * S * t + 2 * t) * pw;
+  const EcFdGeometry g = ec_fd_geometry(group, n, t);
   HIPCHK(ctx, hipSetDevice(ctx->device));
   if (!xb.s) {
     HIPCHK(ctx, hipStreamCreateWithPriority(&xb.s, hipStreamNonBlocking, ctx->prio_high));
@@ -556,7 +591,7 @@ int ec_x_batch_compute(mpvss_ctx* ctx, const EcInfo* gi, int space, const mpvss_
   RET_IF(ensure(ctx, xb.pos, B * n * 8));
   RET_IF(ensure(ctx, xb.pts, B * n * pw * 4));
   RET_IF(ensure(ctx, xb.xenc, B * n * L));
-  RET_IF(ensure(ctx, xb.state, B * state_words * 4));
+  RET_IF(ensure(ctx, xb.state, B * g.state_words * 4));
   RET_IF(ensure(ctx, xb.flags, (B + 16) * 4));
   const size_t pin_need = (B + 16) * 4 + (space == MPVSS_HOST ? B * (t * L + n * 8) : 0);
   if (pin_need > xb.pin_cap) {
@@ -570,8 +605,6 @@ int ec_x_batch_compute(mpvss_ctx* ctx, const EcInfo* gi, int space, const mpvss_
   hipStream_t s = xb.s;
   int* hones = (int*)xb.pin;
   for (size_t b = 0; b < B; ++b) hones[b] = 1;
-  int* flags = (int*)xb.flags.p;
-  const int* gate = nullptr;
   uint8_t* hin = (uint8_t*)xb.pin + (B + 16) * 4;
   for (size_t b = 0; b < B; ++b) {
     uint8_t* dcm = (uint8_t*)xb.cmenc.p + b * t * L;
@@ -588,35 +621,12 @@ int ec_x_batch_compute(mpvss_ctx* ctx, const EcInfo* gi, int space, const mpvss_
       HIPCHK(ctx, hipMemcpyAsync(dpos, bx[b].positions, n * 8, hipMemcpyDeviceToDevice, s));
     }
   }
-  if (space != MPVSS_HOST || quad) {       // device-resident positions: every box decides for itself on the device
-    HIPCHK(ctx, hipMemcpyAsync(flags, hones, B * 4, hipMemcpyHostToDevice, s));
-    if (space != MPVSS_HOST)
-      for (size_t b = 0; b < B; ++b)
-        LAUNCHCHK(ctx, modp_launch_fd_check_positions((const int64_t*)xb.pos.p + b * n, (int)n, flags + b, s));
-    gate = flags;
-  }
-  EcQuadStepping qs{nullptr, 0, flags, quad_fault};
-  bool use_quad = quad;
-  if (use_quad) {
-    qs.oct = quad_oct;
-    qs.hand_box_words = ec_fd_quad_hand_words(group, quad_oct, (int)t, S, w0, chain_len);
-    if (B * qs.hand_box_words * 4 > ((size_t)4 << 30) || !try_ensure(ctx, xb.hand, B * qs.hand_box_words * 4)) use_quad = false;
-    qs.hand = (uint32_t*)xb.hand.p;
-    if (use_quad && quad_seeds) {
-      qs.wtab_box_words = ec_fd_seed_tab_words(group, two_level ? (int)t : S * (int)t);
-      if (try_ensure(ctx, xb.wtab, B * qs.wtab_box_words * 4)) qs.wtab = (uint32_t*)xb.wtab.p;
-    }
-    qs.table = quad_table;
-  }
   LAUNCHCHK(ctx, ec_launch_decode(group, (const uint8_t*)xb.cmenc.p, (int)(B * t), (uint32_t*)xb.cm.p, (uint8_t*)xb.okcm.p, s));
-  uint32_t* st = (uint32_t*)xb.state.p;
-  LAUNCHCHK(ctx, ec_launch_fd_boxes_q(group, (const uint32_t*)xb.cm.p, (int)t, (const int64_t*)xb.pos.p, (int)n, S, w0, chain_len,
-                                      (uint32_t*)xb.pts.p, st, st + (size_t)S * t * pw, two_level ? st + (size_t)2 * S * t * pw : nullptr,
-                                      (uint8_t*)xb.xenc.p, split_seeds, gate, (int)B, t * pw, n, n * pw, state_words, n * L,
-                                      use_quad ? &qs : nullptr, s));
-  if (gate != nullptr)             // fallback per box: Horner's rule when its positions are not consecutive
-    LAUNCHCHK(ctx, ec_launch_commit_eval_boxes(group, (const uint32_t*)xb.cm.p, (int)t, (const int64_t*)xb.pos.p, (int)n,
-                                               (uint8_t*)xb.xenc.p, gate, 0, (int)B, t * pw, n, n * L, s));
+  const EcFdBoxes fb{(const uint32_t*)xb.cm.p, (const int64_t*)xb.pos.p, (uint32_t*)xb.pts.p, (uint32_t*)xb.state.p, (uint8_t*)xb.xenc.p,
+                     (int*)xb.flags.p, hones, xb.hand, xb.wtab, t * pw, n, n * pw, g.state_words, n * L};
+  const int* gate;
+  // (plain launches: the timing spans belong to the context's stream, not to this one)
+  RET_IF(ec_fd_x(ctx, gi, fb, B, n, t, g, space != MPVSS_HOST, may_quad, two_level, s, false, &gate));
   HIPCHK(ctx, hipEventRecord(xb.done, s));
   for (size_t b = 0; b < B; ++b)
     pre[b] = EcPre{(const uint8_t*)xb.xenc.p + b * n * L, (const uint32_t*)xb.pts.p + b * n * pw, gate ? gate + b : nullptr,
@@ -688,21 +698,15 @@ int ec_verify_block_compute_locked(mpvss_ctx* ctx, int group, int space, const u
   RET_IF(ensure(ctx, w.p2, pts_bytes));
   RET_IF(ensure(ctx, w.pg, pts_bytes));      // the generator half of a split a1: sized here, not under the fork (ensure() may free and synchronise)
   uint8_t *dX = (uint8_t*)w.x.p, *d1 = (uint8_t*)w.o1.p, *d2 = (uint8_t*)w.o2.p;
-  struct Swap {
-    mpvss_ctx* c; hipStream_t a;
-    Swap(mpvss_ctx* c_, hipStream_t s) : c(c_), a(c_->stream) { c->stream = s; }
-    ~Swap() { c->stream = a; }
-  };
   // a2 = r*y + c*Y does not depend on X: it runs beside the X path on the slot's low-priority stream   (dleq.rs:79-81)
   // (keeping a block to one stream once several are in flight was measured slower: 5.2 against 6.3 M share verifications/s for
   // secp256k1, profiles/r02_ec_streams_ab.txt)
   // a block that has the chip to itself: the generator half of a1 = r G + c X runs beside the X path
   const bool split_a1 = !ctx->busy_with_others();
   hipStream_t side = sl.work.sb;
-  HIPCHK(ctx, hipEventRecord(sl.work.ev_fork, ctx->stream));
-  HIPCHK(ctx, hipStreamWaitEvent(side, sl.work.ev_fork, 0));
+  RET_IF(fork_side_stream(ctx, sl.work.ev_fork, side));
   {
-    Swap sw(ctx, side);
+    SwapStream sw(ctx, side);
     EcBase by, bY;
     by.enc = (const uint8_t*)dy; by.enc_stride = L;
     bY.enc = (const uint8_t*)dY; bY.enc_stride = L;

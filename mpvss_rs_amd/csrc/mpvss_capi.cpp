@@ -953,7 +953,7 @@ extern "C" int mpvss_modp_batch_exp(mpvss_ctx* ctx, int space, const uint8_t* ba
 }
 
 namespace {
-int pair_mask();     // which kernels take the pair layout (defined with the DLEQ launchers below)
+int launch_comb_exp(mpvss_ctx* ctx, const uint32_t* comb, const uint8_t* e, size_t cnt, uint8_t* out);     // (with the DLEQ launchers below)
 }
 extern "C" int mpvss_modp_batch_exp_fixed_base(mpvss_ctx* ctx, int space, const uint8_t* base_host,
                                                const uint8_t* exps, size_t n, uint8_t* out) {
@@ -978,12 +978,8 @@ extern "C" int mpvss_modp_batch_exp_fixed_base(mpvss_ctx* ctx, int space, const 
       RET_IF(ensure(ctx, ctx->w->out1, cnt * EB));
       dout = (uint8_t*)ctx->w->out1.p;
     }
-    if (cg && (pair_mask() & 1) && cnt >= 64 && comb_bits_of(ctx, cg) == 16)      // batch keygen, commitments C_j = g^a_j: 128 products on the pair layout
-      TIMED_LAUNCH(ctx, 1, modp_launch_comb16_twin_exp_pair(cg, (const uint8_t*)de, nullptr, (int)cnt, dout, nullptr, ctx->consts,
-                                                            ctx->pair_tables, ctx->stream));
-    else if (cg)
-      TIMED_LAUNCH(ctx, 1, modp_launch_comb_dual_exp(cg, cg, 0, (const uint8_t*)de, (const uint8_t*)de, EB, 0, (int)cnt,
-                                                     dout, comb_bits_of(ctx, cg), ctx->consts, ctx->stream));
+    if (cg)
+      RET_IF(launch_comb_exp(ctx, cg, (const uint8_t*)de, cnt, dout));
     else
       RET_IF(dual_exp_any(ctx, tg, 0, tg, 0, (const uint8_t*)de, (const uint8_t*)de, EB, 0, cnt, dout));
     if (space == MPVSS_HOST) RET_IF(copy_out(ctx, space, out + off * EB, dout, cnt * EB));
@@ -1051,17 +1047,35 @@ void invert_root_on_host(void* p) {
   job->ok = hostq::batch_invert(*field, job->in_be, 1, job->out_be) ? 1 : 0;
 }
 
+// is every one of the n 256-byte numbers at y a unit mod q?  (0 and q are the encodings of 0 mod q an input can carry)
+bool all_units_mod_q(const uint8_t* y, size_t n) {
+  static const struct Q {
+    uint8_t be[EB];
+    Q() { modq_modulus_bytes(be); }
+  } q;                                     // assembled once
+  static const uint8_t zero[EB] = {0};
+  for (size_t i = 0; i < n; ++i)
+    if (memcmp(y + i * EB, zero, EB) == 0 || memcmp(y + i * EB, q.be, EB) == 0) return false;
+  return true;
+}
+
+// are the n positions consecutive from a start in [0, 2^61)?  (what the forward differences of either group family step through;
+// n == 0: no)
+bool positions_consecutive(const int64_t* hpos, size_t n) {
+  if (n == 0 || hpos[0] < 0 || hpos[0] >= ((int64_t)1 << 61)) return false;
+  for (size_t i = 1; i < n; ++i)
+    if (hpos[i] != hpos[0] + (int64_t)i) return false;
+  return true;
+}
+
 // does the forward-difference path apply to this run of shares?  (host-side part of the decision)
 bool fd_applies(size_t t, const int64_t* hpos, size_t cnt) {
   static const int fd_on = fd_env("MPVSS_FD", 1);
   static const size_t min_shares = (size_t)fd_env("MPVSS_FD_MIN_SHARES", 4096);
   constexpr size_t max_t = 1024;
   bool fd = fd_on && t >= 16 && t <= max_t && cnt >= 16 * t && cnt >= min_shares;
-  if (fd && hpos) {                       // host positions: decide here; device positions are checked by a kernel
-    for (size_t i = 0; i < cnt && fd; ++i) fd = hpos[i] == hpos[0] + (int64_t)i;
-    fd = fd && hpos[0] >= 0 && hpos[0] < ((int64_t)1 << 61);
-  }
-  return fd;
+  // host positions: decide here; device positions are checked by a kernel
+  return fd && (hpos == nullptr || positions_consecutive(hpos, cnt));
 }
 
 // boxes > 1: a GROUP of same-shaped boxes in one set of launches -- box b has its commitments at w.cm + b * t rows, its `cnt`
@@ -1359,6 +1373,49 @@ int launch_twin_exp(mpvss_ctx* ctx, const uint8_t* base, const uint8_t* e1, cons
   return modp_launch_twin_exp(base, e1, e2, (int)cnt, buckets, occupancy, out1, out2, ctx->consts, ctx->stream);
 }
 
+// does a power through this generator's comb take the pair layout?  (the 16-bit comb, from 64 numbers)
+bool comb_takes_pair(mpvss_ctx* ctx, const uint32_t* comb, size_t cnt) {
+  return (pair_mask() & 1) && cnt >= 64 && comb_bits_of(ctx, comb) == 16;
+}
+
+// out = B^e (big-endian) for `cnt` exponents, B a generator with comb table `comb`: batch keygen and commitments C_j = g^a_j,
+// a1 = G^w of extract_secret_share.  128 products on the pair layout, else the dual form with the same exponent twice.
+int launch_comb_exp(mpvss_ctx* ctx, const uint32_t* comb, const uint8_t* e, size_t cnt, uint8_t* out) {
+  if (comb_takes_pair(ctx, comb, cnt))
+    TIMED_LAUNCH(ctx, 1, modp_launch_comb16_twin_exp_pair(comb, e, nullptr, (int)cnt, out, nullptr, ctx->consts, ctx->pair_tables,
+                                                          ctx->stream));
+  else
+    TIMED_LAUNCH(ctx, 1, modp_launch_comb_dual_exp(comb, comb, 0, e, e, EB, 0, (int)cnt, out, comb_bits_of(ctx, comb), ctx->consts,
+                                                   ctx->stream));
+  return 0;
+}
+
+// gr_m = g^r in Montgomery form (the first factor of a1 = g^r X^c) through g's comb; `pair`: the caller wants the pair layout
+// (its policy: the lone or keyed block and the group differ), taken when the comb is the 16-bit one
+int launch_comb_gr_mont(mpvss_ctx* ctx, const uint32_t* cg, bool pair, const uint8_t* r_dev, const uint8_t* c_dev, size_t cnt,
+                        uint32_t* gr_m) {
+  if (pair && comb_bits_of(ctx, cg) == 16)
+    TIMED_LAUNCH(ctx, 1, modp_launch_comb16_exp_pair(cg, r_dev, (int)cnt, gr_m, ctx->consts, ctx->pair_tables, ctx->stream));
+  else
+    TIMED_LAUNCH(ctx, 1, modp_launch_comb_dual_exp_split(cg, cg, 0, r_dev, c_dev, 0, 0, (int)cnt, nullptr, 1, gr_m,
+                                                         comb_bits_of(ctx, cg), ctx->consts, ctx->stream));
+  return 0;
+}
+
+// A side stream beside ctx->stream.  Fork: what the side stream runs from here on starts after everything enqueued on ctx->stream
+// so far.  The work itself goes through the launchers, which all enqueue on ctx->stream: SwapStream makes the side stream that for
+// a scope (restored on every early return of RET_IF / HIPCHK / TIMED_LAUNCH); the scope records the caller's join event(s).
+int fork_side_stream(mpvss_ctx* ctx, hipEvent_t ev_fork, hipStream_t side) {
+  HIPCHK(ctx, hipEventRecord(ev_fork, ctx->stream));
+  HIPCHK(ctx, hipStreamWaitEvent(side, ev_fork, 0));
+  return 0;
+}
+struct SwapStream {
+  mpvss_ctx* c; hipStream_t a;
+  SwapStream(mpvss_ctx* c_, hipStream_t s) : c(c_), a(c_->stream) { c->stream = s; }
+  ~SwapStream() { c->stream = a; }
+};
+
 // a = B1^r * B2^c for `cnt` shares.  tab_b1: shared table (stride 0) or nullptr -> per-number tables
 // from b1_dev.  c: device pointer, stride c_stride (0 shared).
 int dleq_side(mpvss_ctx* ctx, const uint32_t* shared_b1, const uint8_t* b1_dev, const uint8_t* b2_dev,
@@ -1368,7 +1425,7 @@ int dleq_side(mpvss_ctx* ctx, const uint32_t* shared_b1, const uint8_t* b1_dev, 
   size_t s1 = TABW;
   RET_IF(number_tables(ctx, b2_dev, cnt, t2buf ? *t2buf : ctx->w->tab2, &t2));
   if (comb_b1) {   // B1 is a generator with a comb table: no squarings for B1^r
-    if ((pair_mask() & 1) && c_windows == 64 && cnt >= 64 && comb_bits_of(ctx, comb_b1) == 16) {
+    if (c_windows == 64 && comb_takes_pair(ctx, comb_b1, cnt)) {
       // (verify_share's a1 = G^r pk^c: 45 K instead of 75 K issue slots per share on the pair layout)
       TIMED_LAUNCH(ctx, 1, modp_launch_comb16_dual_exp_pair(comb_b1, t2, r_dev, c_dev, c_stride, (int)cnt, out_dev, ctx->consts,
                                                             ctx->pair_tables, ctx->stream));
@@ -1800,11 +1857,6 @@ int verify_block_compute_locked(mpvss_ctx* ctx, int space, const uint8_t* commit
     uint8_t* da2 = (uint8_t*)ctx->w->out2.p;
     sl.work.fd_used = false;
     const int64_t* hp = space == MPVSS_HOST ? hpos + off : nullptr;
-    struct Swap {
-      mpvss_ctx* c; hipStream_t a;
-      Swap(mpvss_ctx* c_, hipStream_t s) : c(c_), a(c_->stream) { c->stream = s; }
-      ~Swap() { c->stream = a; }
-    };
     // A one-box call of up to ROW_MAX_NUMBERS shares (BASELINE config C2 and everything the reference's tests and examples use) is the
     // latency of its chains, not work: Horner for every share ((t - 1) x 26 operations on the row layout) is shorter than the
     // forward-difference pipeline's seeds + inversion + tables + stepping, and a2 takes the row layout too -- C2: 35.5 -> 17 ms per call.
@@ -1821,8 +1873,7 @@ int verify_block_compute_locked(mpvss_ctx* ctx, int space, const uint8_t* commit
       RET_IF(ensure(ctx, ctx->w->tab3, cnt * TABW * 4));
       RET_IF(ensure(ctx, ctx->w->gr_m, cnt * MODP_L * 4));
       const bool use_keys = ks && c_windows == 64;
-      HIPCHK(ctx, hipEventRecord(ctx->w->ev_fork, ctx->stream));
-      HIPCHK(ctx, hipStreamWaitEvent(ctx->w->sb, ctx->w->ev_fork, 0));
+      RET_IF(fork_side_stream(ctx, ctx->w->ev_fork, ctx->w->sb));
       // Boxes in flight share the chip equally: eight boxes enqueued together finish together (a convoy).  What that
       // costs is the host's turn-around at the end of a convoy, and the cure that works is to enqueue the next box as
       // soon as a box's GPU work is done instead of after its transcript is hashed (run_box_pipeline: 0.90-0.93 -> 0.97 M
@@ -1848,7 +1899,7 @@ int verify_block_compute_locked(mpvss_ctx* ctx, int space, const uint8_t* commit
       const bool pair_gr = (pair_mask() & 4) || short_tail;
       const bool pair_a1 = (pair_mask() & 8) || short_tail;
       {
-        Swap sw(ctx, ctx->w->sb);      // the box's own low-priority stream: the boxes in flight share the chip
+        SwapStream sw(ctx, ctx->w->sb);      // the box's own low-priority stream: the boxes in flight share the chip
         // the schedule travels on THIS stream, ahead of a2; the a1 launch on the other stream waits for ev_gr, recorded below
         if (dsched)
           HIPCHK(ctx, hipMemcpyAsync(ctx->w->csched.p, sl.work.root[0].csched, (1 + 2 * (size_t)sl.work.root[0].csched[0]) * 2,
@@ -1879,13 +1930,7 @@ int verify_block_compute_locked(mpvss_ctx* ctx, int space, const uint8_t* commit
         }
         HIPCHK(ctx, hipEventRecord(ctx->w->ev_a2, ctx->stream));
         // g^r_i needs only the responses: it runs behind a2 instead of after the stepping phase
-        if (pair_gr && comb_bits_of(ctx, cg) == 16)
-          TIMED_LAUNCH(ctx, 1, modp_launch_comb16_exp_pair(cg, (const uint8_t*)dr, (int)cnt, (uint32_t*)ctx->w->gr_m.p, ctx->consts,
-                                                           ctx->pair_tables, ctx->stream));
-        else
-          TIMED_LAUNCH(ctx, 1, modp_launch_comb_dual_exp_split(cg, cg, 0, (const uint8_t*)dr, (const uint8_t*)dchal, 0, 0,
-                                                               (int)cnt, nullptr, 1, (uint32_t*)ctx->w->gr_m.p, comb_bits_of(ctx, cg), ctx->consts,
-                                                               ctx->stream));
+        RET_IF(launch_comb_gr_mont(ctx, cg, pair_gr, (const uint8_t*)dr, (const uint8_t*)dchal, cnt, (uint32_t*)ctx->w->gr_m.p));
         HIPCHK(ctx, hipEventRecord(ctx->w->ev_gr, ctx->stream));
       }
       mark(2);
@@ -1920,10 +1965,9 @@ int verify_block_compute_locked(mpvss_ctx* ctx, int space, const uint8_t* commit
       // A small box, or positions that are not consecutive: a2_i = y_i^r_i * Y_i^c (dleq.rs:79-81) needs nothing of X -- it runs on
       // the slot's second stream beside X_i (participant.rs:423-434) and a1_i = g^r_i * X_i^c (dleq.rs:75-77; X's table in tab3: a2
       // holds tab1 and tab2).  A box of 16 shares: 20.7 -> 7.8 ms per call (profiles/r06_small_box_latency.txt).
-      HIPCHK(ctx, hipEventRecord(ctx->w->ev_fork, ctx->stream));
-      HIPCHK(ctx, hipStreamWaitEvent(ctx->w->sb, ctx->w->ev_fork, 0));
+      RET_IF(fork_side_stream(ctx, ctx->w->ev_fork, ctx->w->sb));
       {
-        Swap sw(ctx, ctx->w->sb);
+        SwapStream sw(ctx, ctx->w->sb);
         RET_IF(dleq_side(ctx, nullptr, (const uint8_t*)dy, (const uint8_t*)dY, (const uint8_t*)dr, (const uint8_t*)dchal,
                          0, c_windows, cnt, da2));
         HIPCHK(ctx, hipEventRecord(ctx->w->ev_a2, ctx->stream));
@@ -2066,15 +2110,9 @@ int verify_group_compute_locked(mpvss_ctx* ctx, int space, const mpvss_modp_box*
   const uint32_t* cg;
   RET_IF(comb_table(ctx, 0, &cg, N));
   uint8_t *dX = (uint8_t*)w.xbe.p, *da1 = (uint8_t*)w.out1.p, *da2 = (uint8_t*)w.out2.p;
-  struct Swap {
-    mpvss_ctx* c; hipStream_t a;
-    Swap(mpvss_ctx* c_, hipStream_t s) : c(c_), a(c_->stream) { c->stream = s; }
-    ~Swap() { c->stream = a; }
-  };
-  HIPCHK(ctx, hipEventRecord(w.ev_fork, ctx->stream));
-  HIPCHK(ctx, hipStreamWaitEvent(w.sb, w.ev_fork, 0));
+  RET_IF(fork_side_stream(ctx, w.ev_fork, w.sb));
   {
-    Swap sw(ctx, w.sb);      // a2 = y^r Y^c and g^r beside the X path, as in a lone block
+    SwapStream sw(ctx, w.sb);      // a2 = y^r Y^c and g^r beside the X path, as in a lone block
     uint32_t *t1p = (uint32_t*)w.tab1.p, *t2p = (uint32_t*)w.tab2.p;
     TIMED_LAUNCH(ctx, 2, modp_launch_build_table(dY, (int)N, t2p, ctx->consts, ctx->stream));
     // a small group with (almost) nothing else in flight -- a short run of tiny boxes -- is the latency of one chain: the row layout
@@ -2086,11 +2124,7 @@ int verify_group_compute_locked(mpvss_ctx* ctx, int space, const mpvss_modp_box*
       TIMED_LAUNCH(ctx, 3, launch_dual_exp_w6(ctx, t1p, t2p, dr, dchal, EB, nullptr, N, da2));
     }
     HIPCHK(ctx, hipEventRecord(w.ev_a2, ctx->stream));
-    if ((pair_mask() & 4) && comb_bits_of(ctx, cg) == 16)
-      TIMED_LAUNCH(ctx, 1, modp_launch_comb16_exp_pair(cg, dr, (int)N, (uint32_t*)w.gr_m.p, ctx->consts, ctx->pair_tables, ctx->stream));
-    else
-      TIMED_LAUNCH(ctx, 1, modp_launch_comb_dual_exp_split(cg, cg, 0, dr, dchal, 0, 0, (int)N, nullptr, 1, (uint32_t*)w.gr_m.p,
-                                                           comb_bits_of(ctx, cg), ctx->consts, ctx->stream));
+    RET_IF(launch_comb_gr_mont(ctx, cg, (pair_mask() & 4) != 0, dr, dchal, N, (uint32_t*)w.gr_m.p));
     HIPCHK(ctx, hipEventRecord(w.ev_gr, ctx->stream));
   }
   RET_IF(eval_x(ctx, t, dpos, nullptr, n, dX, B, n));
@@ -3013,15 +3047,9 @@ int verify_shares_compute_locked(mpvss_ctx* ctx, int space, const uint8_t* pk, c
     // and K7 gives such a share the verdict 0 whatever a1, a2 are.
     if (ctx->w->sb && cnt <= ROW_MAX_NUMBERS) {
       // a small batch is the latency of its longest chain: a2 (2 620 operations) on the slot's second stream beside a1 (830)
-      struct Swap {
-        mpvss_ctx* c; hipStream_t a;
-        Swap(mpvss_ctx* c_, hipStream_t s) : c(c_), a(c_->stream) { c->stream = s; }
-        ~Swap() { c->stream = a; }
-      };
-      HIPCHK(ctx, hipEventRecord(ctx->w->ev_fork, ctx->stream));
-      HIPCHK(ctx, hipStreamWaitEvent(ctx->w->sb, ctx->w->ev_fork, 0));
+      RET_IF(fork_side_stream(ctx, ctx->w->ev_fork, ctx->w->sb));
       {
-        Swap sw(ctx, ctx->w->sb);
+        SwapStream sw(ctx, ctx->w->sb);
         RET_IF(dleq_side(ctx, nullptr, (const uint8_t*)ds, (const uint8_t*)dy, (const uint8_t*)dr, (const uint8_t*)dc, EB, 64, cnt, da2));
         HIPCHK(ctx, hipEventRecord(ctx->w->ev_a2, ctx->stream));
       }
@@ -3195,15 +3223,9 @@ int distribute_block_compute_locked(mpvss_ctx* ctx, int space, const uint8_t* co
     RET_IF(ensure(ctx, ctx->w->out2, cnt * EB));
     RET_IF(ensure(ctx, ctx->w->tab1, cnt * 4 * TABW * 4));
     uint8_t *dX = (uint8_t*)ctx->w->xbe.p, *dY = (uint8_t*)ctx->w->in_d.p, *da1 = (uint8_t*)ctx->w->out1.p, *da2 = (uint8_t*)ctx->w->out2.p;
-    struct Swap {
-      mpvss_ctx* c; hipStream_t a;
-      Swap(mpvss_ctx* c_, hipStream_t s) : c(c_), a(c_->stream) { c->stream = s; }
-      ~Swap() { c->stream = a; }
-    };
-    HIPCHK(ctx, hipEventRecord(ctx->w->ev_fork, ctx->stream));
-    HIPCHK(ctx, hipStreamWaitEvent(ctx->w->sb, ctx->w->ev_fork, 0));
+    RET_IF(fork_side_stream(ctx, ctx->w->ev_fork, ctx->w->sb));
     {
-      Swap sw(ctx, ctx->w->sb);
+      SwapStream sw(ctx, ctx->w->sb);
       // y-tables once, two exponent sets: Y = y^p (participant.rs:219), a2 = y^w (dleq.rs:213-216)
       uint32_t* ty = (uint32_t*)ctx->w->tab1.p;
       if (ks && (pair_mask() & 1) && cnt >= 64) {
@@ -3227,7 +3249,7 @@ int distribute_block_compute_locked(mpvss_ctx* ctx, int space, const uint8_t* co
     }
     // X = g^P(i) and a1 = g^w through the wide comb in ONE pair-layout launch (122 instead of 191 issue slots per product): 12 dealers
     // to registered keys 1.75 -> 2.00 M shares dealt/s; beside the bucket kernels 1.076 -> 1.110 M (profiles/r06_dealer_comb_ab.txt)
-    const bool pair_combs = (pair_mask() & 1) && cnt >= 64 && !commitments && comb_bits_of(ctx, cg) == 16;
+    const bool pair_combs = !commitments && comb_takes_pair(ctx, cg, cnt);
     if (commitments) {
       const int64_t* dpos;
       const void* d;
@@ -3389,15 +3411,7 @@ extern "C" int mpvss_modp_extract_shares(mpvss_ctx* ctx, int space, const uint8_
     // batch takes the two dependent exponentiations.  Host buffers.  Large batches: the dealer's bucket kernels; up to ROW_MAX_NUMBERS
     // shares (the reference calls extract_secret_share for ONE participant at a time): both powers side by side in one row-layout
     // launch over Y's window table -- the latency of one chain instead of two.
-    bool shared = space == MPVSS_HOST;
-    if (shared) {
-      uint8_t qb[EB];
-      modq_modulus_bytes(qb);
-      static const uint8_t zero[EB] = {0};
-      const uint8_t* hy = y + off * EB;
-      for (size_t i = 0; i < cnt && shared; ++i)
-        shared = memcmp(hy + i * EB, zero, EB) != 0 && memcmp(hy + i * EB, qb, EB) != 0;
-    }
+    const bool shared = space == MPVSS_HOST && all_units_mod_q(y + off * EB, cnt);
     bool a1_done = false;
     if (shared) {
       // e2 = w / x mod (q-1) on the device (the scalar ring's product kernel): no host threads, whatever the host has of them
@@ -3407,19 +3421,12 @@ extern "C" int mpvss_modp_extract_shares(mpvss_ctx* ctx, int space, const uint8_
       LAUNCHCHK(ctx, modq_launch_mul((const uint8_t*)dw, (const uint8_t*)dxi, (int)cnt, de2, ctx->consts_q, ctx->stream));
       if (cnt <= ROW_MAX_NUMBERS && ctx->stream_b) {
         // (a1 = G^w, 511 comb products, on the second stream beside the two powers)
-        HIPCHK(ctx, hipEventRecord(ctx->w->ev_fork, ctx->stream));
-        HIPCHK(ctx, hipStreamWaitEvent(ctx->stream_b, ctx->w->ev_fork, 0));
+        RET_IF(fork_side_stream(ctx, ctx->w->ev_fork, ctx->stream_b));
         {
-          hipStream_t main_stream = ctx->stream;
-          ctx->stream = ctx->stream_b;
-          const int rc1 = [&]() -> int {
-            TIMED_LAUNCH(ctx, 1, modp_launch_comb_dual_exp(cG, cG, 0, (const uint8_t*)dw, (const uint8_t*)dw, EB, 0, (int)cnt, da1,
-                                                           comb_bits_of(ctx, cG), ctx->consts, ctx->stream));
-            HIPCHK(ctx, hipEventRecord(ctx->w->ev_a2, ctx->stream));
-            return 0;
-          }();
-          ctx->stream = main_stream;
-          RET_IF(rc1);
+          SwapStream sw(ctx, ctx->stream_b);
+          TIMED_LAUNCH(ctx, 1, modp_launch_comb_dual_exp(cG, cG, 0, (const uint8_t*)dw, (const uint8_t*)dw, EB, 0, (int)cnt, da1,
+                                                         comb_bits_of(ctx, cG), ctx->consts, ctx->stream));
+          HIPCHK(ctx, hipEventRecord(ctx->w->ev_a2, ctx->stream));
         }
         const uint32_t* ty;
         RET_IF(number_tables(ctx, (const uint8_t*)dy, cnt, ctx->w->tab1, &ty));
@@ -3436,13 +3443,7 @@ extern "C" int mpvss_modp_extract_shares(mpvss_ctx* ctx, int space, const uint8_
         uint32_t* bk = (uint32_t*)ctx->w->tab1.p;
         TIMED_LAUNCH(ctx, 3, launch_twin_exp(ctx, (const uint8_t*)dy, (const uint8_t*)dxi, (const uint8_t*)de2, cnt, bk, bk + cnt * bw, dS, da2));
       }
-      if (a1_done) {
-      } else if ((pair_mask() & 1) && cnt >= 64 && comb_bits_of(ctx, cG) == 16)                                            // a1 = G^w
-        TIMED_LAUNCH(ctx, 1, modp_launch_comb16_twin_exp_pair(cG, (const uint8_t*)dw, nullptr, (int)cnt, da1, nullptr, ctx->consts,
-                                                              ctx->pair_tables, ctx->stream));
-      else
-        TIMED_LAUNCH(ctx, 1, modp_launch_comb_dual_exp(cG, cG, 0, (const uint8_t*)dw, (const uint8_t*)dw, EB, 0, (int)cnt,
-                                                       da1, comb_bits_of(ctx, cG), ctx->consts, ctx->stream));
+      if (!a1_done) RET_IF(launch_comb_exp(ctx, cG, (const uint8_t*)dw, cnt, da1));                  // a1 = G^w
     } else {
       RET_IF(exp_dev(ctx, (const uint8_t*)dy, (const uint8_t*)dxi, cnt, dS));                       // S = Y^(1/x)
       TIMED_LAUNCH(ctx, 1, modp_launch_comb_dual_exp(cG, cG, 0, (const uint8_t*)dw, (const uint8_t*)dw, EB, 0, (int)cnt,
@@ -3491,14 +3492,8 @@ int extract_shares_compute_locked(mpvss_ctx* ctx, const uint8_t* pk, const uint8
   RET_IF(be.rc);
   mpvss_ctx::BlockSlot& sl = be.sl;
   if (n > MAX_CHUNK) return fail(ctx, MPVSS_E_UNSUPPORTED, "extract_shares_compute: batch larger than one chunk");
-  {
-    uint8_t qb[EB];
-    modq_modulus_bytes(qb);
-    static const uint8_t zero[EB] = {0};
-    for (size_t i = 0; i < n; ++i)
-      if (memcmp(y + i * EB, zero, EB) == 0 || memcmp(y + i * EB, qb, EB) == 0)
-        return fail(ctx, MPVSS_E_UNSUPPORTED, "extract_shares_compute: an encrypted share is 0 mod q (use mpvss_modp_extract_shares)");
-  }
+  if (!all_units_mod_q(y, n))
+    return fail(ctx, MPVSS_E_UNSUPPORTED, "extract_shares_compute: an encrypted share is 0 mod q (use mpvss_modp_extract_shares)");
   RET_IF(be.enter());
   // pinned staging: outputs S [n][256], c [n][32]; inputs pk, y, xinv, w [n][256] each
   RET_IF(be.pin(n * EB + n * 32 + 4 * n * EB));
@@ -3537,12 +3532,7 @@ int extract_shares_compute_locked(mpvss_ctx* ctx, const uint8_t* pk, const uint8
   uint32_t* bk = (uint32_t*)ctx->w->tab1.p;
   // S = Y^(1/x) and a2 = S^w = Y^(w/x) from one chain of squarings (participant.rs:310-314, dleq.rs:213-216)
   TIMED_LAUNCH(ctx, 3, launch_twin_exp(ctx, (const uint8_t*)dy, (const uint8_t*)dxi, (const uint8_t*)de2, n, bk, bk + n * bw, dS, da2));
-  if ((pair_mask() & 1) && n >= 64 && comb_bits_of(ctx, cG) == 16)                                                           // a1 = G^w
-    TIMED_LAUNCH(ctx, 1, modp_launch_comb16_twin_exp_pair(cG, (const uint8_t*)dw, nullptr, (int)n, da1, nullptr, ctx->consts,
-                                                          ctx->pair_tables, ctx->stream));
-  else
-    TIMED_LAUNCH(ctx, 1, modp_launch_comb_dual_exp(cG, cG, 0, (const uint8_t*)dw, (const uint8_t*)dw, EB, 0, (int)n, da1,
-                                                   comb_bits_of(ctx, cG), ctx->consts, ctx->stream));
+  RET_IF(launch_comb_exp(ctx, cG, (const uint8_t*)dw, n, da1));                                        // a1 = G^w
   // c_i = hash_to_scalar(SHA256(framed(pk_i) framed(Y_i) framed(a1_i) framed(a2_i)))   (participant.rs:329-343), K7
   TIMED_LAUNCH(ctx, 0, verdict_launch_modp_challenge((const uint8_t*)dpk, (const uint8_t*)dy, da1, da2, (int)n, dc, ctx->stream));
   HIPCHK(ctx, hipMemcpyAsync(hS, dS, n * EB, hipMemcpyDeviceToHost, ctx->stream));
