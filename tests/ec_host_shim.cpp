@@ -185,6 +185,11 @@ int ec_decode_ok(int curve, const uint8_t* p) {
   if (curve == 0) { Secp::Point a; return Secp::decode(a, p); }
   Ristretto::Point a; return Ristretto::decode(a, p);
 }
+// decode then encode: 0 and the re-encoded bytes, or -1 when the decoder rejects the input
+int ec_recode(int curve, const uint8_t* p, uint8_t* out) {
+  if (curve == 0) { Secp::Point a; if (!Secp::decode(a, p)) return -1; Secp::encode(out, a); return 0; }
+  Ristretto::Point a; if (!Ristretto::decode(a, p)) return -1; Ristretto::encode(out, a); return 0;
+}
 // field self-test hooks: r = a*b, a^2, a-b (canonical 32-byte LE)
 // mul (op 0) / sqr (op 1) on RAW limbs (10 x u32, any value up to the documented 2^30 input bound); writes the
 // canonical result and returns the largest output limb before canonicalisation (the documented output bound is checked

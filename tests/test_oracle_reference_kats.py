@@ -3,6 +3,7 @@
 import hashlib
 
 import mpvss_oracle as O
+from encoding_vectors import RFC9496_GENERATOR_MULTIPLES
 
 
 # ---- reference KATs -------------------------------------------------------------------------
@@ -79,6 +80,11 @@ def test_secp256k1_kats():
         ok, P = s.decode_element(s.element_to_bytes(s.exp(G, k)))
         assert ok and P == s.exp(G, k)
     assert s.bytes_to_element(b"\x05" + bytes(32)) is None and s.bytes_to_element(bytes(32)) is None
+    import encoding_vectors as EV
+    for label, bad in EV.rejecting("secp256k1"):
+        assert s.decode_element(bad) == (False, None), label
+    for label, enc, pt in EV.valid("secp256k1"):
+        assert s.decode_element(enc) == (True, pt) and s.element_to_bytes(pt) == enc, label
 
 
 def test_ristretto255_kats():
@@ -87,24 +93,7 @@ def test_ristretto255_kats():
     # ristretto255.rs:378-401 order constant
     assert r.group_order_int() == 2**252 + 27742317777372353535851937790883648493
     # RFC 9496 appendix A.1: multiples of the generator
-    expected = [
-        "0000000000000000000000000000000000000000000000000000000000000000",
-        "e2f2ae0a6abc4e71a884a961c500515f58e30b6aa582dd8db6a65945e08d2d76",
-        "6a493210f7499cd17fecb510ae0cea23a110e8d5b901f8acadd3095c73a3b919",
-        "94741f5d5d52755ece4f23f044ee27d5d1ea1e2bd196b462166b16152a9d0259",
-        "da80862773358b466ffadfe0b3293ab3d9fd53c5ea6c955358f568322daf6a57",
-        "e882b131016b52c1d3337080187cf768423efccbb517bb495ab812c4160ff44e",
-        "f64746d3c92b13050ed8d80236a7f0007c3b3f962f5ba793d19a601ebb1df403",
-        "44f53520926ec81fbd5a387845beb7df85a96a24ece18738bdcfa6a7822a176d",
-        "903293d8f2287ebe10e2374dc1a53e0bc887e592699f02d077d5263cdd55601c",
-        "02622ace8f7303a31cafc63f8fc48fdc16e1c8c8d234b2f0d6685282a9076031",
-        "20706fd788b2720a1ed2a5dad4952b01f413bcf0e7564de8cdc816689e2db95f",
-        "bce83f8ba5dd2fa572864c24ba1810f9522bc6004afe95877ac73241cafdab42",
-        "e4549ee16b9aa03099ca208c67adafcafa4c3f3e4e5303de6026e3ca8ff84460",
-        "aa52e000df2e16f55fb1032fc33bc42742dad6bd5a8fc0be0167436c5948501f",
-        "46376b80f409b29dc2b5f6f0c52591990896e5716f41477cd30085ab7f10301e",
-        "e0c418f7c8d9c4cdd7395b93ea124f3ad99021bb681dfc3302a9d99a2e53e64e",
-    ]
+    expected = RFC9496_GENERATOR_MULTIPLES
     for k, e in enumerate(expected):
         P = r.exp(B, k)
         assert r.element_to_bytes(P).hex() == e
@@ -115,6 +104,13 @@ def test_ristretto255_kats():
                 "0100000000000000000000000000000000000000000000000000000000000000",   # negative field element
                 "26948d35ca62e643e26a83177332e6b6afeb9d08e4268b650f1f5bbd8d81d371"):  # non-square x^2
         assert r.bytes_to_element(bytes.fromhex(bad)) is None
+    # every classified rejecting encoding (one failing decode check each, tests/encoding_vectors.py), and the valid ones
+    import encoding_vectors as EV
+    for label, bad in EV.rejecting("ristretto255"):
+        assert r.bytes_to_element(bad) is None, label
+    for label, enc, pt in EV.valid("ristretto255"):
+        Q = r.bytes_to_element(enc)
+        assert Q is not None and r.elements_equal(Q, pt) and r.element_to_bytes(Q) == enc, label
     # ristretto255.rs:620-638 basic ops, 680-682 encoding length
     assert r.elements_equal(r.mul(B, B), r.exp(B, 2))
     assert r.element_to_bytes(r.exp(B, 0)) == bytes(32)
