@@ -29,20 +29,23 @@
 
 #include <type_traits>
 
+#include "modp_limbs.h"
 #include "modp_mfma_tables.h"
 
 
 namespace mm {
 
-typedef uint32_t u32;
-typedef uint64_t u64;
+using limbs::L;
+using limbs::MASK;
+using limbs::u32;
+using limbs::u64;
+using limbs::W;
 typedef int64_t i64;
 typedef int v4i __attribute__((ext_vector_type(4)));
 typedef int v16i __attribute__((ext_vector_type(16)));
 
-constexpr int W = 29, L = 72, LP = 36;
+constexpr int LP = 36;                    // limbs per lane half
 constexpr int SLOTW = 76;                 // LDS words per number slot (72 limbs + pad: 16-byte aligned rows)
-constexpr u32 MASK = (1u << W) - 1;
 constexpr u32 XM = 0x00808080u;           // bytes 0..2 of an operand word are unsigned digits (minus 128 for the MFMA), byte 3 is signed
 
 struct __attribute__((aligned(64))) Tables {   // constant, one copy in LDS per workgroup (17 KB)

@@ -23,16 +23,17 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include "modp_limbs.h"
 
 namespace bn {
 
-typedef uint32_t u32;
-typedef uint64_t u64;
+using limbs::L;
+using limbs::MASK;
+using limbs::u32;
+using limbs::u64;
+using limbs::W;
 
-constexpr int W = 29;
-constexpr int L = 72;
 constexpr int LPL = 18;              // limbs per lane
-constexpr u32 MASK = (1u << W) - 1;
 constexpr int NUMS_PER_WAVE = 16;
 constexpr int SLOT_WORDS = 72;       // LDS words per number operand slot (288 B = 18 x 16 B)
 
@@ -79,60 +80,67 @@ __device__ __forceinline__ Lane make_lane() {
   return ln;
 }
 
-// r = a * b * R^-1 (mod N), result almost normalised and < 2N when a, b < 2N.
-//   a   : this lane's 18 limbs of the first operand (registers)
-//   b   : LDS pointer to the 72 limbs of the second operand of THIS number
-//   n   : this lane's 18 limbs of the modulus (registers)
-// N0INV == 1 for the RFC 3526 prime (N = -1 mod 2^64), the multiply folds away.
+// r = a * b * R^-1 (mod N), R = 2^(29 * 4 K); result almost normalised and < 2N when a, b < 2N.
+//   a     : this lane's K limbs of the first operand (registers); K = 18 for a 2048-bit number, bn_quad_rt.h adds 5 and 9
+//   b     : LDS pointer to the limbs of the second operand of THIS number (a slot of at least 4 K words)
+//   n     : this lane's K limbs of the modulus (registers)
+//   N0INV : -N^-1 mod 2^29 when the modulus is a compile-time one; 1 for the RFC 3526 prime (N = -1 mod 2^64), the multiply
+//           folds away.  N0INV_RUNTIME: the value comes as the last argument (a VGPR), one more v_mul_lo_u32 per row.
 //
-// One step (one limb b_i of b), per lane: 18 mads a[k]*b_i, m from lane 0's lowest column,
-// 18 mads m*n[k]; lane 0's lowest column is then 0 mod 2^29 and retires.  Every lane carries the upper bits
+// One step (one limb b_i of b), per lane: K mads a[k]*b_i, m from lane 0's lowest column,
+// K mads m*n[k]; lane 0's lowest column is then 0 mod 2^29 and retires.  Every lane carries the upper bits
 // of its lowest column into its next column and hands the low 29 bits to the lane below (lane 3 starts a
-// fresh zero column).  Column accumulators stay below 2^64 (at most 18 steps x 2 products < 2^58.01 between two
-// carries of a column, checked for worst-case limbs in tests/test_limb_model.py).
+// fresh zero column).  Column accumulators stay below 2^64 (at most K steps x 2 products < 2^58.01 between two
+// carries of a column, whatever OUTER is; checked for worst-case limbs in tests/test_limb_model.py and, for every
+// instantiated width with a run-time n0inv, in tests/test_modp_rt_model.py).
 //
-// SQ = true: b must be (an LDS copy of) a itself.  Row r = 18 o + rr then only visits the local positions k >= rr:
+// SQ = true: b must be (an LDS copy of) a itself.  Row r = K o + rr then only visits the local positions k >= rr:
 // k > rr with the doubled limb 2 a_r, k == rr with a_r itself.  Every pair {r, j}, r != j, is then counted exactly
 // twice -- once doubled in the row of the limb with the smaller local index, or once in each of the two rows when the
 // local indices are equal -- and every square once, in all four lanes by the same instructions: 9.5 instead of 18
 // mads per row for the a*a half, 24 % fewer mads per squaring.  (Needs an even number of limbs per lane only in
 // the sense that the rule is lane-independent; bounds: tests/test_limb_model.py.)
-// OUTER < L / LPL: only the low 18 OUTER limbs of b take part (b < 2^(522 OUTER)) and the result is a b 2^(-522 OUTER) mod N --
-// the scalar-ring kernels multiply by small numbers this way (a quarter of a product per Horner step).
-template <u32 N0INV, bool SQ = false, int OUTER = L / LPL>
-__device__ __forceinline__ void mont_mul(u32 (&r)[LPL], const u32 (&a)[LPL], const u32* __restrict__ b,
-                                         const u32 (&n)[LPL], const Lane& ln) {
-  u64 T[LPL];
+// OUTER: the product has K OUTER rows and divides by 2^(29 K OUTER), result < N + a b / 2^(29 K OUTER).
+//   OUTER < 4: only the low K OUTER limbs of b take part -- the scalar-ring kernels multiply by small numbers this way (a
+//              quarter of a product per Horner step);
+//   OUTER > 4: b has K OUTER limbs, which is how a 2048-bit input enters a narrower width (bn_quad_rt.h).
+constexpr u32 N0INV_RUNTIME = 0;     // (an n0inv is odd)
+template <u32 N0INV, bool SQ = false, int OUTER = 4, int K>
+__device__ __forceinline__ void mont_mul(u32 (&r)[K], const u32 (&a)[K], const u32* __restrict__ b, const u32 (&n)[K],
+                                         const Lane& ln, u32 n0inv = N0INV) {
+  static_assert(!SQ || OUTER == 4, "a squaring has 4 K rows");
+  constexpr int B_LAST = (OUTER > 4 ? OUTER : 4) * K - 1;   // the prefetch stays inside the slot
+  u64 T[K];
 #pragma unroll
-  for (int k = 0; k < LPL; ++k) T[k] = 0;
+  for (int k = 0; k < K; ++k) T[k] = 0;
   u32 bnext = b[0];   // software prefetch of the next b limb (one LDS read in flight)
 #pragma nounroll
   for (int o = 0; o < OUTER; ++o) {
 #pragma unroll
-    for (int rr = 0; rr < LPL; ++rr) {
-      // local position k lives in T[(k + rr) % LPL]
+    for (int rr = 0; rr < K; ++rr) {
+      // local position k lives in T[(k + rr) % K]
       const u32 bi = bnext;
       {
-        const int nxt = o * LPL + rr + 1;
-        bnext = b[nxt < L ? nxt : L - 1];
+        const int nxt = o * K + rr + 1;
+        bnext = b[nxt <= B_LAST ? nxt : B_LAST];
       }
       if (SQ) {
         const u32 bi2 = bi << 1;
 #pragma unroll
-        for (int k = rr; k < LPL; ++k) T[(k + rr) % LPL] += (u64)a[k] * (k > rr ? bi2 : bi);
+        for (int k = rr; k < K; ++k) T[(k + rr) % K] += (u64)a[k] * (k > rr ? bi2 : bi);
       } else {
 #pragma unroll
-        for (int k = 0; k < LPL; ++k) T[(k + rr) % LPL] += (u64)a[k] * bi;
+        for (int k = 0; k < K; ++k) T[(k + rr) % K] += (u64)a[k] * bi;
       }
-      const u32 m = quad_bcast0((u32)T[rr] * N0INV) & ln.mask28;
+      const u32 m = quad_bcast0((u32)T[rr] * (N0INV != N0INV_RUNTIME ? N0INV : n0inv)) & ln.mask28;
 #pragma unroll
-      for (int k = 0; k < LPL; ++k) T[(k + rr) % LPL] += (u64)m * n[k];
+      for (int k = 0; k < K; ++k) T[(k + rr) % K] += (u64)m * n[k];
       // Every lane moves the upper bits of its lowest column into its next column (same weight) and hands the
       // low 28 bits to the lane below, whose fresh top column they become; lane 0's lowest column is 0 mod 2^W
       // by construction and retires.  No lane-dependent arithmetic: one shift, one 64-bit add, one v_and_b32_dpp.
       {
         const u64 ret = T[rr];
-        T[(rr + 1) % LPL] += ret >> W;
+        T[(rr + 1) % K] += ret >> W;
         T[rr] = (u64)(quad_from_next((u32)ret) & ln.top28);
       }
       // Pin the row-wise order: without this LLVM reassociates the 19-fold unrolled body into a
@@ -140,15 +148,15 @@ __device__ __forceinline__ void mont_mul(u32 (&r)[LPL], const u32 (&a)[LPL], con
       // no longer fits 128 VGPRs (4 waves/SIMD).  The empty asm makes each accumulator opaque.
 #ifndef MODP_NO_PIN
 #pragma unroll
-      for (int k = 0; k < LPL; ++k) asm volatile("" : "+v"(T[k]));
+      for (int k = 0; k < K; ++k) asm volatile("" : "+v"(T[k]));
 #endif
     }
   }
-  // L is a multiple of LPL, so local position k is back in T[k].
+  // whole groups of K rows, so local position k is back in T[k].
   // pass 1: carry-propagate inside the lane
   u64 c = 0;
 #pragma unroll
-  for (int k = 0; k < LPL; ++k) {
+  for (int k = 0; k < K; ++k) {
     const u64 v = T[k] + c;
     r[k] = (u32)v & MASK;
     c = v >> W;
@@ -168,37 +176,43 @@ __device__ __forceinline__ void mont_sqr(u32 (&r)[LPL], const u32 (&a)[LPL], con
   mont_mul<N0INV, true>(r, a, self, n, ln);
 }
 
-// ---- operand slot helpers (one wave = 16 numbers, slot = 76 words per number) -------------
+// ---- lane and operand slot helpers (one wave = 16 numbers; K limbs per lane, 4 K words per number) -------------
 
-// store this lane's 19 limbs into the number's LDS slot
-__device__ __forceinline__ void slot_store(u32* slot, const u32 (&a)[LPL], const Lane& ln) {
+// this lane's K limbs of a number in global memory
+template <int K>
+__device__ __forceinline__ void load_lane_limbs(u32 (&a)[K], const u32* __restrict__ g, const Lane& ln) {
 #pragma unroll
-  for (int k = 0; k < LPL; ++k) slot[ln.q * LPL + k] = a[k];
+  for (int k = 0; k < K; ++k) a[k] = g[ln.q * K + k];
 }
 
-__device__ __forceinline__ void slot_load(u32 (&a)[LPL], const u32* slot, const Lane& ln) {
+template <int K>
+__device__ __forceinline__ void store_lane_limbs(u32* __restrict__ g, const u32 (&a)[K], const Lane& ln) {
 #pragma unroll
-  for (int k = 0; k < LPL; ++k) a[k] = slot[ln.q * LPL + k];
+  for (int k = 0; k < K; ++k) g[ln.q * K + k] = a[k];
 }
 
-// copy 76 words global -> LDS slot with 16-byte accesses: chunk c (0..18) is handled by lane c & 3
+// store this lane's K limbs into the number's LDS slot
+template <int K>
+__device__ __forceinline__ void slot_store(u32* slot, const u32 (&a)[K], const Lane& ln) {
+#pragma unroll
+  for (int k = 0; k < K; ++k) slot[ln.q * K + k] = a[k];
+}
+
+template <int K>
+__device__ __forceinline__ void slot_load(u32 (&a)[K], const u32* slot, const Lane& ln) {
+#pragma unroll
+  for (int k = 0; k < K; ++k) a[k] = slot[ln.q * K + k];
+}
+
+// copy the 4 K words of a number global -> LDS slot with 16-byte accesses: chunk c (0 .. K-1) is handled by lane c & 3
+template <int K = LPL>
 __device__ __forceinline__ void slot_fill_from_global(u32* slot, const u32* __restrict__ g, const Lane& ln) {
   const uint4* g4 = reinterpret_cast<const uint4*>(g);
   uint4* s4 = reinterpret_cast<uint4*>(slot);
 #pragma unroll
-  for (int c = 0; c < 5; ++c) {
+  for (int c = 0; c < (K + 3) / 4; ++c) {
     const int idx = c * 4 + (int)ln.q;
-    if (idx < SLOT_WORDS / 4) s4[idx] = g4[idx];
-  }
-}
-
-__device__ __forceinline__ void slot_spill_to_global(u32* __restrict__ g, const u32* slot, const Lane& ln) {
-  uint4* g4 = reinterpret_cast<uint4*>(g);
-  const uint4* s4 = reinterpret_cast<const uint4*>(slot);
-#pragma unroll
-  for (int c = 0; c < 5; ++c) {
-    const int idx = c * 4 + (int)ln.q;
-    if (idx < SLOT_WORDS / 4) g4[idx] = s4[idx];
+    if (idx < K) s4[idx] = g4[idx];
   }
 }
 

@@ -21,17 +21,18 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include "modp_limbs.h"
 
 namespace bnrow {
 
-typedef uint32_t u32;
-typedef uint64_t u64;
+using limbs::L;                      // limbs of a number (rows of a product)
+using limbs::MASK;
+using limbs::u32;
+using limbs::u64;
+using limbs::W;
 
-constexpr int W = 29;
-constexpr int L = 72;                // limbs of a number (rows of a product)
 constexpr int LPL = 5;               // limb slots per lane
 constexpr int LANES = 16;
-constexpr u32 MASK = (1u << W) - 1;
 constexpr int NUMS_PER_WAVE = 4;
 constexpr int SLOT_WORDS = 80;       // LDS words per number operand slot (16 lanes x 5; words 72..79 are zero)
 constexpr int FULL_GROUPS = L / LPL; // 14 groups of 5 rows, then TAIL_ROWS

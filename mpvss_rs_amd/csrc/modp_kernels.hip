@@ -44,36 +44,8 @@ using namespace bn;
 
 namespace {
 
-// device-resident constants: [0]=N, [1]=R^2 mod N, [2]=R mod N (Montgomery one), [3]=plain 1
-struct ModpConsts {
-  u32 n[L];
-  u32 r2[L];
-  u32 one_m[L];
-  u32 one[L];
-};
-
-__device__ __forceinline__ void load_lane_limbs(u32 (&a)[LPL], const u32* __restrict__ g, const Lane& ln) {
-#pragma unroll
-  for (int k = 0; k < LPL; ++k) a[k] = g[ln.q * LPL + k];
-}
-
-__device__ __forceinline__ void store_lane_limbs(u32* __restrict__ g, const u32 (&a)[LPL], const Lane& ln) {
-#pragma unroll
-  for (int k = 0; k < LPL; ++k) g[ln.q * LPL + k] = a[k];
-}
-
-// limb j (W bits at bit offset W j) of a 256-byte big-endian integer
-__device__ __forceinline__ u32 be256_limb(const uint8_t* __restrict__ be, int j) {
-  const int o = W * j;
-  const int p = o >> 3, s = o & 7;
-  u64 w = 0;
-#pragma unroll
-  for (int t = 0; t < 5; ++t) {                // W + 7 <= 40 bits
-    const int idx = 255 - (p + t);
-    if (idx >= 0) w |= (u64)be[idx] << (8 * t);
-  }
-  return (u32)(w >> s) & MASK;
-}
+using limbs::be256_limb;
+using limbs::ModpConsts;
 
 __device__ __forceinline__ void load_be256(u32 (&a)[LPL], const uint8_t* __restrict__ be, const Lane& ln) {
 #pragma unroll
@@ -94,8 +66,8 @@ __device__ __forceinline__ void to_mont(u32 (&a)[LPL], u32* slot, const ModpCons
 __device__ __forceinline__ void store_canonical_be256(uint8_t* __restrict__ out, u32 (&a)[LPL], bool from_montgomery,
                                                       u32* slot, const ModpConsts* __restrict__ cs,
                                                       const u32 (&n)[LPL], const Lane& ln, bool write, int lift_parity = -1) {
-  // lift_parity 0 / 1 (scalar ring, cs = the constants of q'): the canonical residue v in [0, q') is lifted to the
-  // number in [0, 2q') = [0, q-1) of that parity, v or v + q' (Chinese remainders; q' is odd)
+  // lift_parity 0 / 1 (scalar ring, cs = the constants of q'): the residue is lifted to the number in [0, q-1) of that
+  // parity (limbs::slot_canonicalize)
   if (from_montgomery) {
     slot_fill_from_global(slot, cs->one, ln);
     __builtin_amdgcn_wave_barrier();
@@ -104,41 +76,7 @@ __device__ __forceinline__ void store_canonical_be256(uint8_t* __restrict__ out,
   }
   slot_store(slot, a, ln);
   __builtin_amdgcn_wave_barrier();
-  if (ln.q == 0) {
-    // exact carry propagation
-    u32 c = 0;
-#pragma nounroll
-    for (int j = 0; j < L; ++j) {
-      const u32 v = slot[j] + c;
-      slot[j] = v & MASK;
-      c = v >> W;
-    }
-    // value < 2N: subtract N once if value >= N
-    int ge = 1;  // value >= N ?  (decided by the most significant differing limb)
-#pragma nounroll
-    for (int j = L - 1; j >= 0; --j) {
-      const u32 x = slot[j], y = cs->n[j];
-      if (x != y) { ge = x > y; break; }
-    }
-    if (ge) {
-      u32 borrow = 0;
-#pragma nounroll
-      for (int j = 0; j < L; ++j) {
-        const u32 d = slot[j] - cs->n[j] - borrow;
-        borrow = (d >> 31) & 1;  // operands < 2^W, so a wrap sets the top bit
-        slot[j] = d & MASK;
-      }
-    }
-    if (lift_parity >= 0 && (int)(slot[0] & 1u) != lift_parity) {
-      u32 carry = 0;
-#pragma nounroll
-      for (int j = 0; j < L; ++j) {
-        const u32 v = slot[j] + cs->n[j] + carry;
-        slot[j] = v & MASK;
-        carry = v >> W;
-      }
-    }
-  }
+  if (ln.q == 0) limbs::slot_canonicalize<L>(slot, cs->n, lift_parity);
   __builtin_amdgcn_wave_barrier();
   if (write) {
     // lane q emits little-endian 32-bit words 16q .. 16q+15 (byte-swapped, mirrored position)
@@ -146,14 +84,7 @@ __device__ __forceinline__ void store_canonical_be256(uint8_t* __restrict__ out,
 #pragma unroll
     for (int i = 0; i < 16; ++i) {
       const int wd = (int)ln.q * 16 + i;
-      const int bit = 32 * wd;
-      const int j = bit / W, s = bit % W;
-      // 32 bits starting at bit s of limb j: up to three limbs (s + 32 can exceed 2 W)
-      u64 two = (u64)slot[j] | ((u64)(j + 1 < L ? slot[j + 1] : 0u) << W);
-      two >>= s;
-      if (2 * W - s < 32) two |= (u64)(j + 2 < L ? slot[j + 2] : 0u) << (2 * W - s);
-      const u32 v = (u32)two;
-      out32[63 - wd] = __builtin_bswap32(v);
+      out32[63 - wd] = __builtin_bswap32(limbs::slot_word32<L>(slot, wd));
     }
   }
   __builtin_amdgcn_wave_barrier();
@@ -168,6 +99,16 @@ __device__ __forceinline__ void square_into(u32 (&a)[LPL], u32* slot, const u32 
 
 }  // namespace
 
+// What the quad kernels set up the same way (as PAIR_KERNEL_PROLOGUE of modp_pair_kernels.hip): the lane, its number xi of
+// `total` numbers -- x is xi clamped for the quads past the end, which compute along and write nothing (live) -- and the
+// number's operand slot in the kernel's `lds`.
+#define QUAD_KERNEL_PROLOGUE(total)                                                        \
+  const Lane ln = make_lane();                                                             \
+  const int xi = blockIdx.x * NUMS_PER_BLOCK + (threadIdx.x >> 2);                         \
+  const bool live = xi < (total);                                                          \
+  const int x = live ? xi : (total)-1;                                                     \
+  u32* slot = lds + (threadIdx.x >> 2) * SLOT_WORDS;
+
 // ---------------------------------------------------------------------------------------
 // out[x] = a[x] * b[x] mod q          (Group::mul, modp.rs:130-132)
 // ---------------------------------------------------------------------------------------
@@ -175,11 +116,7 @@ extern "C" __global__ void __launch_bounds__(BLOCK_THREADS) WAVES_ATTR
 k_modp_mul(const uint8_t* __restrict__ a_be, const uint8_t* __restrict__ b_be, uint8_t* __restrict__ out_be,
            int count, const ModpConsts* __restrict__ cs) {
   __shared__ __attribute__((aligned(16))) u32 lds[NUMS_PER_BLOCK * SLOT_WORDS];
-  const Lane ln = make_lane();
-  const int xi = blockIdx.x * NUMS_PER_BLOCK + (threadIdx.x >> 2);
-  const bool live = xi < count;
-  const int x = live ? xi : count - 1;
-  u32* slot = lds + (threadIdx.x >> 2) * SLOT_WORDS;
+  QUAD_KERNEL_PROLOGUE(count)
   u32 n[LPL], a[LPL], b[LPL];
   load_lane_limbs(n, cs->n, ln);
   load_be256(a, a_be + (size_t)x * 256, ln);
@@ -199,11 +136,7 @@ extern "C" __global__ void __launch_bounds__(BLOCK_THREADS) WAVES_ATTR
 k_modp_to_mont(const uint8_t* __restrict__ in_be, u32* __restrict__ out_m, int count,
                const ModpConsts* __restrict__ cs) {
   __shared__ __attribute__((aligned(16))) u32 lds[NUMS_PER_BLOCK * SLOT_WORDS];
-  const Lane ln = make_lane();
-  const int xi = blockIdx.x * NUMS_PER_BLOCK + (threadIdx.x >> 2);
-  const bool live = xi < count;
-  const int x = live ? xi : count - 1;
-  u32* slot = lds + (threadIdx.x >> 2) * SLOT_WORDS;
+  QUAD_KERNEL_PROLOGUE(count)
   u32 n[LPL], a[LPL];
   load_lane_limbs(n, cs->n, ln);
   load_be256(a, in_be + (size_t)x * 256, ln);
@@ -239,11 +172,7 @@ extern "C" __global__ void __launch_bounds__(BLOCK_THREADS) WAVES_ATTR
 k_modq_poly_eval(const u32* __restrict__ coef, int t, const int64_t* __restrict__ positions, int count, int par_even, int par_odd,
                  uint8_t* __restrict__ out_be, const ModpConsts* __restrict__ cs) {
   __shared__ __attribute__((aligned(16))) u32 lds[NUMS_PER_BLOCK * SLOT_WORDS];
-  const Lane ln = make_lane();
-  const int xi = blockIdx.x * NUMS_PER_BLOCK + (threadIdx.x >> 2);
-  const bool live = xi < count;
-  const int x = live ? xi : count - 1;
-  u32* slot = lds + (threadIdx.x >> 2) * SLOT_WORDS;
+  QUAD_KERNEL_PROLOGUE(count)
   const u64 pos = (u64)positions[x];
   u32 n[LPL], acc[LPL], cj[LPL];
   load_lane_limbs(n, cs->n, ln);
@@ -269,11 +198,7 @@ extern "C" __global__ void __launch_bounds__(BLOCK_THREADS) WAVES_ATTR
 k_modq_responses(const uint8_t* __restrict__ w_be, const uint8_t* __restrict__ alpha_be, const uint8_t* __restrict__ cneg_be,
                  int c_parity, int count, uint8_t* __restrict__ out_be, const ModpConsts* __restrict__ cs) {
   __shared__ __attribute__((aligned(16))) u32 lds[NUMS_PER_BLOCK * SLOT_WORDS];
-  const Lane ln = make_lane();
-  const int xi = blockIdx.x * NUMS_PER_BLOCK + (threadIdx.x >> 2);
-  const bool live = xi < count;
-  const int x = live ? xi : count - 1;
-  u32* slot = lds + (threadIdx.x >> 2) * SLOT_WORDS;
+  QUAD_KERNEL_PROLOGUE(count)
   u32 n[LPL], a[LPL], b[LPL];
   load_lane_limbs(n, cs->n, ln);
   load_be256(a, alpha_be + (size_t)x * 256, ln);
@@ -300,11 +225,7 @@ extern "C" __global__ void __launch_bounds__(BLOCK_THREADS) WAVES_ATTR
 k_modq_mul(const uint8_t* __restrict__ a_be, const uint8_t* __restrict__ b_be, int count, uint8_t* __restrict__ out_be,
            const ModpConsts* __restrict__ cs) {
   __shared__ __attribute__((aligned(16))) u32 lds[NUMS_PER_BLOCK * SLOT_WORDS];
-  const Lane ln = make_lane();
-  const int xi = blockIdx.x * NUMS_PER_BLOCK + (threadIdx.x >> 2);
-  const bool live = xi < count;
-  const int x = live ? xi : count - 1;
-  u32* slot = lds + (threadIdx.x >> 2) * SLOT_WORDS;
+  QUAD_KERNEL_PROLOGUE(count)
   u32 n[LPL], a[LPL], b[LPL];
   load_lane_limbs(n, cs->n, ln);
   load_be256(a, a_be + (size_t)x * 256, ln);
@@ -813,11 +734,7 @@ k_modp_from_mont(const u32* __restrict__ x_m, int count, uint8_t* __restrict__ o
                  const ModpConsts* __restrict__ cs) {
   __shared__ __attribute__((aligned(16))) u32 lds[NUMS_PER_BLOCK * SLOT_WORDS];
   if (gate != nullptr && *gate != 1) return;
-  const Lane ln = make_lane();
-  const int xi = blockIdx.x * NUMS_PER_BLOCK + (threadIdx.x >> 2);
-  const bool live = xi < count;
-  const int x = live ? xi : count - 1;
-  u32* slot = lds + (threadIdx.x >> 2) * SLOT_WORDS;
+  QUAD_KERNEL_PROLOGUE(count)
   u32 n[LPL], a[LPL];
   load_lane_limbs(n, cs->n, ln);
   load_lane_limbs(a, x_m + (size_t)x * L, ln);
@@ -832,11 +749,7 @@ extern "C" __global__ void __launch_bounds__(BLOCK_THREADS) WAVES_ATTR
 k_modp_build_table(const uint8_t* __restrict__ base_be, int count, u32* __restrict__ tab,
                    const ModpConsts* __restrict__ cs, int odd_only) {
   __shared__ __attribute__((aligned(16))) u32 lds[NUMS_PER_BLOCK * SLOT_WORDS];
-  const Lane ln = make_lane();
-  const int xi = blockIdx.x * NUMS_PER_BLOCK + (threadIdx.x >> 2);
-  const bool live = xi < count;
-  const int x = live ? xi : count - 1;
-  u32* slot = lds + (threadIdx.x >> 2) * SLOT_WORDS;
+  QUAD_KERNEL_PROLOGUE(count)
   u32 n[LPL], b[LPL], acc[LPL];
   load_lane_limbs(n, cs->n, ln);
   load_be256(b, base_be + (size_t)x * 256, ln);
@@ -883,11 +796,7 @@ k_modp_dual_exp(const u32* __restrict__ tab1, size_t tab1_stride, const u32* __r
                 const uint8_t* __restrict__ e1_be, const uint8_t* __restrict__ e2_be, size_t e2_stride,
                 int e2_windows, int count, uint8_t* __restrict__ out_be, const ModpConsts* __restrict__ cs) {
   __shared__ __attribute__((aligned(16))) u32 lds[NUMS_PER_BLOCK * SLOT_WORDS];
-  const Lane ln = make_lane();
-  const int xi = blockIdx.x * NUMS_PER_BLOCK + (threadIdx.x >> 2);
-  const bool live = xi < count;
-  const int x = live ? xi : count - 1;
-  u32* slot = lds + (threadIdx.x >> 2) * SLOT_WORDS;
+  QUAD_KERNEL_PROLOGUE(count)
   u32 n[LPL], acc[LPL];
   load_lane_limbs(n, cs->n, ln);
   const u32* t1 = tab1 + (size_t)x * tab1_stride;
@@ -1030,11 +939,7 @@ k_modp_comb_dual_exp(const u32* __restrict__ comb, const u32* __restrict__ tab2,
   // mode 0: the whole product.  mode 1: only g^e1 (needs nothing but the exponent, so it can run before B2 is
   // known), left in Montgomery form in p_m.  mode 2: B2^e2 times the stored p_m.
   __shared__ __attribute__((aligned(16))) u32 lds[2 * NUMS_PER_BLOCK * SLOT_WORDS];
-  const Lane ln = make_lane();
-  const int xi = blockIdx.x * NUMS_PER_BLOCK + (threadIdx.x >> 2);
-  const bool live = xi < count;
-  const int x = live ? xi : count - 1;
-  u32* slot = lds + (threadIdx.x >> 2) * SLOT_WORDS;
+  QUAD_KERNEL_PROLOGUE(count)
   u32* pslot = lds + (NUMS_PER_BLOCK + (threadIdx.x >> 2)) * SLOT_WORDS;
   u32 n[LPL], acc[LPL];
   load_lane_limbs(n, cs->n, ln);
@@ -1150,11 +1055,7 @@ extern "C" __global__ void __launch_bounds__(BLOCK_THREADS) WAVES_ATTR
 k_modp_build_table64(const uint8_t* __restrict__ base_be, int count, u32* __restrict__ tab,
                      const ModpConsts* __restrict__ cs) {
   __shared__ __attribute__((aligned(16))) u32 lds[NUMS_PER_BLOCK * SLOT_WORDS];
-  const Lane ln = make_lane();
-  const int xi = blockIdx.x * NUMS_PER_BLOCK + (threadIdx.x >> 2);
-  const bool live = xi < count;
-  const int x = live ? xi : count - 1;
-  u32* slot = lds + (threadIdx.x >> 2) * SLOT_WORDS;
+  QUAD_KERNEL_PROLOGUE(count)
   u32 n[LPL], b[LPL], acc[LPL];
   load_lane_limbs(n, cs->n, ln);
   load_be256(b, base_be + (size_t)x * 256, ln);
@@ -1181,11 +1082,7 @@ k_modp_dual_exp_w6(const u32* __restrict__ tab1, const u32* __restrict__ tab2, c
   // (bit position of the window's lowest bit, odd digit) in descending position -- instead of 64 fixed 4-bit windows:
   // about 51 products for Y^c and a table of the odd powers only (dleq.rs:79-81 has the same c for every share of a box)
   __shared__ __attribute__((aligned(16))) u32 lds[NUMS_PER_BLOCK * SLOT_WORDS];
-  const Lane ln = make_lane();
-  const int xi = blockIdx.x * NUMS_PER_BLOCK + (threadIdx.x >> 2);
-  const bool live = xi < count;
-  const int x = live ? xi : count - 1;
-  u32* slot = lds + (threadIdx.x >> 2) * SLOT_WORDS;
+  QUAD_KERNEL_PROLOGUE(count)
   u32 n[LPL], acc[LPL];
   load_lane_limbs(n, cs->n, ln);
   const u32* t1 = tab1 + (size_t)x * 64 * L;
@@ -1364,11 +1261,7 @@ extern "C" __global__ void __launch_bounds__(BLOCK_THREADS) WAVES_ATTR
 k_modp_bucket_combine(const u32* __restrict__ buckets, const u32* __restrict__ occupancy, int count,
                       uint8_t* __restrict__ out1_be, uint8_t* __restrict__ out2_be, const ModpConsts* __restrict__ cs) {
   __shared__ __attribute__((aligned(16))) u32 lds[NUMS_PER_BLOCK * SLOT_WORDS];
-  const Lane ln = make_lane();
-  const int xi = blockIdx.x * NUMS_PER_BLOCK + (threadIdx.x >> 2);
-  const bool live = xi < 2 * count;
-  const int x = live ? xi : 2 * count - 1;      // (share, exponent) pair: share x >> 1, exponent x & 1
-  u32* slot = lds + (threadIdx.x >> 2) * SLOT_WORDS;
+  QUAD_KERNEL_PROLOGUE(2 * count)      // (share, exponent) pair: share x >> 1, exponent x & 1
   u32 n[LPL], run[LPL], res[LPL], tmp[LPL];
   load_lane_limbs(n, cs->n, ln);
   load_lane_limbs(run, cs->one_m, ln);
@@ -1441,11 +1334,7 @@ extern "C" __global__ void __launch_bounds__(BLOCK_THREADS) WAVES_ATTR
 k_modp_keyset_bases(const uint8_t* __restrict__ pk_be, int count, u32* __restrict__ ks,
                     const ModpConsts* __restrict__ cs) {
   __shared__ __attribute__((aligned(16))) u32 lds[NUMS_PER_BLOCK * SLOT_WORDS];
-  const Lane ln = make_lane();
-  const int xi = blockIdx.x * NUMS_PER_BLOCK + (threadIdx.x >> 2);
-  const bool live = xi < count;
-  const int x = live ? xi : count - 1;
-  u32* slot = lds + (threadIdx.x >> 2) * SLOT_WORDS;
+  QUAD_KERNEL_PROLOGUE(count)
   u32 n[LPL], acc[LPL], one[LPL];
   load_lane_limbs(n, cs->n, ln);
   load_lane_limbs(one, cs->one_m, ln);
@@ -1469,11 +1358,7 @@ k_modp_keyset_bases(const uint8_t* __restrict__ pk_be, int count, u32* __restric
 extern "C" __global__ void __launch_bounds__(BLOCK_THREADS) WAVES_ATTR
 k_modp_keyset_rows(u32* __restrict__ ks, int rows, const ModpConsts* __restrict__ cs) {
   __shared__ __attribute__((aligned(16))) u32 lds[NUMS_PER_BLOCK * SLOT_WORDS];
-  const Lane ln = make_lane();
-  const int xi = blockIdx.x * NUMS_PER_BLOCK + (threadIdx.x >> 2);
-  const bool live = xi < rows;
-  const int x = live ? xi : rows - 1;
-  u32* slot = lds + (threadIdx.x >> 2) * SLOT_WORDS;
+  QUAD_KERNEL_PROLOGUE(rows)
   u32* row = ks + (size_t)x * KS_ENT * L;
   u32 n[LPL], acc[LPL];
   load_lane_limbs(n, cs->n, ln);
@@ -1492,11 +1377,7 @@ k_modp_keyset_dual_exp(const u32* __restrict__ ks, const u32* __restrict__ tab2,
                        const uint8_t* __restrict__ c_be, int count, uint8_t* __restrict__ out_be,
                        const ModpConsts* __restrict__ cs) {
   __shared__ __attribute__((aligned(16))) u32 lds[NUMS_PER_BLOCK * SLOT_WORDS];
-  const Lane ln = make_lane();
-  const int xi = blockIdx.x * NUMS_PER_BLOCK + (threadIdx.x >> 2);
-  const bool live = xi < count;
-  const int x = live ? xi : count - 1;
-  u32* slot = lds + (threadIdx.x >> 2) * SLOT_WORDS;
+  QUAD_KERNEL_PROLOGUE(count)
   u32 n[LPL], acc[LPL];
   load_lane_limbs(n, cs->n, ln);
   const u32* kt = ks + (size_t)x * KS_SUB * KS_ENT * L;

@@ -49,12 +49,8 @@ namespace {
 
 using namespace mm;
 
-struct ModpConsts {             // same layout as in modp_kernels.hip: N, R^2 mod N, R mod N, plain 1
-  u32 n[L];
-  u32 r2[L];
-  u32 one_m[L];
-  u32 one[L];
-};
+using limbs::be256_limb;
+using limbs::ModpConsts;
 
 #ifndef PAIR_LDS_PAD
 #define PAIR_LDS_PAD 0          // bytes of unused LDS per workgroup: lowers the number of workgroups a CU holds (tuning)
@@ -99,36 +95,13 @@ __device__ __forceinline__ void load_pair_limbs(u32 (&a)[LP], const u32* __restr
   }
 }
 
-// plain almost-normalised value < 2N in `a` -> canonical residue in [0, N) as 256 big-endian bytes (as
-// store_canonical_be256 of modp_kernels.hip: exact carry propagation, one conditional subtraction, done by lane half 0)
+// plain almost-normalised value < 2N in `a` -> canonical residue in [0, N) as 256 big-endian bytes (the serial pass of
+// modp_limbs.h, done by lane half 0)
 __device__ __forceinline__ void store_canonical_pair(uint8_t* __restrict__ out, const u32 (&a)[LP], u32* slot,
                                                      const ModpConsts* __restrict__ cs, const PairLane& pl, bool write) {
   slot_store_pair(slot, a, pl);
   __builtin_amdgcn_wave_barrier();
-  if (pl.h == 0) {
-    u32 c = 0;
-#pragma nounroll
-    for (int j = 0; j < L; ++j) {
-      const u32 v = slot[j] + c;
-      slot[j] = v & MASK;
-      c = v >> W;
-    }
-    int ge = 1;
-#pragma nounroll
-    for (int j = L - 1; j >= 0; --j) {
-      const u32 x = slot[j], y = cs->n[j];
-      if (x != y) { ge = x > y; break; }
-    }
-    if (ge) {
-      u32 borrow = 0;
-#pragma nounroll
-      for (int j = 0; j < L; ++j) {
-        const u32 d = slot[j] - cs->n[j] - borrow;
-        borrow = (d >> 31) & 1;
-        slot[j] = d & MASK;
-      }
-    }
-  }
+  if (pl.h == 0) limbs::slot_canonicalize<L>(slot, cs->n);
   __builtin_amdgcn_wave_barrier();
   if (write) {
     // lane half h emits the little-endian 32-bit words 32h .. 32h+31 (byte-swapped, mirrored position)
@@ -136,12 +109,7 @@ __device__ __forceinline__ void store_canonical_pair(uint8_t* __restrict__ out, 
 #pragma nounroll
     for (int i = 0; i < 32; ++i) {
       const int wd = (int)pl.h * 32 + i;
-      const int bit = 32 * wd;
-      const int j = bit / W, s = bit % W;
-      u64 two = (u64)slot[j] | ((u64)(j + 1 < L ? slot[j + 1] : 0u) << W);
-      two >>= s;
-      if (2 * W - s < 32) two |= (u64)(j + 2 < L ? slot[j + 2] : 0u) << (2 * W - s);
-      out32[63 - wd] = __builtin_bswap32((u32)two);
+      out32[63 - wd] = __builtin_bswap32(limbs::slot_word32<L>(slot, wd));
     }
   }
   __builtin_amdgcn_wave_barrier();
@@ -345,22 +313,9 @@ __device__ __forceinline__ void pair_step_pf(u32 (&acc)[LP], bool sq, const u32*
   for (int k = 0; k < LP; ++k) acc[k] = r[k];
 }
 
-// limb j (W bits at bit offset W j) of a 256-byte big-endian integer (as be256_limb of modp_kernels.hip)
-__device__ __forceinline__ u32 be256_limb_pair(const uint8_t* __restrict__ be, int j) {
-  const int o = W * j;
-  const int p = o >> 3, sft = o & 7;
-  u64 w = 0;
-#pragma unroll
-  for (int t = 0; t < 5; ++t) {
-    const int idx = 255 - (p + t);
-    if (idx >= 0) w |= (u64)be[idx] << (8 * t);
-  }
-  return (u32)(w >> sft) & MASK;
-}
-
 __device__ __forceinline__ void load_be256_pair(u32 (&a)[LP], const uint8_t* __restrict__ be, const PairLane& pl) {
 #pragma unroll
-  for (int k = 0; k < LP; ++k) a[k] = be256_limb_pair(be, (int)pl.h * LP + k);
+  for (int k = 0; k < LP; ++k) a[k] = be256_limb(be, (int)pl.h * LP + k);
 }
 
 __device__ __forceinline__ void store_pair_limbs(u32* __restrict__ g, const u32 (&a)[LP], const PairLane& pl) {

@@ -15,14 +15,7 @@
 
 using namespace bnrow;
 
-namespace {
-struct ModpConsts {             // same layout as in modp_kernels.hip: N, R^2 mod N, R mod N, plain 1
-  u32 n[L];
-  u32 r2[L];
-  u32 one_m[L];
-  u32 one[L];
-};
-}  // namespace
+using limbs::ModpConsts;
 
 #ifndef ROW_SETPRIO
 #define ROW_SETPRIO 3

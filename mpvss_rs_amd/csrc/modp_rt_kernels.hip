@@ -7,7 +7,7 @@
 //
 // Layout and program shape are those of the group-14 kernels (modp_kernels.hip): one number per DPP quad, 16 numbers
 // per one-wave workgroup, the second operand of every product staged in LDS, 16-entry window tables in HBM.  The
-// product is bnrt::mont_mul (bn_quad_rt.h): three widths (5, 9, 18 limbs per lane), n0inv a run-time value.
+// product is bn::mont_mul at the widths of bn_quad_rt.h (5, 9, 18 limbs per lane), n0inv a run-time value.
 //
 // Cost follows the operands: the exponent loops run over the wave's largest exponent (4-bit windows), Horner's squarings
 // over the wave's largest reduced position.  Inputs are 256-byte big-endian values of any size: they enter a width by
@@ -29,19 +29,6 @@ template <int LPL> struct Occ { static constexpr int waves = 3; };
 template <> struct Occ<9> { static constexpr int waves = 4; };
 template <> struct Occ<5> { static constexpr int waves = 6; };
 
-// limb j (29 bits at bit 29 j) of a 256-byte big-endian integer; 0 above bit 2047
-__device__ __forceinline__ u32 be_limb(const uint8_t* __restrict__ be, int j) {
-  const int o = W * j;
-  const int p = o >> 3, s = o & 7;
-  u64 w = 0;
-#pragma unroll
-  for (int t = 0; t < 5; ++t) {
-    const int idx = 255 - (p + t);
-    if (idx >= 0) w |= (u64)be[idx] << (8 * t);
-  }
-  return (u32)(w >> s) & MASK;
-}
-
 // a = in R mod N (< 2N) for any 256-byte input: the input's 29-bit limbs go to the LDS slot (IN_ROWS of them), and one
 // long product with kin = 2^(29 (IN_ROWS + L)) mod N gives in kin 2^(-29 IN_ROWS) = in R, below N + kin in / 2^(29 IN_ROWS) < 2N.
 template <int LPL>
@@ -51,12 +38,12 @@ __device__ __forceinline__ void to_mont_in(u32 (&a)[LPL], u32* slot, const uint8
 #pragma unroll
   for (int j = (int)0; j < IN_ROWS; j += 4) {
     const int jj = j + (int)ln.q;
-    if (jj < IN_ROWS) slot[jj] = be_limb(in_be, jj);
+    if (jj < IN_ROWS) slot[jj] = limbs::be256_limb(in_be, jj);
   }
   u32 k[LPL];
-  lane_load<LPL>(k, cs->kin, ln);
+  load_lane_limbs<LPL>(k, cs->kin, ln);
   __builtin_amdgcn_wave_barrier();
-  mont_mul<LPL, false, IN_ROWS>(a, k, slot, n, n0inv, ln);
+  mont_mul<N0INV_RUNTIME, false, IN_ROWS / LPL>(a, k, slot, n, ln, n0inv);
   __builtin_amdgcn_wave_barrier();
 }
 
@@ -67,31 +54,7 @@ __device__ __forceinline__ void store_canonical(uint8_t* __restrict__ out, const
   constexpr int L = Width<LPL>::L;
   slot_store<LPL>(slot, a, ln);
   __builtin_amdgcn_wave_barrier();
-  if (ln.q == 0) {
-    u32 c = 0;
-#pragma nounroll
-    for (int j = 0; j < L; ++j) {
-      const u32 v = slot[j] + c;
-      slot[j] = v & MASK;
-      c = v >> W;
-    }
-    // value < 2N: subtract N once if value >= N
-    int ge = 1;
-#pragma nounroll
-    for (int j = L - 1; j >= 0; --j) {
-      const u32 x = slot[j], y = cs->n[j];
-      if (x != y) { ge = x > y; break; }
-    }
-    if (ge) {
-      u32 borrow = 0;
-#pragma nounroll
-      for (int j = 0; j < L; ++j) {
-        const u32 d = slot[j] - cs->n[j] - borrow;
-        borrow = (d >> 31) & 1;
-        slot[j] = d & MASK;
-      }
-    }
-  }
+  if (ln.q == 0) limbs::slot_canonicalize<L>(slot, cs->n);
   __builtin_amdgcn_wave_barrier();
   if (write) {
     // lane q emits little-endian 32-bit words 16q .. 16q+15 (byte-swapped, mirrored position); limbs >= L are zero
@@ -99,16 +62,7 @@ __device__ __forceinline__ void store_canonical(uint8_t* __restrict__ out, const
 #pragma unroll
     for (int i = 0; i < 16; ++i) {
       const int wd = (int)ln.q * 16 + i;
-      const int bit = 32 * wd;
-      const int j = bit / W, s = bit % W;
-      u32 v = 0;
-      if (j < L) {
-        u64 two = (u64)slot[j] | ((u64)(j + 1 < L ? slot[j + 1] : 0u) << W);
-        two >>= s;
-        if (2 * W - s < 32) two |= (u64)(j + 2 < L ? slot[j + 2] : 0u) << (2 * W - s);
-        v = (u32)two;
-      }
-      out32[63 - wd] = __builtin_bswap32(v);
+      out32[63 - wd] = __builtin_bswap32(limbs::slot_word32<L>(slot, wd));
     }
   }
   __builtin_amdgcn_wave_barrier();
@@ -163,9 +117,9 @@ __global__ void RT_KERNEL(LPL) k_rt_to_mont(const uint8_t* __restrict__ in_be, i
   u32* slot = lds + (threadIdx.x >> 2) * SLOT;
   const u32 n0inv = cs->n0inv;
   u32 n[LPL], a[LPL];
-  lane_load<LPL>(n, cs->n, ln);
+  load_lane_limbs<LPL>(n, cs->n, ln);
   to_mont_in<LPL>(a, slot, in_be + (size_t)x * 256, cs, n, n0inv, ln);
-  if (live) lane_store<LPL>(out_m + (size_t)x * L, a, ln);
+  if (live) store_lane_limbs<LPL>(out_m + (size_t)x * L, a, ln);
 }
 
 // ---------------------------------------------------------------------------------------
@@ -183,19 +137,19 @@ __global__ void RT_KERNEL(LPL) k_rt_table(const uint8_t* __restrict__ base_be, s
   u32* slot = lds + (threadIdx.x >> 2) * SLOT;
   const u32 n0inv = cs->n0inv;
   u32 n[LPL], b[LPL], acc[LPL];
-  lane_load<LPL>(n, cs->n, ln);
+  load_lane_limbs<LPL>(n, cs->n, ln);
   to_mont_in<LPL>(b, slot, base_be + (size_t)x * base_stride, cs, n, n0inv, ln);
   u32* my = tab + (size_t)x * 16 * L;
-  lane_load<LPL>(acc, cs->one_m, ln);
-  if (live) lane_store<LPL>(my, acc, ln);
-  if (live) lane_store<LPL>(my + L, b, ln);
+  load_lane_limbs<LPL>(acc, cs->one_m, ln);
+  if (live) store_lane_limbs<LPL>(my, acc, ln);
+  if (live) store_lane_limbs<LPL>(my + L, b, ln);
   slot_store<LPL>(slot, b, ln);
   __builtin_amdgcn_wave_barrier();
 #pragma unroll
   for (int k = 0; k < LPL; ++k) acc[k] = b[k];
   for (int e = 2; e < 16; ++e) {
-    mont_mul<LPL>(acc, acc, slot, n, n0inv, ln);
-    if (live) lane_store<LPL>(my + (size_t)e * L, acc, ln);
+    mont_mul<N0INV_RUNTIME>(acc, acc, slot, n, ln, n0inv);
+    if (live) store_lane_limbs<LPL>(my + (size_t)e * L, acc, ln);
   }
 }
 
@@ -223,7 +177,7 @@ __global__ void RT_KERNEL(LPL) k_rt_dual_exp(const u32* __restrict__ tab1, size_
   const uint8_t* e1 = e1_be + (size_t)x * e1_stride;
   const uint8_t* e2 = has2 ? e2_be + (size_t)x * e2_stride : e1;
   u32 n[LPL], acc[LPL];
-  lane_load<LPL>(n, cs->n, ln);
+  load_lane_limbs<LPL>(n, cs->n, ln);
   int nb = wave_max_bits(e1, ln);
   if (has2) {
     const int nb2 = wave_max_bits(e2, ln);
@@ -233,10 +187,10 @@ __global__ void RT_KERNEL(LPL) k_rt_dual_exp(const u32* __restrict__ tab1, size_
   // steps: 0..3 square, 4 times tab1[d1], 5 times tab2[d2], 6 next window, 7 final (times plain 1)
   int w = nw - 1, s;
   if (nw == 0) {
-    lane_load<LPL>(acc, cs->one_m, ln);
+    load_lane_limbs<LPL>(acc, cs->one_m, ln);
     s = 7;
   } else {
-    lane_load<LPL>(acc, t1 + (size_t)nibble(e1, w) * L, ln);
+    load_lane_limbs<LPL>(acc, t1 + (size_t)nibble(e1, w) * L, ln);
     s = has2 ? 5 : 6;
   }
   while (true) {
@@ -249,16 +203,16 @@ __global__ void RT_KERNEL(LPL) k_rt_dual_exp(const u32* __restrict__ tab1, size_
       }
     }
     if (s == 7) {
-      slot_fill<LPL>(slot, cs->one, ln);
+      slot_fill_from_global<LPL>(slot, cs->one, ln);
     } else if (s < 4) {
       slot_store<LPL>(slot, acc, ln);
     } else {
       const u32 d = nibble(s == 4 ? e1 : e2, w);
-      slot_fill<LPL>(slot, (s == 4 ? t1 : t2) + (size_t)d * L, ln);
+      slot_fill_from_global<LPL>(slot, (s == 4 ? t1 : t2) + (size_t)d * L, ln);
     }
     __builtin_amdgcn_wave_barrier();
-    if (s < 4) mont_mul<LPL, true>(acc, acc, slot, n, n0inv, ln);
-    else mont_mul<LPL>(acc, acc, slot, n, n0inv, ln);
+    if (s < 4) mont_mul<N0INV_RUNTIME, true>(acc, acc, slot, n, ln, n0inv);
+    else mont_mul<N0INV_RUNTIME>(acc, acc, slot, n, ln, n0inv);
     __builtin_amdgcn_wave_barrier();
     if (s == 7) break;
     ++s;
@@ -282,13 +236,13 @@ __global__ void RT_KERNEL(LPL) k_rt_mul(const u32* __restrict__ a_m, const u32* 
   u32* slot = lds + (threadIdx.x >> 2) * SLOT;
   const u32 n0inv = cs->n0inv;
   u32 n[LPL], acc[LPL];
-  lane_load<LPL>(n, cs->n, ln);
-  lane_load<LPL>(acc, a_m + (size_t)x * L, ln);
+  load_lane_limbs<LPL>(n, cs->n, ln);
+  load_lane_limbs<LPL>(acc, a_m + (size_t)x * L, ln);
 #pragma nounroll
   for (int step = 0; step < 2; ++step) {
-    slot_fill<LPL>(slot, step == 0 ? b_m + (size_t)x * L : cs->one, ln);
+    slot_fill_from_global<LPL>(slot, step == 0 ? b_m + (size_t)x * L : cs->one, ln);
     __builtin_amdgcn_wave_barrier();
-    mont_mul<LPL>(acc, acc, slot, n, n0inv, ln);
+    mont_mul<N0INV_RUNTIME>(acc, acc, slot, n, ln, n0inv);
     __builtin_amdgcn_wave_barrier();
   }
   store_canonical<LPL>(out_be + (size_t)x * 256, acc, slot, cs, ln, live);
@@ -316,8 +270,8 @@ __global__ void RT_KERNEL_LDS2(LPL) k_rt_commit_eval(const u32* __restrict__ cm,
   u32* oneslot = lds + 2 * RT_NUMS * SLOT;
   const u32 n0inv = cs->n0inv;
   u32 n[LPL], acc[LPL];
-  lane_load<LPL>(n, cs->n, ln);
-  if (threadIdx.x < 4) slot_fill<LPL>(oneslot, cs->one_m, ln);
+  load_lane_limbs<LPL>(n, cs->n, ln);
+  if (threadIdx.x < 4) slot_fill_from_global<LPL>(oneslot, cs->one_m, ln);
   const u64 qm1 = ((u64)cs->qm1_hi << 32) | cs->qm1_lo;
   u64 pos = (u64)positions[x];
   if (qm1 != 0) pos %= qm1;
@@ -330,7 +284,7 @@ __global__ void RT_KERNEL_LDS2(LPL) k_rt_commit_eval(const u32* __restrict__ cm,
   nb = __builtin_amdgcn_readfirstlane(nb);
   __builtin_amdgcn_wave_barrier();
 
-  lane_load<LPL>(acc, cm + (size_t)(t - 1) * L, ln);
+  load_lane_limbs<LPL>(acc, cm + (size_t)(t - 1) * L, ln);
   //   for j = t-2 .. 0:   base = acc; acc = topbit ? base : one
   //                       for bit = nb-2 .. 0: SQUARE; CONDMUL (by base or one, skipped if no lane needs it)
   //                       CMUL (by C_j)
@@ -339,12 +293,12 @@ __global__ void RT_KERNEL_LDS2(LPL) k_rt_commit_eval(const u32* __restrict__ cm,
   int j = t - 2, bit = 0, kind = K_FINAL;
   auto begin_coefficient = [&]() {
     if (nb == 0) {   // every i' of the wave is 0: acc^0 = 1
-      lane_load<LPL>(acc, cs->one_m, ln);
+      load_lane_limbs<LPL>(acc, cs->one_m, ln);
       kind = K_CMUL;
       return;
     }
     slot_store<LPL>(bslot, acc, ln);
-    if (!((pos >> (nb - 1)) & 1)) lane_load<LPL>(acc, cs->one_m, ln);
+    if (!((pos >> (nb - 1)) & 1)) load_lane_limbs<LPL>(acc, cs->one_m, ln);
     bit = nb - 2;
     kind = (bit >= 0) ? K_SQUARE : K_CMUL;
   };
@@ -359,14 +313,14 @@ __global__ void RT_KERNEL_LDS2(LPL) k_rt_commit_eval(const u32* __restrict__ cm,
       skip = __builtin_amdgcn_ballot_w64(mine) == 0;
       bptr = mine ? bslot : oneslot;
     } else if (kind == K_CMUL) {
-      slot_fill<LPL>(slot, cm + (size_t)j * L, ln);
+      slot_fill_from_global<LPL>(slot, cm + (size_t)j * L, ln);
     } else {
-      slot_fill<LPL>(slot, cs->one, ln);
+      slot_fill_from_global<LPL>(slot, cs->one, ln);
     }
     if (!skip) {
       __builtin_amdgcn_wave_barrier();
-      if (kind == K_SQUARE) mont_mul<LPL, true>(acc, acc, slot, n, n0inv, ln);
-      else mont_mul<LPL>(acc, acc, bptr, n, n0inv, ln);
+      if (kind == K_SQUARE) mont_mul<N0INV_RUNTIME, true>(acc, acc, slot, n, ln, n0inv);
+      else mont_mul<N0INV_RUNTIME>(acc, acc, bptr, n, ln, n0inv);
       __builtin_amdgcn_wave_barrier();
     }
     if (kind == K_FINAL) break;

@@ -1,4 +1,4 @@
-"""CPU checks of the run-time MODP group: an integer model of bnrt::mont_mul (mpvss_rs_amd/csrc/bn_quad_rt.h) at each
+"""CPU checks of the run-time MODP group: an integer model of bn::mont_mul (mpvss_rs_amd/csrc/bn_quad.h, the widths of bn_quad_rt.h) at each
 instantiated width with a run-time n0inv -- same step order, same lazy carries, same two-pass normalisation -- that proves
 the column bound for worst-case almost-normalised limbs; the long product that brings a 2048-bit input into a narrower width;
 and the host side of the C ABI (group creation, width choice, hash_to_scalar against the oracle)."""
@@ -30,7 +30,7 @@ def in_rows(lpl):
 
 
 def mont_model(a, b, N, lpl, rows, stats, square=False, bound_only=False):
-    """bnrt::mont_mul<lpl, square, rows> as integers: a has L = 4 lpl limbs, b has `rows` limbs; returns the L result limbs
+    """bn::mont_mul<N0INV_RUNTIME, square, rows / lpl> as integers: a has L = 4 lpl limbs, b has `rows` limbs; returns the L result limbs
     (bound_only: operands far above 2N as integers, only the accumulator bound is checked)"""
     L = 4 * lpl
     NL = limbs(N, L)
