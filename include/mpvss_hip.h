@@ -517,11 +517,13 @@ int mpvss_box_verify_wire(mpvss_ctx* ctx, const uint8_t* buf, size_t len, int* v
  * be used from any number of contexts and threads at once.  Elements and scalars keep the 256-byte big-endian encoding
  * of MPVSS_MODP_BYTES; inputs need not be reduced (a value >= q gives what BigInt::modpow / (a * b) % q give, modp.rs:154-156
  * validates nothing), outputs are canonical (< q).  The group's generators are those of ModpGroup: G = 2, g = G^2 = 4.
- * Protocol parity (verify_distribution, verify_shares) is specified for safe primes, which is what ModpGroup::init yields.
+ * Protocol parity is specified for safe primes, which is what ModpGroup::init yields; for another odd q the calls return
+ * without fault and are deterministic.
  * The entry points below mirror the group-14 ones with the handle added, lock the context like them and are safe for
- * concurrent callers on one context in the same sense.  Not offered for a run-time group: the block / pipeline forms,
- * verify_many, key sets, the dealer's one-call deal and the wire format; moduli above 2048 bits (their elements need
- * more than 256 bytes) are refused with MPVSS_E_INVALID. */
+ * concurrent callers on one context in the same sense.  The whole protocol is there: verification, the dealer (distribute,
+ * the one-call deal), extract_secret_share and reconstruct, with the scalar ring Z/(q-1) on host threads.  Not offered for a
+ * run-time group: the block / pipeline forms, verify_many, key sets and the wire format; moduli above 2048 bits (their
+ * elements need more than 256 bytes) are refused with MPVSS_E_INVALID. */
 typedef struct mpvss_modp_group mpvss_modp_group;
 /* q_be: q_len big-endian bytes (leading zeros allowed).  MPVSS_E_INVALID for an even q, q < 5 or q >= 2^2048. */
 int mpvss_modp_group_create(const uint8_t* q_be, size_t q_len, mpvss_modp_group** out);
@@ -554,6 +556,48 @@ int mpvss_modp_group_verify_distribution(mpvss_ctx* ctx, const mpvss_modp_group*
  * per-share hashes on the host */
 int mpvss_modp_group_verify_shares(mpvss_ctx* ctx, const mpvss_modp_group* grp, int space, const uint8_t* pk, const uint8_t* s,
                                    const uint8_t* y, const uint8_t* c, const uint8_t* r, size_t n, uint8_t* verdicts_host);
+
+/* out1[i] = bases[i]^e1[i], out2[i] = bases[i]^e2[i] mod q: two powers of one base per share, the shape of the dealer's
+ * (Y_i, a2_i) = (y_i^P(i), y_i^w_i) and the participant's (S_i, a2_i) = (Y_i^(1/x_i), Y_i^(w_i/x_i)).  Large batches share the
+ * squarings (right to left over 4-bit windows into buckets in HBM, zeroed before the call returns); small ones run two
+ * left-to-right exponent sets in one launch.  Same bytes either way.  All arrays n x 256 bytes in `space`. */
+int mpvss_modp_group_batch_twin_exp(mpvss_ctx* ctx, const mpvss_modp_group* grp, int space, const uint8_t* bases, const uint8_t* e1,
+                                    const uint8_t* e2, size_t n, uint8_t* out1, uint8_t* out2);
+/* the batch size (shares of one call, or of one chunk of a longer one) from which this group's width takes the shared-squarings
+ * kernel; smaller batches run the two exponent sets.  Host only; informational -- the results do not depend on it. */
+int mpvss_modp_group_twin_min_shares(const mpvss_modp_group* grp);
+/* dealer's group side, src/participant.rs:160-286 with p_i = P(i) mod (q-1) and the witnesses as input: same contract as
+ * mpvss_modp_distribute */
+int mpvss_modp_group_distribute(mpvss_ctx* ctx, const mpvss_modp_group* grp, int space, const uint8_t* commitments, size_t t,
+                                const int64_t* positions, const uint8_t* pubkeys, const uint8_t* p_values, const uint8_t* witnesses,
+                                size_t n, uint8_t* x_out, uint8_t* y_out, uint8_t* a1_out, uint8_t* a2_out, uint8_t* digest32_out);
+/* the dealer's whole box in one call from HOST buffers: same contract as mpvss_modp_deal (x_out, a1_out, a2_out, digest32_out
+ * and challenge_out256 optional; t <= n; t == 0 with n > 0 and a negative position are MPVSS_E_INVALID; n == 0 gives the digest
+ * of the empty transcript).  P(i) and the responses are host-thread work here, X_i = g^P(i) and a1_i = g^w_i run over the
+ * window table of g = 4.  Every buffer of the call that held coefficients, P(i), witnesses or buckets is zeroed before it
+ * returns, on error paths too. */
+int mpvss_modp_group_deal(mpvss_ctx* ctx, const mpvss_modp_group* grp, const uint8_t* coeffs_host, size_t t,
+                          const int64_t* positions_host, const uint8_t* pubkeys_host, const uint8_t* witnesses_host, size_t n,
+                          uint8_t* x_out, uint8_t* y_out, uint8_t* a1_out, uint8_t* a2_out, uint8_t* digest32_out,
+                          uint8_t* challenge_out256, uint8_t* r_out);
+/* n participants' extract_secret_share, src/participant.rs:294-353: same contract as mpvss_modp_extract_shares (xinv = x^-1 mod
+ * (q-1) and the witnesses are inputs, the per-share challenge is hashed on the host).  A row whose Y_i is 0 mod q gives the
+ * reference's values (S_i = 0, a2_i = 0^w_i). */
+int mpvss_modp_group_extract_shares(mpvss_ctx* ctx, const mpvss_modp_group* grp, int space, const uint8_t* pk, const uint8_t* y,
+                                    const uint8_t* xinv, const uint8_t* w, size_t n, uint8_t* s_out, uint8_t* c_out_host);
+/* G^s and the mask from m shares, src/participant.rs:462-561: same contract as mpvss_modp_reconstruct (positions >= 1 and pairwise
+ * different; a Lagrange denominator without inverse mod (q-1)/2, an even (q-1)/2, or a share that is 0 mod q where its factor
+ * has to be inverted gives MPVSS_E_INVALID).  mask_out32 = int_BE(SHA256(minimal bytes(G^s))) mod q, 32 bytes big-endian. */
+int mpvss_modp_group_reconstruct(mpvss_ctx* ctx, const mpvss_modp_group* grp, int space, const int64_t* positions_host,
+                                 const uint8_t* shares, size_t m, uint8_t* gs_out256, uint8_t* mask_out32);
+/* the scalar ring Z/(q-1) of the handle (host only, no context): the contracts of mpvss_modp_scalar_mul, _scalar_sub,
+ * _dleq_responses and _poly_eval -- 256-byte big-endian scalars, inputs need not be reduced, threads <= 0: up to 16 */
+int mpvss_modp_group_scalar_mul(const mpvss_modp_group* grp, const uint8_t* a256, const uint8_t* b256, uint8_t* out256);
+int mpvss_modp_group_scalar_sub(const mpvss_modp_group* grp, const uint8_t* a256, const uint8_t* b256, uint8_t* out256);
+int mpvss_modp_group_dleq_responses(const mpvss_modp_group* grp, const uint8_t* w, const uint8_t* alpha, const uint8_t* c,
+                                    int c_per_share, size_t n, uint8_t* r_out, int threads);
+int mpvss_modp_group_poly_eval(const mpvss_modp_group* grp, const uint8_t* coeffs, size_t t, const int64_t* positions, size_t n,
+                               uint8_t* out, int threads);
 
 /* ---- hashing helpers (host only; Group::hash_to_scalar, src/groups/modp.rs:142-148) ------ */
 

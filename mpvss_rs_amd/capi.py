@@ -49,6 +49,9 @@ EXPORTED_SYMBOLS = (
     "mpvss_modp_group_create", "mpvss_modp_group_destroy", "mpvss_modp_group_bits", "mpvss_modp_group_limbs_per_lane",
     "mpvss_modp_group_hash_to_scalar", "mpvss_modp_group_batch_exp", "mpvss_modp_group_batch_mul", "mpvss_modp_group_commit_eval",
     "mpvss_modp_group_dleq_commitments", "mpvss_modp_group_verify_distribution", "mpvss_modp_group_verify_shares",
+    "mpvss_modp_group_batch_twin_exp", "mpvss_modp_group_distribute", "mpvss_modp_group_deal", "mpvss_modp_group_extract_shares",
+    "mpvss_modp_group_reconstruct", "mpvss_modp_group_scalar_mul", "mpvss_modp_group_scalar_sub", "mpvss_modp_group_dleq_responses",
+    "mpvss_modp_group_poly_eval", "mpvss_modp_group_twin_min_shares",
 )
 
 GROUP_SECP256K1 = 1
@@ -217,6 +220,16 @@ def load_library() -> C.CDLL:
     lib.mpvss_modp_group_verify_distribution.argtypes = [vp, vp, ci, u8p, sz, i64p, u8p, u8p, u8p, sz, u8p,
                                                          C.POINTER(ci), u8p, u8p, u8p, u8p]
     lib.mpvss_modp_group_verify_shares.argtypes = [vp, vp, ci, u8p, u8p, u8p, u8p, u8p, sz, u8p]
+    lib.mpvss_modp_group_batch_twin_exp.argtypes = [vp, vp, ci, u8p, u8p, u8p, sz, u8p, u8p]
+    lib.mpvss_modp_group_distribute.argtypes = [vp, vp, ci, u8p, sz, i64p, u8p, u8p, u8p, sz, u8p, u8p, u8p, u8p, u8p]
+    lib.mpvss_modp_group_deal.argtypes = [vp, vp, u8p, sz, i64p, u8p, u8p, sz, u8p, u8p, u8p, u8p, u8p, u8p, u8p]
+    lib.mpvss_modp_group_extract_shares.argtypes = [vp, vp, ci, u8p, u8p, u8p, u8p, sz, u8p, u8p]
+    lib.mpvss_modp_group_reconstruct.argtypes = [vp, vp, ci, i64p, u8p, sz, u8p, u8p]
+    lib.mpvss_modp_group_scalar_mul.argtypes = [vp, u8p, u8p, u8p]
+    lib.mpvss_modp_group_scalar_sub.argtypes = [vp, u8p, u8p, u8p]
+    lib.mpvss_modp_group_dleq_responses.argtypes = [vp, u8p, u8p, u8p, ci, sz, u8p, ci]
+    lib.mpvss_modp_group_poly_eval.argtypes = [vp, u8p, sz, i64p, sz, u8p, ci]
+    lib.mpvss_modp_group_twin_min_shares.argtypes = [vp]
     return lib
 
 
@@ -257,6 +270,11 @@ class ModpGroup:
     @property
     def limbs_per_lane(self) -> int:
         return self.lib.mpvss_modp_group_limbs_per_lane(self.handle)
+
+    @property
+    def twin_min_shares(self) -> int:
+        """batch size from which group_batch_twin_exp / group_deal / group_extract_shares take the shared-squarings kernel"""
+        return self.lib.mpvss_modp_group_twin_min_shares(self.handle)
 
     def hash_to_scalar(self, data: bytes) -> bytes:
         kd, pd = _buf(data if data else b"\0")
@@ -459,6 +477,61 @@ class Engine:
         self._check(self.lib.mpvss_modp_group_verify_shares(self.ctx, grp.handle, MPVSS_HOST, k[0][1], k[1][1], k[2][1], k[3][1],
                                                             k[4][1], n, po), "group_verify_shares")
         return bytes(ko)[:n]
+
+    def group_batch_twin_exp(self, grp: "ModpGroup", bases: bytes, e1: bytes, e2: bytes) -> Tuple[bytes, bytes]:
+        """(bases^e1, bases^e2): two powers of one base per share"""
+        n = len(bases) // EB
+        k = [_buf(x) for x in (bases, e1, e2)]
+        k1, p1 = _out(n * EB); k2, p2 = _out(n * EB)
+        self._check(self.lib.mpvss_modp_group_batch_twin_exp(self.ctx, grp.handle, MPVSS_HOST, k[0][1], k[1][1], k[2][1], n, p1, p2),
+                    "group_batch_twin_exp")
+        return bytes(k1)[: n * EB], bytes(k2)[: n * EB]
+
+    def group_distribute(self, grp: "ModpGroup", commitments: bytes, positions: Sequence[int], pubkeys: bytes, p_values: bytes,
+                         witnesses: bytes):
+        t = len(commitments) // EB
+        n = len(positions)
+        kc, pc = _buf(commitments or None); ky, py = _buf(pubkeys or None); kp, pp = _buf(p_values or None)
+        kw, pw = _buf(witnesses or None)
+        pos = (C.c_int64 * max(n, 1))(*positions)
+        outs = [_out(n * EB) for _ in range(4)]
+        kd, pd = _out(32)
+        self._check(self.lib.mpvss_modp_group_distribute(self.ctx, grp.handle, MPVSS_HOST, pc, t, C.cast(pos, C.c_void_p), py, pp, pw,
+                                                         n, outs[0][1], outs[1][1], outs[2][1], outs[3][1], pd),
+                    "group_distribute")
+        X, Y, a1, a2 = (bytes(o[0])[: n * EB] for o in outs)
+        return {"X": X, "Y": Y, "a1": a1, "a2": a2, "digest": bytes(kd)[:32]}
+
+    def group_deal(self, grp: "ModpGroup", coeffs: bytes, positions: Sequence[int], pubkeys: bytes, witnesses: bytes) -> dict:
+        """the dealer's whole box from host buffers in one call: X, Y, a1, a2, digest, challenge, responses"""
+        n = len(positions)
+        pos = (C.c_int64 * max(n, 1))(*positions)
+        k = [_buf(b or None) for b in (coeffs, pubkeys, witnesses)]
+        outs = [_out(n * EB) for _ in range(5)]
+        kd, pd = _out(32)
+        kc, pc = _out(EB)
+        self._check(self.lib.mpvss_modp_group_deal(self.ctx, grp.handle, k[0][1], len(coeffs) // EB, C.cast(pos, C.c_void_p), k[1][1],
+                                                   k[2][1], n, outs[0][1], outs[1][1], outs[2][1], outs[3][1], pd, pc, outs[4][1]),
+                    "group_deal")
+        X, Y, a1, a2, r = (bytes(o[0])[: n * EB] for o in outs)
+        return {"X": X, "Y": Y, "a1": a1, "a2": a2, "digest": bytes(kd)[:32], "challenge": bytes(kc)[:EB], "responses": r}
+
+    def group_extract_shares(self, grp: "ModpGroup", pk: bytes, y: bytes, xinv: bytes, w: bytes) -> Tuple[bytes, bytes]:
+        n = len(pk) // EB
+        k = [_buf(x) for x in (pk, y, xinv, w)]
+        ks, ps = _out(n * EB); kc, pc = _out(n * EB)
+        self._check(self.lib.mpvss_modp_group_extract_shares(self.ctx, grp.handle, MPVSS_HOST, k[0][1], k[1][1], k[2][1], k[3][1], n,
+                                                             ps, pc), "group_extract_shares")
+        return bytes(ks)[: n * EB], bytes(kc)[: n * EB]
+
+    def group_reconstruct(self, grp: "ModpGroup", positions: Sequence[int], shares: bytes):
+        """(G^s, mask) from m decrypted shares: secret = int(mask) ^ U"""
+        m = len(positions)
+        pos = (C.c_int64 * max(m, 1))(*positions)
+        ks, ps = _buf(shares or None); kg, pg = _out(EB); km, pm = _out(32)
+        self._check(self.lib.mpvss_modp_group_reconstruct(self.ctx, grp.handle, MPVSS_HOST, C.cast(pos, C.c_void_p), ps, m, pg, pm),
+                    "group_reconstruct")
+        return bytes(kg)[:EB], bytes(km)[:32]
 
     # ---- sharded verification (one engine per GPU; see mpvss_rs_amd/sharding.py)
     def verify_block_compute(self, commitments: bytes, positions: Sequence[int], pubkeys: bytes, shares: bytes,
@@ -1045,6 +1118,44 @@ def poly_eval(group: int, coeffs: bytes, positions: Sequence[int], threads: int 
     if rc != 0:
         raise EngineError(f"poly_eval failed: {rc}")
     return bytes(ko)[: n * sw]
+
+
+# ---- scalar ring of a run-time MODP group (host only): Z/(q-1) of the handle, 256-byte big-endian scalars
+def group_scalar_mul(grp: "ModpGroup", a: bytes, b: bytes) -> bytes:
+    ka, pa = _buf(a); kb, pb = _buf(b); ko, po = _out(EB)
+    rc = grp.lib.mpvss_modp_group_scalar_mul(grp.handle, pa, pb, po)
+    if rc != 0:
+        raise EngineError(f"group_scalar_mul failed: {rc}")
+    return bytes(ko)[:EB]
+
+
+def group_scalar_sub(grp: "ModpGroup", a: bytes, b: bytes) -> bytes:
+    ka, pa = _buf(a); kb, pb = _buf(b); ko, po = _out(EB)
+    rc = grp.lib.mpvss_modp_group_scalar_sub(grp.handle, pa, pb, po)
+    if rc != 0:
+        raise EngineError(f"group_scalar_sub failed: {rc}")
+    return bytes(ko)[:EB]
+
+
+def group_dleq_responses(grp: "ModpGroup", w: bytes, alpha: bytes, c: bytes, threads: int = 0) -> bytes:
+    """r_i = w_i - alpha_i * c_i mod (q-1); c is one scalar or one per proof"""
+    n = len(w) // EB
+    kw, pw = _buf(w or None); ka, pa = _buf(alpha or None); kc, pc = _buf(c); ko, po = _out(n * EB)
+    rc = grp.lib.mpvss_modp_group_dleq_responses(grp.handle, pw, pa, pc, int(len(c) != EB), n, po, threads)
+    if rc != 0:
+        raise EngineError(f"group_dleq_responses failed: {rc}")
+    return bytes(ko)[: n * EB]
+
+
+def group_poly_eval(grp: "ModpGroup", coeffs: bytes, positions: Sequence[int], threads: int = 0) -> bytes:
+    """P(i) mod (q-1) for every position"""
+    t, n = len(coeffs) // EB, len(positions)
+    kc, pc = _buf(coeffs or None); ko, po = _out(n * EB)
+    pos = (C.c_int64 * max(n, 1))(*positions)
+    rc = grp.lib.mpvss_modp_group_poly_eval(grp.handle, pc, t, C.cast(pos, C.c_void_p), n, po, threads)
+    if rc != 0:
+        raise EngineError(f"group_poly_eval failed: {rc}")
+    return bytes(ko)[: n * EB]
 
 
 # ---- flat wire format ("MPVSSBX1") ---------------------------------------------------------------------------------

@@ -24,6 +24,7 @@ using bn::MASK;
 using bn::mont_mul;
 using bn::N0INV_RUNTIME;
 using bn::slot_fill_from_global;
+using bn::slot_load;
 using bn::slot_store;
 using bn::store_lane_limbs;
 using bn::u32;

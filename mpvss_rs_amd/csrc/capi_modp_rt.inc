@@ -9,6 +9,8 @@ struct mpvss_modp_group {
   uint8_t sub_be[256];       // (q-1)/2 big-endian: hash_to_scalar's modulus (modp.rs:142-148)
   uint8_t g_be[256];         // subgroup generator 4 (modp.rs:65-66 for any q >= 5)
   uint8_t G_be[256];         // main generator 2
+  uint8_t q_be[256];
+  hsc::ModulusRt mod, ord, sub;   // q, q - 1 and (q-1)/2 for the host-side scalar ring (host_scalar.h)
 };
 
 namespace {
@@ -27,40 +29,28 @@ void rt_from_be(RtNum x, const uint8_t* be, size_t len) {
 void rt_to_be256(const RtNum x, uint8_t* be) {
   for (int i = 0; i < 256; ++i) be[255 - i] = (uint8_t)(x[i / 4] >> (8 * (i % 4)));
 }
-int rt_cmp(const RtNum a, const RtNum b) {
-  for (int i = RTW - 1; i >= 0; --i)
-    if (a[i] != b[i]) return a[i] > b[i] ? 1 : -1;
-  return 0;
-}
-void rt_sub(RtNum a, const RtNum b) {   // a -= b, a >= b
-  uint64_t borrow = 0;
-  for (int i = 0; i < RTW; ++i) {
-    const uint64_t d = (uint64_t)a[i] - b[i] - borrow;
-    a[i] = (uint32_t)d;
-    borrow = (d >> 63) & 1;
-  }
-}
-// a = (2 a + bit) mod n, a < n
-void rt_dbl_mod(RtNum a, uint32_t bit, const RtNum n) {
-  uint32_t c = bit;
-  for (int i = 0; i < RTW; ++i) {
-    const uint32_t v = (a[i] << 1) | c;
-    c = a[i] >> 31;
-    a[i] = v;
-  }
-  if (rt_cmp(a, n) >= 0) rt_sub(a, n);
-}
 int rt_bits(const RtNum a) {
   for (int i = RTW - 1; i >= 0; --i)
     if (a[i]) return 32 * i + 32 - __builtin_clz(a[i]);
   return 0;
 }
-// 2^e mod n
-void rt_pow2_mod(RtNum out, int e, const RtNum n) {
+void rt_to_limbs64(const RtNum x, uint64_t* v) {
+  for (int i = 0; i < 32; ++i) v[i] = (uint64_t)x[2 * i] | ((uint64_t)x[2 * i + 1] << 32);
+}
+// 2^e mod M: products of powers of two below 2^2048
+void rt_pow2_mod(RtNum out, int e, const hsc::ModulusRt& M) {
+  uint64_t r[32], t[32];
+  memset(r, 0, sizeof(r));
+  r[0] = 1;
+  while (e > 0) {
+    const int c = e < 2047 ? e : 2047;
+    memset(t, 0, sizeof(t));
+    t[c / 64] = (uint64_t)1 << (c % 64);
+    M.mulmod(r, r, t);
+    e -= c;
+  }
   memset(out, 0, sizeof(RtNum));
-  out[0] = 1;
-  if (rt_cmp(out, n) >= 0) rt_sub(out, n);
-  for (int i = 0; i < e; ++i) rt_dbl_mod(out, 0, n);
+  for (int i = 0; i < 32; ++i) { out[2 * i] = (uint32_t)r[i]; out[2 * i + 1] = (uint32_t)(r[i] >> 32); }
 }
 // 29-bit limbs (zero above L)
 void rt_limbs(const RtNum x, uint32_t* limbs, int L) {
@@ -146,13 +136,13 @@ int rt_stage_commitments(mpvss_ctx* ctx, const mpvss_modp_group* grp, const modp
 
 // hash_to_scalar of the group: int(SHA-256(data)) mod (q-1)/2, 256 bytes big-endian
 void rt_hash_to_scalar(const mpvss_modp_group* grp, const uint8_t* data, size_t len, uint8_t out256[256]) {
-  uint8_t h[32];
-  mpvss::sha256(data, len, h);
-  RtNum m, r;
-  rt_from_be(m, grp->sub_be, EB);
-  memset(r, 0, sizeof(RtNum));
-  for (int i = 0; i < 256; ++i) rt_dbl_mod(r, (h[i / 8] >> (7 - i % 8)) & 1, m);
-  rt_to_be256(r, out256);
+  uint8_t h[EB];
+  memset(h, 0, EB - 32);
+  mpvss::sha256(data, len, h + EB - 32);
+  uint64_t x[32];
+  hsc::from_bytes<32>(x, h, true);
+  grp->sub.reduce1(x);
+  hsc::to_bytes<32>(out256, x, true);
 }
 
 bool rt_bad_group(const mpvss_modp_group* grp) { return grp == nullptr || grp->lpl == 0; }
@@ -178,10 +168,18 @@ extern "C" int mpvss_modp_group_create(const uint8_t* q_be, size_t q_len, mpvss_
   const int L = 4 * g->lpl;
   const int in_rows = modp_rt_in_rows(g->lpl);
   rt_limbs(q, g->c.n, L);
+  uint64_t q64[32];
+  rt_to_limbs64(q, q64);
+  g->mod.set(q64);
+  q64[0] -= 1;                                   // q is odd
+  g->ord.set(q64);
+  for (int i = 0; i < 32; ++i) q64[i] = (q64[i] >> 1) | (i + 1 < 32 ? q64[i + 1] << 63 : 0);
+  g->sub.set(q64);
+  rt_to_be256(q, g->q_be);
   RtNum k;
-  rt_pow2_mod(k, 29 * (in_rows + L), q);
+  rt_pow2_mod(k, 29 * (in_rows + L), g->mod);
   rt_limbs(k, g->c.kin, L);
-  rt_pow2_mod(k, 29 * L, q);
+  rt_pow2_mod(k, 29 * L, g->mod);
   rt_limbs(k, g->c.one_m, L);
   g->c.one[0] = 1;
   // n0inv = -q^-1 mod 2^29 (Newton: every step doubles the correct low bits)
@@ -472,6 +470,451 @@ extern "C" int mpvss_modp_group_verify_shares(mpvss_ctx* ctx, const mpvss_modp_g
       rt_hash_to_scalar(grp, digest, 32, cc);     // src/dleq.rs:119-126
       verdicts_host[off + i] = memcmp(cc, C + i * EB, EB) == 0 ? 1 : 0;
     }
+  }
+  RET_IF(spans_collect(ctx));
+  return MPVSS_OK;
+}
+
+// =====================================================================================================================
+// The rest of the protocol for a run-time group: the scalar ring Z/(q-1) on the host, the dealer (distribute / deal),
+// extract_secret_share and reconstruct.
+// =====================================================================================================================
+
+// ---- scalar ring (host only, no context): the group-14 contracts of capi_scalar.inc with q - 1 of the handle ---------------
+extern "C" int mpvss_modp_group_scalar_mul(const mpvss_modp_group* grp, const uint8_t* a256, const uint8_t* b256, uint8_t* out256) {
+  if (rt_bad_group(grp) || !a256 || !b256 || !out256) return MPVSS_E_INVALID;
+  scalar_mul_bytes<32>(grp->ord, true, a256, b256, out256);              // modp.rs:180-182
+  return MPVSS_OK;
+}
+extern "C" int mpvss_modp_group_scalar_sub(const mpvss_modp_group* grp, const uint8_t* a256, const uint8_t* b256, uint8_t* out256) {
+  if (rt_bad_group(grp) || !a256 || !b256 || !out256) return MPVSS_E_INVALID;
+  scalar_sub_bytes<32>(grp->ord, true, a256, b256, out256);              // modp.rs:184-192
+  return MPVSS_OK;
+}
+extern "C" int mpvss_modp_group_dleq_responses(const mpvss_modp_group* grp, const uint8_t* w, const uint8_t* alpha, const uint8_t* c,
+                                               int c_per_share, size_t n, uint8_t* r_out, int threads) {
+  if (rt_bad_group(grp)) return MPVSS_E_INVALID;
+  if (n == 0) return MPVSS_OK;
+  if (!w || !alpha || !c || !r_out) return MPVSS_E_INVALID;
+  responses_bytes<32>(grp->ord, true, w, alpha, c, c_per_share ? EB : 0, n, r_out, host_threads(threads));
+  return MPVSS_OK;
+}
+extern "C" int mpvss_modp_group_poly_eval(const mpvss_modp_group* grp, const uint8_t* coeffs, size_t t, const int64_t* positions,
+                                          size_t n, uint8_t* out, int threads) {
+  if (rt_bad_group(grp)) return MPVSS_E_INVALID;
+  if (n == 0) return MPVSS_OK;
+  if (!coeffs || !positions || !out || t == 0) return MPVSS_E_INVALID;
+  for (size_t i = 0; i < n; ++i)
+    if (positions[i] < 0) return MPVSS_E_INVALID;
+  poly_eval_bytes<32>(grp->ord, true, coeffs, t, positions, n, out, host_threads(threads));
+  return MPVSS_OK;
+}
+
+namespace {
+
+// The batch size from which the right-to-left twin kernel (shared squarings, 3 127 operations per share at 2048 bits, but a
+// chain of that length) is taken instead of two left-to-right exponent sets in one launch (5 142 operations, chains of 2 571).
+// Below it the chip is not full and the shorter chain wins.  Both paths give identical bytes.
+// Measured per width, the same at 9 and 18 limbs per lane: profiles/modp_rt_deal_rate.txt (the tuning builds of
+// `make twin-ab` pin it with -DMPVSS_RT_TWIN_MIN_SHARES=n).
+#ifdef MPVSS_RT_TWIN_MIN_SHARES
+size_t rt_twin_min_shares(int) { return (size_t)(MPVSS_RT_TWIN_MIN_SHARES); }
+#else
+size_t rt_twin_min_shares(int) { return 16384; }
+#endif
+
+// zero what held secrets whichever way the call ends (context lock held): device buffers in stream order, then the stream is
+// drained; host vectors word by word
+struct RtWipe {
+  mpvss_ctx* ctx;
+  std::vector<std::pair<DevBuf*, size_t>> dev;
+  std::vector<std::vector<uint8_t>*> host;
+  void device(DevBuf& b, size_t bytes) { dev.push_back({&b, bytes}); }
+  ~RtWipe() {
+    for (auto* v : host) {
+      volatile uint8_t* wp = v->data();
+      for (size_t i = 0; i < v->size(); ++i) wp[i] = 0;
+    }
+    if (dev.empty() || hipSetDevice(ctx->device) != hipSuccess) return;
+    for (auto& d : dev)
+      if (d.first->p) (void)hipMemsetAsync(d.first->p, 0, d.second < d.first->cap ? d.second : d.first->cap, ctx->stream);
+    (void)hipStreamSynchronize(ctx->stream);
+  }
+};
+
+// Shares per k_rt_twin_exp launch: 4096 waves, more than the chip holds at once, and it bounds the bucket scratch the context
+// keeps at 2 x 15 x 65536 numbers (540 MiB at 18 limbs per lane, 270 MiB at 9, 150 MiB at 5) whatever MAX_CHUNK is.
+constexpr size_t RT_TWIN_LAUNCH = 65536;
+
+// out1 = B^e1, out2 = B^e2 for cnt shares (device pointers, one chunk).  Large batches: k_rt_twin_exp over bucket scratch of
+// the context, of which `wipe` zeroes what the call used; small ones, two left-to-right exponent sets over the bases' tables
+// in one launch.
+int rt_twin_dev(mpvss_ctx* ctx, const mpvss_modp_group* grp, const modp_rt_consts* dc, const uint8_t* bases, const uint8_t* e1,
+                const uint8_t* e2, size_t cnt, uint8_t* out1, uint8_t* out2, RtWipe& wipe) {
+  if (cnt >= rt_twin_min_shares(grp->lpl)) {
+    const size_t bytes = modp_rt_twin_scratch_bytes(grp->lpl, (int)std::min(cnt, RT_TWIN_LAUNCH));
+    RET_IF(ensure(ctx, ctx->rt_buckets, bytes));
+    wipe.device(ctx->rt_buckets, bytes);
+    for (size_t off = 0; off < cnt; off += RT_TWIN_LAUNCH) {
+      const size_t m = std::min(cnt - off, RT_TWIN_LAUNCH);
+      TIMED_LAUNCH(ctx, 3, modp_rt_launch_twin_exp(grp->lpl, bases + off * EB, e1 + off * EB, e2 + off * EB, (int)m,
+                                                   (uint32_t*)ctx->rt_buckets.p, out1 + off * EB, out2 + off * EB, dc, ctx->stream));
+    }
+    return 0;
+  }
+  const uint32_t* tb;
+  RET_IF(rt_tables(ctx, grp, dc, bases, EB, cnt, ctx->rt_tab1, &tb));
+  TIMED_LAUNCH(ctx, 3, modp_rt_launch_exp_sets(grp->lpl, tb, 16 * rt_L(grp), e1, e2, (int)cnt, out1, out2, dc, ctx->stream));
+  return 0;
+}
+
+// out = base^e for one shared base (host bytes) and cnt exponents on the device
+int rt_fixed_base_dev(mpvss_ctx* ctx, const mpvss_modp_group* grp, const modp_rt_consts* dc, const uint8_t* base_host, const uint8_t* e,
+                      size_t cnt, uint8_t* out, int timer) {
+  const uint8_t* db;
+  RET_IF(rt_stage_small(ctx, base_host, ctx->rt_small[0], &db));
+  const uint32_t* tg;
+  RET_IF(rt_tables(ctx, grp, dc, db, 0, 1, ctx->rt_tabg, &tg));
+  TIMED_LAUNCH(ctx, timer, modp_rt_launch_dual_exp(grp->lpl, tg, 0, nullptr, 0, e, EB, nullptr, 0, (int)cnt, out, dc, ctx->stream));
+  return 0;
+}
+
+bool rt_zero_mod_q(const mpvss_modp_group* grp, const uint8_t* v256) {
+  uint64_t x[32];
+  hsc::from_bytes<32>(x, v256, true);
+  grp->mod.reduce1(x);
+  uint64_t o = 0;
+  for (int i = 0; i < 32; ++i) o |= x[i];
+  return o == 0;
+}
+
+// The dealer's group side for n shares: X_i (commit_eval, or g^p_i when commitments is null: the dealer's own polynomial),
+// Y_i = y_i^p_i and a2_i = y_i^w_i through the twin path, a1_i = g^w_i, and the transcript digest.  Outputs in `space`
+// (the host ones optional).  p_values and witnesses staged on the device, and the buckets, are zeroed by `wipe`.
+int rt_distribute_locked(mpvss_ctx* ctx, const mpvss_modp_group* grp, int space, const uint8_t* commitments, size_t t,
+                         const int64_t* positions, const uint8_t* pubkeys, const uint8_t* p_values, const uint8_t* witnesses, size_t n,
+                         uint8_t* x_out, uint8_t* y_out, uint8_t* a1_out, uint8_t* a2_out, uint8_t* digest32_out, RtWipe& wipe) {
+  mpvss::Sha256 h;
+  if (n > 0) {
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    spans_reset(ctx);
+    const modp_rt_consts* dc;
+    RET_IF(rt_upload(ctx, grp, &dc));
+    if (commitments) RET_IF(rt_stage_commitments(ctx, grp, dc, space, commitments, t));
+    const bool dev = space == MPVSS_DEVICE;
+    const size_t chunk = std::min(n, MAX_CHUNK);
+    std::vector<uint8_t> hX(chunk * EB), hY(chunk * EB), h1(chunk * EB), h2(chunk * EB);
+    for (size_t off = 0; off < n; off += MAX_CHUNK) {
+      const size_t cnt = (n - off < MAX_CHUNK) ? n - off : MAX_CHUNK;
+      const void *dy, *dp, *dw;
+      RET_IF(stage_in(ctx, space, pubkeys + off * EB, cnt * EB, ctx->rt_in[1], &dy));
+      if (!dev) { wipe.device(ctx->rt_in[2], cnt * EB); wipe.device(ctx->rt_in[3], cnt * EB); }
+      RET_IF(stage_in(ctx, space, p_values + off * EB, cnt * EB, ctx->rt_in[2], &dp));
+      RET_IF(stage_in(ctx, space, witnesses + off * EB, cnt * EB, ctx->rt_in[3], &dw));
+      uint8_t *dX = x_out + off * EB, *dY = y_out + off * EB, *d1 = a1_out + off * EB, *d2 = a2_out + off * EB;
+      if (!dev) {
+        for (DevBuf* b : {&ctx->rt_out[0], &ctx->rt_out[1], &ctx->rt_out[2], &ctx->rt_out_y}) RET_IF(ensure(ctx, *b, cnt * EB));
+        dX = (uint8_t*)ctx->rt_out[0].p;
+        d1 = (uint8_t*)ctx->rt_out[1].p;
+        d2 = (uint8_t*)ctx->rt_out[2].p;
+        dY = (uint8_t*)ctx->rt_out_y.p;
+      }
+      if (commitments) {
+        const int64_t* dpos;
+        RET_IF(stage_positions(ctx, space, positions + off, cnt, &dpos));
+        RET_IF(rt_commit_eval_dev(ctx, grp, dc, t, dpos, cnt, dX));                                   // participant.rs:207-215
+      } else {
+        RET_IF(rt_fixed_base_dev(ctx, grp, dc, grp->g_be, (const uint8_t*)dp, cnt, dX, 0));           // X_i = g^P(i)
+      }
+      RET_IF(rt_fixed_base_dev(ctx, grp, dc, grp->g_be, (const uint8_t*)dw, cnt, d1, 1));             // a1_i = g^w_i, dleq.rs:207-211
+      // Y_i = y_i^P(i) (participant.rs:219), a2_i = y_i^w_i (dleq.rs:213-216): one base, two exponents
+      RET_IF(rt_twin_dev(ctx, grp, dc, (const uint8_t*)dy, (const uint8_t*)dp, (const uint8_t*)dw, cnt, dY, d2, wipe));
+      HIPCHK(ctx, hipMemcpyAsync(hX.data(), dX, cnt * EB, hipMemcpyDeviceToHost, ctx->stream));
+      HIPCHK(ctx, hipMemcpyAsync(hY.data(), dY, cnt * EB, hipMemcpyDeviceToHost, ctx->stream));
+      HIPCHK(ctx, hipMemcpyAsync(h1.data(), d1, cnt * EB, hipMemcpyDeviceToHost, ctx->stream));
+      HIPCHK(ctx, hipMemcpyAsync(h2.data(), d2, cnt * EB, hipMemcpyDeviceToHost, ctx->stream));
+      HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+      frame_shares(h, hX.data(), hY.data(), h1.data(), h2.data(), 0, cnt);                            // participant.rs:238-245
+      if (!dev) {
+        if (x_out) memcpy(x_out + off * EB, hX.data(), cnt * EB);
+        if (y_out) memcpy(y_out + off * EB, hY.data(), cnt * EB);
+        if (a1_out) memcpy(a1_out + off * EB, h1.data(), cnt * EB);
+        if (a2_out) memcpy(a2_out + off * EB, h2.data(), cnt * EB);
+      }
+    }
+    RET_IF(spans_collect(ctx));
+  }
+  uint8_t digest[32];
+  h.final(digest);                                              // participant.rs:251
+  if (digest32_out) memcpy(digest32_out, digest, 32);
+  return MPVSS_OK;
+}
+
+// product of m elements (device bytes) by pairwise rounds through Montgomery form; result in buf[0..256)
+int rt_product_tree(mpvss_ctx* ctx, const mpvss_modp_group* grp, const modp_rt_consts* dc, uint8_t* buf, size_t m) {
+  const size_t LW = rt_L(grp);
+  RET_IF(ensure(ctx, ctx->rt_tab1, m * LW * 4));
+  uint32_t* lm = (uint32_t*)ctx->rt_tab1.p;
+  while (m > 1) {
+    const size_t half = m / 2;
+    LAUNCHCHK(ctx, modp_rt_launch_to_mont(grp->lpl, buf, (int)(2 * half), lm, dc, ctx->stream));
+    LAUNCHCHK(ctx, modp_rt_launch_mul(grp->lpl, lm, lm + half * LW, (int)half, buf, dc, ctx->stream));
+    if (m & 1) {
+      HIPCHK(ctx, hipMemcpyAsync(buf + half * EB, buf + (m - 1) * EB, EB, hipMemcpyDeviceToDevice, ctx->stream));
+      m = half + 1;
+    } else {
+      m = half;
+    }
+  }
+  return 0;
+}
+
+}  // namespace
+
+extern "C" int mpvss_modp_group_twin_min_shares(const mpvss_modp_group* grp) {
+  if (rt_bad_group(grp)) return MPVSS_E_INVALID;
+  return (int)std::min<size_t>(rt_twin_min_shares(grp->lpl), 0x7fffffff);
+}
+
+extern "C" int mpvss_modp_group_batch_twin_exp(mpvss_ctx* ctx, const mpvss_modp_group* grp, int space, const uint8_t* bases,
+                                               const uint8_t* e1, const uint8_t* e2, size_t n, uint8_t* out1, uint8_t* out2) {
+  if (!ctx) return MPVSS_E_INVALID;
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  if (rt_bad_group(grp)) return fail(ctx, MPVSS_E_INVALID, "group_batch_twin_exp: no group");
+  if (n == 0) return MPVSS_OK;
+  if (!bases || !e1 || !e2 || !out1 || !out2 || n > 0x7fffffff) return fail(ctx, MPVSS_E_INVALID, "group_batch_twin_exp: bad argument");
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  spans_reset(ctx);
+  RtWipe wipe{ctx};
+  const modp_rt_consts* dc;
+  RET_IF(rt_upload(ctx, grp, &dc));
+  for (size_t off = 0; off < n; off += MAX_CHUNK) {
+    const size_t cnt = (n - off < MAX_CHUNK) ? n - off : MAX_CHUNK;
+    const void *db, *d1, *d2;
+    RET_IF(stage_in(ctx, space, bases + off * EB, cnt * EB, ctx->rt_in[0], &db));
+    if (space == MPVSS_HOST) { wipe.device(ctx->rt_in[2], cnt * EB); wipe.device(ctx->rt_in[3], cnt * EB); }
+    RET_IF(stage_in(ctx, space, e1 + off * EB, cnt * EB, ctx->rt_in[2], &d1));
+    RET_IF(stage_in(ctx, space, e2 + off * EB, cnt * EB, ctx->rt_in[3], &d2));
+    uint8_t *o1 = out1 + off * EB, *o2 = out2 + off * EB;
+    if (space == MPVSS_HOST) {
+      RET_IF(ensure(ctx, ctx->rt_out[0], cnt * EB));
+      RET_IF(ensure(ctx, ctx->rt_out[1], cnt * EB));
+      o1 = (uint8_t*)ctx->rt_out[0].p;
+      o2 = (uint8_t*)ctx->rt_out[1].p;
+    }
+    RET_IF(rt_twin_dev(ctx, grp, dc, (const uint8_t*)db, (const uint8_t*)d1, (const uint8_t*)d2, cnt, o1, o2, wipe));
+    if (space == MPVSS_HOST) {
+      RET_IF(copy_out(ctx, space, out1 + off * EB, o1, cnt * EB));
+      RET_IF(copy_out(ctx, space, out2 + off * EB, o2, cnt * EB));
+    }
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+  }
+  RET_IF(spans_collect(ctx));
+  return MPVSS_OK;
+}
+
+extern "C" int mpvss_modp_group_distribute(mpvss_ctx* ctx, const mpvss_modp_group* grp, int space, const uint8_t* commitments, size_t t,
+                                           const int64_t* positions, const uint8_t* pubkeys, const uint8_t* p_values,
+                                           const uint8_t* witnesses, size_t n, uint8_t* x_out, uint8_t* y_out, uint8_t* a1_out,
+                                           uint8_t* a2_out, uint8_t* digest32_out) {
+  if (!ctx) return MPVSS_E_INVALID;
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  if (rt_bad_group(grp)) return fail(ctx, MPVSS_E_INVALID, "group_distribute: no group");
+  if (n > 0x7fffffff || (n > 0 && (!commitments || !positions || !pubkeys || !p_values || !witnesses || !x_out || !y_out || !a1_out ||
+                                   !a2_out || t == 0 || t > 0x7fffffff)))
+    return fail(ctx, MPVSS_E_INVALID, "group_distribute: bad argument");
+  if (t > n) return fail(ctx, MPVSS_E_INVALID, "group_distribute: threshold > number of public keys (participant.rs:166)");
+  RtWipe wipe{ctx};
+  return rt_distribute_locked(ctx, grp, space, commitments, t, positions, pubkeys, p_values, witnesses, n, x_out, y_out, a1_out, a2_out,
+                              digest32_out, wipe);
+}
+
+// participant.rs:160-286 after "draw the polynomial and the witnesses": P(i) mod (q-1) on host threads, the group side above with
+// X_i = g^P(i), the challenge and the responses r_i = w_i - P(i) c on host threads.
+extern "C" int mpvss_modp_group_deal(mpvss_ctx* ctx, const mpvss_modp_group* grp, const uint8_t* coeffs_host, size_t t,
+                                     const int64_t* positions_host, const uint8_t* pubkeys_host, const uint8_t* witnesses_host, size_t n,
+                                     uint8_t* x_out, uint8_t* y_out, uint8_t* a1_out, uint8_t* a2_out, uint8_t* digest32_out,
+                                     uint8_t* challenge_out256, uint8_t* r_out) {
+  if (!ctx) return MPVSS_E_INVALID;
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  if (rt_bad_group(grp)) return fail(ctx, MPVSS_E_INVALID, "group_deal: no group");
+  if (n > 0x7fffffff || t > 0x7fffffff ||
+      (n > 0 && (!coeffs_host || !positions_host || !pubkeys_host || !witnesses_host || !y_out || !r_out || t == 0)))
+    return fail(ctx, MPVSS_E_INVALID, "group_deal: bad argument (t >= 1, n < 2^31)");
+  if (t > n) return fail(ctx, MPVSS_E_INVALID, "group_deal: threshold > number of public keys (participant.rs:166)");
+  RET_IF(check_positions_host(ctx, positions_host, n));
+  std::vector<uint8_t> P(n * EB);
+  RtWipe wipe{ctx};
+  wipe.host.push_back(&P);
+  const int threads = host_threads(0);
+  if (n > 0) poly_eval_bytes<32>(grp->ord, true, coeffs_host, t, positions_host, n, P.data(), threads);   // participant.rs:202
+  uint8_t digest[32], challenge[EB];
+  RET_IF(rt_distribute_locked(ctx, grp, MPVSS_HOST, nullptr, t, positions_host, pubkeys_host, P.data(), witnesses_host, n, x_out, y_out,
+                              a1_out, a2_out, digest, wipe));
+  rt_hash_to_scalar(grp, digest, 32, challenge);                 // participant.rs:251-252
+  if (digest32_out) memcpy(digest32_out, digest, 32);
+  if (challenge_out256) memcpy(challenge_out256, challenge, EB);
+  if (n > 0) responses_bytes<32>(grp->ord, true, witnesses_host, P.data(), challenge, 0, n, r_out, threads);   // :255-264
+  return MPVSS_OK;
+}
+
+// participant.rs:294-353 for n participants: S_i = Y_i^(1/x_i), a1_i = G^w_i, a2_i = S_i^w_i = Y_i^(w_i / x_i) -- S and a2 share
+// the base Y_i, so with e2_i = w_i xinv_i mod (q-1) (host threads) both come from the twin path.  That is exact for a unit
+// Y_i; a Y_i that is 0 mod q makes S_i = 0 and a2_i = 0^w_i (modp.rs:122-128), where the reduced exponent would matter: a
+// chunk that holds such a row runs the two dependent k_rt_dual_exp chains instead.
+extern "C" int mpvss_modp_group_extract_shares(mpvss_ctx* ctx, const mpvss_modp_group* grp, int space, const uint8_t* pk,
+                                               const uint8_t* y, const uint8_t* xinv, const uint8_t* w, size_t n, uint8_t* s_out,
+                                               uint8_t* c_out_host) {
+  if (!ctx) return MPVSS_E_INVALID;
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  if (rt_bad_group(grp)) return fail(ctx, MPVSS_E_INVALID, "group_extract_shares: no group");
+  if (n == 0) return MPVSS_OK;
+  if (!pk || !y || !xinv || !w || !s_out || !c_out_host || n > 0x7fffffff)
+    return fail(ctx, MPVSS_E_INVALID, "group_extract_shares: bad argument");
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  spans_reset(ctx);
+  const modp_rt_consts* dc;
+  RET_IF(rt_upload(ctx, grp, &dc));
+  const bool dev = space == MPVSS_DEVICE;
+  const size_t chunk = std::min(n, MAX_CHUNK);
+  std::vector<uint8_t> hpk, hy, hxi, hw, e2(chunk * EB), hS(chunk * EB), h1(chunk * EB), h2(chunk * EB);
+  RtWipe wipe{ctx};
+  wipe.host.push_back(&e2);
+  wipe.host.push_back(&hxi);
+  wipe.host.push_back(&hw);
+  const int threads = host_threads(0);
+  for (size_t off = 0; off < n; off += MAX_CHUNK) {
+    const size_t cnt = (n - off < MAX_CHUNK) ? n - off : MAX_CHUNK;
+    const uint8_t *PK = pk + off * EB, *Y = y + off * EB, *XI = xinv + off * EB, *W = w + off * EB;
+    if (dev) {
+      RET_IF(small_vec_to_host(ctx, space, PK, cnt * EB, hpk));
+      RET_IF(small_vec_to_host(ctx, space, Y, cnt * EB, hy));
+      RET_IF(small_vec_to_host(ctx, space, XI, cnt * EB, hxi));
+      RET_IF(small_vec_to_host(ctx, space, W, cnt * EB, hw));
+      PK = hpk.data(); Y = hy.data(); XI = hxi.data(); W = hw.data();
+    }
+    std::atomic<int> zero_row{0};
+    hsc::parallel_for(cnt, threads, [&](size_t lo, size_t hi) {
+      bool z = false;
+      for (size_t i = lo; i < hi; ++i) {
+        scalar_mul_bytes<32>(grp->ord, true, W + i * EB, XI + i * EB, e2.data() + i * EB);
+        z = z || rt_zero_mod_q(grp, Y + i * EB);
+      }
+      if (z) zero_row.store(1);
+    });
+    const bool shared = zero_row.load() == 0;
+    const void *dy, *dxi, *dw, *de2;
+    RET_IF(stage_in(ctx, space, y + off * EB, cnt * EB, ctx->rt_in[0], &dy));
+    if (!dev) { wipe.device(ctx->rt_in[1], cnt * EB); wipe.device(ctx->rt_in[3], cnt * EB); }
+    wipe.device(ctx->rt_in[2], cnt * EB);
+    RET_IF(stage_in(ctx, space, xinv + off * EB, cnt * EB, ctx->rt_in[1], &dxi));
+    RET_IF(stage_in(ctx, space, w + off * EB, cnt * EB, ctx->rt_in[3], &dw));
+    RET_IF(stage_in(ctx, MPVSS_HOST, e2.data(), cnt * EB, ctx->rt_in[2], &de2));
+    uint8_t* dS = s_out + off * EB;
+    if (!dev) {
+      RET_IF(ensure(ctx, ctx->rt_out[0], cnt * EB));
+      dS = (uint8_t*)ctx->rt_out[0].p;
+    }
+    RET_IF(ensure(ctx, ctx->rt_out[1], cnt * EB));
+    RET_IF(ensure(ctx, ctx->rt_out[2], cnt * EB));
+    uint8_t* d1 = (uint8_t*)ctx->rt_out[1].p;
+    uint8_t* d2 = (uint8_t*)ctx->rt_out[2].p;
+    if (shared) {
+      RET_IF(rt_twin_dev(ctx, grp, dc, (const uint8_t*)dy, (const uint8_t*)dxi, (const uint8_t*)de2, cnt, dS, d2, wipe));
+    } else {
+      const uint32_t* tb;
+      RET_IF(rt_tables(ctx, grp, dc, (const uint8_t*)dy, EB, cnt, ctx->rt_tab1, &tb));                 // S = Y^(1/x), :310-314
+      TIMED_LAUNCH(ctx, 3, modp_rt_launch_dual_exp(grp->lpl, tb, 16 * rt_L(grp), nullptr, 0, (const uint8_t*)dxi, EB, nullptr, 0, (int)cnt,
+                                                   dS, dc, ctx->stream));
+      RET_IF(rt_tables(ctx, grp, dc, dS, EB, cnt, ctx->rt_tab2, &tb));                                 // a2 = S^w
+      TIMED_LAUNCH(ctx, 3, modp_rt_launch_dual_exp(grp->lpl, tb, 16 * rt_L(grp), nullptr, 0, (const uint8_t*)dw, EB, nullptr, 0, (int)cnt,
+                                                   d2, dc, ctx->stream));
+    }
+    RET_IF(rt_fixed_base_dev(ctx, grp, dc, grp->G_be, (const uint8_t*)dw, cnt, d1, 1));                // a1 = G^w
+    HIPCHK(ctx, hipMemcpyAsync(hS.data(), dS, cnt * EB, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipMemcpyAsync(h1.data(), d1, cnt * EB, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipMemcpyAsync(h2.data(), d2, cnt * EB, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    hsc::parallel_for(cnt, threads, [&](size_t lo, size_t hi) {
+      for (size_t i = lo; i < hi; ++i) {
+        mpvss::Sha256 hs;
+        frame_update(hs, PK + i * EB);
+        frame_update(hs, Y + i * EB);
+        frame_update(hs, h1.data() + i * EB);
+        frame_update(hs, h2.data() + i * EB);
+        uint8_t digest[32];
+        hs.final(digest);
+        rt_hash_to_scalar(grp, digest, 32, c_out_host + (off + i) * EB);      // :329-343
+      }
+    });
+    if (!dev) memcpy(s_out + off * EB, hS.data(), cnt * EB);
+  }
+  RET_IF(spans_collect(ctx));
+  return MPVSS_OK;
+}
+
+// participant.rs:462-561: G^s = prod_i S_i^lambda_i.  Lagrange exponents mod (q-1)/2 with the sign kept aside (:526-561); a
+// negative coefficient inverts the factor, and S^-e = S^((q-1) - e) for every unit S mod a prime q, so the m powers run in one
+// k_rt_dual_exp launch with no inversion at all.  (q-1)/2 must be odd (every safe prime above 5).
+extern "C" int mpvss_modp_group_reconstruct(mpvss_ctx* ctx, const mpvss_modp_group* grp, int space, const int64_t* positions_host,
+                                            const uint8_t* shares, size_t m, uint8_t* gs_out256, uint8_t* mask_out32) {
+  if (!ctx) return MPVSS_E_INVALID;
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  if (rt_bad_group(grp)) return fail(ctx, MPVSS_E_INVALID, "group_reconstruct: no group");
+  if (!positions_host || !shares || m == 0 || !gs_out256 || m > 0x7fffffff)
+    return fail(ctx, MPVSS_E_INVALID, "group_reconstruct: bad argument");
+  for (size_t i = 0; i < m; ++i)
+    if (positions_host[i] < 1) return fail(ctx, MPVSS_E_INVALID, "group_reconstruct: positions must be >= 1 (util.rs:47-64)");
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  spans_reset(ctx);
+  std::vector<hsc::Num<32>> mag;
+  std::vector<char> neg;
+  if (!lagrange_at_zero<32>(grp->sub, positions_host, m, mag, neg, false))
+    return fail(ctx, MPVSS_E_INVALID, "group_reconstruct: duplicate positions, or a Lagrange denominator without inverse mod (q-1)/2");
+  std::vector<uint8_t> exps(m * EB), hs;
+  for (size_t i = 0; i < m; ++i) {
+    uint64_t e[32];
+    memcpy(e, mag[i].v, sizeof(e));
+    if (neg[i]) {
+      uint64_t o = 0;
+      for (int k = 0; k < 32; ++k) o |= e[k];
+      if (o) hsc::sub_n<32>(e, grp->ord.m, e);
+    }
+    hsc::to_bytes<32>(exps.data() + i * EB, e, true);
+  }
+  // a share that is 0 mod q has no inverse: the reference returns None when its coefficient is negative (:551-553)
+  RET_IF(small_vec_to_host(ctx, space, shares, m * EB, hs));
+  for (size_t i = 0; i < m; ++i)
+    if (neg[i] && rt_zero_mod_q(grp, hs.data() + i * EB))
+      return fail(ctx, MPVSS_E_INVALID, "group_reconstruct: a share is 0 mod q and has no inverse");
+  const modp_rt_consts* dc;
+  RET_IF(rt_upload(ctx, grp, &dc));
+  const void *dS, *dE;
+  RET_IF(stage_in(ctx, space, shares, m * EB, ctx->rt_in[0], &dS));
+  RET_IF(stage_in(ctx, MPVSS_HOST, exps.data(), m * EB, ctx->rt_in[1], &dE));
+  RET_IF(ensure(ctx, ctx->rt_out[0], m * EB));
+  uint8_t* dF = (uint8_t*)ctx->rt_out[0].p;
+  const uint32_t* tb;
+  RET_IF(rt_tables(ctx, grp, dc, (const uint8_t*)dS, EB, m, ctx->rt_tab2, &tb));
+  TIMED_LAUNCH(ctx, 3, modp_rt_launch_dual_exp(grp->lpl, tb, 16 * rt_L(grp), nullptr, 0, (const uint8_t*)dE, EB, nullptr, 0, (int)m, dF, dc,
+                                               ctx->stream));                                          // S_i^lambda_i
+  RET_IF(rt_product_tree(ctx, grp, dc, dF, m));                                                        // fold with mul, :503-505
+  uint8_t gs[EB];
+  HIPCHK(ctx, hipMemcpyAsync(gs, dF, EB, hipMemcpyDeviceToHost, ctx->stream));
+  HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+  memcpy(gs_out256, gs, EB);
+  if (mask_out32) {
+    // int_BE(SHA256(element_to_bytes(G^s))) mod q (:512-515): the reduction matters for q below 2^256
+    uint8_t hb[EB];
+    memset(hb, 0, EB - 32);
+    mpvss::Sha256 h;
+    frame_min_bytes_update(h, gs);
+    h.final(hb + EB - 32);
+    uint64_t x[32];
+    hsc::from_bytes<32>(x, hb, true);
+    grp->mod.reduce1(x);
+    hsc::to_bytes<32>(hb, x, true);
+    memcpy(mask_out32, hb + EB - 32, 32);
   }
   RET_IF(spans_collect(ctx));
   return MPVSS_OK;

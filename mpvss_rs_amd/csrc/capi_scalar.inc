@@ -50,17 +50,17 @@ int host_threads(int requested) {
   return hc == 0 ? 1 : (hc > 16 ? 16 : (int)hc);
 }
 
-// generic bodies over (N limbs, byte width, endianness)
-template <int N>
-void scalar_mul_bytes(const hsc::Modulus<N>& M, bool be, const uint8_t* a, const uint8_t* b, uint8_t* out) {
+// generic bodies over (N limbs, byte width, endianness); Mod: hsc::Modulus<N>, or hsc::ModulusRt for N = 32
+template <int N, class Mod>
+void scalar_mul_bytes(const Mod& M, bool be, const uint8_t* a, const uint8_t* b, uint8_t* out) {
   uint64_t x[N], y[N], r[N];
   hsc::from_bytes<N>(x, a, be);
   hsc::from_bytes<N>(y, b, be);
   M.mulmod(r, x, y);                                                   // (a * b) % order
   hsc::to_bytes<N>(out, r, be);
 }
-template <int N>
-void scalar_sub_bytes(const hsc::Modulus<N>& M, bool be, const uint8_t* a, const uint8_t* b, uint8_t* out) {
+template <int N, class Mod>
+void scalar_sub_bytes(const Mod& M, bool be, const uint8_t* a, const uint8_t* b, uint8_t* out) {
   // modp.rs:184-192: diff = a - b; diff < 0 ? diff + order : diff % order   (the curve crates reduce as well)
   uint64_t x[N], y[N], r[N];
   hsc::from_bytes<N>(x, a, be);
@@ -69,8 +69,8 @@ void scalar_sub_bytes(const hsc::Modulus<N>& M, bool be, const uint8_t* a, const
   hsc::to_bytes<N>(out, r, be);
 }
 // r_i = w_i - (alpha_i * c) % order, normalised as scalar_sub does   (dleq.rs:42-50, participant.rs:255-264)
-template <int N>
-void responses_bytes(const hsc::Modulus<N>& M, bool be, const uint8_t* w, const uint8_t* alpha, const uint8_t* c, size_t c_stride,
+template <int N, class Mod>
+void responses_bytes(const Mod& M, bool be, const uint8_t* w, const uint8_t* alpha, const uint8_t* c, size_t c_stride,
                      size_t n, uint8_t* r_out, int threads) {
   constexpr size_t SB = (size_t)N * 8;
   hsc::parallel_for(n, threads, [&](size_t lo, size_t hi) {
@@ -88,8 +88,8 @@ void responses_bytes(const hsc::Modulus<N>& M, bool be, const uint8_t* w, const 
 }
 // out_i = P(positions_i) mod order, P = sum_j coeffs_j x^j   (polynomial.rs:50-58 evaluates over the integers and the
 // caller reduces, participant.rs:202 / 1155-1157 / 1619-1621: the same residue as Horner's rule in the ring)
-template <int N>
-void poly_eval_bytes(const hsc::Modulus<N>& M, bool be, const uint8_t* coeffs, size_t t, const int64_t* positions, size_t n,
+template <int N, class Mod>
+void poly_eval_bytes(const Mod& M, bool be, const uint8_t* coeffs, size_t t, const int64_t* positions, size_t n,
                      uint8_t* out, int threads) {
   constexpr size_t SB = (size_t)N * 8;
   std::vector<hsc::Num<N>> cf(t);
@@ -150,8 +150,8 @@ void poly_eval_bytes(const hsc::Modulus<N>& M, bool be, const uint8_t* coeffs, s
 // Lagrange coefficients at 0 over the ring of an ODD prime modulus:
 //   lambda_i = prod_{j != i} x_j / (x_j - x_i)      magnitude mod M, sign separately (participant.rs:1525-1544)
 // positions must be pairwise different.  mag[i] = |num| * |den|^-1 mod M; neg[i] = sign of the integer coefficient.
-template <int N>
-bool lagrange_at_zero(const hsc::Modulus<N>& M, const int64_t* pos, size_t m, std::vector<hsc::Num<N>>& mag, std::vector<char>& neg,
+template <int N, class Mod>
+bool lagrange_at_zero(const Mod& M, const int64_t* pos, size_t m, std::vector<hsc::Num<N>>& mag, std::vector<char>& neg,
                       bool positions_as_u64) {
   mag.resize(m);
   neg.assign(m, 0);

@@ -33,6 +33,15 @@ int modp_rt_launch_table(int lpl, const uint8_t* base_be, size_t base_stride, in
 int modp_rt_launch_dual_exp(int lpl, const uint32_t* tab1, size_t tab1_stride, const uint32_t* tab2, size_t tab2_stride,
                             const uint8_t* e1, size_t e1_stride, const uint8_t* e2, size_t e2_stride, int count, uint8_t* out,
                             const modp_rt_consts* cs, hipStream_t s);
+/* out1[x] = B[x]^e1[x], out2[x] = B[x]^e2[x] from the base's one table, two left-to-right exponent sets in one launch
+   (gridDim.y = 2); exponents and results n x 256 bytes */
+int modp_rt_launch_exp_sets(int lpl, const uint32_t* tab, size_t tab_stride, const uint8_t* e1, const uint8_t* e2, int count,
+                            uint8_t* out1, uint8_t* out2, const modp_rt_consts* cs, hipStream_t s);
+/* the same two results right to left with shared squarings (k_rt_twin_exp): bases as 256-byte values of any size, `buckets`
+   a scratch of modp_rt_twin_scratch_bytes(lpl, count) bytes that holds exponent windows afterwards (the caller zeroes it) */
+size_t modp_rt_twin_scratch_bytes(int lpl, int count);
+int modp_rt_launch_twin_exp(int lpl, const uint8_t* bases, const uint8_t* e1, const uint8_t* e2, int count, uint32_t* buckets,
+                            uint8_t* out1, uint8_t* out2, const modp_rt_consts* cs, hipStream_t s);
 /* out[x] = a[x] b[x] mod q, canonical, from a R and b R (modp_rt_launch_to_mont) */
 int modp_rt_launch_mul(int lpl, const uint32_t* a_m, const uint32_t* b_m, int count, uint8_t* out, const modp_rt_consts* cs, hipStream_t s);
 /* X[x] = Horner in the exponent over the commitments cm_m ([t] numbers in Montgomery form) at i' = positions[x] mod (q-1) */

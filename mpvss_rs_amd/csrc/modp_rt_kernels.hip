@@ -159,12 +159,11 @@ __global__ void RT_KERNEL(LPL) k_rt_table(const uint8_t* __restrict__ base_be, s
 // entry, plain 1 at the end).
 // ---------------------------------------------------------------------------------------
 template <int LPL>
-__global__ void RT_KERNEL(LPL) k_rt_dual_exp(const u32* __restrict__ tab1, size_t tab1_stride, const u32* __restrict__ tab2,
-                                             size_t tab2_stride, const uint8_t* __restrict__ e1_be, size_t e1_stride,
-                                             const uint8_t* __restrict__ e2_be, size_t e2_stride, int count,
-                                             uint8_t* __restrict__ out_be, const modp_rt_consts* __restrict__ cs) {
+__device__ __forceinline__ void rt_dual_exp_body(u32* lds, const u32* __restrict__ tab1, size_t tab1_stride, const u32* __restrict__ tab2,
+                                                 size_t tab2_stride, const uint8_t* __restrict__ e1_be, size_t e1_stride,
+                                                 const uint8_t* __restrict__ e2_be, size_t e2_stride, int count,
+                                                 uint8_t* __restrict__ out_be, const modp_rt_consts* __restrict__ cs) {
   constexpr int L = Width<LPL>::L, SLOT = Width<LPL>::SLOT;
-  __shared__ __attribute__((aligned(16))) u32 lds[RT_NUMS * SLOT];
   const Lane ln = make_lane();
   const int xi = blockIdx.x * RT_NUMS + (threadIdx.x >> 2);
   const bool live = xi < count;
@@ -219,6 +218,144 @@ __global__ void RT_KERNEL(LPL) k_rt_dual_exp(const u32* __restrict__ tab1, size_
     if (s == 5 && !has2) s = 6;
   }
   store_canonical<LPL>(out_be + (size_t)x * 256, acc, slot, cs, ln, live);
+}
+
+template <int LPL>
+__global__ void RT_KERNEL(LPL) k_rt_dual_exp(const u32* __restrict__ tab1, size_t tab1_stride, const u32* __restrict__ tab2,
+                                             size_t tab2_stride, const uint8_t* __restrict__ e1_be, size_t e1_stride,
+                                             const uint8_t* __restrict__ e2_be, size_t e2_stride, int count,
+                                             uint8_t* __restrict__ out_be, const modp_rt_consts* __restrict__ cs) {
+  __shared__ __attribute__((aligned(16))) u32 lds[RT_NUMS * Width<LPL>::SLOT];
+  rt_dual_exp_body<LPL>(lds, tab1, tab1_stride, tab2, tab2_stride, e1_be, e1_stride, e2_be, e2_stride, count, out_be, cs);
+}
+
+// ---------------------------------------------------------------------------------------
+// Two powers of each base in ONE launch: out1[x] = B[x]^e1[x] (blockIdx.y = 0), out2[x] = B[x]^e2[x] (blockIdx.y = 1), both
+// left to right over the base's one 16-entry table.  The form for a batch that does not fill the chip: twice the
+// workgroups of one k_rt_dual_exp launch, each with the short chain of a single exponentiation.
+// ---------------------------------------------------------------------------------------
+template <int LPL>
+__global__ void RT_KERNEL(LPL) k_rt_exp_sets(const u32* __restrict__ tab, size_t tab_stride, const uint8_t* __restrict__ e1_be,
+                                             const uint8_t* __restrict__ e2_be, int count, uint8_t* __restrict__ out1_be,
+                                             uint8_t* __restrict__ out2_be, const modp_rt_consts* __restrict__ cs) {
+  __shared__ __attribute__((aligned(16))) u32 lds[RT_NUMS * Width<LPL>::SLOT];
+  const bool second = blockIdx.y != 0;
+  rt_dual_exp_body<LPL>(lds, tab, tab_stride, nullptr, 0, second ? e2_be : e1_be, 256, nullptr, 0, count, second ? out2_be : out1_be, cs);
+}
+
+// ---------------------------------------------------------------------------------------
+// K_e[d] = prod over the windows k of exponent e with digit d of B^(16^k), for both exponents of each base with the squarings
+// shared: right to left over fixed 4-bit windows.  The running power P_k = B^(16^k) is computed once and multiplied into
+// bucket K_e[d] of each exponent whose k-th digit is d != 0; k_rt_twin_combine then forms
+//   B^e = prod_d K_e[d]^d = prod_{j=1..15} (K_e[15] K_e[14] .. K_e[j]).
+// The counterpart of group 14's k_modp_twin_exp_buckets / k_modp_bucket_combine at a run-time width.  A quad only ever
+// touches its own buckets, and every lane reads back exactly the words it wrote (load_lane_limbs / store_lane_limbs).
+//   buckets : HBM scratch, [16 gridDim.x][2][15][L] words (dead quads of the last workgroup have buckets of their own);
+//             bucket contents tell exponent windows: the caller zeroes the scratch afterwards.
+// Per window: one LDS copy of P_k serves both bucket products AND the first of the four squarings, and P_k comes back from
+// it afterwards, so the kernel holds one number in registers like k_rt_dual_exp.  A bucket product is skipped when the
+// digit is 0 in all 16 numbers of the wave; the window loop runs to the wave's highest set bit over both exponents.
+// Worst case at 2048 bits: 1 entry + 2044 squarings + 1024 bucket products + 2 (28 combine + 1 exit) = 3127 Montgomery
+// operations for both results (tests/test_modp_rt_twin_model.py).
+// ---------------------------------------------------------------------------------------
+#define RT_TWIN_BUCKETS 15
+template <int LPL>
+__global__ void RT_KERNEL(LPL) k_rt_twin_exp(const uint8_t* __restrict__ base_be, const uint8_t* __restrict__ e1_be,
+                                             const uint8_t* __restrict__ e2_be, int count, u32* __restrict__ buckets,
+                                             const modp_rt_consts* __restrict__ cs) {
+  constexpr int L = Width<LPL>::L, SLOT = Width<LPL>::SLOT;
+  __shared__ __attribute__((aligned(16))) u32 lds[RT_NUMS * SLOT];
+  const Lane ln = make_lane();
+  const int xi = blockIdx.x * RT_NUMS + (threadIdx.x >> 2);
+  const bool live = xi < count;
+  const int x = live ? xi : count - 1;
+  u32* slot = lds + (threadIdx.x >> 2) * SLOT;
+  const u32 n0inv = cs->n0inv;
+  const uint8_t* e1 = e1_be + (size_t)x * 256;
+  const uint8_t* e2 = e2_be + (size_t)x * 256;
+  u32* mine = buckets + (size_t)xi * 2 * RT_TWIN_BUCKETS * L;        // xi, not x: a dead quad works on scratch of its own
+  u32 n[LPL], acc[LPL];
+  load_lane_limbs<LPL>(n, cs->n, ln);
+  load_lane_limbs<LPL>(acc, cs->one_m, ln);
+#pragma nounroll
+  for (int b = 0; b < 2 * RT_TWIN_BUCKETS; ++b) store_lane_limbs<LPL>(mine + (size_t)b * L, acc, ln);
+  to_mont_in<LPL>(acc, slot, base_be + (size_t)x * 256, cs, n, n0inv, ln);
+  int nb = wave_max_bits(e1, ln);
+  {
+    const int nb2 = wave_max_bits(e2, ln);
+    nb = nb2 > nb ? nb2 : nb;
+  }
+  const int nw = (nb + 3) >> 2;
+  for (int w = 0; w < nw; ++w) {
+    slot_store<LPL>(slot, acc, ln);
+    __builtin_amdgcn_wave_barrier();
+#pragma nounroll
+    for (int e = 0; e < 2; ++e) {
+      const u32 d = nibble(e ? e2 : e1, w);
+      if (__builtin_amdgcn_ballot_w64(d != 0) == 0) continue;
+      u32* bk = mine + (size_t)(e * RT_TWIN_BUCKETS + (d ? d - 1 : 0)) * L;
+      load_lane_limbs<LPL>(acc, bk, ln);
+      mont_mul<N0INV_RUNTIME>(acc, acc, slot, n, ln, n0inv);
+      if (d != 0) store_lane_limbs<LPL>(bk, acc, ln);
+    }
+    if (w + 1 == nw) break;
+    slot_load<LPL>(acc, slot, ln);               // P_k back from its LDS copy: the window phase holds one number in registers
+#pragma nounroll
+    for (int sq = 0; sq < 4; ++sq) {
+      if (sq) {
+        __builtin_amdgcn_wave_barrier();
+        slot_store<LPL>(slot, acc, ln);
+        __builtin_amdgcn_wave_barrier();
+      }
+      mont_mul<N0INV_RUNTIME, true>(acc, acc, slot, n, ln, n0inv);
+    }
+    __builtin_amdgcn_wave_barrier();
+  }
+}
+
+// Combine step of k_rt_twin_exp, blockIdx.y = exponent: out[x] = prod_d K[d]^d by the running-product rule.  One number in
+// registers: acc = running product S = K[15] .. K[j]; the product T of the running products lives in K[15]'s own words
+// (T starts as K[15]).  A pair of steps for each j = 14 .. 1: S *= K[j]; T *= S with S parked in the LDS slot meanwhile.
+// Last step: T times plain 1.  28 + 1 products.
+template <int LPL>
+__global__ void RT_KERNEL(LPL) k_rt_twin_combine(u32* __restrict__ buckets, int count, uint8_t* __restrict__ out1_be,
+                                                 uint8_t* __restrict__ out2_be, const modp_rt_consts* __restrict__ cs) {
+  constexpr int L = Width<LPL>::L, SLOT = Width<LPL>::SLOT;
+  __shared__ __attribute__((aligned(16))) u32 lds[RT_NUMS * SLOT];
+  const Lane ln = make_lane();
+  const int xi = blockIdx.x * RT_NUMS + (threadIdx.x >> 2);
+  const bool live = xi < count;
+  const int x = live ? xi : count - 1;
+  u32* slot = lds + (threadIdx.x >> 2) * SLOT;
+  const u32 n0inv = cs->n0inv;
+  u32* my = buckets + ((size_t)xi * 2 + blockIdx.y) * RT_TWIN_BUCKETS * L;
+  u32* tprod = my + (size_t)(RT_TWIN_BUCKETS - 1) * L;
+  u32 n[LPL], acc[LPL];
+  load_lane_limbs<LPL>(n, cs->n, ln);
+  load_lane_limbs<LPL>(acc, tprod, ln);
+  constexpr int LAST = 2 * (RT_TWIN_BUCKETS - 1);
+#pragma nounroll
+  for (int step = 0; step <= LAST; ++step) {
+    __builtin_amdgcn_wave_barrier();
+    if (step == LAST) {
+      load_lane_limbs<LPL>(acc, tprod, ln);
+      slot_fill_from_global<LPL>(slot, cs->one, ln);
+    } else if (!(step & 1)) {
+      slot_fill_from_global<LPL>(slot, my + (size_t)(RT_TWIN_BUCKETS - 2 - (step >> 1)) * L, ln);
+    } else {
+      slot_store<LPL>(slot, acc, ln);
+      load_lane_limbs<LPL>(acc, tprod, ln);
+    }
+    __builtin_amdgcn_wave_barrier();
+    mont_mul<N0INV_RUNTIME>(acc, acc, slot, n, ln, n0inv);
+    if (step & 1) {
+      store_lane_limbs<LPL>(tprod, acc, ln);
+      __builtin_amdgcn_wave_barrier();
+      slot_load<LPL>(acc, slot, ln);
+    }
+  }
+  __builtin_amdgcn_wave_barrier();
+  store_canonical<LPL>((blockIdx.y ? out2_be : out1_be) + (size_t)x * 256, acc, slot, cs, ln, live);
 }
 
 // ---------------------------------------------------------------------------------------
@@ -373,6 +510,25 @@ extern "C" int modp_rt_launch_dual_exp(int lpl, const uint32_t* tab1, size_t tab
   if (count <= 0) return 0;
   RT_DISPATCH(lpl, k_rt_dual_exp, dim3(rt_grid(count)), dim3(64), 0, s, tab1, tab1_stride, tab2, tab2_stride, e1, e1_stride, e2,
               e2_stride, count, out, cs);
+  return (int)hipGetLastError();
+}
+
+extern "C" int modp_rt_launch_exp_sets(int lpl, const uint32_t* tab, size_t tab_stride, const uint8_t* e1, const uint8_t* e2, int count,
+                                       uint8_t* out1, uint8_t* out2, const modp_rt_consts* cs, hipStream_t s) {
+  if (count <= 0) return 0;
+  RT_DISPATCH(lpl, k_rt_exp_sets, dim3(rt_grid(count), 2), dim3(64), 0, s, tab, tab_stride, e1, e2, count, out1, out2, cs);
+  return (int)hipGetLastError();
+}
+
+extern "C" size_t modp_rt_twin_scratch_bytes(int lpl, int count) {
+  return (size_t)rt_grid(count) * RT_NUMS * 2 * RT_TWIN_BUCKETS * 4 * lpl * sizeof(uint32_t);
+}
+
+extern "C" int modp_rt_launch_twin_exp(int lpl, const uint8_t* bases, const uint8_t* e1, const uint8_t* e2, int count, uint32_t* buckets,
+                                       uint8_t* out1, uint8_t* out2, const modp_rt_consts* cs, hipStream_t s) {
+  if (count <= 0) return 0;
+  RT_DISPATCH(lpl, k_rt_twin_exp, dim3(rt_grid(count)), dim3(64), 0, s, bases, e1, e2, count, buckets, cs);
+  RT_DISPATCH(lpl, k_rt_twin_combine, dim3(rt_grid(count), 2), dim3(64), 0, s, buckets, count, out1, out2, cs);
   return (int)hipGetLastError();
 }
 

@@ -318,9 +318,10 @@ struct mpvss_ctx {
   EcWork ecwork;
   // workspace of the run-time MODP group entry points (capi_modp_rt.inc), used under `mu`
   DevBuf rt_consts, rt_in[6], rt_out[3], rt_tab1, rt_tab2, rt_tabg, rt_cm, rt_small[2];
+  DevBuf rt_out_y, rt_buckets;   // the dealer's fourth result array; bucket scratch of k_rt_twin_exp (one chunk)
   std::vector<DevBuf*> rt_all() {
     return {&rt_consts, &rt_in[0], &rt_in[1], &rt_in[2], &rt_in[3], &rt_in[4], &rt_in[5], &rt_out[0], &rt_out[1], &rt_out[2],
-            &rt_tab1, &rt_tab2, &rt_tabg, &rt_cm, &rt_small[0], &rt_small[1]};
+            &rt_tab1, &rt_tab2, &rt_tabg, &rt_cm, &rt_small[0], &rt_small[1], &rt_out_y, &rt_buckets};
   }
 };
 

@@ -6,7 +6,7 @@
 //!   many boxes                   one call per dealer in the reference               -> mpvss_modp_verify_many
 //!   verify_share (n boxes)       src/participant.rs:361-386 -> src/dleq.rs:275-302   -> mpvss_modp_verify_shares
 //!   distribute_secret            src/participant.rs:160-286                          -> mpvss_modp_distribute (+ scalar side)
-//!   extract_secret_share (n)     src/participant.rs:294-353                          -> mpvss_modp_extract_shares
+//!   extract_secret_share (n)     src/participant.rs:294-353                          -> mpvss_modp_extract_shares  (run-time group: mpvss_modp_group_extract_shares)
 //!   reconstruct                  src/participant.rs:462-561                          -> mpvss_modp_reconstruct
 //!
 //! `crate::participant::Participant<G>` wraps these in the reference's method names.  Every function here may be called from
@@ -160,7 +160,6 @@ pub fn verify_shares(group: &HipModpGroup, share_boxes: &[ShareBox<HipModpGroup>
 
 /// Drop-in body of `Participant<ModpGroup>::distribute_secret` (participant.rs:160-286).
 pub fn distribute_secret(group: &HipModpGroup, secret: &BigInt, publickeys: &[BigInt], threshold: u32) -> DistributionSharesBox<HipModpGroup> {
-    assert!(group.rt.is_none(), "batch::distribute_secret: RFC 3526 group 14 only (a run-time group offers verify_distribution_shares and verify_shares)");
     assert!(threshold as usize <= publickeys.len());                                   // participant.rs:166
     let n = publickeys.len();
     let t = threshold as usize;
@@ -170,7 +169,14 @@ pub fn distribute_secret(group: &HipModpGroup, secret: &BigInt, publickeys: &[Bi
     let coeffs: Vec<u8> = polynomial.coefficients.iter().flat_map(|a| be256(a)).collect();
     let g = be256(&group.subgroup_generator());
     let mut cm = vec![0u8; t * 256];
-    let rc = unsafe { ffi::mpvss_modp_batch_exp_fixed_base(group.engine.raw(), ffi::MPVSS_HOST, g.as_ptr(), coeffs.as_ptr(), t, cm.as_mut_ptr()) };
+    let rc = match group.rt_handle() {
+        // a run-time group has no fixed-base comb: base 4 for every exponent through mpvss_modp_group_batch_exp
+        Some(h) => {
+            let gs: Vec<u8> = (0..t).flat_map(|_| g.clone()).collect();
+            unsafe { ffi::mpvss_modp_group_batch_exp(group.engine.raw(), h, ffi::MPVSS_HOST, gs.as_ptr(), coeffs.as_ptr(), t, cm.as_mut_ptr()) }
+        }
+        None => unsafe { ffi::mpvss_modp_batch_exp_fixed_base(group.engine.raw(), ffi::MPVSS_HOST, g.as_ptr(), coeffs.as_ptr(), t, cm.as_mut_ptr()) },
+    };
     group.engine.expect(rc, "distribute_secret: commitments");                         // C_j = g^a_j, :189-193
     let positions: Vec<i64> = (1..=n as i64).collect();                                // :186,198,247
     let witnesses: Vec<BigInt> = (0..n).map(|_| group.generate_private_key()).collect();    // :223
@@ -183,10 +189,18 @@ pub fn distribute_secret(group: &HipModpGroup, secret: &BigInt, publickeys: &[Bi
     let mut r = vec![0u8; n * 256];
     let mut digest = [0u8; 32];
     let mut c256 = [0u8; 256];
-    let rc = unsafe {
-        ffi::mpvss_modp_deal(group.engine.raw(), coeffs.as_ptr(), t, positions.as_ptr(), pk.as_ptr(), ws.as_ptr(), n, std::ptr::null_mut(),
-                             y.as_mut_ptr(), std::ptr::null_mut(), std::ptr::null_mut(), digest.as_mut_ptr(), c256.as_mut_ptr(),
-                             r.as_mut_ptr())
+    let rc = match group.rt_handle() {
+        // a run-time group: the same call shape, P(i) and the responses on host threads inside the library
+        Some(h) => unsafe {
+            ffi::mpvss_modp_group_deal(group.engine.raw(), h, coeffs.as_ptr(), t, positions.as_ptr(), pk.as_ptr(), ws.as_ptr(), n,
+                                       std::ptr::null_mut(), y.as_mut_ptr(), std::ptr::null_mut(), std::ptr::null_mut(),
+                                       digest.as_mut_ptr(), c256.as_mut_ptr(), r.as_mut_ptr())
+        },
+        None => unsafe {
+            ffi::mpvss_modp_deal(group.engine.raw(), coeffs.as_ptr(), t, positions.as_ptr(), pk.as_ptr(), ws.as_ptr(), n, std::ptr::null_mut(),
+                                 y.as_mut_ptr(), std::ptr::null_mut(), std::ptr::null_mut(), digest.as_mut_ptr(), c256.as_mut_ptr(),
+                                 r.as_mut_ptr())
+        },
     };
     group.engine.expect(rc, "distribute_secret");
     let challenge = BigInt::from_bytes_be(Sign::Plus, &c256);
@@ -218,7 +232,6 @@ pub fn distribute_secret(group: &HipModpGroup, secret: &BigInt, publickeys: &[Bi
 /// n participants decrypt and prove at once (participant.rs:294-353): `witnesses[i]` is the `w` argument of the i-th call.
 pub fn extract_secret_shares(group: &HipModpGroup, bx: &DistributionSharesBox<HipModpGroup>, private_keys: &[BigInt], witnesses: &[BigInt])
     -> Vec<Option<ShareBox<HipModpGroup>>> {
-    assert!(group.rt.is_none(), "batch::extract_secret_shares: RFC 3526 group 14 only (a run-time group offers verify_distribution_shares and verify_shares)");
     assert_eq!(private_keys.len(), witnesses.len());
     let mut idx = Vec::new();
     let (mut pk, mut y, mut xinv, mut w) = (Vec::new(), Vec::new(), Vec::new(), Vec::new());
@@ -235,10 +248,20 @@ pub fn extract_secret_shares(group: &HipModpGroup, bx: &DistributionSharesBox<Hi
     }
     let m = idx.len();
     let (mut s, mut c, mut r) = (vec![0u8; m * 256], vec![0u8; m * 256], vec![0u8; m * 256]);
-    let rc = unsafe { ffi::mpvss_modp_extract_shares(group.engine.raw(), ffi::MPVSS_HOST, pk.as_ptr(), y.as_ptr(), xinv.as_ptr(), w.as_ptr(), m, s.as_mut_ptr(), c.as_mut_ptr()) };
+    let rc = match group.rt_handle() {
+        Some(h) => unsafe {
+            ffi::mpvss_modp_group_extract_shares(group.engine.raw(), h, ffi::MPVSS_HOST, pk.as_ptr(), y.as_ptr(), xinv.as_ptr(), w.as_ptr(), m,
+                                                 s.as_mut_ptr(), c.as_mut_ptr())
+        },
+        None => unsafe { ffi::mpvss_modp_extract_shares(group.engine.raw(), ffi::MPVSS_HOST, pk.as_ptr(), y.as_ptr(), xinv.as_ptr(), w.as_ptr(), m, s.as_mut_ptr(), c.as_mut_ptr()) },
+    };
     group.engine.expect(rc, "extract_secret_shares");
     let xs: Vec<u8> = idx.iter().flat_map(|&i| be256(&private_keys[i])).collect();
-    unsafe { ffi::mpvss_modp_dleq_responses(w.as_ptr(), xs.as_ptr(), c.as_ptr(), 1, m, r.as_mut_ptr(), 0) };     // r = w - x c, dleq.rs:42-50
+    // r = w - x c, dleq.rs:42-50 (mod q - 1 of the group at hand)
+    match group.rt_handle() {
+        Some(h) => unsafe { ffi::mpvss_modp_group_dleq_responses(h, w.as_ptr(), xs.as_ptr(), c.as_ptr(), 1, m, r.as_mut_ptr(), 0) },
+        None => unsafe { ffi::mpvss_modp_dleq_responses(w.as_ptr(), xs.as_ptr(), c.as_ptr(), 1, m, r.as_mut_ptr(), 0) },
+    };
     let big = |b: &[u8]| BigInt::from_bytes_be(Sign::Plus, b);
     let mut out: Vec<Option<ShareBox<HipModpGroup>>> = (0..private_keys.len()).map(|_| None).collect();
     for (k, &i) in idx.iter().enumerate() {
@@ -251,7 +274,6 @@ pub fn extract_secret_shares(group: &HipModpGroup, bx: &DistributionSharesBox<Hi
 
 /// Drop-in body of `Participant<ModpGroup>::reconstruct` (participant.rs:462-519).
 pub fn reconstruct(group: &HipModpGroup, share_boxes: &[ShareBox<HipModpGroup>], bx: &DistributionSharesBox<HipModpGroup>) -> Option<BigInt> {
-    assert!(group.rt.is_none(), "batch::reconstruct: RFC 3526 group 14 only (a run-time group offers verify_distribution_shares and verify_shares)");
     if share_boxes.len() < bx.commitments.len() {
         return None;
     }
@@ -263,7 +285,13 @@ pub fn reconstruct(group: &HipModpGroup, share_boxes: &[ShareBox<HipModpGroup>],
     let positions: Vec<i64> = shares.keys().copied().collect();
     let s: Vec<u8> = shares.values().flat_map(|v| be256(v)).collect();
     let (mut gs, mut mask) = ([0u8; 256], [0u8; 32]);
-    let rc = unsafe { ffi::mpvss_modp_reconstruct(group.engine.raw(), ffi::MPVSS_HOST, positions.as_ptr(), s.as_ptr(), positions.len(), gs.as_mut_ptr(), mask.as_mut_ptr()) };
+    let rc = match group.rt_handle() {
+        Some(h) => unsafe {
+            ffi::mpvss_modp_group_reconstruct(group.engine.raw(), h, ffi::MPVSS_HOST, positions.as_ptr(), s.as_ptr(), positions.len(),
+                                              gs.as_mut_ptr(), mask.as_mut_ptr())
+        },
+        None => unsafe { ffi::mpvss_modp_reconstruct(group.engine.raw(), ffi::MPVSS_HOST, positions.as_ptr(), s.as_ptr(), positions.len(), gs.as_mut_ptr(), mask.as_mut_ptr()) },
+    };
     if rc != ffi::MPVSS_OK {
         return None;        // a share without an inverse: the reference returns None as well (:551-553)
     }

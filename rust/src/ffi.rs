@@ -254,6 +254,26 @@ unsafe extern "C" {
                                                 a2_out_host: *mut u8) -> c_int;
     pub fn mpvss_modp_group_verify_shares(ctx: *mut mpvss_ctx, grp: *const mpvss_modp_group, space: c_int, pk: *const u8, s: *const u8,
                                           y: *const u8, c: *const u8, r: *const u8, n: usize, verdicts_host: *mut u8) -> c_int;
+    pub fn mpvss_modp_group_batch_twin_exp(ctx: *mut mpvss_ctx, grp: *const mpvss_modp_group, space: c_int, bases: *const u8, e1: *const u8,
+                                           e2: *const u8, n: usize, out1: *mut u8, out2: *mut u8) -> c_int;
+    pub fn mpvss_modp_group_twin_min_shares(grp: *const mpvss_modp_group) -> c_int;
+    pub fn mpvss_modp_group_distribute(ctx: *mut mpvss_ctx, grp: *const mpvss_modp_group, space: c_int, commitments: *const u8, t: usize,
+                                       positions: *const i64, pubkeys: *const u8, p_values: *const u8, witnesses: *const u8, n: usize,
+                                       x_out: *mut u8, y_out: *mut u8, a1_out: *mut u8, a2_out: *mut u8, digest32_out: *mut u8) -> c_int;
+    pub fn mpvss_modp_group_deal(ctx: *mut mpvss_ctx, grp: *const mpvss_modp_group, coeffs_host: *const u8, t: usize,
+                                 positions_host: *const i64, pubkeys_host: *const u8, witnesses_host: *const u8, n: usize,
+                                 x_out: *mut u8, y_out: *mut u8, a1_out: *mut u8, a2_out: *mut u8, digest32_out: *mut u8,
+                                 challenge_out256: *mut u8, r_out: *mut u8) -> c_int;
+    pub fn mpvss_modp_group_extract_shares(ctx: *mut mpvss_ctx, grp: *const mpvss_modp_group, space: c_int, pk: *const u8, y: *const u8,
+                                           xinv: *const u8, w: *const u8, n: usize, s_out: *mut u8, c_out_host: *mut u8) -> c_int;
+    pub fn mpvss_modp_group_reconstruct(ctx: *mut mpvss_ctx, grp: *const mpvss_modp_group, space: c_int, positions_host: *const i64,
+                                        shares: *const u8, m: usize, gs_out256: *mut u8, mask_out32: *mut u8) -> c_int;
+    pub fn mpvss_modp_group_scalar_mul(grp: *const mpvss_modp_group, a256: *const u8, b256: *const u8, out256: *mut u8) -> c_int;
+    pub fn mpvss_modp_group_scalar_sub(grp: *const mpvss_modp_group, a256: *const u8, b256: *const u8, out256: *mut u8) -> c_int;
+    pub fn mpvss_modp_group_dleq_responses(grp: *const mpvss_modp_group, w: *const u8, alpha: *const u8, c: *const u8, c_per_share: c_int,
+                                           n: usize, r_out: *mut u8, threads: c_int) -> c_int;
+    pub fn mpvss_modp_group_poly_eval(grp: *const mpvss_modp_group, coeffs: *const u8, t: usize, positions: *const i64, n: usize,
+                                      out: *mut u8, threads: c_int) -> c_int;
     // ---- hashing helpers
     pub fn mpvss_sha256(data: *const u8, len: usize, out32: *mut u8);
     pub fn mpvss_modp_hash_to_scalar(data: *const u8, len: usize, out256: *mut u8);

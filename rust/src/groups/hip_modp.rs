@@ -48,7 +48,8 @@ impl HipModpGroup {
     }
 
     /// `ModpGroup::init(length)` (modp.rs:72-84): the reference generates the safe prime (num_primes, its own choice of
-    /// prime), the engine runs the group's exp / mul and the batched protocol calls of crate::batch on the GPU.  Moduli above
+    /// prime), the engine runs the group's exp / mul and the whole protocol of crate::batch on the GPU -- distribute_secret,
+    /// verify_distribution_shares, extract_secret_shares, verify_shares and reconstruct (only verify_many stays with group 14).  Moduli above
     /// 2048 bits have no GPU path and there is no CPU fallback: `init(length > 2048)` panics.
     pub fn init(length: u32) -> Arc<Self> {
         assert!(length <= 2048, "HipModpGroup::init({length}): the MI355X engine covers MODP groups of at most 2048 bits and has no CPU fallback");

@@ -5,12 +5,30 @@
   verify      mpvss_modp_group_verify_distribution at (n, t) = (4096, 64) and (65536, 256) for 1024, 1536 and 2048 bits:
               share verifications per second (random box contents: the same work as a valid box, the verdict is 0)
 
+  twin        (--legs twin) two powers of one base, kernels alone (mpvss_last_kernel_ms): mpvss_modp_group_batch_twin_exp as the
+              loaded library dispatches it, beside the baseline a caller had before it: two mpvss_modp_group_batch_exp calls
+              over the same bases, at n = 256 .. 65536 for 1024 and 2048 bits (--twin-parts call / baseline: one of the two)
+  deal        (--legs deal) mpvss_modp_group_deal and mpvss_modp_group_extract_shares as whole calls from host buffers at
+              (n, t) = (4096, 64) and (65536, 256) for 1024 and 2048 bits: shares per second and the kernels' time inside the
+              call.  host_scalar_retimed_ms is NOT measured inside the call: it is a separate timing, afterwards, of the
+              scalar-ring entry points on operands of the same size (P(i) and the responses, or the n products w / x);
+              rest_ms = call - kernels - that figure (hashing, staging, copies)
+  --ab PARENT the interleaved A/B behind the crossover constant (rt_twin_min_shares, capi_modp_rt.inc) and the 1.2x gate.
+              Needs `make -C mpvss_rs_amd/csrc twin-ab` (ab_libs/libmpvss_hip_twin.so and _sets.so: the dispatch pinned to
+              either path) and PARENT, a built checkout of the commit before the twin path (git worktree add PARENT <commit>;
+              make -C PARENT/mpvss_rs_amd/csrc).  Each round runs three fresh processes of this tool one after the other:
+              the twin build, the sets build, and the baseline under PARENT's own bindings and library; the best of all
+              rounds per (path, bits, n) makes the table, the crossover per width is the smallest measured n from which the
+              twin kernel beats the sets at every measured n above, and the gate is twin against PARENT's two batch_exp calls
+              at n = 65536.  Then the deal leg runs under the default library.  All lines go to profiles/modp_rt_deal_rate.txt.
+
 Host buffers in and out (the calls' own staging included), best of `--reps` after one warm-up call.  One JSON line per
-measurement.  Usage: python tools/modp_rt_rate.py [--quick] [--reps 3]"""
+measurement.  Usage: python tools/modp_rt_rate.py [--quick] [--reps 3] [--legs rates,twin,deal] [--ab PARENT [--rounds 2]]"""
 import argparse
 import json
 import os
 import random
+import subprocess
 import sys
 import time
 
@@ -18,7 +36,16 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path[:0] = [ROOT, os.path.join(ROOT, "tests"), os.path.join(ROOT, "oracle")]
 
 import modp_rt_helpers as H  # noqa: E402
-from mpvss_rs_amd import Engine, ModpGroup  # noqa: E402
+
+Engine = ModpGroup = capi = None          # bound by load_package(): from this checkout, or from --package-root
+
+
+def load_package(root):
+    global Engine, ModpGroup, capi
+    if root:
+        sys.path.insert(0, os.path.abspath(root))
+    import mpvss_rs_amd
+    Engine, ModpGroup, capi = mpvss_rs_amd.Engine, mpvss_rs_amd.ModpGroup, mpvss_rs_amd.capi
 
 
 def best(fn, reps):
@@ -40,13 +67,150 @@ def rand_bytes(rng, n, bits):
     return b"".join(rng.getrandbits(bits).to_bytes(256, "big") for _ in range(n))
 
 
+def twin_leg(eng, a, rng):
+    lib = os.path.basename(os.path.dirname(capi.LIB_PATH)) + "/" + os.path.basename(capi.LIB_PATH)
+    sizes = [256, 4096] if a.quick else [256, 1024, 4096, 8192, 16384, 32768, 65536]
+    for bits in (1024, 2048):
+        grp = ModpGroup(H.rfc_prime(bits))
+        for n in sizes:
+            B, E1, E2 = rand_bytes(rng, n, 2048), rand_bytes(rng, n, bits), rand_bytes(rng, n, bits)
+            row = {"what": "twin", "lib": lib, "bits": bits, "n": n}
+            if "call" in a.twin_parts:
+                ts = []
+                for _ in range(a.reps + 1):
+                    eng.group_batch_twin_exp(grp, B, E1, E2)
+                    ts.append(kernel_ms(eng))
+                row["twin_call_kernel_ms"] = min(ts[1:])
+            if "baseline" in a.twin_parts:
+                ts = []
+                for _ in range(a.reps + 1):
+                    eng.group_batch_exp(grp, B, E1)
+                    k = kernel_ms(eng)
+                    eng.group_batch_exp(grp, B, E2)
+                    ts.append(round(k + kernel_ms(eng), 3))
+                row["two_batch_exp_kernel_ms"] = min(ts[1:])
+            if "twin_call_kernel_ms" in row and "two_batch_exp_kernel_ms" in row:
+                row["speedup"] = round(row["two_batch_exp_kernel_ms"] / row["twin_call_kernel_ms"], 3)
+            print(json.dumps(row), flush=True)
+
+
+def deal_leg(eng, a, rng):
+    shapes = [(4096, 64)] if a.quick else [(4096, 64), (65536, 256)]
+    for bits in (1024, 2048):
+        q = H.rfc_prime(bits)
+        grp = ModpGroup(q)
+        for n, t in shapes:
+            coeffs, pos = rand_bytes(rng, t, bits - 1), list(range(1, n + 1))
+            y, w = rand_bytes(rng, n, bits - 1), rand_bytes(rng, n, bits - 1)
+            s = best(lambda: eng.group_deal(grp, coeffs, pos, y, w), a.reps)
+            kms = kernel_ms(eng)
+            t0 = time.perf_counter()
+            P = capi.group_poly_eval(grp, coeffs, pos)
+            capi.group_dleq_responses(grp, w, P, rand_bytes(rng, 1, 255))
+            host = time.perf_counter() - t0
+            print(json.dumps({"what": "group_deal", "bits": bits, "n": n, "t": t, "s": round(s, 4), "shares_per_s": round(n / s),
+                              "kernel_ms": kms, "host_scalar_retimed_ms": round(host * 1e3, 1),
+                              "rest_ms": round(s * 1e3 - host * 1e3 - kms, 1)}), flush=True)
+            xinv = rand_bytes(rng, n, bits - 1)
+            s = best(lambda: eng.group_extract_shares(grp, y, y, xinv, w), a.reps)
+            kms = kernel_ms(eng)
+            t0 = time.perf_counter()
+            capi.group_dleq_responses(grp, w, w, xinv)          # n products mod (q-1): the cost of e2 = w / x
+            host = time.perf_counter() - t0
+            print(json.dumps({"what": "group_extract_shares", "bits": bits, "n": n, "s": round(s, 4), "shares_per_s": round(n / s),
+                              "kernel_ms": kms, "host_scalar_retimed_ms": round(host * 1e3, 1),
+                              "rest_ms": round(s * 1e3 - host * 1e3 - kms, 1)}), flush=True)
+
+
+def child(args, lib, out, limit):
+    """one fresh process of this tool (the GPU is opened there only); its JSON lines, also echoed.  A child that fails ends
+    the whole run: nothing more is started on the GPU after it.  `limit`: seconds this leg may take."""
+    env = dict(os.environ)
+    if lib:
+        env["MPVSS_HIP_LIB"] = lib
+    try:
+        r = subprocess.run([sys.executable, os.path.abspath(__file__)] + args, env=env, stdout=subprocess.PIPE, text=True,
+                           timeout=limit)
+    except subprocess.TimeoutExpired:
+        sys.exit(f"modp_rt_rate: {args} under {lib or 'the default library'} did not end within {limit} s; nothing more is started")
+    rows = [json.loads(l) for l in r.stdout.splitlines() if l.startswith("{")]
+    for row in rows:
+        print(json.dumps(row), flush=True)
+    out += rows
+    if r.returncode != 0:
+        sys.exit(f"modp_rt_rate: {args} under {lib or 'the default library'} ended with {r.returncode}")
+    return rows
+
+
+def ab(a):
+    libs = {k: os.path.join(ROOT, "ab_libs", f"libmpvss_hip_{k}.so") for k in ("twin", "sets")}
+    for f in list(libs.values()) + [os.path.join(a.ab, "mpvss_rs_amd", "libmpvss_hip.so")]:
+        if not os.path.exists(f):
+            sys.exit(f"modp_rt_rate --ab: {f} is missing (see the head of this file)")
+    common = ["--legs", "twin", "--reps", str(a.reps)] + (["--quick"] if a.quick else [])
+    lines, ms = [], {}
+    for rnd in range(a.rounds):
+        for path in ("twin", "sets", "parent"):
+            if path == "parent":
+                rows = child(common + ["--twin-parts", "baseline", "--package-root", a.ab], None, [], a.twin_limit)
+            else:
+                rows = child(common + ["--twin-parts", "call"], libs[path], [], a.twin_limit)
+            for row in rows:
+                row.update(path=path, round=rnd)
+                v = row.get("twin_call_kernel_ms", row.get("two_batch_exp_kernel_ms"))
+                key = (path, row["bits"], row["n"])
+                ms[key] = min(ms.get(key, v), v)
+            lines += rows
+    for bits in sorted({k[1] for k in ms}):
+        sizes = sorted({k[2] for k in ms if k[1] == bits})
+        wins = []
+        for n in sizes:
+            tw, st, pa = ms["twin", bits, n], ms["sets", bits, n], ms["parent", bits, n]
+            wins.append(tw < st)
+            lines.append({"what": "twin_ab", "bits": bits, "n": n, "twin_kernel_ms": tw, "sets_kernel_ms": st,
+                          "parent_two_batch_exp_kernel_ms": pa, "twin_over_parent": round(pa / tw, 3),
+                          "sets_over_parent": round(pa / st, 3), "twin_over_sets": round(st / tw, 3)})
+        first = next((n for i, n in enumerate(sizes) if all(wins[i:])), None)
+        lines.append({"what": "twin_crossover", "bits": bits, "min_shares": first, "measured_sizes": sizes})
+        top = sizes[-1]
+        lines.append({"what": "twin_gate", "bits": bits, "n": top, "twin_over_parent": round(ms["parent", bits, top] / ms["twin", bits, top], 3),
+                      "required": 1.2, "met": ms["parent", bits, top] / ms["twin", bits, top] >= 1.2})
+    for row in lines:
+        if row["what"].startswith("twin_"):
+            print(json.dumps(row), flush=True)
+    child(["--legs", "deal", "--reps", str(a.reps)] + (["--quick"] if a.quick else []), None, lines, a.deal_limit)
+    os.makedirs(os.path.join(ROOT, "profiles"), exist_ok=True)
+    with open(a.out, "w") as f:
+        for row in lines:
+            f.write(json.dumps(row) + "\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--quick", action="store_true", help="smaller shapes (a check of the tool, not a measurement)")
+    ap.add_argument("--legs", default="rates", help="comma-separated: rates (batch_exp, verify), twin, deal")
+    ap.add_argument("--twin-parts", default="call,baseline", help="of the twin leg: call (batch_twin_exp), baseline (two batch_exp)")
+    ap.add_argument("--package-root", default=None, help="import mpvss_rs_amd (bindings and library) from this checkout")
+    ap.add_argument("--ab", default=None, metavar="PARENT", help="the interleaved A/B against a built checkout of the parent commit")
+    ap.add_argument("--rounds", type=int, default=2, help="of --ab: how often the three processes take turns")
+    ap.add_argument("--twin-limit", type=int, default=300, help="of --ab: seconds one twin-leg process may take")
+    ap.add_argument("--deal-limit", type=int, default=900, help="of --ab: seconds the deal-leg process may take (host threads at (65536, 256))")
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "modp_rt_deal_rate.txt"), help="of --ab: the file written")
     a = ap.parse_args()
+    if a.ab:
+        return ab(a)
+    load_package(a.package_root)
     eng = Engine(0)
     rng = random.Random(1)
+    legs = a.legs.split(",")
+    if "twin" in legs:
+        twin_leg(eng, a, rng)
+    if "deal" in legs:
+        deal_leg(eng, a, rng)
+    if "rates" not in legs:
+        eng.close()
+        return
     n = 4096 if a.quick else 65536
     moduli = {512: H.small_safe_primes()[512], 1024: H.rfc_prime(1024), 1536: H.rfc_prime(1536), 2048: H.rfc_prime(2048)}
     rates = {}
