@@ -566,6 +566,24 @@ int mpvss_modp_group_batch_twin_exp(mpvss_ctx* ctx, const mpvss_modp_group* grp,
 /* the batch size (shares of one call, or of one chunk of a longer one) from which this group's width takes the shared-squarings
  * kernel; smaller batches run the two exponent sets.  Host only; informational -- the results do not depend on it. */
 int mpvss_modp_group_twin_min_shares(const mpvss_modp_group* grp);
+/* out[i] = base^exps[i] mod q for ONE base in host memory (256 bytes, any value): the handle's counterpart of
+ * mpvss_modp_batch_exp_fixed_base -- generate_public_key (base G = 2) and the commitments C_j = g^a_j (base g = 4).  exps and out
+ * n x 256 bytes in `space`; exponents staged from the host are zeroed on the device before the call returns.
+ * Fixed-base combs: a context keeps up to 4 tables base^(d 16^k), k < 512, d < 16, keyed by the bytes (q, base), least recently
+ * used evicted, freed with the context.  Every power of a base shared by a whole call -- this entry point, X_i = g^P(i) and
+ * a1_i = g^w_i of group_deal / group_distribute, a1_i = G^w_i of group_extract_shares, the g1^r leg of a1 in
+ * group_dleq_commitments / group_verify_distribution / group_verify_shares -- runs over the comb without squarings when the
+ * context has it, builds it when the call (or chunk) has at least mpvss_modp_group_comb_min_shares shares, and otherwise takes
+ * the 16-entry window table as before.  Same bytes either way.  The tables hold public values only. */
+int mpvss_modp_group_batch_exp_fixed_base(mpvss_ctx* ctx, const mpvss_modp_group* grp, int space, const uint8_t* base_host,
+                                          const uint8_t* exps, size_t n, uint8_t* out);
+/* builds the combs of the group's generators g = 4 and G = 2 on this context now, so that small calls use them too */
+int mpvss_modp_group_prepare(mpvss_ctx* ctx, const mpvss_modp_group* grp);
+/* the batch size from which a call builds a comb it does not find in the context's cache.  Host only; informational -- the
+ * results do not depend on it. */
+int mpvss_modp_group_comb_min_shares(const mpvss_modp_group* grp);
+/* comb cache of the context since it was created: tables built, uses of a cached table, tables evicted (any pointer may be null) */
+int mpvss_modp_group_comb_stats(mpvss_ctx* ctx, unsigned long long* builds, unsigned long long* hits, unsigned long long* evictions);
 /* dealer's group side, src/participant.rs:160-286 with p_i = P(i) mod (q-1) and the witnesses as input: same contract as
  * mpvss_modp_distribute */
 int mpvss_modp_group_distribute(mpvss_ctx* ctx, const mpvss_modp_group* grp, int space, const uint8_t* commitments, size_t t,
@@ -574,7 +592,7 @@ int mpvss_modp_group_distribute(mpvss_ctx* ctx, const mpvss_modp_group* grp, int
 /* the dealer's whole box in one call from HOST buffers: same contract as mpvss_modp_deal (x_out, a1_out, a2_out, digest32_out
  * and challenge_out256 optional; t <= n; t == 0 with n > 0 and a negative position are MPVSS_E_INVALID; n == 0 gives the digest
  * of the empty transcript).  P(i) and the responses are host-thread work here, X_i = g^P(i) and a1_i = g^w_i run over the
- * window table of g = 4.  Every buffer of the call that held coefficients, P(i), witnesses or buckets is zeroed before it
+ * comb of g = 4, or over its window table for a small box on a context without the comb.  Every buffer of the call that held coefficients, P(i), witnesses or buckets is zeroed before it
  * returns, on error paths too. */
 int mpvss_modp_group_deal(mpvss_ctx* ctx, const mpvss_modp_group* grp, const uint8_t* coeffs_host, size_t t,
                           const int64_t* positions_host, const uint8_t* pubkeys_host, const uint8_t* witnesses_host, size_t n,

@@ -52,6 +52,8 @@ EXPORTED_SYMBOLS = (
     "mpvss_modp_group_batch_twin_exp", "mpvss_modp_group_distribute", "mpvss_modp_group_deal", "mpvss_modp_group_extract_shares",
     "mpvss_modp_group_reconstruct", "mpvss_modp_group_scalar_mul", "mpvss_modp_group_scalar_sub", "mpvss_modp_group_dleq_responses",
     "mpvss_modp_group_poly_eval", "mpvss_modp_group_twin_min_shares",
+    "mpvss_modp_group_batch_exp_fixed_base", "mpvss_modp_group_prepare", "mpvss_modp_group_comb_min_shares",
+    "mpvss_modp_group_comb_stats",
 )
 
 GROUP_SECP256K1 = 1
@@ -230,6 +232,10 @@ def load_library() -> C.CDLL:
     lib.mpvss_modp_group_dleq_responses.argtypes = [vp, u8p, u8p, u8p, ci, sz, u8p, ci]
     lib.mpvss_modp_group_poly_eval.argtypes = [vp, u8p, sz, i64p, sz, u8p, ci]
     lib.mpvss_modp_group_twin_min_shares.argtypes = [vp]
+    lib.mpvss_modp_group_batch_exp_fixed_base.argtypes = [vp, vp, ci, u8p, u8p, sz, u8p]
+    lib.mpvss_modp_group_prepare.argtypes = [vp, vp]
+    lib.mpvss_modp_group_comb_min_shares.argtypes = [vp]
+    lib.mpvss_modp_group_comb_stats.argtypes = [vp, C.POINTER(C.c_ulonglong), C.POINTER(C.c_ulonglong), C.POINTER(C.c_ulonglong)]
     return lib
 
 
@@ -275,6 +281,11 @@ class ModpGroup:
     def twin_min_shares(self) -> int:
         """batch size from which group_batch_twin_exp / group_deal / group_extract_shares take the shared-squarings kernel"""
         return self.lib.mpvss_modp_group_twin_min_shares(self.handle)
+
+    @property
+    def comb_min_shares(self) -> int:
+        """batch size from which a call builds the fixed-base comb of a shared base the context has not cached"""
+        return self.lib.mpvss_modp_group_comb_min_shares(self.handle)
 
     def hash_to_scalar(self, data: bytes) -> bytes:
         kd, pd = _buf(data if data else b"\0")
@@ -422,6 +433,24 @@ class Engine:
         ka, pa = _buf(bases); kb, pb = _buf(exps); ko, po = _out(n * EB)
         self._check(self.lib.mpvss_modp_group_batch_exp(self.ctx, grp.handle, MPVSS_HOST, pa, pb, n, po), "group_batch_exp")
         return bytes(ko)[: n * EB]
+
+    def group_batch_exp_fixed_base(self, grp: "ModpGroup", base: bytes, exps: bytes) -> bytes:
+        """base^exps[i] for one 256-byte base: over the base's comb when the context has or builds it"""
+        n = len(exps) // EB
+        ka, pa = _buf(base); kb, pb = _buf(exps or None); ko, po = _out(n * EB)
+        self._check(self.lib.mpvss_modp_group_batch_exp_fixed_base(self.ctx, grp.handle, MPVSS_HOST, pa, pb, n, po),
+                    "group_batch_exp_fixed_base")
+        return bytes(ko)[: n * EB]
+
+    def group_prepare(self, grp: "ModpGroup") -> None:
+        """build the combs of g = 4 and G = 2 on this context now"""
+        self._check(self.lib.mpvss_modp_group_prepare(self.ctx, grp.handle), "group_prepare")
+
+    def group_comb_stats(self) -> dict:
+        """comb cache of this context: tables built, uses of a cached table, tables evicted"""
+        b, h, e = C.c_ulonglong(0), C.c_ulonglong(0), C.c_ulonglong(0)
+        self._check(self.lib.mpvss_modp_group_comb_stats(self.ctx, C.byref(b), C.byref(h), C.byref(e)), "group_comb_stats")
+        return {"builds": int(b.value), "hits": int(h.value), "evictions": int(e.value)}
 
     def group_batch_mul(self, grp: "ModpGroup", a: bytes, b: bytes) -> bytes:
         n = len(a) // EB

@@ -98,16 +98,70 @@ int rt_stage_small(mpvss_ctx* ctx, const uint8_t* host256, DevBuf& buf, const ui
   return 0;
 }
 
-// a1 = g1^r h1^c and a2 = g2^r h2^c for cnt shares (device pointers; g1 one shared base, c stride 0 = shared)
-int rt_dleq_dev(mpvss_ctx* ctx, const mpvss_modp_group* grp, const modp_rt_consts* dc, const uint8_t* g1_dev, const uint8_t* h1,
+// The batch size (shares of one call, or of one chunk) from which a call builds the fixed-base comb of a base it does not find
+// in the context's cache: the build is one sequential chain of 2 044 squarings, and the smallest n from which build + comb
+// launch is no slower than the 16-entry table + left-to-right launch it replaces is what `tools/modp_rt_rate.py --comb --ab`
+// measures (profiles/modp_rt_comb_rate.txt, DESIGN section 13).  A cached comb is used at every size.  The tuning build of
+// `make comb-ab` pins it with -DMPVSS_RT_COMB_MIN_SHARES=n.
+#ifdef MPVSS_RT_COMB_MIN_SHARES
+size_t rt_comb_min_shares(int) { return (size_t)(MPVSS_RT_COMB_MIN_SHARES); }
+#else
+size_t rt_comb_min_shares(int) { return 16384; }   // UNMEASURED placeholder (the twin crossover's figure)
+#endif
+
+// The one launch decision for a power of a base shared by the whole call (context lock held): the comb of (q, base) when the
+// context has it; built now when the call has at least rt_comb_min_shares shares, or when `build` says so
+// (mpvss_modp_group_prepare); otherwise *comb = null and the caller takes the 16-entry table of the base.  Builds run in stream
+// order inside the call that needs them; calls that took the context lock are serialised, so an evicted table has no reader
+// in flight.  The tables hold public values only and are not wiped.
+int rt_comb_for(mpvss_ctx* ctx, const mpvss_modp_group* grp, const modp_rt_consts* dc, const uint8_t* base_host, size_t cnt, bool build,
+                const uint32_t** comb) {
+  *comb = nullptr;
+  uint8_t key[2 * EB];
+  memcpy(key, grp->q_be, EB);
+  memcpy(key + EB, base_host, EB);
+  mpvss_ctx::RtComb* victim = &ctx->rt_comb[0];
+  for (auto& e : ctx->rt_comb) {
+    if (e.key.size() == sizeof(key) && memcmp(e.key.data(), key, sizeof(key)) == 0) {
+      e.used = ++ctx->rt_comb_clock;
+      ++ctx->rt_comb_hits;
+      *comb = (const uint32_t*)e.buf.p;
+      return 0;
+    }
+    if (!victim->key.empty() && (e.key.empty() || e.used < victim->used)) victim = &e;
+  }
+  if (!build && cnt < rt_comb_min_shares(grp->lpl)) return 0;
+  const bool evicts = !victim->key.empty();
+  victim->key.clear();                                   // no table while the build can still fail
+  RET_IF(ensure(ctx, victim->buf, modp_rt_comb_bytes(grp->lpl)));
+  const uint8_t* db;
+  RET_IF(rt_stage_small(ctx, base_host, ctx->rt_small[0], &db));
+  TIMED_LAUNCH(ctx, 2, modp_rt_launch_comb_build(grp->lpl, db, (uint32_t*)victim->buf.p, dc, ctx->stream));
+  victim->key.assign(key, key + sizeof(key));
+  victim->used = ++ctx->rt_comb_clock;
+  ++ctx->rt_comb_builds;
+  if (evicts) ++ctx->rt_comb_evictions;
+  *comb = (const uint32_t*)victim->buf.p;
+  return 0;
+}
+
+// a1 = g1^r h1^c and a2 = g2^r h2^c for cnt shares (device pointers but g1: one shared base in host bytes; c stride 0 = shared)
+int rt_dleq_dev(mpvss_ctx* ctx, const mpvss_modp_group* grp, const modp_rt_consts* dc, const uint8_t* g1_host, const uint8_t* h1,
                 const uint8_t* g2, const uint8_t* h2, const uint8_t* r, const uint8_t* c, size_t c_stride, size_t cnt, uint8_t* a1,
                 uint8_t* a2) {
   const size_t TW = 16 * rt_L(grp);
   const uint32_t *tg, *t1, *t2;
   if (a1) {
-    RET_IF(rt_tables(ctx, grp, dc, g1_dev, 0, 1, ctx->rt_tabg, &tg));
+    RET_IF(rt_comb_for(ctx, grp, dc, g1_host, cnt, false, &tg));
     RET_IF(rt_tables(ctx, grp, dc, h1, EB, cnt, ctx->rt_tab1, &t1));
-    TIMED_LAUNCH(ctx, 1, modp_rt_launch_dual_exp(grp->lpl, tg, 0, t1, TW, r, EB, c, c_stride, (int)cnt, a1, dc, ctx->stream));
+    if (tg) {
+      TIMED_LAUNCH(ctx, 1, modp_rt_launch_comb_exp(grp->lpl, tg, t1, TW, r, c, c_stride, (int)cnt, a1, dc, ctx->stream));
+    } else {
+      const uint8_t* dg1;
+      RET_IF(rt_stage_small(ctx, g1_host, ctx->rt_small[0], &dg1));
+      RET_IF(rt_tables(ctx, grp, dc, dg1, 0, 1, ctx->rt_tabg, &tg));
+      TIMED_LAUNCH(ctx, 1, modp_rt_launch_dual_exp(grp->lpl, tg, 0, t1, TW, r, EB, c, c_stride, (int)cnt, a1, dc, ctx->stream));
+    }
   }
   if (a2) {
     RET_IF(rt_tables(ctx, grp, dc, g2, EB, cnt, ctx->rt_tab1, &t1));
@@ -318,8 +372,7 @@ extern "C" int mpvss_modp_group_dleq_commitments(mpvss_ctx* ctx, const mpvss_mod
   spans_reset(ctx);
   const modp_rt_consts* dc;
   RET_IF(rt_upload(ctx, grp, &dc));
-  const uint8_t *dg1 = nullptr, *dcc = nullptr;
-  RET_IF(rt_stage_small(ctx, g1_host, ctx->rt_small[0], &dg1));
+  const uint8_t* dcc = nullptr;
   if (!c_per_share) RET_IF(rt_stage_small(ctx, c, ctx->rt_small[1], &dcc));
   for (size_t off = 0; off < n; off += MAX_CHUNK) {
     const size_t cnt = (n - off < MAX_CHUNK) ? n - off : MAX_CHUNK;
@@ -337,7 +390,7 @@ extern "C" int mpvss_modp_group_dleq_commitments(mpvss_ctx* ctx, const mpvss_mod
       d1 = (uint8_t*)ctx->rt_out[0].p;
       d2 = (uint8_t*)ctx->rt_out[1].p;
     }
-    RET_IF(rt_dleq_dev(ctx, grp, dc, dg1, (const uint8_t*)dh1, (const uint8_t*)dg2, (const uint8_t*)dh2, (const uint8_t*)dr,
+    RET_IF(rt_dleq_dev(ctx, grp, dc, g1_host, (const uint8_t*)dh1, (const uint8_t*)dg2, (const uint8_t*)dh2, (const uint8_t*)dr,
                        (const uint8_t*)dcs, c_per_share ? EB : 0, cnt, d1, d2));
     if (space == MPVSS_HOST) {
       RET_IF(copy_out(ctx, space, a1_out + off * EB, d1, cnt * EB));
@@ -368,8 +421,7 @@ extern "C" int mpvss_modp_group_verify_distribution(mpvss_ctx* ctx, const mpvss_
     const modp_rt_consts* dc;
     RET_IF(rt_upload(ctx, grp, &dc));
     RET_IF(rt_stage_commitments(ctx, grp, dc, space, commitments, t));
-    const uint8_t *dg, *dch;
-    RET_IF(rt_stage_small(ctx, grp->g_be, ctx->rt_small[0], &dg));
+    const uint8_t* dch;
     RET_IF(rt_stage_small(ctx, challenge_host, ctx->rt_small[1], &dch));
     const size_t chunk = std::min(n, MAX_CHUNK);
     std::vector<uint8_t> hX(chunk * EB), hY(chunk * EB), h1(chunk * EB), h2(chunk * EB);
@@ -387,7 +439,7 @@ extern "C" int mpvss_modp_group_verify_distribution(mpvss_ctx* ctx, const mpvss_
       uint8_t* d2 = (uint8_t*)ctx->rt_out[2].p;
       RET_IF(rt_commit_eval_dev(ctx, grp, dc, t, dpos, cnt, dX));
       // a1 = g^r X^c, a2 = y^r Y^c (src/participant.rs:436-447 -> src/dleq.rs:66-84)
-      RET_IF(rt_dleq_dev(ctx, grp, dc, dg, dX, (const uint8_t*)dy, (const uint8_t*)dY, (const uint8_t*)dr, dch, 0, cnt, d1, d2));
+      RET_IF(rt_dleq_dev(ctx, grp, dc, grp->g_be, dX, (const uint8_t*)dy, (const uint8_t*)dY, (const uint8_t*)dr, dch, 0, cnt, d1, d2));
       HIPCHK(ctx, hipMemcpyAsync(hX.data(), dX, cnt * EB, hipMemcpyDeviceToHost, ctx->stream));
       HIPCHK(ctx, hipMemcpyAsync(h1.data(), d1, cnt * EB, hipMemcpyDeviceToHost, ctx->stream));
       HIPCHK(ctx, hipMemcpyAsync(h2.data(), d2, cnt * EB, hipMemcpyDeviceToHost, ctx->stream));
@@ -428,8 +480,6 @@ extern "C" int mpvss_modp_group_verify_shares(mpvss_ctx* ctx, const mpvss_modp_g
   spans_reset(ctx);
   const modp_rt_consts* dc;
   RET_IF(rt_upload(ctx, grp, &dc));
-  const uint8_t* dG;
-  RET_IF(rt_stage_small(ctx, grp->G_be, ctx->rt_small[0], &dG));
   const size_t chunk = std::min(n, MAX_CHUNK);
   std::vector<uint8_t> hpk, hY, hc, h1(chunk * EB), h2(chunk * EB);
   if (space == MPVSS_DEVICE) { hpk.resize(chunk * EB); hY.resize(chunk * EB); hc.resize(chunk * EB); }
@@ -446,7 +496,7 @@ extern "C" int mpvss_modp_group_verify_shares(mpvss_ctx* ctx, const mpvss_modp_g
     uint8_t* d1 = (uint8_t*)ctx->rt_out[1].p;
     uint8_t* d2 = (uint8_t*)ctx->rt_out[2].p;
     // a1 = G^r pk^c, a2 = S^r Y^c (src/participant.rs:361-386 -> src/dleq.rs:275-302)
-    RET_IF(rt_dleq_dev(ctx, grp, dc, dG, (const uint8_t*)dpk, (const uint8_t*)ds, (const uint8_t*)dy, (const uint8_t*)dr,
+    RET_IF(rt_dleq_dev(ctx, grp, dc, grp->G_be, (const uint8_t*)dpk, (const uint8_t*)ds, (const uint8_t*)dy, (const uint8_t*)dr,
                        (const uint8_t*)dcc, EB, cnt, d1, d2));
     HIPCHK(ctx, hipMemcpyAsync(h1.data(), d1, cnt * EB, hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(ctx, hipMemcpyAsync(h2.data(), d2, cnt * EB, hipMemcpyDeviceToHost, ctx->stream));
@@ -568,9 +618,16 @@ int rt_twin_dev(mpvss_ctx* ctx, const mpvss_modp_group* grp, const modp_rt_const
   return 0;
 }
 
-// out = base^e for one shared base (host bytes) and cnt exponents on the device
+// out = base^e for one shared base (host bytes) and cnt exponents on the device: over the base's comb (rt_comb_for), or else
+// left to right over its 16-entry table
 int rt_fixed_base_dev(mpvss_ctx* ctx, const mpvss_modp_group* grp, const modp_rt_consts* dc, const uint8_t* base_host, const uint8_t* e,
                       size_t cnt, uint8_t* out, int timer) {
+  const uint32_t* comb;
+  RET_IF(rt_comb_for(ctx, grp, dc, base_host, cnt, false, &comb));
+  if (comb) {
+    TIMED_LAUNCH(ctx, timer, modp_rt_launch_comb_exp(grp->lpl, comb, nullptr, 0, e, nullptr, 0, (int)cnt, out, dc, ctx->stream));
+    return 0;
+  }
   const uint8_t* db;
   RET_IF(rt_stage_small(ctx, base_host, ctx->rt_small[0], &db));
   const uint32_t* tg;
@@ -674,6 +731,67 @@ int rt_product_tree(mpvss_ctx* ctx, const mpvss_modp_group* grp, const modp_rt_c
 extern "C" int mpvss_modp_group_twin_min_shares(const mpvss_modp_group* grp) {
   if (rt_bad_group(grp)) return MPVSS_E_INVALID;
   return (int)std::min<size_t>(rt_twin_min_shares(grp->lpl), 0x7fffffff);
+}
+
+extern "C" int mpvss_modp_group_comb_min_shares(const mpvss_modp_group* grp) {
+  if (rt_bad_group(grp)) return MPVSS_E_INVALID;
+  return (int)std::min<size_t>(rt_comb_min_shares(grp->lpl), 0x7fffffff);
+}
+
+extern "C" int mpvss_modp_group_comb_stats(mpvss_ctx* ctx, unsigned long long* builds, unsigned long long* hits,
+                                           unsigned long long* evictions) {
+  if (!ctx) return MPVSS_E_INVALID;
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  if (builds) *builds = ctx->rt_comb_builds;
+  if (hits) *hits = ctx->rt_comb_hits;
+  if (evictions) *evictions = ctx->rt_comb_evictions;
+  return MPVSS_OK;
+}
+
+extern "C" int mpvss_modp_group_prepare(mpvss_ctx* ctx, const mpvss_modp_group* grp) {
+  if (!ctx) return MPVSS_E_INVALID;
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  if (rt_bad_group(grp)) return fail(ctx, MPVSS_E_INVALID, "group_prepare: no group");
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  spans_reset(ctx);
+  const modp_rt_consts* dc;
+  RET_IF(rt_upload(ctx, grp, &dc));
+  const uint32_t* comb;
+  RET_IF(rt_comb_for(ctx, grp, dc, grp->g_be, 0, true, &comb));
+  RET_IF(rt_comb_for(ctx, grp, dc, grp->G_be, 0, true, &comb));
+  RET_IF(spans_collect(ctx));
+  return MPVSS_OK;
+}
+
+// generate_public_key (G^x) and the commitments C_j = g^a_j of a run-time group: one base for the whole call
+extern "C" int mpvss_modp_group_batch_exp_fixed_base(mpvss_ctx* ctx, const mpvss_modp_group* grp, int space, const uint8_t* base_host,
+                                                     const uint8_t* exps, size_t n, uint8_t* out) {
+  if (!ctx) return MPVSS_E_INVALID;
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  if (rt_bad_group(grp)) return fail(ctx, MPVSS_E_INVALID, "group_batch_exp_fixed_base: no group");
+  if (n == 0) return MPVSS_OK;
+  if (!base_host || !exps || !out || n > 0x7fffffff) return fail(ctx, MPVSS_E_INVALID, "group_batch_exp_fixed_base: bad argument");
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  spans_reset(ctx);
+  RtWipe wipe{ctx};
+  const modp_rt_consts* dc;
+  RET_IF(rt_upload(ctx, grp, &dc));
+  for (size_t off = 0; off < n; off += MAX_CHUNK) {
+    const size_t cnt = (n - off < MAX_CHUNK) ? n - off : MAX_CHUNK;
+    const void* de;
+    if (space == MPVSS_HOST) wipe.device(ctx->rt_in[2], cnt * EB);        // keygen secrets
+    RET_IF(stage_in(ctx, space, exps + off * EB, cnt * EB, ctx->rt_in[2], &de));
+    uint8_t* dout = out + off * EB;
+    if (space == MPVSS_HOST) {
+      RET_IF(ensure(ctx, ctx->rt_out[0], cnt * EB));
+      dout = (uint8_t*)ctx->rt_out[0].p;
+    }
+    RET_IF(rt_fixed_base_dev(ctx, grp, dc, base_host, (const uint8_t*)de, cnt, dout, 1));
+    if (space == MPVSS_HOST) RET_IF(copy_out(ctx, space, out + off * EB, dout, cnt * EB));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+  }
+  RET_IF(spans_collect(ctx));
+  return MPVSS_OK;
 }
 
 extern "C" int mpvss_modp_group_batch_twin_exp(mpvss_ctx* ctx, const mpvss_modp_group* grp, int space, const uint8_t* bases,

@@ -33,6 +33,15 @@ int modp_rt_launch_table(int lpl, const uint8_t* base_be, size_t base_stride, in
 int modp_rt_launch_dual_exp(int lpl, const uint32_t* tab1, size_t tab1_stride, const uint32_t* tab2, size_t tab2_stride,
                             const uint8_t* e1, size_t e1_stride, const uint8_t* e2, size_t e2_stride, int count, uint8_t* out,
                             const modp_rt_consts* cs, hipStream_t s);
+/* fixed-base comb of one base shared by every share: comb[k][d] = base^(d 16^k) R mod N, k < 512, d < 16 --
+   modp_rt_comb_bytes(lpl) bytes (2.25 MiB at 18 limbs per lane, 1.125 MiB at 9, 640 KiB at 5).  The base is a 256-byte value
+   of any size on the device. */
+size_t modp_rt_comb_bytes(int lpl);
+int modp_rt_launch_comb_build(int lpl, const uint8_t* base_be, uint32_t* comb, const modp_rt_consts* cs, hipStream_t s);
+/* out[x] = base^e1[x] * B2[x]^e2[x] mod q, canonical: e1 over the comb with no squarings, e2 left to right over B2's 16-entry
+   table (tab2 == NULL: base^e1 alone; tab2_stride in words, e2_stride in bytes, 0 = one exponent for every x); e1 n x 256 bytes */
+int modp_rt_launch_comb_exp(int lpl, const uint32_t* comb, const uint32_t* tab2, size_t tab2_stride, const uint8_t* e1,
+                            const uint8_t* e2, size_t e2_stride, int count, uint8_t* out, const modp_rt_consts* cs, hipStream_t s);
 /* out1[x] = B[x]^e1[x], out2[x] = B[x]^e2[x] from the base's one table, two left-to-right exponent sets in one launch
    (gridDim.y = 2); exponents and results n x 256 bytes */
 int modp_rt_launch_exp_sets(int lpl, const uint32_t* tab, size_t tab_stride, const uint8_t* e1, const uint8_t* e2, int count,

@@ -230,6 +230,140 @@ __global__ void RT_KERNEL(LPL) k_rt_dual_exp(const u32* __restrict__ tab1, size_
 }
 
 // ---------------------------------------------------------------------------------------
+// Fixed-base comb of ONE base shared by every share: comb[k][d] = base^(d 16^k) R mod N, k = 0..511, d = 0..15, entry 0 =
+// R mod N.  Always 512 rows: any 256-byte exponent stays exact.  The counterpart of group 14's k_modp_comb_bases /
+// k_modp_comb_rows at a run-time width.
+//   k_rt_comb_bases (one workgroup, its first quad writes): the base enters through to_mont_in like a table base (a base
+//                   >= q is reduced, one that is 0 mod q gives rows of zeros); comb[k][1] = comb[k-1][1]^16, a row base
+//                   every four squarings, and entry 0 of every row
+//   k_rt_comb_rows  (one number per row k): comb[k][d] = comb[k][d-1] comb[k][1] for d = 2..15
+// ---------------------------------------------------------------------------------------
+#define RT_COMB_ROWS 512
+template <int LPL>
+__global__ void RT_KERNEL(LPL) k_rt_comb_bases(const uint8_t* __restrict__ base_be, u32* __restrict__ comb,
+                                               const modp_rt_consts* __restrict__ cs) {
+  constexpr int L = Width<LPL>::L, SLOT = Width<LPL>::SLOT;
+  __shared__ __attribute__((aligned(16))) u32 lds[RT_NUMS * SLOT];
+  const Lane ln = make_lane();
+  u32* slot = lds + (threadIdx.x >> 2) * SLOT;
+  const bool writer = (blockIdx.x == 0) && (threadIdx.x < 4);
+  const u32 n0inv = cs->n0inv;
+  u32 n[LPL], acc[LPL];
+  load_lane_limbs<LPL>(n, cs->n, ln);
+  load_lane_limbs<LPL>(acc, cs->one_m, ln);
+  if (writer) {
+#pragma nounroll
+    for (int k = 0; k < RT_COMB_ROWS; ++k) store_lane_limbs<LPL>(comb + (size_t)k * 16 * L, acc, ln);
+  }
+  to_mont_in<LPL>(acc, slot, base_be, cs, n, n0inv, ln);
+#pragma nounroll
+  for (int op = 0; op <= (RT_COMB_ROWS - 1) * 4; ++op) {
+    if (writer && (op & 3) == 0) store_lane_limbs<LPL>(comb + ((size_t)(op >> 2) * 16 + 1) * L, acc, ln);
+    if (op == (RT_COMB_ROWS - 1) * 4) break;
+    slot_store<LPL>(slot, acc, ln);
+    __builtin_amdgcn_wave_barrier();
+    mont_mul<N0INV_RUNTIME, true>(acc, acc, slot, n, ln, n0inv);
+    __builtin_amdgcn_wave_barrier();
+  }
+}
+
+template <int LPL>
+__global__ void RT_KERNEL(LPL) k_rt_comb_rows(u32* __restrict__ comb, const modp_rt_consts* __restrict__ cs) {
+  constexpr int L = Width<LPL>::L, SLOT = Width<LPL>::SLOT;
+  __shared__ __attribute__((aligned(16))) u32 lds[RT_NUMS * SLOT];
+  const Lane ln = make_lane();
+  const int xi = blockIdx.x * RT_NUMS + (threadIdx.x >> 2);
+  const bool live = xi < RT_COMB_ROWS;
+  const int k = live ? xi : RT_COMB_ROWS - 1;
+  u32* slot = lds + (threadIdx.x >> 2) * SLOT;
+  const u32 n0inv = cs->n0inv;
+  u32 n[LPL], acc[LPL];
+  load_lane_limbs<LPL>(n, cs->n, ln);
+  u32* row = comb + (size_t)k * 16 * L;
+  load_lane_limbs<LPL>(acc, row + L, ln);
+  slot_store<LPL>(slot, acc, ln);
+  __builtin_amdgcn_wave_barrier();
+#pragma nounroll
+  for (int d = 2; d < 16; ++d) {
+    mont_mul<N0INV_RUNTIME>(acc, acc, slot, n, ln, n0inv);
+    if (live) store_lane_limbs<LPL>(row + (size_t)d * L, acc, ln);
+  }
+}
+
+// ---------------------------------------------------------------------------------------
+// out[x] = base^e1[x] (* B2[x]^e2[x] when tab2 is not null) over the comb of the shared base: no squaring for e1 at all.
+//   phase A (tab2 only): B2^e2 left to right, 4-bit windows over B2's 16-entry table from the wave's highest set bit of e2
+//                        (e2_stride 0: one exponent for every x)
+//   phase B            : acc *= comb[k][nibble(e1, k)] for k = 0 .. nw1-1, nw1 from the wave's longest e1; a window whose digit
+//                        is 0 in all 16 numbers of the wave is skipped, otherwise a lane with digit 0 multiplies by entry 0
+//   then times plain 1.  Without tab2 and with every e1 of the wave 0 the result is 1.
+// One Montgomery-product site as in rt_dual_exp_body: every step only chooses its LDS operand.  The comb index is an exponent
+// digit, so the gather address follows the exponent, as the nibble-indexed table reads of k_rt_dual_exp do.
+// Full-width e1 at 2048 bits: 512 comb products + 1 exit = 513 Montgomery operations (tests/test_modp_rt_comb_model.py).
+// ---------------------------------------------------------------------------------------
+template <int LPL>
+__global__ void RT_KERNEL(LPL) k_rt_comb_exp(const u32* __restrict__ comb, const u32* __restrict__ tab2, size_t tab2_stride,
+                                             const uint8_t* __restrict__ e1_be, const uint8_t* __restrict__ e2_be, size_t e2_stride,
+                                             int count, uint8_t* __restrict__ out_be, const modp_rt_consts* __restrict__ cs) {
+  constexpr int L = Width<LPL>::L, SLOT = Width<LPL>::SLOT;
+  __shared__ __attribute__((aligned(16))) u32 lds[RT_NUMS * SLOT];
+  const Lane ln = make_lane();
+  const int xi = blockIdx.x * RT_NUMS + (threadIdx.x >> 2);
+  const bool live = xi < count;
+  const int x = live ? xi : count - 1;
+  u32* slot = lds + (threadIdx.x >> 2) * SLOT;
+  const u32 n0inv = cs->n0inv;
+  const bool has2 = tab2 != nullptr;
+  const uint8_t* e1 = e1_be + (size_t)x * 256;
+  const uint8_t* e2 = has2 ? e2_be + (size_t)x * e2_stride : e1;
+  const u32* t2 = has2 ? tab2 + (size_t)x * tab2_stride : comb;
+  u32 n[LPL], acc[LPL];
+  load_lane_limbs<LPL>(n, cs->n, ln);
+  const int nw1 = (wave_max_bits(e1, ln) + 3) >> 2;                 // <= 512 = RT_COMB_ROWS
+  const int nw2 = has2 ? (wave_max_bits(e2, ln) + 3) >> 2 : 0;
+  // steps: 0..3 square, 4 times tab2[d2], 5 next window of e2, 6 times comb[k][d1], 7 final (times plain 1)
+  int w = nw2 - 1, k = 0, s;
+  if (nw2 == 0) {
+    load_lane_limbs<LPL>(acc, cs->one_m, ln);
+    s = 6;
+  } else {
+    load_lane_limbs<LPL>(acc, t2 + (size_t)nibble(e2, w) * L, ln);
+    s = 5;
+  }
+  while (true) {
+    if (s == 5) {
+      if (w == 0) {
+        s = 6;
+      } else {
+        --w;
+        s = 0;
+      }
+    }
+    if (s == 6) {
+      while (k < nw1 && __builtin_amdgcn_ballot_w64(nibble(e1, k) != 0) == 0) ++k;
+      if (k == nw1) s = 7;
+    }
+    if (s == 7) {
+      slot_fill_from_global<LPL>(slot, cs->one, ln);
+    } else if (s < 4) {
+      slot_store<LPL>(slot, acc, ln);
+    } else if (s == 4) {
+      slot_fill_from_global<LPL>(slot, t2 + (size_t)nibble(e2, w) * L, ln);
+    } else {
+      slot_fill_from_global<LPL>(slot, comb + ((size_t)k * 16 + nibble(e1, k)) * L, ln);
+      ++k;
+    }
+    __builtin_amdgcn_wave_barrier();
+    if (s < 4) mont_mul<N0INV_RUNTIME, true>(acc, acc, slot, n, ln, n0inv);
+    else mont_mul<N0INV_RUNTIME>(acc, acc, slot, n, ln, n0inv);
+    __builtin_amdgcn_wave_barrier();
+    if (s == 7) break;
+    if (s < 5) ++s;
+  }
+  store_canonical<LPL>(out_be + (size_t)x * 256, acc, slot, cs, ln, live);
+}
+
+// ---------------------------------------------------------------------------------------
 // Two powers of each base in ONE launch: out1[x] = B[x]^e1[x] (blockIdx.y = 0), out2[x] = B[x]^e2[x] (blockIdx.y = 1), both
 // left to right over the base's one 16-entry table.  The form for a batch that does not fill the chip: twice the
 // workgroups of one k_rt_dual_exp launch, each with the short chain of a single exponentiation.
@@ -510,6 +644,22 @@ extern "C" int modp_rt_launch_dual_exp(int lpl, const uint32_t* tab1, size_t tab
   if (count <= 0) return 0;
   RT_DISPATCH(lpl, k_rt_dual_exp, dim3(rt_grid(count)), dim3(64), 0, s, tab1, tab1_stride, tab2, tab2_stride, e1, e1_stride, e2,
               e2_stride, count, out, cs);
+  return (int)hipGetLastError();
+}
+
+extern "C" size_t modp_rt_comb_bytes(int lpl) { return (size_t)RT_COMB_ROWS * 16 * 4 * lpl * sizeof(uint32_t); }
+
+extern "C" int modp_rt_launch_comb_build(int lpl, const uint8_t* base_be, uint32_t* comb, const modp_rt_consts* cs, hipStream_t s) {
+  RT_DISPATCH(lpl, k_rt_comb_bases, dim3(1), dim3(64), 0, s, base_be, comb, cs);
+  RT_DISPATCH(lpl, k_rt_comb_rows, dim3(rt_grid(RT_COMB_ROWS)), dim3(64), 0, s, comb, cs);
+  return (int)hipGetLastError();
+}
+
+extern "C" int modp_rt_launch_comb_exp(int lpl, const uint32_t* comb, const uint32_t* tab2, size_t tab2_stride, const uint8_t* e1,
+                                       const uint8_t* e2, size_t e2_stride, int count, uint8_t* out, const modp_rt_consts* cs,
+                                       hipStream_t s) {
+  if (count <= 0) return 0;
+  RT_DISPATCH(lpl, k_rt_comb_exp, dim3(rt_grid(count)), dim3(64), 0, s, comb, tab2, tab2_stride, e1, e2, e2_stride, count, out, cs);
   return (int)hipGetLastError();
 }
 

@@ -321,8 +321,19 @@ struct mpvss_ctx {
   DevBuf rt_out_y, rt_buckets;   // the dealer's fourth result array; bucket scratch of k_rt_twin_exp (one chunk)
   std::vector<DevBuf*> rt_all() {
     return {&rt_consts, &rt_in[0], &rt_in[1], &rt_in[2], &rt_in[3], &rt_in[4], &rt_in[5], &rt_out[0], &rt_out[1], &rt_out[2],
-            &rt_tab1, &rt_tab2, &rt_tabg, &rt_cm, &rt_small[0], &rt_small[1], &rt_out_y, &rt_buckets};
+            &rt_tab1, &rt_tab2, &rt_tabg, &rt_cm, &rt_small[0], &rt_small[1], &rt_out_y, &rt_buckets,
+            &rt_comb[0].buf, &rt_comb[1].buf, &rt_comb[2].buf, &rt_comb[3].buf};
   }
+  // fixed-base combs of run-time groups (rt_comb_for, capi_modp_rt.inc), used under `mu`: keyed by the bytes (q, base) -- a handle
+  // is host-only, may serve several contexts, and the address of a destroyed one can come back; least recently used goes first
+  struct RtComb {
+    DevBuf buf;
+    std::vector<uint8_t> key;     // q | base, 512 bytes; empty: no table
+    unsigned long long used = 0;
+  };
+  static constexpr int RT_COMBS = 4;
+  RtComb rt_comb[RT_COMBS];
+  unsigned long long rt_comb_clock = 0, rt_comb_builds = 0, rt_comb_hits = 0, rt_comb_evictions = 0;
 };
 
 namespace {

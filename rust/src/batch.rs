@@ -170,11 +170,8 @@ pub fn distribute_secret(group: &HipModpGroup, secret: &BigInt, publickeys: &[Bi
     let g = be256(&group.subgroup_generator());
     let mut cm = vec![0u8; t * 256];
     let rc = match group.rt_handle() {
-        // a run-time group has no fixed-base comb: base 4 for every exponent through mpvss_modp_group_batch_exp
-        Some(h) => {
-            let gs: Vec<u8> = (0..t).flat_map(|_| g.clone()).collect();
-            unsafe { ffi::mpvss_modp_group_batch_exp(group.engine.raw(), h, ffi::MPVSS_HOST, gs.as_ptr(), coeffs.as_ptr(), t, cm.as_mut_ptr()) }
-        }
+        // a run-time group: one base for the whole call, over the comb of g = 4 when the context has or builds it
+        Some(h) => unsafe { ffi::mpvss_modp_group_batch_exp_fixed_base(group.engine.raw(), h, ffi::MPVSS_HOST, g.as_ptr(), coeffs.as_ptr(), t, cm.as_mut_ptr()) },
         None => unsafe { ffi::mpvss_modp_batch_exp_fixed_base(group.engine.raw(), ffi::MPVSS_HOST, g.as_ptr(), coeffs.as_ptr(), t, cm.as_mut_ptr()) },
     };
     group.engine.expect(rc, "distribute_secret: commitments");                         // C_j = g^a_j, :189-193

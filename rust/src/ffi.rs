@@ -257,6 +257,11 @@ unsafe extern "C" {
     pub fn mpvss_modp_group_batch_twin_exp(ctx: *mut mpvss_ctx, grp: *const mpvss_modp_group, space: c_int, bases: *const u8, e1: *const u8,
                                            e2: *const u8, n: usize, out1: *mut u8, out2: *mut u8) -> c_int;
     pub fn mpvss_modp_group_twin_min_shares(grp: *const mpvss_modp_group) -> c_int;
+    pub fn mpvss_modp_group_batch_exp_fixed_base(ctx: *mut mpvss_ctx, grp: *const mpvss_modp_group, space: c_int, base_host: *const u8,
+                                                 exps: *const u8, n: usize, out: *mut u8) -> c_int;
+    pub fn mpvss_modp_group_prepare(ctx: *mut mpvss_ctx, grp: *const mpvss_modp_group) -> c_int;
+    pub fn mpvss_modp_group_comb_min_shares(grp: *const mpvss_modp_group) -> c_int;
+    pub fn mpvss_modp_group_comb_stats(ctx: *mut mpvss_ctx, builds: *mut c_ulonglong, hits: *mut c_ulonglong, evictions: *mut c_ulonglong) -> c_int;
     pub fn mpvss_modp_group_distribute(ctx: *mut mpvss_ctx, grp: *const mpvss_modp_group, space: c_int, commitments: *const u8, t: usize,
                                        positions: *const i64, pubkeys: *const u8, p_values: *const u8, witnesses: *const u8, n: usize,
                                        x_out: *mut u8, y_out: *mut u8, a1_out: *mut u8, a2_out: *mut u8, digest32_out: *mut u8) -> c_int;

@@ -194,12 +194,13 @@ impl Group for HipModpGroup {
 
     /// modp.rs:176-178: G^k through the fixed-base comb
     fn generate_public_key(&self, private_key: &BigInt) -> BigInt {
-        if self.rt.is_some() {
-            return self.exp(&self.gen_main, private_key);
-        }
         let (g, e) = (be256(&self.gen_main), be256(private_key));
         let mut out = [0u8; 256];
-        let rc = unsafe { ffi::mpvss_modp_batch_exp_fixed_base(self.engine.raw(), ffi::MPVSS_HOST, g.as_ptr(), e.as_ptr(), 1, out.as_mut_ptr()) };
+        let rc = match self.rt_handle() {
+            // a run-time group: the comb of G = 2 when the context has it (mpvss_modp_group_prepare, or a large call before)
+            Some(h) => unsafe { ffi::mpvss_modp_group_batch_exp_fixed_base(self.engine.raw(), h, ffi::MPVSS_HOST, g.as_ptr(), e.as_ptr(), 1, out.as_mut_ptr()) },
+            None => unsafe { ffi::mpvss_modp_batch_exp_fixed_base(self.engine.raw(), ffi::MPVSS_HOST, g.as_ptr(), e.as_ptr(), 1, out.as_mut_ptr()) },
+        };
         self.engine.expect(rc, "HipModpGroup::generate_public_key");
         Self::from_be256(&out)
     }

@@ -22,8 +22,22 @@
               twin kernel beats the sets at every measured n above, and the gate is twin against PARENT's two batch_exp calls
               at n = 65536.  Then the deal leg runs under the default library.  All lines go to profiles/modp_rt_deal_rate.txt.
 
+  comb        (--comb, or --legs comb) the fixed-base power g^e of a run-time group, kernels alone (mpvss_last_kernel_ms), at
+              n = 1 .. 65536 for 1024 and 2048 bits.  --comb-parts parent: the launch a caller had before the comb -- a1_i = g^w_i
+              inside mpvss_modp_group_deal (t = 1), timer 1: the 16-entry table of g and the left-to-right kernel.  --comb-parts
+              comb: mpvss_modp_group_batch_exp_fixed_base under the tuning build of `make -C mpvss_rs_amd/csrc comb-ab`
+              (ab_libs/libmpvss_hip_comb.so: every call builds the comb of a base it has not cached) -- cold: a base the
+              context has not seen, build + comb launch (timers 2 + 1); warm: the same base again, the comb launch alone.
+  --comb --ab PARENT  the interleaved A/B behind rt_comb_min_shares (capi_modp_rt.inc) and the 3x kernel gate: each round runs
+              the parent part under PARENT's own bindings and library and the comb part under the tuning build, each in a fresh
+              process; the best of all rounds per (part, bits, n) makes the table.  The crossover per width is the smallest
+              measured n from which the cold call is no slower than the parent's launch at every measured n above (1 if that
+              holds everywhere); the gate is warm against parent at n = 65536.  Then group_deal / group_extract_shares at
+              (65536, 256) and group_verify_distribution at (4096, 64) run as whole calls under PARENT and under the default
+              library (no gate).  All lines go to profiles/modp_rt_comb_rate.txt.
+
 Host buffers in and out (the calls' own staging included), best of `--reps` after one warm-up call.  One JSON line per
-measurement.  Usage: python tools/modp_rt_rate.py [--quick] [--reps 3] [--legs rates,twin,deal] [--ab PARENT [--rounds 2]]"""
+measurement.  Usage: python tools/modp_rt_rate.py [--quick] [--reps 3] [--legs rates,twin,deal,comb,verify] [--comb] [--ab PARENT [--rounds 2]]"""
 import argparse
 import json
 import os
@@ -122,6 +136,54 @@ def deal_leg(eng, a, rng):
                               "rest_ms": round(s * 1e3 - host * 1e3 - kms, 1)}), flush=True)
 
 
+COMB_SIZES = [1, 16, 256, 1024, 4096, 16384, 65536]
+
+
+def comb_leg(eng, a, rng):
+    lib = os.path.basename(os.path.dirname(capi.LIB_PATH)) + "/" + os.path.basename(capi.LIB_PATH)
+    sizes = [1, 256, 4096] if a.quick else COMB_SIZES
+    fresh = 5                                     # bases 5, 6, ..: never a generator, a new one for every cold call
+    for bits in (1024, 2048):
+        grp = ModpGroup(H.rfc_prime(bits))
+        for n in sizes:
+            w = rand_bytes(random.Random(bits * 100003 + n), n, bits)
+            row = {"what": "comb", "lib": lib, "bits": bits, "n": n}
+            if "parent" in a.comb_parts:
+                y, pos, coeffs = rand_bytes(rng, n, bits - 1), list(range(1, n + 1)), rand_bytes(rng, 1, bits - 1)
+                ts = []
+                for _ in range(a.reps + 1):
+                    eng.group_deal(grp, coeffs, pos, y, w)
+                    ts.append(round(max(0.0, eng.kernel_ms(1)), 3))
+                row["parent_fixed_base_kernel_ms"] = min(ts[1:])
+            if "comb" in a.comb_parts:
+                if grp.comb_min_shares != 1:
+                    sys.exit("modp_rt_rate --comb: the comb part needs the tuning build (make -C mpvss_rs_amd/csrc comb-ab, "
+                             "MPVSS_HIP_LIB=ab_libs/libmpvss_hip_comb.so)")
+                cold, build, warm = [], [], []
+                for _ in range(a.reps + 1):
+                    base = fresh.to_bytes(256, "big")
+                    fresh += 1
+                    eng.group_batch_exp_fixed_base(grp, base, w)
+                    build.append(round(max(0.0, eng.kernel_ms(2)), 3))
+                    cold.append(round(build[-1] + max(0.0, eng.kernel_ms(1)), 3))
+                    eng.group_batch_exp_fixed_base(grp, base, w)
+                    warm.append(round(max(0.0, eng.kernel_ms(1)), 3))
+                row.update(comb_cold_kernel_ms=min(cold[1:]), comb_build_kernel_ms=min(build[1:]), comb_warm_kernel_ms=min(warm[1:]))
+            print(json.dumps(row), flush=True)
+
+
+def verify_leg(eng, a, rng):
+    for bits in (1024, 2048):
+        grp = ModpGroup(H.rfc_prime(bits))
+        nn, t = 4096, 64
+        cm, pos = rand_bytes(rng, t, bits), list(range(1, nn + 1))
+        y, Y, r = rand_bytes(rng, nn, bits), rand_bytes(rng, nn, bits), rand_bytes(rng, nn, bits)
+        c = rng.getrandbits(min(bits - 2, 256)).to_bytes(256, "big")
+        s = best(lambda: eng.group_verify_distribution(grp, cm, pos, y, Y, r, c), a.reps)
+        print(json.dumps({"what": "group_verify_distribution", "bits": bits, "n": nn, "t": t, "s": round(s, 4),
+                          "share_verifications_per_s": round(nn / s), "kernel_ms": kernel_ms(eng)}), flush=True)
+
+
 def child(args, lib, out, limit):
     """one fresh process of this tool (the GPU is opened there only); its JSON lines, also echoed.  A child that fails ends
     the whole run: nothing more is started on the GPU after it.  `limit`: seconds this leg may take."""
@@ -185,21 +247,77 @@ def ab(a):
             f.write(json.dumps(row) + "\n")
 
 
+def ab_comb(a):
+    lib = os.path.join(ROOT, "ab_libs", "libmpvss_hip_comb.so")
+    for f in (lib, os.path.join(a.ab, "mpvss_rs_amd", "libmpvss_hip.so")):
+        if not os.path.exists(f):
+            sys.exit(f"modp_rt_rate --comb --ab: {f} is missing (see the head of this file)")
+    common = ["--legs", "comb", "--reps", str(a.reps)] + (["--quick"] if a.quick else [])
+    lines, ms = [], {}
+    for rnd in range(a.rounds):
+        for part in ("parent", "comb"):
+            if part == "parent":
+                rows = child(common + ["--comb-parts", "parent", "--package-root", a.ab], None, [], a.twin_limit)
+            else:
+                rows = child(common + ["--comb-parts", "comb"], lib, [], a.twin_limit)
+            for row in rows:
+                row.update(part=part, round=rnd)
+                for k, v in row.items():
+                    if k.endswith("_kernel_ms"):
+                        key = (k, row["bits"], row["n"])
+                        ms[key] = min(ms.get(key, v), v)
+            lines += rows
+    for bits in sorted({k[1] for k in ms}):
+        sizes = sorted({k[2] for k in ms if k[1] == bits})
+        ok = []
+        for n in sizes:
+            pa, cold = ms["parent_fixed_base_kernel_ms", bits, n], ms["comb_cold_kernel_ms", bits, n]
+            warm, build = ms["comb_warm_kernel_ms", bits, n], ms["comb_build_kernel_ms", bits, n]
+            ok.append(cold <= pa)
+            lines.append({"what": "comb_ab", "bits": bits, "n": n, "parent_fixed_base_kernel_ms": pa, "comb_cold_kernel_ms": cold,
+                          "comb_build_kernel_ms": build, "comb_warm_kernel_ms": warm, "parent_over_cold": round(pa / cold, 3),
+                          "parent_over_warm": round(pa / warm, 3)})
+        first = next((n for i, n in enumerate(sizes) if all(ok[i:])), None)
+        lines.append({"what": "comb_crossover", "bits": bits, "min_shares": first, "measured_sizes": sizes})
+        top = sizes[-1]
+        ratio = ms["parent_fixed_base_kernel_ms", bits, top] / ms["comb_warm_kernel_ms", bits, top]
+        lines.append({"what": "comb_gate", "bits": bits, "n": top, "parent_over_warm": round(ratio, 3), "required": 3.0,
+                      "met": ratio >= 3.0})
+    for row in lines:
+        if row["what"].startswith("comb_"):
+            print(json.dumps(row), flush=True)
+    whole = ["--legs", "deal,verify", "--reps", str(a.reps)] + (["--quick"] if a.quick else [])
+    for side, extra in (("parent", ["--package-root", a.ab]), ("change", [])):
+        for row in child(whole + extra, None, [], a.deal_limit):
+            row["side"] = side
+            lines.append(row)
+    os.makedirs(os.path.join(ROOT, "profiles"), exist_ok=True)
+    with open(a.out, "w") as f:
+        for row in lines:
+            f.write(json.dumps(row) + "\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--quick", action="store_true", help="smaller shapes (a check of the tool, not a measurement)")
     ap.add_argument("--legs", default="rates", help="comma-separated: rates (batch_exp, verify), twin, deal")
     ap.add_argument("--twin-parts", default="call,baseline", help="of the twin leg: call (batch_twin_exp), baseline (two batch_exp)")
+    ap.add_argument("--comb", action="store_true", help="the fixed-base comb: alone, the comb leg; with --ab, its interleaved A/B")
+    ap.add_argument("--comb-parts", default="comb", help="of the comb leg: parent (g^w inside group_deal), comb (cold and warm)")
     ap.add_argument("--package-root", default=None, help="import mpvss_rs_amd (bindings and library) from this checkout")
     ap.add_argument("--ab", default=None, metavar="PARENT", help="the interleaved A/B against a built checkout of the parent commit")
     ap.add_argument("--rounds", type=int, default=2, help="of --ab: how often the three processes take turns")
     ap.add_argument("--twin-limit", type=int, default=300, help="of --ab: seconds one twin-leg process may take")
     ap.add_argument("--deal-limit", type=int, default=900, help="of --ab: seconds the deal-leg process may take (host threads at (65536, 256))")
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "modp_rt_deal_rate.txt"), help="of --ab: the file written")
+    ap.add_argument("--out", default=None, help="of --ab: the file written (profiles/modp_rt_deal_rate.txt, or _comb_rate.txt)")
     a = ap.parse_args()
+    if a.out is None:
+        a.out = os.path.join(ROOT, "profiles", "modp_rt_comb_rate.txt" if a.comb else "modp_rt_deal_rate.txt")
     if a.ab:
-        return ab(a)
+        return ab_comb(a) if a.comb else ab(a)
+    if a.comb:
+        a.legs = "comb"
     load_package(a.package_root)
     eng = Engine(0)
     rng = random.Random(1)
@@ -208,6 +326,10 @@ def main():
         twin_leg(eng, a, rng)
     if "deal" in legs:
         deal_leg(eng, a, rng)
+    if "comb" in legs:
+        comb_leg(eng, a, rng)
+    if "verify" in legs:
+        verify_leg(eng, a, rng)
     if "rates" not in legs:
         eng.close()
         return
