@@ -511,28 +511,37 @@ int mpvss_box_parse(const uint8_t* buf, size_t len, mpvss_box_view* view);
 int mpvss_box_verify_wire(mpvss_ctx* ctx, const uint8_t* buf, size_t len, int* verdict, uint8_t* digest32_out);
 
 /* ---- MODP groups of a run-time modulus (ModpGroup::init, src/groups/modp.rs:72-84) ---------------------------
- * A group handle holds an odd modulus q of at most 2048 bits -- ModpGroup::init(length).modulus() or any other -- and
+ * A group handle holds an odd modulus q of at most 3072 bits -- ModpGroup::init(length).modulus() or any other -- and
  * what the kernels need of it (Montgomery constants, the width: 5, 9 or 18 limbs of 29 bits per lane, the smallest with
- * bits(q) <= 29 * 4 * limbs - 2).  Creating it is host work only (no GPU, no context); it is immutable afterwards and may
- * be used from any number of contexts and threads at once.  Elements and scalars keep the 256-byte big-endian encoding
- * of MPVSS_MODP_BYTES; inputs need not be reduced (a value >= q gives what BigInt::modpow / (a * b) % q give, modp.rs:154-156
+ * bits(q) <= 29 * 4 * limbs - 2, or 27 for a wide handle).  Creating it is host work only (no GPU, no context); it is
+ * immutable afterwards and may be used from any number of contexts and threads at once.
+ * ELEMENT SIZE: every element, scalar and exponent that a mpvss_modp_group_* entry point reads or writes is a big-endian
+ * value of mpvss_modp_group_elem_bytes(handle) bytes, and arrays of them have that stride: 256 (MPVSS_MODP_BYTES) for a
+ * handle of mpvss_modp_group_create, 384 for a wide handle of mpvss_modp_group_create_wide (moduli of 2049 .. 3072 bits, RFC
+ * 3526 group 15 among them).  Parameter names and comments below that say 256 mean that size.  Inputs need not be reduced (a value >= q gives what BigInt::modpow / (a * b) % q give, modp.rs:154-156
  * validates nothing), outputs are canonical (< q).  The group's generators are those of ModpGroup: G = 2, g = G^2 = 4.
  * Protocol parity is specified for safe primes, which is what ModpGroup::init yields; for another odd q the calls return
  * without fault and are deterministic.
  * The entry points below mirror the group-14 ones with the handle added, lock the context like them and are safe for
  * concurrent callers on one context in the same sense.  The whole protocol is there: verification, the dealer (distribute,
  * the one-call deal), extract_secret_share and reconstruct, with the scalar ring Z/(q-1) on host threads.  Not offered for a
- * run-time group: the block / pipeline forms, verify_many, key sets and the wire format; moduli above 2048 bits (their
- * elements need more than 256 bytes) are refused with MPVSS_E_INVALID. */
+ * run-time group: the block / pipeline forms, verify_many, key sets and the wire format; moduli above 3072 bits are refused
+ * with MPVSS_E_INVALID (4096 bits would overflow the product's 64-bit column accumulators). */
 typedef struct mpvss_modp_group mpvss_modp_group;
 /* q_be: q_len big-endian bytes (leading zeros allowed).  MPVSS_E_INVALID for an even q, q < 5 or q >= 2^2048. */
 int mpvss_modp_group_create(const uint8_t* q_be, size_t q_len, mpvss_modp_group** out);
+/* The same with the element size chosen: elem_bytes 256 is mpvss_modp_group_create itself; 384 takes an odd q of 2049 .. 3072
+ * bits and gives a wide handle, which always runs at 27 limbs per lane (a narrower q with 384 is MPVSS_E_INVALID: the 256-byte
+ * handle serves it).  Any other elem_bytes is MPVSS_E_INVALID. */
+int mpvss_modp_group_create_wide(const uint8_t* q_be, size_t q_len, size_t elem_bytes, mpvss_modp_group** out);
 void mpvss_modp_group_destroy(mpvss_modp_group* grp);
-/* bit length of q, and the limbs per lane of the width the kernels run at (5, 9 or 18) */
+/* bit length of q, the limbs per lane of the width the kernels run at (5, 9, 18 or 27), and the element size (256 or 384) */
 int mpvss_modp_group_bits(const mpvss_modp_group* grp);
 int mpvss_modp_group_limbs_per_lane(const mpvss_modp_group* grp);
-/* Group::hash_to_scalar: int_BE(SHA256(data)) mod (q-1)/2 as 256-byte big-endian (src/groups/modp.rs:142-148); host only */
-int mpvss_modp_group_hash_to_scalar(const mpvss_modp_group* grp, const uint8_t* data, size_t len, uint8_t out256[256]);
+int mpvss_modp_group_elem_bytes(const mpvss_modp_group* grp);
+/* Group::hash_to_scalar: int_BE(SHA256(data)) mod (q-1)/2, big-endian, left-padded to the element size
+ * (src/groups/modp.rs:142-148); host only */
+int mpvss_modp_group_hash_to_scalar(const mpvss_modp_group* grp, const uint8_t* data, size_t len, uint8_t* out256);
 /* out[i] = bases[i]^exps[i] mod q                                    ModpGroup::exp (src/groups/modp.rs:122-128) */
 int mpvss_modp_group_batch_exp(mpvss_ctx* ctx, const mpvss_modp_group* grp, int space, const uint8_t* bases, const uint8_t* exps,
                                size_t n, uint8_t* out);
@@ -569,7 +578,7 @@ int mpvss_modp_group_twin_min_shares(const mpvss_modp_group* grp);
 /* out[i] = base^exps[i] mod q for ONE base in host memory (256 bytes, any value): the handle's counterpart of
  * mpvss_modp_batch_exp_fixed_base -- generate_public_key (base G = 2) and the commitments C_j = g^a_j (base g = 4).  exps and out
  * n x 256 bytes in `space`; exponents staged from the host are zeroed on the device before the call returns.
- * Fixed-base combs: a context keeps up to 4 tables base^(d 16^k), k < 512, d < 16, keyed by the bytes (q, base), least recently
+ * Fixed-base combs: a context keeps up to 4 tables base^(d 16^k), k < 2 x element size, d < 16, keyed by the bytes (q, base), least recently
  * used evicted, freed with the context.  Every power of a base shared by a whole call -- this entry point, X_i = g^P(i) and
  * a1_i = g^w_i of group_deal / group_distribute, a1_i = G^w_i of group_extract_shares, the g1^r leg of a1 in
  * group_dleq_commitments / group_verify_distribution / group_verify_shares -- runs over the comb without squarings when the

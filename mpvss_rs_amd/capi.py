@@ -53,7 +53,7 @@ EXPORTED_SYMBOLS = (
     "mpvss_modp_group_reconstruct", "mpvss_modp_group_scalar_mul", "mpvss_modp_group_scalar_sub", "mpvss_modp_group_dleq_responses",
     "mpvss_modp_group_poly_eval", "mpvss_modp_group_twin_min_shares",
     "mpvss_modp_group_batch_exp_fixed_base", "mpvss_modp_group_prepare", "mpvss_modp_group_comb_min_shares",
-    "mpvss_modp_group_comb_stats",
+    "mpvss_modp_group_comb_stats", "mpvss_modp_group_create_wide", "mpvss_modp_group_elem_bytes",
 )
 
 GROUP_SECP256K1 = 1
@@ -210,6 +210,8 @@ def load_library() -> C.CDLL:
     lib.mpvss_modp_extract_shares.argtypes = [vp, ci, u8p, u8p, u8p, u8p, sz, u8p, u8p]
     lib.mpvss_ec_extract_shares.argtypes = [vp, ci, ci, u8p, u8p, u8p, u8p, sz, u8p, u8p]
     lib.mpvss_modp_group_create.argtypes = [u8p, sz, C.POINTER(vp)]
+    lib.mpvss_modp_group_create_wide.argtypes = [u8p, sz, sz, C.POINTER(vp)]
+    lib.mpvss_modp_group_elem_bytes.argtypes = [vp]
     lib.mpvss_modp_group_destroy.argtypes = [vp]
     lib.mpvss_modp_group_destroy.restype = None
     lib.mpvss_modp_group_bits.argtypes = [vp]
@@ -253,21 +255,30 @@ def _out(nbytes: int):
 
 
 class ModpGroup:
-    """Handle of a run-time MODP group (mpvss_modp_group_create): any odd modulus q of at most 2048 bits, host only --
-    the counterpart of the reference's ModpGroup::init(length) (src/groups/modp.rs:72-84).  Usable with every Engine."""
+    """Handle of a run-time MODP group, host only -- the counterpart of the reference's ModpGroup::init(length)
+    (src/groups/modp.rs:72-84).  ModpGroup(q): any odd modulus q of at most 2048 bits, 256-byte elements and scalars
+    (mpvss_modp_group_create).  ModpGroup(q, elem_bytes=384): an odd q of 2049 .. 3072 bits (RFC 3526 group 15), 384-byte
+    elements and scalars (mpvss_modp_group_create_wide).  Every group_* call packs and unpacks at `elem_bytes`.  Usable with
+    every Engine."""
 
-    def __init__(self, q: int):
+    def __init__(self, q: int, elem_bytes: int = EB):
         self.lib = load_library()
         if q < 0:
             raise EngineError("modp group: negative modulus")
         qb = q.to_bytes(max(1, (q.bit_length() + 7) // 8), "big")
         kq, pq = _buf(qb)
         h = C.c_void_p()
-        rc = self.lib.mpvss_modp_group_create(pq, len(qb), C.byref(h))
+        if elem_bytes == EB:
+            rc = self.lib.mpvss_modp_group_create(pq, len(qb), C.byref(h))
+        else:
+            if elem_bytes < 0:
+                raise EngineError("modp group: negative element size")
+            rc = self.lib.mpvss_modp_group_create_wide(pq, len(qb), elem_bytes, C.byref(h))
         if rc != 0:
-            raise EngineError(f"mpvss_modp_group_create failed: rc={rc}")
+            raise EngineError(f"mpvss_modp_group_create{'' if elem_bytes == EB else '_wide'} failed: rc={rc}")
         self.handle = h
         self.q = q
+        self.elem_bytes = self.lib.mpvss_modp_group_elem_bytes(h)
 
     @property
     def bits(self) -> int:
@@ -288,6 +299,7 @@ class ModpGroup:
         return self.lib.mpvss_modp_group_comb_min_shares(self.handle)
 
     def hash_to_scalar(self, data: bytes) -> bytes:
+        EB = self.elem_bytes
         kd, pd = _buf(data if data else b"\0")
         ko, po = _out(EB)
         rc = self.lib.mpvss_modp_group_hash_to_scalar(self.handle, pd, len(data), po)
@@ -429,6 +441,7 @@ class Engine:
 
     # ---- run-time MODP groups (ModpGroup handles; include/mpvss_hip.h "MODP groups of a run-time modulus")
     def group_batch_exp(self, grp: "ModpGroup", bases: bytes, exps: bytes) -> bytes:
+        EB = grp.elem_bytes
         n = len(bases) // EB
         ka, pa = _buf(bases); kb, pb = _buf(exps); ko, po = _out(n * EB)
         self._check(self.lib.mpvss_modp_group_batch_exp(self.ctx, grp.handle, MPVSS_HOST, pa, pb, n, po), "group_batch_exp")
@@ -436,6 +449,7 @@ class Engine:
 
     def group_batch_exp_fixed_base(self, grp: "ModpGroup", base: bytes, exps: bytes) -> bytes:
         """base^exps[i] for one 256-byte base: over the base's comb when the context has or builds it"""
+        EB = grp.elem_bytes
         n = len(exps) // EB
         ka, pa = _buf(base); kb, pb = _buf(exps or None); ko, po = _out(n * EB)
         self._check(self.lib.mpvss_modp_group_batch_exp_fixed_base(self.ctx, grp.handle, MPVSS_HOST, pa, pb, n, po),
@@ -453,12 +467,14 @@ class Engine:
         return {"builds": int(b.value), "hits": int(h.value), "evictions": int(e.value)}
 
     def group_batch_mul(self, grp: "ModpGroup", a: bytes, b: bytes) -> bytes:
+        EB = grp.elem_bytes
         n = len(a) // EB
         ka, pa = _buf(a); kb, pb = _buf(b); ko, po = _out(n * EB)
         self._check(self.lib.mpvss_modp_group_batch_mul(self.ctx, grp.handle, MPVSS_HOST, pa, pb, n, po), "group_batch_mul")
         return bytes(ko)[: n * EB]
 
     def group_commit_eval(self, grp: "ModpGroup", commitments: bytes, positions: Sequence[int]) -> bytes:
+        EB = grp.elem_bytes
         t = len(commitments) // EB
         n = len(positions)
         kc, pc = _buf(commitments)
@@ -470,6 +486,7 @@ class Engine:
 
     def group_dleq_commitments(self, grp: "ModpGroup", g1: bytes, h1: bytes, g2: bytes, h2: bytes, r: bytes, c: bytes,
                                c_per_share: bool) -> Tuple[bytes, bytes]:
+        EB = grp.elem_bytes
         n = len(h1) // EB
         k = [_buf(x) for x in (g1, h1, g2, h2, r, c)]
         k1, p1 = _out(n * EB); k2, p2 = _out(n * EB)
@@ -480,6 +497,7 @@ class Engine:
 
     def group_verify_distribution(self, grp: "ModpGroup", commitments: bytes, positions: Sequence[int], pubkeys: bytes,
                                   shares: bytes, responses: bytes, challenge: bytes, dump: bool = False):
+        EB = grp.elem_bytes
         t = len(commitments) // EB
         n = len(positions)
         kc, pc = _buf(commitments or None); ky, py = _buf(pubkeys or None); kY, pY = _buf(shares or None)
@@ -500,6 +518,7 @@ class Engine:
         return out
 
     def group_verify_shares(self, grp: "ModpGroup", pk: bytes, s: bytes, y: bytes, c: bytes, r: bytes) -> bytes:
+        EB = grp.elem_bytes
         n = len(pk) // EB
         k = [_buf(x) for x in (pk, s, y, c, r)]
         ko, po = _out(n)
@@ -509,6 +528,7 @@ class Engine:
 
     def group_batch_twin_exp(self, grp: "ModpGroup", bases: bytes, e1: bytes, e2: bytes) -> Tuple[bytes, bytes]:
         """(bases^e1, bases^e2): two powers of one base per share"""
+        EB = grp.elem_bytes
         n = len(bases) // EB
         k = [_buf(x) for x in (bases, e1, e2)]
         k1, p1 = _out(n * EB); k2, p2 = _out(n * EB)
@@ -518,6 +538,7 @@ class Engine:
 
     def group_distribute(self, grp: "ModpGroup", commitments: bytes, positions: Sequence[int], pubkeys: bytes, p_values: bytes,
                          witnesses: bytes):
+        EB = grp.elem_bytes
         t = len(commitments) // EB
         n = len(positions)
         kc, pc = _buf(commitments or None); ky, py = _buf(pubkeys or None); kp, pp = _buf(p_values or None)
@@ -533,6 +554,7 @@ class Engine:
 
     def group_deal(self, grp: "ModpGroup", coeffs: bytes, positions: Sequence[int], pubkeys: bytes, witnesses: bytes) -> dict:
         """the dealer's whole box from host buffers in one call: X, Y, a1, a2, digest, challenge, responses"""
+        EB = grp.elem_bytes
         n = len(positions)
         pos = (C.c_int64 * max(n, 1))(*positions)
         k = [_buf(b or None) for b in (coeffs, pubkeys, witnesses)]
@@ -546,6 +568,7 @@ class Engine:
         return {"X": X, "Y": Y, "a1": a1, "a2": a2, "digest": bytes(kd)[:32], "challenge": bytes(kc)[:EB], "responses": r}
 
     def group_extract_shares(self, grp: "ModpGroup", pk: bytes, y: bytes, xinv: bytes, w: bytes) -> Tuple[bytes, bytes]:
+        EB = grp.elem_bytes
         n = len(pk) // EB
         k = [_buf(x) for x in (pk, y, xinv, w)]
         ks, ps = _out(n * EB); kc, pc = _out(n * EB)
@@ -555,6 +578,7 @@ class Engine:
 
     def group_reconstruct(self, grp: "ModpGroup", positions: Sequence[int], shares: bytes):
         """(G^s, mask) from m decrypted shares: secret = int(mask) ^ U"""
+        EB = grp.elem_bytes
         m = len(positions)
         pos = (C.c_int64 * max(m, 1))(*positions)
         ks, ps = _buf(shares or None); kg, pg = _out(EB); km, pm = _out(32)
@@ -1149,8 +1173,9 @@ def poly_eval(group: int, coeffs: bytes, positions: Sequence[int], threads: int 
     return bytes(ko)[: n * sw]
 
 
-# ---- scalar ring of a run-time MODP group (host only): Z/(q-1) of the handle, 256-byte big-endian scalars
+# ---- scalar ring of a run-time MODP group (host only): Z/(q-1) of the handle, big-endian scalars of grp.elem_bytes bytes
 def group_scalar_mul(grp: "ModpGroup", a: bytes, b: bytes) -> bytes:
+    EB = grp.elem_bytes
     ka, pa = _buf(a); kb, pb = _buf(b); ko, po = _out(EB)
     rc = grp.lib.mpvss_modp_group_scalar_mul(grp.handle, pa, pb, po)
     if rc != 0:
@@ -1159,6 +1184,7 @@ def group_scalar_mul(grp: "ModpGroup", a: bytes, b: bytes) -> bytes:
 
 
 def group_scalar_sub(grp: "ModpGroup", a: bytes, b: bytes) -> bytes:
+    EB = grp.elem_bytes
     ka, pa = _buf(a); kb, pb = _buf(b); ko, po = _out(EB)
     rc = grp.lib.mpvss_modp_group_scalar_sub(grp.handle, pa, pb, po)
     if rc != 0:
@@ -1168,6 +1194,7 @@ def group_scalar_sub(grp: "ModpGroup", a: bytes, b: bytes) -> bytes:
 
 def group_dleq_responses(grp: "ModpGroup", w: bytes, alpha: bytes, c: bytes, threads: int = 0) -> bytes:
     """r_i = w_i - alpha_i * c_i mod (q-1); c is one scalar or one per proof"""
+    EB = grp.elem_bytes
     n = len(w) // EB
     kw, pw = _buf(w or None); ka, pa = _buf(alpha or None); kc, pc = _buf(c); ko, po = _out(n * EB)
     rc = grp.lib.mpvss_modp_group_dleq_responses(grp.handle, pw, pa, pc, int(len(c) != EB), n, po, threads)
@@ -1178,6 +1205,7 @@ def group_dleq_responses(grp: "ModpGroup", w: bytes, alpha: bytes, c: bytes, thr
 
 def group_poly_eval(grp: "ModpGroup", coeffs: bytes, positions: Sequence[int], threads: int = 0) -> bytes:
     """P(i) mod (q-1) for every position"""
+    EB = grp.elem_bytes
     t, n = len(coeffs) // EB, len(positions)
     kc, pc = _buf(coeffs or None); ko, po = _out(n * EB)
     pos = (C.c_int64 * max(n, 1))(*positions)

@@ -2,21 +2,39 @@
 // host-side constants and hash_to_scalar, and the batched entry points over modp_rt_kernels.hip.  Included at the end
 // of mpvss_capi.cpp (it uses the context, staging and transcript helpers defined there).
 
+constexpr size_t RT_EB_MAX = 384;     // the widest element / scalar of a handle (mpvss_modp_group_create_wide)
+
+// q, q - 1 and (q-1)/2 for the host-side scalar ring (host_scalar.h) at NW 64-bit words
+template <int NW_>
+struct RtRings {
+  static constexpr int NW = NW_;
+  hsc::ModulusRtN<NW_> mod, ord, sub;
+};
+
 struct mpvss_modp_group {
   modp_rt_consts c;          // device image of the constants (copied to the device by every call)
   int bits = 0;
   int lpl = 0;
-  uint8_t sub_be[256];       // (q-1)/2 big-endian: hash_to_scalar's modulus (modp.rs:142-148)
-  uint8_t g_be[256];         // subgroup generator 4 (modp.rs:65-66 for any q >= 5)
-  uint8_t G_be[256];         // main generator 2
-  uint8_t q_be[256];
-  hsc::ModulusRt mod, ord, sub;   // q, q - 1 and (q-1)/2 for the host-side scalar ring (host_scalar.h)
+  size_t eb = 0;             // bytes of every element, scalar and exponent of this handle on the ABI: 256, or 384 (wide)
+  uint8_t sub_be[RT_EB_MAX]; // (q-1)/2 big-endian, eb bytes: hash_to_scalar's modulus (modp.rs:142-148)
+  uint8_t g_be[RT_EB_MAX];   // subgroup generator 4 (modp.rs:65-66 for any q >= 5)
+  uint8_t G_be[RT_EB_MAX];   // main generator 2
+  uint8_t q_be[RT_EB_MAX];
+  RtRings<32> r32;           // the rings of a 256-byte handle ...
+  RtRings<48> r48;           // ... and of a 384-byte one (the other stays unset)
 };
 
 namespace {
 
-// ---- host big integers: little-endian 32-bit words, fixed capacity (2 q < 2^2050) ------------------------------
-constexpr int RTW = 66;
+// fn(rings) with the handle's own rings: RT_NW(rings), 32 or 48 words, is a compile-time constant inside fn
+#define RT_NW(R) std::decay_t<decltype(R)>::NW
+template <class Fn>
+auto rt_rings(const mpvss_modp_group* grp, Fn fn) {
+  return grp->eb == RT_EB_MAX ? fn(grp->r48) : fn(grp->r32);
+}
+
+// ---- host big integers: little-endian 32-bit words, fixed capacity (2 q < 2^3074) ------------------------------
+constexpr int RTW = 98;
 typedef uint32_t RtNum[RTW];
 
 void rt_from_be(RtNum x, const uint8_t* be, size_t len) {
@@ -26,31 +44,33 @@ void rt_from_be(RtNum x, const uint8_t* be, size_t len) {
     x[bitpos / 32] |= (uint32_t)be[i] << (bitpos % 32);
   }
 }
-void rt_to_be256(const RtNum x, uint8_t* be) {
-  for (int i = 0; i < 256; ++i) be[255 - i] = (uint8_t)(x[i / 4] >> (8 * (i % 4)));
+void rt_to_be(const RtNum x, uint8_t* be, size_t eb) {
+  for (size_t i = 0; i < eb; ++i) be[eb - 1 - i] = (uint8_t)(x[i / 4] >> (8 * (i % 4)));
 }
 int rt_bits(const RtNum a) {
   for (int i = RTW - 1; i >= 0; --i)
     if (a[i]) return 32 * i + 32 - __builtin_clz(a[i]);
   return 0;
 }
+template <int NW>
 void rt_to_limbs64(const RtNum x, uint64_t* v) {
-  for (int i = 0; i < 32; ++i) v[i] = (uint64_t)x[2 * i] | ((uint64_t)x[2 * i + 1] << 32);
+  for (int i = 0; i < NW; ++i) v[i] = (uint64_t)x[2 * i] | ((uint64_t)x[2 * i + 1] << 32);
 }
-// 2^e mod M: products of powers of two below 2^2048
-void rt_pow2_mod(RtNum out, int e, const hsc::ModulusRt& M) {
-  uint64_t r[32], t[32];
+// 2^e mod M: products of powers of two below 2^(64 NW)
+template <int NW>
+void rt_pow2_mod(RtNum out, int e, const hsc::ModulusRtN<NW>& M) {
+  uint64_t r[NW], t[NW];
   memset(r, 0, sizeof(r));
   r[0] = 1;
   while (e > 0) {
-    const int c = e < 2047 ? e : 2047;
+    const int c = e < 64 * NW - 1 ? e : 64 * NW - 1;
     memset(t, 0, sizeof(t));
     t[c / 64] = (uint64_t)1 << (c % 64);
     M.mulmod(r, r, t);
     e -= c;
   }
   memset(out, 0, sizeof(RtNum));
-  for (int i = 0; i < 32; ++i) { out[2 * i] = (uint32_t)r[i]; out[2 * i + 1] = (uint32_t)(r[i] >> 32); }
+  for (int i = 0; i < NW; ++i) { out[2 * i] = (uint32_t)r[i]; out[2 * i + 1] = (uint32_t)(r[i] >> 32); }
 }
 // 29-bit limbs (zero above L)
 void rt_limbs(const RtNum x, uint32_t* limbs, int L) {
@@ -64,7 +84,8 @@ void rt_limbs(const RtNum x, uint32_t* limbs, int L) {
   }
 }
 
-// width of a modulus: the smallest of 5, 9, 18 limbs per lane with bits <= 29 L - 2 (R > 4 N)
+// width of a modulus of a 256-byte handle: the smallest of 5, 9, 18 limbs per lane with bits <= 29 L - 2 (R > 4 N).  A
+// 384-byte handle always runs at 27.
 int rt_lpl_for_bits(int bits) {
   for (int lpl : {5, 9, 18})
     if (bits <= 29 * 4 * lpl - 2) return lpl;
@@ -90,23 +111,23 @@ int rt_tables(mpvss_ctx* ctx, const mpvss_modp_group* grp, const modp_rt_consts*
   return 0;
 }
 
-// a host 256-byte value on the device (small staging buffer of the context)
-int rt_stage_small(mpvss_ctx* ctx, const uint8_t* host256, DevBuf& buf, const uint8_t** dev) {
-  RET_IF(ensure(ctx, buf, EB));
-  HIPCHK(ctx, hipMemcpyAsync(buf.p, host256, EB, hipMemcpyHostToDevice, ctx->stream));
+// a host value of the handle's element size on the device (small staging buffer of the context)
+int rt_stage_small(mpvss_ctx* ctx, const mpvss_modp_group* grp, const uint8_t* host, DevBuf& buf, const uint8_t** dev) {
+  RET_IF(ensure(ctx, buf, grp->eb));
+  HIPCHK(ctx, hipMemcpyAsync(buf.p, host, grp->eb, hipMemcpyHostToDevice, ctx->stream));
   *dev = (const uint8_t*)buf.p;
   return 0;
 }
 
 // The batch size (shares of one call, or of one chunk) from which a call builds the fixed-base comb of a base it does not find
-// in the context's cache: the build is one sequential chain of 2 044 squarings, and the smallest n from which build + comb
+// in the context's cache: the build is one sequential chain of 2 044 squarings (3 068 at the wide width), and the smallest n from which build + comb
 // launch is no slower than the 16-entry table + left-to-right launch it replaces is what `tools/modp_rt_rate.py --comb --ab`
 // measures (profiles/modp_rt_comb_rate.txt, DESIGN section 13).  A cached comb is used at every size.  The tuning build of
 // `make comb-ab` pins it with -DMPVSS_RT_COMB_MIN_SHARES=n.
 #ifdef MPVSS_RT_COMB_MIN_SHARES
 size_t rt_comb_min_shares(int) { return (size_t)(MPVSS_RT_COMB_MIN_SHARES); }
 #else
-size_t rt_comb_min_shares(int) { return 16384; }   // UNMEASURED placeholder (the twin crossover's figure)
+size_t rt_comb_min_shares(int) { return 16384; }   // UNMEASURED placeholder at every width, 27 included (the twin crossover's figure)
 #endif
 
 // The one launch decision for a power of a base shared by the whole call (context lock held): the comb of (q, base) when the
@@ -117,12 +138,13 @@ size_t rt_comb_min_shares(int) { return 16384; }   // UNMEASURED placeholder (th
 int rt_comb_for(mpvss_ctx* ctx, const mpvss_modp_group* grp, const modp_rt_consts* dc, const uint8_t* base_host, size_t cnt, bool build,
                 const uint32_t** comb) {
   *comb = nullptr;
-  uint8_t key[2 * EB];
+  const size_t EB = grp->eb, klen = 2 * EB;               // the key is as long as the handle's (q, base): sizes never mix
+  uint8_t key[2 * RT_EB_MAX];
   memcpy(key, grp->q_be, EB);
   memcpy(key + EB, base_host, EB);
   mpvss_ctx::RtComb* victim = &ctx->rt_comb[0];
   for (auto& e : ctx->rt_comb) {
-    if (e.key.size() == sizeof(key) && memcmp(e.key.data(), key, sizeof(key)) == 0) {
+    if (e.key.size() == klen && memcmp(e.key.data(), key, klen) == 0) {
       e.used = ++ctx->rt_comb_clock;
       ++ctx->rt_comb_hits;
       *comb = (const uint32_t*)e.buf.p;
@@ -135,9 +157,9 @@ int rt_comb_for(mpvss_ctx* ctx, const mpvss_modp_group* grp, const modp_rt_const
   victim->key.clear();                                   // no table while the build can still fail
   RET_IF(ensure(ctx, victim->buf, modp_rt_comb_bytes(grp->lpl)));
   const uint8_t* db;
-  RET_IF(rt_stage_small(ctx, base_host, ctx->rt_small[0], &db));
+  RET_IF(rt_stage_small(ctx, grp, base_host, ctx->rt_small[0], &db));
   TIMED_LAUNCH(ctx, 2, modp_rt_launch_comb_build(grp->lpl, db, (uint32_t*)victim->buf.p, dc, ctx->stream));
-  victim->key.assign(key, key + sizeof(key));
+  victim->key.assign(key, key + klen);
   victim->used = ++ctx->rt_comb_clock;
   ++ctx->rt_comb_builds;
   if (evicts) ++ctx->rt_comb_evictions;
@@ -149,7 +171,7 @@ int rt_comb_for(mpvss_ctx* ctx, const mpvss_modp_group* grp, const modp_rt_const
 int rt_dleq_dev(mpvss_ctx* ctx, const mpvss_modp_group* grp, const modp_rt_consts* dc, const uint8_t* g1_host, const uint8_t* h1,
                 const uint8_t* g2, const uint8_t* h2, const uint8_t* r, const uint8_t* c, size_t c_stride, size_t cnt, uint8_t* a1,
                 uint8_t* a2) {
-  const size_t TW = 16 * rt_L(grp);
+  const size_t TW = 16 * rt_L(grp), EB = grp->eb;
   const uint32_t *tg, *t1, *t2;
   if (a1) {
     RET_IF(rt_comb_for(ctx, grp, dc, g1_host, cnt, false, &tg));
@@ -158,7 +180,7 @@ int rt_dleq_dev(mpvss_ctx* ctx, const mpvss_modp_group* grp, const modp_rt_const
       TIMED_LAUNCH(ctx, 1, modp_rt_launch_comb_exp(grp->lpl, tg, t1, TW, r, c, c_stride, (int)cnt, a1, dc, ctx->stream));
     } else {
       const uint8_t* dg1;
-      RET_IF(rt_stage_small(ctx, g1_host, ctx->rt_small[0], &dg1));
+      RET_IF(rt_stage_small(ctx, grp, g1_host, ctx->rt_small[0], &dg1));
       RET_IF(rt_tables(ctx, grp, dc, dg1, 0, 1, ctx->rt_tabg, &tg));
       TIMED_LAUNCH(ctx, 1, modp_rt_launch_dual_exp(grp->lpl, tg, 0, t1, TW, r, EB, c, c_stride, (int)cnt, a1, dc, ctx->stream));
     }
@@ -181,6 +203,7 @@ int rt_commit_eval_dev(mpvss_ctx* ctx, const mpvss_modp_group* grp, const modp_r
 
 int rt_stage_commitments(mpvss_ctx* ctx, const mpvss_modp_group* grp, const modp_rt_consts* dc, int space, const uint8_t* commitments,
                          size_t t) {
+  const size_t EB = grp->eb;
   const void* dcm;
   RET_IF(stage_in(ctx, space, commitments, t * EB, ctx->rt_in[4], &dcm));
   RET_IF(ensure(ctx, ctx->rt_cm, t * rt_L(grp) * 4));
@@ -188,52 +211,69 @@ int rt_stage_commitments(mpvss_ctx* ctx, const mpvss_modp_group* grp, const modp
   return 0;
 }
 
-// hash_to_scalar of the group: int(SHA-256(data)) mod (q-1)/2, 256 bytes big-endian
-void rt_hash_to_scalar(const mpvss_modp_group* grp, const uint8_t* data, size_t len, uint8_t out256[256]) {
-  uint8_t h[EB];
+// hash_to_scalar of the group: int(SHA-256(data)) mod (q-1)/2, big-endian at the handle's element size
+void rt_hash_to_scalar(const mpvss_modp_group* grp, const uint8_t* data, size_t len, uint8_t* out) {
+  const size_t EB = grp->eb;
+  uint8_t h[RT_EB_MAX];
   memset(h, 0, EB - 32);
   mpvss::sha256(data, len, h + EB - 32);
-  uint64_t x[32];
-  hsc::from_bytes<32>(x, h, true);
-  grp->sub.reduce1(x);
-  hsc::to_bytes<32>(out256, x, true);
+  rt_rings(grp, [&](const auto& R) {
+    constexpr int NW = RT_NW(R);
+    uint64_t x[NW];
+    hsc::from_bytes<NW>(x, h, true);
+    R.sub.reduce1(x);
+    hsc::to_bytes<NW>(out, x, true);
+  });
+}
+
+// the transcript framing of mpvss_capi.cpp (frame_update, frame_shares, frame_min_bytes_update) at the handle's element size:
+// minimal-length big-endian magnitude, zero -> one 0x00 byte (modp.rs:150-152), behind its 8-byte length (dleq.rs:58-61)
+void rt_frame_min_bytes_update(mpvss::Sha256& h, const uint8_t* e, size_t eb) {
+  size_t skip = 0;
+  while (skip < eb - 1 && e[skip] == 0) ++skip;
+  h.update(e + skip, eb - skip);
+}
+void rt_frame_update(mpvss::Sha256& h, const uint8_t* e, size_t eb) {
+  size_t skip = 0;
+  while (skip < eb - 1 && e[skip] == 0) ++skip;
+  const uint64_t len = eb - skip;
+  uint8_t pre[8];
+  for (int i = 0; i < 8; ++i) pre[i] = (uint8_t)(len >> (56 - 8 * i));
+  h.update(pre, 8);
+  h.update(e + skip, (size_t)len);
 }
 
 bool rt_bad_group(const mpvss_modp_group* grp) { return grp == nullptr || grp->lpl == 0; }
 
 }  // namespace
 
-extern "C" int mpvss_modp_group_create(const uint8_t* q_be, size_t q_len, mpvss_modp_group** out) {
-  if (!out) return MPVSS_E_INVALID;
-  *out = nullptr;
-  if (!q_be) return MPVSS_E_INVALID;
-  size_t skip = 0;
-  while (skip < q_len && q_be[skip] == 0) ++skip;          // leading zero bytes are allowed
-  if (q_len - skip > EB) return MPVSS_E_INVALID;           // more than 2048 bits
-  RtNum q;
-  rt_from_be(q, q_be + skip, q_len - skip);
-  const int bits = rt_bits(q);
-  if (bits == 0 || (q[0] & 1) == 0 || (bits <= 3 && q[0] < 5)) return MPVSS_E_INVALID;   // even, or below 5
+namespace {
+
+// the handle of an odd q >= 5 of `bits` bits at element size eb and lpl limbs per lane
+template <int NW>
+int rt_group_build(const RtNum q, int bits, size_t eb, int lpl, RtRings<NW> mpvss_modp_group::*rings, mpvss_modp_group** out) {
   mpvss_modp_group* g = new (std::nothrow) mpvss_modp_group();
   if (!g) return MPVSS_E_NOMEM;
   memset(&g->c, 0, sizeof(g->c));
   g->bits = bits;
-  g->lpl = rt_lpl_for_bits(bits);
+  g->lpl = lpl;
+  g->eb = eb;
+  RtRings<NW>& R = g->*rings;
   const int L = 4 * g->lpl;
   const int in_rows = modp_rt_in_rows(g->lpl);
   rt_limbs(q, g->c.n, L);
-  uint64_t q64[32];
-  rt_to_limbs64(q, q64);
-  g->mod.set(q64);
+  uint64_t q64[NW];
+  rt_to_limbs64<NW>(q, q64);
+  R.mod.set(q64);
   q64[0] -= 1;                                   // q is odd
-  g->ord.set(q64);
-  for (int i = 0; i < 32; ++i) q64[i] = (q64[i] >> 1) | (i + 1 < 32 ? q64[i + 1] << 63 : 0);
-  g->sub.set(q64);
-  rt_to_be256(q, g->q_be);
+  R.ord.set(q64);
+  for (int i = 0; i < NW; ++i) q64[i] = (q64[i] >> 1) | (i + 1 < NW ? q64[i + 1] << 63 : 0);
+  R.sub.set(q64);
+  rt_to_be(q, g->q_be, eb);
   RtNum k;
-  rt_pow2_mod(k, 29 * (in_rows + L), g->mod);
+  rt_pow2_mod<NW>(k, 29 * (in_rows + L), R.mod);
   rt_limbs(k, g->c.kin, L);
-  rt_pow2_mod(k, 29 * L, g->mod);
+  rt_pow2_mod<NW>(k, 29 * L, R.mod);
   rt_limbs(k, g->c.one_m, L);
   g->c.one[0] = 1;
   // n0inv = -q^-1 mod 2^29 (Newton: every step doubles the correct low bits)
@@ -249,13 +289,47 @@ extern "C" int mpvss_modp_group_create(const uint8_t* q_be, size_t q_len, mpvss_
   RtNum sub;
   memcpy(sub, q, sizeof(RtNum));
   for (int i = 0; i < RTW; ++i) sub[i] = (q[i] >> 1) | (i + 1 < RTW ? q[i + 1] << 31 : 0);   // (q-1)/2 = q >> 1 (q odd)
-  rt_to_be256(sub, g->sub_be);
-  memset(g->g_be, 0, EB);
-  g->g_be[EB - 1] = 4;
-  memset(g->G_be, 0, EB);
-  g->G_be[EB - 1] = 2;
+  rt_to_be(sub, g->sub_be, eb);
+  memset(g->g_be, 0, sizeof(g->g_be));
+  g->g_be[eb - 1] = 4;
+  memset(g->G_be, 0, sizeof(g->G_be));
+  g->G_be[eb - 1] = 2;
   *out = g;
   return MPVSS_OK;
+}
+
+// q of at most max_bytes significant bytes, odd and >= 5; its bit length, or 0
+int rt_parse_modulus(const uint8_t* q_be, size_t q_len, size_t max_bytes, RtNum q) {
+  if (!q_be) return 0;
+  size_t skip = 0;
+  while (skip < q_len && q_be[skip] == 0) ++skip;          // leading zero bytes are allowed
+  if (q_len - skip > max_bytes) return 0;
+  rt_from_be(q, q_be + skip, q_len - skip);
+  const int bits = rt_bits(q);
+  if (bits == 0 || (q[0] & 1) == 0 || (bits <= 3 && q[0] < 5)) return 0;   // even, or below 5
+  return bits;
+}
+
+}  // namespace
+
+extern "C" int mpvss_modp_group_create(const uint8_t* q_be, size_t q_len, mpvss_modp_group** out) {
+  if (!out) return MPVSS_E_INVALID;
+  *out = nullptr;
+  RtNum q;
+  const int bits = rt_parse_modulus(q_be, q_len, MPVSS_MODP_BYTES, q);     // more than 2048 bits: mpvss_modp_group_create_wide
+  if (bits == 0) return MPVSS_E_INVALID;
+  return rt_group_build<32>(q, bits, MPVSS_MODP_BYTES, rt_lpl_for_bits(bits), &mpvss_modp_group::r32, out);
+}
+
+extern "C" int mpvss_modp_group_create_wide(const uint8_t* q_be, size_t q_len, size_t elem_bytes, mpvss_modp_group** out) {
+  if (!out) return MPVSS_E_INVALID;
+  *out = nullptr;
+  if (elem_bytes == MPVSS_MODP_BYTES) return mpvss_modp_group_create(q_be, q_len, out);
+  if (elem_bytes != RT_EB_MAX) return MPVSS_E_INVALID;
+  RtNum q;
+  const int bits = rt_parse_modulus(q_be, q_len, RT_EB_MAX, q);
+  if (bits <= 8 * MPVSS_MODP_BYTES) return MPVSS_E_INVALID;                // a 256-byte handle serves it (or q is no modulus)
+  return rt_group_build<48>(q, bits, RT_EB_MAX, 27, &mpvss_modp_group::r48, out);
 }
 
 extern "C" void mpvss_modp_group_destroy(mpvss_modp_group* grp) { delete grp; }
@@ -264,7 +338,9 @@ extern "C" int mpvss_modp_group_bits(const mpvss_modp_group* grp) { return grp ?
 
 extern "C" int mpvss_modp_group_limbs_per_lane(const mpvss_modp_group* grp) { return grp ? grp->lpl : MPVSS_E_INVALID; }
 
-extern "C" int mpvss_modp_group_hash_to_scalar(const mpvss_modp_group* grp, const uint8_t* data, size_t len, uint8_t out256[256]) {
+extern "C" int mpvss_modp_group_elem_bytes(const mpvss_modp_group* grp) { return grp ? (int)grp->eb : MPVSS_E_INVALID; }
+
+extern "C" int mpvss_modp_group_hash_to_scalar(const mpvss_modp_group* grp, const uint8_t* data, size_t len, uint8_t* out256) {
   if (!grp || !out256 || (!data && len)) return MPVSS_E_INVALID;
   rt_hash_to_scalar(grp, data, len, out256);
   return MPVSS_OK;
@@ -275,6 +351,7 @@ extern "C" int mpvss_modp_group_batch_exp(mpvss_ctx* ctx, const mpvss_modp_group
   if (!ctx) return MPVSS_E_INVALID;
   std::lock_guard<std::mutex> lk(ctx->mu);
   if (rt_bad_group(grp)) return fail(ctx, MPVSS_E_INVALID, "group_batch_exp: no group");
+  const size_t EB = grp->eb;
   if (n == 0) return MPVSS_OK;
   if (!bases || !exps || !out) return fail(ctx, MPVSS_E_INVALID, "group_batch_exp: bad argument");
   HIPCHK(ctx, hipSetDevice(ctx->device));
@@ -307,6 +384,7 @@ extern "C" int mpvss_modp_group_batch_mul(mpvss_ctx* ctx, const mpvss_modp_group
   if (!ctx) return MPVSS_E_INVALID;
   std::lock_guard<std::mutex> lk(ctx->mu);
   if (rt_bad_group(grp)) return fail(ctx, MPVSS_E_INVALID, "group_batch_mul: no group");
+  const size_t EB = grp->eb;
   if (n == 0) return MPVSS_OK;
   if (!a || !b || !out || n > 0x7fffffff) return fail(ctx, MPVSS_E_INVALID, "group_batch_mul: bad argument");
   HIPCHK(ctx, hipSetDevice(ctx->device));
@@ -338,6 +416,7 @@ extern "C" int mpvss_modp_group_commit_eval(mpvss_ctx* ctx, const mpvss_modp_gro
   if (!ctx) return MPVSS_E_INVALID;
   std::lock_guard<std::mutex> lk(ctx->mu);
   if (rt_bad_group(grp)) return fail(ctx, MPVSS_E_INVALID, "group_commit_eval: no group");
+  const size_t EB = grp->eb;
   if (n == 0) return MPVSS_OK;
   if (!commitments || !positions || !x_out || t == 0 || t > 0x7fffffff || n > 0x7fffffff)
     return fail(ctx, MPVSS_E_INVALID, "group_commit_eval: bad argument (t must be >= 1)");
@@ -365,6 +444,7 @@ extern "C" int mpvss_modp_group_dleq_commitments(mpvss_ctx* ctx, const mpvss_mod
   if (!ctx) return MPVSS_E_INVALID;
   std::lock_guard<std::mutex> lk(ctx->mu);
   if (rt_bad_group(grp)) return fail(ctx, MPVSS_E_INVALID, "group_dleq_commitments: no group");
+  const size_t EB = grp->eb;
   if (n == 0) return MPVSS_OK;
   if (!g1_host || !h1 || !g2 || !h2 || !r || !c || !a1_out || !a2_out || n > 0x7fffffff)
     return fail(ctx, MPVSS_E_INVALID, "group_dleq_commitments: bad argument");
@@ -373,7 +453,7 @@ extern "C" int mpvss_modp_group_dleq_commitments(mpvss_ctx* ctx, const mpvss_mod
   const modp_rt_consts* dc;
   RET_IF(rt_upload(ctx, grp, &dc));
   const uint8_t* dcc = nullptr;
-  if (!c_per_share) RET_IF(rt_stage_small(ctx, c, ctx->rt_small[1], &dcc));
+  if (!c_per_share) RET_IF(rt_stage_small(ctx, grp, c, ctx->rt_small[1], &dcc));
   for (size_t off = 0; off < n; off += MAX_CHUNK) {
     const size_t cnt = (n - off < MAX_CHUNK) ? n - off : MAX_CHUNK;
     const void *dh1, *dg2, *dh2, *dr, *dcs = dcc;
@@ -410,6 +490,7 @@ extern "C" int mpvss_modp_group_verify_distribution(mpvss_ctx* ctx, const mpvss_
   if (!ctx) return MPVSS_E_INVALID;
   std::lock_guard<std::mutex> lk(ctx->mu);
   if (rt_bad_group(grp)) return fail(ctx, MPVSS_E_INVALID, "group_verify_distribution: no group");
+  const size_t EB = grp->eb;
   if (!verdict || !challenge_host || n > 0x7fffffff || t > 0x7fffffff ||
       (n > 0 && (!commitments || !positions || !pubkeys || !shares || !responses || t == 0)))
     return fail(ctx, MPVSS_E_INVALID, "group_verify_distribution: bad argument");
@@ -422,7 +503,7 @@ extern "C" int mpvss_modp_group_verify_distribution(mpvss_ctx* ctx, const mpvss_
     RET_IF(rt_upload(ctx, grp, &dc));
     RET_IF(rt_stage_commitments(ctx, grp, dc, space, commitments, t));
     const uint8_t* dch;
-    RET_IF(rt_stage_small(ctx, challenge_host, ctx->rt_small[1], &dch));
+    RET_IF(rt_stage_small(ctx, grp, challenge_host, ctx->rt_small[1], &dch));
     const size_t chunk = std::min(n, MAX_CHUNK);
     std::vector<uint8_t> hX(chunk * EB), hY(chunk * EB), h1(chunk * EB), h2(chunk * EB);
     for (size_t off = 0; off < n; off += MAX_CHUNK) {
@@ -448,10 +529,10 @@ extern "C" int mpvss_modp_group_verify_distribution(mpvss_ctx* ctx, const mpvss_
       const uint8_t* Y = (space == MPVSS_DEVICE) ? hY.data() : shares + off * EB;
       // the transcript hashes Y_i as the box carries it (src/participant.rs:448), X_i, a1_i, a2_i canonical
       for (size_t i = 0; i < cnt; ++i) {
-        frame_update(h, hX.data() + i * EB);
-        frame_update(h, Y + i * EB);
-        frame_update(h, h1.data() + i * EB);
-        frame_update(h, h2.data() + i * EB);
+        rt_frame_update(h, hX.data() + i * EB, EB);
+        rt_frame_update(h, Y + i * EB, EB);
+        rt_frame_update(h, h1.data() + i * EB, EB);
+        rt_frame_update(h, h2.data() + i * EB, EB);
       }
       if (x_out_host) memcpy(x_out_host + off * EB, hX.data(), cnt * EB);
       if (a1_out_host) memcpy(a1_out_host + off * EB, h1.data(), cnt * EB);
@@ -459,7 +540,7 @@ extern "C" int mpvss_modp_group_verify_distribution(mpvss_ctx* ctx, const mpvss_
     }
     RET_IF(spans_collect(ctx));
   }
-  uint8_t digest[32], c[256];
+  uint8_t digest[32], c[RT_EB_MAX];
   h.final(digest);
   if (digest32_out) memcpy(digest32_out, digest, 32);
   rt_hash_to_scalar(grp, digest, 32, c);          // src/participant.rs:451-455
@@ -473,6 +554,7 @@ extern "C" int mpvss_modp_group_verify_shares(mpvss_ctx* ctx, const mpvss_modp_g
   if (!ctx) return MPVSS_E_INVALID;
   std::lock_guard<std::mutex> lk(ctx->mu);
   if (rt_bad_group(grp)) return fail(ctx, MPVSS_E_INVALID, "group_verify_shares: no group");
+  const size_t EB = grp->eb;
   if (n == 0) return MPVSS_OK;
   if (!pk || !s || !y || !c || !r || !verdicts_host || n > 0x7fffffff)
     return fail(ctx, MPVSS_E_INVALID, "group_verify_shares: bad argument");
@@ -511,11 +593,11 @@ extern "C" int mpvss_modp_group_verify_shares(mpvss_ctx* ctx, const mpvss_modp_g
     const uint8_t* C = space == MPVSS_DEVICE ? hc.data() : c + off * EB;
     for (size_t i = 0; i < cnt; ++i) {
       mpvss::Sha256 hs;
-      frame_update(hs, P + i * EB);
-      frame_update(hs, Y + i * EB);
-      frame_update(hs, h1.data() + i * EB);
-      frame_update(hs, h2.data() + i * EB);
-      uint8_t digest[32], cc[256];
+      rt_frame_update(hs, P + i * EB, EB);
+      rt_frame_update(hs, Y + i * EB, EB);
+      rt_frame_update(hs, h1.data() + i * EB, EB);
+      rt_frame_update(hs, h2.data() + i * EB, EB);
+      uint8_t digest[32], cc[RT_EB_MAX];
       hs.final(digest);
       rt_hash_to_scalar(grp, digest, 32, cc);     // src/dleq.rs:119-126
       verdicts_host[off + i] = memcmp(cc, C + i * EB, EB) == 0 ? 1 : 0;
@@ -533,12 +615,12 @@ extern "C" int mpvss_modp_group_verify_shares(mpvss_ctx* ctx, const mpvss_modp_g
 // ---- scalar ring (host only, no context): the group-14 contracts of capi_scalar.inc with q - 1 of the handle ---------------
 extern "C" int mpvss_modp_group_scalar_mul(const mpvss_modp_group* grp, const uint8_t* a256, const uint8_t* b256, uint8_t* out256) {
   if (rt_bad_group(grp) || !a256 || !b256 || !out256) return MPVSS_E_INVALID;
-  scalar_mul_bytes<32>(grp->ord, true, a256, b256, out256);              // modp.rs:180-182
+  rt_rings(grp, [&](const auto& R) { scalar_mul_bytes<RT_NW(R)>(R.ord, true, a256, b256, out256); });   // modp.rs:180-182
   return MPVSS_OK;
 }
 extern "C" int mpvss_modp_group_scalar_sub(const mpvss_modp_group* grp, const uint8_t* a256, const uint8_t* b256, uint8_t* out256) {
   if (rt_bad_group(grp) || !a256 || !b256 || !out256) return MPVSS_E_INVALID;
-  scalar_sub_bytes<32>(grp->ord, true, a256, b256, out256);              // modp.rs:184-192
+  rt_rings(grp, [&](const auto& R) { scalar_sub_bytes<RT_NW(R)>(R.ord, true, a256, b256, out256); });   // modp.rs:184-192
   return MPVSS_OK;
 }
 extern "C" int mpvss_modp_group_dleq_responses(const mpvss_modp_group* grp, const uint8_t* w, const uint8_t* alpha, const uint8_t* c,
@@ -546,7 +628,9 @@ extern "C" int mpvss_modp_group_dleq_responses(const mpvss_modp_group* grp, cons
   if (rt_bad_group(grp)) return MPVSS_E_INVALID;
   if (n == 0) return MPVSS_OK;
   if (!w || !alpha || !c || !r_out) return MPVSS_E_INVALID;
-  responses_bytes<32>(grp->ord, true, w, alpha, c, c_per_share ? EB : 0, n, r_out, host_threads(threads));
+  rt_rings(grp, [&](const auto& R) {
+    responses_bytes<RT_NW(R)>(R.ord, true, w, alpha, c, c_per_share ? grp->eb : 0, n, r_out, host_threads(threads));
+  });
   return MPVSS_OK;
 }
 extern "C" int mpvss_modp_group_poly_eval(const mpvss_modp_group* grp, const uint8_t* coeffs, size_t t, const int64_t* positions,
@@ -556,7 +640,7 @@ extern "C" int mpvss_modp_group_poly_eval(const mpvss_modp_group* grp, const uin
   if (!coeffs || !positions || !out || t == 0) return MPVSS_E_INVALID;
   for (size_t i = 0; i < n; ++i)
     if (positions[i] < 0) return MPVSS_E_INVALID;
-  poly_eval_bytes<32>(grp->ord, true, coeffs, t, positions, n, out, host_threads(threads));
+  rt_rings(grp, [&](const auto& R) { poly_eval_bytes<RT_NW(R)>(R.ord, true, coeffs, t, positions, n, out, host_threads(threads)); });
   return MPVSS_OK;
 }
 
@@ -593,14 +677,16 @@ struct RtWipe {
 };
 
 // Shares per k_rt_twin_exp launch: 4096 waves, more than the chip holds at once, and it bounds the bucket scratch the context
-// keeps at 2 x 15 x 65536 numbers (540 MiB at 18 limbs per lane, 270 MiB at 9, 150 MiB at 5) whatever MAX_CHUNK is.
-constexpr size_t RT_TWIN_LAUNCH = 65536;
+// keeps at 2 x 15 x 65536 numbers (540 MiB at 18 limbs per lane, 270 MiB at 9, 150 MiB at 5) whatever MAX_CHUNK is.  At 27
+// limbs per lane a share's buckets are 12 960 bytes: 32768 shares (2048 waves, 405 MiB) keep the same ceiling.
+size_t rt_twin_launch(int lpl) { return lpl == 27 ? 32768 : 65536; }
 
 // out1 = B^e1, out2 = B^e2 for cnt shares (device pointers, one chunk).  Large batches: k_rt_twin_exp over bucket scratch of
 // the context, of which `wipe` zeroes what the call used; small ones, two left-to-right exponent sets over the bases' tables
 // in one launch.
 int rt_twin_dev(mpvss_ctx* ctx, const mpvss_modp_group* grp, const modp_rt_consts* dc, const uint8_t* bases, const uint8_t* e1,
                 const uint8_t* e2, size_t cnt, uint8_t* out1, uint8_t* out2, RtWipe& wipe) {
+  const size_t EB = grp->eb, RT_TWIN_LAUNCH = rt_twin_launch(grp->lpl);
   if (cnt >= rt_twin_min_shares(grp->lpl)) {
     const size_t bytes = modp_rt_twin_scratch_bytes(grp->lpl, (int)std::min(cnt, RT_TWIN_LAUNCH));
     RET_IF(ensure(ctx, ctx->rt_buckets, bytes));
@@ -622,6 +708,7 @@ int rt_twin_dev(mpvss_ctx* ctx, const mpvss_modp_group* grp, const modp_rt_const
 // left to right over its 16-entry table
 int rt_fixed_base_dev(mpvss_ctx* ctx, const mpvss_modp_group* grp, const modp_rt_consts* dc, const uint8_t* base_host, const uint8_t* e,
                       size_t cnt, uint8_t* out, int timer) {
+  const size_t EB = grp->eb;
   const uint32_t* comb;
   RET_IF(rt_comb_for(ctx, grp, dc, base_host, cnt, false, &comb));
   if (comb) {
@@ -629,20 +716,23 @@ int rt_fixed_base_dev(mpvss_ctx* ctx, const mpvss_modp_group* grp, const modp_rt
     return 0;
   }
   const uint8_t* db;
-  RET_IF(rt_stage_small(ctx, base_host, ctx->rt_small[0], &db));
+  RET_IF(rt_stage_small(ctx, grp, base_host, ctx->rt_small[0], &db));
   const uint32_t* tg;
   RET_IF(rt_tables(ctx, grp, dc, db, 0, 1, ctx->rt_tabg, &tg));
   TIMED_LAUNCH(ctx, timer, modp_rt_launch_dual_exp(grp->lpl, tg, 0, nullptr, 0, e, EB, nullptr, 0, (int)cnt, out, dc, ctx->stream));
   return 0;
 }
 
-bool rt_zero_mod_q(const mpvss_modp_group* grp, const uint8_t* v256) {
-  uint64_t x[32];
-  hsc::from_bytes<32>(x, v256, true);
-  grp->mod.reduce1(x);
-  uint64_t o = 0;
-  for (int i = 0; i < 32; ++i) o |= x[i];
-  return o == 0;
+bool rt_zero_mod_q(const mpvss_modp_group* grp, const uint8_t* v) {
+  return rt_rings(grp, [&](const auto& R) {
+    constexpr int NW = RT_NW(R);
+    uint64_t x[NW];
+    hsc::from_bytes<NW>(x, v, true);
+    R.mod.reduce1(x);
+    uint64_t o = 0;
+    for (int i = 0; i < NW; ++i) o |= x[i];
+    return o == 0;
+  });
 }
 
 // The dealer's group side for n shares: X_i (commit_eval, or g^p_i when commitments is null: the dealer's own polynomial),
@@ -651,6 +741,7 @@ bool rt_zero_mod_q(const mpvss_modp_group* grp, const uint8_t* v256) {
 int rt_distribute_locked(mpvss_ctx* ctx, const mpvss_modp_group* grp, int space, const uint8_t* commitments, size_t t,
                          const int64_t* positions, const uint8_t* pubkeys, const uint8_t* p_values, const uint8_t* witnesses, size_t n,
                          uint8_t* x_out, uint8_t* y_out, uint8_t* a1_out, uint8_t* a2_out, uint8_t* digest32_out, RtWipe& wipe) {
+  const size_t EB = grp->eb;
   mpvss::Sha256 h;
   if (n > 0) {
     HIPCHK(ctx, hipSetDevice(ctx->device));
@@ -691,7 +782,12 @@ int rt_distribute_locked(mpvss_ctx* ctx, const mpvss_modp_group* grp, int space,
       HIPCHK(ctx, hipMemcpyAsync(h1.data(), d1, cnt * EB, hipMemcpyDeviceToHost, ctx->stream));
       HIPCHK(ctx, hipMemcpyAsync(h2.data(), d2, cnt * EB, hipMemcpyDeviceToHost, ctx->stream));
       HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-      frame_shares(h, hX.data(), hY.data(), h1.data(), h2.data(), 0, cnt);                            // participant.rs:238-245
+      if (EB == MPVSS_MODP_BYTES) {
+        frame_shares(h, hX.data(), hY.data(), h1.data(), h2.data(), 0, cnt);                          // participant.rs:238-245
+      } else {
+        for (size_t i = 0; i < cnt; ++i)
+          for (const uint8_t* a : {hX.data(), hY.data(), h1.data(), h2.data()}) rt_frame_update(h, a + i * EB, EB);
+      }
       if (!dev) {
         if (x_out) memcpy(x_out + off * EB, hX.data(), cnt * EB);
         if (y_out) memcpy(y_out + off * EB, hY.data(), cnt * EB);
@@ -707,9 +803,9 @@ int rt_distribute_locked(mpvss_ctx* ctx, const mpvss_modp_group* grp, int space,
   return MPVSS_OK;
 }
 
-// product of m elements (device bytes) by pairwise rounds through Montgomery form; result in buf[0..256)
+// product of m elements (device bytes) by pairwise rounds through Montgomery form; result in buf[0..EB)
 int rt_product_tree(mpvss_ctx* ctx, const mpvss_modp_group* grp, const modp_rt_consts* dc, uint8_t* buf, size_t m) {
-  const size_t LW = rt_L(grp);
+  const size_t LW = rt_L(grp), EB = grp->eb;
   RET_IF(ensure(ctx, ctx->rt_tab1, m * LW * 4));
   uint32_t* lm = (uint32_t*)ctx->rt_tab1.p;
   while (m > 1) {
@@ -769,6 +865,7 @@ extern "C" int mpvss_modp_group_batch_exp_fixed_base(mpvss_ctx* ctx, const mpvss
   if (!ctx) return MPVSS_E_INVALID;
   std::lock_guard<std::mutex> lk(ctx->mu);
   if (rt_bad_group(grp)) return fail(ctx, MPVSS_E_INVALID, "group_batch_exp_fixed_base: no group");
+  const size_t EB = grp->eb;
   if (n == 0) return MPVSS_OK;
   if (!base_host || !exps || !out || n > 0x7fffffff) return fail(ctx, MPVSS_E_INVALID, "group_batch_exp_fixed_base: bad argument");
   HIPCHK(ctx, hipSetDevice(ctx->device));
@@ -799,6 +896,7 @@ extern "C" int mpvss_modp_group_batch_twin_exp(mpvss_ctx* ctx, const mpvss_modp_
   if (!ctx) return MPVSS_E_INVALID;
   std::lock_guard<std::mutex> lk(ctx->mu);
   if (rt_bad_group(grp)) return fail(ctx, MPVSS_E_INVALID, "group_batch_twin_exp: no group");
+  const size_t EB = grp->eb;
   if (n == 0) return MPVSS_OK;
   if (!bases || !e1 || !e2 || !out1 || !out2 || n > 0x7fffffff) return fail(ctx, MPVSS_E_INVALID, "group_batch_twin_exp: bad argument");
   HIPCHK(ctx, hipSetDevice(ctx->device));
@@ -856,6 +954,7 @@ extern "C" int mpvss_modp_group_deal(mpvss_ctx* ctx, const mpvss_modp_group* grp
   if (!ctx) return MPVSS_E_INVALID;
   std::lock_guard<std::mutex> lk(ctx->mu);
   if (rt_bad_group(grp)) return fail(ctx, MPVSS_E_INVALID, "group_deal: no group");
+  const size_t EB = grp->eb;
   if (n > 0x7fffffff || t > 0x7fffffff ||
       (n > 0 && (!coeffs_host || !positions_host || !pubkeys_host || !witnesses_host || !y_out || !r_out || t == 0)))
     return fail(ctx, MPVSS_E_INVALID, "group_deal: bad argument (t >= 1, n < 2^31)");
@@ -865,14 +964,16 @@ extern "C" int mpvss_modp_group_deal(mpvss_ctx* ctx, const mpvss_modp_group* grp
   RtWipe wipe{ctx};
   wipe.host.push_back(&P);
   const int threads = host_threads(0);
-  if (n > 0) poly_eval_bytes<32>(grp->ord, true, coeffs_host, t, positions_host, n, P.data(), threads);   // participant.rs:202
-  uint8_t digest[32], challenge[EB];
+  if (n > 0)                                                                                               // participant.rs:202
+    rt_rings(grp, [&](const auto& R) { poly_eval_bytes<RT_NW(R)>(R.ord, true, coeffs_host, t, positions_host, n, P.data(), threads); });
+  uint8_t digest[32], challenge[RT_EB_MAX];
   RET_IF(rt_distribute_locked(ctx, grp, MPVSS_HOST, nullptr, t, positions_host, pubkeys_host, P.data(), witnesses_host, n, x_out, y_out,
                               a1_out, a2_out, digest, wipe));
   rt_hash_to_scalar(grp, digest, 32, challenge);                 // participant.rs:251-252
   if (digest32_out) memcpy(digest32_out, digest, 32);
   if (challenge_out256) memcpy(challenge_out256, challenge, EB);
-  if (n > 0) responses_bytes<32>(grp->ord, true, witnesses_host, P.data(), challenge, 0, n, r_out, threads);   // :255-264
+  if (n > 0)                                                                                               // :255-264
+    rt_rings(grp, [&](const auto& R) { responses_bytes<RT_NW(R)>(R.ord, true, witnesses_host, P.data(), challenge, 0, n, r_out, threads); });
   return MPVSS_OK;
 }
 
@@ -886,6 +987,7 @@ extern "C" int mpvss_modp_group_extract_shares(mpvss_ctx* ctx, const mpvss_modp_
   if (!ctx) return MPVSS_E_INVALID;
   std::lock_guard<std::mutex> lk(ctx->mu);
   if (rt_bad_group(grp)) return fail(ctx, MPVSS_E_INVALID, "group_extract_shares: no group");
+  const size_t EB = grp->eb;
   if (n == 0) return MPVSS_OK;
   if (!pk || !y || !xinv || !w || !s_out || !c_out_host || n > 0x7fffffff)
     return fail(ctx, MPVSS_E_INVALID, "group_extract_shares: bad argument");
@@ -915,7 +1017,7 @@ extern "C" int mpvss_modp_group_extract_shares(mpvss_ctx* ctx, const mpvss_modp_
     hsc::parallel_for(cnt, threads, [&](size_t lo, size_t hi) {
       bool z = false;
       for (size_t i = lo; i < hi; ++i) {
-        scalar_mul_bytes<32>(grp->ord, true, W + i * EB, XI + i * EB, e2.data() + i * EB);
+        rt_rings(grp, [&](const auto& R) { scalar_mul_bytes<RT_NW(R)>(R.ord, true, W + i * EB, XI + i * EB, e2.data() + i * EB); });
         z = z || rt_zero_mod_q(grp, Y + i * EB);
       }
       if (z) zero_row.store(1);
@@ -956,10 +1058,10 @@ extern "C" int mpvss_modp_group_extract_shares(mpvss_ctx* ctx, const mpvss_modp_
     hsc::parallel_for(cnt, threads, [&](size_t lo, size_t hi) {
       for (size_t i = lo; i < hi; ++i) {
         mpvss::Sha256 hs;
-        frame_update(hs, PK + i * EB);
-        frame_update(hs, Y + i * EB);
-        frame_update(hs, h1.data() + i * EB);
-        frame_update(hs, h2.data() + i * EB);
+        rt_frame_update(hs, PK + i * EB, EB);
+        rt_frame_update(hs, Y + i * EB, EB);
+        rt_frame_update(hs, h1.data() + i * EB, EB);
+        rt_frame_update(hs, h2.data() + i * EB, EB);
         uint8_t digest[32];
         hs.final(digest);
         rt_hash_to_scalar(grp, digest, 32, c_out_host + (off + i) * EB);      // :329-343
@@ -979,27 +1081,33 @@ extern "C" int mpvss_modp_group_reconstruct(mpvss_ctx* ctx, const mpvss_modp_gro
   if (!ctx) return MPVSS_E_INVALID;
   std::lock_guard<std::mutex> lk(ctx->mu);
   if (rt_bad_group(grp)) return fail(ctx, MPVSS_E_INVALID, "group_reconstruct: no group");
+  const size_t EB = grp->eb;
   if (!positions_host || !shares || m == 0 || !gs_out256 || m > 0x7fffffff)
     return fail(ctx, MPVSS_E_INVALID, "group_reconstruct: bad argument");
   for (size_t i = 0; i < m; ++i)
     if (positions_host[i] < 1) return fail(ctx, MPVSS_E_INVALID, "group_reconstruct: positions must be >= 1 (util.rs:47-64)");
   HIPCHK(ctx, hipSetDevice(ctx->device));
   spans_reset(ctx);
-  std::vector<hsc::Num<32>> mag;
   std::vector<char> neg;
-  if (!lagrange_at_zero<32>(grp->sub, positions_host, m, mag, neg, false))
-    return fail(ctx, MPVSS_E_INVALID, "group_reconstruct: duplicate positions, or a Lagrange denominator without inverse mod (q-1)/2");
   std::vector<uint8_t> exps(m * EB), hs;
-  for (size_t i = 0; i < m; ++i) {
-    uint64_t e[32];
-    memcpy(e, mag[i].v, sizeof(e));
-    if (neg[i]) {
-      uint64_t o = 0;
-      for (int k = 0; k < 32; ++k) o |= e[k];
-      if (o) hsc::sub_n<32>(e, grp->ord.m, e);
+  const bool lagrange_ok = rt_rings(grp, [&](const auto& R) {
+    constexpr int NW = RT_NW(R);
+    std::vector<hsc::Num<NW>> mag;
+    if (!lagrange_at_zero<NW>(R.sub, positions_host, m, mag, neg, false)) return false;
+    for (size_t i = 0; i < m; ++i) {
+      uint64_t e[NW];
+      memcpy(e, mag[i].v, sizeof(e));
+      if (neg[i]) {
+        uint64_t o = 0;
+        for (int k = 0; k < NW; ++k) o |= e[k];
+        if (o) hsc::sub_n<NW>(e, R.ord.m, e);
+      }
+      hsc::to_bytes<NW>(exps.data() + i * EB, e, true);
     }
-    hsc::to_bytes<32>(exps.data() + i * EB, e, true);
-  }
+    return true;
+  });
+  if (!lagrange_ok)
+    return fail(ctx, MPVSS_E_INVALID, "group_reconstruct: duplicate positions, or a Lagrange denominator without inverse mod (q-1)/2");
   // a share that is 0 mod q has no inverse: the reference returns None when its coefficient is negative (:551-553)
   RET_IF(small_vec_to_host(ctx, space, shares, m * EB, hs));
   for (size_t i = 0; i < m; ++i)
@@ -1017,21 +1125,24 @@ extern "C" int mpvss_modp_group_reconstruct(mpvss_ctx* ctx, const mpvss_modp_gro
   TIMED_LAUNCH(ctx, 3, modp_rt_launch_dual_exp(grp->lpl, tb, 16 * rt_L(grp), nullptr, 0, (const uint8_t*)dE, EB, nullptr, 0, (int)m, dF, dc,
                                                ctx->stream));                                          // S_i^lambda_i
   RET_IF(rt_product_tree(ctx, grp, dc, dF, m));                                                        // fold with mul, :503-505
-  uint8_t gs[EB];
+  uint8_t gs[RT_EB_MAX];
   HIPCHK(ctx, hipMemcpyAsync(gs, dF, EB, hipMemcpyDeviceToHost, ctx->stream));
   HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
   memcpy(gs_out256, gs, EB);
   if (mask_out32) {
     // int_BE(SHA256(element_to_bytes(G^s))) mod q (:512-515): the reduction matters for q below 2^256
-    uint8_t hb[EB];
+    uint8_t hb[RT_EB_MAX];
     memset(hb, 0, EB - 32);
     mpvss::Sha256 h;
-    frame_min_bytes_update(h, gs);
+    rt_frame_min_bytes_update(h, gs, EB);
     h.final(hb + EB - 32);
-    uint64_t x[32];
-    hsc::from_bytes<32>(x, hb, true);
-    grp->mod.reduce1(x);
-    hsc::to_bytes<32>(hb, x, true);
+    rt_rings(grp, [&](const auto& R) {
+      constexpr int NW = RT_NW(R);
+      uint64_t x[NW];
+      hsc::from_bytes<NW>(x, hb, true);
+      R.mod.reduce1(x);
+      hsc::to_bytes<NW>(hb, x, true);
+    });
     memcpy(mask_out32, hb + EB - 32, 32);
   }
   RET_IF(spans_collect(ctx));

@@ -172,17 +172,19 @@ struct Modulus {
 };
 
 // A modulus whose length is known when the program runs (the scalar rings of a run-time MODP group: q - 1, (q-1)/2 and q
-// itself, 3 .. 2048 bits).  Same interface as Modulus<32> -- every operand and result is an array of 32 limbs, zero above
+// itself, 3 .. 64 CAP bits).  Same interface as Modulus<CAP> -- every operand and result is an array of CAP limbs, zero above
 // the modulus' own `n` limbs -- so that the byte-level bodies of capi_scalar.inc serve both; the loops run over n limbs.
-// The division is the same Knuth D; no Montgomery form (q - 1 is even).
-struct ModulusRt {
-  static constexpr int CAP = 32;
+// The division is the same Knuth D; no Montgomery form (q - 1 is even).  CAP = 32 for a group of 256-byte scalars
+// (ModulusRt), 48 for one of 384-byte scalars.
+template <int CAP_>
+struct ModulusRtN {
+  static constexpr int CAP = CAP_;
   uint64_t m[CAP];        // the modulus, zero above n limbs
   uint64_t mn[CAP];       // normalised: m << shift
   int n = 1;              // limbs of the modulus (top one non-zero)
   int shift = 0;
 
-  // mod: 32 limbs, not zero
+  // mod: CAP limbs, not zero
   void set(const uint64_t* mod) {
     memcpy(m, mod, sizeof(m));
     n = CAP;
@@ -195,7 +197,7 @@ struct ModulusRt {
     while (len > 0 && a[len - 1] == 0) --len;
     return len;
   }
-  // r (32 limbs) = u mod m for u of UL limbs, UL <= 2 CAP
+  // r (CAP limbs) = u mod m for u of UL limbs, UL <= 2 CAP
   void reduce(uint64_t* r, const uint64_t* u_in, int UL) const {
     UL = used(u_in, UL);
     if (UL < n) {
@@ -243,7 +245,7 @@ struct ModulusRt {
     for (int i = 0; i < 2 * CAP + 2; ++i) wipe[i] = 0;
   }
   void reduce1(uint64_t* a) const { reduce(a, a, CAP); }
-  // a, b: any 32-limb values
+  // a, b: any CAP-limb values
   void mulmod(uint64_t* r, const uint64_t* a, const uint64_t* b) const {
     const int la = used(a, CAP), lb = used(b, CAP);
     uint64_t t[2 * CAP];
@@ -283,7 +285,7 @@ struct ModulusRt {
   void submod(uint64_t* r, const uint64_t* a, const uint64_t* b) const {
     if (sub_n<CAP>(r, a, b)) add_n<CAP>(r, r, m);
   }
-  // a^-1 mod m for an ODD m (binary extended Euclid over the 32-limb arrays); false when m is even, a is 0 mod m or not invertible
+  // a^-1 mod m for an ODD m (binary extended Euclid over the CAP-limb arrays); false when m is even, a is 0 mod m or not invertible
   bool invert(uint64_t* r, const uint64_t* a_in) const {
     if (!(m[0] & 1)) return false;
     uint64_t a[CAP];
@@ -293,6 +295,7 @@ struct ModulusRt {
     return invert_odd<CAP>(r, a, m);
   }
 };
+typedef ModulusRtN<32> ModulusRt;
 
 // byte conversions: `bytes` is N*8 bytes wide, big- or little-endian
 template <int N>

@@ -31,18 +31,21 @@ struct ModpConsts {
   u32 one[L];
 };
 
-// limb j (W bits at bit offset W j) of a 256-byte big-endian integer; 0 above bit 2047
-LIMBS_HD u32 be256_limb(const uint8_t* __restrict__ be, int j) {
+// limb j (W bits at bit offset W j) of an EB-byte big-endian integer; 0 above bit 8 EB - 1.  EB = 256 on every ABI but that
+// of a wide run-time group (bn_quad_rt.h, 384 bytes).
+template <int EB>
+LIMBS_HD u32 be_limb(const uint8_t* __restrict__ be, int j) {
   const int o = W * j;
   const int p = o >> 3, s = o & 7;
   u64 w = 0;
 #pragma unroll
   for (int t = 0; t < 5; ++t) {                // W + 7 <= 40 bits
-    const int idx = 255 - (p + t);
+    const int idx = EB - 1 - (p + t);
     if (idx >= 0) w |= (u64)be[idx] << (8 * t);
   }
   return (u32)(w >> s) & MASK;
 }
+LIMBS_HD u32 be256_limb(const uint8_t* __restrict__ be, int j) { return be_limb<256>(be, j); }
 
 // Almost-normalised value < 2N in a slot of LIMBS limbs (every limb <= 2^W - 1 + 2^9) -> its canonical residue in
 // [0, N), exact limbs.  Serial: ONE lane of the number runs it, between two barriers.
@@ -85,14 +88,14 @@ LIMBS_HD void slot_canonicalize(u32* slot, const u32* __restrict__ n, int lift_p
   }
 }
 
-// little-endian 32-bit word wd (0..63) of the 2048-bit number in a slot of LIMBS exact limbs (limbs >= LIMBS are zero).
-// The ABI's byte order puts it, byte-swapped, at the mirrored position: out32[63 - wd] = bswap32(word).
-template <int LIMBS>
+// little-endian 32-bit word wd (0 .. EB/4 - 1) of the EB-byte number in a slot of LIMBS exact limbs (limbs >= LIMBS are zero).
+// The ABI's byte order puts it, byte-swapped, at the mirrored position: out32[EB/4 - 1 - wd] = bswap32(word).
+template <int LIMBS, int EB = 256>
 LIMBS_HD u32 slot_word32(const u32* slot, int wd) {
   const int bit = 32 * wd;
   const int j = bit / W, s = bit % W;
   u32 v = 0;
-  if (LIMBS * W >= 2048 || j < LIMBS) {
+  if (LIMBS * W >= 8 * EB || j < LIMBS) {
     // 32 bits starting at bit s of limb j: up to three limbs (s + 32 can exceed 2 W)
     u64 two = (u64)slot[j] | ((u64)(j + 1 < LIMBS ? slot[j + 1] : 0u) << W);
     two >>= s;

@@ -1,618 +1,11 @@
-// Kernels of a run-time MODP group: ModpGroup::init(length) of the reference (src/groups/modp.rs:72-84) -- any odd
-// modulus q of at most 2048 bits, chosen when the program runs.
-//
-//   ModpGroup::exp / ::mul                       (src/groups/modp.rs:122-132)      k_rt_dual_exp, k_rt_mul
-//   DLEQ verifier commitments a = g1^r h1^c      (src/dleq.rs:66-84)               k_rt_dual_exp (two tables)
-//   X_i = prod_j C_j^(i^j mod (q-1))             (src/participant.rs:423-434)      k_rt_commit_eval
-//
-// Layout and program shape are those of the group-14 kernels (modp_kernels.hip): one number per DPP quad, 16 numbers
-// per one-wave workgroup, the second operand of every product staged in LDS, 16-entry window tables in HBM.  The
-// product is bn::mont_mul at the widths of bn_quad_rt.h (5, 9, 18 limbs per lane), n0inv a run-time value.
-//
-// Cost follows the operands: the exponent loops run over the wave's largest exponent (4-bit windows), Horner's squarings
-// over the wave's largest reduced position.  Inputs are 256-byte big-endian values of any size: they enter a width by
-// one long product (bnrt::Width::IN_ROWS rows), which reduces them mod q on the way into Montgomery form.
-#include <hip/hip_runtime.h>
-#include <stdint.h>
-#include "bn_quad_rt.h"
+// Run-time MODP groups of 256-byte elements (moduli of at most 2048 bits): the kernel templates of modp_rt_kernels.inc at
+// 5, 9 and 18 limbs per lane, and the launch interface of modp_rt_kernels.h, which hands the wide width (27 limbs per lane,
+// modp_rt_kernels_wide.hip -- a translation unit of its own because its row loop needs another unroll threshold) over.
 #include "modp_rt_kernels.h"
 
-using namespace bnrt;
-
-#define RT_NUMS 16   // numbers per workgroup (one wave)
-
-namespace {
-
-// occupancy of each width: the 18-limb product wants 3 waves per SIMD like the group-14 kernels (135 VGPRs); the
-// narrower ones fit more
-template <int LPL> struct Occ { static constexpr int waves = 3; };
-template <> struct Occ<9> { static constexpr int waves = 4; };
-template <> struct Occ<5> { static constexpr int waves = 6; };
-
-// a = in R mod N (< 2N) for any 256-byte input: the input's 29-bit limbs go to the LDS slot (IN_ROWS of them), and one
-// long product with kin = 2^(29 (IN_ROWS + L)) mod N gives in kin 2^(-29 IN_ROWS) = in R, below N + kin in / 2^(29 IN_ROWS) < 2N.
-template <int LPL>
-__device__ __forceinline__ void to_mont_in(u32 (&a)[LPL], u32* slot, const uint8_t* __restrict__ in_be, const modp_rt_consts* __restrict__ cs,
-                                           const u32 (&n)[LPL], u32 n0inv, const Lane& ln) {
-  constexpr int IN_ROWS = Width<LPL>::IN_ROWS;
-#pragma unroll
-  for (int j = (int)0; j < IN_ROWS; j += 4) {
-    const int jj = j + (int)ln.q;
-    if (jj < IN_ROWS) slot[jj] = limbs::be256_limb(in_be, jj);
-  }
-  u32 k[LPL];
-  load_lane_limbs<LPL>(k, cs->kin, ln);
-  __builtin_amdgcn_wave_barrier();
-  mont_mul<N0INV_RUNTIME, false, IN_ROWS / LPL>(a, k, slot, n, ln, n0inv);
-  __builtin_amdgcn_wave_barrier();
-}
-
-// plain almost-normalised value < 2N -> canonical residue as 256 big-endian bytes (the slot is scratch)
-template <int LPL>
-__device__ __forceinline__ void store_canonical(uint8_t* __restrict__ out, const u32 (&a)[LPL], u32* slot,
-                                                const modp_rt_consts* __restrict__ cs, const Lane& ln, bool write) {
-  constexpr int L = Width<LPL>::L;
-  slot_store<LPL>(slot, a, ln);
-  __builtin_amdgcn_wave_barrier();
-  if (ln.q == 0) limbs::slot_canonicalize<L>(slot, cs->n);
-  __builtin_amdgcn_wave_barrier();
-  if (write) {
-    // lane q emits little-endian 32-bit words 16q .. 16q+15 (byte-swapped, mirrored position); limbs >= L are zero
-    u32* out32 = reinterpret_cast<u32*>(out);
-#pragma unroll
-    for (int i = 0; i < 16; ++i) {
-      const int wd = (int)ln.q * 16 + i;
-      out32[63 - wd] = __builtin_bswap32(limbs::slot_word32<L>(slot, wd));
-    }
-  }
-  __builtin_amdgcn_wave_barrier();
-}
-
-// bit length of a 256-byte big-endian number, the maximum over the whole wave (every quad: lane q scans bytes 64q .. 64q+63)
-__device__ __forceinline__ int wave_max_bits(const uint8_t* __restrict__ be, const Lane& ln) {
-  const uint4* p = reinterpret_cast<const uint4*>(be + 64 * ln.q);
-  int bl = 0;
-#pragma unroll
-  for (int i = 3; i >= 0; --i) {
-    const uint4 v = p[i];
-    const u32 w4[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-    for (int k = 3; k >= 0; --k) {
-      const u32 word = __builtin_bswap32(w4[k]);       // big-endian word 4 i + k of this lane's quarter
-      if (word != 0) bl = (16 - (4 * i + k)) * 32 - __builtin_clz(word);
-    }
-  }
-  if (bl > 0) bl += (3 - (int)ln.q) * 512;
-#pragma unroll
-  for (int off = 32; off >= 1; off >>= 1) {
-    const int other = __shfl_xor(bl, off);
-    bl = other > bl ? other : bl;
-  }
-  return __builtin_amdgcn_readfirstlane(bl);
-}
-
-__device__ __forceinline__ u32 nibble(const uint8_t* __restrict__ e, int w) {
-  const u32 byte = e[255 - (w >> 1)];
-  return (w & 1) ? (byte >> 4) : (byte & 15u);
-}
-
-}  // namespace
-
-#define RT_KERNEL(LPL) __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(Occ<LPL>::waves, Occ<LPL>::waves)))
-// Horner's kernel holds two slots per number: at 5 limbs per lane its LDS (10 KB per wave) admits 4 waves per SIMD
-#define RT_KERNEL_LDS2(LPL) __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(Occ<LPL>::waves < 4 ? Occ<LPL>::waves : 4, Occ<LPL>::waves < 4 ? Occ<LPL>::waves : 4)))
-
-// ---------------------------------------------------------------------------------------
-// out_m[x] = in[x] R mod N (commitments into Montgomery form)
-// ---------------------------------------------------------------------------------------
-template <int LPL>
-__global__ void RT_KERNEL(LPL) k_rt_to_mont(const uint8_t* __restrict__ in_be, int count, u32* __restrict__ out_m,
-                                            const modp_rt_consts* __restrict__ cs) {
-  constexpr int L = Width<LPL>::L, SLOT = Width<LPL>::SLOT;
-  __shared__ __attribute__((aligned(16))) u32 lds[RT_NUMS * SLOT];
-  const Lane ln = make_lane();
-  const int xi = blockIdx.x * RT_NUMS + (threadIdx.x >> 2);
-  const bool live = xi < count;
-  const int x = live ? xi : count - 1;
-  u32* slot = lds + (threadIdx.x >> 2) * SLOT;
-  const u32 n0inv = cs->n0inv;
-  u32 n[LPL], a[LPL];
-  load_lane_limbs<LPL>(n, cs->n, ln);
-  to_mont_in<LPL>(a, slot, in_be + (size_t)x * 256, cs, n, n0inv, ln);
-  if (live) store_lane_limbs<LPL>(out_m + (size_t)x * L, a, ln);
-}
-
-// ---------------------------------------------------------------------------------------
-// 16-entry window table of each base: tab[x][d] = base^d R mod N
-// ---------------------------------------------------------------------------------------
-template <int LPL>
-__global__ void RT_KERNEL(LPL) k_rt_table(const uint8_t* __restrict__ base_be, size_t base_stride, int count, u32* __restrict__ tab,
-                                          const modp_rt_consts* __restrict__ cs) {
-  constexpr int L = Width<LPL>::L, SLOT = Width<LPL>::SLOT;
-  __shared__ __attribute__((aligned(16))) u32 lds[RT_NUMS * SLOT];
-  const Lane ln = make_lane();
-  const int xi = blockIdx.x * RT_NUMS + (threadIdx.x >> 2);
-  const bool live = xi < count;
-  const int x = live ? xi : count - 1;
-  u32* slot = lds + (threadIdx.x >> 2) * SLOT;
-  const u32 n0inv = cs->n0inv;
-  u32 n[LPL], b[LPL], acc[LPL];
-  load_lane_limbs<LPL>(n, cs->n, ln);
-  to_mont_in<LPL>(b, slot, base_be + (size_t)x * base_stride, cs, n, n0inv, ln);
-  u32* my = tab + (size_t)x * 16 * L;
-  load_lane_limbs<LPL>(acc, cs->one_m, ln);
-  if (live) store_lane_limbs<LPL>(my, acc, ln);
-  if (live) store_lane_limbs<LPL>(my + L, b, ln);
-  slot_store<LPL>(slot, b, ln);
-  __builtin_amdgcn_wave_barrier();
-#pragma unroll
-  for (int k = 0; k < LPL; ++k) acc[k] = b[k];
-  for (int e = 2; e < 16; ++e) {
-    mont_mul<N0INV_RUNTIME>(acc, acc, slot, n, ln, n0inv);
-    if (live) store_lane_limbs<LPL>(my + (size_t)e * L, acc, ln);
-  }
-}
-
-// ---------------------------------------------------------------------------------------
-// out[x] = B1^e1 * B2^e2 mod q (B2 absent when tab2 is null), fixed 4-bit windows from the wave's highest one,
-// squarings shared.  One Montgomery-product site: every step only chooses its LDS operand (own copy = square, a table
-// entry, plain 1 at the end).
-// ---------------------------------------------------------------------------------------
-template <int LPL>
-__device__ __forceinline__ void rt_dual_exp_body(u32* lds, const u32* __restrict__ tab1, size_t tab1_stride, const u32* __restrict__ tab2,
-                                                 size_t tab2_stride, const uint8_t* __restrict__ e1_be, size_t e1_stride,
-                                                 const uint8_t* __restrict__ e2_be, size_t e2_stride, int count,
-                                                 uint8_t* __restrict__ out_be, const modp_rt_consts* __restrict__ cs) {
-  constexpr int L = Width<LPL>::L, SLOT = Width<LPL>::SLOT;
-  const Lane ln = make_lane();
-  const int xi = blockIdx.x * RT_NUMS + (threadIdx.x >> 2);
-  const bool live = xi < count;
-  const int x = live ? xi : count - 1;
-  u32* slot = lds + (threadIdx.x >> 2) * SLOT;
-  const u32 n0inv = cs->n0inv;
-  const bool has2 = tab2 != nullptr;
-  const u32* t1 = tab1 + (size_t)x * tab1_stride;
-  const u32* t2 = has2 ? tab2 + (size_t)x * tab2_stride : t1;
-  const uint8_t* e1 = e1_be + (size_t)x * e1_stride;
-  const uint8_t* e2 = has2 ? e2_be + (size_t)x * e2_stride : e1;
-  u32 n[LPL], acc[LPL];
-  load_lane_limbs<LPL>(n, cs->n, ln);
-  int nb = wave_max_bits(e1, ln);
-  if (has2) {
-    const int nb2 = wave_max_bits(e2, ln);
-    nb = nb2 > nb ? nb2 : nb;
-  }
-  const int nw = (nb + 3) >> 2;
-  // steps: 0..3 square, 4 times tab1[d1], 5 times tab2[d2], 6 next window, 7 final (times plain 1)
-  int w = nw - 1, s;
-  if (nw == 0) {
-    load_lane_limbs<LPL>(acc, cs->one_m, ln);
-    s = 7;
-  } else {
-    load_lane_limbs<LPL>(acc, t1 + (size_t)nibble(e1, w) * L, ln);
-    s = has2 ? 5 : 6;
-  }
-  while (true) {
-    if (s == 6) {
-      if (w == 0) {
-        s = 7;
-      } else {
-        --w;
-        s = 0;
-      }
-    }
-    if (s == 7) {
-      slot_fill_from_global<LPL>(slot, cs->one, ln);
-    } else if (s < 4) {
-      slot_store<LPL>(slot, acc, ln);
-    } else {
-      const u32 d = nibble(s == 4 ? e1 : e2, w);
-      slot_fill_from_global<LPL>(slot, (s == 4 ? t1 : t2) + (size_t)d * L, ln);
-    }
-    __builtin_amdgcn_wave_barrier();
-    if (s < 4) mont_mul<N0INV_RUNTIME, true>(acc, acc, slot, n, ln, n0inv);
-    else mont_mul<N0INV_RUNTIME>(acc, acc, slot, n, ln, n0inv);
-    __builtin_amdgcn_wave_barrier();
-    if (s == 7) break;
-    ++s;
-    if (s == 5 && !has2) s = 6;
-  }
-  store_canonical<LPL>(out_be + (size_t)x * 256, acc, slot, cs, ln, live);
-}
-
-template <int LPL>
-__global__ void RT_KERNEL(LPL) k_rt_dual_exp(const u32* __restrict__ tab1, size_t tab1_stride, const u32* __restrict__ tab2,
-                                             size_t tab2_stride, const uint8_t* __restrict__ e1_be, size_t e1_stride,
-                                             const uint8_t* __restrict__ e2_be, size_t e2_stride, int count,
-                                             uint8_t* __restrict__ out_be, const modp_rt_consts* __restrict__ cs) {
-  __shared__ __attribute__((aligned(16))) u32 lds[RT_NUMS * Width<LPL>::SLOT];
-  rt_dual_exp_body<LPL>(lds, tab1, tab1_stride, tab2, tab2_stride, e1_be, e1_stride, e2_be, e2_stride, count, out_be, cs);
-}
-
-// ---------------------------------------------------------------------------------------
-// Fixed-base comb of ONE base shared by every share: comb[k][d] = base^(d 16^k) R mod N, k = 0..511, d = 0..15, entry 0 =
-// R mod N.  Always 512 rows: any 256-byte exponent stays exact.  The counterpart of group 14's k_modp_comb_bases /
-// k_modp_comb_rows at a run-time width.
-//   k_rt_comb_bases (one workgroup, its first quad writes): the base enters through to_mont_in like a table base (a base
-//                   >= q is reduced, one that is 0 mod q gives rows of zeros); comb[k][1] = comb[k-1][1]^16, a row base
-//                   every four squarings, and entry 0 of every row
-//   k_rt_comb_rows  (one number per row k): comb[k][d] = comb[k][d-1] comb[k][1] for d = 2..15
-// ---------------------------------------------------------------------------------------
-#define RT_COMB_ROWS 512
-template <int LPL>
-__global__ void RT_KERNEL(LPL) k_rt_comb_bases(const uint8_t* __restrict__ base_be, u32* __restrict__ comb,
-                                               const modp_rt_consts* __restrict__ cs) {
-  constexpr int L = Width<LPL>::L, SLOT = Width<LPL>::SLOT;
-  __shared__ __attribute__((aligned(16))) u32 lds[RT_NUMS * SLOT];
-  const Lane ln = make_lane();
-  u32* slot = lds + (threadIdx.x >> 2) * SLOT;
-  const bool writer = (blockIdx.x == 0) && (threadIdx.x < 4);
-  const u32 n0inv = cs->n0inv;
-  u32 n[LPL], acc[LPL];
-  load_lane_limbs<LPL>(n, cs->n, ln);
-  load_lane_limbs<LPL>(acc, cs->one_m, ln);
-  if (writer) {
-#pragma nounroll
-    for (int k = 0; k < RT_COMB_ROWS; ++k) store_lane_limbs<LPL>(comb + (size_t)k * 16 * L, acc, ln);
-  }
-  to_mont_in<LPL>(acc, slot, base_be, cs, n, n0inv, ln);
-#pragma nounroll
-  for (int op = 0; op <= (RT_COMB_ROWS - 1) * 4; ++op) {
-    if (writer && (op & 3) == 0) store_lane_limbs<LPL>(comb + ((size_t)(op >> 2) * 16 + 1) * L, acc, ln);
-    if (op == (RT_COMB_ROWS - 1) * 4) break;
-    slot_store<LPL>(slot, acc, ln);
-    __builtin_amdgcn_wave_barrier();
-    mont_mul<N0INV_RUNTIME, true>(acc, acc, slot, n, ln, n0inv);
-    __builtin_amdgcn_wave_barrier();
-  }
-}
-
-template <int LPL>
-__global__ void RT_KERNEL(LPL) k_rt_comb_rows(u32* __restrict__ comb, const modp_rt_consts* __restrict__ cs) {
-  constexpr int L = Width<LPL>::L, SLOT = Width<LPL>::SLOT;
-  __shared__ __attribute__((aligned(16))) u32 lds[RT_NUMS * SLOT];
-  const Lane ln = make_lane();
-  const int xi = blockIdx.x * RT_NUMS + (threadIdx.x >> 2);
-  const bool live = xi < RT_COMB_ROWS;
-  const int k = live ? xi : RT_COMB_ROWS - 1;
-  u32* slot = lds + (threadIdx.x >> 2) * SLOT;
-  const u32 n0inv = cs->n0inv;
-  u32 n[LPL], acc[LPL];
-  load_lane_limbs<LPL>(n, cs->n, ln);
-  u32* row = comb + (size_t)k * 16 * L;
-  load_lane_limbs<LPL>(acc, row + L, ln);
-  slot_store<LPL>(slot, acc, ln);
-  __builtin_amdgcn_wave_barrier();
-#pragma nounroll
-  for (int d = 2; d < 16; ++d) {
-    mont_mul<N0INV_RUNTIME>(acc, acc, slot, n, ln, n0inv);
-    if (live) store_lane_limbs<LPL>(row + (size_t)d * L, acc, ln);
-  }
-}
-
-// ---------------------------------------------------------------------------------------
-// out[x] = base^e1[x] (* B2[x]^e2[x] when tab2 is not null) over the comb of the shared base: no squaring for e1 at all.
-//   phase A (tab2 only): B2^e2 left to right, 4-bit windows over B2's 16-entry table from the wave's highest set bit of e2
-//                        (e2_stride 0: one exponent for every x)
-//   phase B            : acc *= comb[k][nibble(e1, k)] for k = 0 .. nw1-1, nw1 from the wave's longest e1; a window whose digit
-//                        is 0 in all 16 numbers of the wave is skipped, otherwise a lane with digit 0 multiplies by entry 0
-//   then times plain 1.  Without tab2 and with every e1 of the wave 0 the result is 1.
-// One Montgomery-product site as in rt_dual_exp_body: every step only chooses its LDS operand.  The comb index is an exponent
-// digit, so the gather address follows the exponent, as the nibble-indexed table reads of k_rt_dual_exp do.
-// Full-width e1 at 2048 bits: 512 comb products + 1 exit = 513 Montgomery operations (tests/test_modp_rt_comb_model.py).
-// ---------------------------------------------------------------------------------------
-template <int LPL>
-__global__ void RT_KERNEL(LPL) k_rt_comb_exp(const u32* __restrict__ comb, const u32* __restrict__ tab2, size_t tab2_stride,
-                                             const uint8_t* __restrict__ e1_be, const uint8_t* __restrict__ e2_be, size_t e2_stride,
-                                             int count, uint8_t* __restrict__ out_be, const modp_rt_consts* __restrict__ cs) {
-  constexpr int L = Width<LPL>::L, SLOT = Width<LPL>::SLOT;
-  __shared__ __attribute__((aligned(16))) u32 lds[RT_NUMS * SLOT];
-  const Lane ln = make_lane();
-  const int xi = blockIdx.x * RT_NUMS + (threadIdx.x >> 2);
-  const bool live = xi < count;
-  const int x = live ? xi : count - 1;
-  u32* slot = lds + (threadIdx.x >> 2) * SLOT;
-  const u32 n0inv = cs->n0inv;
-  const bool has2 = tab2 != nullptr;
-  const uint8_t* e1 = e1_be + (size_t)x * 256;
-  const uint8_t* e2 = has2 ? e2_be + (size_t)x * e2_stride : e1;
-  const u32* t2 = has2 ? tab2 + (size_t)x * tab2_stride : comb;
-  u32 n[LPL], acc[LPL];
-  load_lane_limbs<LPL>(n, cs->n, ln);
-  const int nw1 = (wave_max_bits(e1, ln) + 3) >> 2;                 // <= 512 = RT_COMB_ROWS
-  const int nw2 = has2 ? (wave_max_bits(e2, ln) + 3) >> 2 : 0;
-  // steps: 0..3 square, 4 times tab2[d2], 5 next window of e2, 6 times comb[k][d1], 7 final (times plain 1)
-  int w = nw2 - 1, k = 0, s;
-  if (nw2 == 0) {
-    load_lane_limbs<LPL>(acc, cs->one_m, ln);
-    s = 6;
-  } else {
-    load_lane_limbs<LPL>(acc, t2 + (size_t)nibble(e2, w) * L, ln);
-    s = 5;
-  }
-  while (true) {
-    if (s == 5) {
-      if (w == 0) {
-        s = 6;
-      } else {
-        --w;
-        s = 0;
-      }
-    }
-    if (s == 6) {
-      while (k < nw1 && __builtin_amdgcn_ballot_w64(nibble(e1, k) != 0) == 0) ++k;
-      if (k == nw1) s = 7;
-    }
-    if (s == 7) {
-      slot_fill_from_global<LPL>(slot, cs->one, ln);
-    } else if (s < 4) {
-      slot_store<LPL>(slot, acc, ln);
-    } else if (s == 4) {
-      slot_fill_from_global<LPL>(slot, t2 + (size_t)nibble(e2, w) * L, ln);
-    } else {
-      slot_fill_from_global<LPL>(slot, comb + ((size_t)k * 16 + nibble(e1, k)) * L, ln);
-      ++k;
-    }
-    __builtin_amdgcn_wave_barrier();
-    if (s < 4) mont_mul<N0INV_RUNTIME, true>(acc, acc, slot, n, ln, n0inv);
-    else mont_mul<N0INV_RUNTIME>(acc, acc, slot, n, ln, n0inv);
-    __builtin_amdgcn_wave_barrier();
-    if (s == 7) break;
-    if (s < 5) ++s;
-  }
-  store_canonical<LPL>(out_be + (size_t)x * 256, acc, slot, cs, ln, live);
-}
-
-// ---------------------------------------------------------------------------------------
-// Two powers of each base in ONE launch: out1[x] = B[x]^e1[x] (blockIdx.y = 0), out2[x] = B[x]^e2[x] (blockIdx.y = 1), both
-// left to right over the base's one 16-entry table.  The form for a batch that does not fill the chip: twice the
-// workgroups of one k_rt_dual_exp launch, each with the short chain of a single exponentiation.
-// ---------------------------------------------------------------------------------------
-template <int LPL>
-__global__ void RT_KERNEL(LPL) k_rt_exp_sets(const u32* __restrict__ tab, size_t tab_stride, const uint8_t* __restrict__ e1_be,
-                                             const uint8_t* __restrict__ e2_be, int count, uint8_t* __restrict__ out1_be,
-                                             uint8_t* __restrict__ out2_be, const modp_rt_consts* __restrict__ cs) {
-  __shared__ __attribute__((aligned(16))) u32 lds[RT_NUMS * Width<LPL>::SLOT];
-  const bool second = blockIdx.y != 0;
-  rt_dual_exp_body<LPL>(lds, tab, tab_stride, nullptr, 0, second ? e2_be : e1_be, 256, nullptr, 0, count, second ? out2_be : out1_be, cs);
-}
-
-// ---------------------------------------------------------------------------------------
-// K_e[d] = prod over the windows k of exponent e with digit d of B^(16^k), for both exponents of each base with the squarings
-// shared: right to left over fixed 4-bit windows.  The running power P_k = B^(16^k) is computed once and multiplied into
-// bucket K_e[d] of each exponent whose k-th digit is d != 0; k_rt_twin_combine then forms
-//   B^e = prod_d K_e[d]^d = prod_{j=1..15} (K_e[15] K_e[14] .. K_e[j]).
-// The counterpart of group 14's k_modp_twin_exp_buckets / k_modp_bucket_combine at a run-time width.  A quad only ever
-// touches its own buckets, and every lane reads back exactly the words it wrote (load_lane_limbs / store_lane_limbs).
-//   buckets : HBM scratch, [16 gridDim.x][2][15][L] words (dead quads of the last workgroup have buckets of their own);
-//             bucket contents tell exponent windows: the caller zeroes the scratch afterwards.
-// Per window: one LDS copy of P_k serves both bucket products AND the first of the four squarings, and P_k comes back from
-// it afterwards, so the kernel holds one number in registers like k_rt_dual_exp.  A bucket product is skipped when the
-// digit is 0 in all 16 numbers of the wave; the window loop runs to the wave's highest set bit over both exponents.
-// Worst case at 2048 bits: 1 entry + 2044 squarings + 1024 bucket products + 2 (28 combine + 1 exit) = 3127 Montgomery
-// operations for both results (tests/test_modp_rt_twin_model.py).
-// ---------------------------------------------------------------------------------------
-#define RT_TWIN_BUCKETS 15
-template <int LPL>
-__global__ void RT_KERNEL(LPL) k_rt_twin_exp(const uint8_t* __restrict__ base_be, const uint8_t* __restrict__ e1_be,
-                                             const uint8_t* __restrict__ e2_be, int count, u32* __restrict__ buckets,
-                                             const modp_rt_consts* __restrict__ cs) {
-  constexpr int L = Width<LPL>::L, SLOT = Width<LPL>::SLOT;
-  __shared__ __attribute__((aligned(16))) u32 lds[RT_NUMS * SLOT];
-  const Lane ln = make_lane();
-  const int xi = blockIdx.x * RT_NUMS + (threadIdx.x >> 2);
-  const bool live = xi < count;
-  const int x = live ? xi : count - 1;
-  u32* slot = lds + (threadIdx.x >> 2) * SLOT;
-  const u32 n0inv = cs->n0inv;
-  const uint8_t* e1 = e1_be + (size_t)x * 256;
-  const uint8_t* e2 = e2_be + (size_t)x * 256;
-  u32* mine = buckets + (size_t)xi * 2 * RT_TWIN_BUCKETS * L;        // xi, not x: a dead quad works on scratch of its own
-  u32 n[LPL], acc[LPL];
-  load_lane_limbs<LPL>(n, cs->n, ln);
-  load_lane_limbs<LPL>(acc, cs->one_m, ln);
-#pragma nounroll
-  for (int b = 0; b < 2 * RT_TWIN_BUCKETS; ++b) store_lane_limbs<LPL>(mine + (size_t)b * L, acc, ln);
-  to_mont_in<LPL>(acc, slot, base_be + (size_t)x * 256, cs, n, n0inv, ln);
-  int nb = wave_max_bits(e1, ln);
-  {
-    const int nb2 = wave_max_bits(e2, ln);
-    nb = nb2 > nb ? nb2 : nb;
-  }
-  const int nw = (nb + 3) >> 2;
-  for (int w = 0; w < nw; ++w) {
-    slot_store<LPL>(slot, acc, ln);
-    __builtin_amdgcn_wave_barrier();
-#pragma nounroll
-    for (int e = 0; e < 2; ++e) {
-      const u32 d = nibble(e ? e2 : e1, w);
-      if (__builtin_amdgcn_ballot_w64(d != 0) == 0) continue;
-      u32* bk = mine + (size_t)(e * RT_TWIN_BUCKETS + (d ? d - 1 : 0)) * L;
-      load_lane_limbs<LPL>(acc, bk, ln);
-      mont_mul<N0INV_RUNTIME>(acc, acc, slot, n, ln, n0inv);
-      if (d != 0) store_lane_limbs<LPL>(bk, acc, ln);
-    }
-    if (w + 1 == nw) break;
-    slot_load<LPL>(acc, slot, ln);               // P_k back from its LDS copy: the window phase holds one number in registers
-#pragma nounroll
-    for (int sq = 0; sq < 4; ++sq) {
-      if (sq) {
-        __builtin_amdgcn_wave_barrier();
-        slot_store<LPL>(slot, acc, ln);
-        __builtin_amdgcn_wave_barrier();
-      }
-      mont_mul<N0INV_RUNTIME, true>(acc, acc, slot, n, ln, n0inv);
-    }
-    __builtin_amdgcn_wave_barrier();
-  }
-}
-
-// Combine step of k_rt_twin_exp, blockIdx.y = exponent: out[x] = prod_d K[d]^d by the running-product rule.  One number in
-// registers: acc = running product S = K[15] .. K[j]; the product T of the running products lives in K[15]'s own words
-// (T starts as K[15]).  A pair of steps for each j = 14 .. 1: S *= K[j]; T *= S with S parked in the LDS slot meanwhile.
-// Last step: T times plain 1.  28 + 1 products.
-template <int LPL>
-__global__ void RT_KERNEL(LPL) k_rt_twin_combine(u32* __restrict__ buckets, int count, uint8_t* __restrict__ out1_be,
-                                                 uint8_t* __restrict__ out2_be, const modp_rt_consts* __restrict__ cs) {
-  constexpr int L = Width<LPL>::L, SLOT = Width<LPL>::SLOT;
-  __shared__ __attribute__((aligned(16))) u32 lds[RT_NUMS * SLOT];
-  const Lane ln = make_lane();
-  const int xi = blockIdx.x * RT_NUMS + (threadIdx.x >> 2);
-  const bool live = xi < count;
-  const int x = live ? xi : count - 1;
-  u32* slot = lds + (threadIdx.x >> 2) * SLOT;
-  const u32 n0inv = cs->n0inv;
-  u32* my = buckets + ((size_t)xi * 2 + blockIdx.y) * RT_TWIN_BUCKETS * L;
-  u32* tprod = my + (size_t)(RT_TWIN_BUCKETS - 1) * L;
-  u32 n[LPL], acc[LPL];
-  load_lane_limbs<LPL>(n, cs->n, ln);
-  load_lane_limbs<LPL>(acc, tprod, ln);
-  constexpr int LAST = 2 * (RT_TWIN_BUCKETS - 1);
-#pragma nounroll
-  for (int step = 0; step <= LAST; ++step) {
-    __builtin_amdgcn_wave_barrier();
-    if (step == LAST) {
-      load_lane_limbs<LPL>(acc, tprod, ln);
-      slot_fill_from_global<LPL>(slot, cs->one, ln);
-    } else if (!(step & 1)) {
-      slot_fill_from_global<LPL>(slot, my + (size_t)(RT_TWIN_BUCKETS - 2 - (step >> 1)) * L, ln);
-    } else {
-      slot_store<LPL>(slot, acc, ln);
-      load_lane_limbs<LPL>(acc, tprod, ln);
-    }
-    __builtin_amdgcn_wave_barrier();
-    mont_mul<N0INV_RUNTIME>(acc, acc, slot, n, ln, n0inv);
-    if (step & 1) {
-      store_lane_limbs<LPL>(tprod, acc, ln);
-      __builtin_amdgcn_wave_barrier();
-      slot_load<LPL>(acc, slot, ln);
-    }
-  }
-  __builtin_amdgcn_wave_barrier();
-  store_canonical<LPL>((blockIdx.y ? out2_be : out1_be) + (size_t)x * 256, acc, slot, cs, ln, live);
-}
-
-// ---------------------------------------------------------------------------------------
-// out[x] = a[x] b[x] mod q from a R and b R (k_rt_to_mont): a b R, times plain 1
-// ---------------------------------------------------------------------------------------
-template <int LPL>
-__global__ void RT_KERNEL(LPL) k_rt_mul(const u32* __restrict__ a_m, const u32* __restrict__ b_m, int count,
-                                        uint8_t* __restrict__ out_be, const modp_rt_consts* __restrict__ cs) {
-  constexpr int L = Width<LPL>::L, SLOT = Width<LPL>::SLOT;
-  __shared__ __attribute__((aligned(16))) u32 lds[RT_NUMS * SLOT];
-  const Lane ln = make_lane();
-  const int xi = blockIdx.x * RT_NUMS + (threadIdx.x >> 2);
-  const bool live = xi < count;
-  const int x = live ? xi : count - 1;
-  u32* slot = lds + (threadIdx.x >> 2) * SLOT;
-  const u32 n0inv = cs->n0inv;
-  u32 n[LPL], acc[LPL];
-  load_lane_limbs<LPL>(n, cs->n, ln);
-  load_lane_limbs<LPL>(acc, a_m + (size_t)x * L, ln);
-#pragma nounroll
-  for (int step = 0; step < 2; ++step) {
-    slot_fill_from_global<LPL>(slot, step == 0 ? b_m + (size_t)x * L : cs->one, ln);
-    __builtin_amdgcn_wave_barrier();
-    mont_mul<N0INV_RUNTIME>(acc, acc, slot, n, ln, n0inv);
-    __builtin_amdgcn_wave_barrier();
-  }
-  store_canonical<LPL>(out_be + (size_t)x * 256, acc, slot, cs, ln, live);
-}
-
-// ---------------------------------------------------------------------------------------
-// X_i by Horner's rule in the exponent, X = (..((C_{t-1})^i' C_{t-2})^i' ..)^i' C_0 with i' = i mod (q-1).
-// For a safe prime q this is the reference's prod_j C_j^(i^j mod (q-1)) for every input: for a unit C_j the
-// exponents agree mod q-1 (Fermat); a C_j = 0 mod q gives 0 on both sides when i' > 0 (every i'^j >= 1) and when
-// i' = 0 the reference's exponents i^j mod (q-1) of j >= 1 are 0 too, so both sides are C_0.
-//   cm : [t][L] commitments in Montgomery form;  squarings run over the wave's largest i'.
-// LDS per wave: operand slot + saved-base slot per number, one slot with R mod N.
-// ---------------------------------------------------------------------------------------
-template <int LPL>
-__global__ void RT_KERNEL_LDS2(LPL) k_rt_commit_eval(const u32* __restrict__ cm, int t, const int64_t* __restrict__ positions, int count,
-                                                uint8_t* __restrict__ x_be, const modp_rt_consts* __restrict__ cs) {
-  constexpr int L = Width<LPL>::L, SLOT = Width<LPL>::SLOT;
-  __shared__ __attribute__((aligned(16))) u32 lds[(2 * RT_NUMS + 1) * SLOT];
-  const Lane ln = make_lane();
-  const int xi = blockIdx.x * RT_NUMS + (threadIdx.x >> 2);
-  const bool live = xi < count;
-  const int x = live ? xi : count - 1;
-  u32* slot = lds + (threadIdx.x >> 2) * SLOT;
-  u32* bslot = lds + (RT_NUMS + (threadIdx.x >> 2)) * SLOT;
-  u32* oneslot = lds + 2 * RT_NUMS * SLOT;
-  const u32 n0inv = cs->n0inv;
-  u32 n[LPL], acc[LPL];
-  load_lane_limbs<LPL>(n, cs->n, ln);
-  if (threadIdx.x < 4) slot_fill_from_global<LPL>(oneslot, cs->one_m, ln);
-  const u64 qm1 = ((u64)cs->qm1_hi << 32) | cs->qm1_lo;
-  u64 pos = (u64)positions[x];
-  if (qm1 != 0) pos %= qm1;
-  int nb = (pos == 0) ? 0 : 64 - __builtin_clzll(pos);
-#pragma unroll
-  for (int off = 32; off >= 4; off >>= 1) {
-    const int other = __shfl_xor(nb, off);
-    nb = other > nb ? other : nb;
-  }
-  nb = __builtin_amdgcn_readfirstlane(nb);
-  __builtin_amdgcn_wave_barrier();
-
-  load_lane_limbs<LPL>(acc, cm + (size_t)(t - 1) * L, ln);
-  //   for j = t-2 .. 0:   base = acc; acc = topbit ? base : one
-  //                       for bit = nb-2 .. 0: SQUARE; CONDMUL (by base or one, skipped if no lane needs it)
-  //                       CMUL (by C_j)
-  //   FINAL (by plain 1)
-  enum { K_SQUARE, K_CONDMUL, K_CMUL, K_FINAL };
-  int j = t - 2, bit = 0, kind = K_FINAL;
-  auto begin_coefficient = [&]() {
-    if (nb == 0) {   // every i' of the wave is 0: acc^0 = 1
-      load_lane_limbs<LPL>(acc, cs->one_m, ln);
-      kind = K_CMUL;
-      return;
-    }
-    slot_store<LPL>(bslot, acc, ln);
-    if (!((pos >> (nb - 1)) & 1)) load_lane_limbs<LPL>(acc, cs->one_m, ln);
-    bit = nb - 2;
-    kind = (bit >= 0) ? K_SQUARE : K_CMUL;
-  };
-  if (j >= 0) begin_coefficient();
-  while (true) {
-    const u32* bptr = slot;
-    bool skip = false;
-    if (kind == K_SQUARE) {
-      slot_store<LPL>(slot, acc, ln);
-    } else if (kind == K_CONDMUL) {
-      const bool mine = (pos >> bit) & 1;
-      skip = __builtin_amdgcn_ballot_w64(mine) == 0;
-      bptr = mine ? bslot : oneslot;
-    } else if (kind == K_CMUL) {
-      slot_fill_from_global<LPL>(slot, cm + (size_t)j * L, ln);
-    } else {
-      slot_fill_from_global<LPL>(slot, cs->one, ln);
-    }
-    if (!skip) {
-      __builtin_amdgcn_wave_barrier();
-      if (kind == K_SQUARE) mont_mul<N0INV_RUNTIME, true>(acc, acc, slot, n, ln, n0inv);
-      else mont_mul<N0INV_RUNTIME>(acc, acc, bptr, n, ln, n0inv);
-      __builtin_amdgcn_wave_barrier();
-    }
-    if (kind == K_FINAL) break;
-    if (kind == K_SQUARE) {
-      kind = K_CONDMUL;
-    } else if (kind == K_CONDMUL) {
-      --bit;
-      kind = (bit >= 0) ? K_SQUARE : K_CMUL;
-    } else {
-      --j;
-      if (j >= 0) begin_coefficient(); else kind = K_FINAL;
-    }
-  }
-  store_canonical<LPL>(x_be + (size_t)x * 256, acc, slot, cs, ln, live);
-}
-
-// ---------------------------------------------------------------------------------------
-// launchers
-// ---------------------------------------------------------------------------------------
-static inline int rt_grid(int count) { return (count + RT_NUMS - 1) / RT_NUMS; }
-
+#define RT_FN(name) modp_rt_##name
+#define RT_ELSEWHERE(name, lpl, ...) \
+  if ((lpl) == 27) return modp_rt27_##name((lpl), __VA_ARGS__)
 #define RT_DISPATCH(lpl, KERNEL, ...)                                                          \
   do {                                                                                         \
     if ((lpl) == 5) hipLaunchKernelGGL(KERNEL<5>, __VA_ARGS__);                                \
@@ -621,77 +14,19 @@ static inline int rt_grid(int count) { return (count + RT_NUMS - 1) / RT_NUMS; }
     else return (int)hipErrorInvalidValue;                                                     \
   } while (0)
 
+#include "modp_rt_kernels.inc"
+
+// what the host needs to know of a width: none of it launches anything
+extern "C" int modp_rt_elem_bytes(int lpl) { return lpl == 27 ? Width<27>::EB : (lpl == 5 || lpl == 9 || lpl == 18) ? Width<18>::EB : -1; }
+
 extern "C" int modp_rt_in_rows(int lpl) {
-  return lpl == 5 ? Width<5>::IN_ROWS : lpl == 9 ? Width<9>::IN_ROWS : lpl == 18 ? Width<18>::IN_ROWS : -1;
+  return lpl == 5 ? Width<5>::IN_ROWS : lpl == 9 ? Width<9>::IN_ROWS : lpl == 18 ? Width<18>::IN_ROWS : lpl == 27 ? Width<27>::IN_ROWS : -1;
 }
 
-extern "C" int modp_rt_launch_to_mont(int lpl, const uint8_t* in_be, int count, uint32_t* out_m, const modp_rt_consts* cs, hipStream_t s) {
-  if (count <= 0) return 0;
-  RT_DISPATCH(lpl, k_rt_to_mont, dim3(rt_grid(count)), dim3(64), 0, s, in_be, count, out_m, cs);
-  return (int)hipGetLastError();
-}
-
-extern "C" int modp_rt_launch_table(int lpl, const uint8_t* base_be, size_t base_stride, int count, uint32_t* tab,
-                                    const modp_rt_consts* cs, hipStream_t s) {
-  if (count <= 0) return 0;
-  RT_DISPATCH(lpl, k_rt_table, dim3(rt_grid(count)), dim3(64), 0, s, base_be, base_stride, count, tab, cs);
-  return (int)hipGetLastError();
-}
-
-extern "C" int modp_rt_launch_dual_exp(int lpl, const uint32_t* tab1, size_t tab1_stride, const uint32_t* tab2, size_t tab2_stride,
-                                       const uint8_t* e1, size_t e1_stride, const uint8_t* e2, size_t e2_stride, int count, uint8_t* out,
-                                       const modp_rt_consts* cs, hipStream_t s) {
-  if (count <= 0) return 0;
-  RT_DISPATCH(lpl, k_rt_dual_exp, dim3(rt_grid(count)), dim3(64), 0, s, tab1, tab1_stride, tab2, tab2_stride, e1, e1_stride, e2,
-              e2_stride, count, out, cs);
-  return (int)hipGetLastError();
-}
-
-extern "C" size_t modp_rt_comb_bytes(int lpl) { return (size_t)RT_COMB_ROWS * 16 * 4 * lpl * sizeof(uint32_t); }
-
-extern "C" int modp_rt_launch_comb_build(int lpl, const uint8_t* base_be, uint32_t* comb, const modp_rt_consts* cs, hipStream_t s) {
-  RT_DISPATCH(lpl, k_rt_comb_bases, dim3(1), dim3(64), 0, s, base_be, comb, cs);
-  RT_DISPATCH(lpl, k_rt_comb_rows, dim3(rt_grid(RT_COMB_ROWS)), dim3(64), 0, s, comb, cs);
-  return (int)hipGetLastError();
-}
-
-extern "C" int modp_rt_launch_comb_exp(int lpl, const uint32_t* comb, const uint32_t* tab2, size_t tab2_stride, const uint8_t* e1,
-                                       const uint8_t* e2, size_t e2_stride, int count, uint8_t* out, const modp_rt_consts* cs,
-                                       hipStream_t s) {
-  if (count <= 0) return 0;
-  RT_DISPATCH(lpl, k_rt_comb_exp, dim3(rt_grid(count)), dim3(64), 0, s, comb, tab2, tab2_stride, e1, e2, e2_stride, count, out, cs);
-  return (int)hipGetLastError();
-}
-
-extern "C" int modp_rt_launch_exp_sets(int lpl, const uint32_t* tab, size_t tab_stride, const uint8_t* e1, const uint8_t* e2, int count,
-                                       uint8_t* out1, uint8_t* out2, const modp_rt_consts* cs, hipStream_t s) {
-  if (count <= 0) return 0;
-  RT_DISPATCH(lpl, k_rt_exp_sets, dim3(rt_grid(count), 2), dim3(64), 0, s, tab, tab_stride, e1, e2, count, out1, out2, cs);
-  return (int)hipGetLastError();
+extern "C" size_t modp_rt_comb_bytes(int lpl) {
+  return (size_t)(lpl == 27 ? Width<27>::COMB_ROWS : Width<18>::COMB_ROWS) * 16 * 4 * lpl * sizeof(uint32_t);
 }
 
 extern "C" size_t modp_rt_twin_scratch_bytes(int lpl, int count) {
   return (size_t)rt_grid(count) * RT_NUMS * 2 * RT_TWIN_BUCKETS * 4 * lpl * sizeof(uint32_t);
-}
-
-extern "C" int modp_rt_launch_twin_exp(int lpl, const uint8_t* bases, const uint8_t* e1, const uint8_t* e2, int count, uint32_t* buckets,
-                                       uint8_t* out1, uint8_t* out2, const modp_rt_consts* cs, hipStream_t s) {
-  if (count <= 0) return 0;
-  RT_DISPATCH(lpl, k_rt_twin_exp, dim3(rt_grid(count)), dim3(64), 0, s, bases, e1, e2, count, buckets, cs);
-  RT_DISPATCH(lpl, k_rt_twin_combine, dim3(rt_grid(count), 2), dim3(64), 0, s, buckets, count, out1, out2, cs);
-  return (int)hipGetLastError();
-}
-
-extern "C" int modp_rt_launch_mul(int lpl, const uint32_t* a, const uint32_t* b, int count, uint8_t* out, const modp_rt_consts* cs,
-                                  hipStream_t s) {
-  if (count <= 0) return 0;
-  RT_DISPATCH(lpl, k_rt_mul, dim3(rt_grid(count)), dim3(64), 0, s, a, b, count, out, cs);
-  return (int)hipGetLastError();
-}
-
-extern "C" int modp_rt_launch_commit_eval(int lpl, const uint32_t* cm_m, int t, const int64_t* positions, int count, uint8_t* x_be,
-                                          const modp_rt_consts* cs, hipStream_t s) {
-  if (count <= 0) return 0;
-  RT_DISPATCH(lpl, k_rt_commit_eval, dim3(rt_grid(count)), dim3(64), 0, s, cm_m, t, positions, count, x_be, cs);
-  return (int)hipGetLastError();
 }

@@ -1,0 +1,34 @@
+// The launchers of a run-time MODP group, named by MODP_RT_FN: modp_rt_launch_* (modp_rt_kernels.h; every width) and, for
+// modp_rt_kernels.hip alone, modp_rt27_launch_* (modp_rt_kernels_wide.hip; 27 limbs per lane only).  No include guard: it
+// is included once per name.
+/* out_m[x] = in[x] R mod N (< 2N), any EB-byte big-endian input */
+int MODP_RT_FN(launch_to_mont)(int lpl, const uint8_t* in_be, int count, uint32_t* out_m, const modp_rt_consts* cs, hipStream_t s);
+/* tab[x][d] = base[x]^d R mod N, d < 16 (base_stride 0: one base for every x) */
+int MODP_RT_FN(launch_table)(int lpl, const uint8_t* base_be, size_t base_stride, int count, uint32_t* tab, const modp_rt_consts* cs,
+                         hipStream_t s);
+/* out[x] = B1[x]^e1[x] * B2[x]^e2[x] mod q, canonical EB-byte big-endian; tab1/tab2: 16-entry tables (stride in words, 0 = shared),
+   tab2 == NULL: B1^e1 alone; exponent strides in bytes (0 = one exponent for every x) */
+int MODP_RT_FN(launch_dual_exp)(int lpl, const uint32_t* tab1, size_t tab1_stride, const uint32_t* tab2, size_t tab2_stride,
+                            const uint8_t* e1, size_t e1_stride, const uint8_t* e2, size_t e2_stride, int count, uint8_t* out,
+                            const modp_rt_consts* cs, hipStream_t s);
+/* fixed-base comb of one base shared by every share: comb[k][d] = base^(d 16^k) R mod N, k < 2 EB, d < 16 --
+   modp_rt_comb_bytes(lpl) bytes (5.06 MiB at 27 limbs per lane, 2.25 MiB at 18, 1.125 MiB at 9, 640 KiB at 5).  The base is an
+   EB-byte value of any size on the device. */
+int MODP_RT_FN(launch_comb_build)(int lpl, const uint8_t* base_be, uint32_t* comb, const modp_rt_consts* cs, hipStream_t s);
+/* out[x] = base^e1[x] * B2[x]^e2[x] mod q, canonical: e1 over the comb with no squarings, e2 left to right over B2's 16-entry
+   table (tab2 == NULL: base^e1 alone; tab2_stride in words, e2_stride in bytes, 0 = one exponent for every x); e1 n x EB bytes */
+int MODP_RT_FN(launch_comb_exp)(int lpl, const uint32_t* comb, const uint32_t* tab2, size_t tab2_stride, const uint8_t* e1,
+                            const uint8_t* e2, size_t e2_stride, int count, uint8_t* out, const modp_rt_consts* cs, hipStream_t s);
+/* out1[x] = B[x]^e1[x], out2[x] = B[x]^e2[x] from the base's one table, two left-to-right exponent sets in one launch
+   (gridDim.y = 2); exponents and results n x EB bytes */
+int MODP_RT_FN(launch_exp_sets)(int lpl, const uint32_t* tab, size_t tab_stride, const uint8_t* e1, const uint8_t* e2, int count,
+                            uint8_t* out1, uint8_t* out2, const modp_rt_consts* cs, hipStream_t s);
+/* the same two results right to left with shared squarings (k_rt_twin_exp): bases as EB-byte values of any size, `buckets`
+   a scratch of modp_rt_twin_scratch_bytes(lpl, count) bytes that holds exponent windows afterwards (the caller zeroes it) */
+int MODP_RT_FN(launch_twin_exp)(int lpl, const uint8_t* bases, const uint8_t* e1, const uint8_t* e2, int count, uint32_t* buckets,
+                            uint8_t* out1, uint8_t* out2, const modp_rt_consts* cs, hipStream_t s);
+/* out[x] = a[x] b[x] mod q, canonical, from a R and b R (modp_rt_launch_to_mont) */
+int MODP_RT_FN(launch_mul)(int lpl, const uint32_t* a_m, const uint32_t* b_m, int count, uint8_t* out, const modp_rt_consts* cs, hipStream_t s);
+/* X[x] = Horner in the exponent over the commitments cm_m ([t] numbers in Montgomery form) at i' = positions[x] mod (q-1) */
+int MODP_RT_FN(launch_commit_eval)(int lpl, const uint32_t* cm_m, int t, const int64_t* positions, int count, uint8_t* x_be,
+                               const modp_rt_consts* cs, hipStream_t s);

@@ -234,9 +234,11 @@ unsafe extern "C" {
     pub fn mpvss_box_verify_wire(ctx: *mut mpvss_ctx, buf: *const u8, len: usize, verdict: *mut c_int, digest32_out: *mut u8) -> c_int;
     // ---- MODP groups of a run-time modulus (ModpGroup::init)
     pub fn mpvss_modp_group_create(q_be: *const u8, q_len: usize, out: *mut *mut mpvss_modp_group) -> c_int;
+    pub fn mpvss_modp_group_create_wide(q_be: *const u8, q_len: usize, elem_bytes: usize, out: *mut *mut mpvss_modp_group) -> c_int;
     pub fn mpvss_modp_group_destroy(grp: *mut mpvss_modp_group);
     pub fn mpvss_modp_group_bits(grp: *const mpvss_modp_group) -> c_int;
     pub fn mpvss_modp_group_limbs_per_lane(grp: *const mpvss_modp_group) -> c_int;
+    pub fn mpvss_modp_group_elem_bytes(grp: *const mpvss_modp_group) -> c_int;
     pub fn mpvss_modp_group_hash_to_scalar(grp: *const mpvss_modp_group, data: *const u8, len: usize, out256: *mut u8) -> c_int;
     pub fn mpvss_modp_group_batch_exp(ctx: *mut mpvss_ctx, grp: *const mpvss_modp_group, space: c_int, bases: *const u8, exps: *const u8,
                                       n: usize, out: *mut u8) -> c_int;
