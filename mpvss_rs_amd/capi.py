@@ -33,6 +33,7 @@ EXPORTED_SYMBOLS = (
     "mpvss_ec_block_absorb_claimed", "mpvss_ec_poly_eval_device", "mpvss_ec_dleq_responses_device", "mpvss_ec_deal_compute", "mpvss_ec_deal",
     "mpvss_modp_extract_shares", "mpvss_ec_extract_shares", "mpvss_last_kernel_launches",
     "mpvss_modp_keyset_create", "mpvss_modp_keyset_destroy", "mpvss_modp_keyset_bytes", "mpvss_ctx_set_key_cache", "mpvss_ctx_set_key_cache_lru",
+    "mpvss_ctx_set_call_tables", "mpvss_call_tables_stats",
     "mpvss_modp_verify_block_compute_keyset", "mpvss_modp_fd_stats",
     "mpvss_modp_verify_many", "mpvss_modp_verify_many_chained", "mpvss_pipeline_stats_get", "mpvss_blocks_in_flight", "mpvss_sha256_uses_shani", "mpvss_issue_probe",
     "mpvss_modp_verify_shares_compute", "mpvss_modp_verify_shares_absorb",
@@ -117,6 +118,9 @@ def load_library() -> C.CDLL:
     lib.mpvss_modp_fd_stats.argtypes = [vp, C.POINTER(C.c_ulonglong), C.POINTER(C.c_ulonglong)]
     lib.mpvss_modp_keyset_create.argtypes = [vp, ci, u8p, sz, C.POINTER(vp)]
     lib.mpvss_ctx_set_key_cache.argtypes = [vp, ci]
+    lib.mpvss_ctx_set_call_tables.argtypes = [vp, ci]
+    lib.mpvss_ctx_set_call_tables.restype = ci
+    lib.mpvss_call_tables_stats.argtypes = [vp, C.POINTER(C.c_ulonglong), C.POINTER(C.c_ulonglong)]
     lib.mpvss_ctx_set_key_cache_lru.argtypes = [vp, ci, ci]
     lib.mpvss_ctx_set_key_cache_lru.restype = ci
     lib.mpvss_modp_keyset_destroy.argtypes = [vp, vp]
@@ -610,6 +614,20 @@ class Engine:
         rc = int(self.lib.mpvss_ctx_set_key_cache(self.ctx, int(min_boxes)))
         self._check(rc if rc < 0 else 0, "set_key_cache")
         return rc
+
+    def set_call_tables(self, min_boxes: int) -> int:
+        """mpvss_ctx_set_call_tables: per-key rows shared by the boxes of one verify_many call that present the same device key array
+        (on by default, threshold 3; 0: off).  Returns the previous setting."""
+        rc = int(self.lib.mpvss_ctx_set_call_tables(self.ctx, int(min_boxes)))
+        if rc < 0:
+            self._check(rc, "set_call_tables")
+        return rc
+
+    def call_tables_stats(self):
+        """(calls that built rows, boxes whose a2 took them) since the context was created"""
+        builds, served = C.c_ulonglong(0), C.c_ulonglong(0)
+        self._check(self.lib.mpvss_call_tables_stats(self.ctx, C.byref(builds), C.byref(served)), "call_tables_stats")
+        return int(builds.value), int(served.value)
 
     def set_key_cache_lru(self, max_sets: int, min_sightings: int = 2) -> int:
         """mpvss_ctx_set_key_cache_lru: key tables ACROSS one-box calls, keyed by the SHA-256 of the host key array (0: off).

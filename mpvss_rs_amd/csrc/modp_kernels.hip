@@ -1316,67 +1316,67 @@ k_modp_bucket_combine(const u32* __restrict__ buckets, const u32* __restrict__ o
 // 252 squarings shared by all nine bases, 37 x 8 = 296 products from the key table (7-bit windows; signed digits would
 // halve the table in a curve group, here an inverse is not free), 64 from Y's 4-bit table: 613 products instead of 2 620.
 // ---------------------------------------------------------------------------------------
-constexpr int KS_SUB = 8;          // sub-bases per key
-constexpr int KS_WIN = 7;          // window width of the 256-bit rows of r
-constexpr int KS_ENT = 1 << KS_WIN;                  // entries per sub-base
-constexpr int KS_NWIN = (256 + KS_WIN - 1) / KS_WIN; // windows per row (37; the top one holds 4 bits)
-// window w of row j of the 256-byte big-endian r: bits [256 j + 7 w, 256 j + 7 w + 7) of r, without the bits of row j + 1
-__device__ __forceinline__ u32 ks_digit(const uint8_t* __restrict__ r, int j, int w) {
-  const int g = 256 * j + KS_WIN * w, b = g >> 3;
-  const u32 lo = r[255 - b];
-  const u32 hi = (b + 1 < 256) ? r[254 - b] : 0u;
-  const int top = 256 - KS_WIN * w;                  // bits of this window that belong to the row
-  return ((lo | (hi << 8)) >> (g & 7)) & (u32)((1 << (top < KS_WIN ? top : KS_WIN)) - 1);
-}
+// The geometry (rows, bits per row, window bits) is a template parameter of the three kernels' bodies (limbs::RowGeom); the
+// instance behind the C entry points:
+using KeysetGeom = limbs::RowGeom<8, 256, 7>;      // 8 sub-bases per key, 7-bit windows of the 256-bit rows of r: 37 per row, the top one 4 bits
 
 // sub-bases: ks[key][j][1] = y^(2^(256 j)), ks[key][j][0] = 1   (one quad per key, 7 x 256 squarings)
-extern "C" __global__ void __launch_bounds__(BLOCK_THREADS) WAVES_ATTR
-k_modp_keyset_bases(const uint8_t* __restrict__ pk_be, int count, u32* __restrict__ ks,
-                    const ModpConsts* __restrict__ cs) {
-  __shared__ __attribute__((aligned(16))) u32 lds[NUMS_PER_BLOCK * SLOT_WORDS];
+template <class G>
+__device__ __forceinline__ void keyset_bases_body(const uint8_t* __restrict__ pk_be, int count, u32* __restrict__ ks,
+                                                  const ModpConsts* __restrict__ cs, u32* lds) {
   QUAD_KERNEL_PROLOGUE(count)
   u32 n[LPL], acc[LPL], one[LPL];
   load_lane_limbs(n, cs->n, ln);
   load_lane_limbs(one, cs->one_m, ln);
   load_be256(acc, pk_be + (size_t)x * 256, ln);
-  u32* mine = ks + (size_t)x * KS_SUB * KS_ENT * L;
-  // op 0: to Montgomery form; then 256 squarings per further sub-base
-  for (int op = 0; op <= (KS_SUB - 1) * 256; ++op) {
+  u32* mine = ks + (size_t)x * G::R * G::ENT * L;
+  // op 0: to Montgomery form; then B squarings per further sub-base
+  for (int op = 0; op <= (G::R - 1) * G::B; ++op) {
     if (op == 0) slot_fill_from_global(slot, cs->r2, ln); else slot_store(slot, acc, ln);
     __builtin_amdgcn_wave_barrier();
     if (op == 0) mont_mul<MODP_N0INV_C>(acc, acc, slot, n, ln); else mont_sqr<MODP_N0INV_C>(acc, acc, slot, n, ln);
     __builtin_amdgcn_wave_barrier();
-    if (live && (op % 256) == 0) {
-      u32* row = mine + (size_t)(op / 256) * KS_ENT * L;
+    if (live && (op % G::B) == 0) {
+      u32* row = mine + (size_t)(op / G::B) * G::ENT * L;
       store_lane_limbs(row, one, ln);
       store_lane_limbs(row + L, acc, ln);
     }
   }
 }
+extern "C" __global__ void __launch_bounds__(BLOCK_THREADS) WAVES_ATTR
+k_modp_keyset_bases(const uint8_t* __restrict__ pk_be, int count, u32* __restrict__ ks,
+                    const ModpConsts* __restrict__ cs) {
+  __shared__ __attribute__((aligned(16))) u32 lds[NUMS_PER_BLOCK * SLOT_WORDS];
+  keyset_bases_body<KeysetGeom>(pk_be, count, ks, cs, lds);
+}
 
 // rows: ks[key][j][d] = ks[key][j][d-1] * ks[key][j][1], d = 2..255   (one quad per (key, j))
-extern "C" __global__ void __launch_bounds__(BLOCK_THREADS) WAVES_ATTR
-k_modp_keyset_rows(u32* __restrict__ ks, int rows, const ModpConsts* __restrict__ cs) {
-  __shared__ __attribute__((aligned(16))) u32 lds[NUMS_PER_BLOCK * SLOT_WORDS];
+template <class G>
+__device__ __forceinline__ void keyset_rows_body(u32* __restrict__ ks, int rows, const ModpConsts* __restrict__ cs, u32* lds) {
   QUAD_KERNEL_PROLOGUE(rows)
-  u32* row = ks + (size_t)x * KS_ENT * L;
+  u32* row = ks + (size_t)x * G::ENT * L;
   u32 n[LPL], acc[LPL];
   load_lane_limbs(n, cs->n, ln);
   load_lane_limbs(acc, row + L, ln);
   slot_store(slot, acc, ln);
   __builtin_amdgcn_wave_barrier();
-  for (int d = 2; d < KS_ENT; ++d) {
+  for (int d = 2; d < G::ENT; ++d) {
     mont_mul<MODP_N0INV_C>(acc, acc, slot, n, ln);
     if (live) store_lane_limbs(row + (size_t)d * L, acc, ln);
   }
 }
+extern "C" __global__ void __launch_bounds__(BLOCK_THREADS) WAVES_ATTR
+k_modp_keyset_rows(u32* __restrict__ ks, int rows, const ModpConsts* __restrict__ cs) {
+  __shared__ __attribute__((aligned(16))) u32 lds[NUMS_PER_BLOCK * SLOT_WORDS];
+  keyset_rows_body<KeysetGeom>(ks, rows, cs, lds);
+}
 
 // out[x] = y_x^r_x * Y_x^c with y_x's registered table ks[x] and Y's 4-bit table tab2; c < 2^256 shared.
-extern "C" __global__ void __launch_bounds__(BLOCK_THREADS) WAVES_ATTR
-k_modp_keyset_dual_exp(const u32* __restrict__ ks, const u32* __restrict__ tab2, const uint8_t* __restrict__ r_be,
-                       const uint8_t* __restrict__ c_be, int count, uint8_t* __restrict__ out_be,
-                       const ModpConsts* __restrict__ cs) {
-  __shared__ __attribute__((aligned(16))) u32 lds[NUMS_PER_BLOCK * SLOT_WORDS];
+template <class G>
+__device__ __forceinline__ void keyset_dual_exp_body(const u32* __restrict__ ks, const u32* __restrict__ tab2,
+                                                     const uint8_t* __restrict__ r_be, const uint8_t* __restrict__ c_be, int count,
+                                                     uint8_t* __restrict__ out_be, const ModpConsts* __restrict__ cs, u32* lds) {
+  constexpr int KS_SUB = G::R, KS_WIN = G::WIN, KS_ENT = G::ENT, KS_NWIN = G::NWIN;
   QUAD_KERNEL_PROLOGUE(count)
   u32 n[LPL], acc[LPL];
   load_lane_limbs(n, cs->n, ln);
@@ -1394,7 +1394,7 @@ k_modp_keyset_dual_exp(const u32* __restrict__ ks, const u32* __restrict__ tab2,
     if (s == 0) {
       slot_store(slot, acc, ln);                       // squaring
     } else if (s <= KS_SUB) {
-      if (cur % KS_WIN == 0) fill = kt + ((size_t)(s - 1) * KS_ENT + ks_digit(r, s - 1, cur / KS_WIN)) * L; else skip = true;
+      if (cur % KS_WIN == 0) fill = kt + ((size_t)(s - 1) * KS_ENT + G::digit(r, s - 1, cur / KS_WIN)) * L; else skip = true;
     } else if (s == KS_SUB + 1) {
       if ((cur & 3) == 0) {
         const u32 byte = c_be[255 - (cur >> 3)];
@@ -1421,6 +1421,13 @@ k_modp_keyset_dual_exp(const u32* __restrict__ ks, const u32* __restrict__ tab2,
     }
   }
   store_canonical_be256(out_be + (size_t)x * 256, acc, false, slot, cs, n, ln, live);
+}
+extern "C" __global__ void __launch_bounds__(BLOCK_THREADS) WAVES_ATTR
+k_modp_keyset_dual_exp(const u32* __restrict__ ks, const u32* __restrict__ tab2, const uint8_t* __restrict__ r_be,
+                       const uint8_t* __restrict__ c_be, int count, uint8_t* __restrict__ out_be,
+                       const ModpConsts* __restrict__ cs) {
+  __shared__ __attribute__((aligned(16))) u32 lds[NUMS_PER_BLOCK * SLOT_WORDS];
+  keyset_dual_exp_body<KeysetGeom>(ks, tab2, r_be, c_be, count, out_be, cs, lds);
 }
 
 // ---------------------------------------------------------------------------------------
@@ -1720,12 +1727,12 @@ extern "C" int modp_launch_bucket_combine(const uint32_t* buckets, const uint32_
                      out1, out2, (const ModpConsts*)cs);
   return (int)hipGetLastError();
 }
-extern "C" size_t modp_keyset_words_per_key() { return (size_t)KS_SUB * KS_ENT * L; }
+extern "C" size_t modp_keyset_words_per_key() { return (size_t)KeysetGeom::KEY_WORDS; }
 extern "C" int modp_launch_keyset_build(const uint8_t* pk_be, int count, uint32_t* ks, const void* cs, hipStream_t s) {
   if (count <= 0) return 0;
   hipLaunchKernelGGL(k_modp_keyset_bases, dim3(grid_for(count)), dim3(BLOCK_THREADS), 0, s, pk_be, count, ks,
                      (const ModpConsts*)cs);
-  const long long rows = (long long)count * KS_SUB;
+  const long long rows = (long long)count * KeysetGeom::R;
   hipLaunchKernelGGL(k_modp_keyset_rows, dim3((unsigned)((rows + NUMS_PER_BLOCK - 1) / NUMS_PER_BLOCK)), dim3(BLOCK_THREADS),
                      0, s, ks, (int)rows, (const ModpConsts*)cs);
   return (int)hipGetLastError();

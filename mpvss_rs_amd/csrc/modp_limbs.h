@@ -47,6 +47,28 @@ LIMBS_HD u32 be_limb(const uint8_t* __restrict__ be, int j) {
 }
 LIMBS_HD u32 be256_limb(const uint8_t* __restrict__ be, int j) { return be_limb<256>(be, j); }
 
+// Geometry of a rows-by-windows table of one base y: table[j][d] = y^(d 2^(B j)), j < R rows of B bits, d < 2^W -- y^e for a
+// 2048-bit e is then the product over the rows of R B-bit exponentiations that share one chain of TOP squarings.  The registered
+// key tables are RowGeom<8, 256, 7>, the call tables RowGeom<2, 1024, 6>; every kernel that builds or reads such a table takes
+// its sizes and its digits from here.
+template <int R_, int B_, int W_>
+struct RowGeom {
+  static_assert(R_ * B_ == 2048 && W_ >= 1 && W_ <= 8, "rows of a 2048-bit exponent, windows within two bytes");
+  static constexpr int R = R_, B = B_, WIN = W_;
+  static constexpr int ENT = 1 << WIN;                       // entries per row
+  static constexpr int NWIN = (B + WIN - 1) / WIN;           // windows per row (the top one holds B - TOP bits)
+  static constexpr int TOP = WIN * (NWIN - 1);               // weight of a row's top window
+  static constexpr unsigned long long KEY_WORDS = (unsigned long long)R * ENT * L;
+  // window w of row j of the 256-byte big-endian e: bits [B j + WIN w, B j + WIN w + WIN) of e, without the bits of row j + 1
+  static LIMBS_HD u32 digit(const uint8_t* __restrict__ e, int j, int w) {
+    const int g = B * j + WIN * w, b = g >> 3;
+    const u32 lo = e[255 - b];
+    const u32 hi = (b + 1 < 256) ? e[254 - b] : 0u;
+    const int top = B - WIN * w;                             // bits of this window that belong to the row
+    return ((lo | (hi << 8)) >> (g & 7)) & (u32)((1 << (top < WIN ? top : WIN)) - 1);
+  }
+};
+
 // Almost-normalised value < 2N in a slot of LIMBS limbs (every limb <= 2^W - 1 + 2^9) -> its canonical residue in
 // [0, N), exact limbs.  Serial: ONE lane of the number runs it, between two barriers.
 // lift_parity 0 / 1 (scalar ring, n = the limbs of q'): the residue v in [0, q') is lifted to the number in

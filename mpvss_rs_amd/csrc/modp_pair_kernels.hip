@@ -545,50 +545,62 @@ k_modp_sched_exp_mul_pair(const u32* __restrict__ tab2, size_t tab2_stride, cons
 }
 
 // ---------------------------------------------------------------------------------------
-// a2 = y^r * Y^c against a REGISTERED key's table (k_modp_keyset_dual_exp of modp_kernels.hip on the pair layout: the same table
-// ks[key][j][d] = y^(d 2^(256 j)), d < 128, the same program -- 252 squarings, 296 products with table entries (7-bit windows of the
-// eight 256-bit rows of r), 64 with Y^(nibble of c) -- at 85 / 122 instead of 153 / 191 issue slots).  dleq.rs:79-81 with y a
-// long-lived participant key.
+// a2 = y^r * Y^c (dleq.rs:79-81) against a rows-by-windows table of y (limbs::RowGeom<R, B, WIN>: table[x][j][d] = y_x^(d 2^(B j))):
+// ONE program for every geometry.  From weight TOP down: a squaring per bit (not at the first weight), where WIN | weight the R
+// products with table[j][window of r_j], then the product with Y^digit where c has a window; at the end the product with plain 1
+// that leaves the Montgomery domain.   s = 0 squaring, 1 .. R row s - 1, R + 1 the window of c, R + 2 closing.
+//   SCHED = false: c is ONE 256-byte challenge at c_be, fixed nibbles against Y's full 16-entry table; the accumulator starts at 1
+//                  and every row is multiplied in (the program of k_modp_keyset_dual_exp, modp_kernels.hip)
+//   SCHED = true : Y^c as k_modp_dual_exp_w6_pair has it -- the host's sliding-window schedule against Y's odd powers (c_sched), or,
+//                  without one, fixed nibbles of a challenge per share (c_be + x c_stride); row 0's top window is loaded, not multiplied
+// Instances: the REGISTERED keys' table, RowGeom<8, 256, 7> (252 squarings, 296 + 64 products at 85 / 122 instead of 153 / 191
+// issue slots), and the call tables below.
 // ---------------------------------------------------------------------------------------
-extern "C" __global__ void __launch_bounds__(64 * PAIR_WAVES) PAIR_OCC_ATTR
-k_modp_keyset_dual_exp_pair(const u32* __restrict__ ks, size_t key_words, const u32* __restrict__ tab2, const uint8_t* __restrict__ r_be,
-                            const uint8_t* __restrict__ c_be, int count, uint8_t* __restrict__ out_be,
-                            const ModpConsts* __restrict__ cs, const Tables* __restrict__ gtab) {
-  PAIR_KERNEL_PROLOGUE(gtab, count)
+namespace {
+template <class G, bool SCHED>
+__device__ __forceinline__ void rows_dual_exp_pair(const u32* __restrict__ rows, size_t key_words, const u32* __restrict__ tab2,
+                                                   const uint8_t* __restrict__ r_be, const uint8_t* __restrict__ c_be, size_t c_stride,
+                                                   const uint16_t* __restrict__ c_sched, uint8_t* __restrict__ out_be,
+                                                   const ModpConsts* __restrict__ cs, PairCtx& pc) {
+  constexpr int R = G::R, WIN = G::WIN;
+  static_assert(G::B >= 256, "a row is at least as wide as the 256-bit challenge");
   const PairLane& pl = pc.pl;
-  // the program of k_modp_keyset_dual_exp: from bit 252 down, a squaring per bit (not at the first), at bits divisible by 7 the eight
-  // products with ks[j][window of r_j], at bits divisible by 4 the product with Y^(nibble of c), at the end the product with plain 1
-  //   s = 0 squaring, 1 .. 8 key table j = s - 1, 9 nibble of c, 10 closing
-  auto digit = [&](int j, int w) -> u32 {
-    const uint8_t* r = r_be + (size_t)pc.x * 256;
-    const int g = 256 * j + 7 * w, b = g >> 3;
-    const u32 lo = r[255 - b];
-    const u32 hi = (b + 1 < 256) ? r[254 - b] : 0u;
-    const int top = 256 - 7 * w;
-    return ((lo | (hi << 8)) >> (g & 7)) & (u32)((1 << (top < 7 ? top : 7)) - 1);
-  };
+  auto digit = [&](int j, int w) -> u32 { return G::digit(r_be + (size_t)pc.x * 256, j, w); };
   u32 acc[LP];
-  load_pair_limbs(acc, cs->one_m, pl);
-  int cur = 7 * 36, s = 1;
+  int cur = G::TOP, s = 1, si = 0;
+  if (SCHED) {
+    load_pair_limbs(acc, rows + (size_t)pc.x * key_words + (size_t)digit(0, G::NWIN - 1) * L, pl);
+    s = 2;
+  } else {
+    load_pair_limbs(acc, cs->one_m, pl);
+  }
+  const int sn = (SCHED && c_sched) ? (int)c_sched[0] : 0;
   while (true) {
     const u32* fill = nullptr;
     bool skip = false;
-    if (s >= 1 && s <= 8) {
-      if (cur % 7 == 0) fill = ks + (size_t)pc.x * key_words + ((size_t)(s - 1) * 128 + digit(s - 1, cur / 7)) * L; else skip = true;
-    } else if (s == 9) {
-      if ((cur & 3) == 0) {
-        const u32 byte = c_be[255 - (cur >> 3)];
+    if (s >= 1 && s <= R) {
+      if (cur % WIN == 0) fill = rows + (size_t)pc.x * key_words + ((size_t)(s - 1) * G::ENT + digit(s - 1, cur / WIN)) * L; else skip = true;
+    } else if (s == R + 1) {
+      if (SCHED && c_sched != nullptr) {
+        if (si < sn && cur == (int)c_sched[1 + 2 * si]) {
+          fill = tab2 + ((size_t)pc.x * 16 + c_sched[2 + 2 * si]) * L;
+          ++si;
+        } else {
+          skip = true;
+        }
+      } else if ((cur & 3) == 0 && (!SCHED || (cur < 256 && c_be != nullptr))) {
+        const u32 byte = SCHED ? c_be[(size_t)pc.x * c_stride + 255 - (cur >> 3)] : c_be[255 - (cur >> 3)];
         fill = tab2 + ((size_t)pc.x * 16 + ((cur & 4) ? (byte >> 4) : (byte & 15))) * L;
       } else {
         skip = true;
       }
-    } else if (s == 10) {
+    } else if (s == R + 2) {
       fill = cs->one;                                    // leave the Montgomery domain
     }
     if (!skip) pair_step<true>(acc, s == 0, fill, acc, pc.slot, pc.junk, pc.tb, pl);
-    if (s == 10) break;
-    if (s == 9) {
-      if (cur == 0) { s = 10; continue; }
+    if (s == R + 2) break;
+    if (s == R + 1) {
+      if (cur == 0) { s = R + 2; continue; }
       --cur;
       s = 0;
     } else {
@@ -596,6 +608,16 @@ k_modp_keyset_dual_exp_pair(const u32* __restrict__ ks, size_t key_words, const 
     }
   }
   store_canonical_pair(out_be + (size_t)pc.x * 256, acc, pc.slot, cs, pl, pc.live);
+}
+using KeysetGeom = limbs::RowGeom<8, 256, 7>;
+}  // namespace
+
+extern "C" __global__ void __launch_bounds__(64 * PAIR_WAVES) PAIR_OCC_ATTR
+k_modp_keyset_dual_exp_pair(const u32* __restrict__ ks, size_t key_words, const u32* __restrict__ tab2, const uint8_t* __restrict__ r_be,
+                            const uint8_t* __restrict__ c_be, int count, uint8_t* __restrict__ out_be,
+                            const ModpConsts* __restrict__ cs, const Tables* __restrict__ gtab) {
+  PAIR_KERNEL_PROLOGUE(gtab, count)
+  rows_dual_exp_pair<KeysetGeom, false>(ks, key_words, tab2, r_be, c_be, 0, nullptr, out_be, cs, pc);
 }
 
 // ---------------------------------------------------------------------------------------
@@ -613,13 +635,7 @@ k_modp_keyset_twin_exp_pair(const u32* __restrict__ ks, size_t key_words, const 
   const uint8_t* e_be = blockIdx.y ? e2_be : e1_be;
   uint8_t* out_be = blockIdx.y ? out2_be : out1_be;
   const uint8_t* e = e_be + (size_t)pc.x * 256;
-  auto digit = [&](int j, int w) -> u32 {
-    const int g = 256 * j + 7 * w, b = g >> 3;
-    const u32 lo = e[255 - b];
-    const u32 hi = (b + 1 < 256) ? e[254 - b] : 0u;
-    const int top = 256 - 7 * w;
-    return ((lo | (hi << 8)) >> (g & 7)) & (u32)((1 << (top < 7 ? top : 7)) - 1);
-  };
+  auto digit = [&](int j, int w) -> u32 { return KeysetGeom::digit(e, j, w); };
   const u32* kt = ks + (size_t)pc.x * key_words;
   u32 acc[LP];
   load_pair_limbs(acc, cs->one_m, pl);
@@ -640,6 +656,75 @@ k_modp_keyset_twin_exp_pair(const u32* __restrict__ ks, size_t key_words, const 
     }
   }
   store_canonical_pair(out_be + (size_t)pc.x * 256, acc, pc.slot, cs, pl, pc.live);
+}
+
+// ---------------------------------------------------------------------------------------
+// Call tables: the dealers' boxes of ONE verify_many call are boxes for the same participants, and in a2 = y^r * Y^c (dleq.rs:79-81)
+// both the window table of y and the 2 046 squarings under y^r depend on the key alone.  R rows per key,
+//   rows[x][j][d] = y_x^(d 2^(B j)),   d < 64,  j < R,  B = 2048 / R      (limbs::RowGeom<R, B, 6>),
+// built once per call, turn y^r into the product of R exponentiations with B-bit exponents that share ONE chain of squarings:
+// 6 (NWIN - 1) squarings and R NWIN - 1 row products instead of 2 046 and 341, NWIN = ceil(B / 6), through rows_dual_exp_pair above.
+//   R = 2 (the instance in use): 1 020 squarings + 341 row products, 36 KB per key;   R = 4: 510 + 343, 72 KB per key
+// The exact integer model with the operation counts: tests/test_call_tables_model.py.
+// ---------------------------------------------------------------------------------------
+namespace {
+using CallGeom = limbs::RowGeom<2, 1024, 6>;
+}  // namespace
+
+extern "C" __global__ void __launch_bounds__(64 * PAIR_WAVES) PAIR_OCC_ATTR
+k_modp_rows2_dual_exp_pair(const u32* __restrict__ rows, const u32* __restrict__ tab2, const uint8_t* __restrict__ r_be,
+                           const uint8_t* __restrict__ c_all, size_t c_stride, int count, uint8_t* __restrict__ out_be,
+                           const ModpConsts* __restrict__ cs, const uint16_t* __restrict__ c_sched, const Tables* __restrict__ gtab) {
+  PAIR_KERNEL_PROLOGUE(gtab, count)
+  rows_dual_exp_pair<CallGeom, true>(rows, (size_t)CallGeom::KEY_WORDS, tab2, r_be, c_all, c_stride, c_sched, out_be, cs, pc);
+}
+
+// The rows of `count` keys (once per call, one wave per SIMD: the base stays in registers beside the accumulator):
+// y -> Montgomery form, ENT - 2 products for row 0, then per further row B squarings of the row's base and its ENT - 2 products.
+namespace {
+template <class G>
+__device__ __forceinline__ void rows_build_pair(const uint8_t* __restrict__ pk_be, u32* __restrict__ rows, const ModpConsts* __restrict__ cs,
+                                                PairCtx& pc) {
+  const PairLane& pl = pc.pl;
+  u32 acc[LP], b[LP];
+  load_be256_pair(acc, pk_be + (size_t)pc.x * 256, pl);
+  u32* row = rows + (size_t)pc.x * (size_t)G::KEY_WORDS;
+  //   phase 0: acc = y R^2 / R; 1: acc *= b, the next entry of the row; 2: acc = acc^2, `left` times, towards the next row's base
+  int phase = 0, j = 0, e = 0, left = 0;
+  while (true) {
+    pair_step<true>(acc, phase == 2, phase == 0 ? cs->r2 : nullptr, b, pc.slot, pc.junk, pc.tb, pl);
+    if (phase == 1) {
+      if (pc.live) store_pair_limbs(row + (size_t)e * L, acc, pl);
+      if (++e < G::ENT) continue;
+      if (++j == G::R) break;
+      row += (size_t)G::ENT * L;
+#pragma unroll
+      for (int k = 0; k < LP; ++k) acc[k] = b[k];
+      phase = 2;
+      left = G::B;
+      continue;
+    }
+    if (phase == 2 && --left > 0) continue;
+    // acc is the base of row j: entries 0 and 1
+#pragma unroll
+    for (int k = 0; k < LP; ++k) b[k] = acc[k];
+    if (pc.live) {
+      u32 one[LP];
+      load_pair_limbs(one, cs->one_m, pl);
+      store_pair_limbs(row, one, pl);
+      store_pair_limbs(row + L, acc, pl);
+    }
+    e = 2;
+    phase = 1;
+  }
+}
+}  // namespace
+
+extern "C" __global__ void __launch_bounds__(64 * PAIR_WAVES)
+k_modp_rows2_build_pair(const uint8_t* __restrict__ pk_be, int count, u32* __restrict__ rows, const ModpConsts* __restrict__ cs,
+                        const Tables* __restrict__ gtab) {
+  PAIR_KERNEL_PROLOGUE(gtab, count)
+  rows_build_pair<CallGeom>(pk_be, rows, cs, pc);
 }
 
 // ---------------------------------------------------------------------------------------
@@ -1076,5 +1161,26 @@ extern "C" int modp_launch_keyset_dual_exp_pair(const uint32_t* ks, const uint32
   if (count <= 0) return 0;
   hipLaunchKernelGGL(k_modp_keyset_dual_exp_pair, dim3(pair_grid(count)), dim3(64 * PAIR_WAVES), 0, s, ks, modp_keyset_words_per_key(), tab2, r,
                      c, count, out, (const ModpConsts*)cs, (const Tables*)pair_tables);
+  return (int)hipGetLastError();
+}
+
+// (R = 4 -- 510 squarings, 72 KB per key -- was built and measured beside R = 2: faster on average, but not by more than the spread
+//  between runs of one build, profiles/call_tables_ab.txt; the smaller table and the shorter build stay)
+extern "C" size_t modp_call_rows_words_per_key() { return (size_t)CallGeom::KEY_WORDS; }
+
+extern "C" int modp_launch_call_rows_build(const uint8_t* pk_be, int count, uint32_t* tab, const void* cs, const void* pair_tables,
+                                           hipStream_t s) {
+  if (count <= 0) return 0;
+  hipLaunchKernelGGL(k_modp_rows2_build_pair, dim3(pair_grid(count)), dim3(64 * PAIR_WAVES), 0, s, pk_be, count, tab,
+                     (const ModpConsts*)cs, (const Tables*)pair_tables);
+  return (int)hipGetLastError();
+}
+
+extern "C" int modp_launch_call_rows_dual_exp(const uint32_t* tab, const uint32_t* tab2, const uint8_t* r, const uint8_t* c, size_t c_stride,
+                                              const uint16_t* c_sched, int count, uint8_t* out, const void* cs, const void* pair_tables,
+                                              hipStream_t s) {
+  if (count <= 0) return 0;
+  hipLaunchKernelGGL(k_modp_rows2_dual_exp_pair, dim3(pair_grid(count)), dim3(64 * PAIR_WAVES), 0, s, tab, tab2, r, c, c_stride, count, out,
+                     (const ModpConsts*)cs, c_sched, (const Tables*)pair_tables);
   return (int)hipGetLastError();
 }

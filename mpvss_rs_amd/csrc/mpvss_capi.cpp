@@ -227,6 +227,25 @@ struct mpvss_ctx {
     spare_table = nullptr;
     spare_table_cap = 0;
   }
+  // Call tables (mpvss_ctx_set_call_tables, on by default): a few rows per key, rows[key][j][d] = y^(d 2^(B j)), for the key array that
+  // at least `call_tables_min` large boxes of ONE verify_many call share, built on a low-priority stream of the call while the first
+  // boxes' X paths run; those boxes' a2 waits for `ready` and takes modp_launch_call_rows_dual_exp: half of the
+  // squarings under y^r and no window table of y per box.  One buffer per context, kept between calls (hipMalloc of gigabytes has
+  // been measured at up to 1 s), owned by one call at a time (`in_use`); a call that finds it taken goes the plain way.
+  struct CallTables {
+    void* buf = nullptr;           // [n][2][64][72] words
+    size_t cap = 0;
+    hipStream_t stream = nullptr;
+    hipEvent_t ready = nullptr;
+    bool in_use = false;
+    unsigned long long builds = 0, boxes_served = 0;
+    void drop() {
+      if (buf) (void)hipFree(buf);
+      buf = nullptr;
+      cap = 0;
+    }
+  } ct;
+  int call_tables_min = 3;       // 0: off
   int key_cache_min_boxes = 0;   // mpvss_ctx_set_key_cache: verify_many registers key arrays that this many large boxes of a call share (0: off)
   // Key tables ACROSS calls (mpvss_ctx_set_key_cache_lru): the one-box entry point looks the SHA-256 of a host key array up here; an
   // array seen `kc_min_sightings` times gets its tables built once and every later box against it takes the registered-key path.
@@ -387,6 +406,11 @@ int ensure(mpvss_ctx* ctx, DevBuf& b, size_t bytes) {
   if (e != hipSuccess && ctx->spare_table) {      // the key caches' spare table buffer gives way to a workspace
     (void)hipGetLastError();
     ctx->drop_spare_table();
+    e = hipMalloc(&b.p, bytes);
+  }
+  if (e != hipSuccess && ctx->ct.buf && !ctx->ct.in_use) {      // so do the call tables, unless a call is using them
+    (void)hipGetLastError();
+    ctx->ct.drop();
     e = hipMalloc(&b.p, bytes);
   }
   if (e != hipSuccess) {
@@ -788,6 +812,10 @@ extern "C" int mpvss_ctx_create(int device_id, mpvss_ctx** out) {
   }
   ctx->stream_b = ctx->work0.sb;
   ctx->pipelined_env = fd_env("MPVSS_PIPELINED", 0) != 0;
+  {
+    const int m = fd_env("MPVSS_CALL_TABLES", 3);      // 0: off for the process; >= 2: the threshold
+    ctx->call_tables_min = m >= 2 ? m : (m == 0 ? 0 : 3);
+  }
   *out = ctx;
   return MPVSS_OK;
 }
@@ -843,6 +871,9 @@ extern "C" void mpvss_ctx_destroy(mpvss_ctx* ctx) {
     delete d;
   }
   ctx->drop_spare_table();
+  ctx->ct.drop();
+  if (ctx->ct.stream) { (void)hipStreamSynchronize(ctx->ct.stream); (void)hipStreamDestroy(ctx->ct.stream); }
+  if (ctx->ct.ready) (void)hipEventDestroy(ctx->ct.ready);
   for (hipEvent_t e : ctx->main_spans.ev_pool) (void)hipEventDestroy(e);
   for (auto& sl : ctx->slot) {
     if (sl.pin) (void)hipHostFree(sl.pin);
@@ -1422,6 +1453,9 @@ int fork_side_stream(mpvss_ctx* ctx, hipEvent_t ev_fork, hipStream_t side) {
   HIPCHK(ctx, hipStreamWaitEvent(side, ev_fork, 0));
   return 0;
 }
+// the call tables a box of a verify_many call may use (mpvss_ctx::CallTables, filled by CallTablesUse below)
+struct CallRowsRef { const uint32_t* rows = nullptr; hipEvent_t ready = nullptr; };
+
 struct SwapStream {
   mpvss_ctx* c; hipStream_t a;
   SwapStream(mpvss_ctx* c_, hipStream_t s) : c(c_), a(c_->stream) { c->stream = s; }
@@ -1760,7 +1794,9 @@ int verify_block_compute_locked(mpvss_ctx* ctx, int space, const uint8_t* commit
                                 const int64_t* positions, const uint8_t* pubkeys, const uint8_t* shares,
                                 const uint8_t* responses, size_t n, const uint8_t* challenge_host,
                                 const mpvss_keyset* ks = nullptr, size_t key_offset = 0, uint8_t* wf_dev_out = nullptr,
-                                const uint8_t* prestaged = nullptr) {
+                                const uint8_t* prestaged = nullptr, const CallRowsRef* call_rows = nullptr) {
+  // call_rows: the rows of this box's keys are being built for the call (their event: `ready`); a one-chunk box with a 256-bit
+  // challenge takes its a2 from them
   // prestaged (space == MPVSS_HOST only): PINNED memory that already holds pubkeys | shares | responses (n x 256 each) | commitments
   // (t x 256) and stays valid until the block is absorbed: the inputs are not copied again
   if (!challenge_host) return fail(ctx, MPVSS_E_INVALID, "verify: null challenge");
@@ -1880,11 +1916,16 @@ int verify_block_compute_locked(mpvss_ctx* ctx, int space, const uint8_t* commit
       // The forward-difference X path is a chain of latency-bound launches that occupy few wave slots (seeds,
       // inversion tree, difference tables, stepping) and runs on the block slot's high-priority stream.  a2 = y^r Y^c
       // and g^r do not depend on X: they run beside it on the slot's low-priority stream.
-      RET_IF(ensure(ctx, ctx->w->tab1, cnt * TABW * 4 * 4));     // no reallocation while two streams are live
+      const bool use_keys = ks && c_windows == 64;
+      // (a challenge of 0 has no sliding-window schedule: such a box keeps the plain kernels, and its tab1 is allocated here, in
+      //  front of the fork, like everybody's)
+      bool c_nonzero = false;
+      for (size_t i = 0; i < EB; ++i) c_nonzero = c_nonzero || challenge_host[i] != 0;
+      const bool rows_ok = call_rows && !use_keys && c_windows == 64 && c_nonzero && (pair_mask() & 1) && n <= MAX_CHUNK;
+      if (!rows_ok) RET_IF(ensure(ctx, ctx->w->tab1, cnt * TABW * 4 * 4));     // no reallocation while two streams are live
       RET_IF(ensure(ctx, ctx->w->tab2, cnt * TABW * 4));
       RET_IF(ensure(ctx, ctx->w->tab3, cnt * TABW * 4));
       RET_IF(ensure(ctx, ctx->w->gr_m, cnt * MODP_L * 4));
-      const bool use_keys = ks && c_windows == 64;
       RET_IF(fork_side_stream(ctx, ctx->w->ev_fork, ctx->w->sb));
       // Boxes in flight share the chip equally: eight boxes enqueued together finish together (a convoy).  What that
       // costs is the host's turn-around at the end of a convoy, and the cure that works is to enqueue the next box as
@@ -1929,6 +1970,12 @@ int verify_block_compute_locked(mpvss_ctx* ctx, int space, const uint8_t* commit
           else
             TIMED_LAUNCH(ctx, 3, modp_launch_keyset_dual_exp(kt, t2p, (const uint8_t*)dr, (const uint8_t*)dchal, (int)cnt, da2,
                                                              ctx->consts, ctx->stream));
+        } else if (rows_ok) {
+          // the call's rows of these keys: no window table of y, half of the squarings; the build runs on the call's own stream
+          HIPCHK(ctx, hipStreamWaitEvent(ctx->stream, call_rows->ready, 0));
+          TIMED_LAUNCH(ctx, 3, modp_launch_call_rows_dual_exp(call_rows->rows, t2p, (const uint8_t*)dr, (const uint8_t*)dchal, 0,
+                                                              dsched, (int)cnt, da2, ctx->consts, ctx->pair_tables, ctx->stream));
+          ++ctx->ct.boxes_served;
         } else if (c_windows == 64) {
           // 6-bit windows for y^r (64-entry tables, 18 KB per share): 341 products instead of 511
           uint32_t* t1p = (uint32_t*)ctx->w->tab1.p;
@@ -1980,8 +2027,18 @@ int verify_block_compute_locked(mpvss_ctx* ctx, int space, const uint8_t* commit
       RET_IF(fork_side_stream(ctx, ctx->w->ev_fork, ctx->w->sb));
       {
         SwapStream sw(ctx, ctx->w->sb);
-        RET_IF(dleq_side(ctx, nullptr, (const uint8_t*)dy, (const uint8_t*)dY, (const uint8_t*)dr, (const uint8_t*)dchal,
-                         0, c_windows, cnt, da2));
+        if (call_rows && !ks && c_windows == 64 && (pair_mask() & 1) && n <= MAX_CHUNK) {
+          // the call's rows of these keys (see above); Y^c by the fixed nibbles of c against Y's full table, as dleq_side has it
+          const uint32_t* t2;
+          RET_IF(number_tables(ctx, (const uint8_t*)dY, cnt, ctx->w->tab2, &t2));
+          HIPCHK(ctx, hipStreamWaitEvent(ctx->stream, call_rows->ready, 0));
+          TIMED_LAUNCH(ctx, 3, modp_launch_call_rows_dual_exp(call_rows->rows, t2, (const uint8_t*)dr, (const uint8_t*)dchal, 0,
+                                                              nullptr, (int)cnt, da2, ctx->consts, ctx->pair_tables, ctx->stream));
+          ++ctx->ct.boxes_served;
+        } else {
+          RET_IF(dleq_side(ctx, nullptr, (const uint8_t*)dy, (const uint8_t*)dY, (const uint8_t*)dr, (const uint8_t*)dchal,
+                           0, c_windows, cnt, da2));
+        }
         HIPCHK(ctx, hipEventRecord(ctx->w->ev_a2, ctx->stream));
       }
       RET_IF(eval_x(ctx, t, dpos, hp, cnt, dX, 1, 0, false, small_direct));
@@ -2801,7 +2858,121 @@ int run_box_pipeline(mpvss_ctx* ctx, size_t count, int depth, int hash_threads, 
   return sh.rc;
 }
 
+// ---- call tables: per-key rows shared by the boxes of one call --------------------------------------------------------------
+// The boxes of one verify_many call are different dealers' boxes for the same participants: "same pubkeys pointer, same n" inside one
+// call is the same array.  The first array that at least call_tables_min large boxes present (boxes without a key set, not taken by
+// the key cache, GROUP_MAX_BOX < n <= MAX_CHUNK) gets its rows built ONCE, on the context's low-priority call-table stream; nothing
+// waits on the host: the boxes' X paths start at once and each served box's a2 launch waits for the build's event on the device.
+// Whatever goes wrong (no room in HBM, the buffer in another call's hands, a failed launch) costs speed, not the call, and leaves
+// the context's error string alone: nothing here calls fail().  The buffer is released for the next call by the destructor -- the
+// pipeline has absorbed every block of the call by then (their `done` events have been waited for), so nothing reads the rows.
+struct CallTablesUse {
+  mpvss_ctx* ctx;
+  bool mine = false;
+  unsigned long long served0 = 0;      // the context's boxes_served when this call took the buffer
+  CallRowsRef ref;
+  std::vector<char> serves;
+  CallTablesUse(mpvss_ctx* c, int space, const mpvss_modp_box* boxes, size_t count, int depth,
+                const std::vector<const mpvss_keyset*>* taken = nullptr)
+      : ctx(c), serves(count, 0) {
+    const int min_boxes = [&] {      // read once; the buffer's ownership is decided under the lock further down
+      std::lock_guard<std::mutex> lk(ctx->mu);
+      return ctx->ct.in_use ? 0 : ctx->call_tables_min;
+    }();
+    if (min_boxes < 2 || (size_t)min_boxes > count) return;
+    // (device-resident keys only: the build reads the caller's array where it lies.  For host memory it would need a copy of the
+    //  keys of its own in front of the call -- a host-side wait the boxes' X paths would start behind; such calls go the plain way.)
+    if (space != MPVSS_DEVICE || !(pair_mask() & 1)) return;
+    const mpvss_modp_box* first = nullptr;
+    std::vector<char> seen(count, 0);
+    for (size_t b = 0; b < count && !first; ++b) {
+      const mpvss_modp_box& bx = boxes[b];
+      auto plain = [&](size_t k) { return !boxes[k].keyset && !(taken && (*taken)[k]); };
+      if (seen[b] || !plain(b) || !bx.pubkeys || bx.n <= GROUP_MAX_BOX || bx.n > MAX_CHUNK) continue;
+      size_t same = 0;
+      for (size_t k = b; k < count; ++k)
+        if (plain(k) && boxes[k].pubkeys == bx.pubkeys && boxes[k].n == bx.n) { seen[k] = 1; ++same; }
+      if (same < (size_t)min_boxes) continue;
+      first = &bx;
+      for (size_t k = b; k < count; ++k) serves[k] = plain(k) && boxes[k].pubkeys == bx.pubkeys && boxes[k].n == bx.n;
+    }
+    if (!first) return;
+    const size_t n = first->n, need = n * modp_call_rows_words_per_key() * 4;
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    mpvss_ctx::CallTables& ct = ctx->ct;
+    if (ct.in_use || ctx->call_tables_min < 2) return;      // taken, or switched off, since the scan
+    auto give_up = [&] { (void)hipGetLastError(); };
+    if (hipSetDevice(ctx->device) != hipSuccess) { give_up(); return; }
+    if (ct.cap < need) {
+      // leave the block slots' workspaces their room: what is free (with the buffer that goes) must cover the rows and 3 GB per box in flight
+      size_t free_b = 0, total_b = 0;
+      if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) { give_up(); return; }
+      free_b += ct.cap;
+      const size_t reserve_b = ((size_t)3 << 30) * (size_t)std::max(1, std::min(depth, (int)mpvss_ctx::NSLOT));
+      if (free_b < need || free_b - need < reserve_b) return;
+      ct.drop();
+      if (hipMalloc(&ct.buf, need) != hipSuccess) { ct.buf = nullptr; { give_up(); return; } }
+      ct.cap = need;
+    }
+    if (!ct.stream && hipStreamCreateWithPriority(&ct.stream, hipStreamNonBlocking, ctx->prio_low) != hipSuccess) {
+      ct.stream = nullptr;
+      { give_up(); return; }
+    }
+    if (!ct.ready && hipEventCreateWithFlags(&ct.ready, hipEventDisableTiming) != hipSuccess) {
+      ct.ready = nullptr;
+      { give_up(); return; }
+    }
+    if (modp_launch_call_rows_build(first->pubkeys, (int)n, (uint32_t*)ct.buf, ctx->consts, ctx->pair_tables, ct.stream) != 0 ||
+        hipEventRecord(ct.ready, ct.stream) != hipSuccess)
+      { give_up(); return; }
+    ct.in_use = true;
+    ++ct.builds;
+    mine = true;
+    ref.rows = (const uint32_t*)ct.buf;
+    ref.ready = ct.ready;
+    served0 = ct.boxes_served;
+  }
+  ~CallTablesUse() {
+    if (!mine) return;
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    mpvss_ctx::CallTables& ct = ctx->ct;
+    // a served box's block has been absorbed, so the build it waited for is done; if NO box took the rows (every candidate had a wide
+    // challenge, or the call ended early) the build may still be reading the caller's key array: wait for it before the call returns
+    if (ct.boxes_served == served0) {
+      (void)hipSetDevice(ctx->device);
+      if (hipEventSynchronize(ct.ready) != hipSuccess) (void)hipGetLastError();
+    }
+    ct.in_use = false;
+    if (ctx->call_tables_min == 0) {      // switched off while this call held the rows: the buffer goes now
+      (void)hipSetDevice(ctx->device);
+      ct.drop();
+    }
+  }
+  const CallRowsRef* of(size_t b) const { return mine && serves[b] ? &ref : nullptr; }
+};
+
 }  // namespace
+
+extern "C" int mpvss_ctx_set_call_tables(mpvss_ctx* ctx, int min_boxes) {
+  if (!ctx) return MPVSS_E_INVALID;
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  if (min_boxes < 0 || min_boxes == 1) return fail(ctx, MPVSS_E_INVALID, "set_call_tables: min_boxes must be 0 (off) or >= 2");
+  const int prev = ctx->call_tables_min;
+  ctx->call_tables_min = min_boxes;
+  if (min_boxes == 0 && !ctx->ct.in_use) {      // off: the buffer goes too (a call that still uses it frees it when it returns)
+    (void)hipSetDevice(ctx->device);
+    ctx->ct.drop();
+  }
+  return prev;
+}
+
+extern "C" int mpvss_call_tables_stats(mpvss_ctx* ctx, unsigned long long* builds_out, unsigned long long* boxes_served_out) {
+  if (!ctx) return MPVSS_E_INVALID;
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  if (builds_out) *builds_out = ctx->ct.builds;
+  if (boxes_served_out) *boxes_served_out = ctx->ct.boxes_served;
+  return MPVSS_OK;
+}
 
 extern "C" int mpvss_modp_verify_many(mpvss_ctx* ctx, int space, const mpvss_modp_box* boxes, size_t count, int depth,
                                       int hash_threads, int* verdicts, uint8_t* digests32) {
@@ -2858,6 +3029,7 @@ extern "C" int mpvss_modp_verify_many(mpvss_ctx* ctx, int space, const mpvss_mod
       for (size_t k : same) auto_ks[k] = ks;
     }
   }
+  CallTablesUse call_tables(ctx, space, boxes, count, depth, &auto_ks);      // (released after the pipeline has absorbed every block)
   return run_box_pipeline(
       ctx, count, depth, hash_threads,
       [&](size_t b, unsigned* nbox) {
@@ -2876,7 +3048,8 @@ extern "C" int mpvss_modp_verify_many(mpvss_ctx* ctx, int space, const mpvss_mod
         }
         const mpvss_keyset* use_ks = bx.keyset ? bx.keyset : auto_ks[b];
         return verify_block_compute_locked(ctx, space, bx.commitments, bx.t, bx.positions, bx.pubkeys, bx.shares, bx.responses, bx.n,
-                                           bx.challenge_host, use_ks, bx.keyset ? bx.key_offset : 0);
+                                           bx.challenge_host, use_ks, bx.keyset ? bx.key_offset : 0, nullptr, nullptr,
+                                           use_ks ? nullptr : call_tables.of(b));
       },
       [&](size_t idx, const uint8_t* state) {
         return mpvss_modp_transcript_verdict(state, boxes[idx].challenge_host, &verdicts[idx],
@@ -2905,6 +3078,7 @@ extern "C" int mpvss_modp_verify_many_chained(mpvss_ctx* ctx, int space, const m
   }
   for (size_t i = 0; i < count; ++i) verdicts[i] = 0;
   if (digests32) memset(digests32, 0, 32 * count);
+  CallTablesUse call_tables(ctx, space, boxes, count, depth);
   return run_box_pipeline(
       ctx, count, depth, hash_threads,
       [&](size_t b, unsigned* nbox) {
@@ -2912,7 +3086,8 @@ extern "C" int mpvss_modp_verify_many_chained(mpvss_ctx* ctx, int space, const m
         *nbox = 1;
         return verify_block_compute_locked(ctx, space, bx.commitments, bx.t, bx.positions, bx.pubkeys, bx.shares, bx.responses,
                                            bx.n, bx.challenge_host, bx.keyset, bx.key_offset,
-                                           wellformed_dev_out ? wellformed_dev_out[b] : nullptr);
+                                           wellformed_dev_out ? wellformed_dev_out[b] : nullptr, nullptr,
+                                           bx.keyset ? nullptr : call_tables.of(b));
       },
       [&](size_t idx, const uint8_t* state) {
         if (state_out) {
