@@ -605,6 +605,17 @@ int mpvss_modp_group_prepare(mpvss_ctx* ctx, const mpvss_modp_group* grp);
 int mpvss_modp_group_comb_min_shares(const mpvss_modp_group* grp);
 /* comb cache of the context since it was created: tables built, uses of a cached table, tables evicted (any pointer may be null) */
 int mpvss_modp_group_comb_stats(mpvss_ctx* ctx, unsigned long long* builds, unsigned long long* hits, unsigned long long* evictions);
+/* Forward differences in the exponent for X_i of a run-time group (commit_eval, verify_distribution, distribute with commitments):
+ * t - 1 products per share instead of Horner's rule, taken per chunk when the positions are consecutive from p0 >= 0 and all below
+ * q - 1, every commitment is a unit mod q, 2 <= t <= fd_max_t and the chunk has at least fd_min_shares(t) shares.  The results
+ * are the same bytes either way.  mode 0: off; 1: automatic (the default); 2: whenever admissible, whatever fd_min_shares says.
+ * chains 0: automatic; another value is clamped so that every chain holds at least t positions. */
+int mpvss_ctx_set_rt_fd(mpvss_ctx* ctx, int mode, int chains);
+/* the chunk size from which mode 1 takes forward differences at this t, and the largest t they serve.  Host only. */
+int mpvss_modp_group_fd_min_shares(const mpvss_modp_group* grp, size_t t);
+int mpvss_modp_group_fd_max_t(const mpvss_modp_group* grp);
+/* chunks of X_i computed by forward differences and by Horner's rule since the context was created (either pointer may be null) */
+int mpvss_modp_group_fd_stats(mpvss_ctx* ctx, unsigned long long* fd_calls, unsigned long long* horner_calls);
 /* dealer's group side, src/participant.rs:160-286 with p_i = P(i) mod (q-1) and the witnesses as input: same contract as
  * mpvss_modp_distribute */
 int mpvss_modp_group_distribute(mpvss_ctx* ctx, const mpvss_modp_group* grp, int space, const uint8_t* commitments, size_t t,

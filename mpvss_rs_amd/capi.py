@@ -55,6 +55,7 @@ EXPORTED_SYMBOLS = (
     "mpvss_modp_group_poly_eval", "mpvss_modp_group_twin_min_shares",
     "mpvss_modp_group_batch_exp_fixed_base", "mpvss_modp_group_prepare", "mpvss_modp_group_comb_min_shares",
     "mpvss_modp_group_comb_stats", "mpvss_modp_group_create_wide", "mpvss_modp_group_elem_bytes",
+    "mpvss_ctx_set_rt_fd", "mpvss_modp_group_fd_min_shares", "mpvss_modp_group_fd_max_t", "mpvss_modp_group_fd_stats",
 )
 
 GROUP_SECP256K1 = 1
@@ -242,6 +243,10 @@ def load_library() -> C.CDLL:
     lib.mpvss_modp_group_prepare.argtypes = [vp, vp]
     lib.mpvss_modp_group_comb_min_shares.argtypes = [vp]
     lib.mpvss_modp_group_comb_stats.argtypes = [vp, C.POINTER(C.c_ulonglong), C.POINTER(C.c_ulonglong), C.POINTER(C.c_ulonglong)]
+    lib.mpvss_ctx_set_rt_fd.argtypes = [vp, ci, ci]
+    lib.mpvss_modp_group_fd_min_shares.argtypes = [vp, C.c_size_t]
+    lib.mpvss_modp_group_fd_max_t.argtypes = [vp]
+    lib.mpvss_modp_group_fd_stats.argtypes = [vp, C.POINTER(C.c_ulonglong), C.POINTER(C.c_ulonglong)]
     return lib
 
 
@@ -301,6 +306,15 @@ class ModpGroup:
     def comb_min_shares(self) -> int:
         """batch size from which a call builds the fixed-base comb of a shared base the context has not cached"""
         return self.lib.mpvss_modp_group_comb_min_shares(self.handle)
+
+    @property
+    def fd_max_t(self) -> int:
+        """largest t for which X_i can go by forward differences at this group's width"""
+        return self.lib.mpvss_modp_group_fd_max_t(self.handle)
+
+    def fd_min_shares(self, t: int) -> int:
+        """chunk size from which the automatic mode takes forward differences at this t"""
+        return self.lib.mpvss_modp_group_fd_min_shares(self.handle, int(t))
 
     def hash_to_scalar(self, data: bytes) -> bytes:
         EB = self.elem_bytes
@@ -469,6 +483,17 @@ class Engine:
         b, h, e = C.c_ulonglong(0), C.c_ulonglong(0), C.c_ulonglong(0)
         self._check(self.lib.mpvss_modp_group_comb_stats(self.ctx, C.byref(b), C.byref(h), C.byref(e)), "group_comb_stats")
         return {"builds": int(b.value), "hits": int(h.value), "evictions": int(e.value)}
+
+    def set_rt_fd(self, mode: int, chains: int = 0) -> None:
+        """mpvss_ctx_set_rt_fd: forward differences for X_i of run-time groups -- 0 off, 1 automatic, 2 whenever admissible;
+        chains 0 = automatic"""
+        self._check(self.lib.mpvss_ctx_set_rt_fd(self.ctx, int(mode), int(chains)), "set_rt_fd")
+
+    def group_fd_stats(self) -> dict:
+        """chunks of X_i this context computed by forward differences and by Horner's rule"""
+        f, h = C.c_ulonglong(0), C.c_ulonglong(0)
+        self._check(self.lib.mpvss_modp_group_fd_stats(self.ctx, C.byref(f), C.byref(h)), "group_fd_stats")
+        return {"fd": int(f.value), "horner": int(h.value)}
 
     def group_batch_mul(self, grp: "ModpGroup", a: bytes, b: bytes) -> bytes:
         EB = grp.elem_bytes

@@ -193,22 +193,144 @@ int rt_dleq_dev(mpvss_ctx* ctx, const mpvss_modp_group* grp, const modp_rt_const
   return 0;
 }
 
-// X_i of cnt shares (commitments already in ctx->rt_cm, Montgomery form)
+// ---- X_i: Horner's rule, or forward differences in the exponent (DESIGN section 13, "Forward differences") ---------------------
+// Chains a call of n consecutive positions is cut into, and the batch size (shares of one call, or of one chunk) from which
+// mode 1 takes forward differences.  Both come from `tools/modp_rt_rate.py --fd --ab` (profiles/modp_rt_fd_rate.txt).
+// Seeds cost 2 S t Horner evaluations at low occupancy, a chain 3 (t - 1) product latencies of set-up and n / (2 S) of
+// stepping per direction: more chains shorten the stepping until the seeds fill the chip.
+int rt_fd_chains(int, size_t n, size_t t) {
+  const size_t s = n / (4 * t);
+  return (int)(s < 1 ? 1 : s > 32 ? 32 : s);
+}
+size_t rt_fd_min_shares(int, size_t t) { return std::max<size_t>(16384, 8 * t); }
+// mode 1 of mpvss_ctx_set_rt_fd.  The gate of the forward differences (at most half of Horner's time at (65 536, 256) and 2048
+// bits) is judged in DESIGN section 13 from profiles/modp_rt_fd_rate.txt; until it is met "automatic" means Horner.
+constexpr bool RT_FD_AUTO_ON = false;
+
+// Once per call, after rt_stage_commitments: the inverted commitments in Montgomery form (ctx->rt_cm_inv), by Montgomery's
+// trick on the host -- one inversion mod q and 3 (t - 1) products.  Leaves ctx->rt_fd_ready false, and the call with Horner,
+// when the mode, t, the call's size or a commitment that is no unit mod q rules forward differences out.
+int rt_fd_prepare(mpvss_ctx* ctx, const mpvss_modp_group* grp, const modp_rt_consts* dc, int space, const uint8_t* commitments,
+                  size_t t, size_t n) {
+  ctx->rt_fd_ready = false;
+  const int mode = ctx->rt_fd_mode;
+  const size_t most = std::min(n, MAX_CHUNK), EB = grp->eb;
+  if (mode == 0 || (mode == 1 && !RT_FD_AUTO_ON) || t < 2 || t > (size_t)modp_rt_fd_max_t(grp->lpl) || most < t) return 0;
+  if (mode == 1 && most < rt_fd_min_shares(grp->lpl, t)) return 0;
+  std::vector<uint8_t> back;
+  const uint8_t* C = commitments;
+  if (space == MPVSS_DEVICE) {
+    back.resize(t * EB);
+    HIPCHK(ctx, hipMemcpyAsync(back.data(), commitments, t * EB, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    C = back.data();
+  }
+  ctx->rt_fd_inv_host.resize(t * EB);
+  uint8_t* inv = ctx->rt_fd_inv_host.data();
+  const bool units = rt_rings(grp, [&](const auto& R) {
+    constexpr int NW = RT_NW(R);
+    std::vector<uint64_t> v(t * NW), pre(t * NW);
+    for (size_t j = 0; j < t; ++j) {
+      hsc::from_bytes<NW>(&v[j * NW], C + j * EB, true);
+      R.mod.reduce1(&v[j * NW]);
+      if (j == 0) memcpy(&pre[0], &v[0], NW * 8);
+      else R.mod.mulmod(&pre[j * NW], &pre[(j - 1) * NW], &v[j * NW]);
+    }
+    uint64_t run[NW], x[NW];
+    if (!R.mod.invert(run, &pre[(t - 1) * NW])) return false;      // some commitment is 0 or shares a factor with q
+    for (size_t j = t - 1; j > 0; --j) {
+      R.mod.mulmod(x, run, &pre[(j - 1) * NW]);
+      hsc::to_bytes<NW>(inv + j * EB, x, true);
+      R.mod.mulmod(run, run, &v[j * NW]);
+    }
+    hsc::to_bytes<NW>(inv, run, true);
+    return true;
+  });
+  if (!units) return 0;
+  RET_IF(ensure(ctx, ctx->rt_fd_inv, t * EB));
+  HIPCHK(ctx, hipMemcpyAsync(ctx->rt_fd_inv.p, inv, t * EB, hipMemcpyHostToDevice, ctx->stream));
+  RET_IF(ensure(ctx, ctx->rt_cm_inv, t * rt_L(grp) * 4));
+  LAUNCHCHK(ctx, modp_rt_launch_to_mont(grp->lpl, (const uint8_t*)ctx->rt_fd_inv.p, (int)t, (uint32_t*)ctx->rt_cm_inv.p, dc, ctx->stream));
+  ctx->rt_fd_ready = true;
+  return 0;
+}
+
+// The admissibility of one chunk, on the host: cnt positions (in `space`) that are p0, p0 + 1, .. with p0 >= 0, all of them below
+// q - 1 when that fits 64 bits (Horner reduces a position mod q - 1, forward differences use it as an integer).
+int rt_fd_positions_ok(mpvss_ctx* ctx, const mpvss_modp_group* grp, int space, const int64_t* positions, size_t cnt, bool* ok,
+                       int64_t* p0_out) {
+  *ok = false;
+  std::vector<int64_t> back;
+  const int64_t* P = positions;
+  if (space == MPVSS_DEVICE) {
+    back.resize(cnt);
+    HIPCHK(ctx, hipMemcpyAsync(back.data(), positions, cnt * 8, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    P = back.data();
+  }
+  const int64_t p0 = P[0];
+  if (p0 < 0 || p0 > INT64_MAX - (int64_t)(cnt - 1)) return 0;
+  for (size_t i = 1; i < cnt; ++i)
+    if (P[i] != p0 + (int64_t)i) return 0;
+  const uint64_t qm1 = ((uint64_t)grp->c.qm1_hi << 32) | grp->c.qm1_lo;
+  if (qm1 != 0 && (uint64_t)p0 + (cnt - 1) >= qm1) return 0;
+  *p0_out = p0;
+  *ok = true;
+  return 0;
+}
+
+// X_i of cnt shares (commitments already in ctx->rt_cm, Montgomery form; `positions`: the chunk's positions as the caller
+// gave them, in `space`).  THE launch decision of the X path, on the host before anything is launched: forward differences
+// when the call has inverted commitments (rt_fd_prepare), the chunk is large enough for its mode and its positions are
+// admissible; otherwise k_rt_commit_eval.  Under these conditions the recurrences are integer identities in the exponent,
+// so both paths give the same bytes.
 int rt_commit_eval_dev(mpvss_ctx* ctx, const mpvss_modp_group* grp, const modp_rt_consts* dc, size_t t, const int64_t* pos_dev,
-                       size_t cnt, uint8_t* x_dev) {
-  TIMED_LAUNCH(ctx, 0, modp_rt_launch_commit_eval(grp->lpl, (const uint32_t*)ctx->rt_cm.p, (int)t, pos_dev, (int)cnt, x_dev, dc,
-                                                  ctx->stream));
+                       size_t cnt, uint8_t* x_dev, int space, const int64_t* positions) {
+  const size_t LW = rt_L(grp);
+  bool fd = ctx->rt_fd_ready && cnt >= t && (ctx->rt_fd_mode == 2 || cnt >= rt_fd_min_shares(grp->lpl, t)) &&
+            cnt * LW * 4 <= ((size_t)1 << 30);               // X in limbs stays a workspace of at most 1 GiB
+  int64_t p0 = 0;
+  if (fd) RET_IF(rt_fd_positions_ok(ctx, grp, space, positions, cnt, &fd, &p0));
+  if (!fd) {
+    ++ctx->rt_horner_calls;
+    TIMED_LAUNCH(ctx, 0, modp_rt_launch_commit_eval(grp->lpl, (const uint32_t*)ctx->rt_cm.p, (int)t, pos_dev, (int)cnt, x_dev, dc,
+                                                    ctx->stream));
+    return 0;
+  }
+  ++ctx->rt_fd_calls;
+  size_t S = ctx->rt_fd_chains > 0 ? (size_t)ctx->rt_fd_chains : (size_t)rt_fd_chains(grp->lpl, cnt, t);
+  S = std::max<size_t>(1, std::min(S, cnt / t));             // every chain holds at least t positions
+  std::vector<int64_t>& sp = ctx->rt_fd_pos_host;
+  sp.resize(S * t);
+  for (size_t c = 0; c < S; ++c) {
+    int first, len;
+    modp_rt_fd_chain((int)cnt, (int)S, (int)c, &first, &len);
+    for (size_t k = 0; k < t; ++k) sp[c * t + k] = p0 + first + (len - (int)t) / 2 + (int64_t)k;
+  }
+  RET_IF(ensure(ctx, ctx->rt_fd_pos, S * t * 8));
+  RET_IF(ensure(ctx, ctx->rt_fd_seeds, 2 * S * t * LW * 4));
+  RET_IF(ensure(ctx, ctx->rt_fd_x, cnt * LW * 4));
+  RET_IF(ensure(ctx, ctx->rt_fd_park, modp_rt_fd_park_bytes(grp->lpl, (int)t, (int)S)));
+  HIPCHK(ctx, hipMemcpyAsync(ctx->rt_fd_pos.p, sp.data(), S * t * 8, hipMemcpyHostToDevice, ctx->stream));
+  uint32_t* seeds = (uint32_t*)ctx->rt_fd_seeds.p;
+  uint32_t* xm = (uint32_t*)ctx->rt_fd_x.p;
+  RET_IF(span_begin(ctx, 0));
+  LAUNCHCHK(ctx, modp_rt_launch_commit_eval_mont(grp->lpl, (const uint32_t*)ctx->rt_cm.p, (const uint32_t*)ctx->rt_cm_inv.p, (int)t,
+                                                 (const int64_t*)ctx->rt_fd_pos.p, (int)(S * t), seeds, dc, ctx->stream));
+  LAUNCHCHK(ctx, modp_rt_launch_fd_chains(grp->lpl, seeds, (int)t, (int)cnt, (int)S, xm, (uint32_t*)ctx->rt_fd_park.p, dc, ctx->stream));
+  LAUNCHCHK(ctx, modp_rt_launch_from_mont(grp->lpl, xm, (int)cnt, x_dev, dc, ctx->stream));
+  RET_IF(span_end(ctx));
   return 0;
 }
 
 int rt_stage_commitments(mpvss_ctx* ctx, const mpvss_modp_group* grp, const modp_rt_consts* dc, int space, const uint8_t* commitments,
-                         size_t t) {
+                         size_t t, size_t n) {
   const size_t EB = grp->eb;
   const void* dcm;
   RET_IF(stage_in(ctx, space, commitments, t * EB, ctx->rt_in[4], &dcm));
   RET_IF(ensure(ctx, ctx->rt_cm, t * rt_L(grp) * 4));
   LAUNCHCHK(ctx, modp_rt_launch_to_mont(grp->lpl, (const uint8_t*)dcm, (int)t, (uint32_t*)ctx->rt_cm.p, dc, ctx->stream));
-  return 0;
+  return rt_fd_prepare(ctx, grp, dc, space, commitments, t, n);
 }
 
 // hash_to_scalar of the group: int(SHA-256(data)) mod (q-1)/2, big-endian at the handle's element size
@@ -424,7 +546,7 @@ extern "C" int mpvss_modp_group_commit_eval(mpvss_ctx* ctx, const mpvss_modp_gro
   spans_reset(ctx);
   const modp_rt_consts* dc;
   RET_IF(rt_upload(ctx, grp, &dc));
-  RET_IF(rt_stage_commitments(ctx, grp, dc, space, commitments, t));
+  RET_IF(rt_stage_commitments(ctx, grp, dc, space, commitments, t, n));
   const int64_t* dpos;
   RET_IF(stage_positions(ctx, space, positions, n, &dpos));
   uint8_t* dout = x_out;
@@ -432,7 +554,7 @@ extern "C" int mpvss_modp_group_commit_eval(mpvss_ctx* ctx, const mpvss_modp_gro
     RET_IF(ensure(ctx, ctx->rt_out[0], n * EB));
     dout = (uint8_t*)ctx->rt_out[0].p;
   }
-  RET_IF(rt_commit_eval_dev(ctx, grp, dc, t, dpos, n, dout));
+  RET_IF(rt_commit_eval_dev(ctx, grp, dc, t, dpos, n, dout, space, positions));
   if (space == MPVSS_HOST) RET_IF(copy_out(ctx, space, x_out, dout, n * EB));
   RET_IF(spans_collect(ctx));
   return MPVSS_OK;
@@ -501,7 +623,7 @@ extern "C" int mpvss_modp_group_verify_distribution(mpvss_ctx* ctx, const mpvss_
     spans_reset(ctx);
     const modp_rt_consts* dc;
     RET_IF(rt_upload(ctx, grp, &dc));
-    RET_IF(rt_stage_commitments(ctx, grp, dc, space, commitments, t));
+    RET_IF(rt_stage_commitments(ctx, grp, dc, space, commitments, t, n));
     const uint8_t* dch;
     RET_IF(rt_stage_small(ctx, grp, challenge_host, ctx->rt_small[1], &dch));
     const size_t chunk = std::min(n, MAX_CHUNK);
@@ -518,7 +640,7 @@ extern "C" int mpvss_modp_group_verify_distribution(mpvss_ctx* ctx, const mpvss_
       uint8_t* dX = (uint8_t*)ctx->rt_out[0].p;
       uint8_t* d1 = (uint8_t*)ctx->rt_out[1].p;
       uint8_t* d2 = (uint8_t*)ctx->rt_out[2].p;
-      RET_IF(rt_commit_eval_dev(ctx, grp, dc, t, dpos, cnt, dX));
+      RET_IF(rt_commit_eval_dev(ctx, grp, dc, t, dpos, cnt, dX, space, positions + off));
       // a1 = g^r X^c, a2 = y^r Y^c (src/participant.rs:436-447 -> src/dleq.rs:66-84)
       RET_IF(rt_dleq_dev(ctx, grp, dc, grp->g_be, dX, (const uint8_t*)dy, (const uint8_t*)dY, (const uint8_t*)dr, dch, 0, cnt, d1, d2));
       HIPCHK(ctx, hipMemcpyAsync(hX.data(), dX, cnt * EB, hipMemcpyDeviceToHost, ctx->stream));
@@ -748,7 +870,7 @@ int rt_distribute_locked(mpvss_ctx* ctx, const mpvss_modp_group* grp, int space,
     spans_reset(ctx);
     const modp_rt_consts* dc;
     RET_IF(rt_upload(ctx, grp, &dc));
-    if (commitments) RET_IF(rt_stage_commitments(ctx, grp, dc, space, commitments, t));
+    if (commitments) RET_IF(rt_stage_commitments(ctx, grp, dc, space, commitments, t, n));
     const bool dev = space == MPVSS_DEVICE;
     const size_t chunk = std::min(n, MAX_CHUNK);
     std::vector<uint8_t> hX(chunk * EB), hY(chunk * EB), h1(chunk * EB), h2(chunk * EB);
@@ -770,7 +892,7 @@ int rt_distribute_locked(mpvss_ctx* ctx, const mpvss_modp_group* grp, int space,
       if (commitments) {
         const int64_t* dpos;
         RET_IF(stage_positions(ctx, space, positions + off, cnt, &dpos));
-        RET_IF(rt_commit_eval_dev(ctx, grp, dc, t, dpos, cnt, dX));                                   // participant.rs:207-215
+        RET_IF(rt_commit_eval_dev(ctx, grp, dc, t, dpos, cnt, dX, space, positions + off));                                   // participant.rs:207-215
       } else {
         RET_IF(rt_fixed_base_dev(ctx, grp, dc, grp->g_be, (const uint8_t*)dp, cnt, dX, 0));           // X_i = g^P(i)
       }
@@ -841,6 +963,33 @@ extern "C" int mpvss_modp_group_comb_stats(mpvss_ctx* ctx, unsigned long long* b
   if (builds) *builds = ctx->rt_comb_builds;
   if (hits) *hits = ctx->rt_comb_hits;
   if (evictions) *evictions = ctx->rt_comb_evictions;
+  return MPVSS_OK;
+}
+
+extern "C" int mpvss_ctx_set_rt_fd(mpvss_ctx* ctx, int mode, int chains) {
+  if (!ctx) return MPVSS_E_INVALID;
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  if (mode < 0 || mode > 2 || chains < 0) return fail(ctx, MPVSS_E_INVALID, "set_rt_fd: mode is 0, 1 or 2 and chains >= 0");
+  ctx->rt_fd_mode = mode;
+  ctx->rt_fd_chains = chains;
+  return MPVSS_OK;
+}
+
+extern "C" int mpvss_modp_group_fd_min_shares(const mpvss_modp_group* grp, size_t t) {
+  if (rt_bad_group(grp) || t == 0) return MPVSS_E_INVALID;
+  return (int)std::min<size_t>(rt_fd_min_shares(grp->lpl, t), 0x7fffffff);
+}
+
+extern "C" int mpvss_modp_group_fd_max_t(const mpvss_modp_group* grp) {
+  if (rt_bad_group(grp)) return MPVSS_E_INVALID;
+  return modp_rt_fd_max_t(grp->lpl);
+}
+
+extern "C" int mpvss_modp_group_fd_stats(mpvss_ctx* ctx, unsigned long long* fd_calls, unsigned long long* horner_calls) {
+  if (!ctx) return MPVSS_E_INVALID;
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  if (fd_calls) *fd_calls = ctx->rt_fd_calls;
+  if (horner_calls) *horner_calls = ctx->rt_horner_calls;
   return MPVSS_OK;
 }
 

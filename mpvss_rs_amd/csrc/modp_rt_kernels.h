@@ -19,9 +19,24 @@ typedef struct modp_rt_consts {
   uint32_t qm1_lo, qm1_hi;            /* q - 1 when it is below 2^64 (positions are reduced by it), else 0 */
 } modp_rt_consts;
 
+/* Forward differences (k_rt_fd_chain): the largest t a width's workgroup holds -- one level per DPP quad, 16 waves of at most
+ * 128 registers at 5 / 9 / 18 limbs per lane, 8 waves of at most 256 at 27 -- and the one place that cuts n consecutive
+ * positions into S chains (host and device): chain c is [first, first + len), len >= t when n / S >= t; its t seeds start at
+ * first + (len - t) / 2. */
+#define MODP_RT_FD_MAX_T(lpl) ((lpl) == 27 ? 128 : 256)
+static inline __host__ __device__ void modp_rt_fd_chain(int n, int S, int c, int* first, int* len) {
+  const long long a = (long long)c * n / S, b = (long long)(c + 1) * n / S;
+  *first = (int)a;
+  *len = (int)(b - a);
+}
+
 #ifdef __cplusplus
 extern "C" {
 #endif
+/* MODP_RT_FD_MAX_T of a width, -1 for no width */
+int modp_rt_fd_max_t(int lpl);
+/* HBM scratch of modp_rt_launch_fd_chains: one number per level, chain and direction */
+size_t modp_rt_fd_park_bytes(int lpl, int t, int S);
 /* bytes of an element / scalar / exponent of a width (256; 384 at 27 limbs per lane), -1 for no width */
 int modp_rt_elem_bytes(int lpl);
 /* IN_ROWS of a width (rows of the long product that takes an EB-byte input) */
@@ -34,6 +49,9 @@ size_t modp_rt_twin_scratch_bytes(int lpl, int count);
 #define MODP_RT_FN(name) modp_rt27_##name
 #include "modp_rt_launchers.h"
 #undef MODP_RT_FN
+/* modp_rt_fd_kernels.hip: modp_rt_launch_fd_chains at 5, 9 and 18 limbs per lane */
+int modp_rtfd_launch_fd_chains(int lpl, const uint32_t* seeds_m, int t, int n, int S, uint32_t* x_m, uint32_t* park,
+                               const modp_rt_consts* cs, hipStream_t s);
 #ifdef __cplusplus
 }
 #endif

@@ -14,6 +14,11 @@
     else return (int)hipErrorInvalidValue;                                                     \
   } while (0)
 
+#define RT_FD_ELSEWHERE modp_rtfd_launch_fd_chains
+// a host function template of the width: FN<lpl>(args)
+#define RT_DISPATCH_FN(lpl, FN, ...) \
+  ((lpl) == 5 ? FN<5>(__VA_ARGS__) : (lpl) == 9 ? FN<9>(__VA_ARGS__) : (lpl) == 18 ? FN<18>(__VA_ARGS__) : (int)hipErrorInvalidValue)
+
 #include "modp_rt_kernels.inc"
 
 // what the host needs to know of a width: none of it launches anything
@@ -30,3 +35,7 @@ extern "C" size_t modp_rt_comb_bytes(int lpl) {
 extern "C" size_t modp_rt_twin_scratch_bytes(int lpl, int count) {
   return (size_t)rt_grid(count) * RT_NUMS * 2 * RT_TWIN_BUCKETS * 4 * lpl * sizeof(uint32_t);
 }
+
+extern "C" int modp_rt_fd_max_t(int lpl) { return (lpl == 5 || lpl == 9 || lpl == 18 || lpl == 27) ? MODP_RT_FD_MAX_T(lpl) : -1; }
+
+extern "C" size_t modp_rt_fd_park_bytes(int lpl, int t, int S) { return (size_t)S * 2 * (16 * ((t + 15) / 16)) * 4 * lpl * sizeof(uint32_t); }

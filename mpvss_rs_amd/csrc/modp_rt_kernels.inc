@@ -2,7 +2,8 @@
 // (src/groups/modp.rs:72-84) -- any odd modulus q of at most 3072 bits, chosen when the program runs.  Included by the
 // two translation units that instantiate them: modp_rt_kernels.hip (5, 9 and 18 limbs per lane, groups of 256-byte
 // elements) and modp_rt_kernels_wide.hip (27 limbs per lane, groups of 384-byte elements), each of which defines
-// RT_FN, RT_DISPATCH and RT_ELSEWHERE first.
+// RT_FN, RT_DISPATCH, RT_DISPATCH_FN and RT_ELSEWHERE first.  A third unit, modp_rt_fd_kernels.hip (RT_FD_ONLY), holds nothing but
+// k_rt_fd_chain at 5, 9 and 18 limbs per lane, which modp_rt_kernels.hip reaches through RT_FD_ELSEWHERE.
 //
 //   ModpGroup::exp / ::mul                       (src/groups/modp.rs:122-132)      k_rt_dual_exp, k_rt_mul
 //   DLEQ verifier commitments a = g1^r h1^c      (src/dleq.rs:66-84)               k_rt_dual_exp (two tables)
@@ -538,12 +539,13 @@ __global__ void RT_KERNEL(LPL) k_rt_mul(const u32* __restrict__ a_m, const u32* 
 // i' = 0 the reference's exponents i^j mod (q-1) of j >= 1 are 0 too, so both sides are C_0.
 //   cm : [t][L] commitments in Montgomery form;  squarings run over the wave's largest i'.
 // LDS per wave: operand slot + saved-base slot per number, one slot with R mod N.
+//   MONT: the result leaves as Montgomery limbs x_m[x][L] (< 2N, no exit product) -- the seeds of the forward differences
 // ---------------------------------------------------------------------------------------
-template <int LPL>
-__global__ void RT_KERNEL_LDS2(LPL) k_rt_commit_eval(const u32* __restrict__ cm, int t, const int64_t* __restrict__ positions, int count,
-                                                uint8_t* __restrict__ x_be, const modp_rt_consts* __restrict__ cs) {
+template <int LPL, bool MONT>
+__device__ __forceinline__ void rt_commit_eval_body(u32* lds, const u32* __restrict__ cm, int t, const int64_t* __restrict__ positions,
+                                                    int count, uint8_t* __restrict__ x_be, u32* __restrict__ x_m,
+                                                    const modp_rt_consts* __restrict__ cs) {
   constexpr int L = Width<LPL>::L, SLOT = Width<LPL>::SLOT;
-  __shared__ __attribute__((aligned(16))) u32 lds[(2 * RT_NUMS + 1) * SLOT];
   const Lane ln = make_lane();
   const int xi = blockIdx.x * RT_NUMS + (threadIdx.x >> 2);
   const bool live = xi < count;
@@ -598,6 +600,7 @@ __global__ void RT_KERNEL_LDS2(LPL) k_rt_commit_eval(const u32* __restrict__ cm,
     } else if (kind == K_CMUL) {
       slot_fill_from_global<LPL>(slot, cm + (size_t)j * L, ln);
     } else {
+      if (MONT) break;                                  // keep the Montgomery form
       slot_fill_from_global<LPL>(slot, cs->one, ln);
     }
     if (!skip) {
@@ -617,7 +620,149 @@ __global__ void RT_KERNEL_LDS2(LPL) k_rt_commit_eval(const u32* __restrict__ cm,
       if (j >= 0) begin_coefficient(); else kind = K_FINAL;
     }
   }
+  if (MONT) {
+    if (live) store_lane_limbs<LPL>(x_m + (size_t)x * L, acc, ln);
+    return;
+  }
   store_canonical<LPL>(x_be + (size_t)x * Width<LPL>::EB, acc, slot, cs, ln, live);
+}
+
+template <int LPL>
+__global__ void RT_KERNEL_LDS2(LPL) k_rt_commit_eval(const u32* __restrict__ cm, int t, const int64_t* __restrict__ positions, int count,
+                                                uint8_t* __restrict__ x_be, const modp_rt_consts* __restrict__ cs) {
+  __shared__ __attribute__((aligned(16))) u32 lds[(2 * RT_NUMS + 1) * Width<LPL>::SLOT];
+  rt_commit_eval_body<LPL, false>(lds, cm, t, positions, count, x_be, nullptr, cs);
+}
+
+// Horner in Montgomery form over two sets of commitments in one launch: blockIdx.y = 0 evaluates cm (X at the seed positions),
+// 1 evaluates cm_inv, the inverted commitments (X^-1 there).  x_m: [2][count][L].
+template <int LPL>
+__global__ void RT_KERNEL_LDS2(LPL) k_rt_commit_eval_mont(const u32* __restrict__ cm, const u32* __restrict__ cm_inv, int t,
+                                                     const int64_t* __restrict__ positions, int count, u32* __restrict__ x_m,
+                                                     const modp_rt_consts* __restrict__ cs) {
+  __shared__ __attribute__((aligned(16))) u32 lds[(2 * RT_NUMS + 1) * Width<LPL>::SLOT];
+  rt_commit_eval_body<LPL, true>(lds, blockIdx.y ? cm_inv : cm, t, positions, count, nullptr,
+                                 x_m + (size_t)blockIdx.y * count * Width<LPL>::L, cs);
+}
+
+// ---------------------------------------------------------------------------------------
+// Forward differences in the exponent (consecutive positions p0 .. p0+n-1 only; the recurrences of modp_kernels.hip).
+// X(i) = prod_j C_j^(i^j) has a polynomial of degree t-1 in the exponent, so with D_0 = X and D_k(c) = D_{k-1}(c+1) / D_{k-1}(c)
+//   D_k(c+1) = D_k(c) D_{k+1}(c)  for k < t-1,   D_{t-1} constant:
+// t-1 products per share.  The n positions are cut into S contiguous chains (modp_rt_fd_chain); chain c has t seeds in its
+// middle, X and X^-1 there by k_rt_commit_eval_mont, and is served by two workgroups: blockIdx.y = 0 steps forward from the
+// first seed, 1 backward from the last -- which is the forward scheme over the seeds in reverse order, since Y(j) = X(last - j)
+// has a polynomial of the same degree.  A workgroup holds level k in DPP quad k (t <= 16 waves x 16 quads), D in registers,
+// each level's operand in its LDS slot, and waits for nothing but its own barrier.
+//   table : quad k starts from G_0[k] = X(seed k), H_0[k] = X^-1(seed k); level l = 1 .. t-1 updates the quads k >= l in place,
+//           G_l[k] = G_{l-1}[k] H_{l-1}[k-1],  H_l[k] = H_{l-1}[k] G_{l-1}[k-1]
+//           (G_l[k] = E_l[k-l], H_l[k] = F_l[k-l] of E_l[k] = E_{l-1}[k+1] F_{l-1}[k], F_l[k] = F_{l-1}[k+1] E_{l-1}[k]); a quad is
+//           frozen from level k+1 on, holding E_k[0] = D_k.  Over the reversed seeds the same rule leaves E_k[t-1-k] in quad k
+//           for even k and F_k[t-1-k] for odd k: the backward state.  2 (t-1)(t)/2 products, two barriers per level.
+//           park: [S][2][16 waves][L] words of HBM scratch.
+//   step  : D_k <- D_k D_{k+1}; every quad reads the copy of D_{k+1} its neighbour stored BEFORE the barrier (two slot
+//           buffers taken in turn: one barrier per step).  The top level and the idle quads multiply by R mod N.  The first
+//           t-1 steps walk over the seeds; from step t on quad 0 stores X in Montgomery limbs, until the chain's edge.
+//   x_m   : [n][L]; the forward workgroup also stores the seeds' own X.  k_rt_from_mont makes the canonical bytes.
+// LDS: (2 x 16 waves + 1) slots of L words, dynamic.  FdOcc<LPL>::waves = largest workgroup = t_max / 16.
+// ---------------------------------------------------------------------------------------
+template <int LPL> struct FdOcc { static constexpr int waves = MODP_RT_FD_MAX_T(LPL) / 16; };
+
+template <int LPL>
+__global__ void __launch_bounds__(64 * FdOcc<LPL>::waves) k_rt_fd_chain(const u32* __restrict__ seeds_m, int t, int n, int S,
+                                                                        u32* __restrict__ x_m, u32* park, const modp_rt_consts* __restrict__ cs) {
+  constexpr int L = Width<LPL>::L;
+  extern __shared__ __attribute__((aligned(16))) u32 fd_lds[];
+  const Lane ln = make_lane();
+  const int k = threadIdx.x >> 2;                        // this quad's level
+  const int tp = blockDim.x >> 2;                        // levels of the workgroup, >= t
+  const int c = blockIdx.x;
+  const bool back = blockIdx.y != 0;
+  u32* bufa = fd_lds;
+  u32* bufb = fd_lds + (size_t)tp * L;
+  u32* oneslot = fd_lds + (size_t)2 * tp * L;
+  const u32 n0inv = cs->n0inv;
+  int first, len;
+  modp_rt_fd_chain(n, S, c, &first, &len);
+  const int seed0 = first + (len - t) / 2;               // index (within the n positions) of the chain's first seed
+  u32 nn[LPL], g[LPL];
+  load_lane_limbs<LPL>(nn, cs->n, ln);
+  if (threadIdx.x < 4) slot_fill_from_global<LPL>(oneslot, cs->one_m, ln);
+  const bool act = k < t;
+  u32* mypark = park + (((size_t)c * 2 + blockIdx.y) * tp + k) * L;
+  {
+    const int sk = back ? t - 1 - k : k;
+    const u32* sx = act ? seeds_m + ((size_t)c * t + sk) * L : cs->one_m;
+    const u32* si = act ? sx + (size_t)S * t * L : cs->one_m;
+    load_lane_limbs<LPL>(g, si, ln);
+    slot_store<LPL>(bufb + (size_t)k * L, g, ln);
+    load_lane_limbs<LPL>(g, sx, ln);
+    slot_store<LPL>(bufa + (size_t)k * L, g, ln);
+    if (act && !back) store_lane_limbs<LPL>(x_m + (size_t)(seed0 + k) * L, g, ln);
+  }
+  __syncthreads();
+  // Between two levels G lives in bufa and H in bufb.  A level forms H' first and parks it in the quad's own words of `park`
+  // (HBM; every lane reads back what it wrote), then G', so that one number at a time is in registers beside the modulus and
+  // the accumulators; both go to the slots once every quad has read the old ones.
+  const int wave_top = (k | 15);                         // highest level of this wave
+  for (int l = 1; l < t; ++l) {
+    const bool upd = act && k >= l;
+    if (wave_top >= l) {                                 // wave-uniform: a wave of frozen quads only keeps the barriers
+#pragma nounroll
+      for (int half = 0; half < 2; ++half) {             // H' = H G[k-1], then G' = G H[k-1]: one product site
+        const u32* own = half ? bufa : bufb;
+        const u32* other = half ? bufb : bufa;
+        slot_load<LPL>(g, own + (size_t)k * L, ln);
+        mont_mul<N0INV_RUNTIME>(g, g, upd ? other + (size_t)(k - 1) * L : oneslot, nn, ln, n0inv);
+        if (half == 0) store_lane_limbs<LPL>(mypark, g, ln);
+      }
+    }
+    __syncthreads();
+    if (wave_top >= l) {
+      slot_store<LPL>(bufa + (size_t)k * L, g, ln);
+      load_lane_limbs<LPL>(g, mypark, ln);
+      slot_store<LPL>(bufb + (size_t)k * L, g, ln);
+    }
+    __syncthreads();
+  }
+  slot_load<LPL>(g, bufa + (size_t)k * L, ln);
+  __syncthreads();
+  // g = D_k of this direction
+  const int m = back ? seed0 - first : first + len - (seed0 + t);      // shares this direction has to produce
+  const int steps = m > 0 ? t - 1 + m : 0;
+  const bool reads_next = k + 1 < t;
+  for (int i = 1; i <= steps; ++i) {
+    u32* buf = (i & 1) ? bufb : bufa;
+    slot_store<LPL>(buf + (size_t)k * L, g, ln);
+    __syncthreads();
+    mont_mul<N0INV_RUNTIME>(g, g, reads_next ? buf + (size_t)(k + 1) * L : oneslot, nn, ln, n0inv);
+    if (k == 0 && i >= t) {
+      const int idx = back ? seed0 + t - 1 - i : seed0 + i;            // in [first, first + len) by the choice of `steps`
+      store_lane_limbs<LPL>(x_m + (size_t)idx * L, g, ln);
+    }
+  }
+}
+
+// out[x] = canonical bytes of x_m[x] (Montgomery limbs < 2N): times plain 1
+template <int LPL>
+__global__ void RT_KERNEL(LPL) k_rt_from_mont(const u32* __restrict__ x_m, int count, uint8_t* __restrict__ out_be,
+                                              const modp_rt_consts* __restrict__ cs) {
+  constexpr int L = Width<LPL>::L, SLOT = Width<LPL>::SLOT;
+  __shared__ __attribute__((aligned(16))) u32 lds[RT_NUMS * SLOT];
+  const Lane ln = make_lane();
+  const int xi = blockIdx.x * RT_NUMS + (threadIdx.x >> 2);
+  const bool live = xi < count;
+  const int x = live ? xi : count - 1;
+  u32* slot = lds + (threadIdx.x >> 2) * SLOT;
+  const u32 n0inv = cs->n0inv;
+  u32 n[LPL], acc[LPL];
+  load_lane_limbs<LPL>(n, cs->n, ln);
+  load_lane_limbs<LPL>(acc, x_m + (size_t)x * L, ln);
+  slot_fill_from_global<LPL>(slot, cs->one, ln);
+  __builtin_amdgcn_wave_barrier();
+  mont_mul<N0INV_RUNTIME>(acc, acc, slot, n, ln, n0inv);
+  __builtin_amdgcn_wave_barrier();
+  store_canonical<LPL>(out_be + (size_t)x * Width<LPL>::EB, acc, slot, cs, ln, live);
 }
 
 // ---------------------------------------------------------------------------------------
@@ -626,6 +771,7 @@ __global__ void RT_KERNEL_LDS2(LPL) k_rt_commit_eval(const u32* __restrict__ cm,
 // ---------------------------------------------------------------------------------------
 static inline int rt_grid(int count) { return (count + RT_NUMS - 1) / RT_NUMS; }
 
+#ifndef RT_FD_ONLY
 extern "C" int RT_FN(launch_to_mont)(int lpl, const uint8_t* in_be, int count, uint32_t* out_m, const modp_rt_consts* cs, hipStream_t s) {
   RT_ELSEWHERE(launch_to_mont, lpl, in_be, count, out_m, cs, s);
   if (count <= 0) return 0;
@@ -699,3 +845,53 @@ extern "C" int RT_FN(launch_commit_eval)(int lpl, const uint32_t* cm_m, int t, c
   RT_DISPATCH(lpl, k_rt_commit_eval, dim3(rt_grid(count)), dim3(64), 0, s, cm_m, t, positions, count, x_be, cs);
   return (int)hipGetLastError();
 }
+
+// Seeds of the forward differences: X (and, from the inverted commitments, X^-1) at `count` positions, Montgomery limbs,
+// x_m [2][count][L]
+extern "C" int RT_FN(launch_commit_eval_mont)(int lpl, const uint32_t* cm_m, const uint32_t* cm_inv_m, int t, const int64_t* positions,
+                                              int count, uint32_t* x_m, const modp_rt_consts* cs, hipStream_t s) {
+  RT_ELSEWHERE(launch_commit_eval_mont, lpl, cm_m, cm_inv_m, t, positions, count, x_m, cs, s);
+  if (count <= 0) return 0;
+  RT_DISPATCH(lpl, k_rt_commit_eval_mont, dim3(rt_grid(count), 2), dim3(64), 0, s, cm_m, cm_inv_m, t, positions, count, x_m, cs);
+  return (int)hipGetLastError();
+}
+
+#endif  // RT_FD_ONLY
+
+#ifndef RT_FD_ELSEWHERE
+template <int LPL>
+static int rt_fd_launch(const uint32_t* seeds_m, int t, int n, int S, uint32_t* x_m, uint32_t* park, const modp_rt_consts* cs, hipStream_t s) {
+  const int waves = (t + 15) / 16;
+  const size_t lds = ((size_t)2 * 16 * waves + 1) * Width<LPL>::L * sizeof(u32);
+  hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_rt_fd_chain<LPL>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+  if (e != hipSuccess) return (int)e;
+  hipLaunchKernelGGL(k_rt_fd_chain<LPL>, dim3(S, 2), dim3(64 * waves), lds, s, seeds_m, t, n, S, x_m, park, cs);
+  return (int)hipGetLastError();
+}
+
+// X in Montgomery limbs at all n consecutive positions from the seeds of S chains (seeds_m [2][S][t][L], chain geometry
+// modp_rt_fd_chain); park: scratch of modp_rt_fd_park_bytes(lpl, t, S) bytes: 2 <= t <= modp_rt_fd_max_t(lpl), 1 <= S, S t <= n
+extern "C" int RT_FN(launch_fd_chains)(int lpl, const uint32_t* seeds_m, int t, int n, int S, uint32_t* x_m, uint32_t* park,
+                                       const modp_rt_consts* cs, hipStream_t s) {
+  RT_ELSEWHERE(launch_fd_chains, lpl, seeds_m, t, n, S, x_m, park, cs, s);
+  if (t < 2 || t > MODP_RT_FD_MAX_T(lpl) || S < 1 || n / S < t) return (int)hipErrorInvalidValue;
+  return RT_DISPATCH_FN(lpl, rt_fd_launch, seeds_m, t, n, S, x_m, park, cs, s);
+}
+
+#else
+// this unit's widths of k_rt_fd_chain live in a unit of their own (modp_rt_fd_kernels.hip: another unroll threshold)
+extern "C" int RT_FN(launch_fd_chains)(int lpl, const uint32_t* seeds_m, int t, int n, int S, uint32_t* x_m, uint32_t* park,
+                                       const modp_rt_consts* cs, hipStream_t s) {
+  RT_ELSEWHERE(launch_fd_chains, lpl, seeds_m, t, n, S, x_m, park, cs, s);
+  return RT_FD_ELSEWHERE(lpl, seeds_m, t, n, S, x_m, park, cs, s);
+}
+#endif  // RT_FD_ELSEWHERE
+
+#ifndef RT_FD_ONLY
+extern "C" int RT_FN(launch_from_mont)(int lpl, const uint32_t* x_m, int count, uint8_t* out_be, const modp_rt_consts* cs, hipStream_t s) {
+  RT_ELSEWHERE(launch_from_mont, lpl, x_m, count, out_be, cs, s);
+  if (count <= 0) return 0;
+  RT_DISPATCH(lpl, k_rt_from_mont, dim3(rt_grid(count)), dim3(64), 0, s, x_m, count, out_be, cs);
+  return (int)hipGetLastError();
+}
+#endif  // RT_FD_ONLY

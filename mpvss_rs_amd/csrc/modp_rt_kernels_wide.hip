@@ -12,4 +12,6 @@
     else return (int)hipErrorInvalidValue;                                                     \
   } while (0)
 
+#define RT_DISPATCH_FN(lpl, FN, ...) ((lpl) == 27 ? FN<27>(__VA_ARGS__) : (int)hipErrorInvalidValue)
+
 #include "modp_rt_kernels.inc"

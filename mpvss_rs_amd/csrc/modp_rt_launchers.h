@@ -32,3 +32,13 @@ int MODP_RT_FN(launch_mul)(int lpl, const uint32_t* a_m, const uint32_t* b_m, in
 /* X[x] = Horner in the exponent over the commitments cm_m ([t] numbers in Montgomery form) at i' = positions[x] mod (q-1) */
 int MODP_RT_FN(launch_commit_eval)(int lpl, const uint32_t* cm_m, int t, const int64_t* positions, int count, uint8_t* x_be,
                                const modp_rt_consts* cs, hipStream_t s);
+/* the seeds of the forward differences: Horner in Montgomery form at `count` positions over cm_m (gridDim.y = 0) and over the
+   inverted commitments cm_inv_m (1) in one launch; x_m [2][count][L], every number < 2N */
+int MODP_RT_FN(launch_commit_eval_mont)(int lpl, const uint32_t* cm_m, const uint32_t* cm_inv_m, int t, const int64_t* positions,
+                                    int count, uint32_t* x_m, const modp_rt_consts* cs, hipStream_t s);
+/* X in Montgomery limbs, x_m [n][L], at n consecutive positions cut into S chains (modp_rt_fd_chain) from seeds_m [2][S][t][L]:
+   one workgroup per chain and direction; park: scratch of modp_rt_fd_park_bytes(lpl, t, S) bytes.  2 <= t <= MODP_RT_FD_MAX_T(lpl), n / S >= t, else hipErrorInvalidValue */
+int MODP_RT_FN(launch_fd_chains)(int lpl, const uint32_t* seeds_m, int t, int n, int S, uint32_t* x_m, uint32_t* park,
+                             const modp_rt_consts* cs, hipStream_t s);
+/* out[x] = canonical EB bytes of x_m[x] (Montgomery limbs < 2N) */
+int MODP_RT_FN(launch_from_mont)(int lpl, const uint32_t* x_m, int count, uint8_t* out_be, const modp_rt_consts* cs, hipStream_t s);

@@ -338,9 +338,18 @@ struct mpvss_ctx {
   // workspace of the run-time MODP group entry points (capi_modp_rt.inc), used under `mu`
   DevBuf rt_consts, rt_in[6], rt_out[3], rt_tab1, rt_tab2, rt_tabg, rt_cm, rt_small[2];
   DevBuf rt_out_y, rt_buckets;   // the dealer's fourth result array; bucket scratch of k_rt_twin_exp (one chunk)
+  // forward differences for X of a run-time group (rt_commit_eval_dev): inverted commitments (bytes, then Montgomery form), seed
+  // positions, seeds [2][S][t][L], X in limbs [n][L], the chain kernel's scratch -- grown on demand
+  DevBuf rt_fd_inv, rt_cm_inv, rt_fd_pos, rt_fd_seeds, rt_fd_x, rt_fd_park;
+  int rt_fd_mode = 1, rt_fd_chains = 0;          // mpvss_ctx_set_rt_fd
+  bool rt_fd_ready = false;                      // this call's rt_cm_inv is valid (rt_fd_prepare)
+  unsigned long long rt_fd_calls = 0, rt_horner_calls = 0;   // chunks of X by either path (mpvss_modp_group_fd_stats)
+  std::vector<uint8_t> rt_fd_inv_host;           // sources of asynchronous copies: they outlive the call's launches
+  std::vector<int64_t> rt_fd_pos_host;
   std::vector<DevBuf*> rt_all() {
     return {&rt_consts, &rt_in[0], &rt_in[1], &rt_in[2], &rt_in[3], &rt_in[4], &rt_in[5], &rt_out[0], &rt_out[1], &rt_out[2],
             &rt_tab1, &rt_tab2, &rt_tabg, &rt_cm, &rt_small[0], &rt_small[1], &rt_out_y, &rt_buckets,
+            &rt_fd_inv, &rt_cm_inv, &rt_fd_pos, &rt_fd_seeds, &rt_fd_x, &rt_fd_park,
             &rt_comb[0].buf, &rt_comb[1].buf, &rt_comb[2].buf, &rt_comb[3].buf};
   }
   // fixed-base combs of run-time groups (rt_comb_for, capi_modp_rt.inc), used under `mu`: keyed by the bytes (q, base) -- a handle

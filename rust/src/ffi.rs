@@ -266,6 +266,10 @@ unsafe extern "C" {
     pub fn mpvss_modp_group_prepare(ctx: *mut mpvss_ctx, grp: *const mpvss_modp_group) -> c_int;
     pub fn mpvss_modp_group_comb_min_shares(grp: *const mpvss_modp_group) -> c_int;
     pub fn mpvss_modp_group_comb_stats(ctx: *mut mpvss_ctx, builds: *mut c_ulonglong, hits: *mut c_ulonglong, evictions: *mut c_ulonglong) -> c_int;
+    pub fn mpvss_ctx_set_rt_fd(ctx: *mut mpvss_ctx, mode: c_int, chains: c_int) -> c_int;
+    pub fn mpvss_modp_group_fd_min_shares(grp: *const mpvss_modp_group, t: usize) -> c_int;
+    pub fn mpvss_modp_group_fd_max_t(grp: *const mpvss_modp_group) -> c_int;
+    pub fn mpvss_modp_group_fd_stats(ctx: *mut mpvss_ctx, fd_calls: *mut c_ulonglong, horner_calls: *mut c_ulonglong) -> c_int;
     pub fn mpvss_modp_group_distribute(ctx: *mut mpvss_ctx, grp: *const mpvss_modp_group, space: c_int, commitments: *const u8, t: usize,
                                        positions: *const i64, pubkeys: *const u8, p_values: *const u8, witnesses: *const u8, n: usize,
                                        x_out: *mut u8, y_out: *mut u8, a1_out: *mut u8, a2_out: *mut u8, digest32_out: *mut u8) -> c_int;

@@ -37,7 +37,10 @@
               library (no gate).  All lines go to profiles/modp_rt_comb_rate.txt.
 
 Host buffers in and out (the calls' own staging included), best of `--reps` after one warm-up call.  One JSON line per
-measurement.  Usage: python tools/modp_rt_rate.py [--quick] [--reps 3] [--legs rates,twin,deal,comb,verify] [--comb] [--ab PARENT [--rounds 2]]"""
+measurement.  Usage: python tools/modp_rt_rate.py [--quick] [--reps 3] [--legs rates,twin,deal,comb,verify] [--comb | --fd] [--ab PARENT [--rounds 2]]
+  fd          (--fd) X_i of a run-time group by forward differences: timer 0 of group_commit_eval at (4096, 64), (16384, 128),
+              (65536, 256), 1024 and 2048 bits, per chain count, and whole group_verify_distribution calls; --fd --ab PARENT takes
+              turns with a built checkout of the parent commit and writes profiles/modp_rt_fd_rate.txt (one 3072-bit row too)."""
 import argparse
 import json
 import os
@@ -184,6 +187,54 @@ def verify_leg(eng, a, rng):
                           "share_verifications_per_s": round(nn / s), "kernel_ms": kernel_ms(eng)}), flush=True)
 
 
+FD_SHAPES = [(4096, 64), (16384, 128), (65536, 256)]
+FD_CHAINS = [4, 8, 16, 32, 64]
+
+
+def fd_leg(eng, a, rng):
+    """timer 0 alone (the whole X path of mpvss_modp_group_commit_eval) and whole group_verify_distribution calls.  --fd-parts
+    parent: Horner's rule as the library under test has it (a parent build knows nothing else); fd: mode 2 at each chain count,
+    and mode 0 of the same build beside it."""
+    parts = a.fd_parts.split(",")
+    shapes = [(4096, 64)] if a.quick else FD_SHAPES
+    groups = [(1024, ModpGroup(H.rfc_prime(1024))), (2048, ModpGroup(H.rfc_prime(2048)))]
+    if a.fd_wide:
+        groups = [(3072, ModpGroup(H.random_odd_modulus(3072, random.Random(3072)), elem_bytes=384))]
+        shapes = [(16384, 128)]
+    for bits, grp in groups:
+        EB = grp.elem_bytes
+        for nn, t in shapes:
+            cm = b"".join((rng.getrandbits(bits - 1) | 1).to_bytes(EB, "big") for _ in range(t))
+            pos = list(range(1, nn + 1))
+
+            def x_ms():
+                ts = []
+                for _ in range(a.reps + 1):
+                    eng.group_commit_eval(grp, cm, pos)
+                    ts.append(round(max(0.0, eng.kernel_ms(0)), 3))
+                return min(ts[1:])
+
+            row = {"what": "fd", "bits": bits, "n": nn, "t": t}
+            if "parent" in parts:
+                row["horner_kernel_ms"] = x_ms()
+            if "fd" in parts:
+                eng.set_rt_fd(0, 0)
+                row["mode0_kernel_ms"] = x_ms()
+                for ch in FD_CHAINS:
+                    eng.set_rt_fd(2, ch)
+                    before = eng.group_fd_stats()["fd"]
+                    row[f"fd_chains_{ch}_kernel_ms"] = x_ms()
+                    assert eng.group_fd_stats()["fd"] > before, "the call did not take forward differences"
+                eng.set_rt_fd(2, 0)
+            if not a.fd_wide:
+                y, Y, r = (b"".join(rng.getrandbits(bits - 1).to_bytes(EB, "big") for _ in range(nn)) for _ in range(3))
+                c = rng.getrandbits(256).to_bytes(EB, "big")
+                s = best(lambda: eng.group_verify_distribution(grp, cm, pos, y, Y, r, c), a.reps)
+                row["verify_s"] = round(s, 4)
+                row["share_verifications_per_s"] = round(nn / s)
+            print(json.dumps(row), flush=True)
+
+
 def child(args, lib, out, limit):
     """one fresh process of this tool (the GPU is opened there only); its JSON lines, also echoed.  A child that fails ends
     the whole run: nothing more is started on the GPU after it.  `limit`: seconds this leg may take."""
@@ -297,6 +348,52 @@ def ab_comb(a):
             f.write(json.dumps(row) + "\n")
 
 
+def ab_fd(a):
+    """--fd --ab PARENT: fresh processes of the parent build (Horner's rule) and of this build (mode 2 per chain count) take turns;
+    best of the rounds.  rt_fd_chains is the best chain count per shape, rt_fd_min_shares the smallest measured n from which
+    forward differences are no slower than the parent at every larger n; the gate: at most half of the parent's time at
+    (65 536, 256) and 2048 bits."""
+    if not os.path.exists(os.path.join(a.ab, "mpvss_rs_amd", "libmpvss_hip.so")):
+        sys.exit("modp_rt_rate --fd --ab: the parent checkout is not built")
+    common = ["--legs", "fd", "--reps", str(a.reps)] + (["--quick"] if a.quick else [])
+    lines, ms = [], {}
+    for wide in ([], ["--fd-wide"]):
+        for rnd in range(a.rounds):
+            for part, extra in (("parent", ["--package-root", a.ab]), ("fd", [])):
+                for row in child(common + wide + ["--fd-parts", part] + extra, None, [], a.deal_limit):
+                    row.update(part=part, round=rnd)
+                    for k, v in row.items():
+                        if k.endswith("_kernel_ms") or k == "verify_s":
+                            key = (part + ":" + k, row["bits"], row["n"], row["t"])
+                            ms[key] = min(ms.get(key, v), v)
+                    lines.append(row)
+    for bits in sorted({k[1] for k in ms}):
+        shapes = sorted({k[2:] for k in ms if k[1] == bits})
+        ok = []
+        for n, t in shapes:
+            horner = ms["parent:horner_kernel_ms", bits, n, t]
+            fd = {ch: ms[f"fd:fd_chains_{ch}_kernel_ms", bits, n, t] for ch in FD_CHAINS}
+            bestch = min(fd, key=fd.get)
+            ok.append(fd[bestch] <= horner)
+            row = {"what": "fd_ab", "bits": bits, "n": n, "t": t, "parent_horner_kernel_ms": horner, "fd_kernel_ms": fd,
+                   "best_chains": bestch, "fd_over_horner": round(fd[bestch] / horner, 3)}
+            if ("parent:verify_s", bits, n, t) in ms:
+                row.update(parent_verify_s=ms["parent:verify_s", bits, n, t], change_mode2_verify_s=ms["fd:verify_s", bits, n, t])
+            lines.append(row)
+            if (bits, n, t) == (2048, 65536, 256):
+                lines.append({"what": "fd_gate", "bits": bits, "n": n, "t": t, "fd_over_horner": round(fd[bestch] / horner, 3),
+                              "required": 0.5, "met": fd[bestch] <= 0.5 * horner})
+        first = next((shapes[i][0] for i in range(len(shapes)) if all(ok[i:])), None)
+        lines.append({"what": "fd_crossover", "bits": bits, "min_shares": first, "measured_shapes": shapes})
+    for row in lines:
+        if row["what"].startswith("fd_"):
+            print(json.dumps(row), flush=True)
+    os.makedirs(os.path.join(ROOT, "profiles"), exist_ok=True)
+    with open(a.out, "w") as f:
+        for row in lines:
+            f.write(json.dumps(row) + "\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=3)
@@ -305,6 +402,9 @@ def main():
     ap.add_argument("--twin-parts", default="call,baseline", help="of the twin leg: call (batch_twin_exp), baseline (two batch_exp)")
     ap.add_argument("--comb", action="store_true", help="the fixed-base comb: alone, the comb leg; with --ab, its interleaved A/B")
     ap.add_argument("--comb-parts", default="comb", help="of the comb leg: parent (g^w inside group_deal), comb (cold and warm)")
+    ap.add_argument("--fd", action="store_true", help="forward differences for X: alone, the fd leg; with --ab, its interleaved A/B")
+    ap.add_argument("--fd-parts", default="fd", help="of the fd leg: parent (Horner's rule of the library under test), fd (mode 2 per chain count)")
+    ap.add_argument("--fd-wide", action="store_true", help="of the fd leg: the one 3072-bit row, (16384, 128)")
     ap.add_argument("--package-root", default=None, help="import mpvss_rs_amd (bindings and library) from this checkout")
     ap.add_argument("--ab", default=None, metavar="PARENT", help="the interleaved A/B against a built checkout of the parent commit")
     ap.add_argument("--rounds", type=int, default=2, help="of --ab: how often the three processes take turns")
@@ -313,11 +413,13 @@ def main():
     ap.add_argument("--out", default=None, help="of --ab: the file written (profiles/modp_rt_deal_rate.txt, or _comb_rate.txt)")
     a = ap.parse_args()
     if a.out is None:
-        a.out = os.path.join(ROOT, "profiles", "modp_rt_comb_rate.txt" if a.comb else "modp_rt_deal_rate.txt")
+        a.out = os.path.join(ROOT, "profiles", "modp_rt_fd_rate.txt" if a.fd else "modp_rt_comb_rate.txt" if a.comb else "modp_rt_deal_rate.txt")
     if a.ab:
-        return ab_comb(a) if a.comb else ab(a)
+        return ab_fd(a) if a.fd else ab_comb(a) if a.comb else ab(a)
     if a.comb:
         a.legs = "comb"
+    if a.fd:
+        a.legs = "fd"
     load_package(a.package_root)
     eng = Engine(0)
     rng = random.Random(1)
@@ -330,6 +432,8 @@ def main():
         comb_leg(eng, a, rng)
     if "verify" in legs:
         verify_leg(eng, a, rng)
+    if "fd" in legs:
+        fd_leg(eng, a, rng)
     if "rates" not in legs:
         eng.close()
         return
