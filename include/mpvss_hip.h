@@ -536,7 +536,9 @@ int mpvss_box_verify_wire(mpvss_ctx* ctx, const uint8_t* buf, size_t len, int* v
  * without fault and are deterministic.
  * The entry points below mirror the group-14 ones with the handle added, lock the context like them and are safe for
  * concurrent callers on one context in the same sense.  The whole protocol is there: verification, the dealer (distribute,
- * the one-call deal), extract_secret_share and reconstruct, with the scalar ring Z/(q-1) on host threads.  Not offered for a
+ * the one-call deal), extract_secret_share and reconstruct.  The scalar ring Z/(q-1) -- P(i), the responses, e2 = w / x -- runs
+ * on host threads or, for a handle with odd (q-1)/2 >= 3 (every safe prime above 5), on the device: mpvss_ctx_set_rt_scalar and
+ * "the scalar ring on the device" below.  Not offered for a
  * run-time group: the block / pipeline forms, verify_many, key sets and the wire format; moduli above 3072 bits are refused
  * with MPVSS_E_INVALID (4096 bits would overflow the product's 64-bit column accumulators). */
 typedef struct mpvss_modp_group mpvss_modp_group;
@@ -623,7 +625,8 @@ int mpvss_modp_group_distribute(mpvss_ctx* ctx, const mpvss_modp_group* grp, int
                                 size_t n, uint8_t* x_out, uint8_t* y_out, uint8_t* a1_out, uint8_t* a2_out, uint8_t* digest32_out);
 /* the dealer's whole box in one call from HOST buffers: same contract as mpvss_modp_deal (x_out, a1_out, a2_out, digest32_out
  * and challenge_out256 optional; t <= n; t == 0 with n > 0 and a negative position are MPVSS_E_INVALID; n == 0 gives the digest
- * of the empty transcript).  P(i) and the responses are host-thread work here, X_i = g^P(i) and a1_i = g^w_i run over the
+ * of the empty transcript).  P(i) and the responses are host-thread work or run on the device (mpvss_ctx_set_rt_scalar; the same
+ * bytes either way; on the device P(i), w and the responses of all n shares stay in HBM until the call ends, 3 n x the element size in bytes), X_i = g^P(i) and a1_i = g^w_i run over the
  * comb of g = 4, or over its window table for a small box on a context without the comb.  Every buffer of the call that held coefficients, P(i), witnesses or buckets is zeroed before it
  * returns, on error paths too. */
 int mpvss_modp_group_deal(mpvss_ctx* ctx, const mpvss_modp_group* grp, const uint8_t* coeffs_host, size_t t,
@@ -632,7 +635,8 @@ int mpvss_modp_group_deal(mpvss_ctx* ctx, const mpvss_modp_group* grp, const uin
                           uint8_t* challenge_out256, uint8_t* r_out);
 /* n participants' extract_secret_share, src/participant.rs:294-353: same contract as mpvss_modp_extract_shares (xinv = x^-1 mod
  * (q-1) and the witnesses are inputs, the per-share challenge is hashed on the host).  A row whose Y_i is 0 mod q gives the
- * reference's values (S_i = 0, a2_i = 0^w_i). */
+ * reference's values (S_i = 0, a2_i = 0^w_i).  e2_i = w_i xinv_i mod (q-1) is formed on host threads or on the device
+ * (mpvss_ctx_set_rt_scalar), the same bytes either way. */
 int mpvss_modp_group_extract_shares(mpvss_ctx* ctx, const mpvss_modp_group* grp, int space, const uint8_t* pk, const uint8_t* y,
                                     const uint8_t* xinv, const uint8_t* w, size_t n, uint8_t* s_out, uint8_t* c_out_host);
 /* G^s and the mask from m shares, src/participant.rs:462-561: same contract as mpvss_modp_reconstruct (positions >= 1 and pairwise
@@ -648,6 +652,31 @@ int mpvss_modp_group_dleq_responses(const mpvss_modp_group* grp, const uint8_t* 
                                     int c_per_share, size_t n, uint8_t* r_out, int threads);
 int mpvss_modp_group_poly_eval(const mpvss_modp_group* grp, const uint8_t* coeffs, size_t t, const int64_t* positions, size_t n,
                                uint8_t* out, int threads);
+/* The scalar ring on the device.  For odd q' = (q-1)/2, Z/(q-1) = Z/2 x Z/q': the kernels keep a scalar as its residue mod q'
+ * (Montgomery form at the handle's width, constants of q' in the handle) and its parity, and write the one number of [0, q-1)
+ * with both.  mpvss_modp_group_has_device_scalar: 1 when q' is odd and >= 3 (every safe prime above 5), else 0; host only.
+ * The three calls below mirror mpvss_modp_poly_eval_device, mpvss_modp_dleq_responses_device and mpvss_modp_scalar_mul per share,
+ * with the handle added: every scalar 256 bytes (the handle's element size) of any value, results canonical and byte-identical
+ * to mpvss_modp_group_poly_eval / _dleq_responses (one shared c) / _scalar_mul.  n == 0 is MPVSS_OK; t == 0 with n > 0 and a
+ * negative position (found after the fact from the copied-back positions) are MPVSS_E_INVALID; so is a handle without the
+ * constants of q' -- these calls have no host path inside.  They run on the context's stream under its lock and are synchronous.
+ * The staged coefficients (pinned and device copy) are zeroed on every way out; batch_scalar_mul zeroes what it staged from
+ * the host. */
+int mpvss_modp_group_has_device_scalar(const mpvss_modp_group* grp);
+int mpvss_modp_group_poly_eval_device(mpvss_ctx* ctx, const mpvss_modp_group* grp, const uint8_t* coeffs_host, size_t t,
+                                      const int64_t* positions_dev, size_t n, uint8_t* out_dev);
+int mpvss_modp_group_dleq_responses_device(mpvss_ctx* ctx, const mpvss_modp_group* grp, const uint8_t* w_dev, const uint8_t* alpha_dev,
+                                           const uint8_t* c_host, size_t n, uint8_t* r_dev_out);
+int mpvss_modp_group_batch_scalar_mul(mpvss_ctx* ctx, const mpvss_modp_group* grp, int space, const uint8_t* a, const uint8_t* b,
+                                      size_t n, uint8_t* out);
+/* Where group_deal and group_extract_shares run the scalar ring: mode 0 on host threads; 1 automatic (the default): on the device
+ * from mpvss_modp_group_scalar_min_shares shares of a whole call -- not yet measured, so until then automatic means host; 2 on
+ * the device whenever the handle allows it.  A handle without the constants of q' always takes the host path. */
+int mpvss_ctx_set_rt_scalar(mpvss_ctx* ctx, int mode);
+int mpvss_modp_group_scalar_min_shares(const mpvss_modp_group* grp);
+/* whole group_deal / group_extract_shares calls that ran the scalar ring on the device and on the host since the context was
+ * created (either pointer may be null) */
+int mpvss_modp_group_scalar_stats(mpvss_ctx* ctx, unsigned long long* device_calls, unsigned long long* host_calls);
 
 /* ---- hashing helpers (host only; Group::hash_to_scalar, src/groups/modp.rs:142-148) ------ */
 
@@ -661,7 +690,8 @@ void mpvss_modp_hash_to_scalar(const uint8_t* data, size_t len, uint8_t out256[2
 /* Milliseconds the GPU spent in the kernels of the most recent compute call on this context,
  * measured with hipEvents on the stream each kernel was launched on, summed per kind:
  *   0 = the X path (k_modp_commit_eval and, for consecutive positions, the forward-difference kernels),
- *   1 = k_modp_comb_dual_exp (a1), 2 = table builds, 3 = k_modp_dual_exp (a2, batch_exp).
+ *   1 = k_modp_comb_dual_exp (a1), 2 = table builds, 3 = k_modp_dual_exp (a2, batch_exp),
+ *   4 = the scalar-ring kernels of a run-time group (k_rt_modq_*).
  * Kernels of different kinds may overlap in time (two streams), so the sums can exceed the wall time.
  * mpvss_last_kernel_launches gives the number of launches behind each sum.  Negative when unavailable. */
 double mpvss_last_kernel_ms(const mpvss_ctx* ctx, int kernel_id);

@@ -56,6 +56,9 @@ EXPORTED_SYMBOLS = (
     "mpvss_modp_group_batch_exp_fixed_base", "mpvss_modp_group_prepare", "mpvss_modp_group_comb_min_shares",
     "mpvss_modp_group_comb_stats", "mpvss_modp_group_create_wide", "mpvss_modp_group_elem_bytes",
     "mpvss_ctx_set_rt_fd", "mpvss_modp_group_fd_min_shares", "mpvss_modp_group_fd_max_t", "mpvss_modp_group_fd_stats",
+    "mpvss_modp_group_has_device_scalar", "mpvss_modp_group_scalar_min_shares", "mpvss_ctx_set_rt_scalar",
+    "mpvss_modp_group_scalar_stats", "mpvss_modp_group_poly_eval_device", "mpvss_modp_group_dleq_responses_device",
+    "mpvss_modp_group_batch_scalar_mul",
 )
 
 GROUP_SECP256K1 = 1
@@ -247,6 +250,13 @@ def load_library() -> C.CDLL:
     lib.mpvss_modp_group_fd_min_shares.argtypes = [vp, C.c_size_t]
     lib.mpvss_modp_group_fd_max_t.argtypes = [vp]
     lib.mpvss_modp_group_fd_stats.argtypes = [vp, C.POINTER(C.c_ulonglong), C.POINTER(C.c_ulonglong)]
+    lib.mpvss_modp_group_has_device_scalar.argtypes = [vp]
+    lib.mpvss_modp_group_scalar_min_shares.argtypes = [vp]
+    lib.mpvss_ctx_set_rt_scalar.argtypes = [vp, ci]
+    lib.mpvss_modp_group_scalar_stats.argtypes = [vp, C.POINTER(C.c_ulonglong), C.POINTER(C.c_ulonglong)]
+    lib.mpvss_modp_group_poly_eval_device.argtypes = [vp, vp, u8p, sz, vp, sz, vp]
+    lib.mpvss_modp_group_dleq_responses_device.argtypes = [vp, vp, vp, vp, u8p, sz, vp]
+    lib.mpvss_modp_group_batch_scalar_mul.argtypes = [vp, vp, ci, vp, vp, sz, vp]
     return lib
 
 
@@ -306,6 +316,15 @@ class ModpGroup:
     def comb_min_shares(self) -> int:
         """batch size from which a call builds the fixed-base comb of a shared base the context has not cached"""
         return self.lib.mpvss_modp_group_comb_min_shares(self.handle)
+
+    @property
+    def has_device_scalar(self) -> bool:
+        """the handle holds the constants of (q-1)/2 (odd and >= 3): the scalar ring can run on the device"""
+        return self.lib.mpvss_modp_group_has_device_scalar(self.handle) == 1
+
+    @property
+    def scalar_min_shares(self) -> int:
+        return self.lib.mpvss_modp_group_scalar_min_shares(self.handle)
 
     @property
     def fd_max_t(self) -> int:
@@ -488,6 +507,45 @@ class Engine:
         """mpvss_ctx_set_rt_fd: forward differences for X_i of run-time groups -- 0 off, 1 automatic, 2 whenever admissible;
         chains 0 = automatic"""
         self._check(self.lib.mpvss_ctx_set_rt_fd(self.ctx, int(mode), int(chains)), "set_rt_fd")
+
+    def set_rt_scalar(self, mode: int) -> None:
+        """mpvss_ctx_set_rt_scalar: the scalar ring Z/(q-1) of group_deal / group_extract_shares -- 0 host threads, 1 automatic,
+        2 on the device whenever the handle has the constants of (q-1)/2"""
+        self._check(self.lib.mpvss_ctx_set_rt_scalar(self.ctx, int(mode)), "set_rt_scalar")
+
+    def group_scalar_stats(self) -> dict:
+        """whole group_deal / group_extract_shares calls that ran the scalar ring on the device / on the host"""
+        d, h = C.c_ulonglong(0), C.c_ulonglong(0)
+        self._check(self.lib.mpvss_modp_group_scalar_stats(self.ctx, C.byref(d), C.byref(h)), "group_scalar_stats")
+        return {"device": int(d.value), "host": int(h.value)}
+
+    def group_poly_eval_device(self, grp: "ModpGroup", coeffs: bytes, positions_dev_ptr: int, n: int, out_dev_ptr: int) -> None:
+        """P(i) mod (q-1) for n positions in HBM (int64) into n x elem_bytes in HBM; the coefficients are host bytes"""
+        kc, pc = _buf(coeffs or None)
+        self._check(self.lib.mpvss_modp_group_poly_eval_device(self.ctx, grp.handle, pc, len(coeffs) // grp.elem_bytes,
+                                                               positions_dev_ptr, n, out_dev_ptr), "group_poly_eval_device")
+
+    def group_dleq_responses_device(self, grp: "ModpGroup", w_dev_ptr: int, alpha_dev_ptr: int, c: bytes, n: int,
+                                    out_dev_ptr: int) -> None:
+        """r[i] = w[i] - alpha[i] c mod (q-1), everything but the shared c in HBM"""
+        kc, pc = _buf(c)
+        self._check(self.lib.mpvss_modp_group_dleq_responses_device(self.ctx, grp.handle, w_dev_ptr, alpha_dev_ptr, pc, n,
+                                                                    out_dev_ptr), "group_dleq_responses_device")
+
+    def group_batch_scalar_mul(self, grp: "ModpGroup", a: bytes, b: bytes) -> bytes:
+        """out[i] = a[i] b[i] mod (q-1) on the device, from host bytes"""
+        EB = grp.elem_bytes
+        n = len(a) // EB
+        ka, pa = _buf(a or None); kb, pb = _buf(b or None); ko, po = _out(n * EB)
+        self._check(self.lib.mpvss_modp_group_batch_scalar_mul(self.ctx, grp.handle, MPVSS_HOST, C.cast(pa, C.c_void_p),
+                                                               C.cast(pb, C.c_void_p), n, C.cast(po, C.c_void_p)),
+                    "group_batch_scalar_mul")
+        return bytes(ko)[: n * EB]
+
+    def group_batch_scalar_mul_device(self, grp: "ModpGroup", a_dev_ptr: int, b_dev_ptr: int, n: int, out_dev_ptr: int) -> None:
+        """the same with all three arrays in HBM"""
+        self._check(self.lib.mpvss_modp_group_batch_scalar_mul(self.ctx, grp.handle, MPVSS_DEVICE, a_dev_ptr, b_dev_ptr, n,
+                                                               out_dev_ptr), "group_batch_scalar_mul")
 
     def group_fd_stats(self) -> dict:
         """chunks of X_i this context computed by forward differences and by Horner's rule"""

@@ -13,6 +13,10 @@ struct RtRings {
 
 struct mpvss_modp_group {
   modp_rt_consts c;          // device image of the constants (copied to the device by every call)
+  modp_rt_consts cq;         // the same for the modulus q' = (q-1)/2 at the handle's own lpl (R > 4 q' wherever R > 4 q): the scalar
+                             // ring Z/(q-1) = Z/2 x Z/q' on the device.  Built only when q' is odd and >= 3 (has_q)
+  bool has_q = false;
+  uint8_t subR_be[RT_EB_MAX];// R mod q' = 2^(29 L) mod q', eb bytes big-endian (has_q): takes a coefficient into Montgomery form
   int bits = 0;
   int lpl = 0;
   size_t eb = 0;             // bytes of every element, scalar and exponent of this handle on the ABI: 256, or 384 (wide)
@@ -416,6 +420,23 @@ int rt_group_build(const RtNum q, int bits, size_t eb, int lpl, RtRings<NW> mpvs
   g->g_be[eb - 1] = 4;
   memset(g->G_be, 0, sizeof(g->G_be));
   g->G_be[eb - 1] = 2;
+  // the constants of q' for the device-side scalar ring: q' odd (q = 3 mod 4) and q' >= 3 (q >= 7) -- every safe prime above 5
+  memset(&g->cq, 0, sizeof(g->cq));
+  memset(g->subR_be, 0, sizeof(g->subR_be));
+  g->has_q = (q[0] & 3) == 3 && (bits > 3 || q[0] >= 7);
+  if (g->has_q) {
+    rt_limbs(sub, g->cq.n, L);
+    rt_pow2_mod<NW>(k, 29 * (in_rows + L), R.sub);
+    rt_limbs(k, g->cq.kin, L);
+    rt_pow2_mod<NW>(k, 29 * L, R.sub);
+    rt_limbs(k, g->cq.one_m, L);
+    rt_to_be(k, g->subR_be, eb);
+    g->cq.one[0] = 1;
+    uint32_t qinv = sub[0];
+    for (int i = 0; i < 5; ++i) qinv *= 2u - sub[0] * qinv;
+    g->cq.n0inv = (0u - qinv) & ((1u << 29) - 1);
+    g->cq.lpl = (uint32_t)g->lpl;
+  }
   *out = g;
   return MPVSS_OK;
 }
@@ -730,7 +751,7 @@ extern "C" int mpvss_modp_group_verify_shares(mpvss_ctx* ctx, const mpvss_modp_g
 }
 
 // =====================================================================================================================
-// The rest of the protocol for a run-time group: the scalar ring Z/(q-1) on the host, the dealer (distribute / deal),
+// The rest of the protocol for a run-time group: the scalar ring Z/(q-1) on the host (and, further down, on the device), the dealer (distribute / deal),
 // extract_secret_share and reconstruct.
 // =====================================================================================================================
 
@@ -785,18 +806,127 @@ struct RtWipe {
   mpvss_ctx* ctx;
   std::vector<std::pair<DevBuf*, size_t>> dev;
   std::vector<std::vector<uint8_t>*> host;
+  std::vector<std::pair<void*, size_t>> pinned;      // sources of asynchronous copies: zeroed once the stream is drained
   void device(DevBuf& b, size_t bytes) { dev.push_back({&b, bytes}); }
   ~RtWipe() {
     for (auto* v : host) {
       volatile uint8_t* wp = v->data();
       for (size_t i = 0; i < v->size(); ++i) wp[i] = 0;
     }
-    if (dev.empty() || hipSetDevice(ctx->device) != hipSuccess) return;
-    for (auto& d : dev)
-      if (d.first->p) (void)hipMemsetAsync(d.first->p, 0, d.second < d.first->cap ? d.second : d.first->cap, ctx->stream);
-    (void)hipStreamSynchronize(ctx->stream);
+    if ((!dev.empty() || !pinned.empty()) && hipSetDevice(ctx->device) == hipSuccess) {
+      for (auto& d : dev)
+        if (d.first->p) (void)hipMemsetAsync(d.first->p, 0, d.second < d.first->cap ? d.second : d.first->cap, ctx->stream);
+      (void)hipStreamSynchronize(ctx->stream);
+    }
+    for (auto& pp : pinned) {
+      volatile uint8_t* wp = (volatile uint8_t*)pp.first;
+      for (size_t i = 0; wp && i < pp.second; ++i) wp[i] = 0;
+    }
   }
 };
+
+// ---- the scalar ring Z/(q-1) on the device (DESIGN section 13, "Scalar ring on the device") -------------------------------------
+// Mode 1 of mpvss_ctx_set_rt_scalar takes the device path from rt_scalar_min_shares shares of a whole call.  The threshold is what
+// `tools/modp_rt_rate.py --scalar --ab` measures (profiles/modp_rt_scalar_rate.txt): the smallest n from which the whole call under
+// mode 2 is no slower than the parent's at every larger measured n.  Until that is measured "automatic" means host, as
+// RT_FD_AUTO_ON does for the forward differences.
+size_t rt_scalar_min_shares(int) { return 16384; }   // UNMEASURED placeholder at every width
+constexpr bool RT_SCALAR_AUTO_ON = false;
+
+// THE launch decision of the scalar ring for one whole call of n shares (context lock held); counts the call
+bool rt_scalar_on_device(mpvss_ctx* ctx, const mpvss_modp_group* grp, size_t n) {
+  const int mode = ctx->rt_scalar_mode;
+  const bool dev = grp->has_q && n > 0 &&
+                   (mode == 2 || (mode == 1 && RT_SCALAR_AUTO_ON && n >= rt_scalar_min_shares(grp->lpl)));
+  ++(dev ? ctx->rt_scalar_dev_calls : ctx->rt_scalar_host_calls);
+  return dev;
+}
+
+// the call's device copy of the constants of q' (as rt_upload for q)
+int rt_upload_q(mpvss_ctx* ctx, const mpvss_modp_group* grp, const modp_rt_consts** dev) {
+  RET_IF(ensure(ctx, ctx->rt_consts_q, sizeof(modp_rt_consts)));
+  HIPCHK(ctx, hipMemcpyAsync(ctx->rt_consts_q.p, &grp->cq, sizeof(modp_rt_consts), hipMemcpyHostToDevice, ctx->stream));
+  *dev = (const modp_rt_consts*)ctx->rt_consts_q.p;
+  return 0;
+}
+
+// The dealer's coefficients for k_rt_modq_poly_eval: (a_j mod q') R mod q' as L limbs each, through pinned memory of the context
+// into ctx->rt_sc_coef, and the parities of P at even (a_0) and odd (XOR of all a_j mod (q-1)) positions.  Both copies are the
+// dealer's secret: `wipe` zeroes them whichever way the call ends.
+int rt_stage_coeffs(mpvss_ctx* ctx, const mpvss_modp_group* grp, const uint8_t* coeffs_host, size_t t, int* par_even, int* par_odd,
+                    const uint32_t** coef_dev, RtWipe& wipe) {
+  const size_t LW = rt_L(grp), EB = grp->eb, bytes = t * LW * 4;
+  if (bytes > ctx->rt_sc_pin_cap) {
+    if (ctx->rt_sc_pin) {
+      HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+      HIPCHK(ctx, hipHostFree(ctx->rt_sc_pin));
+      ctx->rt_sc_pin = nullptr;
+      ctx->rt_sc_pin_cap = 0;
+    }
+    const hipError_t e = hipHostMalloc(&ctx->rt_sc_pin, bytes, hipHostMallocDefault);
+    if (e != hipSuccess) {
+      ctx->rt_sc_pin = nullptr;
+      return fail(ctx, MPVSS_E_NOMEM, "hipHostMalloc(coefficient staging)", e);
+    }
+    ctx->rt_sc_pin_cap = bytes;
+  }
+  wipe.pinned.push_back({ctx->rt_sc_pin, bytes});
+  RET_IF(ensure(ctx, ctx->rt_sc_coef, bytes));
+  wipe.device(ctx->rt_sc_coef, bytes);
+  uint32_t* limbs = (uint32_t*)ctx->rt_sc_pin;
+  *par_even = 0;
+  *par_odd = 0;
+  rt_rings(grp, [&](const auto& R) {
+    constexpr int NW = RT_NW(R);
+    uint64_t a[NW], r[NW], one_m[NW];
+    hsc::from_bytes<NW>(one_m, grp->subR_be, true);
+    for (size_t j = 0; j < t; ++j) {
+      hsc::from_bytes<NW>(a, coeffs_host + j * EB, true);
+      R.ord.reduce1(a);
+      if (j == 0) *par_even = (int)(a[0] & 1);
+      *par_odd ^= (int)(a[0] & 1);
+      R.sub.mulmod(r, a, one_m);
+      for (size_t k = 0; k < LW; ++k) {
+        const size_t bit = 29 * k, w = bit / 64, sft = bit % 64;
+        uint64_t v = w < (size_t)NW ? r[w] >> sft : 0;
+        if (sft + 29 > 64 && w + 1 < (size_t)NW) v |= r[w + 1] << (64 - sft);
+        limbs[j * LW + k] = (uint32_t)v & ((1u << 29) - 1);
+      }
+    }
+    for (uint64_t* buf : {a, r}) {
+      volatile uint64_t* wp = buf;
+      for (int i = 0; i < NW; ++i) wp[i] = 0;
+    }
+  });
+  HIPCHK(ctx, hipMemcpyAsync(ctx->rt_sc_coef.p, limbs, bytes, hipMemcpyHostToDevice, ctx->stream));
+  *coef_dev = (const uint32_t*)ctx->rt_sc_coef.p;
+  return 0;
+}
+
+// (-c) mod q' on the device (ctx->rt_sc_c) and c mod 2, for k_rt_modq_responses: c is reduced mod q - 1 first, which keeps its parity
+int rt_stage_cneg(mpvss_ctx* ctx, const mpvss_modp_group* grp, const uint8_t* c_host, const uint8_t** cneg_dev, int* c_parity) {
+  uint8_t neg[RT_EB_MAX];
+  rt_rings(grp, [&](const auto& R) {
+    constexpr int NW = RT_NW(R);
+    uint64_t c[NW], m[NW];
+    hsc::from_bytes<NW>(c, c_host, true);
+    R.ord.reduce1(c);
+    *c_parity = (int)(c[0] & 1);
+    R.sub.reduce1(c);
+    uint64_t o = 0;
+    for (int i = 0; i < NW; ++i) o |= c[i];
+    if (o) hsc::sub_n<NW>(m, R.sub.m, c); else memset(m, 0, sizeof(m));
+    hsc::to_bytes<NW>(neg, m, true);
+  });
+  // the challenge is public; the staging buffer is a workspace of the context and the copy is drained before `neg` goes away
+  RET_IF(ensure(ctx, ctx->rt_sc_c, grp->eb));
+  HIPCHK(ctx, hipMemcpyAsync(ctx->rt_sc_c.p, neg, grp->eb, hipMemcpyHostToDevice, ctx->stream));
+  HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+  *cneg_dev = (const uint8_t*)ctx->rt_sc_c.p;
+  return 0;
+}
+
+const char* const RT_NO_Q = "no device scalar ring for this group: (q-1)/2 must be odd and >= 3 (mpvss_modp_group_has_device_scalar)";
 
 // Shares per k_rt_twin_exp launch: 4096 waves, more than the chip holds at once, and it bounds the bucket scratch the context
 // keeps at 2 x 15 x 65536 numbers (540 MiB at 18 limbs per lane, 270 MiB at 9, 150 MiB at 5) whatever MAX_CHUNK is.  At 27
@@ -860,14 +990,17 @@ bool rt_zero_mod_q(const mpvss_modp_group* grp, const uint8_t* v) {
 // The dealer's group side for n shares: X_i (commit_eval, or g^p_i when commitments is null: the dealer's own polynomial),
 // Y_i = y_i^p_i and a2_i = y_i^w_i through the twin path, a1_i = g^w_i, and the transcript digest.  Outputs in `space`
 // (the host ones optional).  p_values and witnesses staged on the device, and the buckets, are zeroed by `wipe`.
+// secrets_dev: p_values and witnesses are device arrays of the caller whatever `space` says (group_deal's device-side scalar ring:
+// P(i) never leaves HBM); the caller has reset the spans, launched into them already and wipes the two arrays itself.
 int rt_distribute_locked(mpvss_ctx* ctx, const mpvss_modp_group* grp, int space, const uint8_t* commitments, size_t t,
                          const int64_t* positions, const uint8_t* pubkeys, const uint8_t* p_values, const uint8_t* witnesses, size_t n,
-                         uint8_t* x_out, uint8_t* y_out, uint8_t* a1_out, uint8_t* a2_out, uint8_t* digest32_out, RtWipe& wipe) {
+                         uint8_t* x_out, uint8_t* y_out, uint8_t* a1_out, uint8_t* a2_out, uint8_t* digest32_out, RtWipe& wipe,
+                         bool secrets_dev = false) {
   const size_t EB = grp->eb;
   mpvss::Sha256 h;
   if (n > 0) {
     HIPCHK(ctx, hipSetDevice(ctx->device));
-    spans_reset(ctx);
+    if (!secrets_dev) spans_reset(ctx);
     const modp_rt_consts* dc;
     RET_IF(rt_upload(ctx, grp, &dc));
     if (commitments) RET_IF(rt_stage_commitments(ctx, grp, dc, space, commitments, t, n));
@@ -878,9 +1011,9 @@ int rt_distribute_locked(mpvss_ctx* ctx, const mpvss_modp_group* grp, int space,
       const size_t cnt = (n - off < MAX_CHUNK) ? n - off : MAX_CHUNK;
       const void *dy, *dp, *dw;
       RET_IF(stage_in(ctx, space, pubkeys + off * EB, cnt * EB, ctx->rt_in[1], &dy));
-      if (!dev) { wipe.device(ctx->rt_in[2], cnt * EB); wipe.device(ctx->rt_in[3], cnt * EB); }
-      RET_IF(stage_in(ctx, space, p_values + off * EB, cnt * EB, ctx->rt_in[2], &dp));
-      RET_IF(stage_in(ctx, space, witnesses + off * EB, cnt * EB, ctx->rt_in[3], &dw));
+      if (!dev && !secrets_dev) { wipe.device(ctx->rt_in[2], cnt * EB); wipe.device(ctx->rt_in[3], cnt * EB); }
+      RET_IF(stage_in(ctx, secrets_dev ? MPVSS_DEVICE : space, p_values + off * EB, cnt * EB, ctx->rt_in[2], &dp));
+      RET_IF(stage_in(ctx, secrets_dev ? MPVSS_DEVICE : space, witnesses + off * EB, cnt * EB, ctx->rt_in[3], &dw));
       uint8_t *dX = x_out + off * EB, *dY = y_out + off * EB, *d1 = a1_out + off * EB, *d2 = a2_out + off * EB;
       if (!dev) {
         for (DevBuf* b : {&ctx->rt_out[0], &ctx->rt_out[1], &ctx->rt_out[2], &ctx->rt_out_y}) RET_IF(ensure(ctx, *b, cnt * EB));
@@ -1094,8 +1227,57 @@ extern "C" int mpvss_modp_group_distribute(mpvss_ctx* ctx, const mpvss_modp_grou
                               digest32_out, wipe);
 }
 
-// participant.rs:160-286 after "draw the polynomial and the witnesses": P(i) mod (q-1) on host threads, the group side above with
-// X_i = g^P(i), the challenge and the responses r_i = w_i - P(i) c on host threads.
+namespace {
+// group_deal with the scalar ring on the device (n > 0, arguments checked, context lock held).  Positions and witnesses are staged
+// once for the whole call; k_rt_modq_poly_eval leaves P(i) in HBM, the group side reads P and w from there chunk by chunk, the
+// challenge is hashed on the host as ever, and k_rt_modq_responses reads the same two arrays.  P and w of EVERY chunk must
+// survive until the challenge is known, so the two buffers hold all n shares; with the responses' own array (r is copied back from
+// it) the call holds 3 n EB bytes of HBM beside the chunk workspaces: 48 MiB for 65 536 shares of 256 bytes, 72 MiB of 384.  P
+// and w join `wipe`, as do the staged coefficient limbs.  Same bytes as the host path.
+int rt_deal_scalar_dev(mpvss_ctx* ctx, const mpvss_modp_group* grp, const uint8_t* coeffs_host, size_t t, const int64_t* positions_host,
+                       const uint8_t* pubkeys_host, const uint8_t* witnesses_host, size_t n, uint8_t* x_out, uint8_t* y_out,
+                       uint8_t* a1_out, uint8_t* a2_out, uint8_t* digest32_out, uint8_t* challenge_out256, uint8_t* r_out) {
+  const size_t EB = grp->eb;
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  spans_reset(ctx);
+  RtWipe wipe{ctx};
+  const modp_rt_consts* dcq;
+  RET_IF(rt_upload_q(ctx, grp, &dcq));
+  int par_even, par_odd;
+  const uint32_t* coef;
+  RET_IF(rt_stage_coeffs(ctx, grp, coeffs_host, t, &par_even, &par_odd, &coef, wipe));
+  RET_IF(ensure(ctx, ctx->rt_sc_p, n * EB));
+  RET_IF(ensure(ctx, ctx->rt_sc_w, n * EB));
+  wipe.device(ctx->rt_sc_p, n * EB);
+  wipe.device(ctx->rt_sc_w, n * EB);
+  const void* dpos;
+  RET_IF(stage_in(ctx, MPVSS_HOST, positions_host, n * 8, ctx->w->pos, &dpos));
+  HIPCHK(ctx, hipMemcpyAsync(ctx->rt_sc_w.p, witnesses_host, n * EB, hipMemcpyHostToDevice, ctx->stream));
+  uint8_t* dP = (uint8_t*)ctx->rt_sc_p.p;
+  const uint8_t* dW = (const uint8_t*)ctx->rt_sc_w.p;
+  TIMED_LAUNCH(ctx, 4, modp_rt_launch_modq_poly_eval(grp->lpl, coef, (int)t, (const int64_t*)dpos, (int)n, par_even, par_odd, dP, dcq,
+                                                     ctx->stream));                                      // participant.rs:202
+  uint8_t digest[32], challenge[RT_EB_MAX];
+  RET_IF(rt_distribute_locked(ctx, grp, MPVSS_HOST, nullptr, t, positions_host, pubkeys_host, dP, dW, n, x_out, y_out, a1_out, a2_out,
+                              digest, wipe, true));
+  rt_hash_to_scalar(grp, digest, 32, challenge);                 // participant.rs:251-252
+  if (digest32_out) memcpy(digest32_out, digest, 32);
+  if (challenge_out256) memcpy(challenge_out256, challenge, EB);
+  const uint8_t* dcneg;
+  int c_parity;
+  RET_IF(rt_stage_cneg(ctx, grp, challenge, &dcneg, &c_parity));
+  RET_IF(ensure(ctx, ctx->rt_sc_r, n * EB));
+  TIMED_LAUNCH(ctx, 4, modp_rt_launch_modq_responses(grp->lpl, dW, dP, dcneg, c_parity, (int)n, (uint8_t*)ctx->rt_sc_r.p, dcq,
+                                                     ctx->stream));                                      // :255-264
+  HIPCHK(ctx, hipMemcpyAsync(r_out, ctx->rt_sc_r.p, n * EB, hipMemcpyDeviceToHost, ctx->stream));
+  RET_IF(spans_collect(ctx));
+  return MPVSS_OK;
+}
+}  // namespace
+
+// participant.rs:160-286 after "draw the polynomial and the witnesses": P(i) mod (q-1), the group side above with X_i = g^P(i), the
+// challenge and the responses r_i = w_i - P(i) c.  The scalar ring runs on the device (rt_deal_scalar_dev) when
+// mpvss_ctx_set_rt_scalar and the handle allow it, otherwise on host threads.
 extern "C" int mpvss_modp_group_deal(mpvss_ctx* ctx, const mpvss_modp_group* grp, const uint8_t* coeffs_host, size_t t,
                                      const int64_t* positions_host, const uint8_t* pubkeys_host, const uint8_t* witnesses_host, size_t n,
                                      uint8_t* x_out, uint8_t* y_out, uint8_t* a1_out, uint8_t* a2_out, uint8_t* digest32_out,
@@ -1109,6 +1291,9 @@ extern "C" int mpvss_modp_group_deal(mpvss_ctx* ctx, const mpvss_modp_group* grp
     return fail(ctx, MPVSS_E_INVALID, "group_deal: bad argument (t >= 1, n < 2^31)");
   if (t > n) return fail(ctx, MPVSS_E_INVALID, "group_deal: threshold > number of public keys (participant.rs:166)");
   RET_IF(check_positions_host(ctx, positions_host, n));
+  if (rt_scalar_on_device(ctx, grp, n))
+    return rt_deal_scalar_dev(ctx, grp, coeffs_host, t, positions_host, pubkeys_host, witnesses_host, n, x_out, y_out, a1_out, a2_out,
+                              digest32_out, challenge_out256, r_out);
   std::vector<uint8_t> P(n * EB);
   RtWipe wipe{ctx};
   wipe.host.push_back(&P);
@@ -1152,21 +1337,28 @@ extern "C" int mpvss_modp_group_extract_shares(mpvss_ctx* ctx, const mpvss_modp_
   wipe.host.push_back(&hxi);
   wipe.host.push_back(&hw);
   const int threads = host_threads(0);
+  // e2 = w / x on the device (k_rt_modq_mul from the staged w and xinv) or on host threads; the zero-row scan of Y stays here
+  const bool sdev = rt_scalar_on_device(ctx, grp, n);
+  const modp_rt_consts* dcq = nullptr;
+  if (sdev) RET_IF(rt_upload_q(ctx, grp, &dcq));
   for (size_t off = 0; off < n; off += MAX_CHUNK) {
     const size_t cnt = (n - off < MAX_CHUNK) ? n - off : MAX_CHUNK;
     const uint8_t *PK = pk + off * EB, *Y = y + off * EB, *XI = xinv + off * EB, *W = w + off * EB;
     if (dev) {
       RET_IF(small_vec_to_host(ctx, space, PK, cnt * EB, hpk));
       RET_IF(small_vec_to_host(ctx, space, Y, cnt * EB, hy));
-      RET_IF(small_vec_to_host(ctx, space, XI, cnt * EB, hxi));
-      RET_IF(small_vec_to_host(ctx, space, W, cnt * EB, hw));
+      if (!sdev) {
+        RET_IF(small_vec_to_host(ctx, space, XI, cnt * EB, hxi));
+        RET_IF(small_vec_to_host(ctx, space, W, cnt * EB, hw));
+      }
       PK = hpk.data(); Y = hy.data(); XI = hxi.data(); W = hw.data();
     }
     std::atomic<int> zero_row{0};
     hsc::parallel_for(cnt, threads, [&](size_t lo, size_t hi) {
       bool z = false;
       for (size_t i = lo; i < hi; ++i) {
-        rt_rings(grp, [&](const auto& R) { scalar_mul_bytes<RT_NW(R)>(R.ord, true, W + i * EB, XI + i * EB, e2.data() + i * EB); });
+        if (!sdev)
+          rt_rings(grp, [&](const auto& R) { scalar_mul_bytes<RT_NW(R)>(R.ord, true, W + i * EB, XI + i * EB, e2.data() + i * EB); });
         z = z || rt_zero_mod_q(grp, Y + i * EB);
       }
       if (z) zero_row.store(1);
@@ -1178,7 +1370,16 @@ extern "C" int mpvss_modp_group_extract_shares(mpvss_ctx* ctx, const mpvss_modp_
     wipe.device(ctx->rt_in[2], cnt * EB);
     RET_IF(stage_in(ctx, space, xinv + off * EB, cnt * EB, ctx->rt_in[1], &dxi));
     RET_IF(stage_in(ctx, space, w + off * EB, cnt * EB, ctx->rt_in[3], &dw));
-    RET_IF(stage_in(ctx, MPVSS_HOST, e2.data(), cnt * EB, ctx->rt_in[2], &de2));
+    if (sdev && !shared) {
+      de2 = nullptr;                                             // a chunk with a zero row takes the two dependent chains: no e2
+    } else if (sdev) {
+      RET_IF(ensure(ctx, ctx->rt_in[2], cnt * EB));
+      de2 = ctx->rt_in[2].p;
+      TIMED_LAUNCH(ctx, 4, modp_rt_launch_modq_mul(grp->lpl, (const uint8_t*)dw, (const uint8_t*)dxi, (int)cnt, (uint8_t*)ctx->rt_in[2].p,
+                                                   dcq, ctx->stream));
+    } else {
+      RET_IF(stage_in(ctx, MPVSS_HOST, e2.data(), cnt * EB, ctx->rt_in[2], &de2));
+    }
     uint8_t* dS = s_out + off * EB;
     if (!dev) {
       RET_IF(ensure(ctx, ctx->rt_out[0], cnt * EB));
@@ -1293,6 +1494,124 @@ extern "C" int mpvss_modp_group_reconstruct(mpvss_ctx* ctx, const mpvss_modp_gro
       hsc::to_bytes<NW>(hb, x, true);
     });
     memcpy(mask_out32, hb + EB - 32, 32);
+  }
+  RET_IF(spans_collect(ctx));
+  return MPVSS_OK;
+}
+
+// =====================================================================================================================
+// The scalar ring Z/(q-1) of a run-time group on the device: the handle's counterparts of mpvss_modp_poly_eval_device and
+// mpvss_modp_dleq_responses_device, and the ring's product per share.  They need the constants of q' (has_q) and have no host
+// path of their own: a handle without them is MPVSS_E_INVALID.  On ctx->stream under the context lock.
+// =====================================================================================================================
+extern "C" int mpvss_modp_group_has_device_scalar(const mpvss_modp_group* grp) {
+  if (rt_bad_group(grp)) return MPVSS_E_INVALID;
+  return grp->has_q ? 1 : 0;
+}
+
+extern "C" int mpvss_ctx_set_rt_scalar(mpvss_ctx* ctx, int mode) {
+  if (!ctx) return MPVSS_E_INVALID;
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  if (mode < 0 || mode > 2) return fail(ctx, MPVSS_E_INVALID, "set_rt_scalar: mode is 0, 1 or 2");
+  ctx->rt_scalar_mode = mode;
+  return MPVSS_OK;
+}
+
+extern "C" int mpvss_modp_group_scalar_stats(mpvss_ctx* ctx, unsigned long long* device_calls, unsigned long long* host_calls) {
+  if (!ctx) return MPVSS_E_INVALID;
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  if (device_calls) *device_calls = ctx->rt_scalar_dev_calls;
+  if (host_calls) *host_calls = ctx->rt_scalar_host_calls;
+  return MPVSS_OK;
+}
+
+extern "C" int mpvss_modp_group_scalar_min_shares(const mpvss_modp_group* grp) {
+  if (rt_bad_group(grp)) return MPVSS_E_INVALID;
+  return (int)std::min<size_t>(rt_scalar_min_shares(grp->lpl), 0x7fffffff);
+}
+
+extern "C" int mpvss_modp_group_poly_eval_device(mpvss_ctx* ctx, const mpvss_modp_group* grp, const uint8_t* coeffs_host, size_t t,
+                                                 const int64_t* positions_dev, size_t n, uint8_t* out_dev) {
+  if (!ctx) return MPVSS_E_INVALID;
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  if (rt_bad_group(grp)) return fail(ctx, MPVSS_E_INVALID, "group_poly_eval_device: no group");
+  if (n == 0) return MPVSS_OK;
+  if (!coeffs_host || !positions_dev || !out_dev || t == 0 || t > 0x7fffffff || n > 0x7fffffff)
+    return fail(ctx, MPVSS_E_INVALID, "group_poly_eval_device: bad argument (t must be >= 1)");
+  if (!grp->has_q) return fail(ctx, MPVSS_E_INVALID, RT_NO_Q);
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  spans_reset(ctx);
+  std::vector<int64_t> hp(n);          // declared before `wipe`: the copy into it is drained by ~RtWipe before it goes away
+  RtWipe wipe{ctx};
+  const modp_rt_consts* dcq;
+  RET_IF(rt_upload_q(ctx, grp, &dcq));
+  int par_even, par_odd;
+  const uint32_t* coef;
+  RET_IF(rt_stage_coeffs(ctx, grp, coeffs_host, t, &par_even, &par_odd, &coef, wipe));
+  TIMED_LAUNCH(ctx, 4, modp_rt_launch_modq_poly_eval(grp->lpl, coef, (int)t, positions_dev, (int)n, par_even, par_odd, out_dev, dcq,
+                                                     ctx->stream));
+  // positions are validated after the fact, as mpvss_modp_poly_eval_device does (a negative one is the caller's bug)
+  HIPCHK(ctx, hipMemcpyAsync(hp.data(), positions_dev, n * 8, hipMemcpyDeviceToHost, ctx->stream));
+  RET_IF(spans_collect(ctx));
+  for (size_t i = 0; i < n; ++i)
+    if (hp[i] < 0) return fail(ctx, MPVSS_E_INVALID, "negative position (the reference panics: negative exponent)");
+  return MPVSS_OK;
+}
+
+extern "C" int mpvss_modp_group_dleq_responses_device(mpvss_ctx* ctx, const mpvss_modp_group* grp, const uint8_t* w_dev,
+                                                      const uint8_t* alpha_dev, const uint8_t* c_host, size_t n, uint8_t* r_dev_out) {
+  if (!ctx) return MPVSS_E_INVALID;
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  if (rt_bad_group(grp)) return fail(ctx, MPVSS_E_INVALID, "group_dleq_responses_device: no group");
+  if (n == 0) return MPVSS_OK;
+  if (!w_dev || !alpha_dev || !c_host || !r_dev_out || n > 0x7fffffff)
+    return fail(ctx, MPVSS_E_INVALID, "group_dleq_responses_device: bad argument");
+  if (!grp->has_q) return fail(ctx, MPVSS_E_INVALID, RT_NO_Q);
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  spans_reset(ctx);
+  const modp_rt_consts* dcq;
+  RET_IF(rt_upload_q(ctx, grp, &dcq));
+  const uint8_t* dcneg;
+  int c_parity;
+  RET_IF(rt_stage_cneg(ctx, grp, c_host, &dcneg, &c_parity));
+  TIMED_LAUNCH(ctx, 4, modp_rt_launch_modq_responses(grp->lpl, w_dev, alpha_dev, dcneg, c_parity, (int)n, r_dev_out, dcq, ctx->stream));
+  RET_IF(spans_collect(ctx));
+  return MPVSS_OK;
+}
+
+extern "C" int mpvss_modp_group_batch_scalar_mul(mpvss_ctx* ctx, const mpvss_modp_group* grp, int space, const uint8_t* a,
+                                                 const uint8_t* b, size_t n, uint8_t* out) {
+  if (!ctx) return MPVSS_E_INVALID;
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  if (rt_bad_group(grp)) return fail(ctx, MPVSS_E_INVALID, "group_batch_scalar_mul: no group");
+  const size_t EB = grp->eb;
+  if (n == 0) return MPVSS_OK;
+  if (!a || !b || !out || n > 0x7fffffff || (space != MPVSS_HOST && space != MPVSS_DEVICE))
+    return fail(ctx, MPVSS_E_INVALID, "group_batch_scalar_mul: bad argument");
+  if (!grp->has_q) return fail(ctx, MPVSS_E_INVALID, RT_NO_Q);
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  spans_reset(ctx);
+  RtWipe wipe{ctx};
+  const modp_rt_consts* dcq;
+  RET_IF(rt_upload_q(ctx, grp, &dcq));
+  for (size_t off = 0; off < n; off += MAX_CHUNK) {
+    const size_t cnt = (n - off < MAX_CHUNK) ? n - off : MAX_CHUNK;
+    const void *da, *db;
+    if (space == MPVSS_HOST) {                                   // scalars of the ring are secrets wherever the protocol forms products
+      wipe.device(ctx->rt_in[2], cnt * EB);
+      wipe.device(ctx->rt_in[3], cnt * EB);
+      wipe.device(ctx->rt_out[0], cnt * EB);
+    }
+    RET_IF(stage_in(ctx, space, a + off * EB, cnt * EB, ctx->rt_in[2], &da));
+    RET_IF(stage_in(ctx, space, b + off * EB, cnt * EB, ctx->rt_in[3], &db));
+    uint8_t* dout = out + off * EB;
+    if (space == MPVSS_HOST) {
+      RET_IF(ensure(ctx, ctx->rt_out[0], cnt * EB));
+      dout = (uint8_t*)ctx->rt_out[0].p;
+    }
+    TIMED_LAUNCH(ctx, 4, modp_rt_launch_modq_mul(grp->lpl, (const uint8_t*)da, (const uint8_t*)db, (int)cnt, dout, dcq, ctx->stream));
+    if (space == MPVSS_HOST) RET_IF(copy_out(ctx, space, out + off * EB, dout, cnt * EB));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
   }
   RET_IF(spans_collect(ctx));
   return MPVSS_OK;

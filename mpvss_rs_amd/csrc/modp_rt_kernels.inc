@@ -8,6 +8,8 @@
 //   ModpGroup::exp / ::mul                       (src/groups/modp.rs:122-132)      k_rt_dual_exp, k_rt_mul
 //   DLEQ verifier commitments a = g1^r h1^c      (src/dleq.rs:66-84)               k_rt_dual_exp (two tables)
 //   X_i = prod_j C_j^(i^j mod (q-1))             (src/participant.rs:423-434)      k_rt_commit_eval
+//   P(i), r_i = w_i - P(i) c, w_i / x_i in Z/(q-1) (src/polynomial.rs:50-58, src/dleq.rs:42-50, modp.rs:180-182)
+//                                                                                  k_rt_modq_poly_eval, _responses, _mul
 //
 // Layout and program shape are those of the group-14 kernels (modp_kernels.hip): one number per DPP quad, 16 numbers
 // per one-wave workgroup, the second operand of every product staged in LDS, 16-entry window tables in HBM.  The
@@ -765,6 +767,181 @@ __global__ void RT_KERNEL(LPL) k_rt_from_mont(const u32* __restrict__ x_m, int c
   store_canonical<LPL>(out_be + (size_t)x * Width<LPL>::EB, acc, slot, cs, ln, live);
 }
 
+// =======================================================================================
+// The scalar ring Z/(q-1) of a run-time group on the device: the dealer's P(i), the responses r_i = w_i - P(i) c and the
+// participant's e2_i = w_i / x_i (src/polynomial.rs:50-58, src/dleq.rs:42-50, src/groups/modp.rs:180-182).  The decomposition
+// is group 14's (k_modq_* in modp_kernels.hip): for odd q' = (q-1)/2, Z/(q-1) = Z/2 x Z/q'; a scalar is its residue mod q' --
+// in the Montgomery machinery above with `cs` the constants of q', built at the handle's own width (q' has one bit fewer than
+// q: R > 8 q') -- and its parity, and it is lifted to [0, q-1) when it is written.  Every input is an EB-byte value of any size:
+// it enters through to_mont_in, which reduces it mod q'; reducing mod the even q - 1 preserves its parity, so the parity is read
+// from the input's last byte.  Bounds and operation counts: tests/test_modp_rt_scalar_model.py.
+// =======================================================================================
+
+// a += b limb by limb, carries inside the lane and one hand-over to the next lane: almost normalised again.  The sums here stay
+// below 4 q' < R / 2, so the top lane has no carry-out.
+template <int LPL>
+__device__ __forceinline__ void add_limbs(u32 (&a)[LPL], const u32 (&b)[LPL], const Lane& ln) {
+  u32 c = 0;
+#pragma unroll
+  for (int k = 0; k < LPL; ++k) {
+    const u32 v = a[k] + b[k] + c;
+    a[k] = v & MASK;
+    c = v >> W;
+  }
+  a[0] += bn::quad_from_prev(c) & ln.not_low;
+}
+
+// The lane for one more to_mont_in in the same kernel.  to_mont_in reads its input as some hundred byte loads at offsets that
+// depend on the lane's place in the quad; a second input would share those 64-bit offsets with the first, and the compiler
+// keeps all of them alive across the product in between and spills them.  An opaque copy of the place makes it form them again.
+__device__ __forceinline__ Lane lane_again(const Lane& ln) {
+  Lane l2 = ln;
+  asm volatile("" : "+v"(l2.q));
+  return l2;
+}
+
+// store_canonical against q' with a parity: the residue v in [0, q') leaves as the one number in [0, 2 q') = [0, q-1) of that
+// parity, v or v + q' (q' is odd, so adding it flips the low bit); quad lane 0 does the lifting (limbs::slot_canonicalize)
+template <int LPL>
+__device__ __forceinline__ void store_canonical_lift(uint8_t* __restrict__ out, const u32 (&a)[LPL], u32* slot,
+                                                     const modp_rt_consts* __restrict__ cs, const Lane& ln, bool write, int parity) {
+  constexpr int L = Width<LPL>::L, EB = Width<LPL>::EB, WPL = EB / 16;
+  slot_store<LPL>(slot, a, ln);
+  __builtin_amdgcn_wave_barrier();
+  if (ln.q == 0) limbs::slot_canonicalize<L>(slot, cs->n, parity);
+  __builtin_amdgcn_wave_barrier();
+  if (write) {
+    u32* out32 = reinterpret_cast<u32*>(out);
+#pragma unroll
+    for (int i = 0; i < WPL; ++i) {
+      const int wd = (int)ln.q * WPL + i;
+      out32[4 * WPL - 1 - wd] = __builtin_bswap32(limbs::slot_word32<L, EB>(slot, wd));
+    }
+  }
+  __builtin_amdgcn_wave_barrier();
+}
+
+// ---------------------------------------------------------------------------------------
+// out[x] = a[x] b[x] mod (q-1).  Steps: a R; b R; a R b R R^-1 = a b R; times plain 1.  2 entry products + 1 + 1 exit.
+// Parity: that of the integer product.
+// ---------------------------------------------------------------------------------------
+template <int LPL>
+__global__ void RT_KERNEL(LPL) k_rt_modq_mul(const uint8_t* __restrict__ a_be, const uint8_t* __restrict__ b_be, int count,
+                                             uint8_t* __restrict__ out_be, const modp_rt_consts* __restrict__ cs) {
+  constexpr int SLOT = Width<LPL>::SLOT, EB = Width<LPL>::EB;
+  __shared__ __attribute__((aligned(16))) u32 lds[RT_NUMS * SLOT];
+  const Lane ln = make_lane();
+  const int xi = blockIdx.x * RT_NUMS + (threadIdx.x >> 2);
+  const bool live = xi < count;
+  const int x = live ? xi : count - 1;
+  u32* slot = lds + (threadIdx.x >> 2) * SLOT;
+  const u32 n0inv = cs->n0inv;
+  const uint8_t* pa = a_be + (size_t)x * EB;
+  const uint8_t* pb = b_be + (size_t)x * EB;
+  const int parity = (int)(pa[EB - 1] & pb[EB - 1] & 1u);
+  u32 n[LPL], acc[LPL], v[LPL];
+  load_lane_limbs<LPL>(n, cs->n, ln);
+  to_mont_in<LPL>(acc, slot, pa, cs, n, n0inv, ln);
+  to_mont_in<LPL>(v, slot, pb, cs, n, n0inv, lane_again(ln));
+  slot_store<LPL>(slot, v, ln);
+#pragma nounroll
+  for (int step = 0; step < 2; ++step) {
+    if (step == 1) slot_fill_from_global<LPL>(slot, cs->one, ln);
+    __builtin_amdgcn_wave_barrier();
+    mont_mul<N0INV_RUNTIME>(acc, acc, slot, n, ln, n0inv);
+    __builtin_amdgcn_wave_barrier();
+  }
+  store_canonical_lift<LPL>(out_be + (size_t)x * EB, acc, slot, cs, ln, live, parity);
+}
+
+// ---------------------------------------------------------------------------------------
+// r[x] = w[x] - alpha[x] c mod (q-1) for one shared c.
+//   cneg_be : (-c) mod q' as EB big-endian bytes (device), c_parity = c mod 2
+// Steps: (-c) R; alpha R and (-c) R alpha R R^-1 = -alpha c R (< 2 q'); w R (< 2 q'), added in the Montgomery domain (< 4 q' < R),
+// times plain 1 (back below 2 q').  3 entry products + 1 + 1 exit.  Parity: w ^ (alpha & c) in the lowest bit.
+// ---------------------------------------------------------------------------------------
+template <int LPL>
+__global__ void RT_KERNEL(LPL) k_rt_modq_responses(const uint8_t* __restrict__ w_be, const uint8_t* __restrict__ alpha_be,
+                                                   const uint8_t* __restrict__ cneg_be, int c_parity, int count,
+                                                   uint8_t* __restrict__ out_be, const modp_rt_consts* __restrict__ cs) {
+  constexpr int SLOT = Width<LPL>::SLOT, EB = Width<LPL>::EB;
+  __shared__ __attribute__((aligned(16))) u32 lds[RT_NUMS * SLOT];
+  const Lane ln = make_lane();
+  const int xi = blockIdx.x * RT_NUMS + (threadIdx.x >> 2);
+  const bool live = xi < count;
+  const int x = live ? xi : count - 1;
+  u32* slot = lds + (threadIdx.x >> 2) * SLOT;
+  const u32 n0inv = cs->n0inv;
+  const uint8_t* pw = w_be + (size_t)x * EB;
+  const uint8_t* pal = alpha_be + (size_t)x * EB;
+  const int parity = (int)((pw[EB - 1] ^ (pal[EB - 1] & (uint8_t)c_parity)) & 1u);
+  u32 n[LPL], acc[LPL], v[LPL];
+  load_lane_limbs<LPL>(n, cs->n, ln);
+  to_mont_in<LPL>(acc, slot, cneg_be, cs, n, n0inv, ln);
+  to_mont_in<LPL>(v, slot, pal, cs, n, n0inv, lane_again(ln));
+  slot_store<LPL>(slot, v, ln);
+  __builtin_amdgcn_wave_barrier();
+  mont_mul<N0INV_RUNTIME>(acc, acc, slot, n, ln, n0inv);           // -alpha c R
+  __builtin_amdgcn_wave_barrier();
+  to_mont_in<LPL>(v, slot, pw, cs, n, n0inv, lane_again(ln));
+  add_limbs<LPL>(acc, v, ln);                                      // (w - alpha c) R, < 4 q'
+  slot_fill_from_global<LPL>(slot, cs->one, ln);
+  __builtin_amdgcn_wave_barrier();
+  mont_mul<N0INV_RUNTIME>(acc, acc, slot, n, ln, n0inv);
+  __builtin_amdgcn_wave_barrier();
+  store_canonical_lift<LPL>(out_be + (size_t)x * EB, acc, slot, cs, ln, live, parity);
+}
+
+// ---------------------------------------------------------------------------------------
+// out[x] = P(positions[x]) mod (q-1), P = sum_j a_j X^j, by Horner's rule in Montgomery form.
+//   coef_m      : [t][L] limbs of (a_j mod q') R mod q' (canonical; the dealer's secret, staged and wiped by the caller)
+//   positions   : 0 <= i < 2^63, used as integers: three limbs, which enter Montgomery form by the long product of to_mont_in
+//   par_even/odd: parity of P at even / odd positions (a_0, resp. the XOR of all a_j)
+// acc <- acc iR R^-1 + a_j R with a normalising add: acc < 4 q' before every product (a product of a < 4 q' and b < 2 q' is
+// below q' + 8 q'^2 / R < 2 q'), t - 1 products per share, 1 entry and 1 exit.  One product site in the loop: the last round
+// multiplies by plain 1 and adds nothing.
+// ---------------------------------------------------------------------------------------
+template <int LPL>
+__global__ void RT_KERNEL(LPL) k_rt_modq_poly_eval(const u32* __restrict__ coef_m, int t, const int64_t* __restrict__ positions, int count,
+                                                   int par_even, int par_odd, uint8_t* __restrict__ out_be,
+                                                   const modp_rt_consts* __restrict__ cs) {
+  constexpr int L = Width<LPL>::L, SLOT = Width<LPL>::SLOT, EB = Width<LPL>::EB, IN_ROWS = Width<LPL>::IN_ROWS;
+  __shared__ __attribute__((aligned(16))) u32 lds[RT_NUMS * SLOT];
+  const Lane ln = make_lane();
+  const int xi = blockIdx.x * RT_NUMS + (threadIdx.x >> 2);
+  const bool live = xi < count;
+  const int x = live ? xi : count - 1;
+  u32* slot = lds + (threadIdx.x >> 2) * SLOT;
+  const u32 n0inv = cs->n0inv;
+  const u64 pos = (u64)positions[x];
+  u32 n[LPL], acc[LPL], v[LPL];
+  load_lane_limbs<LPL>(n, cs->n, ln);
+  // i R mod q' (< 2 q'), left in the slot for the whole loop
+#pragma unroll
+  for (int j = 0; j < IN_ROWS; j += 4) {
+    const int jj = j + (int)ln.q;
+    if (jj < IN_ROWS) slot[jj] = jj < 3 ? (u32)(pos >> (W * jj)) & MASK : 0u;
+  }
+  load_lane_limbs<LPL>(v, cs->kin, ln);
+  __builtin_amdgcn_wave_barrier();
+  mont_mul<N0INV_RUNTIME, false, IN_ROWS / LPL>(acc, v, slot, n, ln, n0inv);
+  __builtin_amdgcn_wave_barrier();
+  slot_store<LPL>(slot, acc, ln);
+  load_lane_limbs<LPL>(acc, coef_m + (size_t)(t - 1) * L, ln);
+#pragma nounroll
+  for (int j = t - 2; j >= -1; --j) {
+    if (j < 0) slot_fill_from_global<LPL>(slot, cs->one, ln);
+    __builtin_amdgcn_wave_barrier();
+    mont_mul<N0INV_RUNTIME>(acc, acc, slot, n, ln, n0inv);
+    __builtin_amdgcn_wave_barrier();
+    if (j >= 0) {
+      load_lane_limbs<LPL>(v, coef_m + (size_t)j * L, ln);
+      add_limbs<LPL>(acc, v, ln);
+    }
+  }
+  store_canonical_lift<LPL>(out_be + (size_t)x * EB, acc, slot, cs, ln, live, (pos & 1) ? par_odd : par_even);
+}
+
 // ---------------------------------------------------------------------------------------
 // launchers: RT_FN names them (modp_rt_launch_* here or modp_rt27_launch_* in the wide unit), RT_DISPATCH launches the
 // instance of a width this unit holds, RT_ELSEWHERE hands a width of the other unit over to it
@@ -892,6 +1069,31 @@ extern "C" int RT_FN(launch_from_mont)(int lpl, const uint32_t* x_m, int count, 
   RT_ELSEWHERE(launch_from_mont, lpl, x_m, count, out_be, cs, s);
   if (count <= 0) return 0;
   RT_DISPATCH(lpl, k_rt_from_mont, dim3(rt_grid(count)), dim3(64), 0, s, x_m, count, out_be, cs);
+  return (int)hipGetLastError();
+}
+
+// the scalar ring Z/(q-1): csq is the device image of the constants of q' = (q-1)/2
+extern "C" int RT_FN(launch_modq_mul)(int lpl, const uint8_t* a_be, const uint8_t* b_be, int count, uint8_t* out_be,
+                                      const modp_rt_consts* csq, hipStream_t s) {
+  RT_ELSEWHERE(launch_modq_mul, lpl, a_be, b_be, count, out_be, csq, s);
+  if (count <= 0) return 0;
+  RT_DISPATCH(lpl, k_rt_modq_mul, dim3(rt_grid(count)), dim3(64), 0, s, a_be, b_be, count, out_be, csq);
+  return (int)hipGetLastError();
+}
+
+extern "C" int RT_FN(launch_modq_responses)(int lpl, const uint8_t* w_be, const uint8_t* alpha_be, const uint8_t* cneg_be, int c_parity,
+                                            int count, uint8_t* out_be, const modp_rt_consts* csq, hipStream_t s) {
+  RT_ELSEWHERE(launch_modq_responses, lpl, w_be, alpha_be, cneg_be, c_parity, count, out_be, csq, s);
+  if (count <= 0) return 0;
+  RT_DISPATCH(lpl, k_rt_modq_responses, dim3(rt_grid(count)), dim3(64), 0, s, w_be, alpha_be, cneg_be, c_parity, count, out_be, csq);
+  return (int)hipGetLastError();
+}
+
+extern "C" int RT_FN(launch_modq_poly_eval)(int lpl, const uint32_t* coef_m, int t, const int64_t* positions, int count, int par_even,
+                                            int par_odd, uint8_t* out_be, const modp_rt_consts* csq, hipStream_t s) {
+  RT_ELSEWHERE(launch_modq_poly_eval, lpl, coef_m, t, positions, count, par_even, par_odd, out_be, csq, s);
+  if (count <= 0 || t <= 0) return 0;
+  RT_DISPATCH(lpl, k_rt_modq_poly_eval, dim3(rt_grid(count)), dim3(64), 0, s, coef_m, t, positions, count, par_even, par_odd, out_be, csq);
   return (int)hipGetLastError();
 }
 #endif  // RT_FD_ONLY

@@ -42,3 +42,15 @@ int MODP_RT_FN(launch_fd_chains)(int lpl, const uint32_t* seeds_m, int t, int n,
                              const modp_rt_consts* cs, hipStream_t s);
 /* out[x] = canonical EB bytes of x_m[x] (Montgomery limbs < 2N) */
 int MODP_RT_FN(launch_from_mont)(int lpl, const uint32_t* x_m, int count, uint8_t* out_be, const modp_rt_consts* cs, hipStream_t s);
+/* The scalar ring Z/(q-1) (csq: the device image of the constants of q' = (q-1)/2, odd and >= 3, at the handle's width; every
+   value EB big-endian bytes of any size, every result canonical in [0, q-1)).
+   out[x] = a[x] b[x] mod (q-1) */
+int MODP_RT_FN(launch_modq_mul)(int lpl, const uint8_t* a_be, const uint8_t* b_be, int count, uint8_t* out_be, const modp_rt_consts* csq,
+                            hipStream_t s);
+/* r[x] = w[x] - alpha[x] c mod (q-1) for one shared c: cneg_be = (-c) mod q' (EB bytes on the device), c_parity = c mod 2 */
+int MODP_RT_FN(launch_modq_responses)(int lpl, const uint8_t* w_be, const uint8_t* alpha_be, const uint8_t* cneg_be, int c_parity, int count,
+                                  uint8_t* out_be, const modp_rt_consts* csq, hipStream_t s);
+/* out[x] = P(positions[x]) mod (q-1): coef_m [t][L] limbs of (a_j mod q') R mod q', 0 <= positions < 2^63, par_even / par_odd the
+   parity of P at even / odd positions */
+int MODP_RT_FN(launch_modq_poly_eval)(int lpl, const uint32_t* coef_m, int t, const int64_t* positions, int count, int par_even, int par_odd,
+                                  uint8_t* out_be, const modp_rt_consts* csq, hipStream_t s);

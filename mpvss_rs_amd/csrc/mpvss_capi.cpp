@@ -156,8 +156,9 @@ struct mpvss_ctx {
   void* pin = nullptr;
   size_t pin_cap = 0;
   hipEvent_t ev[2] = {nullptr, nullptr};
-  double kernel_ms[4] = {-1, -1, -1, -1};   // 0 X path, 1 comb_dual_exp (a1), 2 table builds, 3 dual_exp (a2 / exp)
-  int kernel_launches[4] = {0, 0, 0, 0};
+  // 0 X path, 1 comb_dual_exp (a1), 2 table builds, 3 dual_exp (a2 / exp), 4 the scalar-ring kernels of a run-time group
+  double kernel_ms[5] = {-1, -1, -1, -1, -1};
+  int kernel_launches[5] = {0, 0, 0, 0, 0};
   struct Span { int id; hipEvent_t a, b; };
   struct SpanSet {
     std::vector<Span> spans;
@@ -337,6 +338,13 @@ struct mpvss_ctx {
   EcWork ecwork;
   // workspace of the run-time MODP group entry points (capi_modp_rt.inc), used under `mu`
   DevBuf rt_consts, rt_in[6], rt_out[3], rt_tab1, rt_tab2, rt_tabg, rt_cm, rt_small[2];
+  // the scalar ring Z/(q-1) on the device (capi_modp_rt.inc, "scalar ring on the device"): the constants of q', the staged
+  // coefficient limbs (pinned + device), P(i), w and the responses of a whole deal, and -c
+  DevBuf rt_consts_q, rt_sc_coef, rt_sc_p, rt_sc_w, rt_sc_c, rt_sc_r;
+  void* rt_sc_pin = nullptr;
+  size_t rt_sc_pin_cap = 0;
+  int rt_scalar_mode = 1;                        // mpvss_ctx_set_rt_scalar
+  unsigned long long rt_scalar_dev_calls = 0, rt_scalar_host_calls = 0;   // whole calls (mpvss_modp_group_scalar_stats)
   DevBuf rt_out_y, rt_buckets;   // the dealer's fourth result array; bucket scratch of k_rt_twin_exp (one chunk)
   // forward differences for X of a run-time group (rt_commit_eval_dev): inverted commitments (bytes, then Montgomery form), seed
   // positions, seeds [2][S][t][L], X in limbs [n][L], the chain kernel's scratch -- grown on demand
@@ -350,6 +358,7 @@ struct mpvss_ctx {
     return {&rt_consts, &rt_in[0], &rt_in[1], &rt_in[2], &rt_in[3], &rt_in[4], &rt_in[5], &rt_out[0], &rt_out[1], &rt_out[2],
             &rt_tab1, &rt_tab2, &rt_tabg, &rt_cm, &rt_small[0], &rt_small[1], &rt_out_y, &rt_buckets,
             &rt_fd_inv, &rt_cm_inv, &rt_fd_pos, &rt_fd_seeds, &rt_fd_x, &rt_fd_park,
+            &rt_consts_q, &rt_sc_coef, &rt_sc_p, &rt_sc_w, &rt_sc_c, &rt_sc_r,
             &rt_comb[0].buf, &rt_comb[1].buf, &rt_comb[2].buf, &rt_comb[3].buf};
   }
   // fixed-base combs of run-time groups (rt_comb_for, capi_modp_rt.inc), used under `mu`: keyed by the bytes (q, base) -- a handle
@@ -516,8 +525,8 @@ void spans_reset(mpvss_ctx* ctx) {
   if (ctx->sp == &ctx->main_spans)
     for (double& m : ctx->kernel_ms) m = -1;
 }
-int spans_sum(mpvss_ctx* ctx, mpvss_ctx::SpanSet& ss, double out[4]) {
-  for (int i = 0; i < 4; ++i) { out[i] = 0; ctx->kernel_launches[i] = 0; }
+int spans_sum(mpvss_ctx* ctx, mpvss_ctx::SpanSet& ss, double out[5]) {
+  for (int i = 0; i < 5; ++i) { out[i] = 0; ctx->kernel_launches[i] = 0; }
   for (auto& s : ss.spans) {
     float ms = 0;
     HIPCHK(ctx, hipEventElapsedTime(&ms, s.a, s.b));
@@ -854,6 +863,7 @@ extern "C" void mpvss_ctx_destroy(mpvss_ctx* ctx) {
     delete xb;
   }
   if (ctx->pin) (void)hipHostFree(ctx->pin);
+  if (ctx->rt_sc_pin) (void)hipHostFree(ctx->rt_sc_pin);
   if (ctx->consts) (void)hipFree(ctx->consts);
   if (ctx->consts_q) (void)hipFree(ctx->consts_q);
   for (auto& e : ctx->scalar_ring) {
@@ -930,12 +940,12 @@ extern "C" int mpvss_ctx_synchronize(mpvss_ctx* ctx) {
 }
 
 extern "C" double mpvss_last_kernel_ms(const mpvss_ctx* ctx, int kernel_id) {
-  if (!ctx || kernel_id < 0 || kernel_id > 3) return -1;
+  if (!ctx || kernel_id < 0 || kernel_id > 4) return -1;
   return ctx->kernel_ms[kernel_id];
 }
 
 extern "C" int mpvss_last_kernel_launches(const mpvss_ctx* ctx, int kernel_id) {
-  if (!ctx || kernel_id < 0 || kernel_id > 3) return -1;
+  if (!ctx || kernel_id < 0 || kernel_id > 4) return -1;
   return ctx->kernel_launches[kernel_id];
 }
 

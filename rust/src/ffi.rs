@@ -287,6 +287,17 @@ unsafe extern "C" {
                                            n: usize, r_out: *mut u8, threads: c_int) -> c_int;
     pub fn mpvss_modp_group_poly_eval(grp: *const mpvss_modp_group, coeffs: *const u8, t: usize, positions: *const i64, n: usize,
                                       out: *mut u8, threads: c_int) -> c_int;
+    // the scalar ring Z/(q-1) of a run-time group on the device
+    pub fn mpvss_modp_group_has_device_scalar(grp: *const mpvss_modp_group) -> c_int;
+    pub fn mpvss_modp_group_scalar_min_shares(grp: *const mpvss_modp_group) -> c_int;
+    pub fn mpvss_ctx_set_rt_scalar(ctx: *mut mpvss_ctx, mode: c_int) -> c_int;
+    pub fn mpvss_modp_group_scalar_stats(ctx: *mut mpvss_ctx, device_calls: *mut c_ulonglong, host_calls: *mut c_ulonglong) -> c_int;
+    pub fn mpvss_modp_group_poly_eval_device(ctx: *mut mpvss_ctx, grp: *const mpvss_modp_group, coeffs_host: *const u8, t: usize,
+                                             positions_dev: *const i64, n: usize, out_dev: *mut u8) -> c_int;
+    pub fn mpvss_modp_group_dleq_responses_device(ctx: *mut mpvss_ctx, grp: *const mpvss_modp_group, w_dev: *const u8,
+                                                  alpha_dev: *const u8, c_host: *const u8, n: usize, r_dev_out: *mut u8) -> c_int;
+    pub fn mpvss_modp_group_batch_scalar_mul(ctx: *mut mpvss_ctx, grp: *const mpvss_modp_group, space: c_int, a: *const u8, b: *const u8,
+                                             n: usize, out: *mut u8) -> c_int;
     // ---- hashing helpers
     pub fn mpvss_sha256(data: *const u8, len: usize, out32: *mut u8);
     pub fn mpvss_modp_hash_to_scalar(data: *const u8, len: usize, out256: *mut u8);

@@ -40,7 +40,15 @@ Host buffers in and out (the calls' own staging included), best of `--reps` afte
 measurement.  Usage: python tools/modp_rt_rate.py [--quick] [--reps 3] [--legs rates,twin,deal,comb,verify] [--comb | --fd] [--ab PARENT [--rounds 2]]
   fd          (--fd) X_i of a run-time group by forward differences: timer 0 of group_commit_eval at (4096, 64), (16384, 128),
               (65536, 256), 1024 and 2048 bits, per chain count, and whole group_verify_distribution calls; --fd --ab PARENT takes
-              turns with a built checkout of the parent commit and writes profiles/modp_rt_fd_rate.txt (one 3072-bit row too)."""
+              turns with a built checkout of the parent commit and writes profiles/modp_rt_fd_rate.txt (one 3072-bit row too).
+  scalar      (--scalar) the scalar ring Z/(q-1) of a run-time group on the device: whole group_deal calls at (1024, 32), (4096, 64),
+              (16384, 128), (65536, 256) and whole group_extract_shares calls at n = 1024, 4096, 65536, for 1024 and 2048 bits
+              (--scalar-wide: the one 3072-bit row, group_deal at (4096, 64)).  --scalar-parts parent: the library under test as it
+              is (host threads before this path existed); mode2: mpvss_ctx_set_rt_scalar(2), with the time of the scalar-ring
+              kernels (timer 4).  --scalar --ab PARENT: fresh processes of a built checkout of the parent commit and of this
+              build under mode 2 take turns, best of the rounds, into profiles/modp_rt_scalar_rate.txt; rt_scalar_min_shares of
+              a width is the smallest measured n from which mode 2's whole call is no slower than the parent's at every larger
+              measured n (1 if that holds everywhere).  No speed gate."""
 import argparse
 import json
 import os
@@ -348,6 +356,81 @@ def ab_comb(a):
             f.write(json.dumps(row) + "\n")
 
 
+SCALAR_DEAL = [(1024, 32), (4096, 64), (16384, 128), (65536, 256)]
+SCALAR_EXTRACT = [1024, 4096, 65536]
+
+
+def scalar_leg(eng, a, rng):
+    mode2 = a.scalar_parts == "mode2"
+    if mode2:
+        eng.set_rt_scalar(2)
+    if a.scalar_wide:
+        import modp_rt_wide_helpers as WH
+        groups = [(3072, ModpGroup(WH.group15(), elem_bytes=WH.EB), WH.EB)]
+        deal, extract = [(4096, 64)], []
+    else:
+        groups = [(bits, ModpGroup(H.rfc_prime(bits)), 256) for bits in (1024, 2048)]
+        deal, extract = (SCALAR_DEAL[:2], SCALAR_EXTRACT[:1]) if a.quick else (SCALAR_DEAL, SCALAR_EXTRACT)
+
+    def rb(n, bits, eb):
+        return b"".join(rng.getrandbits(bits).to_bytes(eb, "big") for _ in range(n))
+
+    for bits, grp, eb in groups:
+        for n, t in deal:
+            coeffs, pos = rb(t, bits - 1, eb), list(range(1, n + 1))
+            y, w = rb(n, bits - 1, eb), rb(n, bits - 1, eb)
+            s = best(lambda: eng.group_deal(grp, coeffs, pos, y, w), a.reps)
+            row = {"what": "scalar", "call": "group_deal", "bits": bits, "n": n, "t": t, "whole_s": round(s, 5)}
+            if mode2:
+                row["scalar_kernel_ms"] = round(max(0.0, eng.kernel_ms(4)), 3)
+            print(json.dumps(row), flush=True)
+        for n in extract:
+            pk, y, xi, w = (rb(n, bits - 1, eb) for _ in range(4))
+            s = best(lambda: eng.group_extract_shares(grp, pk, y, xi, w), a.reps)
+            row = {"what": "scalar", "call": "group_extract_shares", "bits": bits, "n": n, "t": 0, "whole_s": round(s, 5)}
+            if mode2:
+                row["scalar_kernel_ms"] = round(max(0.0, eng.kernel_ms(4)), 3)
+            print(json.dumps(row), flush=True)
+
+
+def ab_scalar(a):
+    """--scalar --ab PARENT: fresh processes of the parent build and of this build under mode 2 take turns; best of the rounds"""
+    if not os.path.exists(os.path.join(a.ab, "mpvss_rs_amd", "libmpvss_hip.so")):
+        sys.exit("modp_rt_rate --scalar --ab: the parent checkout is not built")
+    common = ["--legs", "scalar", "--reps", str(a.reps)] + (["--quick"] if a.quick else [])
+    lines, ms, kern = [], {}, {}
+    for wide in ([], ["--scalar-wide"]):
+        for rnd in range(a.rounds):
+            for part, extra in (("parent", ["--package-root", a.ab]), ("mode2", [])):
+                for row in child(common + wide + ["--scalar-parts", part] + extra, None, [], a.deal_limit):
+                    row.update(part=part, round=rnd)
+                    key = (part, row["call"], row["bits"], row["n"], row["t"])
+                    ms[key] = min(ms.get(key, row["whole_s"]), row["whole_s"])
+                    if "scalar_kernel_ms" in row:
+                        kern[key] = min(kern.get(key, row["scalar_kernel_ms"]), row["scalar_kernel_ms"])
+                    lines.append(row)
+    for bits in sorted({k[2] for k in ms}):
+        for call in ("group_deal", "group_extract_shares"):
+            shapes = sorted({k[3:] for k in ms if k[1] == call and k[2] == bits})
+            ok = []
+            for n, t in shapes:
+                pa, m2 = ms["parent", call, bits, n, t], ms["mode2", call, bits, n, t]
+                ok.append(m2 <= pa)
+                lines.append({"what": "scalar_ab", "call": call, "bits": bits, "n": n, "t": t, "parent_whole_s": pa, "mode2_whole_s": m2,
+                              "mode2_scalar_kernel_ms": kern.get(("mode2", call, bits, n, t)), "parent_over_mode2": round(pa / m2, 3)})
+            if shapes:
+                first = next((shapes[i][0] for i in range(len(shapes)) if all(ok[i:])), None)
+                lines.append({"what": "scalar_crossover", "call": call, "bits": bits,
+                              "min_shares": 1 if first == shapes[0][0] else first, "measured_shapes": shapes})
+    for row in lines:
+        if row["what"].startswith("scalar_"):
+            print(json.dumps(row), flush=True)
+    os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+    with open(a.out, "w") as f:
+        for row in lines:
+            f.write(json.dumps(row) + "\n")
+
+
 def ab_fd(a):
     """--fd --ab PARENT: fresh processes of the parent build (Horner's rule) and of this build (mode 2 per chain count) take turns;
     best of the rounds.  rt_fd_chains is the best chain count per shape, rt_fd_min_shares the smallest measured n from which
@@ -405,6 +488,9 @@ def main():
     ap.add_argument("--fd", action="store_true", help="forward differences for X: alone, the fd leg; with --ab, its interleaved A/B")
     ap.add_argument("--fd-parts", default="fd", help="of the fd leg: parent (Horner's rule of the library under test), fd (mode 2 per chain count)")
     ap.add_argument("--fd-wide", action="store_true", help="of the fd leg: the one 3072-bit row, (16384, 128)")
+    ap.add_argument("--scalar", action="store_true", help="the scalar ring on the device: alone, the scalar leg; with --ab, its interleaved A/B")
+    ap.add_argument("--scalar-parts", default="mode2", help="of the scalar leg: parent (the library under test as it is), mode2 (set_rt_scalar(2))")
+    ap.add_argument("--scalar-wide", action="store_true", help="of the scalar leg: the one 3072-bit row, group_deal at (4096, 64)")
     ap.add_argument("--package-root", default=None, help="import mpvss_rs_amd (bindings and library) from this checkout")
     ap.add_argument("--ab", default=None, metavar="PARENT", help="the interleaved A/B against a built checkout of the parent commit")
     ap.add_argument("--rounds", type=int, default=2, help="of --ab: how often the three processes take turns")
@@ -413,13 +499,15 @@ def main():
     ap.add_argument("--out", default=None, help="of --ab: the file written (profiles/modp_rt_deal_rate.txt, or _comb_rate.txt)")
     a = ap.parse_args()
     if a.out is None:
-        a.out = os.path.join(ROOT, "profiles", "modp_rt_fd_rate.txt" if a.fd else "modp_rt_comb_rate.txt" if a.comb else "modp_rt_deal_rate.txt")
+        a.out = os.path.join(ROOT, "profiles", "modp_rt_scalar_rate.txt" if a.scalar else "modp_rt_fd_rate.txt" if a.fd else "modp_rt_comb_rate.txt" if a.comb else "modp_rt_deal_rate.txt")
     if a.ab:
-        return ab_fd(a) if a.fd else ab_comb(a) if a.comb else ab(a)
+        return ab_scalar(a) if a.scalar else ab_fd(a) if a.fd else ab_comb(a) if a.comb else ab(a)
     if a.comb:
         a.legs = "comb"
     if a.fd:
         a.legs = "fd"
+    if a.scalar:
+        a.legs = "scalar"
     load_package(a.package_root)
     eng = Engine(0)
     rng = random.Random(1)
@@ -434,6 +522,8 @@ def main():
         verify_leg(eng, a, rng)
     if "fd" in legs:
         fd_leg(eng, a, rng)
+    if "scalar" in legs:
+        scalar_leg(eng, a, rng)
     if "rates" not in legs:
         eng.close()
         return
