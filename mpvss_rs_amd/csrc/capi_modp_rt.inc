@@ -1,8 +1,15 @@
 // C ABI of a run-time MODP group (include/mpvss_hip.h, "MODP groups of a run-time modulus"): the group handle, its
 // host-side constants and hash_to_scalar, and the batched entry points over modp_rt_kernels.hip.  Included at the end
-// of mpvss_capi.cpp (it uses the context, staging and transcript helpers defined there).
+// of mpvss_capi.cpp (it uses the context, staging and transcript helpers defined there; the transcript is framed by
+// frame_update / frame_shares / frame_min_bytes_update at the handle's element size).
+//
+// Every entry point that touches the device has the same shape: the argument check with its error strings, one RtCall
+// (below) for the device, the constants, the chunk loop, the choice of space, the copies back and the wiping of secrets,
+// and in between only what is its own -- which buffers its arrays use, which of them are secret, what it launches and
+// what it hashes.  The launch decisions (rt_comb_for, rt_dleq_dev, rt_commit_eval_dev with rt_fd_prepare and
+// rt_fd_positions_ok, rt_twin_dev, rt_fixed_base_dev, rt_scalar_on_device, rt_product_tree) are single places of their own.
 
-constexpr size_t RT_EB_MAX = 384;     // the widest element / scalar of a handle (mpvss_modp_group_create_wide)
+constexpr size_t RT_EB_MAX = FRAME_EB_MAX;     // the widest element / scalar of a handle (mpvss_modp_group_create_wide): 384 bytes
 
 // q, q - 1 and (q-1)/2 for the host-side scalar ring (host_scalar.h) at NW 64-bit words
 template <int NW_>
@@ -96,13 +103,187 @@ int rt_lpl_for_bits(int bits) {
   return 0;
 }
 
-// the call's device copy of the group constants (context workspace, stream order)
-int rt_upload(mpvss_ctx* ctx, const mpvss_modp_group* grp, const modp_rt_consts** dev) {
-  RET_IF(ensure(ctx, ctx->rt_consts, sizeof(modp_rt_consts)));
-  HIPCHK(ctx, hipMemcpyAsync(ctx->rt_consts.p, &grp->c, sizeof(modp_rt_consts), hipMemcpyHostToDevice, ctx->stream));
-  *dev = (const modp_rt_consts*)ctx->rt_consts.p;
+// the call's device copy of one image of constants, of q or of q' (context workspace, stream order)
+int rt_upload(mpvss_ctx* ctx, const modp_rt_consts& image, DevBuf& buf, const modp_rt_consts** dev) {
+  RET_IF(ensure(ctx, buf, sizeof(modp_rt_consts)));
+  HIPCHK(ctx, hipMemcpyAsync(buf.p, &image, sizeof(modp_rt_consts), hipMemcpyHostToDevice, ctx->stream));
+  *dev = (const modp_rt_consts*)buf.p;
   return 0;
 }
+
+// zero what held secrets whichever way the call ends (context lock held): device buffers in stream order, then the stream is
+// drained; host vectors word by word
+struct RtWipe {
+  mpvss_ctx* ctx;
+  std::vector<std::pair<DevBuf*, size_t>> dev;
+  std::vector<std::vector<uint8_t>*> host;
+  std::vector<std::pair<void*, size_t>> pinned;      // sources of asynchronous copies: zeroed once the stream is drained
+  void device(DevBuf& b, size_t bytes) {               // one entry per buffer: the most bytes any chunk put there
+    for (auto& d : dev)
+      if (d.first == &b) { d.second = std::max(d.second, bytes); return; }
+    dev.push_back({&b, bytes});
+  }
+  ~RtWipe() {
+    for (auto* v : host) {
+      volatile uint8_t* wp = v->data();
+      for (size_t i = 0; i < v->size(); ++i) wp[i] = 0;
+    }
+    if ((!dev.empty() || !pinned.empty()) && hipSetDevice(ctx->device) == hipSuccess) {
+      for (auto& d : dev)
+        if (d.first->p) (void)hipMemsetAsync(d.first->p, 0, d.second < d.first->cap ? d.second : d.first->cap, ctx->stream);
+      (void)hipStreamSynchronize(ctx->stream);
+    }
+    for (auto& pp : pinned) {
+      volatile uint8_t* wp = (volatile uint8_t*)pp.first;
+      for (size_t i = 0; wp && i < pp.second; ++i) wp[i] = 0;
+    }
+  }
+};
+
+// ---- the frame of one call (DESIGN section 13, "How a run-time entry point is put together") ------------------------------------
+// An entry point checks its arguments, then constructs one RtCall with the context lock held and does everything that depends on
+// `space`, on MAX_CHUNK or on what is secret through it:
+//   begin()       the device, a fresh set of timing spans, and the device copies of the constants the call needs (dc, dcq);
+//   for_chunks()  the one loop over MAX_CHUNK; after the body it settles the chunk unless the body did;
+//   in()          a chunk of an input array on the device.  A Secret array that the frame copied there is zeroed on every way out;
+//                 a caller's own device array is the caller's.  That rule is written here and nowhere else;
+//   out()         where a kernel writes a chunk of an output array; settle() delivers it when the caller's array is host memory;
+//   to_host()     results the host hashes, host_view() the host bytes of an input whichever space it is in;
+//   settle()      the chunk's one synchronisation: outputs copied out, the stream drained, host copies handed on.
+// in(), out() and their kin return null once something failed and keep the first error in `rc`: a body stages everything, checks
+// `rc` once, and then launches.  A body that asks for host copies settles the chunk before it returns, failed or not, so no
+// copy into its vectors outlives them.  Host vectors that hold secrets (wipe.host, host_view() of a Secret array) are declared
+// BEFORE the frame, which zeroes them on its way out.
+struct RtCall {
+  enum Kind { Public, Secret };
+  enum Consts { ModQ = 1, SubQ = 2 };                // the constants of q (dc) and of q' = (q-1)/2 (dcq)
+  mpvss_ctx* const ctx;
+  const mpvss_modp_group* const grp;
+  const int space;
+  const size_t EB;
+  bool secrets_dev = false;    // Secret inputs are device arrays of the caller whatever `space` says (group_deal's device scalar ring)
+  const modp_rt_consts* dc = nullptr;
+  const modp_rt_consts* dcq = nullptr;
+  int rc = 0;
+  RtWipe wipe;
+
+  RtCall(mpvss_ctx* c, const mpvss_modp_group* g, int sp) : ctx(c), grp(g), space(sp), EB(g->eb), wipe{c, {}, {}, {}} {}
+  RtCall(const RtCall&) = delete;
+  ~RtCall() {
+    if (host_pending) (void)hipStreamSynchronize(ctx->stream);
+  }
+
+  // the first begin() of a call selects the device and resets the spans; each uploads the constants asked for once
+  int begin(int which = ModQ) {
+    if (!begun) {
+      HIPCHK(ctx, hipSetDevice(ctx->device));
+      spans_reset(ctx);
+      begun = true;
+    }
+    if ((which & ModQ) && !dc) RET_IF(rt_upload(ctx, grp->c, ctx->rt_consts, &dc));
+    if ((which & SubQ) && !dcq) RET_IF(rt_upload(ctx, grp->cq, ctx->rt_consts_q, &dcq));
+    return 0;
+  }
+
+  template <class Body>
+  int for_chunks(size_t n, Body body) {
+    for (size_t off = 0; off < n; off += MAX_CHUNK) {
+      settled = false;
+      RET_IF(body(off, std::min(n - off, MAX_CHUNK)));
+      if (!settled) RET_IF(settle());
+    }
+    return 0;
+  }
+
+  bool caller_on_host() const { return space != MPVSS_DEVICE; }
+
+  const uint8_t* in(const uint8_t* arr, size_t off, size_t cnt, DevBuf& buf, Kind kind) {
+    return stage(kind == Secret && secrets_dev ? MPVSS_DEVICE : space, arr + off * EB, cnt, buf, kind);
+  }
+  // host bytes of the library's own making (exponents it computed), whatever `space` is
+  const uint8_t* in_host(const uint8_t* host, size_t cnt, DevBuf& buf, Kind kind) { return stage(MPVSS_HOST, host, cnt, buf, kind); }
+  const int64_t* in_positions(const int64_t* positions, size_t off, size_t cnt) {
+    const int64_t* d = nullptr;
+    if (!rc) rc = stage_positions(ctx, space, positions + off, cnt, &d);
+    return d;
+  }
+
+  // cnt elements of a workspace of the context; a Secret one is zeroed on the way out
+  uint8_t* work(DevBuf& buf, size_t cnt, Kind kind = Public) {
+    if (rc) return nullptr;
+    if (kind == Secret) wipe.device(buf, cnt * EB);
+    rc = ensure(ctx, buf, cnt * EB);
+    return rc ? nullptr : (uint8_t*)buf.p;
+  }
+  // the caller's own array when it is on the device; otherwise `buf`, which settle() copies to `arr` (null: nobody wants it)
+  uint8_t* out(uint8_t* arr, size_t off, size_t cnt, DevBuf& buf, Kind kind = Public) {
+    if (arr && !caller_on_host()) return arr + off * EB;
+    uint8_t* d = work(buf, cnt, kind);
+    if (arr && d) outs.push_back({arr + off * EB, d, cnt * EB, nullptr});
+    return d;
+  }
+
+  // cnt elements from the device into vec, valid after settle() or host_ready().  An out() that is read back this way reaches
+  // the caller from vec: one copy over the bus, not two.
+  void to_host(const uint8_t* dev, size_t cnt, std::vector<uint8_t>& vec) {
+    if (rc) return;
+    vec.resize(cnt * EB);
+    rc = read_back(vec.data(), dev, cnt * EB);
+    for (auto& o : outs)
+      if (o.dev == dev) o.host = vec.data();
+  }
+  const uint8_t* host_view(const uint8_t* arr, size_t off, size_t cnt, std::vector<uint8_t>& vec, Kind kind = Public) {
+    if (caller_on_host()) return arr + off * EB;
+    if (kind == Secret && std::find(wipe.host.begin(), wipe.host.end(), &vec) == wipe.host.end()) wipe.host.push_back(&vec);
+    to_host(arr + off * EB, cnt, vec);
+    return vec.data();
+  }
+  // before the host reads what to_host() / host_view() asked for in the middle of a chunk; nothing to wait for in host space
+  int host_ready() {
+    if (host_pending) HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    host_pending = false;
+    return rc;
+  }
+
+  // the copies of the outputs to a caller on the host, in stream order and without waiting (for a call whose end() waits)
+  int flush() {
+    if (rc && host_pending) (void)hipStreamSynchronize(ctx->stream);   // no copy into a body's vector outlives the body
+    RET_IF(rc);
+    for (auto& o : outs)
+      if (!o.host) RET_IF(copy_out(ctx, space, o.dst, o.dev, o.bytes));
+    return 0;
+  }
+  int settle() {
+    RET_IF(flush());
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    for (auto& o : outs)
+      if (o.host) memcpy(o.dst, o.host, o.bytes);
+    outs.clear();
+    host_pending = false;
+    settled = true;
+    return 0;
+  }
+  // the end of a call that timed its launches: the stream drained and the spans summed
+  int end() { return spans_collect(ctx); }
+
+ private:
+  struct Out { uint8_t* dst; const uint8_t* dev; size_t bytes; const uint8_t* host; };
+  std::vector<Out> outs;
+  bool begun = false, settled = false, host_pending = false;
+
+  const uint8_t* stage(int sp, const uint8_t* src, size_t cnt, DevBuf& buf, Kind kind) {
+    if (rc) return nullptr;
+    if (kind == Secret && sp != MPVSS_DEVICE) wipe.device(buf, cnt * EB);
+    const void* d = nullptr;
+    rc = stage_in(ctx, sp, src, cnt * EB, buf, &d);
+    return (const uint8_t*)d;
+  }
+  int read_back(void* dst, const uint8_t* dev, size_t bytes) {
+    host_pending = true;
+    HIPCHK(ctx, hipMemcpyAsync(dst, dev, bytes, hipMemcpyDeviceToHost, ctx->stream));
+    return 0;
+  }
+};
 
 size_t rt_L(const mpvss_modp_group* grp) { return (size_t)4 * grp->lpl; }
 
@@ -288,13 +469,15 @@ int rt_fd_positions_ok(mpvss_ctx* ctx, const mpvss_modp_group* grp, int space, c
 // when the call has inverted commitments (rt_fd_prepare), the chunk is large enough for its mode and its positions are
 // admissible; otherwise k_rt_commit_eval.  Under these conditions the recurrences are integer identities in the exponent,
 // so both paths give the same bytes.
-int rt_commit_eval_dev(mpvss_ctx* ctx, const mpvss_modp_group* grp, const modp_rt_consts* dc, size_t t, const int64_t* pos_dev,
-                       size_t cnt, uint8_t* x_dev, int space, const int64_t* positions) {
+int rt_commit_eval_dev(RtCall& f, size_t t, const int64_t* pos_dev, size_t cnt, uint8_t* x_dev, const int64_t* positions) {
+  mpvss_ctx* const ctx = f.ctx;
+  const mpvss_modp_group* const grp = f.grp;
+  const modp_rt_consts* const dc = f.dc;
   const size_t LW = rt_L(grp);
   bool fd = ctx->rt_fd_ready && cnt >= t && (ctx->rt_fd_mode == 2 || cnt >= rt_fd_min_shares(grp->lpl, t)) &&
             cnt * LW * 4 <= ((size_t)1 << 30);               // X in limbs stays a workspace of at most 1 GiB
   int64_t p0 = 0;
-  if (fd) RET_IF(rt_fd_positions_ok(ctx, grp, space, positions, cnt, &fd, &p0));
+  if (fd) RET_IF(rt_fd_positions_ok(ctx, grp, f.space, positions, cnt, &fd, &p0));
   if (!fd) {
     ++ctx->rt_horner_calls;
     TIMED_LAUNCH(ctx, 0, modp_rt_launch_commit_eval(grp->lpl, (const uint32_t*)ctx->rt_cm.p, (int)t, pos_dev, (int)cnt, x_dev, dc,
@@ -327,14 +510,13 @@ int rt_commit_eval_dev(mpvss_ctx* ctx, const mpvss_modp_group* grp, const modp_r
   return 0;
 }
 
-int rt_stage_commitments(mpvss_ctx* ctx, const mpvss_modp_group* grp, const modp_rt_consts* dc, int space, const uint8_t* commitments,
-                         size_t t, size_t n) {
-  const size_t EB = grp->eb;
-  const void* dcm;
-  RET_IF(stage_in(ctx, space, commitments, t * EB, ctx->rt_in[4], &dcm));
-  RET_IF(ensure(ctx, ctx->rt_cm, t * rt_L(grp) * 4));
-  LAUNCHCHK(ctx, modp_rt_launch_to_mont(grp->lpl, (const uint8_t*)dcm, (int)t, (uint32_t*)ctx->rt_cm.p, dc, ctx->stream));
-  return rt_fd_prepare(ctx, grp, dc, space, commitments, t, n);
+int rt_stage_commitments(RtCall& f, const uint8_t* commitments, size_t t, size_t n) {
+  mpvss_ctx* const ctx = f.ctx;
+  const uint8_t* dcm = f.in(commitments, 0, t, ctx->rt_in[4], RtCall::Public);
+  RET_IF(f.rc);
+  RET_IF(ensure(ctx, ctx->rt_cm, t * rt_L(f.grp) * 4));
+  LAUNCHCHK(ctx, modp_rt_launch_to_mont(f.grp->lpl, dcm, (int)t, (uint32_t*)ctx->rt_cm.p, f.dc, ctx->stream));
+  return rt_fd_prepare(ctx, f.grp, f.dc, f.space, commitments, t, n);
 }
 
 // hash_to_scalar of the group: int(SHA-256(data)) mod (q-1)/2, big-endian at the handle's element size
@@ -352,21 +534,14 @@ void rt_hash_to_scalar(const mpvss_modp_group* grp, const uint8_t* data, size_t 
   });
 }
 
-// the transcript framing of mpvss_capi.cpp (frame_update, frame_shares, frame_min_bytes_update) at the handle's element size:
-// minimal-length big-endian magnitude, zero -> one 0x00 byte (modp.rs:150-152), behind its 8-byte length (dleq.rs:58-61)
-void rt_frame_min_bytes_update(mpvss::Sha256& h, const uint8_t* e, size_t eb) {
-  size_t skip = 0;
-  while (skip < eb - 1 && e[skip] == 0) ++skip;
-  h.update(e + skip, eb - skip);
-}
-void rt_frame_update(mpvss::Sha256& h, const uint8_t* e, size_t eb) {
-  size_t skip = 0;
-  while (skip < eb - 1 && e[skip] == 0) ++skip;
-  const uint64_t len = eb - skip;
-  uint8_t pre[8];
-  for (int i = 0; i < 8; ++i) pre[i] = (uint8_t)(len >> (56 - 8 * i));
-  h.update(pre, 8);
-  h.update(e + skip, (size_t)len);
+// the challenge of one share's DLEQ proof: hash_to_scalar(SHA-256(framed(a) | framed(b) | framed(a1) | framed(a2))), dleq.rs:119-126
+void rt_share_challenge(const mpvss_modp_group* grp, const uint8_t* a, const uint8_t* b, const uint8_t* a1, const uint8_t* a2,
+                        uint8_t* out) {
+  mpvss::Sha256 hs;
+  for (const uint8_t* e : {a, b, a1, a2}) frame_update(hs, e, grp->eb);
+  uint8_t digest[32];
+  hs.final(digest);
+  rt_hash_to_scalar(grp, digest, 32, out);
 }
 
 bool rt_bad_group(const mpvss_modp_group* grp) { return grp == nullptr || grp->lpl == 0; }
@@ -494,32 +669,22 @@ extern "C" int mpvss_modp_group_batch_exp(mpvss_ctx* ctx, const mpvss_modp_group
   if (!ctx) return MPVSS_E_INVALID;
   std::lock_guard<std::mutex> lk(ctx->mu);
   if (rt_bad_group(grp)) return fail(ctx, MPVSS_E_INVALID, "group_batch_exp: no group");
-  const size_t EB = grp->eb;
   if (n == 0) return MPVSS_OK;
   if (!bases || !exps || !out) return fail(ctx, MPVSS_E_INVALID, "group_batch_exp: bad argument");
-  HIPCHK(ctx, hipSetDevice(ctx->device));
-  spans_reset(ctx);
-  const modp_rt_consts* dc;
-  RET_IF(rt_upload(ctx, grp, &dc));
-  for (size_t off = 0; off < n; off += MAX_CHUNK) {
-    const size_t cnt = (n - off < MAX_CHUNK) ? n - off : MAX_CHUNK;
-    const void *db, *de;
-    RET_IF(stage_in(ctx, space, bases + off * EB, cnt * EB, ctx->rt_in[0], &db));
-    RET_IF(stage_in(ctx, space, exps + off * EB, cnt * EB, ctx->rt_in[1], &de));
-    uint8_t* dout = out + off * EB;
-    if (space == MPVSS_HOST) {
-      RET_IF(ensure(ctx, ctx->rt_out[0], cnt * EB));
-      dout = (uint8_t*)ctx->rt_out[0].p;
-    }
+  RtCall f(ctx, grp, space);
+  RET_IF(f.begin());
+  RET_IF(f.for_chunks(n, [&](size_t off, size_t cnt) {
+    const uint8_t* db = f.in(bases, off, cnt, ctx->rt_in[0], RtCall::Public);
+    const uint8_t* de = f.in(exps, off, cnt, ctx->rt_in[1], RtCall::Public);
+    uint8_t* dout = f.out(out, off, cnt, ctx->rt_out[0]);
+    RET_IF(f.rc);
     const uint32_t* t1;
-    RET_IF(rt_tables(ctx, grp, dc, (const uint8_t*)db, EB, cnt, ctx->rt_tab1, &t1));
-    TIMED_LAUNCH(ctx, 3, modp_rt_launch_dual_exp(grp->lpl, t1, 16 * rt_L(grp), nullptr, 0, (const uint8_t*)de, EB, nullptr, 0, (int)cnt,
-                                                 dout, dc, ctx->stream));
-    if (space == MPVSS_HOST) RET_IF(copy_out(ctx, space, out + off * EB, dout, cnt * EB));
-    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-  }
-  RET_IF(spans_collect(ctx));
-  return MPVSS_OK;
+    RET_IF(rt_tables(ctx, grp, f.dc, db, f.EB, cnt, ctx->rt_tab1, &t1));
+    TIMED_LAUNCH(ctx, 3, modp_rt_launch_dual_exp(grp->lpl, t1, 16 * rt_L(grp), nullptr, 0, de, f.EB, nullptr, 0, (int)cnt, dout, f.dc,
+                                                 ctx->stream));
+    return 0;
+  }));
+  return f.end();
 }
 
 extern "C" int mpvss_modp_group_batch_mul(mpvss_ctx* ctx, const mpvss_modp_group* grp, int space, const uint8_t* a, const uint8_t* b,
@@ -527,31 +692,22 @@ extern "C" int mpvss_modp_group_batch_mul(mpvss_ctx* ctx, const mpvss_modp_group
   if (!ctx) return MPVSS_E_INVALID;
   std::lock_guard<std::mutex> lk(ctx->mu);
   if (rt_bad_group(grp)) return fail(ctx, MPVSS_E_INVALID, "group_batch_mul: no group");
-  const size_t EB = grp->eb;
   if (n == 0) return MPVSS_OK;
   if (!a || !b || !out || n > 0x7fffffff) return fail(ctx, MPVSS_E_INVALID, "group_batch_mul: bad argument");
-  HIPCHK(ctx, hipSetDevice(ctx->device));
-  spans_reset(ctx);
-  const modp_rt_consts* dc;
-  RET_IF(rt_upload(ctx, grp, &dc));
-  const void *da, *db;
-  RET_IF(stage_in(ctx, space, a, n * EB, ctx->rt_in[0], &da));
-  RET_IF(stage_in(ctx, space, b, n * EB, ctx->rt_in[1], &db));
-  uint8_t* dout = out;
-  if (space == MPVSS_HOST) {
-    RET_IF(ensure(ctx, ctx->rt_out[0], n * EB));
-    dout = (uint8_t*)ctx->rt_out[0].p;
-  }
+  RtCall f(ctx, grp, space);
+  RET_IF(f.begin());
+  const uint8_t* da = f.in(a, 0, n, ctx->rt_in[0], RtCall::Public);
+  const uint8_t* db = f.in(b, 0, n, ctx->rt_in[1], RtCall::Public);
+  uint8_t* dout = f.out(out, 0, n, ctx->rt_out[0]);
+  RET_IF(f.rc);
   const size_t LW = rt_L(grp);
   RET_IF(ensure(ctx, ctx->rt_tab1, n * LW * 4));
   RET_IF(ensure(ctx, ctx->rt_tab2, n * LW * 4));
-  LAUNCHCHK(ctx, modp_rt_launch_to_mont(grp->lpl, (const uint8_t*)da, (int)n, (uint32_t*)ctx->rt_tab1.p, dc, ctx->stream));
-  LAUNCHCHK(ctx, modp_rt_launch_to_mont(grp->lpl, (const uint8_t*)db, (int)n, (uint32_t*)ctx->rt_tab2.p, dc, ctx->stream));
-  LAUNCHCHK(ctx, modp_rt_launch_mul(grp->lpl, (const uint32_t*)ctx->rt_tab1.p, (const uint32_t*)ctx->rt_tab2.p, (int)n, dout, dc,
+  LAUNCHCHK(ctx, modp_rt_launch_to_mont(grp->lpl, da, (int)n, (uint32_t*)ctx->rt_tab1.p, f.dc, ctx->stream));
+  LAUNCHCHK(ctx, modp_rt_launch_to_mont(grp->lpl, db, (int)n, (uint32_t*)ctx->rt_tab2.p, f.dc, ctx->stream));
+  LAUNCHCHK(ctx, modp_rt_launch_mul(grp->lpl, (const uint32_t*)ctx->rt_tab1.p, (const uint32_t*)ctx->rt_tab2.p, (int)n, dout, f.dc,
                                     ctx->stream));
-  if (space == MPVSS_HOST) RET_IF(copy_out(ctx, space, out, dout, n * EB));
-  HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-  return MPVSS_OK;
+  return f.settle();
 }
 
 extern "C" int mpvss_modp_group_commit_eval(mpvss_ctx* ctx, const mpvss_modp_group* grp, int space, const uint8_t* commitments,
@@ -559,26 +715,18 @@ extern "C" int mpvss_modp_group_commit_eval(mpvss_ctx* ctx, const mpvss_modp_gro
   if (!ctx) return MPVSS_E_INVALID;
   std::lock_guard<std::mutex> lk(ctx->mu);
   if (rt_bad_group(grp)) return fail(ctx, MPVSS_E_INVALID, "group_commit_eval: no group");
-  const size_t EB = grp->eb;
   if (n == 0) return MPVSS_OK;
   if (!commitments || !positions || !x_out || t == 0 || t > 0x7fffffff || n > 0x7fffffff)
     return fail(ctx, MPVSS_E_INVALID, "group_commit_eval: bad argument (t must be >= 1)");
-  HIPCHK(ctx, hipSetDevice(ctx->device));
-  spans_reset(ctx);
-  const modp_rt_consts* dc;
-  RET_IF(rt_upload(ctx, grp, &dc));
-  RET_IF(rt_stage_commitments(ctx, grp, dc, space, commitments, t, n));
-  const int64_t* dpos;
-  RET_IF(stage_positions(ctx, space, positions, n, &dpos));
-  uint8_t* dout = x_out;
-  if (space == MPVSS_HOST) {
-    RET_IF(ensure(ctx, ctx->rt_out[0], n * EB));
-    dout = (uint8_t*)ctx->rt_out[0].p;
-  }
-  RET_IF(rt_commit_eval_dev(ctx, grp, dc, t, dpos, n, dout, space, positions));
-  if (space == MPVSS_HOST) RET_IF(copy_out(ctx, space, x_out, dout, n * EB));
-  RET_IF(spans_collect(ctx));
-  return MPVSS_OK;
+  RtCall f(ctx, grp, space);
+  RET_IF(f.begin());
+  RET_IF(rt_stage_commitments(f, commitments, t, n));
+  const int64_t* dpos = f.in_positions(positions, 0, n);
+  uint8_t* dout = f.out(x_out, 0, n, ctx->rt_out[0]);
+  RET_IF(f.rc);
+  RET_IF(rt_commit_eval_dev(f, t, dpos, n, dout, positions));
+  RET_IF(f.flush());
+  return f.end();
 }
 
 extern "C" int mpvss_modp_group_dleq_commitments(mpvss_ctx* ctx, const mpvss_modp_group* grp, int space, const uint8_t* g1_host,
@@ -587,42 +735,25 @@ extern "C" int mpvss_modp_group_dleq_commitments(mpvss_ctx* ctx, const mpvss_mod
   if (!ctx) return MPVSS_E_INVALID;
   std::lock_guard<std::mutex> lk(ctx->mu);
   if (rt_bad_group(grp)) return fail(ctx, MPVSS_E_INVALID, "group_dleq_commitments: no group");
-  const size_t EB = grp->eb;
   if (n == 0) return MPVSS_OK;
   if (!g1_host || !h1 || !g2 || !h2 || !r || !c || !a1_out || !a2_out || n > 0x7fffffff)
     return fail(ctx, MPVSS_E_INVALID, "group_dleq_commitments: bad argument");
-  HIPCHK(ctx, hipSetDevice(ctx->device));
-  spans_reset(ctx);
-  const modp_rt_consts* dc;
-  RET_IF(rt_upload(ctx, grp, &dc));
+  RtCall f(ctx, grp, space);
+  RET_IF(f.begin());
   const uint8_t* dcc = nullptr;
   if (!c_per_share) RET_IF(rt_stage_small(ctx, grp, c, ctx->rt_small[1], &dcc));
-  for (size_t off = 0; off < n; off += MAX_CHUNK) {
-    const size_t cnt = (n - off < MAX_CHUNK) ? n - off : MAX_CHUNK;
-    const void *dh1, *dg2, *dh2, *dr, *dcs = dcc;
-    RET_IF(stage_in(ctx, space, h1 + off * EB, cnt * EB, ctx->rt_in[0], &dh1));
-    RET_IF(stage_in(ctx, space, g2 + off * EB, cnt * EB, ctx->rt_in[1], &dg2));
-    RET_IF(stage_in(ctx, space, h2 + off * EB, cnt * EB, ctx->rt_in[2], &dh2));
-    RET_IF(stage_in(ctx, space, r + off * EB, cnt * EB, ctx->rt_in[3], &dr));
-    if (c_per_share) RET_IF(stage_in(ctx, space, c + off * EB, cnt * EB, ctx->rt_in[5], &dcs));
-    uint8_t* d1 = a1_out + off * EB;
-    uint8_t* d2 = a2_out + off * EB;
-    if (space == MPVSS_HOST) {
-      RET_IF(ensure(ctx, ctx->rt_out[0], cnt * EB));
-      RET_IF(ensure(ctx, ctx->rt_out[1], cnt * EB));
-      d1 = (uint8_t*)ctx->rt_out[0].p;
-      d2 = (uint8_t*)ctx->rt_out[1].p;
-    }
-    RET_IF(rt_dleq_dev(ctx, grp, dc, g1_host, (const uint8_t*)dh1, (const uint8_t*)dg2, (const uint8_t*)dh2, (const uint8_t*)dr,
-                       (const uint8_t*)dcs, c_per_share ? EB : 0, cnt, d1, d2));
-    if (space == MPVSS_HOST) {
-      RET_IF(copy_out(ctx, space, a1_out + off * EB, d1, cnt * EB));
-      RET_IF(copy_out(ctx, space, a2_out + off * EB, d2, cnt * EB));
-    }
-    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-  }
-  RET_IF(spans_collect(ctx));
-  return MPVSS_OK;
+  RET_IF(f.for_chunks(n, [&](size_t off, size_t cnt) {
+    const uint8_t* dh1 = f.in(h1, off, cnt, ctx->rt_in[0], RtCall::Public);
+    const uint8_t* dg2 = f.in(g2, off, cnt, ctx->rt_in[1], RtCall::Public);
+    const uint8_t* dh2 = f.in(h2, off, cnt, ctx->rt_in[2], RtCall::Public);
+    const uint8_t* dr = f.in(r, off, cnt, ctx->rt_in[3], RtCall::Public);
+    const uint8_t* dcs = c_per_share ? f.in(c, off, cnt, ctx->rt_in[5], RtCall::Public) : dcc;
+    uint8_t* d1 = f.out(a1_out, off, cnt, ctx->rt_out[0]);
+    uint8_t* d2 = f.out(a2_out, off, cnt, ctx->rt_out[1]);
+    RET_IF(f.rc);
+    return rt_dleq_dev(ctx, grp, f.dc, g1_host, dh1, dg2, dh2, dr, dcs, c_per_share ? f.EB : 0, cnt, d1, d2);
+  }));
+  return f.end();
 }
 
 extern "C" int mpvss_modp_group_verify_distribution(mpvss_ctx* ctx, const mpvss_modp_group* grp, int space, const uint8_t* commitments,
@@ -640,48 +771,37 @@ extern "C" int mpvss_modp_group_verify_distribution(mpvss_ctx* ctx, const mpvss_
   *verdict = 0;
   mpvss::Sha256 h;
   if (n > 0) {
-    HIPCHK(ctx, hipSetDevice(ctx->device));
-    spans_reset(ctx);
-    const modp_rt_consts* dc;
-    RET_IF(rt_upload(ctx, grp, &dc));
-    RET_IF(rt_stage_commitments(ctx, grp, dc, space, commitments, t, n));
+    std::vector<uint8_t> hX, hY, h1, h2;
+    RtCall f(ctx, grp, space);
+    RET_IF(f.begin());
+    RET_IF(rt_stage_commitments(f, commitments, t, n));
     const uint8_t* dch;
     RET_IF(rt_stage_small(ctx, grp, challenge_host, ctx->rt_small[1], &dch));
-    const size_t chunk = std::min(n, MAX_CHUNK);
-    std::vector<uint8_t> hX(chunk * EB), hY(chunk * EB), h1(chunk * EB), h2(chunk * EB);
-    for (size_t off = 0; off < n; off += MAX_CHUNK) {
-      const size_t cnt = (n - off < MAX_CHUNK) ? n - off : MAX_CHUNK;
-      const int64_t* dpos;
-      RET_IF(stage_positions(ctx, space, positions + off, cnt, &dpos));
-      const void *dy, *dY, *dr;
-      RET_IF(stage_in(ctx, space, pubkeys + off * EB, cnt * EB, ctx->rt_in[1], &dy));
-      RET_IF(stage_in(ctx, space, shares + off * EB, cnt * EB, ctx->rt_in[2], &dY));
-      RET_IF(stage_in(ctx, space, responses + off * EB, cnt * EB, ctx->rt_in[3], &dr));
-      for (DevBuf* b : {&ctx->rt_out[0], &ctx->rt_out[1], &ctx->rt_out[2]}) RET_IF(ensure(ctx, *b, cnt * EB));
-      uint8_t* dX = (uint8_t*)ctx->rt_out[0].p;
-      uint8_t* d1 = (uint8_t*)ctx->rt_out[1].p;
-      uint8_t* d2 = (uint8_t*)ctx->rt_out[2].p;
-      RET_IF(rt_commit_eval_dev(ctx, grp, dc, t, dpos, cnt, dX, space, positions + off));
+    RET_IF(f.for_chunks(n, [&](size_t off, size_t cnt) {
+      const int64_t* dpos = f.in_positions(positions, off, cnt);
+      const uint8_t* dy = f.in(pubkeys, off, cnt, ctx->rt_in[1], RtCall::Public);
+      const uint8_t* dY = f.in(shares, off, cnt, ctx->rt_in[2], RtCall::Public);
+      const uint8_t* dr = f.in(responses, off, cnt, ctx->rt_in[3], RtCall::Public);
+      uint8_t* dX = f.work(ctx->rt_out[0], cnt);
+      uint8_t* d1 = f.work(ctx->rt_out[1], cnt);
+      uint8_t* d2 = f.work(ctx->rt_out[2], cnt);
+      RET_IF(f.rc);
+      RET_IF(rt_commit_eval_dev(f, t, dpos, cnt, dX, positions + off));
       // a1 = g^r X^c, a2 = y^r Y^c (src/participant.rs:436-447 -> src/dleq.rs:66-84)
-      RET_IF(rt_dleq_dev(ctx, grp, dc, grp->g_be, dX, (const uint8_t*)dy, (const uint8_t*)dY, (const uint8_t*)dr, dch, 0, cnt, d1, d2));
-      HIPCHK(ctx, hipMemcpyAsync(hX.data(), dX, cnt * EB, hipMemcpyDeviceToHost, ctx->stream));
-      HIPCHK(ctx, hipMemcpyAsync(h1.data(), d1, cnt * EB, hipMemcpyDeviceToHost, ctx->stream));
-      HIPCHK(ctx, hipMemcpyAsync(h2.data(), d2, cnt * EB, hipMemcpyDeviceToHost, ctx->stream));
-      if (space == MPVSS_DEVICE) HIPCHK(ctx, hipMemcpyAsync(hY.data(), dY, cnt * EB, hipMemcpyDeviceToHost, ctx->stream));
-      HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-      const uint8_t* Y = (space == MPVSS_DEVICE) ? hY.data() : shares + off * EB;
+      RET_IF(rt_dleq_dev(ctx, grp, f.dc, grp->g_be, dX, dy, dY, dr, dch, 0, cnt, d1, d2));
+      f.to_host(dX, cnt, hX);
+      f.to_host(d1, cnt, h1);
+      f.to_host(d2, cnt, h2);
+      const uint8_t* Y = f.host_view(shares, off, cnt, hY);
+      RET_IF(f.settle());
       // the transcript hashes Y_i as the box carries it (src/participant.rs:448), X_i, a1_i, a2_i canonical
-      for (size_t i = 0; i < cnt; ++i) {
-        rt_frame_update(h, hX.data() + i * EB, EB);
-        rt_frame_update(h, Y + i * EB, EB);
-        rt_frame_update(h, h1.data() + i * EB, EB);
-        rt_frame_update(h, h2.data() + i * EB, EB);
-      }
+      frame_shares(h, hX.data(), Y, h1.data(), h2.data(), 0, cnt, EB);
       if (x_out_host) memcpy(x_out_host + off * EB, hX.data(), cnt * EB);
       if (a1_out_host) memcpy(a1_out_host + off * EB, h1.data(), cnt * EB);
       if (a2_out_host) memcpy(a2_out_host + off * EB, h2.data(), cnt * EB);
-    }
-    RET_IF(spans_collect(ctx));
+      return 0;
+    }));
+    RET_IF(f.end());
   }
   uint8_t digest[32], c[RT_EB_MAX];
   h.final(digest);
@@ -701,53 +821,34 @@ extern "C" int mpvss_modp_group_verify_shares(mpvss_ctx* ctx, const mpvss_modp_g
   if (n == 0) return MPVSS_OK;
   if (!pk || !s || !y || !c || !r || !verdicts_host || n > 0x7fffffff)
     return fail(ctx, MPVSS_E_INVALID, "group_verify_shares: bad argument");
-  HIPCHK(ctx, hipSetDevice(ctx->device));
-  spans_reset(ctx);
-  const modp_rt_consts* dc;
-  RET_IF(rt_upload(ctx, grp, &dc));
-  const size_t chunk = std::min(n, MAX_CHUNK);
-  std::vector<uint8_t> hpk, hY, hc, h1(chunk * EB), h2(chunk * EB);
-  if (space == MPVSS_DEVICE) { hpk.resize(chunk * EB); hY.resize(chunk * EB); hc.resize(chunk * EB); }
-  for (size_t off = 0; off < n; off += MAX_CHUNK) {
-    const size_t cnt = (n - off < MAX_CHUNK) ? n - off : MAX_CHUNK;
-    const void *dpk, *ds, *dy, *dcc, *dr;
-    RET_IF(stage_in(ctx, space, pk + off * EB, cnt * EB, ctx->rt_in[0], &dpk));
-    RET_IF(stage_in(ctx, space, s + off * EB, cnt * EB, ctx->rt_in[1], &ds));
-    RET_IF(stage_in(ctx, space, y + off * EB, cnt * EB, ctx->rt_in[2], &dy));
-    RET_IF(stage_in(ctx, space, c + off * EB, cnt * EB, ctx->rt_in[5], &dcc));
-    RET_IF(stage_in(ctx, space, r + off * EB, cnt * EB, ctx->rt_in[3], &dr));
-    RET_IF(ensure(ctx, ctx->rt_out[1], cnt * EB));
-    RET_IF(ensure(ctx, ctx->rt_out[2], cnt * EB));
-    uint8_t* d1 = (uint8_t*)ctx->rt_out[1].p;
-    uint8_t* d2 = (uint8_t*)ctx->rt_out[2].p;
+  std::vector<uint8_t> hpk, hY, hc, h1, h2;
+  RtCall f(ctx, grp, space);
+  RET_IF(f.begin());
+  RET_IF(f.for_chunks(n, [&](size_t off, size_t cnt) {
+    const uint8_t* dpk = f.in(pk, off, cnt, ctx->rt_in[0], RtCall::Public);
+    const uint8_t* ds = f.in(s, off, cnt, ctx->rt_in[1], RtCall::Public);
+    const uint8_t* dy = f.in(y, off, cnt, ctx->rt_in[2], RtCall::Public);
+    const uint8_t* dcc = f.in(c, off, cnt, ctx->rt_in[5], RtCall::Public);
+    const uint8_t* dr = f.in(r, off, cnt, ctx->rt_in[3], RtCall::Public);
+    uint8_t* d1 = f.work(ctx->rt_out[1], cnt);
+    uint8_t* d2 = f.work(ctx->rt_out[2], cnt);
+    RET_IF(f.rc);
     // a1 = G^r pk^c, a2 = S^r Y^c (src/participant.rs:361-386 -> src/dleq.rs:275-302)
-    RET_IF(rt_dleq_dev(ctx, grp, dc, grp->G_be, (const uint8_t*)dpk, (const uint8_t*)ds, (const uint8_t*)dy, (const uint8_t*)dr,
-                       (const uint8_t*)dcc, EB, cnt, d1, d2));
-    HIPCHK(ctx, hipMemcpyAsync(h1.data(), d1, cnt * EB, hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(ctx, hipMemcpyAsync(h2.data(), d2, cnt * EB, hipMemcpyDeviceToHost, ctx->stream));
-    if (space == MPVSS_DEVICE) {
-      HIPCHK(ctx, hipMemcpyAsync(hpk.data(), pk + off * EB, cnt * EB, hipMemcpyDeviceToHost, ctx->stream));
-      HIPCHK(ctx, hipMemcpyAsync(hY.data(), y + off * EB, cnt * EB, hipMemcpyDeviceToHost, ctx->stream));
-      HIPCHK(ctx, hipMemcpyAsync(hc.data(), c + off * EB, cnt * EB, hipMemcpyDeviceToHost, ctx->stream));
-    }
-    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-    const uint8_t* P = space == MPVSS_DEVICE ? hpk.data() : pk + off * EB;
-    const uint8_t* Y = space == MPVSS_DEVICE ? hY.data() : y + off * EB;
-    const uint8_t* C = space == MPVSS_DEVICE ? hc.data() : c + off * EB;
+    RET_IF(rt_dleq_dev(ctx, grp, f.dc, grp->G_be, dpk, ds, dy, dr, dcc, EB, cnt, d1, d2));
+    f.to_host(d1, cnt, h1);
+    f.to_host(d2, cnt, h2);
+    const uint8_t* P = f.host_view(pk, off, cnt, hpk);
+    const uint8_t* Y = f.host_view(y, off, cnt, hY);
+    const uint8_t* C = f.host_view(c, off, cnt, hc);
+    RET_IF(f.settle());
     for (size_t i = 0; i < cnt; ++i) {
-      mpvss::Sha256 hs;
-      rt_frame_update(hs, P + i * EB, EB);
-      rt_frame_update(hs, Y + i * EB, EB);
-      rt_frame_update(hs, h1.data() + i * EB, EB);
-      rt_frame_update(hs, h2.data() + i * EB, EB);
-      uint8_t digest[32], cc[RT_EB_MAX];
-      hs.final(digest);
-      rt_hash_to_scalar(grp, digest, 32, cc);     // src/dleq.rs:119-126
+      uint8_t cc[RT_EB_MAX];
+      rt_share_challenge(grp, P + i * EB, Y + i * EB, h1.data() + i * EB, h2.data() + i * EB, cc);
       verdicts_host[off + i] = memcmp(cc, C + i * EB, EB) == 0 ? 1 : 0;
     }
-  }
-  RET_IF(spans_collect(ctx));
-  return MPVSS_OK;
+    return 0;
+  }));
+  return f.end();
 }
 
 // =====================================================================================================================
@@ -800,31 +901,6 @@ size_t rt_twin_min_shares(int) { return (size_t)(MPVSS_RT_TWIN_MIN_SHARES); }
 size_t rt_twin_min_shares(int) { return 16384; }
 #endif
 
-// zero what held secrets whichever way the call ends (context lock held): device buffers in stream order, then the stream is
-// drained; host vectors word by word
-struct RtWipe {
-  mpvss_ctx* ctx;
-  std::vector<std::pair<DevBuf*, size_t>> dev;
-  std::vector<std::vector<uint8_t>*> host;
-  std::vector<std::pair<void*, size_t>> pinned;      // sources of asynchronous copies: zeroed once the stream is drained
-  void device(DevBuf& b, size_t bytes) { dev.push_back({&b, bytes}); }
-  ~RtWipe() {
-    for (auto* v : host) {
-      volatile uint8_t* wp = v->data();
-      for (size_t i = 0; i < v->size(); ++i) wp[i] = 0;
-    }
-    if ((!dev.empty() || !pinned.empty()) && hipSetDevice(ctx->device) == hipSuccess) {
-      for (auto& d : dev)
-        if (d.first->p) (void)hipMemsetAsync(d.first->p, 0, d.second < d.first->cap ? d.second : d.first->cap, ctx->stream);
-      (void)hipStreamSynchronize(ctx->stream);
-    }
-    for (auto& pp : pinned) {
-      volatile uint8_t* wp = (volatile uint8_t*)pp.first;
-      for (size_t i = 0; wp && i < pp.second; ++i) wp[i] = 0;
-    }
-  }
-};
-
 // ---- the scalar ring Z/(q-1) on the device (DESIGN section 13, "Scalar ring on the device") -------------------------------------
 // Mode 1 of mpvss_ctx_set_rt_scalar takes the device path from rt_scalar_min_shares shares of a whole call.  The threshold is what
 // `tools/modp_rt_rate.py --scalar --ab` measures (profiles/modp_rt_scalar_rate.txt): the smallest n from which the whole call under
@@ -840,14 +916,6 @@ bool rt_scalar_on_device(mpvss_ctx* ctx, const mpvss_modp_group* grp, size_t n) 
                    (mode == 2 || (mode == 1 && RT_SCALAR_AUTO_ON && n >= rt_scalar_min_shares(grp->lpl)));
   ++(dev ? ctx->rt_scalar_dev_calls : ctx->rt_scalar_host_calls);
   return dev;
-}
-
-// the call's device copy of the constants of q' (as rt_upload for q)
-int rt_upload_q(mpvss_ctx* ctx, const mpvss_modp_group* grp, const modp_rt_consts** dev) {
-  RET_IF(ensure(ctx, ctx->rt_consts_q, sizeof(modp_rt_consts)));
-  HIPCHK(ctx, hipMemcpyAsync(ctx->rt_consts_q.p, &grp->cq, sizeof(modp_rt_consts), hipMemcpyHostToDevice, ctx->stream));
-  *dev = (const modp_rt_consts*)ctx->rt_consts_q.p;
-  return 0;
 }
 
 // The dealer's coefficients for k_rt_modq_poly_eval: (a_j mod q') R mod q' as L limbs each, through pinned memory of the context
@@ -934,15 +1002,17 @@ const char* const RT_NO_Q = "no device scalar ring for this group: (q-1)/2 must 
 size_t rt_twin_launch(int lpl) { return lpl == 27 ? 32768 : 65536; }
 
 // out1 = B^e1, out2 = B^e2 for cnt shares (device pointers, one chunk).  Large batches: k_rt_twin_exp over bucket scratch of
-// the context, of which `wipe` zeroes what the call used; small ones, two left-to-right exponent sets over the bases' tables
+// the context, of which the frame's wipe zeroes what the call used; small ones, two left-to-right exponent sets over the bases' tables
 // in one launch.
-int rt_twin_dev(mpvss_ctx* ctx, const mpvss_modp_group* grp, const modp_rt_consts* dc, const uint8_t* bases, const uint8_t* e1,
-                const uint8_t* e2, size_t cnt, uint8_t* out1, uint8_t* out2, RtWipe& wipe) {
+int rt_twin_dev(RtCall& f, const uint8_t* bases, const uint8_t* e1, const uint8_t* e2, size_t cnt, uint8_t* out1, uint8_t* out2) {
+  mpvss_ctx* const ctx = f.ctx;
+  const mpvss_modp_group* const grp = f.grp;
+  const modp_rt_consts* const dc = f.dc;
   const size_t EB = grp->eb, RT_TWIN_LAUNCH = rt_twin_launch(grp->lpl);
   if (cnt >= rt_twin_min_shares(grp->lpl)) {
     const size_t bytes = modp_rt_twin_scratch_bytes(grp->lpl, (int)std::min(cnt, RT_TWIN_LAUNCH));
     RET_IF(ensure(ctx, ctx->rt_buckets, bytes));
-    wipe.device(ctx->rt_buckets, bytes);
+    f.wipe.device(ctx->rt_buckets, bytes);
     for (size_t off = 0; off < cnt; off += RT_TWIN_LAUNCH) {
       const size_t m = std::min(cnt - off, RT_TWIN_LAUNCH);
       TIMED_LAUNCH(ctx, 3, modp_rt_launch_twin_exp(grp->lpl, bases + off * EB, e1 + off * EB, e2 + off * EB, (int)m,
@@ -989,68 +1059,47 @@ bool rt_zero_mod_q(const mpvss_modp_group* grp, const uint8_t* v) {
 
 // The dealer's group side for n shares: X_i (commit_eval, or g^p_i when commitments is null: the dealer's own polynomial),
 // Y_i = y_i^p_i and a2_i = y_i^w_i through the twin path, a1_i = g^w_i, and the transcript digest.  Outputs in `space`
-// (the host ones optional).  p_values and witnesses staged on the device, and the buckets, are zeroed by `wipe`.
-// secrets_dev: p_values and witnesses are device arrays of the caller whatever `space` says (group_deal's device-side scalar ring:
-// P(i) never leaves HBM); the caller has reset the spans, launched into them already and wipes the two arrays itself.
-int rt_distribute_locked(mpvss_ctx* ctx, const mpvss_modp_group* grp, int space, const uint8_t* commitments, size_t t,
-                         const int64_t* positions, const uint8_t* pubkeys, const uint8_t* p_values, const uint8_t* witnesses, size_t n,
-                         uint8_t* x_out, uint8_t* y_out, uint8_t* a1_out, uint8_t* a2_out, uint8_t* digest32_out, RtWipe& wipe,
-                         bool secrets_dev = false) {
-  const size_t EB = grp->eb;
+// (the host ones optional).  p_values and witnesses are the frame's Secret inputs: zeroed where it staged them, and under
+// f.secrets_dev device arrays of the caller whatever `space` says (group_deal's device-side scalar ring: P(i) never leaves HBM;
+// the caller began the frame, launched into its spans already and wipes the two arrays itself).
+int rt_distribute_locked(RtCall& f, const uint8_t* commitments, size_t t, const int64_t* positions, const uint8_t* pubkeys,
+                         const uint8_t* p_values, const uint8_t* witnesses, size_t n, uint8_t* x_out, uint8_t* y_out, uint8_t* a1_out,
+                         uint8_t* a2_out, uint8_t* digest32_out) {
+  mpvss_ctx* const ctx = f.ctx;
+  const mpvss_modp_group* const grp = f.grp;
   mpvss::Sha256 h;
+  std::vector<uint8_t> hv[4];                                   // X, Y, a1, a2 of one chunk for the transcript
   if (n > 0) {
-    HIPCHK(ctx, hipSetDevice(ctx->device));
-    if (!secrets_dev) spans_reset(ctx);
-    const modp_rt_consts* dc;
-    RET_IF(rt_upload(ctx, grp, &dc));
-    if (commitments) RET_IF(rt_stage_commitments(ctx, grp, dc, space, commitments, t, n));
-    const bool dev = space == MPVSS_DEVICE;
-    const size_t chunk = std::min(n, MAX_CHUNK);
-    std::vector<uint8_t> hX(chunk * EB), hY(chunk * EB), h1(chunk * EB), h2(chunk * EB);
-    for (size_t off = 0; off < n; off += MAX_CHUNK) {
-      const size_t cnt = (n - off < MAX_CHUNK) ? n - off : MAX_CHUNK;
-      const void *dy, *dp, *dw;
-      RET_IF(stage_in(ctx, space, pubkeys + off * EB, cnt * EB, ctx->rt_in[1], &dy));
-      if (!dev && !secrets_dev) { wipe.device(ctx->rt_in[2], cnt * EB); wipe.device(ctx->rt_in[3], cnt * EB); }
-      RET_IF(stage_in(ctx, secrets_dev ? MPVSS_DEVICE : space, p_values + off * EB, cnt * EB, ctx->rt_in[2], &dp));
-      RET_IF(stage_in(ctx, secrets_dev ? MPVSS_DEVICE : space, witnesses + off * EB, cnt * EB, ctx->rt_in[3], &dw));
-      uint8_t *dX = x_out + off * EB, *dY = y_out + off * EB, *d1 = a1_out + off * EB, *d2 = a2_out + off * EB;
-      if (!dev) {
-        for (DevBuf* b : {&ctx->rt_out[0], &ctx->rt_out[1], &ctx->rt_out[2], &ctx->rt_out_y}) RET_IF(ensure(ctx, *b, cnt * EB));
-        dX = (uint8_t*)ctx->rt_out[0].p;
-        d1 = (uint8_t*)ctx->rt_out[1].p;
-        d2 = (uint8_t*)ctx->rt_out[2].p;
-        dY = (uint8_t*)ctx->rt_out_y.p;
-      }
+    RET_IF(f.begin());
+    if (commitments) RET_IF(rt_stage_commitments(f, commitments, t, n));
+    RET_IF(f.for_chunks(n, [&](size_t off, size_t cnt) {
+      const uint8_t* dy = f.in(pubkeys, off, cnt, ctx->rt_in[1], RtCall::Public);
+      const uint8_t* dp = f.in(p_values, off, cnt, ctx->rt_in[2], RtCall::Secret);
+      const uint8_t* dw = f.in(witnesses, off, cnt, ctx->rt_in[3], RtCall::Secret);
+      uint8_t* dX = f.out(x_out, off, cnt, ctx->rt_out[0]);
+      uint8_t* d1 = f.out(a1_out, off, cnt, ctx->rt_out[1]);
+      uint8_t* d2 = f.out(a2_out, off, cnt, ctx->rt_out[2]);
+      uint8_t* dY = f.out(y_out, off, cnt, ctx->rt_out_y);
+      RET_IF(f.rc);
       if (commitments) {
-        const int64_t* dpos;
-        RET_IF(stage_positions(ctx, space, positions + off, cnt, &dpos));
-        RET_IF(rt_commit_eval_dev(ctx, grp, dc, t, dpos, cnt, dX, space, positions + off));                                   // participant.rs:207-215
+        const int64_t* dpos = f.in_positions(positions, off, cnt);
+        RET_IF(f.rc);
+        RET_IF(rt_commit_eval_dev(f, t, dpos, cnt, dX, positions + off));                             // participant.rs:207-215
       } else {
-        RET_IF(rt_fixed_base_dev(ctx, grp, dc, grp->g_be, (const uint8_t*)dp, cnt, dX, 0));           // X_i = g^P(i)
+        RET_IF(rt_fixed_base_dev(ctx, grp, f.dc, grp->g_be, dp, cnt, dX, 0));                         // X_i = g^P(i)
       }
-      RET_IF(rt_fixed_base_dev(ctx, grp, dc, grp->g_be, (const uint8_t*)dw, cnt, d1, 1));             // a1_i = g^w_i, dleq.rs:207-211
+      RET_IF(rt_fixed_base_dev(ctx, grp, f.dc, grp->g_be, dw, cnt, d1, 1));                           // a1_i = g^w_i, dleq.rs:207-211
       // Y_i = y_i^P(i) (participant.rs:219), a2_i = y_i^w_i (dleq.rs:213-216): one base, two exponents
-      RET_IF(rt_twin_dev(ctx, grp, dc, (const uint8_t*)dy, (const uint8_t*)dp, (const uint8_t*)dw, cnt, dY, d2, wipe));
-      HIPCHK(ctx, hipMemcpyAsync(hX.data(), dX, cnt * EB, hipMemcpyDeviceToHost, ctx->stream));
-      HIPCHK(ctx, hipMemcpyAsync(hY.data(), dY, cnt * EB, hipMemcpyDeviceToHost, ctx->stream));
-      HIPCHK(ctx, hipMemcpyAsync(h1.data(), d1, cnt * EB, hipMemcpyDeviceToHost, ctx->stream));
-      HIPCHK(ctx, hipMemcpyAsync(h2.data(), d2, cnt * EB, hipMemcpyDeviceToHost, ctx->stream));
-      HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-      if (EB == MPVSS_MODP_BYTES) {
-        frame_shares(h, hX.data(), hY.data(), h1.data(), h2.data(), 0, cnt);                          // participant.rs:238-245
-      } else {
-        for (size_t i = 0; i < cnt; ++i)
-          for (const uint8_t* a : {hX.data(), hY.data(), h1.data(), h2.data()}) rt_frame_update(h, a + i * EB, EB);
-      }
-      if (!dev) {
-        if (x_out) memcpy(x_out + off * EB, hX.data(), cnt * EB);
-        if (y_out) memcpy(y_out + off * EB, hY.data(), cnt * EB);
-        if (a1_out) memcpy(a1_out + off * EB, h1.data(), cnt * EB);
-        if (a2_out) memcpy(a2_out + off * EB, h2.data(), cnt * EB);
-      }
-    }
-    RET_IF(spans_collect(ctx));
+      RET_IF(rt_twin_dev(f, dy, dp, dw, cnt, dY, d2));
+      f.to_host(dX, cnt, hv[0]);
+      f.to_host(dY, cnt, hv[1]);
+      f.to_host(d1, cnt, hv[2]);
+      f.to_host(d2, cnt, hv[3]);
+      RET_IF(f.settle());
+      frame_shares(h, hv[0].data(), hv[1].data(), hv[2].data(), hv[3].data(), 0, cnt, f.EB);          // participant.rs:238-245
+      return 0;
+    }));
+    RET_IF(f.end());
   }
   uint8_t digest[32];
   h.final(digest);                                              // participant.rs:251
@@ -1130,15 +1179,12 @@ extern "C" int mpvss_modp_group_prepare(mpvss_ctx* ctx, const mpvss_modp_group* 
   if (!ctx) return MPVSS_E_INVALID;
   std::lock_guard<std::mutex> lk(ctx->mu);
   if (rt_bad_group(grp)) return fail(ctx, MPVSS_E_INVALID, "group_prepare: no group");
-  HIPCHK(ctx, hipSetDevice(ctx->device));
-  spans_reset(ctx);
-  const modp_rt_consts* dc;
-  RET_IF(rt_upload(ctx, grp, &dc));
+  RtCall f(ctx, grp, MPVSS_HOST);
+  RET_IF(f.begin());
   const uint32_t* comb;
-  RET_IF(rt_comb_for(ctx, grp, dc, grp->g_be, 0, true, &comb));
-  RET_IF(rt_comb_for(ctx, grp, dc, grp->G_be, 0, true, &comb));
-  RET_IF(spans_collect(ctx));
-  return MPVSS_OK;
+  RET_IF(rt_comb_for(ctx, grp, f.dc, grp->g_be, 0, true, &comb));
+  RET_IF(rt_comb_for(ctx, grp, f.dc, grp->G_be, 0, true, &comb));
+  return f.end();
 }
 
 // generate_public_key (G^x) and the commitments C_j = g^a_j of a run-time group: one base for the whole call
@@ -1147,30 +1193,17 @@ extern "C" int mpvss_modp_group_batch_exp_fixed_base(mpvss_ctx* ctx, const mpvss
   if (!ctx) return MPVSS_E_INVALID;
   std::lock_guard<std::mutex> lk(ctx->mu);
   if (rt_bad_group(grp)) return fail(ctx, MPVSS_E_INVALID, "group_batch_exp_fixed_base: no group");
-  const size_t EB = grp->eb;
   if (n == 0) return MPVSS_OK;
   if (!base_host || !exps || !out || n > 0x7fffffff) return fail(ctx, MPVSS_E_INVALID, "group_batch_exp_fixed_base: bad argument");
-  HIPCHK(ctx, hipSetDevice(ctx->device));
-  spans_reset(ctx);
-  RtWipe wipe{ctx};
-  const modp_rt_consts* dc;
-  RET_IF(rt_upload(ctx, grp, &dc));
-  for (size_t off = 0; off < n; off += MAX_CHUNK) {
-    const size_t cnt = (n - off < MAX_CHUNK) ? n - off : MAX_CHUNK;
-    const void* de;
-    if (space == MPVSS_HOST) wipe.device(ctx->rt_in[2], cnt * EB);        // keygen secrets
-    RET_IF(stage_in(ctx, space, exps + off * EB, cnt * EB, ctx->rt_in[2], &de));
-    uint8_t* dout = out + off * EB;
-    if (space == MPVSS_HOST) {
-      RET_IF(ensure(ctx, ctx->rt_out[0], cnt * EB));
-      dout = (uint8_t*)ctx->rt_out[0].p;
-    }
-    RET_IF(rt_fixed_base_dev(ctx, grp, dc, base_host, (const uint8_t*)de, cnt, dout, 1));
-    if (space == MPVSS_HOST) RET_IF(copy_out(ctx, space, out + off * EB, dout, cnt * EB));
-    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-  }
-  RET_IF(spans_collect(ctx));
-  return MPVSS_OK;
+  RtCall f(ctx, grp, space);
+  RET_IF(f.begin());
+  RET_IF(f.for_chunks(n, [&](size_t off, size_t cnt) {
+    const uint8_t* de = f.in(exps, off, cnt, ctx->rt_in[2], RtCall::Secret);          // keygen secrets
+    uint8_t* dout = f.out(out, off, cnt, ctx->rt_out[0]);
+    RET_IF(f.rc);
+    return rt_fixed_base_dev(ctx, grp, f.dc, base_host, de, cnt, dout, 1);
+  }));
+  return f.end();
 }
 
 extern "C" int mpvss_modp_group_batch_twin_exp(mpvss_ctx* ctx, const mpvss_modp_group* grp, int space, const uint8_t* bases,
@@ -1178,37 +1211,20 @@ extern "C" int mpvss_modp_group_batch_twin_exp(mpvss_ctx* ctx, const mpvss_modp_
   if (!ctx) return MPVSS_E_INVALID;
   std::lock_guard<std::mutex> lk(ctx->mu);
   if (rt_bad_group(grp)) return fail(ctx, MPVSS_E_INVALID, "group_batch_twin_exp: no group");
-  const size_t EB = grp->eb;
   if (n == 0) return MPVSS_OK;
   if (!bases || !e1 || !e2 || !out1 || !out2 || n > 0x7fffffff) return fail(ctx, MPVSS_E_INVALID, "group_batch_twin_exp: bad argument");
-  HIPCHK(ctx, hipSetDevice(ctx->device));
-  spans_reset(ctx);
-  RtWipe wipe{ctx};
-  const modp_rt_consts* dc;
-  RET_IF(rt_upload(ctx, grp, &dc));
-  for (size_t off = 0; off < n; off += MAX_CHUNK) {
-    const size_t cnt = (n - off < MAX_CHUNK) ? n - off : MAX_CHUNK;
-    const void *db, *d1, *d2;
-    RET_IF(stage_in(ctx, space, bases + off * EB, cnt * EB, ctx->rt_in[0], &db));
-    if (space == MPVSS_HOST) { wipe.device(ctx->rt_in[2], cnt * EB); wipe.device(ctx->rt_in[3], cnt * EB); }
-    RET_IF(stage_in(ctx, space, e1 + off * EB, cnt * EB, ctx->rt_in[2], &d1));
-    RET_IF(stage_in(ctx, space, e2 + off * EB, cnt * EB, ctx->rt_in[3], &d2));
-    uint8_t *o1 = out1 + off * EB, *o2 = out2 + off * EB;
-    if (space == MPVSS_HOST) {
-      RET_IF(ensure(ctx, ctx->rt_out[0], cnt * EB));
-      RET_IF(ensure(ctx, ctx->rt_out[1], cnt * EB));
-      o1 = (uint8_t*)ctx->rt_out[0].p;
-      o2 = (uint8_t*)ctx->rt_out[1].p;
-    }
-    RET_IF(rt_twin_dev(ctx, grp, dc, (const uint8_t*)db, (const uint8_t*)d1, (const uint8_t*)d2, cnt, o1, o2, wipe));
-    if (space == MPVSS_HOST) {
-      RET_IF(copy_out(ctx, space, out1 + off * EB, o1, cnt * EB));
-      RET_IF(copy_out(ctx, space, out2 + off * EB, o2, cnt * EB));
-    }
-    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-  }
-  RET_IF(spans_collect(ctx));
-  return MPVSS_OK;
+  RtCall f(ctx, grp, space);
+  RET_IF(f.begin());
+  RET_IF(f.for_chunks(n, [&](size_t off, size_t cnt) {
+    const uint8_t* db = f.in(bases, off, cnt, ctx->rt_in[0], RtCall::Public);
+    const uint8_t* d1 = f.in(e1, off, cnt, ctx->rt_in[2], RtCall::Secret);
+    const uint8_t* d2 = f.in(e2, off, cnt, ctx->rt_in[3], RtCall::Secret);
+    uint8_t* o1 = f.out(out1, off, cnt, ctx->rt_out[0]);
+    uint8_t* o2 = f.out(out2, off, cnt, ctx->rt_out[1]);
+    RET_IF(f.rc);
+    return rt_twin_dev(f, db, d1, d2, cnt, o1, o2);
+  }));
+  return f.end();
 }
 
 extern "C" int mpvss_modp_group_distribute(mpvss_ctx* ctx, const mpvss_modp_group* grp, int space, const uint8_t* commitments, size_t t,
@@ -1222,9 +1238,8 @@ extern "C" int mpvss_modp_group_distribute(mpvss_ctx* ctx, const mpvss_modp_grou
                                    !a2_out || t == 0 || t > 0x7fffffff)))
     return fail(ctx, MPVSS_E_INVALID, "group_distribute: bad argument");
   if (t > n) return fail(ctx, MPVSS_E_INVALID, "group_distribute: threshold > number of public keys (participant.rs:166)");
-  RtWipe wipe{ctx};
-  return rt_distribute_locked(ctx, grp, space, commitments, t, positions, pubkeys, p_values, witnesses, n, x_out, y_out, a1_out, a2_out,
-                              digest32_out, wipe);
+  RtCall f(ctx, grp, space);
+  return rt_distribute_locked(f, commitments, t, positions, pubkeys, p_values, witnesses, n, x_out, y_out, a1_out, a2_out, digest32_out);
 }
 
 namespace {
@@ -1233,45 +1248,38 @@ namespace {
 // challenge is hashed on the host as ever, and k_rt_modq_responses reads the same two arrays.  P and w of EVERY chunk must
 // survive until the challenge is known, so the two buffers hold all n shares; with the responses' own array (r is copied back from
 // it) the call holds 3 n EB bytes of HBM beside the chunk workspaces: 48 MiB for 65 536 shares of 256 bytes, 72 MiB of 384.  P
-// and w join `wipe`, as do the staged coefficient limbs.  Same bytes as the host path.
+// and w join the frame's wipe, as do the staged coefficient limbs.  Same bytes as the host path.
 int rt_deal_scalar_dev(mpvss_ctx* ctx, const mpvss_modp_group* grp, const uint8_t* coeffs_host, size_t t, const int64_t* positions_host,
                        const uint8_t* pubkeys_host, const uint8_t* witnesses_host, size_t n, uint8_t* x_out, uint8_t* y_out,
                        uint8_t* a1_out, uint8_t* a2_out, uint8_t* digest32_out, uint8_t* challenge_out256, uint8_t* r_out) {
   const size_t EB = grp->eb;
-  HIPCHK(ctx, hipSetDevice(ctx->device));
-  spans_reset(ctx);
-  RtWipe wipe{ctx};
-  const modp_rt_consts* dcq;
-  RET_IF(rt_upload_q(ctx, grp, &dcq));
+  RtCall f(ctx, grp, MPVSS_HOST);
+  f.secrets_dev = true;
+  RET_IF(f.begin(RtCall::SubQ));
   int par_even, par_odd;
   const uint32_t* coef;
-  RET_IF(rt_stage_coeffs(ctx, grp, coeffs_host, t, &par_even, &par_odd, &coef, wipe));
-  RET_IF(ensure(ctx, ctx->rt_sc_p, n * EB));
-  RET_IF(ensure(ctx, ctx->rt_sc_w, n * EB));
-  wipe.device(ctx->rt_sc_p, n * EB);
-  wipe.device(ctx->rt_sc_w, n * EB);
+  RET_IF(rt_stage_coeffs(ctx, grp, coeffs_host, t, &par_even, &par_odd, &coef, f.wipe));
+  uint8_t* dP = f.work(ctx->rt_sc_p, n, RtCall::Secret);
+  uint8_t* dW = f.work(ctx->rt_sc_w, n, RtCall::Secret);
+  RET_IF(f.rc);
   const void* dpos;
   RET_IF(stage_in(ctx, MPVSS_HOST, positions_host, n * 8, ctx->w->pos, &dpos));
-  HIPCHK(ctx, hipMemcpyAsync(ctx->rt_sc_w.p, witnesses_host, n * EB, hipMemcpyHostToDevice, ctx->stream));
-  uint8_t* dP = (uint8_t*)ctx->rt_sc_p.p;
-  const uint8_t* dW = (const uint8_t*)ctx->rt_sc_w.p;
-  TIMED_LAUNCH(ctx, 4, modp_rt_launch_modq_poly_eval(grp->lpl, coef, (int)t, (const int64_t*)dpos, (int)n, par_even, par_odd, dP, dcq,
+  HIPCHK(ctx, hipMemcpyAsync(dW, witnesses_host, n * EB, hipMemcpyHostToDevice, ctx->stream));
+  TIMED_LAUNCH(ctx, 4, modp_rt_launch_modq_poly_eval(grp->lpl, coef, (int)t, (const int64_t*)dpos, (int)n, par_even, par_odd, dP, f.dcq,
                                                      ctx->stream));                                      // participant.rs:202
   uint8_t digest[32], challenge[RT_EB_MAX];
-  RET_IF(rt_distribute_locked(ctx, grp, MPVSS_HOST, nullptr, t, positions_host, pubkeys_host, dP, dW, n, x_out, y_out, a1_out, a2_out,
-                              digest, wipe, true));
+  RET_IF(rt_distribute_locked(f, nullptr, t, positions_host, pubkeys_host, dP, dW, n, x_out, y_out, a1_out, a2_out, digest));
   rt_hash_to_scalar(grp, digest, 32, challenge);                 // participant.rs:251-252
   if (digest32_out) memcpy(digest32_out, digest, 32);
   if (challenge_out256) memcpy(challenge_out256, challenge, EB);
   const uint8_t* dcneg;
   int c_parity;
   RET_IF(rt_stage_cneg(ctx, grp, challenge, &dcneg, &c_parity));
-  RET_IF(ensure(ctx, ctx->rt_sc_r, n * EB));
-  TIMED_LAUNCH(ctx, 4, modp_rt_launch_modq_responses(grp->lpl, dW, dP, dcneg, c_parity, (int)n, (uint8_t*)ctx->rt_sc_r.p, dcq,
-                                                     ctx->stream));                                      // :255-264
-  HIPCHK(ctx, hipMemcpyAsync(r_out, ctx->rt_sc_r.p, n * EB, hipMemcpyDeviceToHost, ctx->stream));
-  RET_IF(spans_collect(ctx));
-  return MPVSS_OK;
+  uint8_t* dR = f.work(ctx->rt_sc_r, n);
+  RET_IF(f.rc);
+  TIMED_LAUNCH(ctx, 4, modp_rt_launch_modq_responses(grp->lpl, dW, dP, dcneg, c_parity, (int)n, dR, f.dcq, ctx->stream));   // :255-264
+  HIPCHK(ctx, hipMemcpyAsync(r_out, dR, n * EB, hipMemcpyDeviceToHost, ctx->stream));
+  return f.end();
 }
 }  // namespace
 
@@ -1295,14 +1303,14 @@ extern "C" int mpvss_modp_group_deal(mpvss_ctx* ctx, const mpvss_modp_group* grp
     return rt_deal_scalar_dev(ctx, grp, coeffs_host, t, positions_host, pubkeys_host, witnesses_host, n, x_out, y_out, a1_out, a2_out,
                               digest32_out, challenge_out256, r_out);
   std::vector<uint8_t> P(n * EB);
-  RtWipe wipe{ctx};
-  wipe.host.push_back(&P);
+  RtCall f(ctx, grp, MPVSS_HOST);
+  f.wipe.host.push_back(&P);
   const int threads = host_threads(0);
   if (n > 0)                                                                                               // participant.rs:202
     rt_rings(grp, [&](const auto& R) { poly_eval_bytes<RT_NW(R)>(R.ord, true, coeffs_host, t, positions_host, n, P.data(), threads); });
   uint8_t digest[32], challenge[RT_EB_MAX];
-  RET_IF(rt_distribute_locked(ctx, grp, MPVSS_HOST, nullptr, t, positions_host, pubkeys_host, P.data(), witnesses_host, n, x_out, y_out,
-                              a1_out, a2_out, digest, wipe));
+  RET_IF(rt_distribute_locked(f, nullptr, t, positions_host, pubkeys_host, P.data(), witnesses_host, n, x_out, y_out, a1_out, a2_out,
+                              digest));
   rt_hash_to_scalar(grp, digest, 32, challenge);                 // participant.rs:251-252
   if (digest32_out) memcpy(digest32_out, digest, 32);
   if (challenge_out256) memcpy(challenge_out256, challenge, EB);
@@ -1325,34 +1333,20 @@ extern "C" int mpvss_modp_group_extract_shares(mpvss_ctx* ctx, const mpvss_modp_
   if (n == 0) return MPVSS_OK;
   if (!pk || !y || !xinv || !w || !s_out || !c_out_host || n > 0x7fffffff)
     return fail(ctx, MPVSS_E_INVALID, "group_extract_shares: bad argument");
-  HIPCHK(ctx, hipSetDevice(ctx->device));
-  spans_reset(ctx);
-  const modp_rt_consts* dc;
-  RET_IF(rt_upload(ctx, grp, &dc));
-  const bool dev = space == MPVSS_DEVICE;
-  const size_t chunk = std::min(n, MAX_CHUNK);
-  std::vector<uint8_t> hpk, hy, hxi, hw, e2(chunk * EB), hS(chunk * EB), h1(chunk * EB), h2(chunk * EB);
-  RtWipe wipe{ctx};
-  wipe.host.push_back(&e2);
-  wipe.host.push_back(&hxi);
-  wipe.host.push_back(&hw);
+  std::vector<uint8_t> hpk, hy, hxi, hw, e2, hS, h1, h2;
+  RtCall f(ctx, grp, space);
+  f.wipe.host.push_back(&e2);
   const int threads = host_threads(0);
   // e2 = w / x on the device (k_rt_modq_mul from the staged w and xinv) or on host threads; the zero-row scan of Y stays here
   const bool sdev = rt_scalar_on_device(ctx, grp, n);
-  const modp_rt_consts* dcq = nullptr;
-  if (sdev) RET_IF(rt_upload_q(ctx, grp, &dcq));
-  for (size_t off = 0; off < n; off += MAX_CHUNK) {
-    const size_t cnt = (n - off < MAX_CHUNK) ? n - off : MAX_CHUNK;
-    const uint8_t *PK = pk + off * EB, *Y = y + off * EB, *XI = xinv + off * EB, *W = w + off * EB;
-    if (dev) {
-      RET_IF(small_vec_to_host(ctx, space, PK, cnt * EB, hpk));
-      RET_IF(small_vec_to_host(ctx, space, Y, cnt * EB, hy));
-      if (!sdev) {
-        RET_IF(small_vec_to_host(ctx, space, XI, cnt * EB, hxi));
-        RET_IF(small_vec_to_host(ctx, space, W, cnt * EB, hw));
-      }
-      PK = hpk.data(); Y = hy.data(); XI = hxi.data(); W = hw.data();
-    }
+  RET_IF(f.begin(sdev ? RtCall::ModQ | RtCall::SubQ : RtCall::ModQ));
+  RET_IF(f.for_chunks(n, [&](size_t off, size_t cnt) {
+    const uint8_t* PK = f.host_view(pk, off, cnt, hpk);
+    const uint8_t* Y = f.host_view(y, off, cnt, hy);
+    const uint8_t* XI = sdev ? nullptr : f.host_view(xinv, off, cnt, hxi, RtCall::Secret);
+    const uint8_t* W = sdev ? nullptr : f.host_view(w, off, cnt, hw, RtCall::Secret);
+    RET_IF(f.host_ready());
+    if (!sdev) e2.resize(cnt * EB);
     std::atomic<int> zero_row{0};
     hsc::parallel_for(cnt, threads, [&](size_t lo, size_t hi) {
       bool z = false;
@@ -1364,63 +1358,40 @@ extern "C" int mpvss_modp_group_extract_shares(mpvss_ctx* ctx, const mpvss_modp_
       if (z) zero_row.store(1);
     });
     const bool shared = zero_row.load() == 0;
-    const void *dy, *dxi, *dw, *de2;
-    RET_IF(stage_in(ctx, space, y + off * EB, cnt * EB, ctx->rt_in[0], &dy));
-    if (!dev) { wipe.device(ctx->rt_in[1], cnt * EB); wipe.device(ctx->rt_in[3], cnt * EB); }
-    wipe.device(ctx->rt_in[2], cnt * EB);
-    RET_IF(stage_in(ctx, space, xinv + off * EB, cnt * EB, ctx->rt_in[1], &dxi));
-    RET_IF(stage_in(ctx, space, w + off * EB, cnt * EB, ctx->rt_in[3], &dw));
-    if (sdev && !shared) {
-      de2 = nullptr;                                             // a chunk with a zero row takes the two dependent chains: no e2
-    } else if (sdev) {
-      RET_IF(ensure(ctx, ctx->rt_in[2], cnt * EB));
-      de2 = ctx->rt_in[2].p;
-      TIMED_LAUNCH(ctx, 4, modp_rt_launch_modq_mul(grp->lpl, (const uint8_t*)dw, (const uint8_t*)dxi, (int)cnt, (uint8_t*)ctx->rt_in[2].p,
-                                                   dcq, ctx->stream));
-    } else {
-      RET_IF(stage_in(ctx, MPVSS_HOST, e2.data(), cnt * EB, ctx->rt_in[2], &de2));
-    }
-    uint8_t* dS = s_out + off * EB;
-    if (!dev) {
-      RET_IF(ensure(ctx, ctx->rt_out[0], cnt * EB));
-      dS = (uint8_t*)ctx->rt_out[0].p;
-    }
-    RET_IF(ensure(ctx, ctx->rt_out[1], cnt * EB));
-    RET_IF(ensure(ctx, ctx->rt_out[2], cnt * EB));
-    uint8_t* d1 = (uint8_t*)ctx->rt_out[1].p;
-    uint8_t* d2 = (uint8_t*)ctx->rt_out[2].p;
+    const uint8_t* dy = f.in(y, off, cnt, ctx->rt_in[0], RtCall::Public);
+    const uint8_t* dxi = f.in(xinv, off, cnt, ctx->rt_in[1], RtCall::Secret);
+    const uint8_t* dw = f.in(w, off, cnt, ctx->rt_in[3], RtCall::Secret);
+    // e2 lives in rt_in[2] wherever it was formed: a secret of the library's own making, zeroed in either space
+    const uint8_t* de2 = sdev ? f.work(ctx->rt_in[2], cnt, RtCall::Secret) : f.in_host(e2.data(), cnt, ctx->rt_in[2], RtCall::Secret);
+    uint8_t* dS = f.out(s_out, off, cnt, ctx->rt_out[0]);
+    uint8_t* d1 = f.work(ctx->rt_out[1], cnt);
+    uint8_t* d2 = f.work(ctx->rt_out[2], cnt);
+    RET_IF(f.rc);
+    if (sdev && shared)                                          // a chunk with a zero row takes the two dependent chains: no e2
+      TIMED_LAUNCH(ctx, 4, modp_rt_launch_modq_mul(grp->lpl, dw, dxi, (int)cnt, (uint8_t*)de2, f.dcq, ctx->stream));
     if (shared) {
-      RET_IF(rt_twin_dev(ctx, grp, dc, (const uint8_t*)dy, (const uint8_t*)dxi, (const uint8_t*)de2, cnt, dS, d2, wipe));
+      RET_IF(rt_twin_dev(f, dy, dxi, de2, cnt, dS, d2));
     } else {
       const uint32_t* tb;
-      RET_IF(rt_tables(ctx, grp, dc, (const uint8_t*)dy, EB, cnt, ctx->rt_tab1, &tb));                 // S = Y^(1/x), :310-314
-      TIMED_LAUNCH(ctx, 3, modp_rt_launch_dual_exp(grp->lpl, tb, 16 * rt_L(grp), nullptr, 0, (const uint8_t*)dxi, EB, nullptr, 0, (int)cnt,
-                                                   dS, dc, ctx->stream));
-      RET_IF(rt_tables(ctx, grp, dc, dS, EB, cnt, ctx->rt_tab2, &tb));                                 // a2 = S^w
-      TIMED_LAUNCH(ctx, 3, modp_rt_launch_dual_exp(grp->lpl, tb, 16 * rt_L(grp), nullptr, 0, (const uint8_t*)dw, EB, nullptr, 0, (int)cnt,
-                                                   d2, dc, ctx->stream));
+      RET_IF(rt_tables(ctx, grp, f.dc, dy, EB, cnt, ctx->rt_tab1, &tb));                               // S = Y^(1/x), :310-314
+      TIMED_LAUNCH(ctx, 3, modp_rt_launch_dual_exp(grp->lpl, tb, 16 * rt_L(grp), nullptr, 0, dxi, EB, nullptr, 0, (int)cnt, dS, f.dc,
+                                                   ctx->stream));
+      RET_IF(rt_tables(ctx, grp, f.dc, dS, EB, cnt, ctx->rt_tab2, &tb));                               // a2 = S^w
+      TIMED_LAUNCH(ctx, 3, modp_rt_launch_dual_exp(grp->lpl, tb, 16 * rt_L(grp), nullptr, 0, dw, EB, nullptr, 0, (int)cnt, d2, f.dc,
+                                                   ctx->stream));
     }
-    RET_IF(rt_fixed_base_dev(ctx, grp, dc, grp->G_be, (const uint8_t*)dw, cnt, d1, 1));                // a1 = G^w
-    HIPCHK(ctx, hipMemcpyAsync(hS.data(), dS, cnt * EB, hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(ctx, hipMemcpyAsync(h1.data(), d1, cnt * EB, hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(ctx, hipMemcpyAsync(h2.data(), d2, cnt * EB, hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    RET_IF(rt_fixed_base_dev(ctx, grp, f.dc, grp->G_be, dw, cnt, d1, 1));                              // a1 = G^w
+    f.to_host(dS, cnt, hS);
+    f.to_host(d1, cnt, h1);
+    f.to_host(d2, cnt, h2);
+    RET_IF(f.settle());
     hsc::parallel_for(cnt, threads, [&](size_t lo, size_t hi) {
-      for (size_t i = lo; i < hi; ++i) {
-        mpvss::Sha256 hs;
-        rt_frame_update(hs, PK + i * EB, EB);
-        rt_frame_update(hs, Y + i * EB, EB);
-        rt_frame_update(hs, h1.data() + i * EB, EB);
-        rt_frame_update(hs, h2.data() + i * EB, EB);
-        uint8_t digest[32];
-        hs.final(digest);
-        rt_hash_to_scalar(grp, digest, 32, c_out_host + (off + i) * EB);      // :329-343
-      }
+      for (size_t i = lo; i < hi; ++i)                                                                // :329-343
+        rt_share_challenge(grp, PK + i * EB, Y + i * EB, h1.data() + i * EB, h2.data() + i * EB, c_out_host + (off + i) * EB);
     });
-    if (!dev) memcpy(s_out + off * EB, hS.data(), cnt * EB);
-  }
-  RET_IF(spans_collect(ctx));
-  return MPVSS_OK;
+    return 0;
+  }));
+  return f.end();
 }
 
 // participant.rs:462-561: G^s = prod_i S_i^lambda_i.  Lagrange exponents mod (q-1)/2 with the sign kept aside (:526-561); a
@@ -1436,10 +1407,10 @@ extern "C" int mpvss_modp_group_reconstruct(mpvss_ctx* ctx, const mpvss_modp_gro
     return fail(ctx, MPVSS_E_INVALID, "group_reconstruct: bad argument");
   for (size_t i = 0; i < m; ++i)
     if (positions_host[i] < 1) return fail(ctx, MPVSS_E_INVALID, "group_reconstruct: positions must be >= 1 (util.rs:47-64)");
-  HIPCHK(ctx, hipSetDevice(ctx->device));
-  spans_reset(ctx);
   std::vector<char> neg;
   std::vector<uint8_t> exps(m * EB), hs;
+  RtCall f(ctx, grp, space);
+  RET_IF(f.begin());
   const bool lagrange_ok = rt_rings(grp, [&](const auto& R) {
     constexpr int NW = RT_NW(R);
     std::vector<hsc::Num<NW>> mag;
@@ -1459,32 +1430,30 @@ extern "C" int mpvss_modp_group_reconstruct(mpvss_ctx* ctx, const mpvss_modp_gro
   if (!lagrange_ok)
     return fail(ctx, MPVSS_E_INVALID, "group_reconstruct: duplicate positions, or a Lagrange denominator without inverse mod (q-1)/2");
   // a share that is 0 mod q has no inverse: the reference returns None when its coefficient is negative (:551-553)
-  RET_IF(small_vec_to_host(ctx, space, shares, m * EB, hs));
+  const uint8_t* S = f.host_view(shares, 0, m, hs);
+  RET_IF(f.host_ready());
   for (size_t i = 0; i < m; ++i)
-    if (neg[i] && rt_zero_mod_q(grp, hs.data() + i * EB))
+    if (neg[i] && rt_zero_mod_q(grp, S + i * EB))
       return fail(ctx, MPVSS_E_INVALID, "group_reconstruct: a share is 0 mod q and has no inverse");
-  const modp_rt_consts* dc;
-  RET_IF(rt_upload(ctx, grp, &dc));
-  const void *dS, *dE;
-  RET_IF(stage_in(ctx, space, shares, m * EB, ctx->rt_in[0], &dS));
-  RET_IF(stage_in(ctx, MPVSS_HOST, exps.data(), m * EB, ctx->rt_in[1], &dE));
-  RET_IF(ensure(ctx, ctx->rt_out[0], m * EB));
-  uint8_t* dF = (uint8_t*)ctx->rt_out[0].p;
+  const uint8_t* dS = f.in(shares, 0, m, ctx->rt_in[0], RtCall::Public);
+  const uint8_t* dE = f.in_host(exps.data(), m, ctx->rt_in[1], RtCall::Public);
+  uint8_t* dF = f.work(ctx->rt_out[0], m);
+  RET_IF(f.rc);
   const uint32_t* tb;
-  RET_IF(rt_tables(ctx, grp, dc, (const uint8_t*)dS, EB, m, ctx->rt_tab2, &tb));
-  TIMED_LAUNCH(ctx, 3, modp_rt_launch_dual_exp(grp->lpl, tb, 16 * rt_L(grp), nullptr, 0, (const uint8_t*)dE, EB, nullptr, 0, (int)m, dF, dc,
+  RET_IF(rt_tables(ctx, grp, f.dc, dS, EB, m, ctx->rt_tab2, &tb));
+  TIMED_LAUNCH(ctx, 3, modp_rt_launch_dual_exp(grp->lpl, tb, 16 * rt_L(grp), nullptr, 0, dE, EB, nullptr, 0, (int)m, dF, f.dc,
                                                ctx->stream));                                          // S_i^lambda_i
-  RET_IF(rt_product_tree(ctx, grp, dc, dF, m));                                                        // fold with mul, :503-505
-  uint8_t gs[RT_EB_MAX];
-  HIPCHK(ctx, hipMemcpyAsync(gs, dF, EB, hipMemcpyDeviceToHost, ctx->stream));
-  HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-  memcpy(gs_out256, gs, EB);
+  RET_IF(rt_product_tree(ctx, grp, f.dc, dF, m));                                                      // fold with mul, :503-505
+  std::vector<uint8_t> gs;
+  f.to_host(dF, 1, gs);
+  RET_IF(f.settle());
+  memcpy(gs_out256, gs.data(), EB);
   if (mask_out32) {
     // int_BE(SHA256(element_to_bytes(G^s))) mod q (:512-515): the reduction matters for q below 2^256
     uint8_t hb[RT_EB_MAX];
     memset(hb, 0, EB - 32);
     mpvss::Sha256 h;
-    rt_frame_min_bytes_update(h, gs, EB);
+    frame_min_bytes_update(h, gs.data(), EB);
     h.final(hb + EB - 32);
     rt_rings(grp, [&](const auto& R) {
       constexpr int NW = RT_NW(R);
@@ -1495,8 +1464,7 @@ extern "C" int mpvss_modp_group_reconstruct(mpvss_ctx* ctx, const mpvss_modp_gro
     });
     memcpy(mask_out32, hb + EB - 32, 32);
   }
-  RET_IF(spans_collect(ctx));
-  return MPVSS_OK;
+  return f.end();
 }
 
 // =====================================================================================================================
@@ -1539,20 +1507,17 @@ extern "C" int mpvss_modp_group_poly_eval_device(mpvss_ctx* ctx, const mpvss_mod
   if (!coeffs_host || !positions_dev || !out_dev || t == 0 || t > 0x7fffffff || n > 0x7fffffff)
     return fail(ctx, MPVSS_E_INVALID, "group_poly_eval_device: bad argument (t must be >= 1)");
   if (!grp->has_q) return fail(ctx, MPVSS_E_INVALID, RT_NO_Q);
-  HIPCHK(ctx, hipSetDevice(ctx->device));
-  spans_reset(ctx);
-  std::vector<int64_t> hp(n);          // declared before `wipe`: the copy into it is drained by ~RtWipe before it goes away
-  RtWipe wipe{ctx};
-  const modp_rt_consts* dcq;
-  RET_IF(rt_upload_q(ctx, grp, &dcq));
+  std::vector<int64_t> hp(n);          // declared before the frame, which drains the copy into it before it goes away
+  RtCall f(ctx, grp, MPVSS_DEVICE);
+  RET_IF(f.begin(RtCall::SubQ));
   int par_even, par_odd;
   const uint32_t* coef;
-  RET_IF(rt_stage_coeffs(ctx, grp, coeffs_host, t, &par_even, &par_odd, &coef, wipe));
-  TIMED_LAUNCH(ctx, 4, modp_rt_launch_modq_poly_eval(grp->lpl, coef, (int)t, positions_dev, (int)n, par_even, par_odd, out_dev, dcq,
+  RET_IF(rt_stage_coeffs(ctx, grp, coeffs_host, t, &par_even, &par_odd, &coef, f.wipe));
+  TIMED_LAUNCH(ctx, 4, modp_rt_launch_modq_poly_eval(grp->lpl, coef, (int)t, positions_dev, (int)n, par_even, par_odd, out_dev, f.dcq,
                                                      ctx->stream));
   // positions are validated after the fact, as mpvss_modp_poly_eval_device does (a negative one is the caller's bug)
   HIPCHK(ctx, hipMemcpyAsync(hp.data(), positions_dev, n * 8, hipMemcpyDeviceToHost, ctx->stream));
-  RET_IF(spans_collect(ctx));
+  RET_IF(f.end());
   for (size_t i = 0; i < n; ++i)
     if (hp[i] < 0) return fail(ctx, MPVSS_E_INVALID, "negative position (the reference panics: negative exponent)");
   return MPVSS_OK;
@@ -1567,16 +1532,13 @@ extern "C" int mpvss_modp_group_dleq_responses_device(mpvss_ctx* ctx, const mpvs
   if (!w_dev || !alpha_dev || !c_host || !r_dev_out || n > 0x7fffffff)
     return fail(ctx, MPVSS_E_INVALID, "group_dleq_responses_device: bad argument");
   if (!grp->has_q) return fail(ctx, MPVSS_E_INVALID, RT_NO_Q);
-  HIPCHK(ctx, hipSetDevice(ctx->device));
-  spans_reset(ctx);
-  const modp_rt_consts* dcq;
-  RET_IF(rt_upload_q(ctx, grp, &dcq));
+  RtCall f(ctx, grp, MPVSS_DEVICE);
+  RET_IF(f.begin(RtCall::SubQ));
   const uint8_t* dcneg;
   int c_parity;
   RET_IF(rt_stage_cneg(ctx, grp, c_host, &dcneg, &c_parity));
-  TIMED_LAUNCH(ctx, 4, modp_rt_launch_modq_responses(grp->lpl, w_dev, alpha_dev, dcneg, c_parity, (int)n, r_dev_out, dcq, ctx->stream));
-  RET_IF(spans_collect(ctx));
-  return MPVSS_OK;
+  TIMED_LAUNCH(ctx, 4, modp_rt_launch_modq_responses(grp->lpl, w_dev, alpha_dev, dcneg, c_parity, (int)n, r_dev_out, f.dcq, ctx->stream));
+  return f.end();
 }
 
 extern "C" int mpvss_modp_group_batch_scalar_mul(mpvss_ctx* ctx, const mpvss_modp_group* grp, int space, const uint8_t* a,
@@ -1584,35 +1546,19 @@ extern "C" int mpvss_modp_group_batch_scalar_mul(mpvss_ctx* ctx, const mpvss_mod
   if (!ctx) return MPVSS_E_INVALID;
   std::lock_guard<std::mutex> lk(ctx->mu);
   if (rt_bad_group(grp)) return fail(ctx, MPVSS_E_INVALID, "group_batch_scalar_mul: no group");
-  const size_t EB = grp->eb;
   if (n == 0) return MPVSS_OK;
   if (!a || !b || !out || n > 0x7fffffff || (space != MPVSS_HOST && space != MPVSS_DEVICE))
     return fail(ctx, MPVSS_E_INVALID, "group_batch_scalar_mul: bad argument");
   if (!grp->has_q) return fail(ctx, MPVSS_E_INVALID, RT_NO_Q);
-  HIPCHK(ctx, hipSetDevice(ctx->device));
-  spans_reset(ctx);
-  RtWipe wipe{ctx};
-  const modp_rt_consts* dcq;
-  RET_IF(rt_upload_q(ctx, grp, &dcq));
-  for (size_t off = 0; off < n; off += MAX_CHUNK) {
-    const size_t cnt = (n - off < MAX_CHUNK) ? n - off : MAX_CHUNK;
-    const void *da, *db;
-    if (space == MPVSS_HOST) {                                   // scalars of the ring are secrets wherever the protocol forms products
-      wipe.device(ctx->rt_in[2], cnt * EB);
-      wipe.device(ctx->rt_in[3], cnt * EB);
-      wipe.device(ctx->rt_out[0], cnt * EB);
-    }
-    RET_IF(stage_in(ctx, space, a + off * EB, cnt * EB, ctx->rt_in[2], &da));
-    RET_IF(stage_in(ctx, space, b + off * EB, cnt * EB, ctx->rt_in[3], &db));
-    uint8_t* dout = out + off * EB;
-    if (space == MPVSS_HOST) {
-      RET_IF(ensure(ctx, ctx->rt_out[0], cnt * EB));
-      dout = (uint8_t*)ctx->rt_out[0].p;
-    }
-    TIMED_LAUNCH(ctx, 4, modp_rt_launch_modq_mul(grp->lpl, (const uint8_t*)da, (const uint8_t*)db, (int)cnt, dout, dcq, ctx->stream));
-    if (space == MPVSS_HOST) RET_IF(copy_out(ctx, space, out + off * EB, dout, cnt * EB));
-    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-  }
-  RET_IF(spans_collect(ctx));
-  return MPVSS_OK;
+  RtCall f(ctx, grp, space);
+  RET_IF(f.begin(RtCall::SubQ));
+  RET_IF(f.for_chunks(n, [&](size_t off, size_t cnt) {      // scalars of the ring are secrets wherever the protocol forms products
+    const uint8_t* da = f.in(a, off, cnt, ctx->rt_in[2], RtCall::Secret);
+    const uint8_t* db = f.in(b, off, cnt, ctx->rt_in[3], RtCall::Secret);
+    uint8_t* dout = f.out(out, off, cnt, ctx->rt_out[0], RtCall::Secret);
+    RET_IF(f.rc);
+    TIMED_LAUNCH(ctx, 4, modp_rt_launch_modq_mul(grp->lpl, da, db, (int)cnt, dout, f.dcq, ctx->stream));
+    return 0;
+  }));
+  return f.end();
 }

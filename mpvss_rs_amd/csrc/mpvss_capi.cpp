@@ -554,33 +554,38 @@ struct Timed {
     RET_IF(span_end((ctx)));            \
   } while (0)
 
-// minimal-length big-endian view of a 256-byte element (modp.rs:150-152: zero -> one 0x00 byte)
-inline void frame_update(mpvss::Sha256& h, const uint8_t* e256) {
+// The widest element the transcript helpers frame: a 384-byte handle of a run-time group (capi_modp_rt.inc).  The helpers take the
+// element size as a trailing parameter; the group-14 call sites leave it at EB.
+constexpr size_t FRAME_EB_MAX = 384;
+
+// minimal-length big-endian view of an eb-byte element (modp.rs:150-152: zero -> one 0x00 byte)
+inline void frame_update(mpvss::Sha256& h, const uint8_t* e, size_t eb = EB) {
   size_t skip = 0;
-  while (skip < EB - 1 && e256[skip] == 0) ++skip;
-  const uint64_t len = EB - skip;
+  while (skip < eb - 1 && e[skip] == 0) ++skip;
+  const uint64_t len = eb - skip;
   uint8_t pre[8];
   for (int i = 0; i < 8; ++i) pre[i] = (uint8_t)(len >> (56 - 8 * i));
   h.update(pre, 8);                 // dleq.rs:58-61
-  h.update(e256 + skip, (size_t)len);
+  h.update(e + skip, (size_t)len);
 }
 
 // The transcript entries of shares [i0, i1): framed(X_i) | framed(Y_i) | framed(a1_i) | framed(a2_i) in share order (dleq.rs:87-99).
 // The frames of a run of shares are laid out contiguously in a cache-resident buffer and hashed with ONE update: the compression
 // function then runs over ~1000 blocks per call with its state in registers, instead of eight small updates per share (each with a
 // partial-block copy and a one-block call) -- 5 % less time per box on the SHA-NI path, same bytes into the hash.
-inline void frame_shares(mpvss::Sha256& h, const uint8_t* hX, const uint8_t* hY, const uint8_t* h1, const uint8_t* h2, size_t i0, size_t i1) {
+inline void frame_shares(mpvss::Sha256& h, const uint8_t* hX, const uint8_t* hY, const uint8_t* h1, const uint8_t* h2, size_t i0, size_t i1,
+                         size_t eb = EB) {
   constexpr size_t RUN = 32;
-  uint8_t buf[RUN * 4 * (EB + 8)];
+  uint8_t buf[RUN * 4 * (FRAME_EB_MAX + 8)];
   for (size_t i = i0; i < i1; i += RUN) {
     const size_t e = i + RUN < i1 ? i + RUN : i1;
     uint8_t* w = buf;
     for (size_t k = i; k < e; ++k)
       for (const uint8_t* a : {hX, hY, h1, h2}) {
-        const uint8_t* el = a + k * EB;
+        const uint8_t* el = a + k * eb;
         size_t skip = 0;
-        while (skip < EB - 1 && el[skip] == 0) ++skip;      // minimal-length big-endian magnitude, zero -> one 0x00 byte (modp.rs:150-152)
-        const uint64_t len = EB - skip;
+        while (skip < eb - 1 && el[skip] == 0) ++skip;      // minimal-length big-endian magnitude, zero -> one 0x00 byte (modp.rs:150-152)
+        const uint64_t len = eb - skip;
         for (int b = 0; b < 8; ++b) w[b] = (uint8_t)(len >> (56 - 8 * b));     // dleq.rs:58-61
         memcpy(w + 8, el + skip, (size_t)len);
         w += 8 + len;
@@ -590,10 +595,10 @@ inline void frame_shares(mpvss::Sha256& h, const uint8_t* hX, const uint8_t* hY,
 }
 
 // the minimal-length bytes alone (no length prefix): SHA256(element_to_bytes(e)) of reconstruct, participant.rs:512
-inline void frame_min_bytes_update(mpvss::Sha256& h, const uint8_t* e256) {
+inline void frame_min_bytes_update(mpvss::Sha256& h, const uint8_t* e, size_t eb = EB) {
   size_t skip = 0;
-  while (skip < EB - 1 && e256[skip] == 0) ++skip;
-  h.update(e256 + skip, EB - skip);
+  while (skip < eb - 1 && e[skip] == 0) ++skip;
+  h.update(e + skip, eb - skip);
 }
 
 // hash_to_scalar(digest) == c  (modp.rs:142-148; the 256-bit hash is already < (q-1)/2)
