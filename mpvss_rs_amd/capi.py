@@ -571,6 +571,13 @@ class Engine:
                     "group_commit_eval")
         return bytes(ko)[: n * EB]
 
+    def group_commit_eval_device(self, grp: "ModpGroup", commitments_dev_ptr: int, t: int, positions_dev_ptr: int, n: int,
+                                 out_dev_ptr: int) -> None:
+        """the same with the t commitments, the n positions (int64) and the n x elem_bytes of X in HBM"""
+        self._check(self.lib.mpvss_modp_group_commit_eval(self.ctx, grp.handle, MPVSS_DEVICE, C.c_void_p(commitments_dev_ptr), int(t),
+                                                          C.c_void_p(positions_dev_ptr), int(n), C.c_void_p(out_dev_ptr)),
+                    "group_commit_eval")
+
     def group_dleq_commitments(self, grp: "ModpGroup", g1: bytes, h1: bytes, g2: bytes, h2: bytes, r: bytes, c: bytes,
                                c_per_share: bool) -> Tuple[bytes, bytes]:
         EB = grp.elem_bytes
