@@ -487,8 +487,8 @@ int mpvss_modp_dleq_responses_device(mpvss_ctx* ctx, const uint8_t* w_dev, const
 /* ---- reconstruct ---------------------------------------------------------------------------------------------------
  * G^s = prod_i S_i^lambda_i from m >= t decrypted shares S_i at pairwise different positions (host int64):
  * src/participant.rs:462-561 (MODP; positions >= 1 as util.rs:47-64 assumes), 1452-1557 (secp256k1), 1895-2002
- * (ristretto255).  Lagrange coefficients in the scalar field on the host, the m exponentiations and their product on
- * the GPU.  gs_out: G^s (256 / 33 / 32 bytes); mask_out32 (optional): the 32-byte big-endian mask the reference XORs
+ * (ristretto255).  A position below 1 is MPVSS_E_INVALID in all three groups: a box's positions are 1..n.  Lagrange
+ * coefficients in the scalar field on the host, the m exponentiations and their product on the GPU.  gs_out: G^s (256 / 33 / 32 bytes); mask_out32 (optional): the 32-byte big-endian mask the reference XORs
  * onto U -- int_BE(SHA256(bytes(G^s))) mod q / mod n / mod l (participant.rs:512-517, 1495-1511, 1939-1949):
  * secret = mask XOR U.  shares in `space`. */
 int mpvss_modp_reconstruct(mpvss_ctx* ctx, int space, const int64_t* positions_host, const uint8_t* shares, size_t m,

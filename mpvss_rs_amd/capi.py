@@ -902,21 +902,36 @@ class Engine:
         self._check(self.lib.mpvss_box_verify_wire(self.ctx, C.cast(buf, C.c_void_p), len(wire), C.byref(v), pd), "box_verify_wire")
         return bool(v.value), bytes(kd)[:32]
 
-    def reconstruct(self, positions: Sequence[int], shares: bytes):
-        """(G^s, mask) from m decrypted shares: secret = int(mask) ^ U (participant.rs:462-519)"""
-        m = len(positions)
-        pos = (C.c_int64 * max(m, 1))(*positions)
-        ks, ps = _buf(shares); kg, pg = _out(EB); km, pm = _out(32)
-        self._check(self.lib.mpvss_modp_reconstruct(self.ctx, MPVSS_HOST, C.cast(pos, C.c_void_p), ps, m, pg, pm), "reconstruct")
-        return bytes(kg)[:EB], bytes(km)[:32]
+    def _reconstruct(self, group: int, space: int, positions: Sequence[int], shares_ptr, m: int, want_mask: bool):
+        """group 0: mpvss_modp_reconstruct, else mpvss_ec_reconstruct; positions are host memory in either space.
+        want_mask=False passes NULL for mask_out32 and returns None in its place."""
+        pos = (C.c_int64 * max(len(positions), 1))(*positions)
+        enc = EC_ENC[group] if group else EB
+        kg, pg = _out(enc)
+        km, pm = _out(32) if want_mask else (None, None)
+        if group:
+            rc = self.lib.mpvss_ec_reconstruct(self.ctx, group, space, C.cast(pos, C.c_void_p), shares_ptr, m, pg, pm)
+        else:
+            rc = self.lib.mpvss_modp_reconstruct(self.ctx, space, C.cast(pos, C.c_void_p), shares_ptr, m, pg, pm)
+        self._check(rc, "ec_reconstruct" if group else "reconstruct")
+        return bytes(kg)[:enc], (bytes(km)[:32] if want_mask else None)
 
-    def ec_reconstruct(self, group: int, positions: Sequence[int], shares: bytes):
-        m = len(positions)
-        pos = (C.c_int64 * max(m, 1))(*positions)
-        ks, ps = _buf(shares); kg, pg = _out(EC_ENC[group]); km, pm = _out(32)
-        self._check(self.lib.mpvss_ec_reconstruct(self.ctx, group, MPVSS_HOST, C.cast(pos, C.c_void_p), ps, m, pg, pm),
-                    "ec_reconstruct")
-        return bytes(kg)[:EC_ENC[group]], bytes(km)[:32]
+    def reconstruct(self, positions: Sequence[int], shares: bytes, want_mask: bool = True):
+        """(G^s, mask) from m decrypted shares: secret = int(mask) ^ U (participant.rs:462-519)"""
+        ks, ps = _buf(shares)
+        return self._reconstruct(0, MPVSS_HOST, positions, ps, len(positions), want_mask)
+
+    def reconstruct_device(self, positions: Sequence[int], shares_dev_ptr: int, m: int, want_mask: bool = True):
+        """reconstruct with the m shares in HBM ([m][256] bytes, left unchanged); positions stay host memory"""
+        return self._reconstruct(0, MPVSS_DEVICE, positions, C.c_void_p(shares_dev_ptr), m, want_mask)
+
+    def ec_reconstruct(self, group: int, positions: Sequence[int], shares: bytes, want_mask: bool = True):
+        ks, ps = _buf(shares)
+        return self._reconstruct(group, MPVSS_HOST, positions, ps, len(positions), want_mask)
+
+    def ec_reconstruct_device(self, group: int, positions: Sequence[int], shares_dev_ptr: int, m: int, want_mask: bool = True):
+        """ec_reconstruct with the m encoded shares in HBM (left unchanged); positions stay host memory"""
+        return self._reconstruct(group, MPVSS_DEVICE, positions, C.c_void_p(shares_dev_ptr), m, want_mask)
 
     def ec_batch_exp_generator(self, group: int, scalars: bytes) -> bytes:
         n = len(scalars) // 32

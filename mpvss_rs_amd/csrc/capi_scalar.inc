@@ -706,6 +706,10 @@ extern "C" int mpvss_ec_reconstruct(mpvss_ctx* ctx, int group, int space, const 
                                     size_t m, uint8_t* gs_out, uint8_t* mask_out32) {
   EC_PROLOGUE("ec_reconstruct");
   if (!positions_host || !shares || m == 0 || !gs_out || m > 0x7fffffff) return fail(ctx, MPVSS_E_INVALID, "ec_reconstruct: bad argument");
+  // a box's positions are 1..n (participant.rs:1127, 1600); the coefficient of a position <= 0 would multiply `j as u64` into
+  // the numerator and the signed difference into the denominator, which is no Lagrange coefficient: refused as for MODP
+  for (size_t i = 0; i < m; ++i)
+    if (positions_host[i] < 1) return fail(ctx, MPVSS_E_INVALID, "ec_reconstruct: positions must be >= 1");
   std::vector<hsc::Num<4>> mag;
   std::vector<char> neg;
   if (!lagrange_at_zero<4>(ec_order(gi), positions_host, m, mag, neg, true))
