@@ -538,8 +538,9 @@ int mpvss_box_verify_wire(mpvss_ctx* ctx, const uint8_t* buf, size_t len, int* v
  * concurrent callers on one context in the same sense.  The whole protocol is there: verification, the dealer (distribute,
  * the one-call deal), extract_secret_share and reconstruct.  The scalar ring Z/(q-1) -- P(i), the responses, e2 = w / x -- runs
  * on host threads or, for a handle with odd (q-1)/2 >= 3 (every safe prime above 5), on the device: mpvss_ctx_set_rt_scalar and
- * "the scalar ring on the device" below.  Not offered for a
- * run-time group: the block / pipeline forms, verify_many, key sets and the wire format; moduli above 3072 bits are refused
+ * "the scalar ring on the device" below.  Long-lived public keys can be registered as a key set ("Key sets of a run-time group"
+ * below).  Not offered for a
+ * run-time group: the block / pipeline forms, verify_many and the wire format; moduli above 3072 bits are refused
  * with MPVSS_E_INVALID (4096 bits would overflow the product's 64-bit column accumulators). */
 typedef struct mpvss_modp_group mpvss_modp_group;
 /* q_be: q_len big-endian bytes (leading zeros allowed).  MPVSS_E_INVALID for an even q, q < 5 or q >= 2^2048. */
@@ -677,6 +678,50 @@ int mpvss_modp_group_scalar_min_shares(const mpvss_modp_group* grp);
 /* whole group_deal / group_extract_shares calls that ran the scalar ring on the device and on the host since the context was
  * created (either pointer may be null) */
 int mpvss_modp_group_scalar_stats(mpvss_ctx* ctx, unsigned long long* device_calls, unsigned long long* host_calls);
+
+/* Key sets of a run-time group.  The full-width powers of a participant's public key -- a2_i = y_i^r_i Y_i^c of the verifier,
+ * Y_i = y_i^P(i) and a2_i = y_i^w_i of the dealer -- are the largest term of a share, and keys are long-lived: a key set holds,
+ * for each of n keys, the rows y^(d 2^(256 j)), j < element size / 32, d < 16 (mpvss_modp_group_keyset_bytes_per_key bytes per
+ * key: 10 240, 18 432, 36 864 or 82 944 at 5, 9, 18 or 27 limbs per lane), over which such a power needs 252 squarings instead
+ * of 2 044 at 2048 bits.  Keys need not be reduced; a key that is 0 mod q gives 0^0 = 1 and 0^e = 0 (modp.rs:122-128).
+ * OWNERSHIP: a set belongs to the context that built it, remembers the modulus and width it was built for and never changes.
+ * The calls below are synchronous, so destroying a set after the last call that named it has returned is safe; destroy frees it
+ * on its own context whichever context is named (both arguments may be null); a set is destroyed before its context.
+ * ERRORS: MPVSS_E_INVALID for a set of another context or another modulus, for key_offset + n beyond the set, and for create
+ * with n == 0 or a null pointer; an allocation that fails is MPVSS_E_NOMEM and leaves the context usable.  RESULTS are byte-identical to the calls that take the keys as an
+ * array -- a2 of mpvss_modp_group_dleq_commitments, mpvss_modp_group_batch_twin_exp, mpvss_modp_group_verify_distribution and
+ * mpvss_modp_group_deal with pubkeys = the keys key_offset .. key_offset + n - 1 of the set -- n == 0, the optional dumps, the
+ * digests and the challenge included, under every mode of mpvss_ctx_set_rt_scalar and mpvss_ctx_set_rt_fd.  The rows hold
+ * public values only and are not wiped; exponents staged from the host are treated as in those calls.  Not offered: a key
+ * cache behind the calls that take a key array, and group_distribute over a key set. */
+typedef struct mpvss_modp_group_keyset mpvss_modp_group_keyset;
+/* bytes of one key's rows at this handle's width; host only; 0 for no group */
+size_t mpvss_modp_group_keyset_bytes_per_key(const mpvss_modp_group* grp);
+/* pubkeys: n x element size bytes in `space`; the build is 1 + 256 (J - 1) + 14 J products per key, J = element size / 32 */
+int mpvss_modp_group_keyset_create(mpvss_ctx* ctx, const mpvss_modp_group* grp, int space, const uint8_t* pubkeys, size_t n,
+                                   mpvss_modp_group_keyset** out);
+void mpvss_modp_group_keyset_destroy(mpvss_ctx* ctx, mpvss_modp_group_keyset* keyset);
+/* device bytes of the set's rows; host only; 0 for no set */
+size_t mpvss_modp_group_keyset_bytes(const mpvss_modp_group_keyset* keyset);
+/* out[i] = y_(key_offset+i)^e1[i] * h2[i]^e2[i] mod q; h2 == NULL: the first factor alone.  e2: n scalars in `space` when
+ * e2_per_share, else ONE scalar in host memory for every share (as c of mpvss_modp_group_dleq_commitments) */
+int mpvss_modp_group_keyset_dual_exp(mpvss_ctx* ctx, const mpvss_modp_group* grp, int space, const mpvss_modp_group_keyset* keyset,
+                                     size_t key_offset, const uint8_t* e1, const uint8_t* h2, const uint8_t* e2, int e2_per_share,
+                                     size_t n, uint8_t* out);
+/* out1[i] = y_(key_offset+i)^e1[i], out2[i] = y_(key_offset+i)^e2[i] mod q: two exponent sets in one launch */
+int mpvss_modp_group_keyset_twin_exp(mpvss_ctx* ctx, const mpvss_modp_group* grp, int space, const mpvss_modp_group_keyset* keyset,
+                                     size_t key_offset, const uint8_t* e1, const uint8_t* e2, size_t n, uint8_t* out1, uint8_t* out2);
+/* mpvss_modp_group_verify_distribution with (keyset, key_offset) in place of pubkeys */
+int mpvss_modp_group_verify_distribution_keyset(mpvss_ctx* ctx, const mpvss_modp_group* grp, int space, const uint8_t* commitments,
+                                                size_t t, const int64_t* positions, const mpvss_modp_group_keyset* keyset,
+                                                size_t key_offset, const uint8_t* shares, const uint8_t* responses, size_t n,
+                                                const uint8_t* challenge_host, int* verdict, uint8_t* digest32_out,
+                                                uint8_t* x_out_host, uint8_t* a1_out_host, uint8_t* a2_out_host);
+/* mpvss_modp_group_deal with (keyset, key_offset) in place of pubkeys_host */
+int mpvss_modp_group_deal_keyset(mpvss_ctx* ctx, const mpvss_modp_group* grp, const uint8_t* coeffs_host, size_t t,
+                                 const int64_t* positions_host, const mpvss_modp_group_keyset* keyset, size_t key_offset,
+                                 const uint8_t* witnesses_host, size_t n, uint8_t* x_out, uint8_t* y_out, uint8_t* a1_out,
+                                 uint8_t* a2_out, uint8_t* digest32_out, uint8_t* challenge_out256, uint8_t* r_out);
 
 /* ---- hashing helpers (host only; Group::hash_to_scalar, src/groups/modp.rs:142-148) ------ */
 

@@ -59,6 +59,9 @@ EXPORTED_SYMBOLS = (
     "mpvss_modp_group_has_device_scalar", "mpvss_modp_group_scalar_min_shares", "mpvss_ctx_set_rt_scalar",
     "mpvss_modp_group_scalar_stats", "mpvss_modp_group_poly_eval_device", "mpvss_modp_group_dleq_responses_device",
     "mpvss_modp_group_batch_scalar_mul",
+    "mpvss_modp_group_keyset_bytes_per_key", "mpvss_modp_group_keyset_create", "mpvss_modp_group_keyset_destroy",
+    "mpvss_modp_group_keyset_bytes", "mpvss_modp_group_keyset_dual_exp", "mpvss_modp_group_keyset_twin_exp",
+    "mpvss_modp_group_verify_distribution_keyset", "mpvss_modp_group_deal_keyset",
 )
 
 GROUP_SECP256K1 = 1
@@ -257,6 +260,18 @@ def load_library() -> C.CDLL:
     lib.mpvss_modp_group_poly_eval_device.argtypes = [vp, vp, u8p, sz, vp, sz, vp]
     lib.mpvss_modp_group_dleq_responses_device.argtypes = [vp, vp, vp, vp, u8p, sz, vp]
     lib.mpvss_modp_group_batch_scalar_mul.argtypes = [vp, vp, ci, vp, vp, sz, vp]
+    lib.mpvss_modp_group_keyset_bytes_per_key.argtypes = [vp]
+    lib.mpvss_modp_group_keyset_bytes_per_key.restype = sz
+    lib.mpvss_modp_group_keyset_create.argtypes = [vp, vp, ci, vp, sz, C.POINTER(vp)]
+    lib.mpvss_modp_group_keyset_destroy.argtypes = [vp, vp]
+    lib.mpvss_modp_group_keyset_destroy.restype = None
+    lib.mpvss_modp_group_keyset_bytes.argtypes = [vp]
+    lib.mpvss_modp_group_keyset_bytes.restype = sz
+    lib.mpvss_modp_group_keyset_dual_exp.argtypes = [vp, vp, ci, vp, sz, u8p, u8p, u8p, ci, sz, u8p]
+    lib.mpvss_modp_group_keyset_twin_exp.argtypes = [vp, vp, ci, vp, sz, u8p, u8p, sz, u8p, u8p]
+    lib.mpvss_modp_group_verify_distribution_keyset.argtypes = [vp, vp, ci, u8p, sz, i64p, vp, sz, u8p, u8p, sz, u8p,
+                                                                C.POINTER(ci), u8p, u8p, u8p, u8p]
+    lib.mpvss_modp_group_deal_keyset.argtypes = [vp, vp, u8p, sz, i64p, vp, sz, u8p, sz, u8p, u8p, u8p, u8p, u8p, u8p, u8p]
     return lib
 
 
@@ -271,6 +286,29 @@ def _buf(b: Optional[bytes]):
 def _out(nbytes: int):
     arr = (C.c_uint8 * max(nbytes, 1))()
     return arr, C.cast(arr, C.c_void_p)
+
+
+class GroupKeySet:
+    """The rows of registered public keys of a run-time group on one Engine's context (mpvss_modp_group_keyset_create): immutable;
+    close() frees the device memory (after the last call that uses the set has returned)."""
+
+    def __init__(self, engine, grp, handle, n):
+        self.engine, self.grp, self.handle, self.n = engine, grp, handle, n
+
+    @property
+    def nbytes(self) -> int:
+        return int(self.engine.lib.mpvss_modp_group_keyset_bytes(self.handle)) if self.handle else 0
+
+    def close(self) -> None:
+        if self.handle:
+            self.engine.lib.mpvss_modp_group_keyset_destroy(self.engine.ctx, self.handle)
+            self.handle = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
 
 
 class ModpGroup:
@@ -316,6 +354,11 @@ class ModpGroup:
     def comb_min_shares(self) -> int:
         """batch size from which a call builds the fixed-base comb of a shared base the context has not cached"""
         return self.lib.mpvss_modp_group_comb_min_shares(self.handle)
+
+    @property
+    def keyset_bytes_per_key(self) -> int:
+        """device bytes of one key's rows in a key set of this group (Engine.group_keyset_create)"""
+        return int(self.lib.mpvss_modp_group_keyset_bytes_per_key(self.handle))
 
     @property
     def has_device_scalar(self) -> bool:
@@ -658,6 +701,82 @@ class Engine:
         self._check(self.lib.mpvss_modp_group_deal(self.ctx, grp.handle, k[0][1], len(coeffs) // EB, C.cast(pos, C.c_void_p), k[1][1],
                                                    k[2][1], n, outs[0][1], outs[1][1], outs[2][1], outs[3][1], pd, pc, outs[4][1]),
                     "group_deal")
+        X, Y, a1, a2, r = (bytes(o[0])[: n * EB] for o in outs)
+        return {"X": X, "Y": Y, "a1": a1, "a2": a2, "digest": bytes(kd)[:32], "challenge": bytes(kc)[:EB], "responses": r}
+
+    # ---- key sets of a run-time group -------------------------------------------------------------------------------
+    def group_keyset_create(self, grp: "ModpGroup", pubkeys: bytes) -> "GroupKeySet":
+        """register n public keys (n x elem_bytes, host): their rows are built once and stay on this context"""
+        n = len(pubkeys) // grp.elem_bytes
+        kk, pk = _buf(pubkeys or None)
+        h = C.c_void_p()
+        self._check(self.lib.mpvss_modp_group_keyset_create(self.ctx, grp.handle, MPVSS_HOST, pk, n, C.byref(h)), "group_keyset_create")
+        return GroupKeySet(self, grp, h, n)
+
+    def group_keyset_create_device(self, grp: "ModpGroup", pubkeys_dev_ptr: int, n: int) -> "GroupKeySet":
+        """the same from n keys in HBM"""
+        h = C.c_void_p()
+        self._check(self.lib.mpvss_modp_group_keyset_create(self.ctx, grp.handle, MPVSS_DEVICE, C.c_void_p(pubkeys_dev_ptr), int(n),
+                                                            C.byref(h)), "group_keyset_create")
+        return GroupKeySet(self, grp, h, int(n))
+
+    def group_keyset_dual_exp(self, grp: "ModpGroup", keyset: "GroupKeySet", key_offset: int, e1: bytes, h2: Optional[bytes] = None,
+                              e2: Optional[bytes] = None, e2_per_share: bool = False) -> bytes:
+        """out[i] = y_(key_offset+i)^e1[i] * h2[i]^e2[i]; h2 None: the first factor alone; e2: one scalar, or n when e2_per_share"""
+        EB = grp.elem_bytes
+        n = len(e1) // EB
+        k = [_buf(x or None) for x in (e1, h2, e2)]
+        ko, po = _out(n * EB)
+        self._check(self.lib.mpvss_modp_group_keyset_dual_exp(self.ctx, grp.handle, MPVSS_HOST, keyset.handle, int(key_offset), k[0][1],
+                                                              k[1][1], k[2][1], int(e2_per_share), n, po), "group_keyset_dual_exp")
+        return bytes(ko)[: n * EB]
+
+    def group_keyset_twin_exp(self, grp: "ModpGroup", keyset: "GroupKeySet", key_offset: int, e1: bytes, e2: bytes) -> Tuple[bytes, bytes]:
+        """(y^e1, y^e2) of the keys key_offset .. of the set"""
+        EB = grp.elem_bytes
+        n = len(e1) // EB
+        k = [_buf(x or None) for x in (e1, e2)]
+        k1, p1 = _out(n * EB); k2, p2 = _out(n * EB)
+        self._check(self.lib.mpvss_modp_group_keyset_twin_exp(self.ctx, grp.handle, MPVSS_HOST, keyset.handle, int(key_offset), k[0][1],
+                                                              k[1][1], n, p1, p2), "group_keyset_twin_exp")
+        return bytes(k1)[: n * EB], bytes(k2)[: n * EB]
+
+    def group_verify_distribution_keyset(self, grp: "ModpGroup", commitments: bytes, positions: Sequence[int], keyset: "GroupKeySet",
+                                         key_offset: int, shares: bytes, responses: bytes, challenge: bytes, dump: bool = False):
+        """group_verify_distribution with the keys key_offset .. key_offset + n - 1 of a key set for pubkeys"""
+        EB = grp.elem_bytes
+        t = len(commitments) // EB
+        n = len(positions)
+        kc, pc = _buf(commitments or None); kY, pY = _buf(shares or None)
+        kr, pr = _buf(responses or None); kch, pch = _buf(challenge)
+        pos = (C.c_int64 * max(n, 1))(*positions)
+        verdict = C.c_int(0)
+        kd, pd = _out(32)
+        kx = k1 = k2 = None
+        px = p1 = p2 = None
+        if dump:
+            kx, px = _out(n * EB); k1, p1 = _out(n * EB); k2, p2 = _out(n * EB)
+        self._check(self.lib.mpvss_modp_group_verify_distribution_keyset(
+            self.ctx, grp.handle, MPVSS_HOST, pc, t, C.cast(pos, C.c_void_p), keyset.handle, int(key_offset), pY, pr, n, pch,
+            C.byref(verdict), pd, px, p1, p2), "group_verify_distribution_keyset")
+        out = {"verdict": bool(verdict.value), "digest": bytes(kd)[:32]}
+        if dump:
+            out.update(X=bytes(kx)[: n * EB], a1=bytes(k1)[: n * EB], a2=bytes(k2)[: n * EB])
+        return out
+
+    def group_deal_keyset(self, grp: "ModpGroup", coeffs: bytes, positions: Sequence[int], keyset: "GroupKeySet", key_offset: int,
+                          witnesses: bytes) -> dict:
+        """group_deal with the keys key_offset .. key_offset + n - 1 of a key set for pubkeys"""
+        EB = grp.elem_bytes
+        n = len(positions)
+        pos = (C.c_int64 * max(n, 1))(*positions)
+        k = [_buf(b or None) for b in (coeffs, witnesses)]
+        outs = [_out(n * EB) for _ in range(5)]
+        kd, pd = _out(32)
+        kc, pc = _out(EB)
+        self._check(self.lib.mpvss_modp_group_deal_keyset(self.ctx, grp.handle, k[0][1], len(coeffs) // EB, C.cast(pos, C.c_void_p),
+                                                          keyset.handle, int(key_offset), k[1][1], n, outs[0][1], outs[1][1],
+                                                          outs[2][1], outs[3][1], pd, pc, outs[4][1]), "group_deal_keyset")
         X, Y, a1, a2, r = (bytes(o[0])[: n * EB] for o in outs)
         return {"X": X, "Y": Y, "a1": a1, "a2": a2, "digest": bytes(kd)[:32], "challenge": bytes(kc)[:EB], "responses": r}
 

@@ -36,13 +36,15 @@ using bn::W;
 
 // the width's constants; EB: bytes of an element or scalar on the ABI of a group of this width; IN_ROWS: rows of the long
 // product that takes a whole EB-byte input (its limbs, padded to a multiple of LPL so that the accumulators end where they
-// started: 75, 72, 72 and, at the wide width, 108 = L, a plain product with R^2 mod N); COMB_ROWS: 4-bit windows of an exponent
+// started: 75, 72, 72 and, at the wide width, 108 = L, a plain product with R^2 mod N); COMB_ROWS: 4-bit windows of an exponent;
+// KS_ROWS: 256-bit rows of an exponent (the rows of a key set)
 template <int LPL>
 struct Width {
   static constexpr int L = 4 * LPL;
   static constexpr int EB = LPL == 27 ? 384 : 256;
   static constexpr int IN_ROWS = LPL * (((8 * EB + 28) / 29 + LPL - 1) / LPL);
   static constexpr int COMB_ROWS = 2 * EB;
+  static constexpr int KS_ROWS = EB / 32;
   static constexpr int SLOT = ((IN_ROWS > L ? IN_ROWS : L) + 3) & ~3;   // LDS words of one operand slot (16-byte multiple)
   static constexpr int CAP_BITS = 29 * L - 2;                            // largest modulus this width takes
 };

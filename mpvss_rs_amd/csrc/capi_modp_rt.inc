@@ -35,6 +35,18 @@ struct mpvss_modp_group {
   RtRings<48> r48;           // ... and of a 384-byte one (the other stays unset)
 };
 
+// A key set of a run-time group (include/mpvss_hip.h, "Key sets of a run-time group"): the rows of n public keys on the device
+// (modp_rt_launch_keyset_build).  It belongs to the context that built it, remembers the modulus and the width it was built for,
+// and never changes after create.  The rows hold public values only and are not wiped.
+struct mpvss_modp_group_keyset {
+  mpvss_ctx* ctx = nullptr;
+  uint8_t q_be[RT_EB_MAX];
+  size_t eb = 0;
+  int lpl = 0;
+  size_t n = 0;
+  uint32_t* rows = nullptr;  // [n][eb / 32][16][L] words
+};
+
 namespace {
 
 // fn(rings) with the handle's own rings: RT_NW(rings), 32 or 48 words, is a compile-time constant inside fn
@@ -352,10 +364,11 @@ int rt_comb_for(mpvss_ctx* ctx, const mpvss_modp_group* grp, const modp_rt_const
   return 0;
 }
 
-// a1 = g1^r h1^c and a2 = g2^r h2^c for cnt shares (device pointers but g1: one shared base in host bytes; c stride 0 = shared)
+// a1 = g1^r h1^c and a2 = g2^r h2^c for cnt shares (device pointers but g1: one shared base in host bytes; c stride 0 = shared);
+// g2: the second proof's bases as bytes, or (g2 null) g2_rows: the rows of a key set from the chunk's first key on
 int rt_dleq_dev(mpvss_ctx* ctx, const mpvss_modp_group* grp, const modp_rt_consts* dc, const uint8_t* g1_host, const uint8_t* h1,
-                const uint8_t* g2, const uint8_t* h2, const uint8_t* r, const uint8_t* c, size_t c_stride, size_t cnt, uint8_t* a1,
-                uint8_t* a2) {
+                const uint8_t* g2, const uint32_t* g2_rows, const uint8_t* h2, const uint8_t* r, const uint8_t* c, size_t c_stride,
+                size_t cnt, uint8_t* a1, uint8_t* a2) {
   const size_t TW = 16 * rt_L(grp), EB = grp->eb;
   const uint32_t *tg, *t1, *t2;
   if (a1) {
@@ -371,9 +384,14 @@ int rt_dleq_dev(mpvss_ctx* ctx, const mpvss_modp_group* grp, const modp_rt_const
     }
   }
   if (a2) {
-    RET_IF(rt_tables(ctx, grp, dc, g2, EB, cnt, ctx->rt_tab1, &t1));
     RET_IF(rt_tables(ctx, grp, dc, h2, EB, cnt, ctx->rt_tab2, &t2));
-    TIMED_LAUNCH(ctx, 3, modp_rt_launch_dual_exp(grp->lpl, t1, TW, t2, TW, r, EB, c, c_stride, (int)cnt, a2, dc, ctx->stream));
+    if (g2) {
+      RET_IF(rt_tables(ctx, grp, dc, g2, EB, cnt, ctx->rt_tab1, &t1));
+      TIMED_LAUNCH(ctx, 3, modp_rt_launch_dual_exp(grp->lpl, t1, TW, t2, TW, r, EB, c, c_stride, (int)cnt, a2, dc, ctx->stream));
+    } else {
+      TIMED_LAUNCH(ctx, 3, modp_rt_launch_keyset_exp(grp->lpl, g2_rows, t2, TW, r, nullptr, c, c_stride, (int)cnt, a2, nullptr, dc,
+                                                     ctx->stream));
+    }
   }
   return 0;
 }
@@ -545,6 +563,22 @@ void rt_share_challenge(const mpvss_modp_group* grp, const uint8_t* a, const uin
 }
 
 bool rt_bad_group(const mpvss_modp_group* grp) { return grp == nullptr || grp->lpl == 0; }
+
+// words of one key's rows
+size_t rt_keyset_stride(const mpvss_modp_group* grp) { return modp_rt_keyset_bytes(grp->lpl, 1) / 4; }
+
+// The one admission of a key set to a call (context lock held): built by this context, for this modulus at this width, and
+// holding the keys key_offset .. key_offset + n - 1.  *rows: the rows of key key_offset.
+int rt_keyset_rows(mpvss_ctx* ctx, const mpvss_modp_group* grp, const mpvss_modp_group_keyset* ks, size_t key_offset, size_t n,
+                   const uint32_t** rows) {
+  if (!ks) return fail(ctx, MPVSS_E_INVALID, "key set: none given");
+  if (ks->ctx != ctx) return fail(ctx, MPVSS_E_INVALID, "key set: built by another context");
+  if (ks->eb != grp->eb || ks->lpl != grp->lpl || memcmp(ks->q_be, grp->q_be, grp->eb) != 0)
+    return fail(ctx, MPVSS_E_INVALID, "key set: built for another modulus");
+  if (key_offset > ks->n || n > ks->n - key_offset) return fail(ctx, MPVSS_E_INVALID, "key set: key_offset + n is beyond the set");
+  *rows = ks->rows + key_offset * rt_keyset_stride(grp);
+  return 0;
+}
 
 }  // namespace
 
@@ -751,23 +785,19 @@ extern "C" int mpvss_modp_group_dleq_commitments(mpvss_ctx* ctx, const mpvss_mod
     uint8_t* d1 = f.out(a1_out, off, cnt, ctx->rt_out[0]);
     uint8_t* d2 = f.out(a2_out, off, cnt, ctx->rt_out[1]);
     RET_IF(f.rc);
-    return rt_dleq_dev(ctx, grp, f.dc, g1_host, dh1, dg2, dh2, dr, dcs, c_per_share ? f.EB : 0, cnt, d1, d2);
+    return rt_dleq_dev(ctx, grp, f.dc, g1_host, dh1, dg2, nullptr, dh2, dr, dcs, c_per_share ? f.EB : 0, cnt, d1, d2);
   }));
   return f.end();
 }
 
-extern "C" int mpvss_modp_group_verify_distribution(mpvss_ctx* ctx, const mpvss_modp_group* grp, int space, const uint8_t* commitments,
-                                                    size_t t, const int64_t* positions, const uint8_t* pubkeys, const uint8_t* shares,
-                                                    const uint8_t* responses, size_t n, const uint8_t* challenge_host, int* verdict,
-                                                    uint8_t* digest32_out, uint8_t* x_out_host, uint8_t* a1_out_host,
-                                                    uint8_t* a2_out_host) {
-  if (!ctx) return MPVSS_E_INVALID;
-  std::lock_guard<std::mutex> lk(ctx->mu);
-  if (rt_bad_group(grp)) return fail(ctx, MPVSS_E_INVALID, "group_verify_distribution: no group");
+namespace {
+// participant.rs:399-455 for one box, arguments checked and the context lock held: the keys are the caller's array `pubkeys`, or
+// (pubkeys null) key_rows, the rows of a key set from the box's first key on
+int rt_verify_distribution_locked(mpvss_ctx* ctx, const mpvss_modp_group* grp, int space, const uint8_t* commitments, size_t t,
+                                  const int64_t* positions, const uint8_t* pubkeys, const uint32_t* key_rows, const uint8_t* shares,
+                                  const uint8_t* responses, size_t n, const uint8_t* challenge_host, int* verdict,
+                                  uint8_t* digest32_out, uint8_t* x_out_host, uint8_t* a1_out_host, uint8_t* a2_out_host) {
   const size_t EB = grp->eb;
-  if (!verdict || !challenge_host || n > 0x7fffffff || t > 0x7fffffff ||
-      (n > 0 && (!commitments || !positions || !pubkeys || !shares || !responses || t == 0)))
-    return fail(ctx, MPVSS_E_INVALID, "group_verify_distribution: bad argument");
   *verdict = 0;
   mpvss::Sha256 h;
   if (n > 0) {
@@ -779,7 +809,7 @@ extern "C" int mpvss_modp_group_verify_distribution(mpvss_ctx* ctx, const mpvss_
     RET_IF(rt_stage_small(ctx, grp, challenge_host, ctx->rt_small[1], &dch));
     RET_IF(f.for_chunks(n, [&](size_t off, size_t cnt) {
       const int64_t* dpos = f.in_positions(positions, off, cnt);
-      const uint8_t* dy = f.in(pubkeys, off, cnt, ctx->rt_in[1], RtCall::Public);
+      const uint8_t* dy = pubkeys ? f.in(pubkeys, off, cnt, ctx->rt_in[1], RtCall::Public) : nullptr;
       const uint8_t* dY = f.in(shares, off, cnt, ctx->rt_in[2], RtCall::Public);
       const uint8_t* dr = f.in(responses, off, cnt, ctx->rt_in[3], RtCall::Public);
       uint8_t* dX = f.work(ctx->rt_out[0], cnt);
@@ -788,7 +818,8 @@ extern "C" int mpvss_modp_group_verify_distribution(mpvss_ctx* ctx, const mpvss_
       RET_IF(f.rc);
       RET_IF(rt_commit_eval_dev(f, t, dpos, cnt, dX, positions + off));
       // a1 = g^r X^c, a2 = y^r Y^c (src/participant.rs:436-447 -> src/dleq.rs:66-84)
-      RET_IF(rt_dleq_dev(ctx, grp, f.dc, grp->g_be, dX, dy, dY, dr, dch, 0, cnt, d1, d2));
+      RET_IF(rt_dleq_dev(ctx, grp, f.dc, grp->g_be, dX, dy, pubkeys ? nullptr : key_rows + off * rt_keyset_stride(grp), dY, dr, dch, 0,
+                         cnt, d1, d2));
       f.to_host(dX, cnt, hX);
       f.to_host(d1, cnt, h1);
       f.to_host(d2, cnt, h2);
@@ -809,6 +840,22 @@ extern "C" int mpvss_modp_group_verify_distribution(mpvss_ctx* ctx, const mpvss_
   rt_hash_to_scalar(grp, digest, 32, c);          // src/participant.rs:451-455
   *verdict = memcmp(c, challenge_host, EB) == 0 ? 1 : 0;
   return MPVSS_OK;
+}
+}  // namespace
+
+extern "C" int mpvss_modp_group_verify_distribution(mpvss_ctx* ctx, const mpvss_modp_group* grp, int space, const uint8_t* commitments,
+                                                    size_t t, const int64_t* positions, const uint8_t* pubkeys, const uint8_t* shares,
+                                                    const uint8_t* responses, size_t n, const uint8_t* challenge_host, int* verdict,
+                                                    uint8_t* digest32_out, uint8_t* x_out_host, uint8_t* a1_out_host,
+                                                    uint8_t* a2_out_host) {
+  if (!ctx) return MPVSS_E_INVALID;
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  if (rt_bad_group(grp)) return fail(ctx, MPVSS_E_INVALID, "group_verify_distribution: no group");
+  if (!verdict || !challenge_host || n > 0x7fffffff || t > 0x7fffffff ||
+      (n > 0 && (!commitments || !positions || !pubkeys || !shares || !responses || t == 0)))
+    return fail(ctx, MPVSS_E_INVALID, "group_verify_distribution: bad argument");
+  return rt_verify_distribution_locked(ctx, grp, space, commitments, t, positions, pubkeys, nullptr, shares, responses, n, challenge_host,
+                                       verdict, digest32_out, x_out_host, a1_out_host, a2_out_host);
 }
 
 extern "C" int mpvss_modp_group_verify_shares(mpvss_ctx* ctx, const mpvss_modp_group* grp, int space, const uint8_t* pk,
@@ -834,7 +881,7 @@ extern "C" int mpvss_modp_group_verify_shares(mpvss_ctx* ctx, const mpvss_modp_g
     uint8_t* d2 = f.work(ctx->rt_out[2], cnt);
     RET_IF(f.rc);
     // a1 = G^r pk^c, a2 = S^r Y^c (src/participant.rs:361-386 -> src/dleq.rs:275-302)
-    RET_IF(rt_dleq_dev(ctx, grp, f.dc, grp->G_be, dpk, ds, dy, dr, dcc, EB, cnt, d1, d2));
+    RET_IF(rt_dleq_dev(ctx, grp, f.dc, grp->G_be, dpk, ds, nullptr, dy, dr, dcc, EB, cnt, d1, d2));
     f.to_host(d1, cnt, h1);
     f.to_host(d2, cnt, h2);
     const uint8_t* P = f.host_view(pk, off, cnt, hpk);
@@ -1061,9 +1108,11 @@ bool rt_zero_mod_q(const mpvss_modp_group* grp, const uint8_t* v) {
 // Y_i = y_i^p_i and a2_i = y_i^w_i through the twin path, a1_i = g^w_i, and the transcript digest.  Outputs in `space`
 // (the host ones optional).  p_values and witnesses are the frame's Secret inputs: zeroed where it staged them, and under
 // f.secrets_dev device arrays of the caller whatever `space` says (group_deal's device-side scalar ring: P(i) never leaves HBM;
-// the caller began the frame, launched into its spans already and wipes the two arrays itself).
+// the caller began the frame, launched into its spans already and wipes the two arrays itself).  The keys are the array
+// `pubkeys`, or (pubkeys null) key_rows, the rows of a key set from the first share's key on: then both powers of a key are the two
+// exponent sets of one k_rt_keyset_exp launch.
 int rt_distribute_locked(RtCall& f, const uint8_t* commitments, size_t t, const int64_t* positions, const uint8_t* pubkeys,
-                         const uint8_t* p_values, const uint8_t* witnesses, size_t n, uint8_t* x_out, uint8_t* y_out, uint8_t* a1_out,
+                         const uint32_t* key_rows, const uint8_t* p_values, const uint8_t* witnesses, size_t n, uint8_t* x_out, uint8_t* y_out, uint8_t* a1_out,
                          uint8_t* a2_out, uint8_t* digest32_out) {
   mpvss_ctx* const ctx = f.ctx;
   const mpvss_modp_group* const grp = f.grp;
@@ -1073,7 +1122,7 @@ int rt_distribute_locked(RtCall& f, const uint8_t* commitments, size_t t, const 
     RET_IF(f.begin());
     if (commitments) RET_IF(rt_stage_commitments(f, commitments, t, n));
     RET_IF(f.for_chunks(n, [&](size_t off, size_t cnt) {
-      const uint8_t* dy = f.in(pubkeys, off, cnt, ctx->rt_in[1], RtCall::Public);
+      const uint8_t* dy = pubkeys ? f.in(pubkeys, off, cnt, ctx->rt_in[1], RtCall::Public) : nullptr;
       const uint8_t* dp = f.in(p_values, off, cnt, ctx->rt_in[2], RtCall::Secret);
       const uint8_t* dw = f.in(witnesses, off, cnt, ctx->rt_in[3], RtCall::Secret);
       uint8_t* dX = f.out(x_out, off, cnt, ctx->rt_out[0]);
@@ -1090,7 +1139,12 @@ int rt_distribute_locked(RtCall& f, const uint8_t* commitments, size_t t, const 
       }
       RET_IF(rt_fixed_base_dev(ctx, grp, f.dc, grp->g_be, dw, cnt, d1, 1));                           // a1_i = g^w_i, dleq.rs:207-211
       // Y_i = y_i^P(i) (participant.rs:219), a2_i = y_i^w_i (dleq.rs:213-216): one base, two exponents
-      RET_IF(rt_twin_dev(f, dy, dp, dw, cnt, dY, d2));
+      if (pubkeys) {
+        RET_IF(rt_twin_dev(f, dy, dp, dw, cnt, dY, d2));
+      } else {
+        TIMED_LAUNCH(ctx, 3, modp_rt_launch_keyset_exp(grp->lpl, key_rows + off * rt_keyset_stride(grp), nullptr, 0, dp, dw, nullptr, 0,
+                                                       (int)cnt, dY, d2, f.dc, ctx->stream));
+      }
       f.to_host(dX, cnt, hv[0]);
       f.to_host(dY, cnt, hv[1]);
       f.to_host(d1, cnt, hv[2]);
@@ -1239,7 +1293,7 @@ extern "C" int mpvss_modp_group_distribute(mpvss_ctx* ctx, const mpvss_modp_grou
     return fail(ctx, MPVSS_E_INVALID, "group_distribute: bad argument");
   if (t > n) return fail(ctx, MPVSS_E_INVALID, "group_distribute: threshold > number of public keys (participant.rs:166)");
   RtCall f(ctx, grp, space);
-  return rt_distribute_locked(f, commitments, t, positions, pubkeys, p_values, witnesses, n, x_out, y_out, a1_out, a2_out, digest32_out);
+  return rt_distribute_locked(f, commitments, t, positions, pubkeys, nullptr, p_values, witnesses, n, x_out, y_out, a1_out, a2_out, digest32_out);
 }
 
 namespace {
@@ -1250,7 +1304,7 @@ namespace {
 // it) the call holds 3 n EB bytes of HBM beside the chunk workspaces: 48 MiB for 65 536 shares of 256 bytes, 72 MiB of 384.  P
 // and w join the frame's wipe, as do the staged coefficient limbs.  Same bytes as the host path.
 int rt_deal_scalar_dev(mpvss_ctx* ctx, const mpvss_modp_group* grp, const uint8_t* coeffs_host, size_t t, const int64_t* positions_host,
-                       const uint8_t* pubkeys_host, const uint8_t* witnesses_host, size_t n, uint8_t* x_out, uint8_t* y_out,
+                       const uint8_t* pubkeys_host, const uint32_t* key_rows, const uint8_t* witnesses_host, size_t n, uint8_t* x_out, uint8_t* y_out,
                        uint8_t* a1_out, uint8_t* a2_out, uint8_t* digest32_out, uint8_t* challenge_out256, uint8_t* r_out) {
   const size_t EB = grp->eb;
   RtCall f(ctx, grp, MPVSS_HOST);
@@ -1268,7 +1322,7 @@ int rt_deal_scalar_dev(mpvss_ctx* ctx, const mpvss_modp_group* grp, const uint8_
   TIMED_LAUNCH(ctx, 4, modp_rt_launch_modq_poly_eval(grp->lpl, coef, (int)t, (const int64_t*)dpos, (int)n, par_even, par_odd, dP, f.dcq,
                                                      ctx->stream));                                      // participant.rs:202
   uint8_t digest[32], challenge[RT_EB_MAX];
-  RET_IF(rt_distribute_locked(f, nullptr, t, positions_host, pubkeys_host, dP, dW, n, x_out, y_out, a1_out, a2_out, digest));
+  RET_IF(rt_distribute_locked(f, nullptr, t, positions_host, pubkeys_host, key_rows, dP, dW, n, x_out, y_out, a1_out, a2_out, digest));
   rt_hash_to_scalar(grp, digest, 32, challenge);                 // participant.rs:251-252
   if (digest32_out) memcpy(digest32_out, digest, 32);
   if (challenge_out256) memcpy(challenge_out256, challenge, EB);
@@ -1285,23 +1339,17 @@ int rt_deal_scalar_dev(mpvss_ctx* ctx, const mpvss_modp_group* grp, const uint8_
 
 // participant.rs:160-286 after "draw the polynomial and the witnesses": P(i) mod (q-1), the group side above with X_i = g^P(i), the
 // challenge and the responses r_i = w_i - P(i) c.  The scalar ring runs on the device (rt_deal_scalar_dev) when
-// mpvss_ctx_set_rt_scalar and the handle allow it, otherwise on host threads.
-extern "C" int mpvss_modp_group_deal(mpvss_ctx* ctx, const mpvss_modp_group* grp, const uint8_t* coeffs_host, size_t t,
-                                     const int64_t* positions_host, const uint8_t* pubkeys_host, const uint8_t* witnesses_host, size_t n,
-                                     uint8_t* x_out, uint8_t* y_out, uint8_t* a1_out, uint8_t* a2_out, uint8_t* digest32_out,
-                                     uint8_t* challenge_out256, uint8_t* r_out) {
-  if (!ctx) return MPVSS_E_INVALID;
-  std::lock_guard<std::mutex> lk(ctx->mu);
-  if (rt_bad_group(grp)) return fail(ctx, MPVSS_E_INVALID, "group_deal: no group");
+// mpvss_ctx_set_rt_scalar and the handle allow it, otherwise on host threads.  Arguments checked, context lock held; the keys are
+// pubkeys_host, or (pubkeys_host null) key_rows of a key set.
+namespace {
+int rt_deal_locked(mpvss_ctx* ctx, const mpvss_modp_group* grp, const uint8_t* coeffs_host, size_t t, const int64_t* positions_host,
+                   const uint8_t* pubkeys_host, const uint32_t* key_rows, const uint8_t* witnesses_host, size_t n, uint8_t* x_out,
+                   uint8_t* y_out, uint8_t* a1_out, uint8_t* a2_out, uint8_t* digest32_out, uint8_t* challenge_out256, uint8_t* r_out) {
   const size_t EB = grp->eb;
-  if (n > 0x7fffffff || t > 0x7fffffff ||
-      (n > 0 && (!coeffs_host || !positions_host || !pubkeys_host || !witnesses_host || !y_out || !r_out || t == 0)))
-    return fail(ctx, MPVSS_E_INVALID, "group_deal: bad argument (t >= 1, n < 2^31)");
-  if (t > n) return fail(ctx, MPVSS_E_INVALID, "group_deal: threshold > number of public keys (participant.rs:166)");
   RET_IF(check_positions_host(ctx, positions_host, n));
   if (rt_scalar_on_device(ctx, grp, n))
-    return rt_deal_scalar_dev(ctx, grp, coeffs_host, t, positions_host, pubkeys_host, witnesses_host, n, x_out, y_out, a1_out, a2_out,
-                              digest32_out, challenge_out256, r_out);
+    return rt_deal_scalar_dev(ctx, grp, coeffs_host, t, positions_host, pubkeys_host, key_rows, witnesses_host, n, x_out, y_out, a1_out,
+                              a2_out, digest32_out, challenge_out256, r_out);
   std::vector<uint8_t> P(n * EB);
   RtCall f(ctx, grp, MPVSS_HOST);
   f.wipe.host.push_back(&P);
@@ -1309,14 +1357,30 @@ extern "C" int mpvss_modp_group_deal(mpvss_ctx* ctx, const mpvss_modp_group* grp
   if (n > 0)                                                                                               // participant.rs:202
     rt_rings(grp, [&](const auto& R) { poly_eval_bytes<RT_NW(R)>(R.ord, true, coeffs_host, t, positions_host, n, P.data(), threads); });
   uint8_t digest[32], challenge[RT_EB_MAX];
-  RET_IF(rt_distribute_locked(f, nullptr, t, positions_host, pubkeys_host, P.data(), witnesses_host, n, x_out, y_out, a1_out, a2_out,
-                              digest));
+  RET_IF(rt_distribute_locked(f, nullptr, t, positions_host, pubkeys_host, key_rows, P.data(), witnesses_host, n, x_out, y_out, a1_out,
+                              a2_out, digest));
   rt_hash_to_scalar(grp, digest, 32, challenge);                 // participant.rs:251-252
   if (digest32_out) memcpy(digest32_out, digest, 32);
   if (challenge_out256) memcpy(challenge_out256, challenge, EB);
   if (n > 0)                                                                                               // :255-264
     rt_rings(grp, [&](const auto& R) { responses_bytes<RT_NW(R)>(R.ord, true, witnesses_host, P.data(), challenge, 0, n, r_out, threads); });
   return MPVSS_OK;
+}
+}  // namespace
+
+extern "C" int mpvss_modp_group_deal(mpvss_ctx* ctx, const mpvss_modp_group* grp, const uint8_t* coeffs_host, size_t t,
+                                     const int64_t* positions_host, const uint8_t* pubkeys_host, const uint8_t* witnesses_host, size_t n,
+                                     uint8_t* x_out, uint8_t* y_out, uint8_t* a1_out, uint8_t* a2_out, uint8_t* digest32_out,
+                                     uint8_t* challenge_out256, uint8_t* r_out) {
+  if (!ctx) return MPVSS_E_INVALID;
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  if (rt_bad_group(grp)) return fail(ctx, MPVSS_E_INVALID, "group_deal: no group");
+  if (n > 0x7fffffff || t > 0x7fffffff ||
+      (n > 0 && (!coeffs_host || !positions_host || !pubkeys_host || !witnesses_host || !y_out || !r_out || t == 0)))
+    return fail(ctx, MPVSS_E_INVALID, "group_deal: bad argument (t >= 1, n < 2^31)");
+  if (t > n) return fail(ctx, MPVSS_E_INVALID, "group_deal: threshold > number of public keys (participant.rs:166)");
+  return rt_deal_locked(ctx, grp, coeffs_host, t, positions_host, pubkeys_host, nullptr, witnesses_host, n, x_out, y_out, a1_out, a2_out,
+                        digest32_out, challenge_out256, r_out);
 }
 
 // participant.rs:294-353 for n participants: S_i = Y_i^(1/x_i), a1_i = G^w_i, a2_i = S_i^w_i = Y_i^(w_i / x_i) -- S and a2 share
@@ -1561,4 +1625,164 @@ extern "C" int mpvss_modp_group_batch_scalar_mul(mpvss_ctx* ctx, const mpvss_mod
     return 0;
   }));
   return f.end();
+}
+
+// =====================================================================================================================
+// Key sets of a run-time group (DESIGN section 13, "Key sets"): the rows of long-lived public keys, built once, and the calls
+// that raise those keys to full-width powers over them -- a2_i = y_i^r_i Y_i^c of the verifier, Y_i = y_i^P(i) and a2_i = y_i^w_i
+// of the dealer.  A set is explicit: the caller built it and names it, so nothing here decides by a threshold.
+// =====================================================================================================================
+extern "C" size_t mpvss_modp_group_keyset_bytes_per_key(const mpvss_modp_group* grp) {
+  return rt_bad_group(grp) ? 0 : modp_rt_keyset_bytes(grp->lpl, 1);
+}
+
+extern "C" size_t mpvss_modp_group_keyset_bytes(const mpvss_modp_group_keyset* ks) {
+  return ks ? modp_rt_keyset_bytes(ks->lpl, ks->n) : 0;
+}
+
+extern "C" int mpvss_modp_group_keyset_create(mpvss_ctx* ctx, const mpvss_modp_group* grp, int space, const uint8_t* pubkeys, size_t n,
+                                              mpvss_modp_group_keyset** out) {
+  if (out) *out = nullptr;
+  if (!ctx) return MPVSS_E_INVALID;
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  if (rt_bad_group(grp)) return fail(ctx, MPVSS_E_INVALID, "group_keyset_create: no group");
+  if (!out || !pubkeys || n == 0 || n > 0x7fffffff) return fail(ctx, MPVSS_E_INVALID, "group_keyset_create: bad argument (n >= 1)");
+  mpvss_modp_group_keyset* ks = new (std::nothrow) mpvss_modp_group_keyset();
+  if (!ks) return fail(ctx, MPVSS_E_NOMEM, "group_keyset_create: no memory for the handle");
+  ks->ctx = ctx;
+  memcpy(ks->q_be, grp->q_be, sizeof(ks->q_be));
+  ks->eb = grp->eb;
+  ks->lpl = grp->lpl;
+  ks->n = n;
+  const int rc = [&]() -> int {
+    RtCall f(ctx, grp, space);
+    RET_IF(f.begin());
+    const hipError_t e = hipMalloc((void**)&ks->rows, modp_rt_keyset_bytes(grp->lpl, n));
+    if (e != hipSuccess) {
+      (void)hipGetLastError();       // the runtime's last-error slot is sticky: the next launcher must not see this
+      ks->rows = nullptr;
+      return fail(ctx, MPVSS_E_NOMEM, "group_keyset_create: hipMalloc(rows)", e);
+    }
+    // a chunk's launch works on at most 2^20 keys, so that keys x rows fits the launcher's int
+    const size_t step = std::min(MAX_CHUNK, (size_t)1 << 20), stride = rt_keyset_stride(grp);
+    for (size_t off = 0; off < n; off += step) {
+      const size_t cnt = std::min(n - off, step);
+      const uint8_t* dk = f.in(pubkeys, off, cnt, ctx->rt_in[1], RtCall::Public);
+      RET_IF(f.rc);
+      TIMED_LAUNCH(ctx, 2, modp_rt_launch_keyset_build(grp->lpl, dk, (int)cnt, ks->rows + off * stride, f.dc, ctx->stream));
+      RET_IF(f.settle());            // the staging buffer is reused by the next chunk
+    }
+    return f.end();
+  }();
+  if (rc != MPVSS_OK) {
+    if (ks->rows) {
+      (void)hipStreamSynchronize(ctx->stream);
+      (void)hipFree(ks->rows);
+    }
+    delete ks;
+    return rc;
+  }
+  *out = ks;
+  return MPVSS_OK;
+}
+
+// The run-time calls are synchronous: once the last call that named the set has returned, nothing reads its rows.
+extern "C" void mpvss_modp_group_keyset_destroy(mpvss_ctx* ctx, mpvss_modp_group_keyset* ks) {
+  if (!ks) return;
+  mpvss_ctx* const owner = ks->ctx;          // the set is freed on its own context's device whichever context is named
+  (void)ctx;
+  std::lock_guard<std::mutex> lk(owner->mu);
+  if (ks->rows && hipSetDevice(owner->device) == hipSuccess) {
+    (void)hipStreamSynchronize(owner->stream);
+    (void)hipFree(ks->rows);
+  }
+  delete ks;
+}
+
+extern "C" int mpvss_modp_group_keyset_dual_exp(mpvss_ctx* ctx, const mpvss_modp_group* grp, int space,
+                                                const mpvss_modp_group_keyset* keyset, size_t key_offset, const uint8_t* e1,
+                                                const uint8_t* h2, const uint8_t* e2, int e2_per_share, size_t n, uint8_t* out) {
+  if (!ctx) return MPVSS_E_INVALID;
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  if (rt_bad_group(grp)) return fail(ctx, MPVSS_E_INVALID, "group_keyset_dual_exp: no group");
+  const uint32_t* rows;
+  RET_IF(rt_keyset_rows(ctx, grp, keyset, key_offset, n, &rows));
+  if (n == 0) return MPVSS_OK;
+  if (!e1 || !out || (h2 && !e2) || n > 0x7fffffff) return fail(ctx, MPVSS_E_INVALID, "group_keyset_dual_exp: bad argument");
+  RtCall f(ctx, grp, space);
+  RET_IF(f.begin());
+  const uint8_t* dshared = nullptr;
+  if (h2 && !e2_per_share) RET_IF(rt_stage_small(ctx, grp, e2, ctx->rt_small[1], &dshared));   // host bytes, as group_dleq_commitments' c
+  RET_IF(f.for_chunks(n, [&](size_t off, size_t cnt) {
+    const uint8_t* d1 = f.in(e1, off, cnt, ctx->rt_in[3], RtCall::Public);
+    const uint8_t* dh = h2 ? f.in(h2, off, cnt, ctx->rt_in[2], RtCall::Public) : nullptr;
+    const uint8_t* d2 = (h2 && e2_per_share) ? f.in(e2, off, cnt, ctx->rt_in[5], RtCall::Public) : dshared;
+    uint8_t* dout = f.out(out, off, cnt, ctx->rt_out[0]);
+    RET_IF(f.rc);
+    const uint32_t* t2 = nullptr;
+    if (h2) RET_IF(rt_tables(ctx, grp, f.dc, dh, f.EB, cnt, ctx->rt_tab2, &t2));
+    TIMED_LAUNCH(ctx, 3, modp_rt_launch_keyset_exp(grp->lpl, rows + off * rt_keyset_stride(grp), t2, 16 * rt_L(grp), d1, nullptr, d2,
+                                                   e2_per_share ? f.EB : 0, (int)cnt, dout, nullptr, f.dc, ctx->stream));
+    return 0;
+  }));
+  return f.end();
+}
+
+extern "C" int mpvss_modp_group_keyset_twin_exp(mpvss_ctx* ctx, const mpvss_modp_group* grp, int space,
+                                                const mpvss_modp_group_keyset* keyset, size_t key_offset, const uint8_t* e1,
+                                                const uint8_t* e2, size_t n, uint8_t* out1, uint8_t* out2) {
+  if (!ctx) return MPVSS_E_INVALID;
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  if (rt_bad_group(grp)) return fail(ctx, MPVSS_E_INVALID, "group_keyset_twin_exp: no group");
+  const uint32_t* rows;
+  RET_IF(rt_keyset_rows(ctx, grp, keyset, key_offset, n, &rows));
+  if (n == 0) return MPVSS_OK;
+  if (!e1 || !e2 || !out1 || !out2 || n > 0x7fffffff) return fail(ctx, MPVSS_E_INVALID, "group_keyset_twin_exp: bad argument");
+  RtCall f(ctx, grp, space);
+  RET_IF(f.begin());
+  RET_IF(f.for_chunks(n, [&](size_t off, size_t cnt) {
+    const uint8_t* d1 = f.in(e1, off, cnt, ctx->rt_in[2], RtCall::Secret);      // the dealer's P(i) and w_i, as group_batch_twin_exp's
+    const uint8_t* d2 = f.in(e2, off, cnt, ctx->rt_in[3], RtCall::Secret);
+    uint8_t* o1 = f.out(out1, off, cnt, ctx->rt_out[0]);
+    uint8_t* o2 = f.out(out2, off, cnt, ctx->rt_out[1]);
+    RET_IF(f.rc);
+    TIMED_LAUNCH(ctx, 3, modp_rt_launch_keyset_exp(grp->lpl, rows + off * rt_keyset_stride(grp), nullptr, 0, d1, d2, nullptr, 0, (int)cnt,
+                                                   o1, o2, f.dc, ctx->stream));
+    return 0;
+  }));
+  return f.end();
+}
+
+extern "C" int mpvss_modp_group_verify_distribution_keyset(mpvss_ctx* ctx, const mpvss_modp_group* grp, int space,
+                                                           const uint8_t* commitments, size_t t, const int64_t* positions,
+                                                           const mpvss_modp_group_keyset* keyset, size_t key_offset,
+                                                           const uint8_t* shares, const uint8_t* responses, size_t n,
+                                                           const uint8_t* challenge_host, int* verdict, uint8_t* digest32_out,
+                                                           uint8_t* x_out_host, uint8_t* a1_out_host, uint8_t* a2_out_host) {
+  if (!ctx) return MPVSS_E_INVALID;
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  if (rt_bad_group(grp)) return fail(ctx, MPVSS_E_INVALID, "group_verify_distribution_keyset: no group");
+  if (!verdict || !challenge_host || n > 0x7fffffff || t > 0x7fffffff ||
+      (n > 0 && (!commitments || !positions || !shares || !responses || t == 0)))
+    return fail(ctx, MPVSS_E_INVALID, "group_verify_distribution_keyset: bad argument");
+  const uint32_t* rows;
+  RET_IF(rt_keyset_rows(ctx, grp, keyset, key_offset, n, &rows));
+  return rt_verify_distribution_locked(ctx, grp, space, commitments, t, positions, nullptr, rows, shares, responses, n, challenge_host,
+                                       verdict, digest32_out, x_out_host, a1_out_host, a2_out_host);
+}
+
+extern "C" int mpvss_modp_group_deal_keyset(mpvss_ctx* ctx, const mpvss_modp_group* grp, const uint8_t* coeffs_host, size_t t,
+                                            const int64_t* positions_host, const mpvss_modp_group_keyset* keyset, size_t key_offset,
+                                            const uint8_t* witnesses_host, size_t n, uint8_t* x_out, uint8_t* y_out, uint8_t* a1_out,
+                                            uint8_t* a2_out, uint8_t* digest32_out, uint8_t* challenge_out256, uint8_t* r_out) {
+  if (!ctx) return MPVSS_E_INVALID;
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  if (rt_bad_group(grp)) return fail(ctx, MPVSS_E_INVALID, "group_deal_keyset: no group");
+  if (n > 0x7fffffff || t > 0x7fffffff || (n > 0 && (!coeffs_host || !positions_host || !witnesses_host || !y_out || !r_out || t == 0)))
+    return fail(ctx, MPVSS_E_INVALID, "group_deal_keyset: bad argument (t >= 1, n < 2^31)");
+  if (t > n) return fail(ctx, MPVSS_E_INVALID, "group_deal_keyset: threshold > number of public keys (participant.rs:166)");
+  const uint32_t* rows;
+  RET_IF(rt_keyset_rows(ctx, grp, keyset, key_offset, n, &rows));
+  return rt_deal_locked(ctx, grp, coeffs_host, t, positions_host, nullptr, rows, witnesses_host, n, x_out, y_out, a1_out, a2_out,
+                        digest32_out, challenge_out256, r_out);
 }

@@ -43,6 +43,8 @@ int modp_rt_elem_bytes(int lpl);
 int modp_rt_in_rows(int lpl);
 size_t modp_rt_comb_bytes(int lpl);
 size_t modp_rt_twin_scratch_bytes(int lpl, int count);
+/* bytes of the rows of `count` keys of a key set: EB / 32 rows of 16 numbers each (0 for no width) */
+size_t modp_rt_keyset_bytes(int lpl, size_t count);
 #define MODP_RT_FN(name) modp_rt_##name
 #include "modp_rt_launchers.h"
 #undef MODP_RT_FN

@@ -36,6 +36,11 @@ extern "C" size_t modp_rt_twin_scratch_bytes(int lpl, int count) {
   return (size_t)rt_grid(count) * RT_NUMS * 2 * RT_TWIN_BUCKETS * 4 * lpl * sizeof(uint32_t);
 }
 
+extern "C" size_t modp_rt_keyset_bytes(int lpl, size_t count) {
+  if (lpl != 5 && lpl != 9 && lpl != 18 && lpl != 27) return 0;
+  return count * (size_t)(lpl == 27 ? Width<27>::KS_ROWS : Width<18>::KS_ROWS) * 16 * 4 * lpl * sizeof(uint32_t);
+}
+
 extern "C" int modp_rt_fd_max_t(int lpl) { return (lpl == 5 || lpl == 9 || lpl == 18 || lpl == 27) ? MODP_RT_FD_MAX_T(lpl) : -1; }
 
 extern "C" size_t modp_rt_fd_park_bytes(int lpl, int t, int S) { return (size_t)S * 2 * (16 * ((t + 15) / 16)) * 4 * lpl * sizeof(uint32_t); }

@@ -10,6 +10,7 @@
 //   X_i = prod_j C_j^(i^j mod (q-1))             (src/participant.rs:423-434)      k_rt_commit_eval
 //   P(i), r_i = w_i - P(i) c, w_i / x_i in Z/(q-1) (src/polynomial.rs:50-58, src/dleq.rs:42-50, modp.rs:180-182)
 //                                                                                  k_rt_modq_poly_eval, _responses, _mul
+//   y_i^r_i Y_i^c, y_i^P(i), y_i^w_i for long-lived keys    (src/participant.rs:436-447, :219)  k_rt_keyset_bases, _rows, _exp
 //
 // Layout and program shape are those of the group-14 kernels (modp_kernels.hip): one number per DPP quad, 16 numbers
 // per one-wave workgroup, the second operand of every product staged in LDS, 16-entry window tables in HBM.  The
@@ -389,6 +390,160 @@ __global__ void RT_KERNEL(LPL) k_rt_exp_sets(const u32* __restrict__ tab, size_t
   __shared__ __attribute__((aligned(16))) u32 lds[RT_NUMS * Width<LPL>::SLOT];
   const bool second = blockIdx.y != 0;
   rt_dual_exp_body<LPL>(lds, tab, tab_stride, nullptr, 0, second ? e2_be : e1_be, Width<LPL>::EB, nullptr, 0, count, second ? out2_be : out1_be, cs);
+}
+
+// ---------------------------------------------------------------------------------------
+// Key sets: per-key row tables for full-width powers of long-lived public keys (the counterpart of group 14's key sets at a
+// run-time width).  ks[key][j][d] = y^(d 2^(256 j)) R mod N, j < J = Width::KS_ROWS = EB / 32 (8 rows, 12 at the wide width),
+// d < 16, entry 0 = R mod N: always J rows, so any EB-byte exponent stays exact, as the comb's 2 EB rows do.
+//   k_rt_keyset_bases (one key per quad): the key enters through to_mont_in like a table base (a key >= q is reduced, one that
+//                     is 0 mod q gives rows of zeros beside entry 0); one chain of 256 (J - 1) squarings, entry 1 of row j
+//                     stored every 256 of them, and entry 0 of every row
+//   k_rt_keyset_rows  (one number per (key, row)): d = 2..15, as k_rt_comb_rows fills the comb's rows
+// 1 + 256 (J - 1) + 14 J operations per key: 1 905 at 256 bytes, 2 985 at 384 (tests/test_modp_rt_keyset_model.py).
+// ---------------------------------------------------------------------------------------
+template <int LPL>
+__global__ void RT_KERNEL(LPL) k_rt_keyset_bases(const uint8_t* __restrict__ keys_be, int count, u32* __restrict__ ks,
+                                                 const modp_rt_consts* __restrict__ cs) {
+  constexpr int L = Width<LPL>::L, SLOT = Width<LPL>::SLOT, J = Width<LPL>::KS_ROWS;
+  __shared__ __attribute__((aligned(16))) u32 lds[RT_NUMS * SLOT];
+  const Lane ln = make_lane();
+  const int xi = blockIdx.x * RT_NUMS + (threadIdx.x >> 2);
+  const bool live = xi < count;
+  const int x = live ? xi : count - 1;
+  u32* slot = lds + (threadIdx.x >> 2) * SLOT;
+  const u32 n0inv = cs->n0inv;
+  u32* my = ks + (size_t)x * J * 16 * L;
+  u32 n[LPL], acc[LPL];
+  load_lane_limbs<LPL>(n, cs->n, ln);
+  load_lane_limbs<LPL>(acc, cs->one_m, ln);
+  if (live) {
+#pragma nounroll
+    for (int j = 0; j < J; ++j) store_lane_limbs<LPL>(my + (size_t)j * 16 * L, acc, ln);
+  }
+  to_mont_in<LPL>(acc, slot, keys_be + (size_t)x * Width<LPL>::EB, cs, n, n0inv, ln);
+#pragma nounroll
+  for (int op = 0; op <= (J - 1) * 256; ++op) {
+    if (live && (op & 255) == 0) store_lane_limbs<LPL>(my + ((size_t)(op >> 8) * 16 + 1) * L, acc, ln);
+    if (op == (J - 1) * 256) break;
+    slot_store<LPL>(slot, acc, ln);
+    __builtin_amdgcn_wave_barrier();
+    mont_mul<N0INV_RUNTIME, true>(acc, acc, slot, n, ln, n0inv);
+    __builtin_amdgcn_wave_barrier();
+  }
+}
+
+// k_rt_comb_rows over a run-time number of rows.  A body of its own: k_rt_comb_rows with the count made an argument allocates
+// other registers at 18 limbs per lane (114 instead of 118), and existing instances keep their figures.
+template <int LPL>
+__global__ void RT_KERNEL(LPL) k_rt_keyset_rows(u32* __restrict__ ks, int nrows, const modp_rt_consts* __restrict__ cs) {
+  constexpr int L = Width<LPL>::L, SLOT = Width<LPL>::SLOT;
+  __shared__ __attribute__((aligned(16))) u32 lds[RT_NUMS * SLOT];
+  const Lane ln = make_lane();
+  const int xi = blockIdx.x * RT_NUMS + (threadIdx.x >> 2);
+  const bool live = xi < nrows;
+  const int k = live ? xi : nrows - 1;
+  u32* slot = lds + (threadIdx.x >> 2) * SLOT;
+  const u32 n0inv = cs->n0inv;
+  u32 n[LPL], acc[LPL];
+  load_lane_limbs<LPL>(n, cs->n, ln);
+  u32* row = ks + (size_t)k * 16 * L;
+  load_lane_limbs<LPL>(acc, row + L, ln);
+  slot_store<LPL>(slot, acc, ln);
+  __builtin_amdgcn_wave_barrier();
+#pragma nounroll
+  for (int d = 2; d < 16; ++d) {
+    mont_mul<N0INV_RUNTIME>(acc, acc, slot, n, ln, n0inv);
+    if (live) store_lane_limbs<LPL>(row + (size_t)d * L, acc, ln);
+  }
+}
+
+// ---------------------------------------------------------------------------------------
+// out[x] = y_x^e1[x] (* B2[x]^e2[x] when tab2 is not null) over the rows ks[x] of a key set: Straus over the key's J rows and
+// B2's 16-entry table, 4-bit windows, 63 x 4 squarings for a full-width e1 instead of 2 044.  blockIdx.y selects an exponent set:
+// 0 is (e1a, out_a), 1 is (e1b, out_b) -- the dealer's two powers of one key in one launch (gridDim.y = 2, no tab2), as
+// k_rt_exp_sets does.
+//   W = max(ceil(min(bits(e1), 256) / 4), ceil(bits(e2) / 4)) over the wave.  For w = W-1 .. 0: four squarings (none while the
+//   accumulator is still one); for w < 64 one product per row j by ks[j][nibble(e1, 64 j + w)], rows above the wave's longest e1
+//   left out and a row whose digit is 0 in all 16 numbers of the wave skipped (otherwise a lane with digit 0 multiplies by entry
+//   0); then the product by tab2[nibble(e2, w)] while w is below the wave's longest e2.  Windows of e2 above 64 run before the
+//   rows join, so any EB-byte e2 stays exact.  Then times plain 1.
+// One Montgomery-product site as in rt_dual_exp_body: every step only chooses its LDS operand.  The row index is an exponent
+// digit, so the gather address follows the exponent, as the comb's does; the table is per share, so no gather is shared.
+// Full-width e1 with a 256-bit e2 at 2048 bits: 252 squarings + 512 row products + 64 products by B2 + 1 exit = 829 (844 with
+// B2's table; tests/test_modp_rt_keyset_model.py).
+// ---------------------------------------------------------------------------------------
+template <int LPL>
+__global__ void RT_KERNEL(LPL) k_rt_keyset_exp(const u32* __restrict__ ks, const u32* __restrict__ tab2, size_t tab2_stride,
+                                               const uint8_t* __restrict__ e1a_be, const uint8_t* __restrict__ e1b_be,
+                                               const uint8_t* __restrict__ e2_be, size_t e2_stride, int count,
+                                               uint8_t* __restrict__ out_a, uint8_t* __restrict__ out_b,
+                                               const modp_rt_consts* __restrict__ cs) {
+  constexpr int L = Width<LPL>::L, SLOT = Width<LPL>::SLOT, EB = Width<LPL>::EB, J = Width<LPL>::KS_ROWS;
+  __shared__ __attribute__((aligned(16))) u32 lds[RT_NUMS * SLOT];
+  const Lane ln = make_lane();
+  const int xi = blockIdx.x * RT_NUMS + (threadIdx.x >> 2);
+  const bool live = xi < count;
+  const int x = live ? xi : count - 1;
+  u32* slot = lds + (threadIdx.x >> 2) * SLOT;
+  const u32 n0inv = cs->n0inv;
+  const bool second = blockIdx.y != 0;
+  const bool has2 = tab2 != nullptr;
+  const u32* rows = ks + (size_t)x * J * 16 * L;
+  const uint8_t* e1 = (second ? e1b_be : e1a_be) + (size_t)x * EB;
+  const uint8_t* e2 = has2 ? e2_be + (size_t)x * e2_stride : e1;
+  const u32* t2 = has2 ? tab2 + (size_t)x * tab2_stride : rows;
+  u32 n[LPL], acc[LPL];
+  load_lane_limbs<LPL>(n, cs->n, ln);
+  const int nb1 = wave_max_bits<EB>(e1, ln);
+  const int jl = (nb1 + 255) >> 8;                                     // rows the wave's longest e1 reaches, <= J
+  const int nw2 = has2 ? (wave_max_bits<EB>(e2, ln) + 3) >> 2 : 0;
+  const int nw1 = ((nb1 < 256 ? nb1 : 256) + 3) >> 2;
+  const int nw = nw1 > nw2 ? nw1 : nw2;
+  // steps: 0..3 square, 4 + j times ks[j][d1], 4 + J times tab2[d2], 5 + J next window, 6 + J final (times plain 1)
+  constexpr int S_TAB2 = 4 + J, S_NEXT = 5 + J, S_FINAL = 6 + J;
+  int w = nw - 1, s = nw == 0 ? S_FINAL : 4;
+  bool one = true;                                                     // the accumulator is still R mod N (wave-uniform)
+  load_lane_limbs<LPL>(acc, cs->one_m, ln);
+  while (true) {
+    while (s != S_FINAL) {                                             // the next step that has work
+      if (s == S_NEXT) {
+        if (w == 0) {
+          s = S_FINAL;
+        } else {
+          --w;
+          s = one ? 4 : 0;
+        }
+      } else if (s < 4) {
+        break;
+      } else if (s < S_TAB2) {
+        const int j = s - 4;
+        if (w < 64 && j < jl && __builtin_amdgcn_ballot_w64(nibble<EB>(e1, 64 * j + w) != 0) != 0) break;
+        s = (w < 64 && j + 1 < jl) ? s + 1 : S_TAB2;
+      } else {
+        if (w < nw2) break;
+        s = S_NEXT;
+      }
+    }
+    if (s == S_FINAL) {
+      slot_fill_from_global<LPL>(slot, cs->one, ln);
+    } else if (s < 4) {
+      slot_store<LPL>(slot, acc, ln);
+    } else if (s < S_TAB2) {
+      const int j = s - 4;
+      slot_fill_from_global<LPL>(slot, rows + ((size_t)j * 16 + nibble<EB>(e1, 64 * j + w)) * L, ln);
+    } else {
+      slot_fill_from_global<LPL>(slot, t2 + (size_t)nibble<EB>(e2, w) * L, ln);
+    }
+    __builtin_amdgcn_wave_barrier();
+    if (s < 4) mont_mul<N0INV_RUNTIME, true>(acc, acc, slot, n, ln, n0inv);
+    else mont_mul<N0INV_RUNTIME>(acc, acc, slot, n, ln, n0inv);
+    __builtin_amdgcn_wave_barrier();
+    if (s == S_FINAL) break;
+    if (s >= 4) one = false;
+    ++s;
+  }
+  store_canonical<LPL>((second ? out_b : out_a) + (size_t)x * EB, acc, slot, cs, ln, live);
 }
 
 // ---------------------------------------------------------------------------------------
@@ -995,6 +1150,26 @@ extern "C" int RT_FN(launch_exp_sets)(int lpl, const uint32_t* tab, size_t tab_s
   RT_ELSEWHERE(launch_exp_sets, lpl, tab, tab_stride, e1, e2, count, out1, out2, cs, s);
   if (count <= 0) return 0;
   RT_DISPATCH(lpl, k_rt_exp_sets, dim3(rt_grid(count), 2), dim3(64), 0, s, tab, tab_stride, e1, e2, count, out1, out2, cs);
+  return (int)hipGetLastError();
+}
+
+extern "C" int RT_FN(launch_keyset_build)(int lpl, const uint8_t* keys_be, int count, uint32_t* ks, const modp_rt_consts* cs, hipStream_t s) {
+  RT_ELSEWHERE(launch_keyset_build, lpl, keys_be, count, ks, cs, s);
+  if (count <= 0) return 0;
+  const int nrows = count * (lpl == 27 ? Width<27>::KS_ROWS : Width<18>::KS_ROWS);
+  RT_DISPATCH(lpl, k_rt_keyset_bases, dim3(rt_grid(count)), dim3(64), 0, s, keys_be, count, ks, cs);
+  RT_DISPATCH(lpl, k_rt_keyset_rows, dim3(rt_grid(nrows)), dim3(64), 0, s, ks, nrows, cs);
+  return (int)hipGetLastError();
+}
+
+extern "C" int RT_FN(launch_keyset_exp)(int lpl, const uint32_t* ks, const uint32_t* tab2, size_t tab2_stride, const uint8_t* e1a,
+                                        const uint8_t* e1b, const uint8_t* e2, size_t e2_stride, int count, uint8_t* out_a,
+                                        uint8_t* out_b, const modp_rt_consts* cs, hipStream_t s) {
+  RT_ELSEWHERE(launch_keyset_exp, lpl, ks, tab2, tab2_stride, e1a, e1b, e2, e2_stride, count, out_a, out_b, cs, s);
+  if (count <= 0) return 0;
+  if (e1b && tab2) return (int)hipErrorInvalidValue;       // the second exponent set is for powers of the key alone
+  RT_DISPATCH(lpl, k_rt_keyset_exp, dim3(rt_grid(count), e1b ? 2 : 1), dim3(64), 0, s, ks, tab2, tab2_stride, e1a, e1b, e2, e2_stride,
+              count, out_a, out_b, cs);
   return (int)hipGetLastError();
 }
 

@@ -23,6 +23,15 @@ int MODP_RT_FN(launch_comb_exp)(int lpl, const uint32_t* comb, const uint32_t* t
    (gridDim.y = 2); exponents and results n x EB bytes */
 int MODP_RT_FN(launch_exp_sets)(int lpl, const uint32_t* tab, size_t tab_stride, const uint8_t* e1, const uint8_t* e2, int count,
                             uint8_t* out1, uint8_t* out2, const modp_rt_consts* cs, hipStream_t s);
+/* key set of `count` keys (EB-byte values of any size on the device): ks[key][j][d] = key^(d 2^(256 j)) R mod N, j < EB / 32,
+   d < 16 -- modp_rt_keyset_bytes(lpl, count) bytes; count times EB / 32 must fit an int */
+int MODP_RT_FN(launch_keyset_build)(int lpl, const uint8_t* keys_be, int count, uint32_t* ks, const modp_rt_consts* cs, hipStream_t s);
+/* out_a[x] = key_x^e1a[x] * B2[x]^e2[x] mod q, canonical, over the rows ks[x] of a key set (ks: the rows of the first key) and B2's
+   16-entry table (tab2 == NULL: the power of the key alone; tab2_stride in words, e2_stride in bytes, 0 = one exponent for every
+   x).  e1b != NULL (tab2 must be NULL): out_b[x] = key_x^e1b[x] as well, a second exponent set in the same launch (gridDim.y = 2) */
+int MODP_RT_FN(launch_keyset_exp)(int lpl, const uint32_t* ks, const uint32_t* tab2, size_t tab2_stride, const uint8_t* e1a,
+                              const uint8_t* e1b, const uint8_t* e2, size_t e2_stride, int count, uint8_t* out_a, uint8_t* out_b,
+                              const modp_rt_consts* cs, hipStream_t s);
 /* the same two results right to left with shared squarings (k_rt_twin_exp): bases as EB-byte values of any size, `buckets`
    a scratch of modp_rt_twin_scratch_bytes(lpl, count) bytes that holds exponent windows afterwards (the caller zeroes it) */
 int MODP_RT_FN(launch_twin_exp)(int lpl, const uint8_t* bases, const uint8_t* e1, const uint8_t* e2, int count, uint32_t* buckets,

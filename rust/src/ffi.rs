@@ -30,6 +30,11 @@ pub struct mpvss_keyset {
 pub struct mpvss_modp_group {
     _private: [u8; 0],
 }
+/// the rows of registered public keys of a run-time MODP group (mpvss_modp_group_keyset_create): owned by one context
+#[repr(C)]
+pub struct mpvss_modp_group_keyset {
+    _private: [u8; 0],
+}
 #[repr(C)]
 pub struct mpvss_modp_box {
     pub commitments: *const u8,
@@ -298,6 +303,28 @@ unsafe extern "C" {
                                                   alpha_dev: *const u8, c_host: *const u8, n: usize, r_dev_out: *mut u8) -> c_int;
     pub fn mpvss_modp_group_batch_scalar_mul(ctx: *mut mpvss_ctx, grp: *const mpvss_modp_group, space: c_int, a: *const u8, b: *const u8,
                                              n: usize, out: *mut u8) -> c_int;
+    // ---- key sets of a run-time group
+    pub fn mpvss_modp_group_keyset_bytes_per_key(grp: *const mpvss_modp_group) -> usize;
+    pub fn mpvss_modp_group_keyset_create(ctx: *mut mpvss_ctx, grp: *const mpvss_modp_group, space: c_int, pubkeys: *const u8, n: usize,
+                                          out: *mut *mut mpvss_modp_group_keyset) -> c_int;
+    pub fn mpvss_modp_group_keyset_destroy(ctx: *mut mpvss_ctx, keyset: *mut mpvss_modp_group_keyset);
+    pub fn mpvss_modp_group_keyset_bytes(keyset: *const mpvss_modp_group_keyset) -> usize;
+    pub fn mpvss_modp_group_keyset_dual_exp(ctx: *mut mpvss_ctx, grp: *const mpvss_modp_group, space: c_int,
+                                            keyset: *const mpvss_modp_group_keyset, key_offset: usize, e1: *const u8, h2: *const u8,
+                                            e2: *const u8, e2_per_share: c_int, n: usize, out: *mut u8) -> c_int;
+    pub fn mpvss_modp_group_keyset_twin_exp(ctx: *mut mpvss_ctx, grp: *const mpvss_modp_group, space: c_int,
+                                            keyset: *const mpvss_modp_group_keyset, key_offset: usize, e1: *const u8, e2: *const u8,
+                                            n: usize, out1: *mut u8, out2: *mut u8) -> c_int;
+    pub fn mpvss_modp_group_verify_distribution_keyset(ctx: *mut mpvss_ctx, grp: *const mpvss_modp_group, space: c_int,
+                                                       commitments: *const u8, t: usize, positions: *const i64,
+                                                       keyset: *const mpvss_modp_group_keyset, key_offset: usize, shares: *const u8,
+                                                       responses: *const u8, n: usize, challenge_host: *const u8, verdict: *mut c_int,
+                                                       digest32_out: *mut u8, x_out_host: *mut u8, a1_out_host: *mut u8,
+                                                       a2_out_host: *mut u8) -> c_int;
+    pub fn mpvss_modp_group_deal_keyset(ctx: *mut mpvss_ctx, grp: *const mpvss_modp_group, coeffs_host: *const u8, t: usize,
+                                        positions_host: *const i64, keyset: *const mpvss_modp_group_keyset, key_offset: usize,
+                                        witnesses_host: *const u8, n: usize, x_out: *mut u8, y_out: *mut u8, a1_out: *mut u8,
+                                        a2_out: *mut u8, digest32_out: *mut u8, challenge_out256: *mut u8, r_out: *mut u8) -> c_int;
     // ---- hashing helpers
     pub fn mpvss_sha256(data: *const u8, len: usize, out32: *mut u8);
     pub fn mpvss_modp_hash_to_scalar(data: *const u8, len: usize, out256: *mut u8);

@@ -37,7 +37,7 @@
               library (no gate).  All lines go to profiles/modp_rt_comb_rate.txt.
 
 Host buffers in and out (the calls' own staging included), best of `--reps` after one warm-up call.  One JSON line per
-measurement.  Usage: python tools/modp_rt_rate.py [--quick] [--reps 3] [--legs rates,twin,deal,comb,verify] [--comb | --fd] [--ab PARENT [--rounds 2]]
+measurement.  Usage: python tools/modp_rt_rate.py [--quick] [--reps 3] [--legs rates,twin,deal,comb,verify] [--comb | --fd | --scalar | --keyset] [--ab PARENT [--rounds 2]]
   fd          (--fd) X_i of a run-time group by forward differences: timer 0 of group_commit_eval at (4096, 64), (16384, 128),
               (65536, 256), 1024 and 2048 bits, per chain count, and whole group_verify_distribution calls; --fd --ab PARENT takes
               turns with a built checkout of the parent commit and writes profiles/modp_rt_fd_rate.txt (one 3072-bit row too).
@@ -48,7 +48,17 @@ measurement.  Usage: python tools/modp_rt_rate.py [--quick] [--reps 3] [--legs r
               kernels (timer 4).  --scalar --ab PARENT: fresh processes of a built checkout of the parent commit and of this
               build under mode 2 take turns, best of the rounds, into profiles/modp_rt_scalar_rate.txt; rt_scalar_min_shares of
               a width is the smallest measured n from which mode 2's whole call is no slower than the parent's at every larger
-              measured n (1 if that holds everywhere).  No speed gate."""
+              measured n (1 if that holds everywhere).  No speed gate.
+  keyset      (--keyset) key sets of a run-time group, kernels alone, at n = 4096, 16384, 65536 for 1024 and 2048 bits (--keyset-wide:
+              the one 3072-bit row, n = 16384); exponents as long as q, c of 256 bits.  --keyset-parts parent: what a caller has
+              without a set -- the a2 launch of group_dleq_commitments (timer 3) and the twin launch inside group_deal (t = 1,
+              timer 3); keyset: the build (timer 2) and its bytes, the launch of group_keyset_dual_exp with h2 and a shared c, and of
+              group_keyset_twin_exp (timer 3).  At (65536, 256) both parts also time whole group_verify_distribution and group_deal
+              calls (the key-set forms in the keyset part; the build is not in them).
+  --keyset --ab PARENT  fresh processes of a built checkout of the parent commit and of this build take turns, best of the rounds,
+              into profiles/modp_rt_keyset_rate.txt.  The gate, at n = 65536 and 2048 bits: the key-set a2 launch against the
+              parent's a2 launch, at least 2x required (the operation counts say 3.65x); below 1x the kernels do not ship.  The
+              twin ratio is recorded and not gated."""
 import argparse
 import json
 import os
@@ -431,6 +441,103 @@ def ab_scalar(a):
             f.write(json.dumps(row) + "\n")
 
 
+KEYSET_SIZES = [4096, 16384, 65536]
+
+
+def keyset_leg(eng, a, rng):
+    parts = a.keyset_parts.split(",")
+    sizes = [4096] if a.quick else KEYSET_SIZES
+    groups = [(1024, ModpGroup(H.rfc_prime(1024))), (2048, ModpGroup(H.rfc_prime(2048)))]
+    if a.keyset_wide:
+        import modp_rt_wide_helpers as WH
+        groups, sizes = [(3072, ModpGroup(WH.group15(), elem_bytes=WH.EB))], [4096 if a.quick else 16384]
+    for bits, grp in groups:
+        EB = grp.elem_bytes
+
+        def rb(n, nbits):
+            return b"".join(rng.getrandbits(nbits).to_bytes(EB, "big") for _ in range(n))
+
+        def timer(fn, k):
+            ts = []
+            for _ in range(a.reps + 1):
+                fn()
+                ts.append(round(max(0.0, eng.kernel_ms(k)), 3))
+            return min(ts[1:])
+
+        for n in sizes:
+            y, Y, r, w = rb(n, bits - 1), rb(n, bits - 1), rb(n, bits - 1), rb(n, bits - 1)
+            c, g1 = rb(1, 256), (4).to_bytes(EB, "big")
+            pos, coef = list(range(1, n + 1)), rb(1, bits - 2)
+            whole = n == 65536 and not a.keyset_wide
+            t = 256
+            cm = b"".join((rng.getrandbits(bits - 2) | 1).to_bytes(EB, "big") for _ in range(t)) if whole else None
+            coefs = rb(t, bits - 2) if whole else None
+            row = {"what": "keyset", "bits": bits, "n": n}
+            if "parent" in parts:
+                row["parent_a2_kernel_ms"] = timer(lambda: eng.group_dleq_commitments(grp, g1, Y, y, Y, r, c, False), 3)
+                row["parent_twin_kernel_ms"] = timer(lambda: eng.group_deal(grp, coef, pos, y, w), 3)
+                if whole:
+                    row["verify_s"] = round(best(lambda: eng.group_verify_distribution(grp, cm, pos, y, Y, r, c), a.reps), 4)
+                    row["deal_s"] = round(best(lambda: eng.group_deal(grp, coefs, pos, y, w), a.reps), 4)
+            if "keyset" in parts:
+                builds = []
+                for _ in range(2):
+                    ks = eng.group_keyset_create(grp, y)
+                    builds.append(round(max(0.0, eng.kernel_ms(2)), 3))
+                    if len(builds) < 2:
+                        ks.close()
+                row.update(keyset_build_kernel_ms=min(builds), keyset_bytes=ks.nbytes)
+                row["keyset_a2_kernel_ms"] = timer(lambda: eng.group_keyset_dual_exp(grp, ks, 0, r, Y, c, False), 3)
+                row["keyset_twin_kernel_ms"] = timer(lambda: eng.group_keyset_twin_exp(grp, ks, 0, r, w), 3)
+                if whole:
+                    row["verify_s"] = round(best(lambda: eng.group_verify_distribution_keyset(grp, cm, pos, ks, 0, Y, r, c), a.reps), 4)
+                    row["deal_s"] = round(best(lambda: eng.group_deal_keyset(grp, coefs, pos, ks, 0, w), a.reps), 4)
+                ks.close()
+            print(json.dumps(row), flush=True)
+
+
+def ab_keyset(a):
+    """--keyset --ab PARENT: fresh processes of the parent build and of this build take turns; best of the rounds"""
+    if not os.path.exists(os.path.join(a.ab, "mpvss_rs_amd", "libmpvss_hip.so")):
+        sys.exit("modp_rt_rate --keyset --ab: the parent checkout is not built")
+    common = ["--legs", "keyset", "--reps", str(a.reps)] + (["--quick"] if a.quick else [])
+    lines, ms = [], {}
+    for wide in ([], ["--keyset-wide"]):
+        for rnd in range(a.rounds):
+            for part, extra in (("parent", ["--package-root", a.ab]), ("keyset", [])):
+                for row in child(common + wide + ["--keyset-parts", part] + extra, None, [], a.deal_limit):
+                    row.update(part=part, round=rnd)
+                    for k, v in row.items():
+                        if k.endswith("_kernel_ms") or k.endswith("_s") or k == "keyset_bytes":
+                            key = (part + ":" + k, row["bits"], row["n"])
+                            ms[key] = min(ms.get(key, v), v)
+                    lines.append(row)
+    for bits in sorted({k[1] for k in ms}):
+        for n in sorted({k[2] for k in ms if k[1] == bits}):
+            pa2, ka2 = ms["parent:parent_a2_kernel_ms", bits, n], ms["keyset:keyset_a2_kernel_ms", bits, n]
+            ptw, ktw = ms["parent:parent_twin_kernel_ms", bits, n], ms["keyset:keyset_twin_kernel_ms", bits, n]
+            row = {"what": "keyset_ab", "bits": bits, "n": n, "parent_a2_kernel_ms": pa2, "keyset_a2_kernel_ms": ka2,
+                   "a2_parent_over_keyset": round(pa2 / ka2, 3), "parent_twin_kernel_ms": ptw, "keyset_twin_kernel_ms": ktw,
+                   "twin_parent_over_keyset": round(ptw / ktw, 3),
+                   "keyset_build_kernel_ms": ms["keyset:keyset_build_kernel_ms", bits, n], "keyset_bytes": ms["keyset:keyset_bytes", bits, n]}
+            if ("parent:verify_s", bits, n) in ms:
+                row.update(t=256, parent_verify_s=ms["parent:verify_s", bits, n], keyset_verify_s=ms["keyset:verify_s", bits, n],
+                           parent_deal_s=ms["parent:deal_s", bits, n], keyset_deal_s=ms["keyset:deal_s", bits, n])
+            lines.append(row)
+            if (bits, n) == (2048, 65536):
+                ratio = pa2 / ka2
+                lines.append({"what": "keyset_gate", "bits": bits, "n": n, "a2_parent_over_keyset": round(ratio, 3), "counts_say": 3.65,
+                              "required": 2.0, "met": ratio >= 2.0, "ships": ratio >= 1.0,
+                              "twin_parent_over_keyset_not_gated": round(ptw / ktw, 3)})
+    for row in lines:
+        if row["what"].startswith("keyset_"):
+            print(json.dumps(row), flush=True)
+    os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+    with open(a.out, "w") as f:
+        for row in lines:
+            f.write(json.dumps(row) + "\n")
+
+
 def ab_fd(a):
     """--fd --ab PARENT: fresh processes of the parent build (Horner's rule) and of this build (mode 2 per chain count) take turns;
     best of the rounds.  rt_fd_chains is the best chain count per shape, rt_fd_min_shares the smallest measured n from which
@@ -491,6 +598,9 @@ def main():
     ap.add_argument("--scalar", action="store_true", help="the scalar ring on the device: alone, the scalar leg; with --ab, its interleaved A/B")
     ap.add_argument("--scalar-parts", default="mode2", help="of the scalar leg: parent (the library under test as it is), mode2 (set_rt_scalar(2))")
     ap.add_argument("--scalar-wide", action="store_true", help="of the scalar leg: the one 3072-bit row, group_deal at (4096, 64)")
+    ap.add_argument("--keyset", action="store_true", help="key sets of a run-time group: alone, the keyset leg; with --ab, its interleaved A/B")
+    ap.add_argument("--keyset-parts", default="keyset", help="of the keyset leg: parent (the launches without a set), keyset (build and launches over a set)")
+    ap.add_argument("--keyset-wide", action="store_true", help="of the keyset leg: the one 3072-bit row, n = 16384")
     ap.add_argument("--package-root", default=None, help="import mpvss_rs_amd (bindings and library) from this checkout")
     ap.add_argument("--ab", default=None, metavar="PARENT", help="the interleaved A/B against a built checkout of the parent commit")
     ap.add_argument("--rounds", type=int, default=2, help="of --ab: how often the three processes take turns")
@@ -499,15 +609,17 @@ def main():
     ap.add_argument("--out", default=None, help="of --ab: the file written (profiles/modp_rt_deal_rate.txt, or _comb_rate.txt)")
     a = ap.parse_args()
     if a.out is None:
-        a.out = os.path.join(ROOT, "profiles", "modp_rt_scalar_rate.txt" if a.scalar else "modp_rt_fd_rate.txt" if a.fd else "modp_rt_comb_rate.txt" if a.comb else "modp_rt_deal_rate.txt")
+        a.out = os.path.join(ROOT, "profiles", "modp_rt_keyset_rate.txt" if a.keyset else "modp_rt_scalar_rate.txt" if a.scalar else "modp_rt_fd_rate.txt" if a.fd else "modp_rt_comb_rate.txt" if a.comb else "modp_rt_deal_rate.txt")
     if a.ab:
-        return ab_scalar(a) if a.scalar else ab_fd(a) if a.fd else ab_comb(a) if a.comb else ab(a)
+        return ab_keyset(a) if a.keyset else ab_scalar(a) if a.scalar else ab_fd(a) if a.fd else ab_comb(a) if a.comb else ab(a)
     if a.comb:
         a.legs = "comb"
     if a.fd:
         a.legs = "fd"
     if a.scalar:
         a.legs = "scalar"
+    if a.keyset:
+        a.legs = "keyset"
     load_package(a.package_root)
     eng = Engine(0)
     rng = random.Random(1)
@@ -524,6 +636,8 @@ def main():
         fd_leg(eng, a, rng)
     if "scalar" in legs:
         scalar_leg(eng, a, rng)
+    if "keyset" in legs:
+        keyset_leg(eng, a, rng)
     if "rates" not in legs:
         eng.close()
         return
