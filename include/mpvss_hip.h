@@ -641,8 +641,10 @@ int mpvss_modp_group_deal(mpvss_ctx* ctx, const mpvss_modp_group* grp, const uin
 int mpvss_modp_group_extract_shares(mpvss_ctx* ctx, const mpvss_modp_group* grp, int space, const uint8_t* pk, const uint8_t* y,
                                     const uint8_t* xinv, const uint8_t* w, size_t n, uint8_t* s_out, uint8_t* c_out_host);
 /* G^s and the mask from m shares, src/participant.rs:462-561: same contract as mpvss_modp_reconstruct (positions >= 1 and pairwise
- * different; a Lagrange denominator without inverse mod (q-1)/2, an even (q-1)/2, or a share that is 0 mod q where its factor
- * has to be inverted gives MPVSS_E_INVALID).  mask_out32 = int_BE(SHA256(minimal bytes(G^s))) mod q, 32 bytes big-endian. */
+ * different; a Lagrange coefficient whose denominator, with the fraction in lowest terms as the reference takes it (:546-553),
+ * has no inverse mod (q-1)/2, an even (q-1)/2, or a share that is 0 mod q where its factor has to be inverted gives
+ * MPVSS_E_INVALID).  A raw denominator that is 0 mod a small (q-1)/2 is no refusal by itself: q = 23 with positions {1, 11, 12}
+ * has 132/110 = 6/5 mod 11.  mask_out32 = int_BE(SHA256(minimal bytes(G^s))) mod q, 32 bytes big-endian. */
 int mpvss_modp_group_reconstruct(mpvss_ctx* ctx, const mpvss_modp_group* grp, int space, const int64_t* positions_host,
                                  const uint8_t* shares, size_t m, uint8_t* gs_out256, uint8_t* mask_out32);
 /* the scalar ring Z/(q-1) of the handle (host only, no context): the contracts of mpvss_modp_scalar_mul, _scalar_sub,

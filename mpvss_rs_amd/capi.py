@@ -789,15 +789,25 @@ class Engine:
                                                              ps, pc), "group_extract_shares")
         return bytes(ks)[: n * EB], bytes(kc)[: n * EB]
 
-    def group_reconstruct(self, grp: "ModpGroup", positions: Sequence[int], shares: bytes):
-        """(G^s, mask) from m decrypted shares: secret = int(mask) ^ U"""
+    def _group_reconstruct(self, grp: "ModpGroup", space: int, positions: Sequence[int], shares_ptr, m: int, want_mask: bool):
+        """mpvss_modp_group_reconstruct; positions are host memory in either space.  want_mask=False passes NULL for mask_out32
+        and returns None in its place."""
         EB = grp.elem_bytes
-        m = len(positions)
-        pos = (C.c_int64 * max(m, 1))(*positions)
-        ks, ps = _buf(shares or None); kg, pg = _out(EB); km, pm = _out(32)
-        self._check(self.lib.mpvss_modp_group_reconstruct(self.ctx, grp.handle, MPVSS_HOST, C.cast(pos, C.c_void_p), ps, m, pg, pm),
+        pos = (C.c_int64 * max(len(positions), 1))(*positions)
+        kg, pg = _out(EB)
+        km, pm = _out(32) if want_mask else (None, None)
+        self._check(self.lib.mpvss_modp_group_reconstruct(self.ctx, grp.handle, space, C.cast(pos, C.c_void_p), shares_ptr, m, pg, pm),
                     "group_reconstruct")
-        return bytes(kg)[:EB], bytes(km)[:32]
+        return bytes(kg)[:EB], (bytes(km)[:32] if want_mask else None)
+
+    def group_reconstruct(self, grp: "ModpGroup", positions: Sequence[int], shares: bytes, want_mask: bool = True):
+        """(G^s, mask) from m decrypted shares: secret = int(mask) ^ U"""
+        ks, ps = _buf(shares or None)
+        return self._group_reconstruct(grp, MPVSS_HOST, positions, ps, len(positions), want_mask)
+
+    def group_reconstruct_device(self, grp: "ModpGroup", positions: Sequence[int], shares_dev_ptr: int, m: int, want_mask: bool = True):
+        """group_reconstruct with the m shares in HBM ([m][elem_bytes] bytes, left unchanged); positions stay host memory"""
+        return self._group_reconstruct(grp, MPVSS_DEVICE, positions, C.c_void_p(shares_dev_ptr), m, want_mask)
 
     # ---- sharded verification (one engine per GPU; see mpvss_rs_amd/sharding.py)
     def verify_block_compute(self, commitments: bytes, positions: Sequence[int], pubkeys: bytes, shares: bytes,

@@ -1460,7 +1460,9 @@ extern "C" int mpvss_modp_group_extract_shares(mpvss_ctx* ctx, const mpvss_modp_
 
 // participant.rs:462-561: G^s = prod_i S_i^lambda_i.  Lagrange exponents mod (q-1)/2 with the sign kept aside (:526-561); a
 // negative coefficient inverts the factor, and S^-e = S^((q-1) - e) for every unit S mod a prime q, so the m powers run in one
-// k_rt_dual_exp launch with no inversion at all.  (q-1)/2 must be odd (every safe prime above 5).
+// k_rt_dual_exp launch with no inversion at all.  (q-1)/2 must be odd (every safe prime above 5).  A coefficient is reduced to
+// lowest terms before its denominator is inverted (:546-553), which matters only for a (q-1)/2 small enough to divide a position
+// or a difference of two: lagrange_at_zero does so where the raw denominator has no inverse.
 extern "C" int mpvss_modp_group_reconstruct(mpvss_ctx* ctx, const mpvss_modp_group* grp, int space, const int64_t* positions_host,
                                             const uint8_t* shares, size_t m, uint8_t* gs_out256, uint8_t* mask_out32) {
   if (!ctx) return MPVSS_E_INVALID;
@@ -1492,7 +1494,7 @@ extern "C" int mpvss_modp_group_reconstruct(mpvss_ctx* ctx, const mpvss_modp_gro
     return true;
   });
   if (!lagrange_ok)
-    return fail(ctx, MPVSS_E_INVALID, "group_reconstruct: duplicate positions, or a Lagrange denominator without inverse mod (q-1)/2");
+    return fail(ctx, MPVSS_E_INVALID, "group_reconstruct: duplicate positions, or a Lagrange coefficient whose denominator in lowest terms has no inverse mod (q-1)/2");
   // a share that is 0 mod q has no inverse: the reference returns None when its coefficient is negative (:551-553)
   const uint8_t* S = f.host_view(shares, 0, m, hs);
   RET_IF(f.host_ready());

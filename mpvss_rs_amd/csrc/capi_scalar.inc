@@ -147,9 +147,48 @@ void poly_eval_bytes(const Mod& M, bool be, const uint8_t* coeffs, size_t t, con
   }
 }
 
-// Lagrange coefficients at 0 over the ring of an ODD prime modulus:
+// |lambda_i| mod M with the fraction in lowest terms first, as the reference forms it for MODP (participant.rs:546-553: numerator
+// and denominator divided by their gcd, then the denominator inverted mod M).  lagrange_at_zero comes here only when the raw
+// denominator has no inverse mod M: a modulus so small that a position or a difference of two positions shares a factor with it
+// (q = 23: positions {1, 11, 12} give 132/110 = 6/5 mod 11).  The 64-bit factors x_j and |x_j - x_i| are cancelled pairwise; each
+// pair is visited once and later steps only divide, so afterwards every pair is coprime and so are the two products.  A
+// quadratic number of gcds per coefficient, paid by no call whose raw denominators are units.  False: the reduced denominator
+// has no inverse either (the reference returns None).
+template <int N, class Mod>
+bool lagrange_reduced_magnitude(const Mod& M, const int64_t* pos, size_t m, size_t i, uint64_t* mag) {
+  std::vector<uint64_t> top, bot;
+  for (size_t j = 0; j < m; ++j) {
+    if (j == i) continue;
+    const int64_t diff = pos[j] - pos[i];
+    top.push_back((uint64_t)pos[j]);
+    bot.push_back((uint64_t)(diff < 0 ? -diff : diff));
+  }
+  for (uint64_t& x : top)
+    for (uint64_t& y : bot) {
+      if (x == 1) break;
+      uint64_t a = x, b = y;
+      while (b) { const uint64_t r = a % b; a = b; b = r; }
+      x /= a;
+      y /= a;
+    }
+  uint64_t num[N], den[N], inv[N];
+  const uint64_t zero[N] = {0};
+  memset(num, 0, sizeof(num));
+  num[0] = 1;
+  memcpy(den, num, sizeof(num));
+  for (uint64_t x : top) M.muladd_small(num, num, x, zero);
+  for (uint64_t y : bot) M.muladd_small(den, den, y, zero);
+  if (!M.invert(inv, den)) return false;
+  M.mulmod(mag, num, inv);
+  return true;
+}
+
+// Lagrange coefficients at 0 over the ring of an ODD modulus:
 //   lambda_i = prod_{j != i} x_j / (x_j - x_i)      magnitude mod M, sign separately (participant.rs:1525-1544)
-// positions must be pairwise different.  mag[i] = |num| * |den|^-1 mod M; neg[i] = sign of the integer coefficient.
+// positions must be pairwise different.  mag[i] = |num| * |den|^-1 mod M; neg[i] = sign of the integer coefficient.  A unit
+// denominator gives the value of the reduced fraction as it stands (the gcd divides it, so the gcd is a unit too); only a
+// denominator without inverse goes through lagrange_reduced_magnitude.  Over the prime moduli of the fixed groups (all above 2^63)
+// every denominator is a unit.
 template <int N, class Mod>
 bool lagrange_at_zero(const Mod& M, const int64_t* pos, size_t m, std::vector<hsc::Num<N>>& mag, std::vector<char>& neg,
                       bool positions_as_u64) {
@@ -174,8 +213,8 @@ bool lagrange_at_zero(const Mod& M, const int64_t* pos, size_t m, std::vector<hs
       M.muladd_small(den, den, (uint64_t)(diff < 0 ? -diff : diff), zero);
     }
     uint64_t inv[N];
-    if (!M.invert(inv, den)) return false;
-    M.mulmod(mag[i].v, num, inv);
+    if (M.invert(inv, den)) M.mulmod(mag[i].v, num, inv);
+    else if (!lagrange_reduced_magnitude<N>(M, pos, m, i, mag[i].v)) return false;
     neg[i] = negative ? 1 : 0;
   }
   return true;

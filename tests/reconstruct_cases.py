@@ -84,7 +84,10 @@ def ref_reconstruct(G, positions, shares, memo=None):
     mod = lagrange_modulus(G)
     acc = G.identity()
     for lam, S in zip(exact_lagrange(positions), shares):
-        mag = abs(lam.numerator) * pow(lam.denominator, -1, mod) % mod
+        try:
+            mag = abs(lam.numerator) * pow(lam.denominator, -1, mod) % mod
+        except ValueError:            # the denominator in lowest terms has no inverse (a run-time group with a small (q-1)/2)
+            return REFUSED
         key = (S, mag, lam < 0)
         if memo is not None and key in memo:
             f = memo[key]
