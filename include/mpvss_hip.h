@@ -539,8 +539,9 @@ int mpvss_box_verify_wire(mpvss_ctx* ctx, const uint8_t* buf, size_t len, int* v
  * the one-call deal), extract_secret_share and reconstruct.  The scalar ring Z/(q-1) -- P(i), the responses, e2 = w / x -- runs
  * on host threads or, for a handle with odd (q-1)/2 >= 3 (every safe prime above 5), on the device: mpvss_ctx_set_rt_scalar and
  * "the scalar ring on the device" below.  Long-lived public keys can be registered as a key set ("Key sets of a run-time group"
- * below).  Not offered for a
- * run-time group: the block / pipeline forms, verify_many and the wire format; moduli above 3072 bits are refused
+ * below), and the boxes of a whole round verified in one call ("Many boxes in one call" below).  Not offered for a
+ * run-time group: the block / pipeline forms, the wire format, and the overlap of one run's hashing with the next run's GPU
+ * work; moduli above 3072 bits are refused
  * with MPVSS_E_INVALID (4096 bits would overflow the product's 64-bit column accumulators). */
 typedef struct mpvss_modp_group mpvss_modp_group;
 /* q_be: q_len big-endian bytes (leading zeros allowed).  MPVSS_E_INVALID for an even q, q < 5 or q >= 2^2048. */
@@ -724,6 +725,36 @@ int mpvss_modp_group_deal_keyset(mpvss_ctx* ctx, const mpvss_modp_group* grp, co
                                  const int64_t* positions_host, const mpvss_modp_group_keyset* keyset, size_t key_offset,
                                  const uint8_t* witnesses_host, size_t n, uint8_t* x_out, uint8_t* y_out, uint8_t* a1_out,
                                  uint8_t* a2_out, uint8_t* digest32_out, uint8_t* challenge_out256, uint8_t* r_out);
+
+/* Many boxes in one call.  Every participant of a PVSS round deals, so a verifier holds tens to hundreds of boxes for the same
+ * keys, most of them small.  verdicts[i] and digests32[32 i .. 32 i + 31] (optional) are what
+ * mpvss_modp_group_verify_distribution -- for a box with a key set, mpvss_modp_group_verify_distribution_keyset -- gives for
+ * boxes[i] on the same context, byte for byte, at every width and under every mode of mpvss_ctx_set_rt_fd; a box with n == 0
+ * hashes the empty transcript.  Runs of consecutive small boxes (1 <= n, t <= 16384) that take their keys the same way -- all
+ * from arrays, or all from one and the same key set -- travel through the GPU as one batch of at most MPVSS_MAX_CHUNK shares;
+ * every other box, and a run of one, takes the one-box path.
+ * The array pointers of a box live in `space`; challenge_host, boxes, verdicts and digests32 are host memory; keyset != NULL:
+ * pubkeys is ignored and may be NULL.  The call is synchronous, holds the context lock like its one-box sibling and has no
+ * dumps of X, a1, a2.  hash_threads: up to that many host threads hash the transcripts of a run's boxes (clamped to 1..16;
+ * <= 0: the library chooses, at most 16).
+ * ERRORS: count == 0 is MPVSS_OK; no context or no group, and boxes or verdicts NULL with count > 0, are MPVSS_E_INVALID.  A
+ * malformed box -- a required pointer NULL (with n > 0; the challenge always), t == 0 with n > 0, n or t above 0x7fffffff, a key
+ * set of another context or another modulus, key_offset + n beyond the set -- costs only itself: verdict 0, a digest of zeros,
+ * and the call goes on and returns MPVSS_OK (as mpvss_modp_verify_many).  A negative position, a HIP error or a failed
+ * allocation ends the call with the code the one-box call returns and leaves the context usable.
+ * mpvss_modp_group_verify_many_stats: since the context was created, the grouped passes, the boxes that went through them and
+ * the boxes that went through the one-box path (empty and malformed boxes are in neither); any pointer may be NULL. */
+typedef struct mpvss_modp_group_box {
+  const uint8_t* commitments; size_t t;
+  const int64_t* positions;
+  const uint8_t* pubkeys; const uint8_t* shares; const uint8_t* responses; size_t n;
+  const uint8_t* challenge_host;
+  const mpvss_modp_group_keyset* keyset; size_t key_offset;
+} mpvss_modp_group_box;
+int mpvss_modp_group_verify_many(mpvss_ctx* ctx, const mpvss_modp_group* grp, int space, const mpvss_modp_group_box* boxes, size_t count,
+                                 int hash_threads, int* verdicts, uint8_t* digests32);
+int mpvss_modp_group_verify_many_stats(mpvss_ctx* ctx, unsigned long long* groups, unsigned long long* grouped_boxes,
+                                       unsigned long long* single_boxes);
 
 /* ---- hashing helpers (host only; Group::hash_to_scalar, src/groups/modp.rs:142-148) ------ */
 

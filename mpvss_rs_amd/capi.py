@@ -62,6 +62,7 @@ EXPORTED_SYMBOLS = (
     "mpvss_modp_group_keyset_bytes_per_key", "mpvss_modp_group_keyset_create", "mpvss_modp_group_keyset_destroy",
     "mpvss_modp_group_keyset_bytes", "mpvss_modp_group_keyset_dual_exp", "mpvss_modp_group_keyset_twin_exp",
     "mpvss_modp_group_verify_distribution_keyset", "mpvss_modp_group_deal_keyset",
+    "mpvss_modp_group_verify_many", "mpvss_modp_group_verify_many_stats",
 )
 
 GROUP_SECP256K1 = 1
@@ -78,6 +79,13 @@ class EngineError(RuntimeError):
 
 class ModpBox(C.Structure):
     """struct mpvss_modp_box (include/mpvss_hip.h)"""
+    _fields_ = [("commitments", C.c_void_p), ("t", C.c_size_t), ("positions", C.c_void_p), ("pubkeys", C.c_void_p),
+                ("shares", C.c_void_p), ("responses", C.c_void_p), ("n", C.c_size_t), ("challenge_host", C.c_void_p),
+                ("keyset", C.c_void_p), ("key_offset", C.c_size_t)]
+
+
+class GroupBox(C.Structure):
+    """struct mpvss_modp_group_box"""
     _fields_ = [("commitments", C.c_void_p), ("t", C.c_size_t), ("positions", C.c_void_p), ("pubkeys", C.c_void_p),
                 ("shares", C.c_void_p), ("responses", C.c_void_p), ("n", C.c_size_t), ("challenge_host", C.c_void_p),
                 ("keyset", C.c_void_p), ("key_offset", C.c_size_t)]
@@ -272,6 +280,9 @@ def load_library() -> C.CDLL:
     lib.mpvss_modp_group_verify_distribution_keyset.argtypes = [vp, vp, ci, u8p, sz, i64p, vp, sz, u8p, u8p, sz, u8p,
                                                                 C.POINTER(ci), u8p, u8p, u8p, u8p]
     lib.mpvss_modp_group_deal_keyset.argtypes = [vp, vp, u8p, sz, i64p, vp, sz, u8p, sz, u8p, u8p, u8p, u8p, u8p, u8p, u8p]
+    lib.mpvss_modp_group_verify_many.argtypes = [vp, vp, ci, C.POINTER(GroupBox), sz, ci, C.POINTER(ci), u8p]
+    lib.mpvss_modp_group_verify_many_stats.argtypes = [vp, C.POINTER(C.c_ulonglong), C.POINTER(C.c_ulonglong),
+                                                       C.POINTER(C.c_ulonglong)]
     return lib
 
 
@@ -763,6 +774,50 @@ class Engine:
         if dump:
             out.update(X=bytes(kx)[: n * EB], a1=bytes(k1)[: n * EB], a2=bytes(k2)[: n * EB])
         return out
+
+    # ---- many boxes of a run-time group in one call ----------------------------------------------------------------------
+    def _group_verify_many(self, grp: "ModpGroup", space: int, arr, count: int, hash_threads: int):
+        verdicts = (C.c_int * max(count, 1))()
+        kd, pd = _out(32 * count)
+        self._check(self.lib.mpvss_modp_group_verify_many(self.ctx, grp.handle, space, arr, count, int(hash_threads), verdicts, pd),
+                    "group_verify_many")
+        raw = bytes(kd)
+        return [(bool(verdicts[i]), raw[32 * i:32 * i + 32]) for i in range(count)]
+
+    def group_verify_many(self, grp: "ModpGroup", boxes: Sequence[dict], hash_threads: int = 0):
+        """boxes: dicts with commitments, positions, pubkeys, shares, responses, challenge (host bytes; None: a null pointer) and,
+        in place of pubkeys, keyset (a GroupKeySet) with key_offset.  Returns [(verdict, digest)] in box order: what
+        group_verify_distribution / group_verify_distribution_keyset give box by box, small boxes travelling in groups."""
+        EB = grp.elem_bytes
+        keep, arr = [], (GroupBox * max(len(boxes), 1))()
+        for i, b in enumerate(boxes):
+            n = len(b["positions"])
+            pos = (C.c_int64 * max(n, 1))(*b["positions"])
+            bufs = [_buf(b.get(k) or None) for k in ("commitments", "pubkeys", "shares", "responses", "challenge")]
+            ks = b.get("keyset")
+            keep.append((pos, bufs, ks))
+            arr[i] = GroupBox(bufs[0][1], len(b.get("commitments") or b"") // EB, C.cast(pos, C.c_void_p), bufs[1][1], bufs[2][1],
+                              bufs[3][1], n, bufs[4][1], ks.handle if ks is not None else None, int(b.get("key_offset", 0)))
+        return self._group_verify_many(grp, MPVSS_HOST, arr, len(boxes), hash_threads)
+
+    def group_verify_many_device(self, grp: "ModpGroup", boxes: Sequence[dict], hash_threads: int = 0):
+        """the same with every array of a box in HBM: dicts with commitments_ptr, t, positions_ptr (int64), pubkeys_ptr,
+        shares_ptr, responses_ptr, n, and challenge (host bytes); keyset / key_offset as in group_verify_many"""
+        keep, arr = [], (GroupBox * max(len(boxes), 1))()
+        for i, b in enumerate(boxes):
+            kc, pc = _buf(b["challenge"])
+            ks = b.get("keyset")
+            keep.append((kc, ks))
+            ptr = lambda k: C.c_void_p(b[k]) if b.get(k) else None
+            arr[i] = GroupBox(ptr("commitments_ptr"), int(b["t"]), ptr("positions_ptr"), ptr("pubkeys_ptr"), ptr("shares_ptr"),
+                              ptr("responses_ptr"), int(b["n"]), pc, ks.handle if ks is not None else None, int(b.get("key_offset", 0)))
+        return self._group_verify_many(grp, MPVSS_DEVICE, arr, len(boxes), hash_threads)
+
+    def group_verify_many_stats(self) -> dict:
+        """since the context was created: grouped passes, boxes that went through them, boxes that took the one-box path"""
+        g, b, s = C.c_ulonglong(0), C.c_ulonglong(0), C.c_ulonglong(0)
+        self._check(self.lib.mpvss_modp_group_verify_many_stats(self.ctx, C.byref(g), C.byref(b), C.byref(s)), "group_verify_many_stats")
+        return {"groups": int(g.value), "grouped_boxes": int(b.value), "single_boxes": int(s.value)}
 
     def group_deal_keyset(self, grp: "ModpGroup", coeffs: bytes, positions: Sequence[int], keyset: "GroupKeySet", key_offset: int,
                           witnesses: bytes) -> dict:

@@ -7,7 +7,8 @@
 // (below) for the device, the constants, the chunk loop, the choice of space, the copies back and the wiping of secrets,
 // and in between only what is its own -- which buffers its arrays use, which of them are secret, what it launches and
 // what it hashes.  The launch decisions (rt_comb_for, rt_dleq_dev, rt_commit_eval_dev with rt_fd_prepare and
-// rt_fd_positions_ok, rt_twin_dev, rt_fixed_base_dev, rt_scalar_on_device, rt_product_tree) are single places of their own.
+// rt_fd_positions_ok, rt_twin_dev, rt_fixed_base_dev, rt_scalar_on_device, rt_product_tree, and the grouping of small boxes in
+// mpvss_modp_group_verify_many) are single places of their own.
 
 constexpr size_t RT_EB_MAX = FRAME_EB_MAX;     // the widest element / scalar of a handle (mpvss_modp_group_create_wide): 384 bytes
 
@@ -365,10 +366,11 @@ int rt_comb_for(mpvss_ctx* ctx, const mpvss_modp_group* grp, const modp_rt_const
 }
 
 // a1 = g1^r h1^c and a2 = g2^r h2^c for cnt shares (device pointers but g1: one shared base in host bytes; c stride 0 = shared);
-// g2: the second proof's bases as bytes, or (g2 null) g2_rows: the rows of a key set from the chunk's first key on
+// g2: the second proof's bases as bytes, or (g2 null) g2_rows: the rows of a key set from the chunk's first key on -- or, with
+// g2_key_of, from the set's first key on, share i taking key g2_key_of[i] (device; a run of boxes of mpvss_modp_group_verify_many)
 int rt_dleq_dev(mpvss_ctx* ctx, const mpvss_modp_group* grp, const modp_rt_consts* dc, const uint8_t* g1_host, const uint8_t* h1,
                 const uint8_t* g2, const uint32_t* g2_rows, const uint8_t* h2, const uint8_t* r, const uint8_t* c, size_t c_stride,
-                size_t cnt, uint8_t* a1, uint8_t* a2) {
+                size_t cnt, uint8_t* a1, uint8_t* a2, const uint32_t* g2_key_of = nullptr) {
   const size_t TW = 16 * rt_L(grp), EB = grp->eb;
   const uint32_t *tg, *t1, *t2;
   if (a1) {
@@ -388,6 +390,8 @@ int rt_dleq_dev(mpvss_ctx* ctx, const mpvss_modp_group* grp, const modp_rt_const
     if (g2) {
       RET_IF(rt_tables(ctx, grp, dc, g2, EB, cnt, ctx->rt_tab1, &t1));
       TIMED_LAUNCH(ctx, 3, modp_rt_launch_dual_exp(grp->lpl, t1, TW, t2, TW, r, EB, c, c_stride, (int)cnt, a2, dc, ctx->stream));
+    } else if (g2_key_of) {
+      TIMED_LAUNCH(ctx, 3, modp_rt_launch_keyset_exp_idx(grp->lpl, g2_rows, g2_key_of, t2, TW, r, c, c_stride, (int)cnt, a2, dc, ctx->stream));
     } else {
       TIMED_LAUNCH(ctx, 3, modp_rt_launch_keyset_exp(grp->lpl, g2_rows, t2, TW, r, nullptr, c, c_stride, (int)cnt, a2, nullptr, dc,
                                                      ctx->stream));
@@ -569,13 +573,18 @@ size_t rt_keyset_stride(const mpvss_modp_group* grp) { return modp_rt_keyset_byt
 
 // The one admission of a key set to a call (context lock held): built by this context, for this modulus at this width, and
 // holding the keys key_offset .. key_offset + n - 1.  *rows: the rows of key key_offset.
+// Why not, or null when the set is admitted (mpvss_modp_group_verify_many asks without failing the call).
+const char* rt_keyset_refusal(const mpvss_ctx* ctx, const mpvss_modp_group* grp, const mpvss_modp_group_keyset* ks, size_t key_offset,
+                              size_t n) {
+  if (!ks) return "key set: none given";
+  if (ks->ctx != ctx) return "key set: built by another context";
+  if (ks->eb != grp->eb || ks->lpl != grp->lpl || memcmp(ks->q_be, grp->q_be, grp->eb) != 0) return "key set: built for another modulus";
+  if (key_offset > ks->n || n > ks->n - key_offset) return "key set: key_offset + n is beyond the set";
+  return nullptr;
+}
 int rt_keyset_rows(mpvss_ctx* ctx, const mpvss_modp_group* grp, const mpvss_modp_group_keyset* ks, size_t key_offset, size_t n,
                    const uint32_t** rows) {
-  if (!ks) return fail(ctx, MPVSS_E_INVALID, "key set: none given");
-  if (ks->ctx != ctx) return fail(ctx, MPVSS_E_INVALID, "key set: built by another context");
-  if (ks->eb != grp->eb || ks->lpl != grp->lpl || memcmp(ks->q_be, grp->q_be, grp->eb) != 0)
-    return fail(ctx, MPVSS_E_INVALID, "key set: built for another modulus");
-  if (key_offset > ks->n || n > ks->n - key_offset) return fail(ctx, MPVSS_E_INVALID, "key set: key_offset + n is beyond the set");
+  if (const char* why = rt_keyset_refusal(ctx, grp, ks, key_offset, n)) return fail(ctx, MPVSS_E_INVALID, why);
   *rows = ks->rows + key_offset * rt_keyset_stride(grp);
   return 0;
 }
@@ -1787,4 +1796,258 @@ extern "C" int mpvss_modp_group_deal_keyset(mpvss_ctx* ctx, const mpvss_modp_gro
   RET_IF(rt_keyset_rows(ctx, grp, keyset, key_offset, n, &rows));
   return rt_deal_locked(ctx, grp, coeffs_host, t, positions_host, nullptr, rows, witnesses_host, n, x_out, y_out, a1_out, a2_out,
                         digest32_out, challenge_out256, r_out);
+}
+
+// =====================================================================================================================
+// Many boxes in one call (DESIGN section 13, "Many boxes in one call"): mpvss_modp_group_verify_many.  A PVSS round gives a
+// verifier tens to hundreds of small boxes for the same keys; one box per call is the latency of a chain of Montgomery products
+// on one or two waves.  Runs of small boxes therefore travel as ONE dense concatenation through the launches of one box:
+// k_rt_to_mont over all commitments, k_rt_commit_eval_tiles (a tile = up to RT_NUMS shares of one box = one workgroup), the
+// challenge of each box spread to its shares, then rt_dleq_dev with a per-share c.  THE grouping decision is rt_many_walk below.
+// =====================================================================================================================
+namespace {
+
+// The largest n and t of a box that may travel in a run: 16384, the group-14 figure.  The condition on it -- for no measured shape
+// may the grouped call be slower than the loop of one-box calls -- holds with room at every shape of tools/modp_rt_many_boxes.py
+// (profiles/modp_rt_many_boxes.txt: 400 x (5, 3) 159 .. 385 times faster, 200 x (100, 34) 18 .. 104 times, 60 x (1024, 32), the
+// largest boxes measured, 5.6 .. 12.9 times, at 1024 and 2048 bits, host and device space, key arrays and one key set), so the
+// value stays.  Boxes between 1024 and 16384 shares have not been measured.
+constexpr size_t RT_GROUP_BOX_MAX = 16384;
+constexpr size_t RT_TILE = 16;                     // RT_NUMS of modp_rt_kernels.inc: numbers per workgroup of every run-time kernel
+
+enum RtBoxKind { RT_BOX_MALFORMED, RT_BOX_EMPTY, RT_BOX_SMALL, RT_BOX_SINGLE };
+
+// one box, judged on the host before anything is launched
+RtBoxKind rt_box_kind(const mpvss_ctx* ctx, const mpvss_modp_group* grp, const mpvss_modp_group_box& b) {
+  if (!b.challenge_host || b.n > 0x7fffffff || b.t > 0x7fffffff) return RT_BOX_MALFORMED;
+  if (b.n > 0 && (!b.commitments || !b.positions || !b.shares || !b.responses || b.t == 0 || (!b.keyset && !b.pubkeys)))
+    return RT_BOX_MALFORMED;
+  if (b.keyset && rt_keyset_refusal(ctx, grp, b.keyset, b.key_offset, b.n)) return RT_BOX_MALFORMED;
+  if (b.n == 0) return RT_BOX_EMPTY;
+  // a run holds at most MAX_CHUNK shares and as many commitments (its launchers count in int)
+  return (b.n <= RT_GROUP_BOX_MAX && b.t <= RT_GROUP_BOX_MAX && b.n <= MAX_CHUNK && b.t <= MAX_CHUNK) ? RT_BOX_SMALL : RT_BOX_SINGLE;
+}
+
+// the one-box path, unchanged: chunking and forward differences included
+int rt_many_single(mpvss_ctx* ctx, const mpvss_modp_group* grp, int space, const mpvss_modp_group_box& b, int* verdict, uint8_t* digest) {
+  const uint32_t* rows = nullptr;
+  if (b.keyset) RET_IF(rt_keyset_rows(ctx, grp, b.keyset, b.key_offset, b.n, &rows));
+  return rt_verify_distribution_locked(ctx, grp, space, b.commitments, b.t, b.positions, b.keyset ? nullptr : b.pubkeys, rows, b.shares,
+                                       b.responses, b.n, b.challenge_host, verdict, digest, nullptr, nullptr, nullptr);
+}
+
+// one array of a run on the device, dense: gathered on the host and copied once (host space), or one device-to-device copy per
+// box (device space).  piece(k, &src, &bytes): box k's part.
+template <class Piece>
+int rt_run_gather(mpvss_ctx* ctx, int space, size_t boxes, size_t total_bytes, DevBuf& buf, std::vector<uint8_t>& host, Piece piece) {
+  RET_IF(ensure(ctx, buf, total_bytes));
+  if (space == MPVSS_DEVICE) {
+    size_t at = 0;
+    for (size_t k = 0; k < boxes; ++k) {
+      const void* src;
+      size_t bytes;
+      piece(k, &src, &bytes);
+      HIPCHK(ctx, hipMemcpyAsync((uint8_t*)buf.p + at, src, bytes, hipMemcpyDeviceToDevice, ctx->stream));
+      at += bytes;
+    }
+    return 0;
+  }
+  host.resize(total_bytes);
+  size_t at = 0;
+  for (size_t k = 0; k < boxes; ++k) {
+    const void* src;
+    size_t bytes;
+    piece(k, &src, &bytes);
+    memcpy(host.data() + at, src, bytes);
+    at += bytes;
+  }
+  HIPCHK(ctx, hipMemcpyAsync(buf.p, host.data(), total_bytes, hipMemcpyHostToDevice, ctx->stream));
+  return 0;
+}
+
+// a grouped pass: the boxes run[0 .. B) (indices into `boxes`, all RT_BOX_SMALL, all with array keys or all with the key set
+// `ks`), shares in all <= MAX_CHUNK.  Same launches as one box, plus the spreading kernel.
+int rt_many_run(mpvss_ctx* ctx, const mpvss_modp_group* grp, int space, const mpvss_modp_group_box* boxes, const std::vector<size_t>& run,
+                int hash_threads, int* verdicts, uint8_t* digests32) {
+  const size_t B = run.size(), EB = grp->eb;
+  const mpvss_modp_group_keyset* ks = boxes[run[0]].keyset;
+  // the tables: tiles {box, first share, live count, 0}, boxes {first commitment, t}, and with a key set the key of every share
+  std::vector<uint32_t> tiles, btab(2 * B), key_of;
+  std::vector<size_t> first(B + 1);
+  size_t S = 0, T = 0;
+  for (size_t k = 0; k < B; ++k) {
+    const mpvss_modp_group_box& b = boxes[run[k]];
+    first[k] = S;
+    btab[2 * k] = (uint32_t)T;
+    btab[2 * k + 1] = (uint32_t)b.t;
+    for (size_t off = 0; off < b.n; off += RT_TILE) {
+      const uint32_t tile[4] = {(uint32_t)k, (uint32_t)(S + off), (uint32_t)std::min(b.n - off, RT_TILE), 0};
+      tiles.insert(tiles.end(), tile, tile + 4);
+    }
+    if (ks)
+      for (size_t i = 0; i < b.n; ++i) key_of.push_back((uint32_t)(b.key_offset + i));
+    S += b.n;
+    T += b.t;
+  }
+  first[B] = S;
+  const size_t ntiles = tiles.size() / 4;
+  std::vector<uint8_t> ch(B * EB);
+  for (size_t k = 0; k < B; ++k) memcpy(ch.data() + k * EB, boxes[run[k]].challenge_host, EB);
+
+  // host sources of asynchronous copies and the results read back: declared before the frame, whose way out drains the stream
+  std::vector<uint8_t> g_pos, g_cm, g_y, g_Y, g_r, hX, h1, h2, hYdev;
+  std::vector<int64_t> pos_back;
+  RtCall f(ctx, grp, space);
+  struct Drain {            // no copy out of (or into) the vectors above outlives them, whichever way the pass ends
+    mpvss_ctx* c;
+    ~Drain() { (void)hipStreamSynchronize(c->stream); }
+  } drain{ctx};
+  RET_IF(f.begin());
+  auto part = [&](const uint8_t* mpvss_modp_group_box::*arr, size_t mpvss_modp_group_box::*cnt, size_t unit) {
+    return [&run, boxes, arr, cnt, unit](size_t k, const void** src, size_t* bytes) {
+      *src = boxes[run[k]].*arr;
+      *bytes = boxes[run[k]].*cnt * unit;
+    };
+  };
+  RET_IF(rt_run_gather(ctx, space, B, S * 8, ctx->rt_run_pos, g_pos, [&](size_t k, const void** src, size_t* bytes) {
+    *src = boxes[run[k]].positions;
+    *bytes = boxes[run[k]].n * 8;
+  }));
+  RET_IF(rt_run_gather(ctx, space, B, T * EB, ctx->rt_in[4], g_cm, part(&mpvss_modp_group_box::commitments, &mpvss_modp_group_box::t, EB)));
+  if (!ks) RET_IF(rt_run_gather(ctx, space, B, S * EB, ctx->rt_in[1], g_y, part(&mpvss_modp_group_box::pubkeys, &mpvss_modp_group_box::n, EB)));
+  RET_IF(rt_run_gather(ctx, space, B, S * EB, ctx->rt_in[2], g_Y, part(&mpvss_modp_group_box::shares, &mpvss_modp_group_box::n, EB)));
+  RET_IF(rt_run_gather(ctx, space, B, S * EB, ctx->rt_in[3], g_r, part(&mpvss_modp_group_box::responses, &mpvss_modp_group_box::n, EB)));
+  // positions are checked as the one-box call checks them: a negative one ends the call (the reference panics)
+  const int64_t* P = (const int64_t*)g_pos.data();
+  if (space == MPVSS_DEVICE) {
+    pos_back.resize(S);
+    HIPCHK(ctx, hipMemcpyAsync(pos_back.data(), ctx->rt_run_pos.p, S * 8, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    P = pos_back.data();
+  }
+  RET_IF(check_positions_host(ctx, P, S));
+  RET_IF(ensure(ctx, ctx->rt_run_tiles, tiles.size() * 4));
+  RET_IF(ensure(ctx, ctx->rt_run_boxes, btab.size() * 4));
+  RET_IF(ensure(ctx, ctx->rt_run_ch, B * EB));
+  HIPCHK(ctx, hipMemcpyAsync(ctx->rt_run_tiles.p, tiles.data(), tiles.size() * 4, hipMemcpyHostToDevice, ctx->stream));
+  HIPCHK(ctx, hipMemcpyAsync(ctx->rt_run_boxes.p, btab.data(), btab.size() * 4, hipMemcpyHostToDevice, ctx->stream));
+  HIPCHK(ctx, hipMemcpyAsync(ctx->rt_run_ch.p, ch.data(), B * EB, hipMemcpyHostToDevice, ctx->stream));
+  if (ks) {
+    RET_IF(ensure(ctx, ctx->rt_run_keyof, S * 4));
+    HIPCHK(ctx, hipMemcpyAsync(ctx->rt_run_keyof.p, key_of.data(), S * 4, hipMemcpyHostToDevice, ctx->stream));
+  }
+  uint8_t* dc_share = f.work(ctx->rt_in[5], S);
+  uint8_t* dX = f.work(ctx->rt_out[0], S);
+  uint8_t* d1 = f.work(ctx->rt_out[1], S);
+  uint8_t* d2 = f.work(ctx->rt_out[2], S);
+  RET_IF(f.rc);
+  RET_IF(ensure(ctx, ctx->rt_cm, T * rt_L(grp) * 4));
+  LAUNCHCHK(ctx, modp_rt_launch_to_mont(grp->lpl, (const uint8_t*)ctx->rt_in[4].p, (int)T, (uint32_t*)ctx->rt_cm.p, f.dc, ctx->stream));
+  ++ctx->rt_horner_calls;
+  TIMED_LAUNCH(ctx, 0, modp_rt_launch_commit_eval_tiles(grp->lpl, (const uint32_t*)ctx->rt_cm.p, (const uint32_t*)ctx->rt_run_tiles.p,
+                                                        (int)ntiles, (const uint32_t*)ctx->rt_run_boxes.p,
+                                                        (const int64_t*)ctx->rt_run_pos.p, dX, f.dc, ctx->stream));
+  LAUNCHCHK(ctx, modp_rt_launch_spread_challenge((const uint8_t*)ctx->rt_run_ch.p, (const uint32_t*)ctx->rt_run_tiles.p, (int)ntiles, (int)EB,
+                                                 dc_share, ctx->stream));
+  // a1 = g^r X^c, a2 = y^r Y^c over the concatenation, every share with its own box's c
+  RET_IF(rt_dleq_dev(ctx, grp, f.dc, grp->g_be, dX, ks ? nullptr : (const uint8_t*)ctx->rt_in[1].p, ks ? ks->rows : nullptr,
+                     (const uint8_t*)ctx->rt_in[2].p, (const uint8_t*)ctx->rt_in[3].p, dc_share, EB, S, d1, d2,
+                     ks ? (const uint32_t*)ctx->rt_run_keyof.p : nullptr));
+  f.to_host(dX, S, hX);
+  f.to_host(d1, S, h1);
+  f.to_host(d2, S, h2);
+  const uint8_t* Y = g_Y.data();
+  if (space == MPVSS_DEVICE) {
+    f.to_host((const uint8_t*)ctx->rt_in[2].p, S, hYdev);
+    Y = hYdev.data();
+  }
+  RET_IF(f.settle());
+  // the boxes' transcripts are independent: box k hashes the shares first[k] .. first[k+1] of the concatenation
+  auto hash_boxes = [&](size_t k0, size_t k1) {
+    for (size_t k = k0; k < k1; ++k) {
+      mpvss::Sha256 h;
+      frame_shares(h, hX.data(), Y, h1.data(), h2.data(), first[k], first[k + 1], EB);
+      uint8_t digest[32], c[RT_EB_MAX];
+      h.final(digest);
+      if (digests32) memcpy(digests32 + 32 * run[k], digest, 32);
+      rt_hash_to_scalar(grp, digest, 32, c);
+      verdicts[run[k]] = memcmp(c, boxes[run[k]].challenge_host, EB) == 0 ? 1 : 0;
+    }
+  };
+  // automatic: one thread per 512 shares of the run (half a megabyte of transcript and more), never sized by the machine
+  size_t nth = hash_threads > 0 ? (size_t)hash_threads : std::max<size_t>(1, S / 512);
+  nth = std::min(std::min<size_t>(nth, 16), B);
+  if (nth <= 1) {
+    hash_boxes(0, B);
+  } else {
+    std::vector<std::thread> pool;
+    pool.reserve(nth - 1);
+    for (size_t i = 1; i < nth; ++i) pool.emplace_back(hash_boxes, B * i / nth, B * (i + 1) / nth);
+    hash_boxes(0, B / nth);
+    for (auto& th : pool) th.join();
+  }
+  ++ctx->rt_many_groups;
+  ctx->rt_many_grouped_boxes += B;
+  return f.end();
+}
+
+}  // namespace
+
+extern "C" int mpvss_modp_group_verify_many(mpvss_ctx* ctx, const mpvss_modp_group* grp, int space, const mpvss_modp_group_box* boxes,
+                                            size_t count, int hash_threads, int* verdicts, uint8_t* digests32) {
+  if (!ctx) return MPVSS_E_INVALID;
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  if (rt_bad_group(grp)) return fail(ctx, MPVSS_E_INVALID, "group_verify_many: no group");
+  if (count == 0) return MPVSS_OK;
+  if (!boxes || !verdicts) return fail(ctx, MPVSS_E_INVALID, "group_verify_many: bad argument");
+  for (size_t i = 0; i < count; ++i) verdicts[i] = 0;
+  if (digests32) memset(digests32, 0, 32 * count);         // a malformed box has no transcript: verdict 0, digest zero
+  // THE grouping decision: a run is a maximal stretch of consecutive small boxes that take keys the same way (arrays, or one and
+  // the same key set) and hold at most MAX_CHUNK shares (and commitments) together.  Empty and malformed boxes are settled here
+  // and do not end a run; a run of one box takes the one-box path, like every box that fits no run.
+  std::vector<size_t> run;
+  size_t run_shares = 0, run_cms = 0;
+  auto flush = [&]() -> int {
+    int rc = MPVSS_OK;
+    if (run.size() == 1) {
+      const size_t i = run[0];
+      rc = rt_many_single(ctx, grp, space, boxes[i], &verdicts[i], digests32 ? digests32 + 32 * i : nullptr);
+      if (rc == MPVSS_OK) ++ctx->rt_many_single_boxes;
+    } else if (run.size() > 1) {
+      rc = rt_many_run(ctx, grp, space, boxes, run, hash_threads, verdicts, digests32);
+    }
+    run.clear();
+    run_shares = run_cms = 0;
+    return rc;
+  };
+  for (size_t i = 0; i < count; ++i) {
+    const mpvss_modp_group_box& b = boxes[i];
+    const RtBoxKind kind = rt_box_kind(ctx, grp, b);
+    if (kind == RT_BOX_MALFORMED) continue;
+    if (kind == RT_BOX_EMPTY) {                           // the empty transcript, on the host
+      RET_IF(rt_many_single(ctx, grp, space, b, &verdicts[i], digests32 ? digests32 + 32 * i : nullptr));
+      continue;
+    }
+    if (kind == RT_BOX_SINGLE) {
+      RET_IF(flush());
+      RET_IF(rt_many_single(ctx, grp, space, b, &verdicts[i], digests32 ? digests32 + 32 * i : nullptr));
+      ++ctx->rt_many_single_boxes;
+      continue;
+    }
+    if (!run.empty() && (boxes[run[0]].keyset != b.keyset || run_shares + b.n > MAX_CHUNK || run_cms + b.t > MAX_CHUNK)) RET_IF(flush());
+    run.push_back(i);
+    run_shares += b.n;
+    run_cms += b.t;
+  }
+  return flush();
+}
+
+extern "C" int mpvss_modp_group_verify_many_stats(mpvss_ctx* ctx, unsigned long long* groups, unsigned long long* grouped_boxes,
+                                                  unsigned long long* single_boxes) {
+  if (!ctx) return MPVSS_E_INVALID;
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  if (groups) *groups = ctx->rt_many_groups;
+  if (grouped_boxes) *grouped_boxes = ctx->rt_many_grouped_boxes;
+  if (single_boxes) *single_boxes = ctx->rt_many_single_boxes;
+  return MPVSS_OK;
 }

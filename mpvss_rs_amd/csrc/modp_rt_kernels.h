@@ -51,6 +51,9 @@ size_t modp_rt_keyset_bytes(int lpl, size_t count);
 #define MODP_RT_FN(name) modp_rt27_##name
 #include "modp_rt_launchers.h"
 #undef MODP_RT_FN
+/* c_out[first + i] = c_box[box] (eb bytes each, eb a multiple of 4) for the live shares i of every tile of
+ * modp_rt_launch_commit_eval_tiles' tile table: plain bytes, no width */
+int modp_rt_launch_spread_challenge(const uint8_t* c_box, const uint32_t* tiles, int ntiles, int eb, uint8_t* c_out, hipStream_t s);
 /* modp_rt_fd_kernels.hip: modp_rt_launch_fd_chains at 5, 9 and 18 limbs per lane */
 int modp_rtfd_launch_fd_chains(int lpl, const uint32_t* seeds_m, int t, int n, int S, uint32_t* x_m, uint32_t* park,
                                const modp_rt_consts* cs, hipStream_t s);

@@ -19,6 +19,8 @@
 #define RT_DISPATCH_FN(lpl, FN, ...) \
   ((lpl) == 5 ? FN<5>(__VA_ARGS__) : (lpl) == 9 ? FN<9>(__VA_ARGS__) : (lpl) == 18 ? FN<18>(__VA_ARGS__) : (int)hipErrorInvalidValue)
 
+#define RT_WIDTH_FREE   // the kernel that has no width (k_rt_spread_challenge) lives in this unit alone
+
 #include "modp_rt_kernels.inc"
 
 // what the host needs to know of a width: none of it launches anything

@@ -8,9 +8,10 @@
 //   ModpGroup::exp / ::mul                       (src/groups/modp.rs:122-132)      k_rt_dual_exp, k_rt_mul
 //   DLEQ verifier commitments a = g1^r h1^c      (src/dleq.rs:66-84)               k_rt_dual_exp (two tables)
 //   X_i = prod_j C_j^(i^j mod (q-1))             (src/participant.rs:423-434)      k_rt_commit_eval
+//   X_i of the small boxes of a whole round, one launch   (one call per box in the reference)  k_rt_commit_eval_tiles, k_rt_spread_challenge
 //   P(i), r_i = w_i - P(i) c, w_i / x_i in Z/(q-1) (src/polynomial.rs:50-58, src/dleq.rs:42-50, modp.rs:180-182)
 //                                                                                  k_rt_modq_poly_eval, _responses, _mul
-//   y_i^r_i Y_i^c, y_i^P(i), y_i^w_i for long-lived keys    (src/participant.rs:436-447, :219)  k_rt_keyset_bases, _rows, _exp
+//   y_i^r_i Y_i^c, y_i^P(i), y_i^w_i for long-lived keys    (src/participant.rs:436-447, :219)  k_rt_keyset_bases, _rows, _exp, _exp_idx
 //
 // Layout and program shape are those of the group-14 kernels (modp_kernels.hip): one number per DPP quad, 16 numbers
 // per one-wave workgroup, the second operand of every product staged in LDS, 16-entry window tables in HBM.  The
@@ -473,23 +474,21 @@ __global__ void RT_KERNEL(LPL) k_rt_keyset_rows(u32* __restrict__ ks, int nrows,
 // Full-width e1 with a 256-bit e2 at 2048 bits: 252 squarings + 512 row products + 64 products by B2 + 1 exit = 829 (844 with
 // B2's table; tests/test_modp_rt_keyset_model.py).
 // ---------------------------------------------------------------------------------------
+//   rows, x, live : the rows of this quad's key, the share it works on and whether it stores its result -- the entry decides
+//                   which key a share takes: the x-th of the rows it was given (k_rt_keyset_exp) or the one an index names
+//                   (k_rt_keyset_exp_idx)
 template <int LPL>
-__global__ void RT_KERNEL(LPL) k_rt_keyset_exp(const u32* __restrict__ ks, const u32* __restrict__ tab2, size_t tab2_stride,
-                                               const uint8_t* __restrict__ e1a_be, const uint8_t* __restrict__ e1b_be,
-                                               const uint8_t* __restrict__ e2_be, size_t e2_stride, int count,
-                                               uint8_t* __restrict__ out_a, uint8_t* __restrict__ out_b,
-                                               const modp_rt_consts* __restrict__ cs) {
+__device__ __forceinline__ void rt_keyset_exp_body(u32* lds, const u32* __restrict__ rows, int x, bool live, const u32* __restrict__ tab2,
+                                                   size_t tab2_stride, const uint8_t* __restrict__ e1a_be,
+                                                   const uint8_t* __restrict__ e1b_be, const uint8_t* __restrict__ e2_be,
+                                                   size_t e2_stride, uint8_t* __restrict__ out_a, uint8_t* __restrict__ out_b,
+                                                   const modp_rt_consts* __restrict__ cs) {
   constexpr int L = Width<LPL>::L, SLOT = Width<LPL>::SLOT, EB = Width<LPL>::EB, J = Width<LPL>::KS_ROWS;
-  __shared__ __attribute__((aligned(16))) u32 lds[RT_NUMS * SLOT];
   const Lane ln = make_lane();
-  const int xi = blockIdx.x * RT_NUMS + (threadIdx.x >> 2);
-  const bool live = xi < count;
-  const int x = live ? xi : count - 1;
   u32* slot = lds + (threadIdx.x >> 2) * SLOT;
   const u32 n0inv = cs->n0inv;
   const bool second = blockIdx.y != 0;
   const bool has2 = tab2 != nullptr;
-  const u32* rows = ks + (size_t)x * J * 16 * L;
   const uint8_t* e1 = (second ? e1b_be : e1a_be) + (size_t)x * EB;
   const uint8_t* e2 = has2 ? e2_be + (size_t)x * e2_stride : e1;
   const u32* t2 = has2 ? tab2 + (size_t)x * tab2_stride : rows;
@@ -544,6 +543,35 @@ __global__ void RT_KERNEL(LPL) k_rt_keyset_exp(const u32* __restrict__ ks, const
     ++s;
   }
   store_canonical<LPL>((second ? out_b : out_a) + (size_t)x * EB, acc, slot, cs, ln, live);
+}
+
+template <int LPL>
+__global__ void RT_KERNEL(LPL) k_rt_keyset_exp(const u32* __restrict__ ks, const u32* __restrict__ tab2, size_t tab2_stride,
+                                               const uint8_t* __restrict__ e1a_be, const uint8_t* __restrict__ e1b_be,
+                                               const uint8_t* __restrict__ e2_be, size_t e2_stride, int count,
+                                               uint8_t* __restrict__ out_a, uint8_t* __restrict__ out_b,
+                                               const modp_rt_consts* __restrict__ cs) {
+  __shared__ __attribute__((aligned(16))) u32 lds[RT_NUMS * Width<LPL>::SLOT];
+  const int xi = blockIdx.x * RT_NUMS + (threadIdx.x >> 2);
+  const bool live = xi < count;
+  const int x = live ? xi : count - 1;
+  rt_keyset_exp_body<LPL>(lds, ks + (size_t)x * Width<LPL>::KS_ROWS * 16 * Width<LPL>::L, x, live, tab2, tab2_stride, e1a_be, e1b_be, e2_be,
+                          e2_stride, out_a, out_b, cs);
+}
+
+// The same over keys named one by one: share x takes the rows of key key_of[x] of the set (ks: the rows of the set's first key).
+// The shares of a run of boxes do not walk the set's rows consecutively (capi_modp_rt.inc, "Many boxes in one call").
+template <int LPL>
+__global__ void RT_KERNEL(LPL) k_rt_keyset_exp_idx(const u32* __restrict__ ks, const u32* __restrict__ key_of, const u32* __restrict__ tab2,
+                                                   size_t tab2_stride, const uint8_t* __restrict__ e1_be,
+                                                   const uint8_t* __restrict__ e2_be, size_t e2_stride, int count,
+                                                   uint8_t* __restrict__ out, const modp_rt_consts* __restrict__ cs) {
+  __shared__ __attribute__((aligned(16))) u32 lds[RT_NUMS * Width<LPL>::SLOT];
+  const int xi = blockIdx.x * RT_NUMS + (threadIdx.x >> 2);
+  const bool live = xi < count;
+  const int x = live ? xi : count - 1;
+  rt_keyset_exp_body<LPL>(lds, ks + (size_t)key_of[x] * Width<LPL>::KS_ROWS * 16 * Width<LPL>::L, x, live, tab2, tab2_stride, e1_be, nullptr,
+                          e2_be, e2_stride, out, nullptr, cs);
 }
 
 // ---------------------------------------------------------------------------------------
@@ -698,15 +726,14 @@ __global__ void RT_KERNEL(LPL) k_rt_mul(const u32* __restrict__ a_m, const u32* 
 // LDS per wave: operand slot + saved-base slot per number, one slot with R mod N.
 //   MONT: the result leaves as Montgomery limbs x_m[x][L] (< 2N, no exit product) -- the seeds of the forward differences
 // ---------------------------------------------------------------------------------------
+//   x, live : the share this quad works on and whether it stores its result (a dead quad is clamped to a live share by the
+//             caller); cm and t are wave-uniform, so one workgroup may serve a box of its own (k_rt_commit_eval_tiles)
 template <int LPL, bool MONT>
 __device__ __forceinline__ void rt_commit_eval_body(u32* lds, const u32* __restrict__ cm, int t, const int64_t* __restrict__ positions,
-                                                    int count, uint8_t* __restrict__ x_be, u32* __restrict__ x_m,
+                                                    int x, bool live, uint8_t* __restrict__ x_be, u32* __restrict__ x_m,
                                                     const modp_rt_consts* __restrict__ cs) {
   constexpr int L = Width<LPL>::L, SLOT = Width<LPL>::SLOT;
   const Lane ln = make_lane();
-  const int xi = blockIdx.x * RT_NUMS + (threadIdx.x >> 2);
-  const bool live = xi < count;
-  const int x = live ? xi : count - 1;
   u32* slot = lds + (threadIdx.x >> 2) * SLOT;
   u32* bslot = lds + (RT_NUMS + (threadIdx.x >> 2)) * SLOT;
   u32* oneslot = lds + 2 * RT_NUMS * SLOT;
@@ -788,7 +815,28 @@ template <int LPL>
 __global__ void RT_KERNEL_LDS2(LPL) k_rt_commit_eval(const u32* __restrict__ cm, int t, const int64_t* __restrict__ positions, int count,
                                                 uint8_t* __restrict__ x_be, const modp_rt_consts* __restrict__ cs) {
   __shared__ __attribute__((aligned(16))) u32 lds[(2 * RT_NUMS + 1) * Width<LPL>::SLOT];
-  rt_commit_eval_body<LPL, false>(lds, cm, t, positions, count, x_be, nullptr, cs);
+  const int xi = blockIdx.x * RT_NUMS + (threadIdx.x >> 2);
+  const bool live = xi < count;
+  rt_commit_eval_body<LPL, false>(lds, cm, t, positions, live ? xi : count - 1, live, x_be, nullptr, cs);
+}
+
+// X of a whole run of boxes in one launch (capi_modp_rt.inc, "Many boxes in one call"): workgroup w serves tile w, up to
+// RT_NUMS consecutive shares of ONE box, so the commitments and t of that box are wave-uniform.
+//   tiles  : [gridDim.x] of {box, first share of the tile in the run's concatenation, live shares (1 .. RT_NUMS), 0}
+//   boxes  : [boxes of the run] of {index of the box's first commitment in cm_all, t}
+//   cm_all : the commitments of every box of the run, concatenated, in Montgomery form
+// Quads at or beyond the tile's live count are dead lanes, clamped to the tile's last share.
+template <int LPL>
+__global__ void RT_KERNEL_LDS2(LPL) k_rt_commit_eval_tiles(const u32* __restrict__ cm_all, const uint4* __restrict__ tiles,
+                                                      const uint2* __restrict__ boxes, const int64_t* __restrict__ positions,
+                                                      uint8_t* __restrict__ x_be, const modp_rt_consts* __restrict__ cs) {
+  __shared__ __attribute__((aligned(16))) u32 lds[(2 * RT_NUMS + 1) * Width<LPL>::SLOT];
+  const uint4 tile = tiles[blockIdx.x];
+  const uint2 box = boxes[tile.x];
+  const int quad = threadIdx.x >> 2;
+  const bool live = quad < (int)tile.z;
+  rt_commit_eval_body<LPL, false>(lds, cm_all + (size_t)box.x * Width<LPL>::L, (int)box.y, positions,
+                                  (int)tile.y + (live ? quad : (int)tile.z - 1), live, x_be, nullptr, cs);
 }
 
 // Horner in Montgomery form over two sets of commitments in one launch: blockIdx.y = 0 evaluates cm (X at the seed positions),
@@ -798,7 +846,9 @@ __global__ void RT_KERNEL_LDS2(LPL) k_rt_commit_eval_mont(const u32* __restrict_
                                                      const int64_t* __restrict__ positions, int count, u32* __restrict__ x_m,
                                                      const modp_rt_consts* __restrict__ cs) {
   __shared__ __attribute__((aligned(16))) u32 lds[(2 * RT_NUMS + 1) * Width<LPL>::SLOT];
-  rt_commit_eval_body<LPL, true>(lds, blockIdx.y ? cm_inv : cm, t, positions, count, nullptr,
+  const int xi = blockIdx.x * RT_NUMS + (threadIdx.x >> 2);
+  const bool live = xi < count;
+  rt_commit_eval_body<LPL, true>(lds, blockIdx.y ? cm_inv : cm, t, positions, live ? xi : count - 1, live, nullptr,
                                  x_m + (size_t)blockIdx.y * count * Width<LPL>::L, cs);
 }
 
@@ -1103,6 +1153,31 @@ __global__ void RT_KERNEL(LPL) k_rt_modq_poly_eval(const u32* __restrict__ coef_
 // ---------------------------------------------------------------------------------------
 static inline int rt_grid(int count) { return (count + RT_NUMS - 1) / RT_NUMS; }
 
+#ifdef RT_WIDTH_FREE
+// ---------------------------------------------------------------------------------------
+// The challenge of each box of a run, written to every share of the box: c_out[first + i] = c_box[box] for the live shares i of
+// tile blockIdx.x (the tile table of k_rt_commit_eval_tiles).  Plain bytes moved as 32-bit words, eb a multiple of 4: no width,
+// so the unit that defines RT_WIDTH_FREE holds the one instance.
+// ---------------------------------------------------------------------------------------
+__global__ void __launch_bounds__(64) k_rt_spread_challenge(const u32* __restrict__ c_box, const uint4* __restrict__ tiles, int eb,
+                                                            u32* __restrict__ c_out) {
+  const uint4 tile = tiles[blockIdx.x];
+  const int words = eb / 4, total = (int)tile.z * words;
+  const u32* src = c_box + (size_t)tile.x * words;
+  u32* dst = c_out + (size_t)tile.y * words;
+  for (int i = threadIdx.x; i < total; i += 64) dst[i] = src[i % words];
+}
+
+extern "C" int modp_rt_launch_spread_challenge(const uint8_t* c_box, const uint32_t* tiles, int ntiles, int eb, uint8_t* c_out,
+                                               hipStream_t s) {
+  if (ntiles <= 0) return 0;
+  if (eb <= 0 || (eb & 3)) return (int)hipErrorInvalidValue;
+  hipLaunchKernelGGL(k_rt_spread_challenge, dim3(ntiles), dim3(64), 0, s, reinterpret_cast<const u32*>(c_box),
+                     reinterpret_cast<const uint4*>(tiles), eb, reinterpret_cast<u32*>(c_out));
+  return (int)hipGetLastError();
+}
+#endif  // RT_WIDTH_FREE
+
 #ifndef RT_FD_ONLY
 extern "C" int RT_FN(launch_to_mont)(int lpl, const uint8_t* in_be, int count, uint32_t* out_m, const modp_rt_consts* cs, hipStream_t s) {
   RT_ELSEWHERE(launch_to_mont, lpl, in_be, count, out_m, cs, s);
@@ -1173,6 +1248,16 @@ extern "C" int RT_FN(launch_keyset_exp)(int lpl, const uint32_t* ks, const uint3
   return (int)hipGetLastError();
 }
 
+extern "C" int RT_FN(launch_keyset_exp_idx)(int lpl, const uint32_t* ks, const uint32_t* key_of, const uint32_t* tab2, size_t tab2_stride,
+                                            const uint8_t* e1, const uint8_t* e2, size_t e2_stride, int count, uint8_t* out,
+                                            const modp_rt_consts* cs, hipStream_t s) {
+  RT_ELSEWHERE(launch_keyset_exp_idx, lpl, ks, key_of, tab2, tab2_stride, e1, e2, e2_stride, count, out, cs, s);
+  if (count <= 0) return 0;
+  RT_DISPATCH(lpl, k_rt_keyset_exp_idx, dim3(rt_grid(count)), dim3(64), 0, s, ks, key_of, tab2, tab2_stride, e1, e2, e2_stride, count, out,
+              cs);
+  return (int)hipGetLastError();
+}
+
 extern "C" int RT_FN(launch_twin_exp)(int lpl, const uint8_t* bases, const uint8_t* e1, const uint8_t* e2, int count, uint32_t* buckets,
                                       uint8_t* out1, uint8_t* out2, const modp_rt_consts* cs, hipStream_t s) {
   RT_ELSEWHERE(launch_twin_exp, lpl, bases, e1, e2, count, buckets, out1, out2, cs, s);
@@ -1195,6 +1280,15 @@ extern "C" int RT_FN(launch_commit_eval)(int lpl, const uint32_t* cm_m, int t, c
   RT_ELSEWHERE(launch_commit_eval, lpl, cm_m, t, positions, count, x_be, cs, s);
   if (count <= 0) return 0;
   RT_DISPATCH(lpl, k_rt_commit_eval, dim3(rt_grid(count)), dim3(64), 0, s, cm_m, t, positions, count, x_be, cs);
+  return (int)hipGetLastError();
+}
+
+extern "C" int RT_FN(launch_commit_eval_tiles)(int lpl, const uint32_t* cm_all_m, const uint32_t* tiles, int ntiles, const uint32_t* boxes,
+                                               const int64_t* positions, uint8_t* x_be, const modp_rt_consts* cs, hipStream_t s) {
+  RT_ELSEWHERE(launch_commit_eval_tiles, lpl, cm_all_m, tiles, ntiles, boxes, positions, x_be, cs, s);
+  if (ntiles <= 0) return 0;
+  RT_DISPATCH(lpl, k_rt_commit_eval_tiles, dim3(ntiles), dim3(64), 0, s, cm_all_m, reinterpret_cast<const uint4*>(tiles),
+              reinterpret_cast<const uint2*>(boxes), positions, x_be, cs);
   return (int)hipGetLastError();
 }
 

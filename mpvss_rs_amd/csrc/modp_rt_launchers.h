@@ -32,6 +32,11 @@ int MODP_RT_FN(launch_keyset_build)(int lpl, const uint8_t* keys_be, int count, 
 int MODP_RT_FN(launch_keyset_exp)(int lpl, const uint32_t* ks, const uint32_t* tab2, size_t tab2_stride, const uint8_t* e1a,
                               const uint8_t* e1b, const uint8_t* e2, size_t e2_stride, int count, uint8_t* out_a, uint8_t* out_b,
                               const modp_rt_consts* cs, hipStream_t s);
+/* out[x] = key_(key_of[x])^e1[x] * B2[x]^e2[x] mod q: modp_rt_launch_keyset_exp's first exponent set with the key of every share
+   named by its index in the set (ks: the rows of the set's FIRST key; key_of: `count` indices on the device) */
+int MODP_RT_FN(launch_keyset_exp_idx)(int lpl, const uint32_t* ks, const uint32_t* key_of, const uint32_t* tab2, size_t tab2_stride,
+                                  const uint8_t* e1, const uint8_t* e2, size_t e2_stride, int count, uint8_t* out,
+                                  const modp_rt_consts* cs, hipStream_t s);
 /* the same two results right to left with shared squarings (k_rt_twin_exp): bases as EB-byte values of any size, `buckets`
    a scratch of modp_rt_twin_scratch_bytes(lpl, count) bytes that holds exponent windows afterwards (the caller zeroes it) */
 int MODP_RT_FN(launch_twin_exp)(int lpl, const uint8_t* bases, const uint8_t* e1, const uint8_t* e2, int count, uint32_t* buckets,
@@ -41,6 +46,11 @@ int MODP_RT_FN(launch_mul)(int lpl, const uint32_t* a_m, const uint32_t* b_m, in
 /* X[x] = Horner in the exponent over the commitments cm_m ([t] numbers in Montgomery form) at i' = positions[x] mod (q-1) */
 int MODP_RT_FN(launch_commit_eval)(int lpl, const uint32_t* cm_m, int t, const int64_t* positions, int count, uint8_t* x_be,
                                const modp_rt_consts* cs, hipStream_t s);
+/* X of a run of boxes in one launch, one workgroup per tile (up to 16 consecutive shares of one box): tiles [ntiles][4] words
+   {box, first share in the concatenation, live shares, 0}, boxes [boxes][2] words {first commitment in cm_all_m, t}, cm_all_m the
+   commitments of all boxes in Montgomery form, positions and x_be over the concatenated shares */
+int MODP_RT_FN(launch_commit_eval_tiles)(int lpl, const uint32_t* cm_all_m, const uint32_t* tiles, int ntiles, const uint32_t* boxes,
+                                     const int64_t* positions, uint8_t* x_be, const modp_rt_consts* cs, hipStream_t s);
 /* the seeds of the forward differences: Horner in Montgomery form at `count` positions over cm_m (gridDim.y = 0) and over the
    inverted commitments cm_inv_m (1) in one launch; x_m [2][count][L], every number < 2N */
 int MODP_RT_FN(launch_commit_eval_mont)(int lpl, const uint32_t* cm_m, const uint32_t* cm_inv_m, int t, const int64_t* positions,

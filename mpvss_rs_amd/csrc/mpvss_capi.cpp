@@ -354,11 +354,16 @@ struct mpvss_ctx {
   unsigned long long rt_fd_calls = 0, rt_horner_calls = 0;   // chunks of X by either path (mpvss_modp_group_fd_stats)
   std::vector<uint8_t> rt_fd_inv_host;           // sources of asynchronous copies: they outlive the call's launches
   std::vector<int64_t> rt_fd_pos_host;
+  // a run of small boxes of mpvss_modp_group_verify_many (capi_modp_rt.inc, "Many boxes in one call"): the tile table, the per-box
+  // table, the per-share key indices, the boxes' challenges, the concatenated positions
+  DevBuf rt_run_tiles, rt_run_boxes, rt_run_keyof, rt_run_ch, rt_run_pos;
+  unsigned long long rt_many_groups = 0, rt_many_grouped_boxes = 0, rt_many_single_boxes = 0;   // mpvss_modp_group_verify_many_stats
   std::vector<DevBuf*> rt_all() {
     return {&rt_consts, &rt_in[0], &rt_in[1], &rt_in[2], &rt_in[3], &rt_in[4], &rt_in[5], &rt_out[0], &rt_out[1], &rt_out[2],
             &rt_tab1, &rt_tab2, &rt_tabg, &rt_cm, &rt_small[0], &rt_small[1], &rt_out_y, &rt_buckets,
             &rt_fd_inv, &rt_cm_inv, &rt_fd_pos, &rt_fd_seeds, &rt_fd_x, &rt_fd_park,
             &rt_consts_q, &rt_sc_coef, &rt_sc_p, &rt_sc_w, &rt_sc_c, &rt_sc_r,
+            &rt_run_tiles, &rt_run_boxes, &rt_run_keyof, &rt_run_ch, &rt_run_pos,
             &rt_comb[0].buf, &rt_comb[1].buf, &rt_comb[2].buf, &rt_comb[3].buf};
   }
   // fixed-base combs of run-time groups (rt_comb_for, capi_modp_rt.inc), used under `mu`: keyed by the bytes (q, base) -- a handle

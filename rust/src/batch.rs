@@ -3,7 +3,7 @@
 //! shape with `mpvss_ec_*` and 33 / 32-byte encodings (helpers at the bottom).
 //!
 //!   verify_distribution_shares   src/participant.rs:399-455  (= src/mpvss.rs:90-144)  -> mpvss_modp_verify_distribution
-//!   many boxes                   one call per dealer in the reference               -> mpvss_modp_verify_many
+//!   many boxes                   one call per dealer in the reference               -> mpvss_modp_verify_many  (run-time group: mpvss_modp_group_verify_many)
 //!   verify_share (n boxes)       src/participant.rs:361-386 -> src/dleq.rs:275-302   -> mpvss_modp_verify_shares
 //!   distribute_secret            src/participant.rs:160-286                          -> mpvss_modp_distribute (+ scalar side)
 //!   extract_secret_share (n)     src/participant.rs:294-353                          -> mpvss_modp_extract_shares  (run-time group: mpvss_modp_group_extract_shares)
@@ -88,7 +88,9 @@ pub fn verify_distribution_shares(group: &HipModpGroup, bx: &DistributionSharesB
 /// transcript hashers).  Boxes with a missing map entry get `false` without touching the GPU.
 pub fn verify_many(group: &HipModpGroup, boxes: &[&DistributionSharesBox<HipModpGroup>], depth: i32, hash_threads: i32)
     -> Result<Vec<bool>, EngineError> {
-    assert!(group.rt.is_none(), "batch::verify_many: RFC 3526 group 14 only (a run-time group offers verify_distribution_shares and verify_shares)");
+    if let Some(h) = group.rt_handle() {
+        return group_verify_many(group, h, boxes, hash_threads);
+    }
     let flats: Vec<Option<FlatBox>> = boxes.iter().map(|b| flatten(group, b)).collect();
     let mut descs = Vec::new();
     let mut index = Vec::new();
@@ -113,6 +115,36 @@ pub fn verify_many(group: &HipModpGroup, boxes: &[&DistributionSharesBox<HipModp
     let rc = unsafe {
         ffi::mpvss_modp_verify_many(group.engine.raw(), ffi::MPVSS_HOST, descs.as_ptr(), descs.len(), depth, hash_threads,
                                     verdicts.as_mut_ptr(), std::ptr::null_mut())
+    };
+    group.engine.check(rc)?;
+    let mut out = vec![false; boxes.len()];
+    for (k, i) in index.into_iter().enumerate() {
+        out[i] = verdicts[k] == 1;
+    }
+    Ok(out)
+}
+
+/// `verify_many` for a run-time group (HipModpGroup::init / with_modulus): mpvss_modp_group_verify_many verifies the boxes in one
+/// synchronous call, runs of small boxes as one batch on the GPU; `depth` has no meaning there.
+fn group_verify_many(group: &HipModpGroup, h: *const ffi::mpvss_modp_group, boxes: &[&DistributionSharesBox<HipModpGroup>],
+                     hash_threads: i32) -> Result<Vec<bool>, EngineError> {
+    let flats: Vec<Option<FlatBox>> = boxes.iter().map(|b| flatten(group, b)).collect();
+    let mut descs = Vec::new();
+    let mut index = Vec::new();
+    for (i, (f, b)) in flats.iter().zip(boxes).enumerate() {
+        if let Some(f) = f {
+            index.push(i);
+            descs.push(ffi::mpvss_modp_group_box {
+                commitments: f.commitments.as_ptr(), t: b.commitments.len(), positions: f.positions.as_ptr(),
+                pubkeys: f.pubkeys.as_ptr(), shares: f.shares.as_ptr(), responses: f.responses.as_ptr(), n: f.positions.len(),
+                challenge_host: f.challenge.as_ptr(), keyset: std::ptr::null(), key_offset: 0,
+            });
+        }
+    }
+    let mut verdicts = vec![0i32; descs.len()];
+    let rc = unsafe {
+        ffi::mpvss_modp_group_verify_many(group.engine.raw(), h, ffi::MPVSS_HOST, descs.as_ptr(), descs.len(), hash_threads,
+                                          verdicts.as_mut_ptr(), std::ptr::null_mut())
     };
     group.engine.check(rc)?;
     let mut out = vec![false; boxes.len()];

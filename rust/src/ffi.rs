@@ -48,6 +48,20 @@ pub struct mpvss_modp_box {
     pub keyset: *const mpvss_keyset,
     pub key_offset: usize,
 }
+/// one box of mpvss_modp_group_verify_many: mpvss_modp_box with a key set of the run-time group
+#[repr(C)]
+pub struct mpvss_modp_group_box {
+    pub commitments: *const u8,
+    pub t: usize,
+    pub positions: *const i64,
+    pub pubkeys: *const u8,
+    pub shares: *const u8,
+    pub responses: *const u8,
+    pub n: usize,
+    pub challenge_host: *const u8,
+    pub keyset: *const mpvss_modp_group_keyset,
+    pub key_offset: usize,
+}
 #[repr(C)]
 pub struct mpvss_ec_box {
     pub commitments: *const u8,
@@ -325,6 +339,10 @@ unsafe extern "C" {
                                         positions_host: *const i64, keyset: *const mpvss_modp_group_keyset, key_offset: usize,
                                         witnesses_host: *const u8, n: usize, x_out: *mut u8, y_out: *mut u8, a1_out: *mut u8,
                                         a2_out: *mut u8, digest32_out: *mut u8, challenge_out256: *mut u8, r_out: *mut u8) -> c_int;
+    pub fn mpvss_modp_group_verify_many(ctx: *mut mpvss_ctx, grp: *const mpvss_modp_group, space: c_int, boxes: *const mpvss_modp_group_box,
+                                        count: usize, hash_threads: c_int, verdicts: *mut c_int, digests32: *mut u8) -> c_int;
+    pub fn mpvss_modp_group_verify_many_stats(ctx: *mut mpvss_ctx, groups: *mut c_ulonglong, grouped_boxes: *mut c_ulonglong,
+                                              single_boxes: *mut c_ulonglong) -> c_int;
     // ---- hashing helpers
     pub fn mpvss_sha256(data: *const u8, len: usize, out32: *mut u8);
     pub fn mpvss_modp_hash_to_scalar(data: *const u8, len: usize, out256: *mut u8);
