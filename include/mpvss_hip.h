@@ -539,7 +539,8 @@ int mpvss_box_verify_wire(mpvss_ctx* ctx, const uint8_t* buf, size_t len, int* v
  * the one-call deal), extract_secret_share and reconstruct.  The scalar ring Z/(q-1) -- P(i), the responses, e2 = w / x -- runs
  * on host threads or, for a handle with odd (q-1)/2 >= 3 (every safe prime above 5), on the device: mpvss_ctx_set_rt_scalar and
  * "the scalar ring on the device" below.  Long-lived public keys can be registered as a key set ("Key sets of a run-time group"
- * below), and the boxes of a whole round verified in one call ("Many boxes in one call" below).  Not offered for a
+ * below), the boxes of a whole round verified in one call ("Many boxes in one call" below) and the secrets of a whole round
+ * reconstructed in one call ("Many secrets in one call" below).  Not offered for a
  * run-time group: the block / pipeline forms, the wire format, and the overlap of one run's hashing with the next run's GPU
  * work; moduli above 3072 bits are refused
  * with MPVSS_E_INVALID (4096 bits would overflow the product's 64-bit column accumulators). */
@@ -755,6 +756,37 @@ int mpvss_modp_group_verify_many(mpvss_ctx* ctx, const mpvss_modp_group* grp, in
                                  int hash_threads, int* verdicts, uint8_t* digests32);
 int mpvss_modp_group_verify_many_stats(mpvss_ctx* ctx, unsigned long long* groups, unsigned long long* grouped_boxes,
                                        unsigned long long* single_boxes);
+
+/* Many secrets in one call.  After verifying, a participant of a round reconstructs one secret per dealer, usually from the same
+ * responding participants.  For every secret i that mpvss_modp_group_reconstruct accepts, status[i] == MPVSS_OK and
+ * gs_out[i eb .. i eb + eb - 1] (eb = mpvss_modp_group_elem_bytes) and masks_out32[32 i .. 32 i + 31] (optional) are what that
+ * call gives for (positions_host, shares, m) on the same context, byte for byte, at every width and in both spaces; in device
+ * space the share buffers are left unchanged.  The Lagrange coefficients are computed once per distinct position list of the call
+ * (lists are equal when their sequences are: a permuted list is another list).  Runs of consecutive secrets of at most 16384
+ * shares each travel through the GPU as one batch of at most MPVSS_MAX_CHUNK shares, one workgroup per secret for the product;
+ * every longer secret, and a run of one, takes the one-secret path.
+ * shares live in `space`; positions_host, secrets, status, gs_out and masks_out32 are host memory.  The call is synchronous and
+ * holds the context lock like its one-secret sibling.  host_threads: up to that many host threads compute the Lagrange
+ * coefficients and the masks (clamped to 1..16; <= 0: the library chooses from the work of the call, at most 16, never by the
+ * machine's CPU count).
+ * ERRORS: count == 0 is MPVSS_OK; no context or no group, and secrets, status or gs_out NULL with count > 0, are MPVSS_E_INVALID
+ * and write no output.  A refused secret -- whatever the one-secret call answers with MPVSS_E_INVALID: a pointer NULL, m == 0,
+ * m above 0x7fffffff, a position below 1, duplicate positions, a coefficient whose reduced denominator has no inverse mod
+ * (q-1)/2, an even (q-1)/2, a share that is 0 mod q under a negative coefficient -- costs only itself: that code in status[i],
+ * zeros in gs_out[i] and in its mask, and the call goes on and returns MPVSS_OK.  A HIP error or a failed allocation ends the call
+ * with the code the one-secret call returns and leaves the context usable.
+ * mpvss_modp_group_reconstruct_many_stats: since the context was created, the grouped passes, the secrets that went through them
+ * and the secrets that took the one-secret path (refused secrets are in none); any pointer may be NULL, no context is
+ * MPVSS_E_INVALID. */
+typedef struct mpvss_modp_group_secret {
+  const int64_t* positions_host;   /* m positions, host memory in either space */
+  const uint8_t* shares;           /* m x element size, in `space` */
+  size_t m;
+} mpvss_modp_group_secret;
+int mpvss_modp_group_reconstruct_many(mpvss_ctx* ctx, const mpvss_modp_group* grp, int space, const mpvss_modp_group_secret* secrets,
+                                      size_t count, int host_threads, int* status, uint8_t* gs_out, uint8_t* masks_out32);
+int mpvss_modp_group_reconstruct_many_stats(mpvss_ctx* ctx, unsigned long long* passes, unsigned long long* grouped_secrets,
+                                            unsigned long long* single_secrets);
 
 /* ---- hashing helpers (host only; Group::hash_to_scalar, src/groups/modp.rs:142-148) ------ */
 

@@ -63,6 +63,7 @@ EXPORTED_SYMBOLS = (
     "mpvss_modp_group_keyset_bytes", "mpvss_modp_group_keyset_dual_exp", "mpvss_modp_group_keyset_twin_exp",
     "mpvss_modp_group_verify_distribution_keyset", "mpvss_modp_group_deal_keyset",
     "mpvss_modp_group_verify_many", "mpvss_modp_group_verify_many_stats",
+    "mpvss_modp_group_reconstruct_many", "mpvss_modp_group_reconstruct_many_stats",
 )
 
 GROUP_SECP256K1 = 1
@@ -89,6 +90,11 @@ class GroupBox(C.Structure):
     _fields_ = [("commitments", C.c_void_p), ("t", C.c_size_t), ("positions", C.c_void_p), ("pubkeys", C.c_void_p),
                 ("shares", C.c_void_p), ("responses", C.c_void_p), ("n", C.c_size_t), ("challenge_host", C.c_void_p),
                 ("keyset", C.c_void_p), ("key_offset", C.c_size_t)]
+
+
+class GroupSecret(C.Structure):
+    """struct mpvss_modp_group_secret"""
+    _fields_ = [("positions_host", C.c_void_p), ("shares", C.c_void_p), ("m", C.c_size_t)]
 
 
 class EcBox(C.Structure):
@@ -283,6 +289,9 @@ def load_library() -> C.CDLL:
     lib.mpvss_modp_group_verify_many.argtypes = [vp, vp, ci, C.POINTER(GroupBox), sz, ci, C.POINTER(ci), u8p]
     lib.mpvss_modp_group_verify_many_stats.argtypes = [vp, C.POINTER(C.c_ulonglong), C.POINTER(C.c_ulonglong),
                                                        C.POINTER(C.c_ulonglong)]
+    lib.mpvss_modp_group_reconstruct_many.argtypes = [vp, vp, ci, C.POINTER(GroupSecret), sz, ci, C.POINTER(ci), u8p, u8p]
+    lib.mpvss_modp_group_reconstruct_many_stats.argtypes = [vp, C.POINTER(C.c_ulonglong), C.POINTER(C.c_ulonglong),
+                                                            C.POINTER(C.c_ulonglong)]
     return lib
 
 
@@ -863,6 +872,54 @@ class Engine:
     def group_reconstruct_device(self, grp: "ModpGroup", positions: Sequence[int], shares_dev_ptr: int, m: int, want_mask: bool = True):
         """group_reconstruct with the m shares in HBM ([m][elem_bytes] bytes, left unchanged); positions stay host memory"""
         return self._group_reconstruct(grp, MPVSS_DEVICE, positions, C.c_void_p(shares_dev_ptr), m, want_mask)
+
+    # ---- many secrets of a run-time group in one call ----------------------------------------------------------------------
+    def _group_reconstruct_many(self, grp: "ModpGroup", space: int, arr, count: int, host_threads: int, want_masks: bool):
+        EB = grp.elem_bytes
+        status = (C.c_int * max(count, 1))()
+        kg, pg = _out(count * EB)
+        km, pm = _out(32 * count) if want_masks else (None, None)
+        self._check(self.lib.mpvss_modp_group_reconstruct_many(self.ctx, grp.handle, space, arr, count, int(host_threads), status, pg,
+                                                               pm), "group_reconstruct_many")
+        gs = bytes(kg)
+        masks = bytes(km) if want_masks else None
+        return [(int(status[i]), gs[i * EB:(i + 1) * EB], masks[32 * i:32 * i + 32] if want_masks else None) for i in range(count)]
+
+    def group_reconstruct_many(self, grp: "ModpGroup", secrets: Sequence[dict], host_threads: int = 0, want_masks: bool = True):
+        """secrets: dicts with positions (a sequence of int) and shares (host bytes); None: a null pointer.  Returns
+        [(status, G^s, mask)] in the order given: for status 0 what group_reconstruct gives secret by secret, the Lagrange
+        coefficients computed once per distinct position list and small secrets travelling in groups; a refused secret has
+        status -1, zeros for G^s and a mask of zeros."""
+        EB = grp.elem_bytes
+        keep, arr = [], (GroupSecret * max(len(secrets), 1))()
+        for i, s in enumerate(secrets):
+            positions, shares = s.get("positions"), s.get("shares")
+            m = len(positions) if positions is not None else len(shares or b"") // EB
+            pos = (C.c_int64 * max(m, 1))(*positions) if positions is not None else None
+            ks, ps = _buf(shares or None)
+            keep.append((pos, ks))
+            arr[i] = GroupSecret(C.cast(pos, C.c_void_p) if pos is not None else None, ps, m)
+        return self._group_reconstruct_many(grp, MPVSS_HOST, arr, len(secrets), host_threads, want_masks)
+
+    def group_reconstruct_many_device(self, grp: "ModpGroup", secrets: Sequence[dict], host_threads: int = 0, want_masks: bool = True):
+        """the same with the shares of every secret in HBM ([m][elem_bytes] bytes, left unchanged): dicts with positions (host),
+        shares_ptr and m"""
+        keep, arr = [], (GroupSecret * max(len(secrets), 1))()
+        for i, s in enumerate(secrets):
+            positions = s.get("positions")
+            m = int(s["m"])
+            pos = (C.c_int64 * max(len(positions), 1))(*positions) if positions is not None else None
+            keep.append(pos)
+            arr[i] = GroupSecret(C.cast(pos, C.c_void_p) if pos is not None else None,
+                                 C.c_void_p(s["shares_ptr"]) if s.get("shares_ptr") else None, m)
+        return self._group_reconstruct_many(grp, MPVSS_DEVICE, arr, len(secrets), host_threads, want_masks)
+
+    def group_reconstruct_many_stats(self) -> dict:
+        """since the context was created: grouped passes, secrets that went through them, secrets that took the one-secret path"""
+        p, g, s = C.c_ulonglong(0), C.c_ulonglong(0), C.c_ulonglong(0)
+        self._check(self.lib.mpvss_modp_group_reconstruct_many_stats(self.ctx, C.byref(p), C.byref(g), C.byref(s)),
+                    "group_reconstruct_many_stats")
+        return {"passes": int(p.value), "grouped_secrets": int(g.value), "single_secrets": int(s.value)}
 
     # ---- sharded verification (one engine per GPU; see mpvss_rs_amd/sharding.py)
     def verify_block_compute(self, commitments: bytes, positions: Sequence[int], pubkeys: bytes, shares: bytes,

@@ -7,8 +7,8 @@
 // (below) for the device, the constants, the chunk loop, the choice of space, the copies back and the wiping of secrets,
 // and in between only what is its own -- which buffers its arrays use, which of them are secret, what it launches and
 // what it hashes.  The launch decisions (rt_comb_for, rt_dleq_dev, rt_commit_eval_dev with rt_fd_prepare and
-// rt_fd_positions_ok, rt_twin_dev, rt_fixed_base_dev, rt_scalar_on_device, rt_product_tree, and the grouping of small boxes in
-// mpvss_modp_group_verify_many) are single places of their own.
+// rt_fd_positions_ok, rt_twin_dev, rt_fixed_base_dev, rt_scalar_on_device, rt_product_tree, the grouping of small boxes in
+// mpvss_modp_group_verify_many and that of secrets in mpvss_modp_group_reconstruct_many) are single places of their own.
 
 constexpr size_t RT_EB_MAX = FRAME_EB_MAX;     // the widest element / scalar of a handle (mpvss_modp_group_create_wide): 384 bytes
 
@@ -1467,43 +1467,71 @@ extern "C" int mpvss_modp_group_extract_shares(mpvss_ctx* ctx, const mpvss_modp_
   return f.end();
 }
 
+namespace {
+
+// lambda_i of a position list as the exponent of S_i: |lambda_i| mod (q-1)/2 in lowest terms (lagrange_coefficient_at_zero), and
+// (q-1) - |lambda_i| for a negative coefficient of nonzero magnitude.  *neg: the sign, which the zero-share check needs.  False:
+// duplicate positions, or a denominator that has no inverse even in lowest terms.
+bool rt_lagrange_exponent(const mpvss_modp_group* grp, const int64_t* positions, size_t m, size_t i, uint8_t* exp_out, char* neg) {
+  return rt_rings(grp, [&](const auto& R) {
+    constexpr int NW = RT_NW(R);
+    uint64_t e[NW];
+    if (!lagrange_coefficient_at_zero<NW>(R.sub, positions, m, i, e, neg)) return false;
+    if (*neg) {
+      uint64_t o = 0;
+      for (int k = 0; k < NW; ++k) o |= e[k];
+      if (o) hsc::sub_n<NW>(e, R.ord.m, e);
+    }
+    hsc::to_bytes<NW>(exp_out, e, true);
+    return true;
+  });
+}
+
+// int_BE(SHA256(element_to_bytes(G^s))) mod q (participant.rs:512-515): the reduction matters for q below 2^256
+void rt_secret_mask(const mpvss_modp_group* grp, const uint8_t* gs, uint8_t* mask_out32) {
+  const size_t EB = grp->eb;
+  uint8_t hb[RT_EB_MAX];
+  memset(hb, 0, EB - 32);
+  mpvss::Sha256 h;
+  frame_min_bytes_update(h, gs, EB);
+  h.final(hb + EB - 32);
+  rt_rings(grp, [&](const auto& R) {
+    constexpr int NW = RT_NW(R);
+    uint64_t x[NW];
+    hsc::from_bytes<NW>(x, hb, true);
+    R.mod.reduce1(x);
+    hsc::to_bytes<NW>(hb, x, true);
+  });
+  memcpy(mask_out32, hb + EB - 32, 32);
+}
+
 // participant.rs:462-561: G^s = prod_i S_i^lambda_i.  Lagrange exponents mod (q-1)/2 with the sign kept aside (:526-561); a
 // negative coefficient inverts the factor, and S^-e = S^((q-1) - e) for every unit S mod a prime q, so the m powers run in one
 // k_rt_dual_exp launch with no inversion at all.  (q-1)/2 must be odd (every safe prime above 5).  A coefficient is reduced to
 // lowest terms before its denominator is inverted (:546-553), which matters only for a (q-1)/2 small enough to divide a position
 // or a difference of two: lagrange_at_zero does so where the raw denominator has no inverse.
-extern "C" int mpvss_modp_group_reconstruct(mpvss_ctx* ctx, const mpvss_modp_group* grp, int space, const int64_t* positions_host,
-                                            const uint8_t* shares, size_t m, uint8_t* gs_out256, uint8_t* mask_out32) {
-  if (!ctx) return MPVSS_E_INVALID;
-  std::lock_guard<std::mutex> lk(ctx->mu);
-  if (rt_bad_group(grp)) return fail(ctx, MPVSS_E_INVALID, "group_reconstruct: no group");
+// The body of mpvss_modp_group_reconstruct (context lock held, the group checked).  exps_pre / neg_pre: the m exponents and signs
+// when the caller has them already (mpvss_modp_group_reconstruct_many computed them with the call's other position lists).
+int rt_reconstruct_locked(mpvss_ctx* ctx, const mpvss_modp_group* grp, int space, const int64_t* positions_host, const uint8_t* shares,
+                          size_t m, uint8_t* gs_out256, uint8_t* mask_out32, const uint8_t* exps_pre, const char* neg_pre) {
   const size_t EB = grp->eb;
   if (!positions_host || !shares || m == 0 || !gs_out256 || m > 0x7fffffff)
     return fail(ctx, MPVSS_E_INVALID, "group_reconstruct: bad argument");
   for (size_t i = 0; i < m; ++i)
     if (positions_host[i] < 1) return fail(ctx, MPVSS_E_INVALID, "group_reconstruct: positions must be >= 1 (util.rs:47-64)");
-  std::vector<char> neg;
-  std::vector<uint8_t> exps(m * EB), hs;
+  std::vector<char> neg_own;
+  std::vector<uint8_t> exps_own, hs;
   RtCall f(ctx, grp, space);
   RET_IF(f.begin());
-  const bool lagrange_ok = rt_rings(grp, [&](const auto& R) {
-    constexpr int NW = RT_NW(R);
-    std::vector<hsc::Num<NW>> mag;
-    if (!lagrange_at_zero<NW>(R.sub, positions_host, m, mag, neg, false)) return false;
-    for (size_t i = 0; i < m; ++i) {
-      uint64_t e[NW];
-      memcpy(e, mag[i].v, sizeof(e));
-      if (neg[i]) {
-        uint64_t o = 0;
-        for (int k = 0; k < NW; ++k) o |= e[k];
-        if (o) hsc::sub_n<NW>(e, R.ord.m, e);
-      }
-      hsc::to_bytes<NW>(exps.data() + i * EB, e, true);
-    }
-    return true;
-  });
-  if (!lagrange_ok)
-    return fail(ctx, MPVSS_E_INVALID, "group_reconstruct: duplicate positions, or a Lagrange coefficient whose denominator in lowest terms has no inverse mod (q-1)/2");
+  if (!exps_pre) {
+    neg_own.assign(m, 0);
+    exps_own.resize(m * EB);
+    for (size_t i = 0; i < m; ++i)
+      if (!rt_lagrange_exponent(grp, positions_host, m, i, exps_own.data() + i * EB, &neg_own[i]))
+        return fail(ctx, MPVSS_E_INVALID, "group_reconstruct: duplicate positions, or a Lagrange coefficient whose denominator in lowest terms has no inverse mod (q-1)/2");
+  }
+  const uint8_t* exps = exps_pre ? exps_pre : exps_own.data();
+  const char* neg = exps_pre ? neg_pre : neg_own.data();
   // a share that is 0 mod q has no inverse: the reference returns None when its coefficient is negative (:551-553)
   const uint8_t* S = f.host_view(shares, 0, m, hs);
   RET_IF(f.host_ready());
@@ -1511,7 +1539,7 @@ extern "C" int mpvss_modp_group_reconstruct(mpvss_ctx* ctx, const mpvss_modp_gro
     if (neg[i] && rt_zero_mod_q(grp, S + i * EB))
       return fail(ctx, MPVSS_E_INVALID, "group_reconstruct: a share is 0 mod q and has no inverse");
   const uint8_t* dS = f.in(shares, 0, m, ctx->rt_in[0], RtCall::Public);
-  const uint8_t* dE = f.in_host(exps.data(), m, ctx->rt_in[1], RtCall::Public);
+  const uint8_t* dE = f.in_host(exps, m, ctx->rt_in[1], RtCall::Public);
   uint8_t* dF = f.work(ctx->rt_out[0], m);
   RET_IF(f.rc);
   const uint32_t* tb;
@@ -1523,23 +1551,18 @@ extern "C" int mpvss_modp_group_reconstruct(mpvss_ctx* ctx, const mpvss_modp_gro
   f.to_host(dF, 1, gs);
   RET_IF(f.settle());
   memcpy(gs_out256, gs.data(), EB);
-  if (mask_out32) {
-    // int_BE(SHA256(element_to_bytes(G^s))) mod q (:512-515): the reduction matters for q below 2^256
-    uint8_t hb[RT_EB_MAX];
-    memset(hb, 0, EB - 32);
-    mpvss::Sha256 h;
-    frame_min_bytes_update(h, gs.data(), EB);
-    h.final(hb + EB - 32);
-    rt_rings(grp, [&](const auto& R) {
-      constexpr int NW = RT_NW(R);
-      uint64_t x[NW];
-      hsc::from_bytes<NW>(x, hb, true);
-      R.mod.reduce1(x);
-      hsc::to_bytes<NW>(hb, x, true);
-    });
-    memcpy(mask_out32, hb + EB - 32, 32);
-  }
+  if (mask_out32) rt_secret_mask(grp, gs.data(), mask_out32);
   return f.end();
+}
+
+}  // namespace
+
+extern "C" int mpvss_modp_group_reconstruct(mpvss_ctx* ctx, const mpvss_modp_group* grp, int space, const int64_t* positions_host,
+                                            const uint8_t* shares, size_t m, uint8_t* gs_out256, uint8_t* mask_out32) {
+  if (!ctx) return MPVSS_E_INVALID;
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  if (rt_bad_group(grp)) return fail(ctx, MPVSS_E_INVALID, "group_reconstruct: no group");
+  return rt_reconstruct_locked(ctx, grp, space, positions_host, shares, m, gs_out256, mask_out32, nullptr, nullptr);
 }
 
 // =====================================================================================================================
@@ -2049,5 +2072,226 @@ extern "C" int mpvss_modp_group_verify_many_stats(mpvss_ctx* ctx, unsigned long 
   if (groups) *groups = ctx->rt_many_groups;
   if (grouped_boxes) *grouped_boxes = ctx->rt_many_grouped_boxes;
   if (single_boxes) *single_boxes = ctx->rt_many_single_boxes;
+  return MPVSS_OK;
+}
+
+// =====================================================================================================================
+// Many secrets in one call (DESIGN section 13, "Many secrets in one call"): mpvss_modp_group_reconstruct_many.  After verifying, a
+// participant of a PVSS round reconstructs one secret per dealer, usually from the same responding participants: one secret per
+// call is the latency of a chain of Montgomery products plus ceil(log2 m) rounds of the pairwise product, on one or two waves,
+// and the same m Lagrange coefficients computed again by every call.  Here the coefficients are computed once per distinct
+// position list, and runs of secrets travel as ONE dense concatenation of shares through the launches of one secret, the
+// pairwise rounds replaced by one k_rt_product_segments launch (one workgroup per secret).  THE grouping decision is in
+// mpvss_modp_group_reconstruct_many below.
+// =====================================================================================================================
+namespace {
+
+enum RtSecretKind { RT_SECRET_REFUSED, RT_SECRET_GROUPED, RT_SECRET_SINGLE };
+
+// what the host knows of a secret before anything is launched: its kind, and where its exponents and signs start in the call's
+// arrays (the coefficients of its position list; npos for a secret that computes its own)
+struct RtSecretPlan {
+  RtSecretKind kind = RT_SECRET_REFUSED;
+  size_t coef = (size_t)-1;
+};
+
+// host threads of a call: what the caller asked for, or one per `per_thread` items of work; 1 .. 16, never the machine's count
+int rt_many_threads(int requested, size_t work, size_t per_thread) {
+  const size_t nth = requested > 0 ? (size_t)requested : work / per_thread;
+  return (int)std::min<size_t>(std::max<size_t>(nth, 1), 16);
+}
+
+// a grouped pass: the secrets run[0 .. B) (indices into `secrets`, all RT_SECRET_GROUPED), shares in all <= MAX_CHUNK.  The
+// launches of one secret over the concatenation, then one k_rt_product_segments launch and one settle.  A secret with a share that
+// is 0 mod q under a negative coefficient is refused here (the one copy back of a pass in device space shows it): its powers run
+// with the others, its result is dropped.
+int rt_reconstruct_pass(mpvss_ctx* ctx, const mpvss_modp_group* grp, int space, const mpvss_modp_group_secret* secrets,
+                        const std::vector<size_t>& run, const std::vector<RtSecretPlan>& plan, const uint8_t* exps, const char* negs,
+                        int host_threads, int* status, uint8_t* gs_out, uint8_t* masks_out32) {
+  const size_t B = run.size(), EB = grp->eb;
+  std::vector<uint32_t> segs(2 * B);                                // {first factor, m} of every secret
+  std::vector<size_t> first(B + 1);
+  size_t S = 0;
+  for (size_t k = 0; k < B; ++k) {
+    first[k] = S;
+    segs[2 * k] = (uint32_t)S;
+    segs[2 * k + 1] = (uint32_t)secrets[run[k]].m;
+    S += secrets[run[k]].m;
+  }
+  first[B] = S;
+  // host sources of asynchronous copies and the results read back: declared before the frame, whose way out drains the stream
+  std::vector<uint8_t> g_sh, g_exp(S * EB), h_sh, h_gs;
+  for (size_t k = 0; k < B; ++k) memcpy(g_exp.data() + first[k] * EB, exps + plan[run[k]].coef * EB, secrets[run[k]].m * EB);
+  RtCall f(ctx, grp, space);
+  struct Drain {            // no copy out of (or into) the vectors above outlives them, whichever way the pass ends
+    mpvss_ctx* c;
+    ~Drain() { (void)hipStreamSynchronize(c->stream); }
+  } drain{ctx};
+  RET_IF(f.begin());
+  RET_IF(rt_run_gather(ctx, space, B, S * EB, ctx->rt_in[0], g_sh, [&](size_t k, const void** src, size_t* bytes) {
+    *src = secrets[run[k]].shares;
+    *bytes = secrets[run[k]].m * EB;
+  }));
+  const uint8_t* dS = (const uint8_t*)ctx->rt_in[0].p;
+  // a share that is 0 mod q has no inverse: the reference returns None when its coefficient is negative (:551-553)
+  const uint8_t* Sv = g_sh.data();
+  if (space == MPVSS_DEVICE) {
+    f.to_host(dS, S, h_sh);
+    RET_IF(f.host_ready());
+    Sv = h_sh.data();
+  }
+  std::vector<char> refused(B, 0);
+  size_t good = 0;
+  for (size_t k = 0; k < B; ++k) {
+    const char* neg = negs + plan[run[k]].coef;
+    for (size_t i = 0; i < secrets[run[k]].m && !refused[k]; ++i)
+      if (neg[i] && rt_zero_mod_q(grp, Sv + (first[k] + i) * EB)) refused[k] = 1;
+    if (!refused[k]) ++good;
+  }
+  const uint8_t* dE = f.in_host(g_exp.data(), S, ctx->rt_in[1], RtCall::Public);
+  uint8_t* dF = f.work(ctx->rt_out[0], S);
+  uint8_t* dG = f.work(ctx->rt_out[1], B);
+  RET_IF(f.rc);
+  RET_IF(ensure(ctx, ctx->rt_run_boxes, segs.size() * 4));
+  HIPCHK(ctx, hipMemcpyAsync(ctx->rt_run_boxes.p, segs.data(), segs.size() * 4, hipMemcpyHostToDevice, ctx->stream));
+  RET_IF(ensure(ctx, ctx->rt_tab1, S * rt_L(grp) * 4));
+  const uint32_t* tb;
+  RET_IF(rt_tables(ctx, grp, f.dc, dS, EB, S, ctx->rt_tab2, &tb));
+  TIMED_LAUNCH(ctx, 3, modp_rt_launch_dual_exp(grp->lpl, tb, 16 * rt_L(grp), nullptr, 0, dE, EB, nullptr, 0, (int)S, dF, f.dc,
+                                               ctx->stream));                                          // S_i^lambda_i, every secret
+  LAUNCHCHK(ctx, modp_rt_launch_to_mont(grp->lpl, dF, (int)S, (uint32_t*)ctx->rt_tab1.p, f.dc, ctx->stream));
+  LAUNCHCHK(ctx, modp_rt_launch_product_segments(grp->lpl, (const uint32_t*)ctx->rt_tab1.p, (const uint32_t*)ctx->rt_run_boxes.p, (int)B,
+                                                 dG, f.dc, ctx->stream));                              // one product per secret
+  f.to_host(dG, B, h_gs);
+  RET_IF(f.settle());
+  hsc::parallel_for(B, rt_many_threads(host_threads, B, 256), [&](size_t lo, size_t hi) {
+    for (size_t k = lo; k < hi; ++k) {
+      if (refused[k]) continue;
+      const size_t i = run[k];
+      memcpy(gs_out + i * EB, h_gs.data() + k * EB, EB);
+      if (masks_out32) rt_secret_mask(grp, h_gs.data() + k * EB, masks_out32 + 32 * i);
+      status[i] = MPVSS_OK;
+    }
+  });
+  for (size_t k = 0; k < B; ++k)
+    if (refused[k]) status[run[k]] = MPVSS_E_INVALID;
+  if (good) {
+    ++ctx->rt_rec_passes;
+    ctx->rt_rec_grouped_secrets += good;
+  }
+  return f.end();
+}
+
+}  // namespace
+
+extern "C" int mpvss_modp_group_reconstruct_many(mpvss_ctx* ctx, const mpvss_modp_group* grp, int space,
+                                                 const mpvss_modp_group_secret* secrets, size_t count, int host_threads, int* status,
+                                                 uint8_t* gs_out, uint8_t* masks_out32) {
+  if (!ctx) return MPVSS_E_INVALID;
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  if (rt_bad_group(grp)) return fail(ctx, MPVSS_E_INVALID, "group_reconstruct_many: no group");
+  if (count == 0) return MPVSS_OK;
+  if (!secrets || !status || !gs_out) return fail(ctx, MPVSS_E_INVALID, "group_reconstruct_many: bad argument");
+  const size_t EB = grp->eb;
+  // a refused secret has no result: its status, zeros in gs and in its mask.  Every secret is refused until it has its result.
+  for (size_t i = 0; i < count; ++i) status[i] = MPVSS_E_INVALID;
+  memset(gs_out, 0, count * EB);
+  if (masks_out32) memset(masks_out32, 0, 32 * count);
+
+  // the arguments of every secret, as the one-secret call judges them; then the Lagrange exponents ONCE per distinct position
+  // list -- the sequences equal element by element: a permuted list is another list, coefficients belong to indices -- of the
+  // secrets that may travel in a pass (a secret too long for one computes its own on the one-secret path)
+  std::vector<RtSecretPlan> plan(count);
+  std::map<std::vector<int64_t>, size_t> lists;          // position list -> its index
+  std::vector<const int64_t*> list_pos;
+  std::vector<size_t> list_m, list_first, list_of(count, (size_t)-1);
+  size_t coefs = 0;
+  for (size_t i = 0; i < count; ++i) {
+    const mpvss_modp_group_secret& s = secrets[i];
+    if (!s.positions_host || !s.shares || s.m == 0 || s.m > 0x7fffffff) continue;
+    bool ok = true;
+    for (size_t k = 0; k < s.m && ok; ++k) ok = s.positions_host[k] >= 1;
+    if (!ok) continue;
+    if (s.m > RT_GROUP_BOX_MAX || s.m > MAX_CHUNK) {
+      plan[i].kind = RT_SECRET_SINGLE;
+      continue;
+    }
+    plan[i].kind = RT_SECRET_GROUPED;
+    const auto it = lists.emplace(std::vector<int64_t>(s.positions_host, s.positions_host + s.m), list_pos.size());
+    if (it.second) {
+      list_pos.push_back(s.positions_host);
+      list_m.push_back(s.m);
+      list_first.push_back(coefs);
+      coefs += s.m;
+    }
+    list_of[i] = it.first->second;
+  }
+  lists.clear();
+  std::vector<uint8_t> exps(coefs * EB);
+  std::vector<char> negs(coefs, 0), coef_ok(coefs, 0);
+  // a coefficient costs m small products and one inversion at the modulus' width: a thread per 64 of them when the library chooses
+  hsc::parallel_for(coefs, rt_many_threads(host_threads, coefs, 64), [&](size_t lo, size_t hi) {
+    size_t l = std::upper_bound(list_first.begin(), list_first.end(), lo) - list_first.begin() - 1;
+    for (size_t c = lo; c < hi; ++c) {
+      while (l + 1 < list_first.size() && list_first[l + 1] <= c) ++l;
+      coef_ok[c] = rt_lagrange_exponent(grp, list_pos[l], list_m[l], c - list_first[l], exps.data() + c * EB, &negs[c]) ? 1 : 0;
+    }
+  });
+  for (size_t i = 0; i < count; ++i) {
+    if (plan[i].kind != RT_SECRET_GROUPED) continue;
+    const size_t l = list_of[i];
+    plan[i].coef = list_first[l];
+    // duplicate positions, or a denominator without inverse (an even (q-1)/2 among the causes): refused
+    if (std::find(coef_ok.begin() + list_first[l], coef_ok.begin() + list_first[l] + list_m[l], 0) != coef_ok.begin() + list_first[l] + list_m[l])
+      plan[i].kind = RT_SECRET_REFUSED;
+  }
+
+  // THE grouping decision: a pass is a maximal stretch of consecutive grouped secrets that hold at most MAX_CHUNK shares together,
+  // cut only at secret boundaries.  Refused secrets are settled above and do not end a pass; a pass of one secret takes the
+  // one-secret path, like every secret too long for a pass.  A code of the one-secret path other than MPVSS_E_INVALID (which
+  // refuses that secret alone) ends the call.
+  auto single = [&](size_t i) -> int {
+    const mpvss_modp_group_secret& s = secrets[i];
+    const bool pre = plan[i].coef != (size_t)-1;
+    const int rc = rt_reconstruct_locked(ctx, grp, space, s.positions_host, s.shares, s.m, gs_out + i * EB,
+                                         masks_out32 ? masks_out32 + 32 * i : nullptr, pre ? exps.data() + plan[i].coef * EB : nullptr,
+                                         pre ? negs.data() + plan[i].coef : nullptr);
+    if (rc == MPVSS_E_INVALID) return MPVSS_OK;
+    RET_IF(rc);
+    status[i] = MPVSS_OK;
+    ++ctx->rt_rec_single_secrets;
+    return MPVSS_OK;
+  };
+  std::vector<size_t> run;
+  size_t run_shares = 0;
+  auto flush = [&]() -> int {
+    int rc = MPVSS_OK;
+    if (run.size() == 1) rc = single(run[0]);
+    else if (run.size() > 1) rc = rt_reconstruct_pass(ctx, grp, space, secrets, run, plan, exps.data(), negs.data(), host_threads, status, gs_out, masks_out32);
+    run.clear();
+    run_shares = 0;
+    return rc;
+  };
+  for (size_t i = 0; i < count; ++i) {
+    if (plan[i].kind == RT_SECRET_REFUSED) continue;
+    if (plan[i].kind == RT_SECRET_SINGLE) {
+      RET_IF(flush());
+      RET_IF(single(i));
+      continue;
+    }
+    if (!run.empty() && run_shares + secrets[i].m > MAX_CHUNK) RET_IF(flush());
+    run.push_back(i);
+    run_shares += secrets[i].m;
+  }
+  return flush();
+}
+
+extern "C" int mpvss_modp_group_reconstruct_many_stats(mpvss_ctx* ctx, unsigned long long* passes, unsigned long long* grouped_secrets,
+                                                       unsigned long long* single_secrets) {
+  if (!ctx) return MPVSS_E_INVALID;
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  if (passes) *passes = ctx->rt_rec_passes;
+  if (grouped_secrets) *grouped_secrets = ctx->rt_rec_grouped_secrets;
+  if (single_secrets) *single_secrets = ctx->rt_rec_single_secrets;
   return MPVSS_OK;
 }

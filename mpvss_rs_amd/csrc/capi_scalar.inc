@@ -189,34 +189,41 @@ bool lagrange_reduced_magnitude(const Mod& M, const int64_t* pos, size_t m, size
 // denominator gives the value of the reduced fraction as it stands (the gcd divides it, so the gcd is a unit too); only a
 // denominator without inverse goes through lagrange_reduced_magnitude.  Over the prime moduli of the fixed groups (all above 2^63)
 // every denominator is a unit.
+// One coefficient, lambda_i: the coefficients of a position list are independent of each other, so a caller with many of them may
+// spread them over host threads (mpvss_modp_group_reconstruct_many).
+template <int N, class Mod>
+bool lagrange_coefficient_at_zero(const Mod& M, const int64_t* pos, size_t m, size_t i, uint64_t* mag, char* neg) {
+  uint64_t num[N], den[N], one[N];
+  memset(one, 0, sizeof(one));
+  one[0] = 1;
+  memcpy(num, one, sizeof(one));
+  memcpy(den, one, sizeof(one));
+  const uint64_t zero[N] = {0};
+  bool negative = false;
+  for (size_t j = 0; j < m; ++j) {
+    if (j == i) continue;
+    if (pos[j] == pos[i]) return false;
+    const uint64_t xj = (uint64_t)pos[j];           // Scalar::from(j as u64) / BigInt j >= 1
+    M.muladd_small(num, num, xj, zero);
+    const int64_t diff = pos[j] - pos[i];
+    if (diff < 0) negative = !negative;
+    M.muladd_small(den, den, (uint64_t)(diff < 0 ? -diff : diff), zero);
+  }
+  uint64_t inv[N];
+  if (M.invert(inv, den)) M.mulmod(mag, num, inv);
+  else if (!lagrange_reduced_magnitude<N>(M, pos, m, i, mag)) return false;
+  *neg = negative ? 1 : 0;
+  return true;
+}
+
 template <int N, class Mod>
 bool lagrange_at_zero(const Mod& M, const int64_t* pos, size_t m, std::vector<hsc::Num<N>>& mag, std::vector<char>& neg,
                       bool positions_as_u64) {
+  (void)positions_as_u64;
   mag.resize(m);
   neg.assign(m, 0);
-  for (size_t i = 0; i < m; ++i) {
-    uint64_t num[N], den[N], one[N];
-    memset(one, 0, sizeof(one));
-    one[0] = 1;
-    memcpy(num, one, sizeof(one));
-    memcpy(den, one, sizeof(one));
-    const uint64_t zero[N] = {0};
-    bool negative = false;
-    for (size_t j = 0; j < m; ++j) {
-      if (j == i) continue;
-      if (pos[j] == pos[i]) return false;
-      const uint64_t xj = (uint64_t)pos[j];           // Scalar::from(j as u64) / BigInt j >= 1
-      M.muladd_small(num, num, xj, zero);
-      const int64_t diff = pos[j] - pos[i];
-      (void)positions_as_u64;
-      if (diff < 0) negative = !negative;
-      M.muladd_small(den, den, (uint64_t)(diff < 0 ? -diff : diff), zero);
-    }
-    uint64_t inv[N];
-    if (M.invert(inv, den)) M.mulmod(mag[i].v, num, inv);
-    else if (!lagrange_reduced_magnitude<N>(M, pos, m, i, mag[i].v)) return false;
-    neg[i] = negative ? 1 : 0;
-  }
+  for (size_t i = 0; i < m; ++i)
+    if (!lagrange_coefficient_at_zero<N>(M, pos, m, i, mag[i].v, &neg[i])) return false;
   return true;
 }
 

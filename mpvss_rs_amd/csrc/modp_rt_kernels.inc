@@ -9,6 +9,7 @@
 //   DLEQ verifier commitments a = g1^r h1^c      (src/dleq.rs:66-84)               k_rt_dual_exp (two tables)
 //   X_i = prod_j C_j^(i^j mod (q-1))             (src/participant.rs:423-434)      k_rt_commit_eval
 //   X_i of the small boxes of a whole round, one launch   (one call per box in the reference)  k_rt_commit_eval_tiles, k_rt_spread_challenge
+//   G^s = prod_i S_i^lambda_i of the secrets of a whole round, one launch (src/participant.rs:503-505)   k_rt_product_segments
 //   P(i), r_i = w_i - P(i) c, w_i / x_i in Z/(q-1) (src/polynomial.rs:50-58, src/dleq.rs:42-50, modp.rs:180-182)
 //                                                                                  k_rt_modq_poly_eval, _responses, _mul
 //   y_i^r_i Y_i^c, y_i^P(i), y_i^w_i for long-lived keys    (src/participant.rs:436-447, :219)  k_rt_keyset_bases, _rows, _exp, _exp_idx
@@ -718,6 +719,57 @@ __global__ void RT_KERNEL(LPL) k_rt_mul(const u32* __restrict__ a_m, const u32* 
 }
 
 // ---------------------------------------------------------------------------------------
+// out[s] = prod of the factors first_s .. first_s + m_s - 1 mod q, one segment of a dense array of factors per workgroup: the
+// secrets of a whole round in one launch (capi_modp_rt.inc, "Many secrets in one call"), where one secret alone takes
+// ceil(log2 m) rounds of k_rt_to_mont and k_rt_mul.
+//   f_m  : the factors of every segment, concatenated, in Montgomery form (k_rt_to_mont)
+//   segs : [gridDim.x] of {first factor of the segment, m}
+// Quad k starts from R mod N and multiplies in the factors first + k, first + k + 16, ..: ceil(m / 16) trips, the same for the
+// whole wave, a quad with no factor in a trip multiplying by R mod N.  The 16 partial products are then folded through the quads'
+// LDS slots in four rounds (strides 8, 4, 2, 1): every quad stores its product, a wave barrier, and quad k < stride multiplies
+// by the slot of quad k + stride.  Every quad takes every step: one outside a round's lower half multiplies by its own stored
+// value, a number below 2N like every other, and nobody reads its result.  Quad 0 leaves the Montgomery domain by plain 1.  The
+// order of the products is free -- the result is the canonical residue, hence the bytes of the pairwise rounds.
+// ceil(m / 16) + 4 + 1 Montgomery operations, one product site (every step only chooses its LDS operand).
+// ---------------------------------------------------------------------------------------
+template <int LPL>
+__global__ void RT_KERNEL(LPL) k_rt_product_segments(const u32* __restrict__ f_m, const uint2* __restrict__ segs,
+                                                     uint8_t* __restrict__ out_be, const modp_rt_consts* __restrict__ cs) {
+  constexpr int L = Width<LPL>::L, SLOT = Width<LPL>::SLOT;
+  __shared__ __attribute__((aligned(16))) u32 lds[RT_NUMS * SLOT];
+  const Lane ln = make_lane();
+  const int quad = threadIdx.x >> 2;
+  u32* slot = lds + quad * SLOT;
+  const uint2 seg = segs[blockIdx.x];
+  const int m = (int)seg.y;
+  const u32* mine = f_m + (size_t)seg.x * L;
+  const u32 n0inv = cs->n0inv;
+  u32 n[LPL], acc[LPL];
+  load_lane_limbs<LPL>(n, cs->n, ln);
+  load_lane_limbs<LPL>(acc, cs->one_m, ln);
+  // steps: 0 .. trips-1 times a factor (or R mod N), trips .. trips+3 a fold round, trips+4 final (times plain 1)
+  const int trips = (m + RT_NUMS - 1) / RT_NUMS;
+#pragma nounroll
+  for (int s = 0; s <= trips + 4; ++s) {
+    const u32* b = slot;
+    if (s < trips) {
+      const int k = s * RT_NUMS + quad;
+      slot_fill_from_global<LPL>(slot, k < m ? mine + (size_t)k * L : cs->one_m, ln);
+    } else if (s < trips + 4) {
+      const int stride = (RT_NUMS / 2) >> (s - trips);
+      slot_store<LPL>(slot, acc, ln);
+      if (quad < stride) b = lds + (quad + stride) * SLOT;
+    } else {
+      slot_fill_from_global<LPL>(slot, cs->one, ln);
+    }
+    __builtin_amdgcn_wave_barrier();
+    mont_mul<N0INV_RUNTIME>(acc, acc, b, n, ln, n0inv);
+    __builtin_amdgcn_wave_barrier();
+  }
+  store_canonical<LPL>(out_be + (size_t)blockIdx.x * Width<LPL>::EB, acc, slot, cs, ln, quad == 0);
+}
+
+// ---------------------------------------------------------------------------------------
 // X_i by Horner's rule in the exponent, X = (..((C_{t-1})^i' C_{t-2})^i' ..)^i' C_0 with i' = i mod (q-1).
 // For a safe prime q this is the reference's prod_j C_j^(i^j mod (q-1)) for every input: for a unit C_j the
 // exponents agree mod q-1 (Fermat); a C_j = 0 mod q gives 0 on both sides when i' > 0 (every i'^j >= 1) and when
@@ -1272,6 +1324,14 @@ extern "C" int RT_FN(launch_mul)(int lpl, const uint32_t* a, const uint32_t* b, 
   RT_ELSEWHERE(launch_mul, lpl, a, b, count, out, cs, s);
   if (count <= 0) return 0;
   RT_DISPATCH(lpl, k_rt_mul, dim3(rt_grid(count)), dim3(64), 0, s, a, b, count, out, cs);
+  return (int)hipGetLastError();
+}
+
+extern "C" int RT_FN(launch_product_segments)(int lpl, const uint32_t* f_m, const uint32_t* segs, int nsegs, uint8_t* out,
+                                              const modp_rt_consts* cs, hipStream_t s) {
+  RT_ELSEWHERE(launch_product_segments, lpl, f_m, segs, nsegs, out, cs, s);
+  if (nsegs <= 0) return 0;
+  RT_DISPATCH(lpl, k_rt_product_segments, dim3(nsegs), dim3(64), 0, s, f_m, reinterpret_cast<const uint2*>(segs), out, cs);
   return (int)hipGetLastError();
 }
 

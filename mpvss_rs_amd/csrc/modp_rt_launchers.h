@@ -43,6 +43,10 @@ int MODP_RT_FN(launch_twin_exp)(int lpl, const uint8_t* bases, const uint8_t* e1
                             uint8_t* out1, uint8_t* out2, const modp_rt_consts* cs, hipStream_t s);
 /* out[x] = a[x] b[x] mod q, canonical, from a R and b R (modp_rt_launch_to_mont) */
 int MODP_RT_FN(launch_mul)(int lpl, const uint32_t* a_m, const uint32_t* b_m, int count, uint8_t* out, const modp_rt_consts* cs, hipStream_t s);
+/* out[s] = prod of the factors f_m[first_s .. first_s + m_s) mod q, canonical, one workgroup per segment: f_m numbers in
+   Montgomery form (modp_rt_launch_to_mont), segs [nsegs][2] words {first factor, m} on the device, every segment inside f_m */
+int MODP_RT_FN(launch_product_segments)(int lpl, const uint32_t* f_m, const uint32_t* segs, int nsegs, uint8_t* out,
+                                    const modp_rt_consts* cs, hipStream_t s);
 /* X[x] = Horner in the exponent over the commitments cm_m ([t] numbers in Montgomery form) at i' = positions[x] mod (q-1) */
 int MODP_RT_FN(launch_commit_eval)(int lpl, const uint32_t* cm_m, int t, const int64_t* positions, int count, uint8_t* x_be,
                                const modp_rt_consts* cs, hipStream_t s);

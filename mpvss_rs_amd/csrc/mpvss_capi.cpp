@@ -14,6 +14,7 @@
 #include <atomic>
 #include <chrono>
 #include <condition_variable>
+#include <map>
 #include <mutex>
 #include <new>
 #include <string>
@@ -358,6 +359,8 @@ struct mpvss_ctx {
   // table, the per-share key indices, the boxes' challenges, the concatenated positions
   DevBuf rt_run_tiles, rt_run_boxes, rt_run_keyof, rt_run_ch, rt_run_pos;
   unsigned long long rt_many_groups = 0, rt_many_grouped_boxes = 0, rt_many_single_boxes = 0;   // mpvss_modp_group_verify_many_stats
+  // mpvss_modp_group_reconstruct_many_stats (a pass keeps its segment table in rt_run_boxes)
+  unsigned long long rt_rec_passes = 0, rt_rec_grouped_secrets = 0, rt_rec_single_secrets = 0;
   std::vector<DevBuf*> rt_all() {
     return {&rt_consts, &rt_in[0], &rt_in[1], &rt_in[2], &rt_in[3], &rt_in[4], &rt_in[5], &rt_out[0], &rt_out[1], &rt_out[2],
             &rt_tab1, &rt_tab2, &rt_tabg, &rt_cm, &rt_small[0], &rt_small[1], &rt_out_y, &rt_buckets,

@@ -62,6 +62,13 @@ pub struct mpvss_modp_group_box {
     pub keyset: *const mpvss_modp_group_keyset,
     pub key_offset: usize,
 }
+/// one secret of mpvss_modp_group_reconstruct_many: m positions (host memory) and m shares (in the call's space)
+#[repr(C)]
+pub struct mpvss_modp_group_secret {
+    pub positions_host: *const i64,
+    pub shares: *const u8,
+    pub m: usize,
+}
 #[repr(C)]
 pub struct mpvss_ec_box {
     pub commitments: *const u8,
@@ -343,6 +350,11 @@ unsafe extern "C" {
                                         count: usize, hash_threads: c_int, verdicts: *mut c_int, digests32: *mut u8) -> c_int;
     pub fn mpvss_modp_group_verify_many_stats(ctx: *mut mpvss_ctx, groups: *mut c_ulonglong, grouped_boxes: *mut c_ulonglong,
                                               single_boxes: *mut c_ulonglong) -> c_int;
+    pub fn mpvss_modp_group_reconstruct_many(ctx: *mut mpvss_ctx, grp: *const mpvss_modp_group, space: c_int,
+                                             secrets: *const mpvss_modp_group_secret, count: usize, host_threads: c_int,
+                                             status: *mut c_int, gs_out: *mut u8, masks_out32: *mut u8) -> c_int;
+    pub fn mpvss_modp_group_reconstruct_many_stats(ctx: *mut mpvss_ctx, passes: *mut c_ulonglong, grouped_secrets: *mut c_ulonglong,
+                                                   single_secrets: *mut c_ulonglong) -> c_int;
     // ---- hashing helpers
     pub fn mpvss_sha256(data: *const u8, len: usize, out32: *mut u8);
     pub fn mpvss_modp_hash_to_scalar(data: *const u8, len: usize, out256: *mut u8);
