@@ -579,7 +579,8 @@ int mpvss_modp_group_verify_distribution(mpvss_ctx* ctx, const mpvss_modp_group*
                                          const uint8_t* responses, size_t n, const uint8_t* challenge_host, int* verdict,
                                          uint8_t* digest32_out, uint8_t* x_out_host, uint8_t* a1_out_host, uint8_t* a2_out_host);
 /* n share-box proofs, src/participant.rs:361-386 -> src/dleq.rs:275-302 (as mpvss_modp_verify_shares); products on the GPU, the
- * per-share hashes on the host */
+ * per-share hashes on the host or on the device (mpvss_ctx_set_rt_share_hash below; the same verdicts either way -- on the
+ * device a1 and a2 stay there and one verdict byte per share crosses the bus) */
 int mpvss_modp_group_verify_shares(mpvss_ctx* ctx, const mpvss_modp_group* grp, int space, const uint8_t* pk, const uint8_t* s,
                                    const uint8_t* y, const uint8_t* c, const uint8_t* r, size_t n, uint8_t* verdicts_host);
 
@@ -637,7 +638,8 @@ int mpvss_modp_group_deal(mpvss_ctx* ctx, const mpvss_modp_group* grp, const uin
                           uint8_t* x_out, uint8_t* y_out, uint8_t* a1_out, uint8_t* a2_out, uint8_t* digest32_out,
                           uint8_t* challenge_out256, uint8_t* r_out);
 /* n participants' extract_secret_share, src/participant.rs:294-353: same contract as mpvss_modp_extract_shares (xinv = x^-1 mod
- * (q-1) and the witnesses are inputs, the per-share challenge is hashed on the host).  A row whose Y_i is 0 mod q gives the
+ * (q-1) and the witnesses are inputs; the per-share challenge is hashed on the host or on the device, mpvss_ctx_set_rt_share_hash below,
+ * the same bytes either way).  A row whose Y_i is 0 mod q gives the
  * reference's values (S_i = 0, a2_i = 0^w_i).  e2_i = w_i xinv_i mod (q-1) is formed on host threads or on the device
  * (mpvss_ctx_set_rt_scalar), the same bytes either way. */
 int mpvss_modp_group_extract_shares(mpvss_ctx* ctx, const mpvss_modp_group* grp, int space, const uint8_t* pk, const uint8_t* y,
@@ -682,6 +684,25 @@ int mpvss_modp_group_scalar_min_shares(const mpvss_modp_group* grp);
 /* whole group_deal / group_extract_shares calls that ran the scalar ring on the device and on the host since the context was
  * created (either pointer may be null) */
 int mpvss_modp_group_scalar_stats(mpvss_ctx* ctx, unsigned long long* device_calls, unsigned long long* host_calls);
+/* The per-share DLEQ hash on the device.  The challenge of a share proof is hash_to_scalar(SHA256(framed(pk_i) framed(Y_i)
+ * framed(a1_i) framed(a2_i))) (src/dleq.rs:87-126: framed(b) = u64-BE(len) || the minimal big-endian bytes of the element as given,
+ * zero as one 0x00 byte); verify_share compares it with c_i (src/participant.rs:361-386 -> src/dleq.rs:275-302), the prover of
+ * extract_secret_share hands it out (src/participant.rs:329-343).  The kernel computes int_BE(SHA256(SHA256(transcript))) and does
+ * not reduce it, so a handle is admitted only where hash_to_scalar's reduction is the identity; every other handle (moduli below
+ * 258 bits: test sizes) keeps the host path under every mode. */
+/* 1 when (q-1)/2 >= 2^256, so hash_to_scalar is the identity on a SHA-256 output; host only */
+int mpvss_modp_group_has_device_share_hash(const mpvss_modp_group* grp);
+/* where group_verify_shares / group_extract_shares hash: 0 host, 1 automatic (default), 2 device whenever the handle allows.
+ * Automatic takes the device at every batch size: measured no slower than the host path from the smallest size on (DESIGN
+ * section 13, "Per-share hash on the device"; profiles/modp_rt_share_hash_rate.txt). */
+int mpvss_ctx_set_rt_share_hash(mpvss_ctx* ctx, int mode);
+/* whole calls of those two entry points that hashed on the device / on the host since the context was created */
+int mpvss_modp_group_share_hash_stats(mpvss_ctx* ctx, unsigned long long* device_calls, unsigned long long* host_calls);
+/* c_out[i] = hash_to_scalar(SHA256(framed(h1_i) framed(h2_i) framed(a1_i) framed(a2_i))), dleq.rs:87-126, for n transcripts;
+ * all five arrays n x element size in `space`; n == 0 is MPVSS_OK; a handle without the device hash is MPVSS_E_INVALID
+ * (no host path inside, as mpvss_modp_group_batch_scalar_mul) */
+int mpvss_modp_group_dleq_challenges(mpvss_ctx* ctx, const mpvss_modp_group* grp, int space, const uint8_t* h1, const uint8_t* h2,
+                                     const uint8_t* a1, const uint8_t* a2, size_t n, uint8_t* c_out);
 
 /* Key sets of a run-time group.  The full-width powers of a participant's public key -- a2_i = y_i^r_i Y_i^c of the verifier,
  * Y_i = y_i^P(i) and a2_i = y_i^w_i of the dealer -- are the largest term of a share, and keys are long-lived: a key set holds,

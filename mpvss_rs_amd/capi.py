@@ -59,6 +59,8 @@ EXPORTED_SYMBOLS = (
     "mpvss_modp_group_has_device_scalar", "mpvss_modp_group_scalar_min_shares", "mpvss_ctx_set_rt_scalar",
     "mpvss_modp_group_scalar_stats", "mpvss_modp_group_poly_eval_device", "mpvss_modp_group_dleq_responses_device",
     "mpvss_modp_group_batch_scalar_mul",
+    "mpvss_modp_group_has_device_share_hash", "mpvss_ctx_set_rt_share_hash", "mpvss_modp_group_share_hash_stats",
+    "mpvss_modp_group_dleq_challenges",
     "mpvss_modp_group_keyset_bytes_per_key", "mpvss_modp_group_keyset_create", "mpvss_modp_group_keyset_destroy",
     "mpvss_modp_group_keyset_bytes", "mpvss_modp_group_keyset_dual_exp", "mpvss_modp_group_keyset_twin_exp",
     "mpvss_modp_group_verify_distribution_keyset", "mpvss_modp_group_deal_keyset",
@@ -274,6 +276,10 @@ def load_library() -> C.CDLL:
     lib.mpvss_modp_group_poly_eval_device.argtypes = [vp, vp, u8p, sz, vp, sz, vp]
     lib.mpvss_modp_group_dleq_responses_device.argtypes = [vp, vp, vp, vp, u8p, sz, vp]
     lib.mpvss_modp_group_batch_scalar_mul.argtypes = [vp, vp, ci, vp, vp, sz, vp]
+    lib.mpvss_modp_group_has_device_share_hash.argtypes = [vp]
+    lib.mpvss_ctx_set_rt_share_hash.argtypes = [vp, ci]
+    lib.mpvss_modp_group_share_hash_stats.argtypes = [vp, C.POINTER(C.c_ulonglong), C.POINTER(C.c_ulonglong)]
+    lib.mpvss_modp_group_dleq_challenges.argtypes = [vp, vp, ci, vp, vp, vp, vp, sz, vp]
     lib.mpvss_modp_group_keyset_bytes_per_key.argtypes = [vp]
     lib.mpvss_modp_group_keyset_bytes_per_key.restype = sz
     lib.mpvss_modp_group_keyset_create.argtypes = [vp, vp, ci, vp, sz, C.POINTER(vp)]
@@ -384,6 +390,11 @@ class ModpGroup:
     def has_device_scalar(self) -> bool:
         """the handle holds the constants of (q-1)/2 (odd and >= 3): the scalar ring can run on the device"""
         return self.lib.mpvss_modp_group_has_device_scalar(self.handle) == 1
+
+    @property
+    def has_device_share_hash(self) -> bool:
+        """(q-1)/2 >= 2^256: the per-share DLEQ hash of group_verify_shares / group_extract_shares can run on the device"""
+        return self.lib.mpvss_modp_group_has_device_share_hash(self.handle) == 1
 
     @property
     def scalar_min_shares(self) -> int:
@@ -581,6 +592,34 @@ class Engine:
         d, h = C.c_ulonglong(0), C.c_ulonglong(0)
         self._check(self.lib.mpvss_modp_group_scalar_stats(self.ctx, C.byref(d), C.byref(h)), "group_scalar_stats")
         return {"device": int(d.value), "host": int(h.value)}
+
+    def set_rt_share_hash(self, mode: int) -> None:
+        """mpvss_ctx_set_rt_share_hash: where group_verify_shares / group_extract_shares hash each share's transcript -- 0 host,
+        1 automatic, 2 on the device whenever the handle allows it (has_device_share_hash)"""
+        self._check(self.lib.mpvss_ctx_set_rt_share_hash(self.ctx, int(mode)), "set_rt_share_hash")
+
+    def group_share_hash_stats(self) -> dict:
+        """whole group_verify_shares / group_extract_shares calls that hashed on the device / on the host"""
+        d, h = C.c_ulonglong(0), C.c_ulonglong(0)
+        self._check(self.lib.mpvss_modp_group_share_hash_stats(self.ctx, C.byref(d), C.byref(h)), "group_share_hash_stats")
+        return {"device": int(d.value), "host": int(h.value)}
+
+    def group_dleq_challenges(self, grp: "ModpGroup", h1: bytes, h2: bytes, a1: bytes, a2: bytes) -> bytes:
+        """c[i] = hash_to_scalar(SHA256(framed(h1_i) framed(h2_i) framed(a1_i) framed(a2_i))) on the device, from host bytes"""
+        EB = grp.elem_bytes
+        n = len(h1) // EB
+        k = [_buf(x or None) for x in (h1, h2, a1, a2)]
+        ko, po = _out(n * EB)
+        self._check(self.lib.mpvss_modp_group_dleq_challenges(self.ctx, grp.handle, MPVSS_HOST, k[0][1], k[1][1], k[2][1], k[3][1], n, po),
+                    "group_dleq_challenges")
+        return bytes(ko)[: n * EB]
+
+    def group_dleq_challenges_device(self, grp: "ModpGroup", h1_dev_ptr: int, h2_dev_ptr: int, a1_dev_ptr: int, a2_dev_ptr: int, n: int,
+                                     out_dev_ptr: int) -> None:
+        """the same with all five arrays (n x elem_bytes each) in HBM"""
+        self._check(self.lib.mpvss_modp_group_dleq_challenges(self.ctx, grp.handle, MPVSS_DEVICE, C.c_void_p(h1_dev_ptr),
+                                                              C.c_void_p(h2_dev_ptr), C.c_void_p(a1_dev_ptr), C.c_void_p(a2_dev_ptr),
+                                                              int(n), C.c_void_p(out_dev_ptr)), "group_dleq_challenges")
 
     def group_poly_eval_device(self, grp: "ModpGroup", coeffs: bytes, positions_dev_ptr: int, n: int, out_dev_ptr: int) -> None:
         """P(i) mod (q-1) for n positions in HBM (int64) into n x elem_bytes in HBM; the coefficients are host bytes"""

@@ -7,7 +7,7 @@
 // (below) for the device, the constants, the chunk loop, the choice of space, the copies back and the wiping of secrets,
 // and in between only what is its own -- which buffers its arrays use, which of them are secret, what it launches and
 // what it hashes.  The launch decisions (rt_comb_for, rt_dleq_dev, rt_commit_eval_dev with rt_fd_prepare and
-// rt_fd_positions_ok, rt_twin_dev, rt_fixed_base_dev, rt_scalar_on_device, rt_product_tree, the grouping of small boxes in
+// rt_fd_positions_ok, rt_twin_dev, rt_fixed_base_dev, rt_scalar_on_device, rt_share_hash_on_device, rt_product_tree, the grouping of small boxes in
 // mpvss_modp_group_verify_many and that of secrets in mpvss_modp_group_reconstruct_many) are single places of their own.
 
 constexpr size_t RT_EB_MAX = FRAME_EB_MAX;     // the widest element / scalar of a handle (mpvss_modp_group_create_wide): 384 bytes
@@ -24,6 +24,8 @@ struct mpvss_modp_group {
   modp_rt_consts cq;         // the same for the modulus q' = (q-1)/2 at the handle's own lpl (R > 4 q' wherever R > 4 q): the scalar
                              // ring Z/(q-1) = Z/2 x Z/q' on the device.  Built only when q' is odd and >= 3 (has_q)
   bool has_q = false;
+  bool has_sh = false;       // (q-1)/2 >= 2^256, i.e. bits >= 258: hash_to_scalar is the identity on a SHA-256 output, so the per-share
+                             // DLEQ hash may run on the device (k_rt_share_verdict does not reduce)
   uint8_t subR_be[RT_EB_MAX];// R mod q' = 2^(29 L) mod q', eb bytes big-endian (has_q): takes a coefficient into Montgomery form
   int bits = 0;
   int lpl = 0;
@@ -250,6 +252,16 @@ struct RtCall {
     if (kind == Secret && std::find(wipe.host.begin(), wipe.host.end(), &vec) == wipe.host.end()) wipe.host.push_back(&vec);
     to_host(arr + off * EB, cnt, vec);
     return vec.data();
+  }
+  // results that are not elements (one verdict byte, or a 32-byte challenge, per share): `bytes` of a workspace of the context, and
+  // their copy into host memory, valid after settle() or host_ready() whatever `space` is
+  uint8_t* raw(DevBuf& buf, size_t bytes) {
+    if (rc) return nullptr;
+    rc = ensure(ctx, buf, bytes);
+    return rc ? nullptr : (uint8_t*)buf.p;
+  }
+  void host_bytes(void* host_dst, const uint8_t* dev, size_t bytes) {
+    if (!rc) rc = read_back(host_dst, dev, bytes);
   }
   // before the host reads what to_host() / host_view() asked for in the middle of a chunk; nothing to wait for in host space
   int host_ready() {
@@ -566,6 +578,26 @@ void rt_share_challenge(const mpvss_modp_group* grp, const uint8_t* a, const uin
   rt_hash_to_scalar(grp, digest, 32, out);
 }
 
+// THE launch decision of the per-share hash for one whole call of n shares (defined beside rt_scalar_on_device); counts the call
+bool rt_share_hash_on_device(mpvss_ctx* ctx, const mpvss_modp_group* grp, size_t n);
+
+// The same challenges for cnt shares on the device (k_rt_share_verdict, timer 5; all pointers device memory, arrays [cnt][EB]).
+// c_out null: verdict[i] = (c_i == challenge_i); c_out given: challenge_i as c_out_stride (32 or EB) bytes.  For handles with
+// has_sh only: the kernel leaves out the reduction mod (q-1)/2, which is the identity there.
+int rt_share_hash_dev(RtCall& f, const uint8_t* a, const uint8_t* b, const uint8_t* a1, const uint8_t* a2, const uint8_t* c, size_t cnt,
+                      uint8_t* verdict, uint8_t* c_out, size_t c_out_stride) {
+  TIMED_LAUNCH(f.ctx, 5, verdict_launch_rt((int)f.EB, a, b, a1, a2, c, (int)cnt, verdict, c_out, (int)c_out_stride, f.ctx->stream));
+  return 0;
+}
+// 32-byte challenges as they crossed the bus -> EB-byte big-endian scalars
+void rt_widen_challenges(const uint8_t* c32, size_t cnt, size_t EB, uint8_t* out) {
+  for (size_t i = 0; i < cnt; ++i) {
+    memset(out + i * EB, 0, EB - 32);
+    memcpy(out + i * EB + EB - 32, c32 + i * 32, 32);
+  }
+}
+const char* const RT_NO_SH = "the handle has no device share hash: (q-1)/2 is below 2^256 (mpvss_modp_group_has_device_share_hash)";
+
 bool rt_bad_group(const mpvss_modp_group* grp) { return grp == nullptr || grp->lpl == 0; }
 
 // words of one key's rows
@@ -642,6 +674,7 @@ int rt_group_build(const RtNum q, int bits, size_t eb, int lpl, RtRings<NW> mpvs
   memset(&g->cq, 0, sizeof(g->cq));
   memset(g->subR_be, 0, sizeof(g->subR_be));
   g->has_q = (q[0] & 3) == 3 && (bits > 3 || q[0] >= 7);
+  g->has_sh = bits >= 258;                       // q odd: (q-1)/2 >= 2^256  <=>  q >= 2^257 + 1  <=>  bits(q) >= 258
   if (g->has_q) {
     rt_limbs(sub, g->cq.n, L);
     rt_pow2_mod<NW>(k, 29 * (in_rows + L), R.sub);
@@ -879,6 +912,7 @@ extern "C" int mpvss_modp_group_verify_shares(mpvss_ctx* ctx, const mpvss_modp_g
     return fail(ctx, MPVSS_E_INVALID, "group_verify_shares: bad argument");
   std::vector<uint8_t> hpk, hY, hc, h1, h2;
   RtCall f(ctx, grp, space);
+  const bool hdev = rt_share_hash_on_device(ctx, grp, n);
   RET_IF(f.begin());
   RET_IF(f.for_chunks(n, [&](size_t off, size_t cnt) {
     const uint8_t* dpk = f.in(pk, off, cnt, ctx->rt_in[0], RtCall::Public);
@@ -888,9 +922,15 @@ extern "C" int mpvss_modp_group_verify_shares(mpvss_ctx* ctx, const mpvss_modp_g
     const uint8_t* dr = f.in(r, off, cnt, ctx->rt_in[3], RtCall::Public);
     uint8_t* d1 = f.work(ctx->rt_out[1], cnt);
     uint8_t* d2 = f.work(ctx->rt_out[2], cnt);
+    uint8_t* dv = hdev ? f.raw(ctx->rt_sh_verdict, cnt) : nullptr;
     RET_IF(f.rc);
     // a1 = G^r pk^c, a2 = S^r Y^c (src/participant.rs:361-386 -> src/dleq.rs:275-302)
     RET_IF(rt_dleq_dev(ctx, grp, f.dc, grp->G_be, dpk, ds, nullptr, dy, dr, dcc, EB, cnt, d1, d2));
+    if (hdev) {                                  // a1 and a2 stay where they are; the chunk's verdict bytes alone cross the bus
+      RET_IF(rt_share_hash_dev(f, dpk, dy, d1, d2, dcc, cnt, dv, nullptr, 0));
+      f.host_bytes(verdicts_host + off, dv, cnt);
+      return f.rc;
+    }
     f.to_host(d1, cnt, h1);
     f.to_host(d2, cnt, h2);
     const uint8_t* P = f.host_view(pk, off, cnt, hpk);
@@ -971,6 +1011,22 @@ bool rt_scalar_on_device(mpvss_ctx* ctx, const mpvss_modp_group* grp, size_t n) 
   const bool dev = grp->has_q && n > 0 &&
                    (mode == 2 || (mode == 1 && RT_SCALAR_AUTO_ON && n >= rt_scalar_min_shares(grp->lpl)));
   ++(dev ? ctx->rt_scalar_dev_calls : ctx->rt_scalar_host_calls);
+  return dev;
+}
+
+// ---- the per-share DLEQ hash on the device (DESIGN section 13, "Per-share hash on the device") ----------------------------------
+// Mode 1 of mpvss_ctx_set_rt_share_hash takes the device path from rt_share_hash_min_shares shares of a whole call: the smallest
+// measured n from which the whole call under mode 2 is no slower than the parent's at every larger measured n, from
+// `tools/modp_rt_rate.py --share-hash --ab` (profiles/modp_rt_share_hash_rate.txt).  Measured at 1024, 2048 and 3072 bits: mode 2 is
+// no slower at any measured n (1024, 4096, 65536; 16384 at 3072 bits), for both entry points, so the threshold is 1.
+size_t rt_share_hash_min_shares(int) { return 1; }
+constexpr bool RT_SHARE_HASH_AUTO_ON = true;
+
+bool rt_share_hash_on_device(mpvss_ctx* ctx, const mpvss_modp_group* grp, size_t n) {
+  const int mode = ctx->rt_share_hash_mode;
+  const bool dev = grp->has_sh && n > 0 &&
+                   (mode == 2 || (mode == 1 && RT_SHARE_HASH_AUTO_ON && n >= rt_share_hash_min_shares(grp->lpl)));
+  ++(dev ? ctx->rt_share_hash_dev_calls : ctx->rt_share_hash_host_calls);
   return dev;
 }
 
@@ -1406,15 +1462,17 @@ extern "C" int mpvss_modp_group_extract_shares(mpvss_ctx* ctx, const mpvss_modp_
   if (n == 0) return MPVSS_OK;
   if (!pk || !y || !xinv || !w || !s_out || !c_out_host || n > 0x7fffffff)
     return fail(ctx, MPVSS_E_INVALID, "group_extract_shares: bad argument");
-  std::vector<uint8_t> hpk, hy, hxi, hw, e2, hS, h1, h2;
+  std::vector<uint8_t> hpk, hy, hxi, hw, e2, hS, h1, h2, c32;
   RtCall f(ctx, grp, space);
   f.wipe.host.push_back(&e2);
   const int threads = host_threads(0);
   // e2 = w / x on the device (k_rt_modq_mul from the staged w and xinv) or on host threads; the zero-row scan of Y stays here
   const bool sdev = rt_scalar_on_device(ctx, grp, n);
+  // the challenges from k_rt_share_verdict (a1 and a2 never leave the device) or framed and hashed on host threads
+  const bool hdev = rt_share_hash_on_device(ctx, grp, n);
   RET_IF(f.begin(sdev ? RtCall::ModQ | RtCall::SubQ : RtCall::ModQ));
   RET_IF(f.for_chunks(n, [&](size_t off, size_t cnt) {
-    const uint8_t* PK = f.host_view(pk, off, cnt, hpk);
+    const uint8_t* PK = hdev ? nullptr : f.host_view(pk, off, cnt, hpk);
     const uint8_t* Y = f.host_view(y, off, cnt, hy);
     const uint8_t* XI = sdev ? nullptr : f.host_view(xinv, off, cnt, hxi, RtCall::Secret);
     const uint8_t* W = sdev ? nullptr : f.host_view(w, off, cnt, hw, RtCall::Secret);
@@ -1439,6 +1497,8 @@ extern "C" int mpvss_modp_group_extract_shares(mpvss_ctx* ctx, const mpvss_modp_
     uint8_t* dS = f.out(s_out, off, cnt, ctx->rt_out[0]);
     uint8_t* d1 = f.work(ctx->rt_out[1], cnt);
     uint8_t* d2 = f.work(ctx->rt_out[2], cnt);
+    const uint8_t* dpk = hdev ? f.in(pk, off, cnt, ctx->rt_in[5], RtCall::Public) : nullptr;
+    uint8_t* dc32 = hdev ? f.raw(ctx->rt_sh_c32, cnt * 32) : nullptr;
     RET_IF(f.rc);
     if (sdev && shared)                                          // a chunk with a zero row takes the two dependent chains: no e2
       TIMED_LAUNCH(ctx, 4, modp_rt_launch_modq_mul(grp->lpl, dw, dxi, (int)cnt, (uint8_t*)de2, f.dcq, ctx->stream));
@@ -1454,6 +1514,14 @@ extern "C" int mpvss_modp_group_extract_shares(mpvss_ctx* ctx, const mpvss_modp_
                                                    ctx->stream));
     }
     RET_IF(rt_fixed_base_dev(ctx, grp, f.dc, grp->G_be, dw, cnt, d1, 1));                              // a1 = G^w
+    if (hdev) {                                                  // :329-343; S goes out by settle(), the challenges as 32 bytes each
+      RET_IF(rt_share_hash_dev(f, dpk, dy, d1, d2, nullptr, cnt, nullptr, dc32, 32));
+      c32.resize(cnt * 32);
+      f.host_bytes(c32.data(), dc32, cnt * 32);
+      RET_IF(f.settle());
+      rt_widen_challenges(c32.data(), cnt, EB, c_out_host + off * EB);
+      return 0;
+    }
     f.to_host(dS, cnt, hS);
     f.to_host(d1, cnt, h1);
     f.to_host(d2, cnt, h2);
@@ -1656,6 +1724,65 @@ extern "C" int mpvss_modp_group_batch_scalar_mul(mpvss_ctx* ctx, const mpvss_mod
     uint8_t* dout = f.out(out, off, cnt, ctx->rt_out[0], RtCall::Secret);
     RET_IF(f.rc);
     TIMED_LAUNCH(ctx, 4, modp_rt_launch_modq_mul(grp->lpl, da, db, (int)cnt, dout, f.dcq, ctx->stream));
+    return 0;
+  }));
+  return f.end();
+}
+
+// =====================================================================================================================
+// The per-share DLEQ hash of a run-time group on the device (DESIGN section 13, "Per-share hash on the device"): where
+// group_verify_shares / group_extract_shares hash, and the challenges of n transcripts on their own.
+// =====================================================================================================================
+extern "C" int mpvss_modp_group_has_device_share_hash(const mpvss_modp_group* grp) {
+  if (rt_bad_group(grp)) return MPVSS_E_INVALID;
+  return grp->has_sh ? 1 : 0;
+}
+
+extern "C" int mpvss_ctx_set_rt_share_hash(mpvss_ctx* ctx, int mode) {
+  if (!ctx) return MPVSS_E_INVALID;
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  if (mode < 0 || mode > 2) return fail(ctx, MPVSS_E_INVALID, "set_rt_share_hash: mode is 0, 1 or 2");
+  ctx->rt_share_hash_mode = mode;
+  return MPVSS_OK;
+}
+
+extern "C" int mpvss_modp_group_share_hash_stats(mpvss_ctx* ctx, unsigned long long* device_calls, unsigned long long* host_calls) {
+  if (!ctx) return MPVSS_E_INVALID;
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  if (device_calls) *device_calls = ctx->rt_share_hash_dev_calls;
+  if (host_calls) *host_calls = ctx->rt_share_hash_host_calls;
+  return MPVSS_OK;
+}
+
+// dleq.rs:87-126 for n transcripts: a caller's own DLEQ shape after group_dleq_commitments.  No host path inside.
+extern "C" int mpvss_modp_group_dleq_challenges(mpvss_ctx* ctx, const mpvss_modp_group* grp, int space, const uint8_t* h1,
+                                                const uint8_t* h2, const uint8_t* a1, const uint8_t* a2, size_t n, uint8_t* c_out) {
+  if (!ctx) return MPVSS_E_INVALID;
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  if (rt_bad_group(grp)) return fail(ctx, MPVSS_E_INVALID, "group_dleq_challenges: no group");
+  if (n == 0) return MPVSS_OK;
+  if (!h1 || !h2 || !a1 || !a2 || !c_out || n > 0x7fffffff || (space != MPVSS_HOST && space != MPVSS_DEVICE))
+    return fail(ctx, MPVSS_E_INVALID, "group_dleq_challenges: bad argument");
+  if (!grp->has_sh) return fail(ctx, MPVSS_E_INVALID, RT_NO_SH);
+  std::vector<uint8_t> c32;
+  RtCall f(ctx, grp, space);
+  RET_IF(f.begin(0));                                         // nothing here needs the constants of q
+  RET_IF(f.for_chunks(n, [&](size_t off, size_t cnt) {
+    const uint8_t* d1 = f.in(h1, off, cnt, ctx->rt_in[0], RtCall::Public);
+    const uint8_t* d2 = f.in(h2, off, cnt, ctx->rt_in[1], RtCall::Public);
+    const uint8_t* d3 = f.in(a1, off, cnt, ctx->rt_in[2], RtCall::Public);
+    const uint8_t* d4 = f.in(a2, off, cnt, ctx->rt_in[3], RtCall::Public);
+    if (!f.caller_on_host()) {                                // the caller's own array: EB bytes per share, written by the kernel
+      RET_IF(f.rc);
+      return rt_share_hash_dev(f, d1, d2, d3, d4, nullptr, cnt, nullptr, c_out + off * f.EB, f.EB);
+    }
+    uint8_t* dc32 = f.raw(ctx->rt_sh_c32, cnt * 32);
+    RET_IF(f.rc);
+    RET_IF(rt_share_hash_dev(f, d1, d2, d3, d4, nullptr, cnt, nullptr, dc32, 32));
+    c32.resize(cnt * 32);
+    f.host_bytes(c32.data(), dc32, cnt * 32);
+    RET_IF(f.settle());
+    rt_widen_challenges(c32.data(), cnt, f.EB, c_out + off * f.EB);
     return 0;
   }));
   return f.end();

@@ -157,9 +157,10 @@ struct mpvss_ctx {
   void* pin = nullptr;
   size_t pin_cap = 0;
   hipEvent_t ev[2] = {nullptr, nullptr};
-  // 0 X path, 1 comb_dual_exp (a1), 2 table builds, 3 dual_exp (a2 / exp), 4 the scalar-ring kernels of a run-time group
-  double kernel_ms[5] = {-1, -1, -1, -1, -1};
-  int kernel_launches[5] = {0, 0, 0, 0, 0};
+  // 0 X path, 1 comb_dual_exp (a1), 2 table builds, 3 dual_exp (a2 / exp), 4 the scalar-ring kernels of a run-time group,
+  // 5 the per-share hash of a run-time group (k_rt_share_verdict)
+  double kernel_ms[6] = {-1, -1, -1, -1, -1, -1};
+  int kernel_launches[6] = {0, 0, 0, 0, 0, 0};
   struct Span { int id; hipEvent_t a, b; };
   struct SpanSet {
     std::vector<Span> spans;
@@ -346,6 +347,11 @@ struct mpvss_ctx {
   size_t rt_sc_pin_cap = 0;
   int rt_scalar_mode = 1;                        // mpvss_ctx_set_rt_scalar
   unsigned long long rt_scalar_dev_calls = 0, rt_scalar_host_calls = 0;   // whole calls (mpvss_modp_group_scalar_stats)
+  // the per-share DLEQ hash on the device (capi_modp_rt.inc, "per-share hash on the device"): verdict bytes and 32-byte challenges
+  // of one chunk
+  DevBuf rt_sh_verdict, rt_sh_c32;
+  int rt_share_hash_mode = 1;                    // mpvss_ctx_set_rt_share_hash
+  unsigned long long rt_share_hash_dev_calls = 0, rt_share_hash_host_calls = 0;   // whole calls (mpvss_modp_group_share_hash_stats)
   DevBuf rt_out_y, rt_buckets;   // the dealer's fourth result array; bucket scratch of k_rt_twin_exp (one chunk)
   // forward differences for X of a run-time group (rt_commit_eval_dev): inverted commitments (bytes, then Montgomery form), seed
   // positions, seeds [2][S][t][L], X in limbs [n][L], the chain kernel's scratch -- grown on demand
@@ -365,7 +371,7 @@ struct mpvss_ctx {
     return {&rt_consts, &rt_in[0], &rt_in[1], &rt_in[2], &rt_in[3], &rt_in[4], &rt_in[5], &rt_out[0], &rt_out[1], &rt_out[2],
             &rt_tab1, &rt_tab2, &rt_tabg, &rt_cm, &rt_small[0], &rt_small[1], &rt_out_y, &rt_buckets,
             &rt_fd_inv, &rt_cm_inv, &rt_fd_pos, &rt_fd_seeds, &rt_fd_x, &rt_fd_park,
-            &rt_consts_q, &rt_sc_coef, &rt_sc_p, &rt_sc_w, &rt_sc_c, &rt_sc_r,
+            &rt_consts_q, &rt_sc_coef, &rt_sc_p, &rt_sc_w, &rt_sc_c, &rt_sc_r, &rt_sh_verdict, &rt_sh_c32,
             &rt_run_tiles, &rt_run_boxes, &rt_run_keyof, &rt_run_ch, &rt_run_pos,
             &rt_comb[0].buf, &rt_comb[1].buf, &rt_comb[2].buf, &rt_comb[3].buf};
   }
@@ -533,8 +539,8 @@ void spans_reset(mpvss_ctx* ctx) {
   if (ctx->sp == &ctx->main_spans)
     for (double& m : ctx->kernel_ms) m = -1;
 }
-int spans_sum(mpvss_ctx* ctx, mpvss_ctx::SpanSet& ss, double out[5]) {
-  for (int i = 0; i < 5; ++i) { out[i] = 0; ctx->kernel_launches[i] = 0; }
+int spans_sum(mpvss_ctx* ctx, mpvss_ctx::SpanSet& ss, double out[6]) {
+  for (int i = 0; i < 6; ++i) { out[i] = 0; ctx->kernel_launches[i] = 0; }
   for (auto& s : ss.spans) {
     float ms = 0;
     HIPCHK(ctx, hipEventElapsedTime(&ms, s.a, s.b));
@@ -953,12 +959,12 @@ extern "C" int mpvss_ctx_synchronize(mpvss_ctx* ctx) {
 }
 
 extern "C" double mpvss_last_kernel_ms(const mpvss_ctx* ctx, int kernel_id) {
-  if (!ctx || kernel_id < 0 || kernel_id > 4) return -1;
+  if (!ctx || kernel_id < 0 || kernel_id > 5) return -1;
   return ctx->kernel_ms[kernel_id];
 }
 
 extern "C" int mpvss_last_kernel_launches(const mpvss_ctx* ctx, int kernel_id) {
-  if (!ctx || kernel_id < 0 || kernel_id > 4) return -1;
+  if (!ctx || kernel_id < 0 || kernel_id > 5) return -1;
   return ctx->kernel_launches[kernel_id];
 }
 

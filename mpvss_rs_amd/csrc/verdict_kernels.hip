@@ -184,21 +184,22 @@ __device__ __forceinline__ void sha512_of_digest(u64 (&out)[8], const u32 (&d)[8
   out[4] = st[4] + e; out[5] = st[5] + f; out[6] = st[6] + g; out[7] = st[7] + h;
 }
 
-// frame one MODP element: minimal-length big-endian bytes of a 256-byte value (modp.rs:150-152)
+// frame one MODP element: minimal-length big-endian bytes of an EB-byte value (modp.rs:150-152), hashed as given (not reduced)
+template <int EB>
 __device__ __forceinline__ void frame_modp(LaneSha256& h, const uint8_t* __restrict__ e) {
   const u32* e32 = reinterpret_cast<const u32*>(e);
-  int skip = 255;                                        // zero is hashed as one 0x00 byte
-  for (int k = 0; k < 64; ++k) {
+  int skip = EB - 1;                                     // zero is hashed as one 0x00 byte
+  for (int k = 0; k < EB / 4; ++k) {
     const u32 w = e32[k];                                // little-endian load: byte 4k is the low byte
     if (w != 0) {
       skip = 4 * k + (__builtin_ctz(w) >> 3);
       break;
     }
   }
-  h.push_len(256u - (u32)skip);
+  h.push_len((u32)EB - (u32)skip);
   int i = skip;
-  while ((i & 3) != 0 && i < 256) h.push(e[i++]);
-  for (; i < 256; i += 4) h.push_be32(__builtin_bswap32(e32[i >> 2]));
+  while ((i & 3) != 0 && i < EB) h.push(e[i++]);
+  for (; i < EB; i += 4) h.push_be32(__builtin_bswap32(e32[i >> 2]));
 }
 
 template <int LEN>
@@ -290,10 +291,10 @@ k_modp_share_verdict(const uint8_t* __restrict__ h1, const uint8_t* __restrict__
   LaneSha256 h;
   h.init(lds + threadIdx.x);
   const size_t off = (size_t)x * 256;
-  frame_modp(h, h1 + off);
-  frame_modp(h, h2 + off);
-  frame_modp(h, a1 + off);
-  frame_modp(h, a2 + off);
+  frame_modp<256>(h, h1 + off);
+  frame_modp<256>(h, h2 + off);
+  frame_modp<256>(h, a1 + off);
+  frame_modp<256>(h, a2 + off);
   u32 digest[8], hs[8];
   h.finish(digest);
   sha256_of_digest(hs, digest);                         // modp.rs:142-148 hashes the digest again
@@ -310,6 +311,48 @@ k_modp_share_verdict(const uint8_t* __restrict__ h1, const uint8_t* __restrict__
   for (int k = 0; k < 56; ++k) diff |= c32[k];
 #pragma unroll
   for (int k = 0; k < 8; ++k) diff |= __builtin_bswap32(c32[56 + k]) ^ hs[k];
+  verdict[x] = diff == 0 ? 1 : 0;
+}
+
+// ---- MODP groups of a run-time modulus (capi_modp_rt.inc) ----------------------------------------------------------
+// K7 at the handle's element size EB (256, or 384 for a wide handle): one lane per share, four EB-byte elements at stride EB
+// hashed as given, c' = int_BE(SHA256(SHA256(transcript))).  The kernel does NOT reduce c' mod (q-1)/2: the host admits a handle
+// only when (q-1)/2 >= 2^256 (mpvss_modp_group_has_device_share_hash), where the reduction is the identity.
+//   c_out == null  verdict[i] = 1 iff the EB-byte big-endian c_i has its leading EB - 32 bytes zero and its last 32 equal to c'
+//   c_out != null  the prover's side: c' as c_out_stride bytes big-endian per share, zero-extended on the left -- 32 for a
+//                  result the host widens after it crossed the bus, EB for a caller's own device array
+template <int EB>
+__global__ void __launch_bounds__(64)
+k_rt_share_verdict(const uint8_t* __restrict__ h1, const uint8_t* __restrict__ h2, const uint8_t* __restrict__ a1,
+                   const uint8_t* __restrict__ a2, const uint8_t* __restrict__ c, int count, uint8_t* __restrict__ verdict,
+                   uint8_t* __restrict__ c_out, int c_out_stride) {
+  __shared__ u32 lds[16 * 64];
+  const int x = blockIdx.x * 64 + threadIdx.x;
+  if (x >= count) return;
+  LaneSha256 h;
+  h.init(lds + threadIdx.x);
+  const size_t off = (size_t)x * EB;
+  frame_modp<EB>(h, h1 + off);
+  frame_modp<EB>(h, h2 + off);
+  frame_modp<EB>(h, a1 + off);
+  frame_modp<EB>(h, a2 + off);
+  u32 digest[8], hs[8];
+  h.finish(digest);
+  sha256_of_digest(hs, digest);                         // modp.rs:142-148 hashes the digest again
+  if (c_out != nullptr) {                               // extract_secret_share, participant.rs:329-343
+    u32* o = reinterpret_cast<u32*>(c_out + (size_t)x * c_out_stride);
+    const int lead = (c_out_stride - 32) >> 2;
+    for (int k = 0; k < lead; ++k) o[k] = 0;
+#pragma unroll
+    for (int k = 0; k < 8; ++k) o[lead + k] = __builtin_bswap32(hs[k]);
+    return;
+  }
+  constexpr int LEAD = (EB - 32) / 4;
+  const u32* c32 = reinterpret_cast<const u32*>(c + off);
+  u32 diff = 0;
+  for (int k = 0; k < LEAD; ++k) diff |= c32[k];
+#pragma unroll
+  for (int k = 0; k < 8; ++k) diff |= __builtin_bswap32(c32[LEAD + k]) ^ hs[k];
   verdict[x] = diff == 0 ? 1 : 0;
 }
 
@@ -442,7 +485,18 @@ extern "C" int verdict_launch_modp_challenge(const uint8_t* h1, const uint8_t* h
                      (uint8_t*)nullptr, c_out32);
   return (int)hipGetLastError();
 }
-extern "C" int verdict_launch_ec(int group, const uint8_t* h1, const uint8_t* h2, const uint8_t* a1, const uint8_t* a2,
+// c_out null: verdicts against c; otherwise challenges at c_out_stride (32 or eb) bytes per share.  eb: 256 or 384
+extern "C" int verdict_launch_rt(int eb, const uint8_t* h1, const uint8_t* h2, const uint8_t* a1, const uint8_t* a2, const uint8_t* c,
+                                 int count, uint8_t* verdict, uint8_t* c_out, int c_out_stride, hipStream_t s) {
+  if (count <= 0) return 0;
+  if ((eb != 256 && eb != 384) || (c_out ? (c_out_stride != 32 && c_out_stride != eb) : (c == nullptr || verdict == nullptr)))
+    return (int)hipErrorInvalidValue;
+  const dim3 grid((count + 63) / 64), block(64);
+  if (eb == 256) hipLaunchKernelGGL(k_rt_share_verdict<256>, grid, block, 0, s, h1, h2, a1, a2, c, count, verdict, c_out, c_out_stride);
+  else hipLaunchKernelGGL(k_rt_share_verdict<384>, grid, block, 0, s, h1, h2, a1, a2, c, count, verdict, c_out, c_out_stride);
+  return (int)hipGetLastError();
+}
+extern "C" int verdict_launch_ec(int group,const uint8_t* h1, const uint8_t* h2, const uint8_t* a1, const uint8_t* a2,
                                  const uint8_t* c, const uint8_t* r, int count, uint8_t* verdict, uint8_t* ok,
                                  hipStream_t s) {
   if (count <= 0) return 0;

@@ -128,6 +128,14 @@ impl Engine {
         Ok(rc)
     }
 
+    /// Where `mpvss_modp_group_verify_shares` / `mpvss_modp_group_extract_shares` hash each share's DLEQ transcript
+    /// (`Participant::verify_share`, src/participant.rs:361-386, and the prover's challenge of `extract_secret_share`, :329-343)
+    /// for a run-time MODP group: 0 on the host, 1 automatic (the default), 2 on the device whenever (q-1)/2 >= 2^256.  The
+    /// verdicts and challenges are the same bytes either way.
+    pub fn set_rt_share_hash(&self, mode: i32) -> Result<(), EngineError> {
+        self.check(unsafe { ffi::mpvss_ctx_set_rt_share_hash(self.ctx.0, mode) })
+    }
+
     /// For trait methods that cannot return an error (`Group::exp`): a failing engine is a programmer / hardware
     /// error there, as a panic in the reference's arithmetic crates would be.
     pub(crate) fn expect(&self, rc: i32, what: &str) {

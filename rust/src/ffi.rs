@@ -324,6 +324,12 @@ unsafe extern "C" {
                                                   alpha_dev: *const u8, c_host: *const u8, n: usize, r_dev_out: *mut u8) -> c_int;
     pub fn mpvss_modp_group_batch_scalar_mul(ctx: *mut mpvss_ctx, grp: *const mpvss_modp_group, space: c_int, a: *const u8, b: *const u8,
                                              n: usize, out: *mut u8) -> c_int;
+    // the per-share DLEQ hash of a run-time group on the device
+    pub fn mpvss_modp_group_has_device_share_hash(grp: *const mpvss_modp_group) -> c_int;
+    pub fn mpvss_ctx_set_rt_share_hash(ctx: *mut mpvss_ctx, mode: c_int) -> c_int;
+    pub fn mpvss_modp_group_share_hash_stats(ctx: *mut mpvss_ctx, device_calls: *mut c_ulonglong, host_calls: *mut c_ulonglong) -> c_int;
+    pub fn mpvss_modp_group_dleq_challenges(ctx: *mut mpvss_ctx, grp: *const mpvss_modp_group, space: c_int, h1: *const u8, h2: *const u8,
+                                            a1: *const u8, a2: *const u8, n: usize, c_out: *mut u8) -> c_int;
     // ---- key sets of a run-time group
     pub fn mpvss_modp_group_keyset_bytes_per_key(grp: *const mpvss_modp_group) -> usize;
     pub fn mpvss_modp_group_keyset_create(ctx: *mut mpvss_ctx, grp: *const mpvss_modp_group, space: c_int, pubkeys: *const u8, n: usize,

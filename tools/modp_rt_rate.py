@@ -37,7 +37,7 @@
               library (no gate).  All lines go to profiles/modp_rt_comb_rate.txt.
 
 Host buffers in and out (the calls' own staging included), best of `--reps` after one warm-up call.  One JSON line per
-measurement.  Usage: python tools/modp_rt_rate.py [--quick] [--reps 3] [--legs rates,twin,deal,comb,verify] [--comb | --fd | --scalar | --keyset] [--ab PARENT [--rounds 2]]
+measurement.  Usage: python tools/modp_rt_rate.py [--quick] [--reps 3] [--legs rates,twin,deal,comb,verify] [--comb | --fd | --scalar | --keyset | --share-hash] [--ab PARENT [--rounds 2]]
   fd          (--fd) X_i of a run-time group by forward differences: timer 0 of group_commit_eval at (4096, 64), (16384, 128),
               (65536, 256), 1024 and 2048 bits, per chain count, and whole group_verify_distribution calls; --fd --ab PARENT takes
               turns with a built checkout of the parent commit and writes profiles/modp_rt_fd_rate.txt (one 3072-bit row too).
@@ -58,7 +58,16 @@ measurement.  Usage: python tools/modp_rt_rate.py [--quick] [--reps 3] [--legs r
   --keyset --ab PARENT  fresh processes of a built checkout of the parent commit and of this build take turns, best of the rounds,
               into profiles/modp_rt_keyset_rate.txt.  The gate, at n = 65536 and 2048 bits: the key-set a2 launch against the
               parent's a2 launch, at least 2x required (the operation counts say 3.65x); below 1x the kernels do not ship.  The
-              twin ratio is recorded and not gated."""
+              twin ratio is recorded and not gated.
+  share-hash  (--share-hash) the per-share DLEQ hash of a run-time group on the device: whole group_verify_shares and
+              group_extract_shares calls at n = 1024, 4096, 65536 for 1024 and 2048 bits from host buffers, plus one row with the
+              arrays in device memory (group_verify_shares, 2048 bits, n = 65536; torch tensors); --share-hash-wide: the one 3072-bit
+              row, both calls at n = 16384.  --share-hash-parts parent: the library under test as it is (every share hashed on the
+              host before this path existed); mode2: mpvss_ctx_set_rt_share_hash(2), with the time of the hash launches (timer 5).
+  --share-hash --ab PARENT  fresh processes of a built checkout of the parent commit and of this build under mode 2 take turns,
+              best of the rounds, into profiles/modp_rt_share_hash_rate.txt.  rt_share_hash_min_shares is the smallest measured n
+              from which mode 2's whole call is no slower than the parent's at every larger measured n (1 if that holds
+              everywhere).  The gate, at n = 65536: mode 2 no slower than the parent beyond the spread of the parent's own rounds."""
 import argparse
 import json
 import os
@@ -441,6 +450,96 @@ def ab_scalar(a):
             f.write(json.dumps(row) + "\n")
 
 
+SHARE_HASH_SIZES = [1024, 4096, 65536]
+
+
+def share_hash_leg(eng, a, rng):
+    mode2 = a.share_hash_parts == "mode2"
+    if mode2:
+        eng.set_rt_share_hash(2)
+    if a.share_hash_wide:
+        import modp_rt_wide_helpers as WH
+        groups, sizes = [(3072, ModpGroup(WH.group15(), elem_bytes=WH.EB), WH.EB)], [4096 if a.quick else 16384]
+    else:
+        groups = [(bits, ModpGroup(H.rfc_prime(bits)), 256) for bits in (1024, 2048)]
+        sizes = SHARE_HASH_SIZES[:2] if a.quick else SHARE_HASH_SIZES
+
+    def rb(n, bits, eb):
+        return b"".join(rng.getrandbits(bits).to_bytes(eb, "big") for _ in range(n))
+
+    def emit(call, bits, n, space, s):
+        row = {"what": "share_hash", "call": call, "bits": bits, "n": n, "space": space, "whole_s": round(s, 5)}
+        if mode2:
+            row["hash_kernel_ms"] = round(max(0.0, eng.kernel_ms(5)), 3)
+            row["hash_launches"] = eng.kernel_launches(5)
+        print(json.dumps(row), flush=True)
+
+    for bits, grp, eb in groups:
+        for n in sizes:
+            pk, s_, y, r = (rb(n, bits - 1, eb) for _ in range(4))
+            c = rb(n, 256, eb)
+            emit("group_verify_shares", bits, n, "host", best(lambda: eng.group_verify_shares(grp, pk, s_, y, c, r), a.reps))
+            xi, w = rb(n, bits - 1, eb), rb(n, bits - 1, eb)
+            emit("group_extract_shares", bits, n, "host", best(lambda: eng.group_extract_shares(grp, pk, y, xi, w), a.reps))
+            if bits == 2048 and n == sizes[-1]:                 # the one device-space row: the five arrays are torch tensors
+                import ctypes as C
+                import torch
+                dev = [torch.frombuffer(bytearray(b), dtype=torch.uint8).cuda() for b in (pk, s_, y, c, r)]
+                out = (C.c_uint8 * n)()
+                torch.cuda.synchronize()
+
+                def call():
+                    rc = eng.lib.mpvss_modp_group_verify_shares(eng.ctx, grp.handle, capi.MPVSS_DEVICE, *(C.c_void_p(t.data_ptr()) for t in dev),
+                                                                n, out)
+                    assert rc == 0, eng.last_error()
+
+                emit("group_verify_shares", bits, n, "device", best(call, a.reps))
+
+
+def ab_share_hash(a):
+    """--share-hash --ab PARENT: fresh processes of the parent build and of this build under mode 2 take turns; best of the rounds"""
+    if not os.path.exists(os.path.join(a.ab, "mpvss_rs_amd", "libmpvss_hip.so")):
+        sys.exit("modp_rt_rate --share-hash --ab: the parent checkout is not built")
+    common = ["--legs", "share_hash", "--share-hash", "--reps", str(a.reps)] + (["--quick"] if a.quick else [])
+    lines, per_round, kern = [], {}, {}
+    for wide in ([], ["--share-hash-wide"]):
+        for rnd in range(a.rounds):
+            for part, extra in (("parent", ["--package-root", a.ab]), ("mode2", [])):
+                for row in child(common + wide + ["--share-hash-parts", part] + extra, None, [], a.deal_limit):
+                    row.update(part=part, round=rnd)
+                    key = (part, row["call"], row["bits"], row["space"], row["n"])
+                    per_round.setdefault(key, []).append(row["whole_s"])
+                    if "hash_kernel_ms" in row:
+                        kern[key] = min(kern.get(key, row["hash_kernel_ms"]), row["hash_kernel_ms"])
+                    lines.append(row)
+    shapes = sorted({k[1:4] for k in per_round})
+    for call, bits, space in shapes:
+        sizes = sorted({k[4] for k in per_round if k[1:4] == (call, bits, space)})
+        ok = []
+        for n in sizes:
+            pa, m2 = per_round["parent", call, bits, space, n], per_round["mode2", call, bits, space, n]
+            spread = round(max(pa) - min(pa), 5)
+            ok.append(min(m2) <= min(pa))
+            lines.append({"what": "share_hash_ab", "call": call, "bits": bits, "space": space, "n": n, "parent_whole_s": min(pa),
+                          "parent_rounds_s": pa, "parent_spread_s": spread, "mode2_whole_s": min(m2), "mode2_rounds_s": m2,
+                          "mode2_hash_kernel_ms": kern.get(("mode2", call, bits, space, n)), "parent_over_mode2": round(min(pa) / min(m2), 3)})
+            if n == 65536:
+                lines.append({"what": "share_hash_gate", "call": call, "bits": bits, "space": space, "n": n,
+                              "mode2_minus_parent_s": round(min(m2) - min(pa), 5), "parent_spread_s": spread,
+                              "met": min(m2) <= min(pa) + spread})
+        if space == "host":
+            first = next((sizes[i] for i in range(len(sizes)) if all(ok[i:])), None)
+            lines.append({"what": "share_hash_crossover", "call": call, "bits": bits, "min_shares": 1 if first == sizes[0] else first,
+                          "measured_sizes": sizes})
+    for row in lines:
+        if row["what"].startswith("share_hash_"):
+            print(json.dumps(row), flush=True)
+    os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+    with open(a.out, "w") as f:
+        for row in lines:
+            f.write(json.dumps(row) + "\n")
+
+
 KEYSET_SIZES = [4096, 16384, 65536]
 
 
@@ -601,6 +700,9 @@ def main():
     ap.add_argument("--keyset", action="store_true", help="key sets of a run-time group: alone, the keyset leg; with --ab, its interleaved A/B")
     ap.add_argument("--keyset-parts", default="keyset", help="of the keyset leg: parent (the launches without a set), keyset (build and launches over a set)")
     ap.add_argument("--keyset-wide", action="store_true", help="of the keyset leg: the one 3072-bit row, n = 16384")
+    ap.add_argument("--share-hash", action="store_true", help="the per-share hash on the device: alone, the share-hash leg; with --ab, its interleaved A/B")
+    ap.add_argument("--share-hash-parts", default="mode2", help="of the share-hash leg: parent (the library under test as it is), mode2 (set_rt_share_hash(2))")
+    ap.add_argument("--share-hash-wide", action="store_true", help="of the share-hash leg: the one 3072-bit row, n = 16384")
     ap.add_argument("--package-root", default=None, help="import mpvss_rs_amd (bindings and library) from this checkout")
     ap.add_argument("--ab", default=None, metavar="PARENT", help="the interleaved A/B against a built checkout of the parent commit")
     ap.add_argument("--rounds", type=int, default=2, help="of --ab: how often the three processes take turns")
@@ -609,9 +711,9 @@ def main():
     ap.add_argument("--out", default=None, help="of --ab: the file written (profiles/modp_rt_deal_rate.txt, or _comb_rate.txt)")
     a = ap.parse_args()
     if a.out is None:
-        a.out = os.path.join(ROOT, "profiles", "modp_rt_keyset_rate.txt" if a.keyset else "modp_rt_scalar_rate.txt" if a.scalar else "modp_rt_fd_rate.txt" if a.fd else "modp_rt_comb_rate.txt" if a.comb else "modp_rt_deal_rate.txt")
+        a.out = os.path.join(ROOT, "profiles", "modp_rt_share_hash_rate.txt" if a.share_hash else "modp_rt_keyset_rate.txt" if a.keyset else "modp_rt_scalar_rate.txt" if a.scalar else "modp_rt_fd_rate.txt" if a.fd else "modp_rt_comb_rate.txt" if a.comb else "modp_rt_deal_rate.txt")
     if a.ab:
-        return ab_keyset(a) if a.keyset else ab_scalar(a) if a.scalar else ab_fd(a) if a.fd else ab_comb(a) if a.comb else ab(a)
+        return ab_share_hash(a) if a.share_hash else ab_keyset(a) if a.keyset else ab_scalar(a) if a.scalar else ab_fd(a) if a.fd else ab_comb(a) if a.comb else ab(a)
     if a.comb:
         a.legs = "comb"
     if a.fd:
@@ -620,6 +722,9 @@ def main():
         a.legs = "scalar"
     if a.keyset:
         a.legs = "keyset"
+    if a.share_hash:
+        a.legs = "share_hash"
+        import torch  # noqa: F401  (its own HIP runtime must be loaded before the library's, for the device-space row)
     load_package(a.package_root)
     eng = Engine(0)
     rng = random.Random(1)
@@ -638,6 +743,8 @@ def main():
         scalar_leg(eng, a, rng)
     if "keyset" in legs:
         keyset_leg(eng, a, rng)
+    if "share_hash" in legs:
+        share_hash_leg(eng, a, rng)
     if "rates" not in legs:
         eng.close()
         return
