@@ -496,6 +496,37 @@ int mpvss_modp_reconstruct(mpvss_ctx* ctx, int space, const int64_t* positions_h
 int mpvss_ec_reconstruct(mpvss_ctx* ctx, int group, int space, const int64_t* positions_host, const uint8_t* shares, size_t m,
                          uint8_t* gs_out, uint8_t* mask_out32);
 
+/* Many secrets of a curve group in one call: the contract of mpvss_modp_group_reconstruct_many (below, run-time MODP groups) with
+ * the group's encoding length L (33 / 32) as the element size.  For every secret i that mpvss_ec_reconstruct accepts,
+ * status[i] == MPVSS_OK and gs_out[i L .. i L + L - 1] and masks_out32[32 i .. 32 i + 31] (optional) are what that call gives for
+ * (positions_host, shares, m) on the same context, byte for byte, in both spaces and for both curves; in device space the share
+ * buffers are left unchanged.  The Lagrange coefficients are computed once per distinct position list of the call (lists are equal
+ * when their sequences are: a permuted list is another list).  Runs of consecutive secrets of at most 16384 shares each travel
+ * through the GPU as one batch of at most MPVSS_MAX_CHUNK shares, one wave per secret for the sum; every longer secret, and a run
+ * of one, takes the one-secret path.
+ * shares live in `space`; positions_host, secrets, status, gs_out and masks_out32 are host memory.  The call is synchronous and
+ * holds the context lock like its one-secret sibling.  host_threads: up to that many host threads compute the Lagrange
+ * coefficients and the masks (clamped to 1..16; <= 0: the library chooses from the work of the call, at most 16, never by the
+ * machine's CPU count).
+ * ERRORS: no context is MPVSS_E_INVALID, an unknown group MPVSS_E_UNSUPPORTED; count == 0 is MPVSS_OK; secrets, status or gs_out
+ * NULL with count > 0 are MPVSS_E_INVALID; all of these write no output.  A refused secret -- whatever the one-secret call answers
+ * with MPVSS_E_INVALID: a pointer NULL, m == 0, m above 0x7fffffff, a position below 1, duplicate positions, a share that is not a
+ * valid encoding -- costs only itself: that code in status[i], zeros in gs_out[i] and in its mask, and the call goes on and returns
+ * MPVSS_OK.  A HIP error or a failed allocation ends the call with the code the one-secret call returns and leaves the context
+ * usable.
+ * mpvss_ec_reconstruct_many_stats: since the context was created, the grouped passes, the secrets that went through them and the
+ * secrets that took the one-secret path (refused secrets are in none; both curves count together); any pointer may be NULL, no
+ * context is MPVSS_E_INVALID. */
+typedef struct mpvss_ec_secret {
+  const int64_t* positions_host;   /* m positions, host memory in either space */
+  const uint8_t* shares;           /* m encoded elements (33 / 32 bytes each), in `space` */
+  size_t m;
+} mpvss_ec_secret;
+int mpvss_ec_reconstruct_many(mpvss_ctx* ctx, int group, int space, const mpvss_ec_secret* secrets, size_t count,
+                              int host_threads, int* status, uint8_t* gs_out, uint8_t* masks_out32);
+int mpvss_ec_reconstruct_many_stats(mpvss_ctx* ctx, unsigned long long* passes, unsigned long long* grouped_secrets,
+                                    unsigned long long* single_secrets);
+
 /* ---- flat wire format of a DistributionSharesBox ("MPVSSBX1") ---------------------------------------------------------
  * The reference keeps a box as three HashMap<Vec<u8>, _> (src/sharebox.rs:74-86) and defines no serialisation.  This
  * format is the boundary's own layout -- rows in `publickeys` order (the order src/participant.rs:408-448 iterates in),

@@ -66,6 +66,7 @@ EXPORTED_SYMBOLS = (
     "mpvss_modp_group_verify_distribution_keyset", "mpvss_modp_group_deal_keyset",
     "mpvss_modp_group_verify_many", "mpvss_modp_group_verify_many_stats",
     "mpvss_modp_group_reconstruct_many", "mpvss_modp_group_reconstruct_many_stats",
+    "mpvss_ec_reconstruct_many", "mpvss_ec_reconstruct_many_stats",
 )
 
 GROUP_SECP256K1 = 1
@@ -96,6 +97,11 @@ class GroupBox(C.Structure):
 
 class GroupSecret(C.Structure):
     """struct mpvss_modp_group_secret"""
+    _fields_ = [("positions_host", C.c_void_p), ("shares", C.c_void_p), ("m", C.c_size_t)]
+
+
+class EcSecret(C.Structure):
+    """struct mpvss_ec_secret"""
     _fields_ = [("positions_host", C.c_void_p), ("shares", C.c_void_p), ("m", C.c_size_t)]
 
 
@@ -222,6 +228,9 @@ def load_library() -> C.CDLL:
     lib.mpvss_ec_poly_eval.argtypes = [ci, u8p, sz, i64p, sz, u8p, ci]
     lib.mpvss_modp_reconstruct.argtypes = [vp, ci, i64p, u8p, sz, u8p, u8p]
     lib.mpvss_ec_reconstruct.argtypes = [vp, ci, ci, i64p, u8p, sz, u8p, u8p]
+    lib.mpvss_ec_reconstruct_many.argtypes = [vp, ci, ci, C.POINTER(EcSecret), sz, ci, C.POINTER(ci), u8p, u8p]
+    lib.mpvss_ec_reconstruct_many_stats.argtypes = [vp, C.POINTER(C.c_ulonglong), C.POINTER(C.c_ulonglong),
+                                                    C.POINTER(C.c_ulonglong)]
     lib.mpvss_ec_verify_block_compute.argtypes = [vp, ci, ci, u8p, sz, i64p, u8p, u8p, u8p, sz, u8p]
     lib.mpvss_ec_verify_block_absorb.argtypes = [vp, u8p, u8p, u8p, u8p]
     lib.mpvss_ec_transcript_absorb.argtypes = [ci, u8p, u8p, sz]
@@ -1212,6 +1221,54 @@ class Engine:
     def ec_reconstruct_device(self, group: int, positions: Sequence[int], shares_dev_ptr: int, m: int, want_mask: bool = True):
         """ec_reconstruct with the m encoded shares in HBM (left unchanged); positions stay host memory"""
         return self._reconstruct(group, MPVSS_DEVICE, positions, C.c_void_p(shares_dev_ptr), m, want_mask)
+
+    # ---- many secrets of a curve group in one call -------------------------------------------------------------------------
+    def _ec_reconstruct_many(self, group: int, space: int, arr, count: int, host_threads: int, want_masks: bool):
+        L = EC_ENC[group]
+        status = (C.c_int * max(count, 1))()
+        kg, pg = _out(count * L)
+        km, pm = _out(32 * count) if want_masks else (None, None)
+        self._check(self.lib.mpvss_ec_reconstruct_many(self.ctx, group, space, arr, count, int(host_threads), status, pg, pm),
+                    "ec_reconstruct_many")
+        gs = bytes(kg)
+        masks = bytes(km) if want_masks else None
+        return [(int(status[i]), gs[i * L:(i + 1) * L], masks[32 * i:32 * i + 32] if want_masks else None) for i in range(count)]
+
+    def ec_reconstruct_many(self, group: int, secrets: Sequence[dict], host_threads: int = 0, want_masks: bool = True):
+        """secrets: dicts with positions (a sequence of int) and shares (host bytes); None: a null pointer.  Returns
+        [(status, G^s, mask)] in the order given: for status 0 what ec_reconstruct gives secret by secret, the Lagrange
+        coefficients computed once per distinct position list and small secrets travelling in groups; a refused secret has
+        status -1, zeros for G^s and a mask of zeros."""
+        L = EC_ENC[group]
+        keep, arr = [], (EcSecret * max(len(secrets), 1))()
+        for i, s in enumerate(secrets):
+            positions, shares = s.get("positions"), s.get("shares")
+            m = len(positions) if positions is not None else len(shares or b"") // L
+            pos = (C.c_int64 * max(m, 1))(*positions) if positions is not None else None
+            ks, ps = _buf(shares or None)
+            keep.append((pos, ks))
+            arr[i] = EcSecret(C.cast(pos, C.c_void_p) if pos is not None else None, ps, m)
+        return self._ec_reconstruct_many(group, MPVSS_HOST, arr, len(secrets), host_threads, want_masks)
+
+    def ec_reconstruct_many_device(self, group: int, secrets: Sequence[dict], host_threads: int = 0, want_masks: bool = True):
+        """the same with the encoded shares of every secret in HBM (left unchanged): dicts with positions (host), shares_ptr
+        and m"""
+        keep, arr = [], (EcSecret * max(len(secrets), 1))()
+        for i, s in enumerate(secrets):
+            positions = s.get("positions")
+            m = int(s["m"])
+            pos = (C.c_int64 * max(len(positions), 1))(*positions) if positions is not None else None
+            keep.append(pos)
+            arr[i] = EcSecret(C.cast(pos, C.c_void_p) if pos is not None else None,
+                              C.c_void_p(s["shares_ptr"]) if s.get("shares_ptr") else None, m)
+        return self._ec_reconstruct_many(group, MPVSS_DEVICE, arr, len(secrets), host_threads, want_masks)
+
+    def ec_reconstruct_many_stats(self) -> dict:
+        """since the context was created: grouped passes, secrets that went through them, secrets that took the one-secret path"""
+        p, g, s = C.c_ulonglong(0), C.c_ulonglong(0), C.c_ulonglong(0)
+        self._check(self.lib.mpvss_ec_reconstruct_many_stats(self.ctx, C.byref(p), C.byref(g), C.byref(s)),
+                    "ec_reconstruct_many_stats")
+        return {"passes": int(p.value), "grouped_secrets": int(g.value), "single_secrets": int(s.value)}
 
     def ec_batch_exp_generator(self, group: int, scalars: bytes) -> bytes:
         n = len(scalars) // 32

@@ -198,7 +198,7 @@ struct EcBase {
 
 // out_enc[x] = k1[x] * B1[x] + k2[x] * B2[x] for n shares on ctx->stream (b2 == null: out = k1 * B1).
 // Window tables go to tabA / tabB, the internal results to pout; ok1 / ok2 (device, n bytes each, may be null) receive
-// the validity of decoded bases.
+// the validity of decoded bases.  out_enc may be null: the results stay in pout alone.
 int ec_dual(mpvss_ctx* ctx, const EcInfo* gi, const EcBase& b1, const uint8_t* k1, size_t k1_stride, const EcBase* b2,
             const uint8_t* k2, size_t k2_stride, size_t n, DevBuf& tabA, DevBuf& tabB, DevBuf& pout, uint8_t* out_enc,
             uint8_t* ok1, uint8_t* ok2) {
@@ -230,7 +230,8 @@ int ec_dual(mpvss_ctx* ctx, const EcInfo* gi, const EcBase& b1, const uint8_t* k
   RET_IF(ensure(ctx, pout, n * (size_t)ec_point_words(group) * 4));
   TIMED_LAUNCH(ctx, 1, ec_launch_dual_win(group, comb, t1, k1, k1_stride, t2, k2, k2_stride, (int)n, (uint32_t*)pout.p,
                                           ctx->stream));
-  TIMED_LAUNCH(ctx, 3, ec_launch_encode(group, (const uint32_t*)pout.p, (int)n, out_enc, ctx->stream));
+  // (out_enc == null: the caller goes on with the internal points in pout and nobody reads the encodings -- a reconstruct pass)
+  if (out_enc != nullptr) TIMED_LAUNCH(ctx, 3, ec_launch_encode(group, (const uint32_t*)pout.p, (int)n, out_enc, ctx->stream));
   return 0;
 }
 

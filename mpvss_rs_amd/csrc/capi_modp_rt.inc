@@ -2222,11 +2222,7 @@ struct RtSecretPlan {
   size_t coef = (size_t)-1;
 };
 
-// host threads of a call: what the caller asked for, or one per `per_thread` items of work; 1 .. 16, never the machine's count
-int rt_many_threads(int requested, size_t work, size_t per_thread) {
-  const size_t nth = requested > 0 ? (size_t)requested : work / per_thread;
-  return (int)std::min<size_t>(std::max<size_t>(nth, 1), 16);
-}
+// (host threads of a call: rt_many_threads, capi_scalar.inc -- shared with mpvss_ec_reconstruct_many)
 
 // a grouped pass: the secrets run[0 .. B) (indices into `secrets`, all RT_SECRET_GROUPED), shares in all <= MAX_CHUNK.  The
 // launches of one secret over the concatenation, then one k_rt_product_segments launch and one settle.  A secret with a share that

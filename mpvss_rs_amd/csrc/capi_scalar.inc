@@ -49,6 +49,12 @@ int host_threads(int requested) {
   const unsigned hc = std::thread::hardware_concurrency();
   return hc == 0 ? 1 : (hc > 16 ? 16 : (int)hc);
 }
+// host threads of a many-secrets call (mpvss_modp_group_reconstruct_many, mpvss_ec_reconstruct_many): what the caller asked for, or
+// one per `per_thread` items of work; 1 .. 16, never the machine's count
+int rt_many_threads(int requested, size_t work, size_t per_thread) {
+  const size_t nth = requested > 0 ? (size_t)requested : work / per_thread;
+  return (int)std::min<size_t>(std::max<size_t>(nth, 1), 16);
+}
 
 // generic bodies over (N limbs, byte width, endianness); Mod: hsc::Modulus<N>, or hsc::ModulusRt for N = 32
 template <int N, class Mod>
@@ -748,30 +754,52 @@ extern "C" int mpvss_modp_reconstruct(mpvss_ctx* ctx, int space, const int64_t* 
   return MPVSS_OK;
 }
 
-extern "C" int mpvss_ec_reconstruct(mpvss_ctx* ctx, int group, int space, const int64_t* positions_host, const uint8_t* shares,
-                                    size_t m, uint8_t* gs_out, uint8_t* mask_out32) {
-  EC_PROLOGUE("ec_reconstruct");
+namespace {
+
+// lambda_i of a position list as the 32-byte scalar the kernels multiply a share by: |lambda_i| mod the order, the order's
+// complement for a negative non-zero coefficient (-(lambda S) = (order - lambda) S, participant.rs:1546-1555), in the group's scalar
+// byte order.  False: duplicate positions.  One place for the one-secret call and for mpvss_ec_reconstruct_many.
+bool ec_lagrange_scalar(const EcInfo* gi, const int64_t* pos, size_t m, size_t i, uint8_t* out32) {
+  uint64_t e[4];
+  char neg = 0;
+  if (!lagrange_coefficient_at_zero<4>(ec_order(gi), pos, m, i, e, &neg)) return false;
+  if (neg && (e[0] | e[1] | e[2] | e[3])) hsc::sub_n<4>(e, ec_order(gi).m, e);
+  hsc::to_bytes<4>(out32, e, gi->scalar_be);
+  return true;
+}
+// SHA256(bytes(G^s)) as a big-endian integer, reduced mod the group order (participant.rs:1495-1508, 1939-1946);
+// secp256k1's Scalar::from_repr(...).unwrap() panics for a digest >= n (p ~ 2^-128): reduced here instead
+void ec_secret_mask(const EcInfo* gi, const uint8_t* gs, uint8_t* mask_out32) {
+  uint8_t h[32];
+  mpvss::sha256(gs, gi->enc, h);
+  uint64_t x[4];
+  hsc::from_bytes<4>(x, h, true);
+  ec_order(gi).reduce1(x);
+  hsc::to_bytes<4>(mask_out32, x, true);
+}
+
+// one secret under the context lock (mpvss_ec_reconstruct, and the one-secret path of mpvss_ec_reconstruct_many).  scalars_pre: the
+// m scalars of ec_lagrange_scalar when the caller has them already (computed with the call's other position lists), else null.
+int ec_reconstruct_locked(mpvss_ctx* ctx, const EcInfo* gi, EcWork& w, int space, const int64_t* positions_host, const uint8_t* shares,
+                          size_t m, uint8_t* gs_out, uint8_t* mask_out32, const uint8_t* scalars_pre) {
+  const int group = gi->group;
   if (!positions_host || !shares || m == 0 || !gs_out || m > 0x7fffffff) return fail(ctx, MPVSS_E_INVALID, "ec_reconstruct: bad argument");
   // a box's positions are 1..n (participant.rs:1127, 1600); the coefficient of a position <= 0 would multiply `j as u64` into
   // the numerator and the signed difference into the denominator, which is no Lagrange coefficient: refused as for MODP
   for (size_t i = 0; i < m; ++i)
     if (positions_host[i] < 1) return fail(ctx, MPVSS_E_INVALID, "ec_reconstruct: positions must be >= 1");
-  std::vector<hsc::Num<4>> mag;
-  std::vector<char> neg;
-  if (!lagrange_at_zero<4>(ec_order(gi), positions_host, m, mag, neg, true))
-    return fail(ctx, MPVSS_E_INVALID, "ec_reconstruct: duplicate positions");
-  // lambda * S, negated for a negative coefficient (participant.rs:1546-1555): -(lambda S) = (order - lambda) S
-  std::vector<uint8_t> ks(m * 32);
-  for (size_t i = 0; i < m; ++i) {
-    uint64_t e[4];
-    memcpy(e, mag[i].v, sizeof(e));
-    if (neg[i] && (e[0] | e[1] | e[2] | e[3])) hsc::sub_n<4>(e, ec_order(gi).m, e);
-    hsc::to_bytes<4>(ks.data() + i * 32, e, gi->scalar_be);
+  // lambda * S, negated for a negative coefficient (participant.rs:1546-1555)
+  std::vector<uint8_t> ks;
+  if (!scalars_pre) {
+    ks.resize(m * 32);
+    for (size_t i = 0; i < m; ++i)
+      if (!ec_lagrange_scalar(gi, positions_host, m, i, ks.data() + i * 32)) return fail(ctx, MPVSS_E_INVALID, "ec_reconstruct: duplicate positions");
+    scalars_pre = ks.data();
   }
   const void* dS;
   RET_IF(stage_in(ctx, space, shares, m * gi->enc, w.a, &dS));
   RET_IF(ensure(ctx, w.d, m * 32));
-  HIPCHK(ctx, hipMemcpyAsync(w.d.p, ks.data(), m * 32, hipMemcpyHostToDevice, ctx->stream));
+  HIPCHK(ctx, hipMemcpyAsync(w.d.p, scalars_pre, m * 32, hipMemcpyHostToDevice, ctx->stream));
   HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
   RET_IF(ensure(ctx, w.ok, m > 4096 ? m : 4096));
   RET_IF(ensure(ctx, w.o1, (m + 1) * gi->enc));
@@ -787,16 +815,228 @@ extern "C" int mpvss_ec_reconstruct(mpvss_ctx* ctx, int group, int space, const 
   HIPCHK(ctx, hipMemcpyAsync(gs, dF, gi->enc, hipMemcpyDeviceToHost, ctx->stream));
   RET_IF(ec_check_ok(ctx, (const uint8_t*)w.ok.p, m, "ec_reconstruct shares"));
   memcpy(gs_out, gs, gi->enc);
-  if (mask_out32) {
-    // SHA256(bytes(G^s)) as a big-endian integer, reduced mod the group order (participant.rs:1495-1508, 1939-1946);
-    // secp256k1's Scalar::from_repr(...).unwrap() panics for a digest >= n (p ~ 2^-128): reduced here instead
-    uint8_t h[32];
-    mpvss::sha256(gs, gi->enc, h);
-    uint64_t x[4];
-    hsc::from_bytes<4>(x, h, true);
-    ec_order(gi).reduce1(x);
-    hsc::to_bytes<4>(mask_out32, x, true);
-  }
+  if (mask_out32) ec_secret_mask(gi, gs, mask_out32);
   RET_IF(spans_collect(ctx));
+  return MPVSS_OK;
+}
+
+}  // namespace
+
+extern "C" int mpvss_ec_reconstruct(mpvss_ctx* ctx, int group, int space, const int64_t* positions_host, const uint8_t* shares,
+                                    size_t m, uint8_t* gs_out, uint8_t* mask_out32) {
+  EC_PROLOGUE("ec_reconstruct");
+  return ec_reconstruct_locked(ctx, gi, w, space, positions_host, shares, m, gs_out, mask_out32, nullptr);
+}
+
+// =====================================================================================================================
+// Many secrets of a curve group in one call (DESIGN section 13, "Many secrets in one call, curve groups"):
+// mpvss_ec_reconstruct_many, the curve counterpart of mpvss_modp_group_reconstruct_many (capi_modp_rt.inc).  One secret per call is
+// a quadratic Lagrange loop on one host thread, two synchronisations and three launches of one partial workgroup each; here the
+// coefficients are computed once per distinct position list on the call's host threads, and runs of secrets travel as ONE dense
+// concatenation of shares through the launches of one secret, the fold replaced by one k_*_sum_segments launch (one wave per
+// secret).  THE grouping decision is in mpvss_ec_reconstruct_many below.
+// =====================================================================================================================
+namespace {
+
+// shares of one secret that may travel in a pass (the project's RT_GROUP_BOX_MAX; DESIGN section 13 has the measurement it rests on)
+constexpr size_t EC_GROUP_SECRET_MAX = 16384;
+
+enum EcSecretKind { EC_SECRET_REFUSED, EC_SECRET_GROUPED, EC_SECRET_SINGLE };
+
+// what the host knows of a secret before anything is launched: its kind, and where the scalars of its position list start in the
+// call's array (npos for a secret that computes its own)
+struct EcSecretPlan {
+  EcSecretKind kind = EC_SECRET_REFUSED;
+  size_t coef = (size_t)-1;
+};
+
+// a grouped pass: the secrets run[0 .. B) (indices into `secrets`, all EC_SECRET_GROUPED), S <= MAX_CHUNK shares in all.  The
+// launches of one secret over the concatenation -- the S factors are never encoded -- then one sum per secret into B dense points,
+// one encode of those and one synchronisation.  A secret with a share that is no valid encoding is refused here: its sum ran with
+// the others and is dropped.
+int ec_reconstruct_pass(mpvss_ctx* ctx, const EcInfo* gi, EcWork& w, int space, const mpvss_ec_secret* secrets,
+                        const std::vector<size_t>& run, const std::vector<EcSecretPlan>& plan, const uint8_t* scalars, int host_threads,
+                        int* status, uint8_t* gs_out, uint8_t* masks_out32) {
+  const int group = gi->group;
+  const size_t B = run.size(), L = gi->enc;
+  std::vector<uint32_t> segs(2 * B);                                // {first factor, m} of every secret
+  size_t S = 0;
+  for (size_t k = 0; k < B; ++k) {
+    segs[2 * k] = (uint32_t)S;
+    segs[2 * k + 1] = (uint32_t)secrets[run[k]].m;
+    S += secrets[run[k]].m;
+  }
+  // host sources of asynchronous copies and the results read back: declared before the guard, whose way out drains the stream
+  std::vector<uint8_t> g_sh, g_k(S * 32), h_enc(B * L), h_ok(S);
+  std::vector<const uint8_t*> srcs;
+  struct Drain {            // no copy out of (or into) the vectors above outlives them, whichever way the pass ends
+    mpvss_ctx* c;
+    ~Drain() { (void)hipStreamSynchronize(c->stream); }
+  } drain{ctx};
+  spans_reset(ctx);
+  for (size_t k = 0; k < B; ++k) memcpy(g_k.data() + (size_t)segs[2 * k] * 32, scalars + plan[run[k]].coef * 32, secrets[run[k]].m * 32);
+  RET_IF(ensure(ctx, w.a, S * L));
+  RET_IF(ensure(ctx, w.b, segs.size() * 4));
+  RET_IF(ensure(ctx, w.d, S * 32));
+  RET_IF(ensure(ctx, w.ok, S > 4096 ? S : 4096));
+  RET_IF(ensure(ctx, w.p2, B * (size_t)ec_point_words(group) * 4));
+  RET_IF(ensure(ctx, w.o1, (B + 1) * L));
+  HIPCHK(ctx, hipMemcpyAsync(w.b.p, segs.data(), segs.size() * 4, hipMemcpyHostToDevice, ctx->stream));
+  if (space == MPVSS_HOST) {
+    g_sh.resize(S * L);
+    for (size_t k = 0; k < B; ++k) memcpy(g_sh.data() + (size_t)segs[2 * k] * L, secrets[run[k]].shares, secrets[run[k]].m * L);
+    HIPCHK(ctx, hipMemcpyAsync(w.a.p, g_sh.data(), S * L, hipMemcpyHostToDevice, ctx->stream));
+  } else {                  // every secret's shares lie in a device buffer of their own: one gather launch, not B copies
+    srcs.resize(B);
+    for (size_t k = 0; k < B; ++k) srcs[k] = secrets[run[k]].shares;
+    RET_IF(ensure(ctx, w.c, B * sizeof(const uint8_t*)));
+    HIPCHK(ctx, hipMemcpyAsync(w.c.p, srcs.data(), B * sizeof(const uint8_t*), hipMemcpyHostToDevice, ctx->stream));
+    LAUNCHCHK(ctx, ec_launch_gather_segments((const uint8_t* const*)w.c.p, (const uint32_t*)w.b.p, (int)B, (uint32_t)L, (uint8_t*)w.a.p,
+                                             ctx->stream));
+  }
+  HIPCHK(ctx, hipMemcpyAsync(w.d.p, g_k.data(), S * 32, hipMemcpyHostToDevice, ctx->stream));
+  EcBase b1;
+  b1.enc = (const uint8_t*)w.a.p;
+  b1.enc_stride = L;
+  RET_IF(ec_dual(ctx, gi, b1, (const uint8_t*)w.d.p, 32, nullptr, nullptr, 0, S, w.tab1, w.tab2, w.p1, nullptr, (uint8_t*)w.ok.p, nullptr));
+  LAUNCHCHK(ctx, ec_launch_sum_segments(group, (const uint32_t*)w.p1.p, (const uint32_t*)w.b.p, (int)B, (uint32_t*)w.p2.p, ctx->stream));
+  LAUNCHCHK(ctx, ec_launch_encode(group, (const uint32_t*)w.p2.p, (int)B, (uint8_t*)w.o1.p, ctx->stream));
+  HIPCHK(ctx, hipMemcpyAsync(h_enc.data(), w.o1.p, B * L, hipMemcpyDeviceToHost, ctx->stream));
+  HIPCHK(ctx, hipMemcpyAsync(h_ok.data(), w.ok.p, S, hipMemcpyDeviceToHost, ctx->stream));
+  RET_IF(spans_collect(ctx));                                       // the pass's one synchronisation
+  std::vector<char> refused(B, 0);
+  size_t good = 0;
+  for (size_t k = 0; k < B; ++k) {
+    const uint8_t* ok = h_ok.data() + segs[2 * k];
+    refused[k] = std::find(ok, ok + segs[2 * k + 1], 0) != ok + segs[2 * k + 1];
+    if (!refused[k]) ++good;
+  }
+  hsc::parallel_for(B, rt_many_threads(host_threads, B, 256), [&](size_t lo, size_t hi) {
+    for (size_t k = lo; k < hi; ++k) {
+      if (refused[k]) continue;
+      const size_t i = run[k];
+      memcpy(gs_out + i * L, h_enc.data() + k * L, L);
+      if (masks_out32) ec_secret_mask(gi, h_enc.data() + k * L, masks_out32 + 32 * i);
+      status[i] = MPVSS_OK;
+    }
+  });
+  if (good) {
+    ++ctx->ec_rec_passes;
+    ctx->ec_rec_grouped_secrets += good;
+  }
+  return MPVSS_OK;
+}
+
+}  // namespace
+
+extern "C" int mpvss_ec_reconstruct_many(mpvss_ctx* ctx, int group, int space, const mpvss_ec_secret* secrets, size_t count,
+                                         int host_threads, int* status, uint8_t* gs_out, uint8_t* masks_out32) {
+  EC_PROLOGUE("ec_reconstruct_many");
+  if (count == 0) return MPVSS_OK;
+  if (!secrets || !status || !gs_out) return fail(ctx, MPVSS_E_INVALID, "ec_reconstruct_many: bad argument");
+  const size_t L = gi->enc;
+  // a refused secret has no result: its status, zeros in gs and in its mask.  Every secret is refused until it has its result.
+  for (size_t i = 0; i < count; ++i) status[i] = MPVSS_E_INVALID;
+  memset(gs_out, 0, count * L);
+  if (masks_out32) memset(masks_out32, 0, 32 * count);
+
+  // the arguments of every secret, as the one-secret call judges them; then the Lagrange scalars ONCE per distinct position list
+  // -- the sequences equal element by element: a permuted list is another list, coefficients belong to indices -- of the secrets
+  // that may travel in a pass (a secret too long for one computes its own on the one-secret path)
+  std::vector<EcSecretPlan> plan(count);
+  std::map<std::vector<int64_t>, size_t> lists;          // position list -> its index
+  std::vector<const int64_t*> list_pos;
+  std::vector<size_t> list_m, list_first, list_of(count, (size_t)-1);
+  size_t coefs = 0;
+  for (size_t i = 0; i < count; ++i) {
+    const mpvss_ec_secret& s = secrets[i];
+    if (!s.positions_host || !s.shares || s.m == 0 || s.m > 0x7fffffff) continue;
+    bool ok = true;
+    for (size_t k = 0; k < s.m && ok; ++k) ok = s.positions_host[k] >= 1;
+    if (!ok) continue;
+    if (s.m > EC_GROUP_SECRET_MAX || s.m > MAX_CHUNK) {
+      plan[i].kind = EC_SECRET_SINGLE;
+      continue;
+    }
+    plan[i].kind = EC_SECRET_GROUPED;
+    const auto it = lists.emplace(std::vector<int64_t>(s.positions_host, s.positions_host + s.m), list_pos.size());
+    if (it.second) {
+      list_pos.push_back(s.positions_host);
+      list_m.push_back(s.m);
+      list_first.push_back(coefs);
+      coefs += s.m;
+    }
+    list_of[i] = it.first->second;
+  }
+  lists.clear();
+  std::vector<uint8_t> scalars(coefs * 32);
+  std::vector<char> coef_ok(coefs, 0);
+  // a coefficient costs 2 m small products and one inversion in the 256-bit field: a thread per 64 of them when the library chooses
+  hsc::parallel_for(coefs, rt_many_threads(host_threads, coefs, 64), [&](size_t lo, size_t hi) {
+    size_t l = std::upper_bound(list_first.begin(), list_first.end(), lo) - list_first.begin() - 1;
+    for (size_t c = lo; c < hi; ++c) {
+      while (l + 1 < list_first.size() && list_first[l + 1] <= c) ++l;
+      coef_ok[c] = ec_lagrange_scalar(gi, list_pos[l], list_m[l], c - list_first[l], scalars.data() + c * 32) ? 1 : 0;
+    }
+  });
+  for (size_t i = 0; i < count; ++i) {
+    if (plan[i].kind != EC_SECRET_GROUPED) continue;
+    const size_t l = list_of[i];
+    plan[i].coef = list_first[l];
+    const auto first = coef_ok.begin() + list_first[l], last = first + list_m[l];
+    if (std::find(first, last, 0) != last) plan[i].kind = EC_SECRET_REFUSED;                  // duplicate positions
+  }
+
+  // THE grouping decision: a pass is a maximal stretch of consecutive grouped secrets (at most EC_GROUP_SECRET_MAX shares each) that
+  // hold at most MAX_CHUNK shares together, cut only at secret boundaries.  Refused secrets are settled above and do not end a pass;
+  // a pass of one secret takes the one-secret path, like every secret too long for a pass.  A code of the one-secret path other
+  // than MPVSS_E_INVALID (which refuses that secret alone) ends the call.
+  auto single = [&](size_t i) -> int {
+    const mpvss_ec_secret& s = secrets[i];
+    spans_reset(ctx);
+    const int rc = ec_reconstruct_locked(ctx, gi, w, space, s.positions_host, s.shares, s.m, gs_out + i * L,
+                                         masks_out32 ? masks_out32 + 32 * i : nullptr,
+                                         plan[i].coef != (size_t)-1 ? scalars.data() + plan[i].coef * 32 : nullptr);
+    if (rc == MPVSS_E_INVALID) {                            // (nothing of a refused secret stays in its outputs)
+      memset(gs_out + i * L, 0, L);
+      if (masks_out32) memset(masks_out32 + 32 * i, 0, 32);
+      return MPVSS_OK;
+    }
+    RET_IF(rc);
+    status[i] = MPVSS_OK;
+    ++ctx->ec_rec_single_secrets;
+    return MPVSS_OK;
+  };
+  std::vector<size_t> run;
+  size_t run_shares = 0;
+  auto flush = [&]() -> int {
+    int rc = MPVSS_OK;
+    if (run.size() == 1) rc = single(run[0]);
+    else if (run.size() > 1) rc = ec_reconstruct_pass(ctx, gi, w, space, secrets, run, plan, scalars.data(), host_threads, status, gs_out, masks_out32);
+    run.clear();
+    run_shares = 0;
+    return rc;
+  };
+  for (size_t i = 0; i < count; ++i) {
+    if (plan[i].kind == EC_SECRET_REFUSED) continue;
+    if (plan[i].kind == EC_SECRET_SINGLE) {
+      RET_IF(flush());
+      RET_IF(single(i));
+      continue;
+    }
+    if (!run.empty() && run_shares + secrets[i].m > MAX_CHUNK) RET_IF(flush());
+    run.push_back(i);
+    run_shares += secrets[i].m;
+  }
+  return flush();
+}
+
+extern "C" int mpvss_ec_reconstruct_many_stats(mpvss_ctx* ctx, unsigned long long* passes, unsigned long long* grouped_secrets,
+                                               unsigned long long* single_secrets) {
+  if (!ctx) return MPVSS_E_INVALID;
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  if (passes) *passes = ctx->ec_rec_passes;
+  if (grouped_secrets) *grouped_secrets = ctx->ec_rec_grouped_secrets;
+  if (single_secrets) *single_secrets = ctx->ec_rec_single_secrets;
   return MPVSS_OK;
 }

@@ -68,6 +68,10 @@ int ec_launch_encode(int group, const uint32_t* pts, int count, uint8_t* enc, hi
 int ec_launch_add_pts(int group, const uint32_t* a, const uint32_t* b, int count, uint32_t* out, hipStream_t s);
 /* out (one internal point, may alias pts) = sum of the m internal points at pts */
 int ec_launch_sum(int group, const uint32_t* pts, int m, uint32_t* out, hipStream_t s);
+/* out[b] (dense internal points) = sum of the segs[2 b + 1] points from pts[segs[2 b]] on, b < count: one wave per segment */
+int ec_launch_sum_segments(int group, const uint32_t* pts, const uint32_t* segs, int count, uint32_t* out, hipStream_t s);
+/* dst[segs[2 b] * len ..] = the segs[2 b + 1] * len bytes at src[b] (src: `count` device pointers in device memory) */
+int ec_launch_gather_segments(const uint8_t* const* src, const uint32_t* segs, int count, uint32_t len, uint8_t* dst, hipStream_t s);
 int ec_launch_encode_gated(int group, const uint32_t* pts, int count, uint8_t* enc, const int* gate, hipStream_t s);
 #ifdef __cplusplus
 }

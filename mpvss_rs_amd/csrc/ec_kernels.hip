@@ -876,6 +876,36 @@ __device__ __forceinline__ void sum_points_body(const u32* __restrict__ pts, int
   if (k == 0) store_point_aos<C>(out, acc);
 }
 
+// out[b] = sum of the points first .. first + m of secret b, {first, m} = segs[2 b], segs[2 b + 1]: the folds of all the secrets of a
+// reconstruct pass in one launch (mpvss_ec_reconstruct_many).  One wave per secret: lane k adds up the points first + k, first + k + 64,
+// ... (the formulas are complete, as sum_points_body relies on), then a tree through LDS that starts at the smallest power of two
+// not below min(m, 64): 2 rounds for a secret of 3 shares, not 6.  Nothing beyond first + m is read: the next secret's factors lie there.
+template <class C>
+__device__ __forceinline__ void sum_segments_body(const u32* __restrict__ pts, const u32* __restrict__ segs, int count,
+                                                  u32* __restrict__ out, u32* lds) {
+  const int b = blockIdx.x, k = threadIdx.x;
+  if (b >= count) return;                                   // the whole workgroup leaves: no barrier is left waiting
+  const u32 first = segs[2 * b], m = segs[2 * b + 1];      // wave-uniform
+  typename C::Point acc, p;
+  C::identity(acc);
+  for (u32 i = k; i < m; i += 64) {
+    load_point_aos<C>(p, pts + ((size_t)first + i) * C::POINT_WORDS);
+    C::add(acc, acc, p);
+  }
+  int width = 1;
+  while (width < 64 && (u32)width < m) width <<= 1;
+  for (int d = width / 2; d >= 1; d >>= 1) {
+    lds_put_raw<C>(lds, k, acc);
+    __syncthreads();
+    if (k < d) {
+      lds_get_raw<C>(p, lds, k + d);
+      C::add(acc, acc, p);
+    }
+    __syncthreads();
+  }
+  if (k == 0) store_point_aos<C>(out + (size_t)b * C::POINT_WORDS, acc);
+}
+
 // secp256k1: eight points per lane share one field inversion (Montgomery's trick)
 __device__ __forceinline__ void secp_encode_batch_body(const u32* __restrict__ pts, int count, uint8_t* __restrict__ enc) {
   constexpr int B = 8;
@@ -982,7 +1012,10 @@ __device__ __forceinline__ void secp_encode_batch_body(const u32* __restrict__ p
            CURVE::add(r, p, q);                                                                                              \
            store_point_aos<CURVE>(out + (size_t)x * CURVE::POINT_WORDS, r);)                                                 \
   extern "C" __global__ void __launch_bounds__(256) k_##NAME##_sum_points(const u32* pts, int m, u32* out)                   \
-      BODY(extern __shared__ u32 lds[]; sum_points_body<CURVE>(pts, m, out, lds);)
+      BODY(extern __shared__ u32 lds[]; sum_points_body<CURVE>(pts, m, out, lds);)                                           \
+  extern "C" __global__ void __launch_bounds__(64) k_##NAME##_sum_segments(const u32* pts, const u32* segs, int count,       \
+                                                                           u32* out)                                         \
+      BODY(extern __shared__ u32 lds[]; sum_segments_body<CURVE>(pts, segs, count, out, lds);)
 
 #if EC_PART != 2
 EC_KERNELS(secp, Secp, OrderSecp, QuadSecp, EC_DEF)
@@ -1004,6 +1037,18 @@ extern "C" __global__ void __launch_bounds__(64) k_secp_encode_batch(const u32* 
                                                                      BoxStride bs) {
   EC_BOX_GATE_CHECK(gate, 1);
   secp_encode_batch_body(pts + blockIdx.y * bs.pts, count, enc + blockIdx.y * bs.enc);
+}
+// dst[first * len ..] = the m * len bytes at src[b], {first, m} = segs[2 b], segs[2 b + 1]: the shares of the secrets of a reconstruct
+// pass, each in a device buffer of its own, into one dense array (one launch instead of a device-to-device copy per secret).
+// Byte loads: 33-byte elements at any address.  The curve plays no part.
+extern "C" __global__ void __launch_bounds__(256) k_ec_gather_segments(const uint8_t* const* src, const u32* segs, int count, u32 len,
+                                                                       uint8_t* dst) {
+  const int b = blockIdx.x;
+  if (b >= count) return;
+  const uint8_t* __restrict__ from = src[b];
+  const size_t bytes = (size_t)segs[2 * b + 1] * len;
+  uint8_t* __restrict__ to = dst + (size_t)segs[2 * b] * len;
+  for (size_t i = threadIdx.x; i < bytes; i += blockDim.x) to[i] = from[i];
 }
 #endif
 #if EC_PART == 1
@@ -1283,6 +1328,21 @@ extern "C" int ec_launch_sum(int group, const uint32_t* pts, int m, uint32_t* ou
   const size_t lds = (size_t)256 * ec_point_words(group) * 4;
   if (group == 1) hipLaunchKernelGGL(k_secp_sum_points, dim3(1), dim3(256), lds, s, pts, m, out);
   else hipLaunchKernelGGL(k_rist_sum_points, dim3(1), dim3(256), lds, s, pts, m, out);
+  return (int)hipGetLastError();
+}
+// out[b] (dense internal points) = sum of the points of segment b: segs = `count` pairs {first, m}
+extern "C" int ec_launch_sum_segments(int group, const uint32_t* pts, const uint32_t* segs, int count, uint32_t* out, hipStream_t s) {
+  if (count <= 0) return 0;
+  const size_t lds = (size_t)64 * ec_point_words(group) * 4;
+  if (group == 1) hipLaunchKernelGGL(k_secp_sum_segments, dim3(count), dim3(64), lds, s, pts, segs, count, out);
+  else hipLaunchKernelGGL(k_rist_sum_segments, dim3(count), dim3(64), lds, s, pts, segs, count, out);
+  return (int)hipGetLastError();
+}
+// dst = the segments' bytes side by side: src = `count` device pointers, segment b has segs[2 b + 1] elements of len bytes
+extern "C" int ec_launch_gather_segments(const uint8_t* const* src, const uint32_t* segs, int count, uint32_t len, uint8_t* dst,
+                                         hipStream_t s) {
+  if (count <= 0) return 0;
+  hipLaunchKernelGGL(k_ec_gather_segments, dim3(count), dim3(256), 0, s, src, segs, count, len, dst);
   return (int)hipGetLastError();
 }
 #endif  // EC_PART != 2

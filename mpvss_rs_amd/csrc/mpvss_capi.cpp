@@ -338,6 +338,8 @@ struct mpvss_ctx {
     unsigned long long blocks = 0;
   } pstats;
   EcWork ecwork;
+  // mpvss_ec_reconstruct_many_stats (capi_scalar.inc), both curves together
+  unsigned long long ec_rec_passes = 0, ec_rec_grouped_secrets = 0, ec_rec_single_secrets = 0;
   // workspace of the run-time MODP group entry points (capi_modp_rt.inc), used under `mu`
   DevBuf rt_consts, rt_in[6], rt_out[3], rt_tab1, rt_tab2, rt_tabg, rt_cm, rt_small[2];
   // the scalar ring Z/(q-1) on the device (capi_modp_rt.inc, "scalar ring on the device"): the constants of q', the staged

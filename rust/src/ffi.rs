@@ -69,6 +69,13 @@ pub struct mpvss_modp_group_secret {
     pub shares: *const u8,
     pub m: usize,
 }
+/// one secret of mpvss_ec_reconstruct_many: m positions (host memory) and m encoded shares (in the call's space)
+#[repr(C)]
+pub struct mpvss_ec_secret {
+    pub positions_host: *const i64,
+    pub shares: *const u8,
+    pub m: usize,
+}
 #[repr(C)]
 pub struct mpvss_ec_box {
     pub commitments: *const u8,
@@ -253,6 +260,10 @@ unsafe extern "C" {
                                   mask_out32: *mut u8) -> c_int;
     pub fn mpvss_ec_reconstruct(ctx: *mut mpvss_ctx, group: c_int, space: c_int, positions_host: *const i64, shares: *const u8, m: usize,
                                 gs_out: *mut u8, mask_out32: *mut u8) -> c_int;
+    pub fn mpvss_ec_reconstruct_many(ctx: *mut mpvss_ctx, group: c_int, space: c_int, secrets: *const mpvss_ec_secret, count: usize,
+                                     host_threads: c_int, status: *mut c_int, gs_out: *mut u8, masks_out32: *mut u8) -> c_int;
+    pub fn mpvss_ec_reconstruct_many_stats(ctx: *mut mpvss_ctx, passes: *mut c_ulonglong, grouped_secrets: *mut c_ulonglong,
+                                           single_secrets: *mut c_ulonglong) -> c_int;
     // ---- wire format
     pub fn mpvss_box_wire_size(group: c_int, n: usize, t: usize, u_len: usize) -> usize;
     pub fn mpvss_box_serialize(group: c_int, commitments: *const u8, t: usize, positions: *const i64, pubkeys: *const u8, shares: *const u8,
