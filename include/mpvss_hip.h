@@ -381,8 +381,31 @@ typedef struct mpvss_ec_box {
   const uint8_t* pubkeys; const uint8_t* shares; const uint8_t* responses; size_t n;
   const uint8_t* challenge_host;
 } mpvss_ec_box;
+/* Many boxes of a curve group in one call: for every box, verdicts[i] and digests32[32 i ..] (may be NULL) are what
+ * mpvss_ec_verify_distribution gives for that box.
+ * RUNS OF SMALL BOXES (mode 1 of mpvss_ctx_set_ec_box_groups, the default): a box is small when 1 <= n < 4096, 1 <= t < 4096 (the
+ * bound below which the forward differences never apply), all its pointers are set and its challenge is below the group order.  A
+ * run is a maximal stretch of consecutive small boxes that hold at most MPVSS_MAX_CHUNK shares and at most MPVSS_MAX_CHUNK
+ * commitments together.  A run of two or more boxes travels through the GPU as ONE dense batch -- one workgroup per 64 shares of
+ * a box -- synchronously and with the context lock held for the pass (a few milliseconds); its transcripts are hashed by up to
+ * hash_threads host threads (clamped to 1..16; <= 0: one per 512 shares of the run, at most 16, never by the machine's CPU count).
+ * Every other box -- a run of one, an empty box, a malformed box, a box of n or t >= 4096 -- goes through a block slot of its own,
+ * pipelined over the stretches between the runs: up to `depth` boxes enqueued ahead, hashed by hash_threads library threads (see
+ * mpvss_modp_verify_many).  `depth` means nothing inside a run.
+ * A box the engine turns down costs only itself, in a run or outside: verdict 0, a digest of zeros, and the call goes on and
+ * returns MPVSS_OK.  That is an invalid encoding among commitments, public keys or shares, a response or challenge that is not
+ * below the group order, a NULL pointer, t == 0 with n > 0.  mpvss_last_error names the reason and the index inside the box; of
+ * the boxes of one run the last in box order.  A HIP error or a failed allocation ends the call.
+ * mpvss_ctx_set_ec_box_groups: 0 = every box through a block slot of its own, 1 = automatic (the rule above); anything else is
+ * MPVSS_E_INVALID.
+ * mpvss_ec_verify_many_stats: since the context was created, both curves together: the grouped passes, the boxes they verified
+ * and the boxes verified through a slot of their own.  Empty boxes and boxes turned down are in none of the counts.  Any pointer
+ * may be NULL; no context is MPVSS_E_INVALID. */
 int mpvss_ec_verify_many(mpvss_ctx* ctx, int group, int space, const mpvss_ec_box* boxes, size_t count, int depth,
                          int hash_threads, int* verdicts, uint8_t* digests32);
+int mpvss_ctx_set_ec_box_groups(mpvss_ctx* ctx, int mode);
+int mpvss_ec_verify_many_stats(mpvss_ctx* ctx, unsigned long long* passes, unsigned long long* grouped_boxes,
+                               unsigned long long* single_boxes);
 /* src/participant.rs:1346-1371 (secp256k1), 1789-1814 (ristretto255) */
 int mpvss_ec_verify_shares(mpvss_ctx* ctx, int group, int space, const uint8_t* pk, const uint8_t* s, const uint8_t* y,
                            const uint8_t* c, const uint8_t* r, size_t n, uint8_t* verdicts_host);

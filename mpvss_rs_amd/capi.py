@@ -67,6 +67,7 @@ EXPORTED_SYMBOLS = (
     "mpvss_modp_group_verify_many", "mpvss_modp_group_verify_many_stats",
     "mpvss_modp_group_reconstruct_many", "mpvss_modp_group_reconstruct_many_stats",
     "mpvss_ec_reconstruct_many", "mpvss_ec_reconstruct_many_stats",
+    "mpvss_ctx_set_ec_box_groups", "mpvss_ec_verify_many_stats",
 )
 
 GROUP_SECP256K1 = 1
@@ -236,6 +237,9 @@ def load_library() -> C.CDLL:
     lib.mpvss_ec_transcript_absorb.argtypes = [ci, u8p, u8p, sz]
     lib.mpvss_ec_transcript_verdict.argtypes = [ci, u8p, u8p, C.POINTER(ci), u8p]
     lib.mpvss_ec_verify_many.argtypes = [vp, ci, ci, C.POINTER(EcBox), sz, ci, ci, C.POINTER(ci), u8p]
+    if hasattr(lib, "mpvss_ec_verify_many_stats"):      # (an A/B library of an older commit, MPVSS_HIP_LIB, does without the two)
+        lib.mpvss_ctx_set_ec_box_groups.argtypes = [vp, ci]
+        lib.mpvss_ec_verify_many_stats.argtypes = [vp, C.POINTER(C.c_ulonglong), C.POINTER(C.c_ulonglong), C.POINTER(C.c_ulonglong)]
     lib.mpvss_modp_verify_many.argtypes = [vp, ci, C.POINTER(ModpBox), sz, ci, ci, C.POINTER(ci), u8p]
     lib.mpvss_modp_verify_many_chained.argtypes = [vp, ci, C.POINTER(ModpBox), sz, ci, ci, C.POINTER(vp), CHAIN_CB, CHAIN_CB, vp,
                                                    C.POINTER(ci), u8p]
@@ -1291,9 +1295,18 @@ class Engine:
         self._check(self.lib.mpvss_ec_verify_block_absorb(self.ctx, ps, None, None, None), "ec_verify_block_absorb")
         return bytes(ks)
 
+    def _ec_verify_many(self, group: int, space: int, arr, count: int, depth: int, hash_threads: int):
+        verdicts = (C.c_int * max(count, 1))()
+        kd, pd = _out(32 * count)
+        self._check(self.lib.mpvss_ec_verify_many(self.ctx, group, space, arr, count, depth, hash_threads, verdicts, pd),
+                    "ec_verify_many")
+        raw = bytes(kd)
+        return [(bool(verdicts[i]), raw[32 * i:32 * i + 32]) for i in range(count)]
+
     def ec_verify_many(self, group: int, boxes: Sequence[dict], depth: int = 6, hash_threads: int = 3):
-        """boxes: dicts with commitments, positions, pubkeys, shares, responses, challenge (host bytes).
-        Returns [(verdict, digest)] in box order."""
+        """boxes: dicts with commitments, positions, pubkeys, shares, responses, challenge (host bytes; None for one of the
+        byte arrays: a null pointer).  Returns [(verdict, digest)] in box order.  Runs of small boxes travel as one dense
+        batch (set_ec_box_groups, ec_verify_many_stats)."""
         keep, arr = [], (EcBox * max(len(boxes), 1))()
         e = EC_ENC[group]
         for i, b in enumerate(boxes):
@@ -1301,14 +1314,32 @@ class Engine:
             pos = (C.c_int64 * max(n, 1))(*b["positions"])
             bufs = [_buf(b[k]) for k in ("commitments", "pubkeys", "shares", "responses", "challenge")]
             keep.append((pos, bufs))
-            arr[i] = EcBox(bufs[0][1], len(b["commitments"]) // e, C.cast(pos, C.c_void_p), bufs[1][1], bufs[2][1],
+            arr[i] = EcBox(bufs[0][1], len(b["commitments"] or b"") // e, C.cast(pos, C.c_void_p), bufs[1][1], bufs[2][1],
                            bufs[3][1], n, bufs[4][1])
-        verdicts = (C.c_int * max(len(boxes), 1))()
-        kd, pd = _out(32 * len(boxes))
-        self._check(self.lib.mpvss_ec_verify_many(self.ctx, group, MPVSS_HOST, arr, len(boxes), depth, hash_threads, verdicts,
-                                                  pd), "ec_verify_many")
-        raw = bytes(kd)
-        return [(bool(verdicts[i]), raw[32 * i:32 * i + 32]) for i in range(len(boxes))]
+        return self._ec_verify_many(group, MPVSS_HOST, arr, len(boxes), depth, hash_threads)
+
+    def ec_verify_many_device(self, group: int, boxes: Sequence[dict], depth: int = 6, hash_threads: int = 3):
+        """the same with every box's arrays in HBM (left unchanged): dicts with commitments_ptr, t, positions_ptr, pubkeys_ptr,
+        shares_ptr, responses_ptr, n (device addresses, 0: a null pointer) and challenge (host bytes)"""
+        keep, arr = [], (EcBox * max(len(boxes), 1))()
+        for i, b in enumerate(boxes):
+            kc, pc = _buf(b["challenge"])
+            keep.append(kc)
+            ptr = [C.c_void_p(b[k]) if b.get(k) else None for k in ("commitments_ptr", "positions_ptr", "pubkeys_ptr", "shares_ptr",
+                                                                     "responses_ptr")]
+            arr[i] = EcBox(ptr[0], int(b["t"]), ptr[1], ptr[2], ptr[3], ptr[4], int(b["n"]), pc)
+        return self._ec_verify_many(group, MPVSS_DEVICE, arr, len(boxes), depth, hash_threads)
+
+    def set_ec_box_groups(self, mode: int) -> None:
+        """mpvss_ctx_set_ec_box_groups: runs of small boxes of ec_verify_many as one dense batch -- 0 every box on its own,
+        1 automatic"""
+        self._check(self.lib.mpvss_ctx_set_ec_box_groups(self.ctx, int(mode)), "set_ec_box_groups")
+
+    def ec_verify_many_stats(self) -> dict:
+        """since the context was created: grouped passes, boxes they verified, boxes verified through a slot of their own"""
+        p, g, s = C.c_ulonglong(0), C.c_ulonglong(0), C.c_ulonglong(0)
+        self._check(self.lib.mpvss_ec_verify_many_stats(self.ctx, C.byref(p), C.byref(g), C.byref(s)), "ec_verify_many_stats")
+        return {"passes": int(p.value), "grouped_boxes": int(g.value), "single_boxes": int(s.value)}
 
     def ec_batch_mul(self, group: int, a: bytes, b: bytes) -> bytes:
         n = len(a) // EC_ENC[group]

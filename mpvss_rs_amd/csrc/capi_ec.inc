@@ -1113,15 +1113,216 @@ extern "C" int mpvss_ec_verify_distribution(mpvss_ctx* ctx, int group, int space
   return mpvss_ec_transcript_verdict(group, state, challenge_host, verdict, digest32_out);
 }
 
+// =====================================================================================================================
+// Runs of small boxes as one dense batch (DESIGN section 8, "Runs of small boxes"): a verifier of a PVSS round holds one box per
+// dealer, tens to hundreds of boxes of 5 to 1 000 shares.  Through a block slot each costs its own decode, Horner launch, three
+// table builds, two or three multiplications, an addition and two encodes, about ten copies, two forks and an event wait: the
+// latency of a chain of narrow launches.  A run of such boxes travels instead as ONE concatenation through the launches of one
+// box, X by k_*_commit_eval_tiles (a tile = up to 64 shares of one box = one workgroup) and the DLEQ multiplications with a
+// challenge per share.  THE grouping decision is in mpvss_ec_verify_many below.
+// =====================================================================================================================
+namespace {
+
+// A box of n or t >= 4096 never travels in a run: 4096 is the bound below which ec_fd_shape never holds, so no box that the
+// forward differences or the X batches serve changes its path.  Derived, not measured.
+constexpr size_t EC_GROUP_BOX_MAX = 4096;
+constexpr size_t EC_TILE = 64;                     // shares per tile: one wave, one workgroup of the 64-lane curve kernels
+
+int rt_many_threads(int requested, size_t work, size_t per_thread);      // capi_scalar.inc
+
+// may this box travel in a run?  Judged on the host before anything is launched.
+bool ec_box_small(const EcInfo* gi, const mpvss_ec_box& b) {
+  if (b.n < 1 || b.n >= EC_GROUP_BOX_MAX || b.t < 1 || b.t >= EC_GROUP_BOX_MAX || b.n > MAX_CHUNK || b.t > MAX_CHUNK) return false;
+  if (!b.commitments || !b.positions || !b.pubkeys || !b.shares || !b.responses || !b.challenge_host) return false;
+  return scalar_canonical(gi, b.challenge_host);
+}
+
+// A grouped pass: the boxes [lo, hi) (all ec_box_small, at least two, at most MAX_CHUNK shares and as many commitments in all).
+// Synchronous, under the context lock, on the context's own EcWork and pinned staging -- the lock is held for the pass (a few
+// milliseconds); pipe_mu plays no part.  A box the engine turns down (an encoding that is no group element, a response that is
+// not below the order) is refused here: its lanes ran with the others and are dropped.
+int ec_many_run(mpvss_ctx* ctx, const EcInfo* gi, int space, const mpvss_ec_box* boxes, size_t lo, size_t hi, int hash_threads,
+                int* verdicts, uint8_t* digests32) {
+  const int group = gi->group;
+  const size_t B = hi - lo, L = gi->enc, pw = (size_t)ec_point_words(group);
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  EcWork& w = ecw(ctx);
+  // the tables: tiles {box, first share, live count}, boxes {first commitment, t} (also the commitments' gather segments),
+  // shares {first share, n} (the gather segments of the per-share arrays)
+  std::vector<uint32_t> tab;
+  std::vector<size_t> first(B + 1), first_cm(B + 1);
+  size_t S = 0, T = 0;
+  for (size_t k = 0; k < B; ++k) {
+    const mpvss_ec_box& b = boxes[lo + k];
+    first[k] = S;
+    first_cm[k] = T;
+    for (size_t off = 0; off < b.n; off += EC_TILE) {
+      const uint32_t tile[3] = {(uint32_t)k, (uint32_t)(S + off), (uint32_t)std::min(b.n - off, EC_TILE)};
+      tab.insert(tab.end(), tile, tile + 3);
+    }
+    S += b.n;
+    T += b.t;
+  }
+  first[B] = S;
+  first_cm[B] = T;
+  const size_t ntiles = tab.size() / 3;
+  const size_t o_btab = tab.size();
+  for (size_t k = 0; k < B; ++k) { tab.push_back((uint32_t)first_cm[k]); tab.push_back((uint32_t)boxes[lo + k].t); }
+  const size_t o_segs = tab.size();
+  for (size_t k = 0; k < B; ++k) { tab.push_back((uint32_t)first[k]); tab.push_back((uint32_t)boxes[lo + k].n); }
+  const size_t tab_bytes = ((tab.size() * 4 + 15) / 16) * 16;
+  const bool dev = space != MPVSS_HOST;
+  // pinned staging, 16-byte aligned parts: [tables | 5 B source pointers (device space)] [challenge per share] [host space: positions,
+  // commitments, public keys, shares, responses] [back: X, a1, a2, flags; device space: shares, responses]
+  auto al = [](size_t v) { return (v + 15) / 16 * 16; };
+  size_t off = 0;
+  auto take = [&](size_t bytes) { const size_t at = off; off += al(bytes); return at; };
+  const size_t p_tab = take(tab_bytes + (dev ? 5 * B * sizeof(void*) : 0)), p_ch = take(S * 32);
+  const size_t p_pos = take(dev ? 0 : S * 8), p_cm = take(dev ? 0 : T * L), p_y = take(dev ? 0 : S * L), p_Y = take(dev ? 0 : S * L),
+               p_r = take(dev ? 0 : S * 32);
+  const size_t p_X = take(S * L), p_a1 = take(S * L), p_a2 = take(S * L), p_ok = take(T + 2 * S);
+  const size_t p_Yb = take(dev ? S * L : 0), p_rb = take(dev ? S * 32 : 0);
+  spans_reset(ctx);
+  RET_IF(ensure_pinned(ctx, off));
+  uint8_t* pin = (uint8_t*)ctx->pin;
+  struct Drain {            // no copy out of (or into) the staging is pending when the pass ends, whichever way it ends
+    mpvss_ctx* c;
+    ~Drain() { (void)hipStreamSynchronize(c->stream); }
+  } drain{ctx};
+  memcpy(pin + p_tab, tab.data(), tab.size() * 4);
+  const uint8_t** srcs = (const uint8_t**)(pin + p_tab + tab_bytes);      // [array][box]: positions, commitments, y, Y, r
+  for (size_t k = 0; k < B; ++k) {
+    const mpvss_ec_box& b = boxes[lo + k];
+    for (size_t i = first[k]; i < first[k + 1]; ++i) memcpy(pin + p_ch + i * 32, b.challenge_host, 32);
+    if (dev) {
+      srcs[0 * B + k] = (const uint8_t*)b.positions;
+      srcs[1 * B + k] = b.commitments;
+      srcs[2 * B + k] = b.pubkeys;
+      srcs[3 * B + k] = b.shares;
+      srcs[4 * B + k] = b.responses;
+    } else {
+      memcpy(pin + p_pos + first[k] * 8, b.positions, b.n * 8);
+      memcpy(pin + p_cm + first_cm[k] * L, b.commitments, b.t * L);
+      memcpy(pin + p_y + first[k] * L, b.pubkeys, b.n * L);
+      memcpy(pin + p_Y + first[k] * L, b.shares, b.n * L);
+      memcpy(pin + p_r + first[k] * 32, b.responses, b.n * 32);
+    }
+  }
+  const uint32_t* comb;
+  RET_IF(ec_comb(ctx, group, &comb));
+  const size_t okn = T + 2 * S;
+  RET_IF(ensure(ctx, w.e, p_ch - p_tab));
+  RET_IF(ensure(ctx, w.chal, std::max<size_t>(S * 32, 64)));
+  RET_IF(ensure(ctx, w.pos, S * 8));
+  RET_IF(ensure(ctx, w.cmenc, T * L));
+  RET_IF(ensure(ctx, w.cm, T * pw * 4));
+  RET_IF(ensure(ctx, w.a, S * L));
+  RET_IF(ensure(ctx, w.b, S * L));
+  RET_IF(ensure(ctx, w.d, S * 32));
+  RET_IF(ensure(ctx, w.ok, okn > 4096 ? okn : 4096));
+  RET_IF(ensure(ctx, w.x, S * L));
+  RET_IF(ensure(ctx, w.pts, S * pw * 4));
+  RET_IF(ensure(ctx, w.o1, S * L));
+  RET_IF(ensure(ctx, w.o2, S * L));
+  hipStream_t s = ctx->stream;
+  HIPCHK(ctx, hipMemcpyAsync(w.e.p, pin + p_tab, p_ch - p_tab, hipMemcpyHostToDevice, s));
+  HIPCHK(ctx, hipMemcpyAsync(w.chal.p, pin + p_ch, S * 32, hipMemcpyHostToDevice, s));
+  const uint32_t* d_tiles = (const uint32_t*)w.e.p;
+  const uint32_t *d_btab = d_tiles + o_btab, *d_segs = d_tiles + o_segs;
+  if (dev) {                // every box's arrays lie in device buffers of their own: one gather launch per array, no copy per box
+    const uint8_t* const* d_srcs = (const uint8_t* const*)((const uint8_t*)w.e.p + tab_bytes);
+    LAUNCHCHK(ctx, ec_launch_gather_segments(d_srcs + 0 * B, d_segs, (int)B, 8, (uint8_t*)w.pos.p, s));
+    LAUNCHCHK(ctx, ec_launch_gather_segments(d_srcs + 1 * B, d_btab, (int)B, (uint32_t)L, (uint8_t*)w.cmenc.p, s));
+    LAUNCHCHK(ctx, ec_launch_gather_segments(d_srcs + 2 * B, d_segs, (int)B, (uint32_t)L, (uint8_t*)w.a.p, s));
+    LAUNCHCHK(ctx, ec_launch_gather_segments(d_srcs + 3 * B, d_segs, (int)B, (uint32_t)L, (uint8_t*)w.b.p, s));
+    LAUNCHCHK(ctx, ec_launch_gather_segments(d_srcs + 4 * B, d_segs, (int)B, 32, (uint8_t*)w.d.p, s));
+  } else {
+    HIPCHK(ctx, hipMemcpyAsync(w.pos.p, pin + p_pos, S * 8, hipMemcpyHostToDevice, s));
+    HIPCHK(ctx, hipMemcpyAsync(w.cmenc.p, pin + p_cm, T * L, hipMemcpyHostToDevice, s));
+    HIPCHK(ctx, hipMemcpyAsync(w.a.p, pin + p_y, S * L, hipMemcpyHostToDevice, s));
+    HIPCHK(ctx, hipMemcpyAsync(w.b.p, pin + p_Y, S * L, hipMemcpyHostToDevice, s));
+    HIPCHK(ctx, hipMemcpyAsync(w.d.p, pin + p_r, S * 32, hipMemcpyHostToDevice, s));
+  }
+  uint8_t* ok = (uint8_t*)w.ok.p;
+  const uint8_t *dr = (const uint8_t*)w.d.p, *dc = (const uint8_t*)w.chal.p;
+  uint8_t *dX = (uint8_t*)w.x.p, *d1 = (uint8_t*)w.o1.p, *d2 = (uint8_t*)w.o2.p;
+  // the launches of ONE box over the concatenation: decode, X (encodings and internal points), a2 = r y + c Y, a1 = r G + c X with
+  // X handed over as internal points (EcBase::pts, as the forward-difference path does: no second decode of X)
+  LAUNCHCHK(ctx, ec_launch_decode(group, (const uint8_t*)w.cmenc.p, (int)T, (uint32_t*)w.cm.p, ok, s));
+  TIMED_LAUNCH(ctx, 0, ec_launch_commit_eval_tiles(group, (const uint32_t*)w.cm.p, d_tiles, (int)ntiles, d_btab, (const int64_t*)w.pos.p,
+                                                   dX, (uint32_t*)w.pts.p, s));
+  EcBase by, bY, bg, bX;
+  by.enc = (const uint8_t*)w.a.p; by.enc_stride = L;
+  bY.enc = (const uint8_t*)w.b.p; bY.enc_stride = L;
+  RET_IF(ec_dual(ctx, gi, by, dr, 32, &bY, dc, 32, S, w.tab1, w.tab2, w.p2, d2, ok + T, ok + T + S));
+  bg.generator = true;
+  bX.pts = (const uint32_t*)w.pts.p;
+  RET_IF(ec_dual(ctx, gi, bg, dr, 32, &bX, dc, 32, S, w.tab3, w.tab3, w.p1, d1, nullptr, nullptr));
+  HIPCHK(ctx, hipMemcpyAsync(pin + p_X, dX, S * L, hipMemcpyDeviceToHost, s));
+  HIPCHK(ctx, hipMemcpyAsync(pin + p_a1, d1, S * L, hipMemcpyDeviceToHost, s));
+  HIPCHK(ctx, hipMemcpyAsync(pin + p_a2, d2, S * L, hipMemcpyDeviceToHost, s));
+  HIPCHK(ctx, hipMemcpyAsync(pin + p_ok, ok, okn, hipMemcpyDeviceToHost, s));
+  if (dev) {
+    HIPCHK(ctx, hipMemcpyAsync(pin + p_Yb, w.b.p, S * L, hipMemcpyDeviceToHost, s));
+    HIPCHK(ctx, hipMemcpyAsync(pin + p_rb, w.d.p, S * 32, hipMemcpyDeviceToHost, s));
+  }
+  RET_IF(spans_collect(ctx));                                       // the pass's one synchronisation
+  const uint8_t *hX = pin + p_X, *h1 = pin + p_a1, *h2 = pin + p_a2, *hok = pin + p_ok;
+  const uint8_t *hY = pin + (dev ? p_Yb : p_Y), *hr = pin + (dev ? p_rb : p_r);
+  // The boxes' transcripts are independent: every thread takes a contiguous range of boxes.  A box's flags are judged in the order
+  // ec_verify_block_absorb_locked looks at them: responses, then commitments, public keys, shares; the first of each.
+  struct Refusal { const char* what = nullptr; size_t i = 0; bool scalar = false; };
+  std::vector<Refusal> refused(B);
+  // automatic: one thread per 512 shares of the run; 1 .. 16, never sized by the machine
+  const size_t nth = std::min<size_t>((size_t)rt_many_threads(hash_threads, S, 512), B);
+  hsc::parallel_indices((unsigned)nth, [&](unsigned part) {
+    for (size_t k = B * part / nth; k < B * (part + 1) / nth; ++k) {
+      const mpvss_ec_box& b = boxes[lo + k];
+      const size_t s0 = first[k], n = b.n, c0 = first_cm[k], t = b.t;
+      Refusal& r = refused[k];
+      for (size_t i = 0; i < n && !r.what; ++i)
+        if (!scalar_canonical(gi, hr + (s0 + i) * 32)) r = Refusal{"responses", i, true};
+      for (size_t i = 0; i < t && !r.what; ++i)
+        if (!hok[c0 + i]) r = Refusal{"commitments", i, false};
+      for (size_t i = 0; i < n && !r.what; ++i)
+        if (!hok[T + s0 + i]) r = Refusal{"public keys", i, false};
+      for (size_t i = 0; i < n && !r.what; ++i)
+        if (!hok[T + S + s0 + i]) r = Refusal{"encrypted shares", i, false};
+      if (r.what) continue;
+      mpvss::Sha256 tr;                                             // dleq.rs:87-99, share order = array order
+      ec_frame_shares(tr, hX, hY, h1, h2, L, s0, s0 + n);
+      (void)mpvss_ec_transcript_verdict(group, (const uint8_t*)&tr, b.challenge_host, &verdicts[lo + k],
+                                        digests32 ? digests32 + 32 * (lo + k) : nullptr);
+    }
+  });
+  size_t good = 0;
+  for (size_t k = 0; k < B; ++k) {                                  // in box order: the message is that of the last box turned down
+    const Refusal& r = refused[k];
+    if (!r.what) ++good;
+    else if (r.scalar) (void)ec_report_bad_scalar(ctx, r.what, r.i);
+    else (void)ec_report_bad_element(ctx, r.what, r.i);
+  }
+  if (good) {
+    ++ctx->ec_many_passes;
+    ctx->ec_many_grouped_boxes += good;
+  }
+  return MPVSS_OK;
+}
+
+}  // namespace
+
 extern "C" int mpvss_ec_verify_many(mpvss_ctx* ctx, int group, int space, const mpvss_ec_box* boxes, size_t count, int depth,
                                     int hash_threads, int* verdicts, uint8_t* digests32) {
   if (!ctx) return MPVSS_E_INVALID;
   if (count == 0) return MPVSS_OK;
+  int mode;
   {
     std::lock_guard<std::mutex> lk(ctx->mu);
     if (!ec_info(group)) return fail(ctx, MPVSS_E_UNSUPPORTED, "ec_verify_many: unknown group");
     if (!boxes || !verdicts) return fail(ctx, MPVSS_E_INVALID, "ec_verify_many: bad argument");
+    mode = ctx->ec_box_groups;
   }
+  const EcInfo* gi = ec_info(group);
   for (size_t i = 0; i < count; ++i) verdicts[i] = 0;
   if (digests32) memset(digests32, 0, 32 * count);       // a malformed box has no transcript: verdict 0, digest zero
   // X paths of up to MPVSS_EC_X_BATCH consecutive boxes of one shape in the same launches (0 / 1: every box on its own):
@@ -1133,28 +1334,82 @@ extern "C" int mpvss_ec_verify_many(mpvss_ctx* ctx, int group, int space, const 
   std::vector<EcPre> pre(count);
   std::vector<char> has_pre(count, 0), looked(count, 0);
   size_t batch_no = 0;
-  return run_box_pipeline(
-      ctx, count, depth, hash_threads,
-      [&](size_t b, unsigned*) {
-        const mpvss_ec_box& bx = boxes[b];
-        if (xB > 1 && !looked[b]) {
-          size_t B = 0;
-          while (B < xB && b + B < count && ec_x_box_batchable(space, boxes[b + B], bx.n, bx.t)) ++B;
-          for (size_t i = 0; i < std::max<size_t>(B, 1); ++i) looked[b + i] = 1;
-          if (B >= 2) {
-            while (ctx->ec_xb.size() < ring) ctx->ec_xb.push_back(new mpvss_ctx::XBatch());
-            const int rc = ec_x_batch_compute(ctx, ec_info(group), space, boxes + b, B, *ctx->ec_xb[batch_no++ % ring], &pre[b]);
-            if (rc == MPVSS_OK) for (size_t i = 0; i < B; ++i) has_pre[b + i] = 1;
-            else if (rc != 1) return rc;
+  std::atomic<unsigned long long> finished{0};           // boxes the pipeline verified (turned-down and empty ones count nowhere)
+  // the unchanged pipeline over the boxes [lo, hi): every box through a block slot of its own
+  auto pipeline = [&](size_t lo, size_t hi) -> int {
+    if (lo == hi) return MPVSS_OK;
+    return run_box_pipeline(
+        ctx, hi - lo, depth, hash_threads,
+        [&](size_t rel, unsigned*) {
+          const size_t b = lo + rel;
+          const mpvss_ec_box& bx = boxes[b];
+          if (xB > 1 && !looked[b]) {
+            size_t B = 0;
+            while (B < xB && b + B < hi && ec_x_box_batchable(space, boxes[b + B], bx.n, bx.t)) ++B;
+            for (size_t i = 0; i < std::max<size_t>(B, 1); ++i) looked[b + i] = 1;
+            if (B >= 2) {
+              while (ctx->ec_xb.size() < ring) ctx->ec_xb.push_back(new mpvss_ctx::XBatch());
+              const int rc = ec_x_batch_compute(ctx, gi, space, boxes + b, B, *ctx->ec_xb[batch_no++ % ring], &pre[b]);
+              if (rc == MPVSS_OK) for (size_t i = 0; i < B; ++i) has_pre[b + i] = 1;
+              else if (rc != 1) return rc;
+            }
           }
-        }
-        return ec_verify_block_compute_locked(ctx, group, space, bx.commitments, bx.t, bx.positions, bx.pubkeys, bx.shares,
-                                              bx.responses, bx.n, bx.challenge_host, has_pre[b] ? &pre[b] : nullptr);
-      },
-      [&](size_t idx, const uint8_t* state) {
-        return mpvss_ec_transcript_verdict(group, state, boxes[idx].challenge_host, &verdicts[idx],
-                                           digests32 ? digests32 + 32 * idx : nullptr);
-      });
+          return ec_verify_block_compute_locked(ctx, group, space, bx.commitments, bx.t, bx.positions, bx.pubkeys, bx.shares,
+                                                bx.responses, bx.n, bx.challenge_host, has_pre[b] ? &pre[b] : nullptr);
+        },
+        [&](size_t rel, const uint8_t* state) {
+          const size_t idx = lo + rel;
+          if (boxes[idx].n > 0) ++finished;
+          return mpvss_ec_transcript_verdict(group, state, boxes[idx].challenge_host, &verdicts[idx],
+                                             digests32 ? digests32 + 32 * idx : nullptr);
+        });
+  };
+  // THE grouping decision: a run is a maximal stretch of consecutive small boxes (ec_box_small) that hold at most MAX_CHUNK shares
+  // and at most MAX_CHUNK commitments together.  A run of two or more boxes is one grouped pass; every other box -- a run of
+  // one, an empty, malformed or larger box -- goes through the pipeline, which is applied to the stretches between the passes
+  // (the X-batch look-ahead works inside a stretch).  `depth` means nothing inside a pass.
+  int rc = MPVSS_OK;
+  size_t stretch = 0;                                    // first box not yet handed to the pipeline or to a pass
+  for (size_t i = 0; mode == 1 && i < count && rc == MPVSS_OK;) {
+    if (!ec_box_small(gi, boxes[i])) { ++i; continue; }
+    size_t j = i, shares = 0, cms = 0;
+    while (j < count && ec_box_small(gi, boxes[j]) && shares + boxes[j].n <= MAX_CHUNK && cms + boxes[j].t <= MAX_CHUNK) {
+      shares += boxes[j].n;
+      cms += boxes[j].t;
+      ++j;
+    }
+    if (j - i >= 2) {
+      rc = pipeline(stretch, i);
+      if (rc == MPVSS_OK) {
+        std::lock_guard<std::mutex> lk(ctx->mu);
+        rc = ec_many_run(ctx, gi, space, boxes, i, j, hash_threads, verdicts, digests32);
+      }
+      stretch = j;
+    }
+    i = j;
+  }
+  if (rc == MPVSS_OK) rc = pipeline(stretch, count);
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  ctx->ec_many_single_boxes += finished.load();
+  return rc;
+}
+
+extern "C" int mpvss_ctx_set_ec_box_groups(mpvss_ctx* ctx, int mode) {
+  if (!ctx) return MPVSS_E_INVALID;
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  if (mode != 0 && mode != 1) return fail(ctx, MPVSS_E_INVALID, "set_ec_box_groups: mode must be 0 (every box on its own) or 1 (automatic)");
+  ctx->ec_box_groups = mode;
+  return MPVSS_OK;
+}
+
+extern "C" int mpvss_ec_verify_many_stats(mpvss_ctx* ctx, unsigned long long* passes, unsigned long long* grouped_boxes,
+                                          unsigned long long* single_boxes) {
+  if (!ctx) return MPVSS_E_INVALID;
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  if (passes) *passes = ctx->ec_many_passes;
+  if (grouped_boxes) *grouped_boxes = ctx->ec_many_grouped_boxes;
+  if (single_boxes) *single_boxes = ctx->ec_many_single_boxes;
+  return MPVSS_OK;
 }
 
 // ---- verify_share, batched (participant.rs:1346-1371, 1789-1814) ---------------------------------------------

@@ -46,6 +46,11 @@ int ec_launch_fd_boxes_q(int group, const uint32_t* cm, int t, const int64_t* po
 int ec_launch_commit_eval_boxes(int group, const uint32_t* cm, int t, const int64_t* positions, int count, uint8_t* x_enc,
                                 const int* gate, int want, int boxes, size_t cm_stride, size_t pos_stride, size_t enc_stride,
                                 hipStream_t s);
+/* X of boxes of any shapes in one concatenation: workgroup w = tile w = up to 64 consecutive shares of one box;
+   tiles[3 w ..] = {box, first share, live count 1 .. 64}, boxes[2 b ..] = {first commitment in cm, t}; positions, x_enc and
+   x_pts (the same points in internal coordinates, or null) are indexed by the share's place in the concatenation */
+int ec_launch_commit_eval_tiles(int group, const uint32_t* cm, const uint32_t* tiles, int ntiles, const uint32_t* boxes,
+                                const int64_t* positions, uint8_t* x_enc, uint32_t* x_pts, hipStream_t s);
 int ec_launch_encode_boxes(int group, const uint32_t* pts, int count, uint8_t* enc, const int* gate, int boxes,
                            size_t pts_stride, size_t enc_stride, hipStream_t s);
 int ec_launch_fd(int group, const uint32_t* cm, int t, const int64_t* positions, int count, int chains, int w0,

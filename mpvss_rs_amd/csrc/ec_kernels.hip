@@ -63,12 +63,11 @@ struct BoxStride {
 #define EC_BOX_GATE_CHECK(gate, want) \
   if ((gate) != nullptr && (gate)[blockIdx.y] != (want)) return
 
+// share x of `positions` / `x_enc` (/ `x_pts`: the same point in internal coordinates, or null); a dead lane (!live) runs the
+// loop on a share of its wave and stores nothing
 template <class C>
 __device__ __forceinline__ void commit_eval_body(const u32* __restrict__ cm, int t, const int64_t* __restrict__ positions,
-                                                 int count, uint8_t* __restrict__ x_enc) {
-  const int xi = blockIdx.x * blockDim.x + threadIdx.x;
-  const bool live = xi < count;
-  const int x = live ? xi : count - 1;
+                                                 int x, bool live, uint8_t* __restrict__ x_enc, u32* __restrict__ x_pts) {
   const uint64_t pos = (uint64_t)positions[x];
   int nb = (pos == 0) ? 0 : 64 - __builtin_clzll(pos);
   typename C::Point acc, cj, r;
@@ -78,7 +77,34 @@ __device__ __forceinline__ void commit_eval_body(const u32* __restrict__ cm, int
     load_point_aos<C>(cj, cm + (size_t)j * C::POINT_WORDS);
     C::add(acc, r, cj);
   }
-  if (live) C::encode(x_enc + (size_t)x * C::ENC_LEN, acc);
+  if (live) {
+    if (x_pts != nullptr) store_point_aos<C>(x_pts + (size_t)x * C::POINT_WORDS, acc);
+    C::encode(x_enc + (size_t)x * C::ENC_LEN, acc);
+  }
+}
+// one box, lane = share: k_*_commit_eval (blockIdx.y = box of a batch of one shape)
+template <class C>
+__device__ __forceinline__ void commit_eval_body(const u32* __restrict__ cm, int t, const int64_t* __restrict__ positions,
+                                                 int count, uint8_t* __restrict__ x_enc) {
+  const int xi = blockIdx.x * blockDim.x + threadIdx.x;
+  const bool live = xi < count;
+  const int x = live ? xi : count - 1;
+  commit_eval_body<C>(cm, t, positions, x, live, x_enc, nullptr);
+}
+// Boxes of ANY shapes, concatenated (a run of mpvss_ec_verify_many): workgroup w = tile w = up to 64 consecutive shares of ONE box,
+// tiles[3 w ..] = {box, first share in the concatenation, live count 1 .. 64}, boxes[2 b ..] = {first commitment in cm, t}.  The
+// box of a workgroup, hence its commitments and t, are wave-uniform: the Horner loop does not diverge.  Lanes at or beyond the
+// live count are clamped to the tile's last share.
+template <class C>
+__device__ __forceinline__ void commit_eval_tiles_body(const u32* __restrict__ cm, const u32* __restrict__ tiles,
+                                                       const u32* __restrict__ boxes, const int64_t* __restrict__ positions,
+                                                       uint8_t* __restrict__ x_enc, u32* __restrict__ x_pts) {
+  const u32* tile = tiles + 3 * (size_t)blockIdx.x;
+  const u32 box = tile[0], first = tile[1], cnt = tile[2];
+  if (cnt == 0) return;
+  const bool live = threadIdx.x < cnt;
+  const int x = (int)(first + (live ? threadIdx.x : cnt - 1));
+  commit_eval_body<C>(cm + (size_t)boxes[2 * box] * C::POINT_WORDS, (int)boxes[2 * box + 1], positions, x, live, x_enc, x_pts);
 }
 
 // out = k1 * P1 + k2 * P2.  p1_stride / k2_stride 0 = shared operand; p2 == nullptr: out = k1 * P1.
@@ -939,6 +965,9 @@ __device__ __forceinline__ void secp_encode_batch_body(const u32* __restrict__ p
       BODY(EC_BOX_GATE_CHECK(gate, want);                                                                              \
            commit_eval_body<CURVE>(cm + blockIdx.y * bs.cm, t, pos + blockIdx.y * bs.pos, count,                       \
                                    x_enc + blockIdx.y * bs.enc);)                                                      \
+  extern "C" __global__ void __launch_bounds__(64) k_##NAME##_commit_eval_tiles(                                       \
+      const u32* cm, const u32* tiles, const u32* boxes, const int64_t* pos, uint8_t* x_enc, u32* x_pts)               \
+      BODY(commit_eval_tiles_body<CURVE>(cm, tiles, boxes, pos, x_enc, x_pts);)                                        \
   extern "C" __global__ void __launch_bounds__(64) k_##NAME##_dual_mul(                                                \
       const uint8_t* p1, size_t p1_stride, const uint8_t* k1, const uint8_t* p2, const uint8_t* k2, size_t k2_stride,  \
       int count, uint8_t* out, uint8_t* ok)                                                                            \
@@ -1086,6 +1115,16 @@ extern "C" int ec_launch_commit_eval_boxes(int group, const uint32_t* cm, int t,
 extern "C" int ec_launch_commit_eval(int group, const uint32_t* cm, int t, const int64_t* positions, int count,
                                      uint8_t* x_enc, const int* gate, int want, hipStream_t s) {
   return ec_launch_commit_eval_boxes(group, cm, t, positions, count, x_enc, gate, want, 1, 0, 0, 0, s);
+}
+// X of the boxes of a run, one workgroup per tile (commit_eval_tiles_body); x_pts: the same points in internal coordinates or null
+extern "C" int ec_launch_commit_eval_tiles(int group, const uint32_t* cm, const uint32_t* tiles, int ntiles, const uint32_t* boxes,
+                                           const int64_t* positions, uint8_t* x_enc, uint32_t* x_pts, hipStream_t s) {
+  if (ntiles <= 0) return 0;
+  if (group == 1)
+    hipLaunchKernelGGL(k_secp_commit_eval_tiles, dim3(ntiles), dim3(64), 0, s, cm, tiles, boxes, positions, x_enc, x_pts);
+  else
+    hipLaunchKernelGGL(k_rist_commit_eval_tiles, dim3(ntiles), dim3(64), 0, s, cm, tiles, boxes, positions, x_enc, x_pts);
+  return (int)hipGetLastError();
 }
 extern "C" int ec_launch_dual_mul(int group, const uint8_t* p1, size_t p1_stride, const uint8_t* k1, const uint8_t* p2,
                                   const uint8_t* k2, size_t k2_stride, int count, uint8_t* out, uint8_t* ok,

@@ -57,6 +57,10 @@ struct DevBuf {
 
 }  // namespace
 
+// mpvss_ec_verify_many: what a context does with runs of small boxes until mpvss_ctx_set_ec_box_groups says otherwise (DESIGN
+// section 8, "Runs of small boxes": the measurement the value rests on)
+constexpr int EC_BOX_GROUPS_DEFAULT = 1;
+
 struct EcWork {   // device workspace of the elliptic-curve entry points (one per context and one per block slot)
   DevBuf a, b, c, d, e, pos, cm, cmenc, x, o1, o2, ok, gen, chal, pts, fdst;
   DevBuf tab1, tab2, tab3;       // window tables of per-share bases: [n][8][cached words]
@@ -340,6 +344,10 @@ struct mpvss_ctx {
   EcWork ecwork;
   // mpvss_ec_reconstruct_many_stats (capi_scalar.inc), both curves together
   unsigned long long ec_rec_passes = 0, ec_rec_grouped_secrets = 0, ec_rec_single_secrets = 0;
+  // mpvss_ec_verify_many (capi_ec.inc): runs of small boxes as one dense batch (mpvss_ctx_set_ec_box_groups: 0 never, 1 automatic),
+  // and mpvss_ec_verify_many_stats, both curves together
+  int ec_box_groups = EC_BOX_GROUPS_DEFAULT;
+  unsigned long long ec_many_passes = 0, ec_many_grouped_boxes = 0, ec_many_single_boxes = 0;
   // workspace of the run-time MODP group entry points (capi_modp_rt.inc), used under `mu`
   DevBuf rt_consts, rt_in[6], rt_out[3], rt_tab1, rt_tab2, rt_tabg, rt_cm, rt_small[2];
   // the scalar ring Z/(q-1) on the device (capi_modp_rt.inc, "scalar ring on the device"): the constants of q', the staged

@@ -210,6 +210,9 @@ unsafe extern "C" {
     pub fn mpvss_ec_transcript_verdict(group: c_int, state: *const u8, challenge_host: *const u8, verdict: *mut c_int, digest32_out: *mut u8) -> c_int;
     pub fn mpvss_ec_verify_many(ctx: *mut mpvss_ctx, group: c_int, space: c_int, boxes: *const mpvss_ec_box, count: usize, depth: c_int,
                                 hash_threads: c_int, verdicts: *mut c_int, digests32: *mut u8) -> c_int;
+    pub fn mpvss_ctx_set_ec_box_groups(ctx: *mut mpvss_ctx, mode: c_int) -> c_int;
+    pub fn mpvss_ec_verify_many_stats(ctx: *mut mpvss_ctx, passes: *mut c_ulonglong, grouped_boxes: *mut c_ulonglong,
+                                      single_boxes: *mut c_ulonglong) -> c_int;
     pub fn mpvss_ec_verify_shares(ctx: *mut mpvss_ctx, group: c_int, space: c_int, pk: *const u8, s: *const u8, y: *const u8, c: *const u8,
                                   r: *const u8, n: usize, verdicts_host: *mut u8) -> c_int;
     pub fn mpvss_ec_verify_shares_compute(ctx: *mut mpvss_ctx, group: c_int, space: c_int, pk: *const u8, s: *const u8,
