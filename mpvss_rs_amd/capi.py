@@ -836,15 +836,54 @@ class Engine:
             out.update(X=bytes(kx)[: n * EB], a1=bytes(k1)[: n * EB], a2=bytes(k2)[: n * EB])
         return out
 
-    # ---- many boxes of a run-time group in one call ----------------------------------------------------------------------
-    def _group_verify_many(self, grp: "ModpGroup", space: int, arr, count: int, hash_threads: int):
+    # ---- what the four *_many calls and their stats share (the C side: csrc/host_many.h) ---------------------------------------
+    def _three_counters(self, fn, name: str, keys) -> dict:
+        """fn(ctx, &a, &b, &c) as {keys[0]: a, keys[1]: b, keys[2]: c}"""
+        vals = [C.c_ulonglong(0) for _ in keys]
+        self._check(fn(self.ctx, *map(C.byref, vals)), name)
+        return {k: int(v.value) for k, v in zip(keys, vals)}
+
+    def _verify_many(self, fn, name: str, args):
+        """fn(ctx, *args, verdicts, digests); args = (group, space, boxes, count, ...).  [(verdict, digest)] in box order."""
+        count = args[3]
         verdicts = (C.c_int * max(count, 1))()
         kd, pd = _out(32 * count)
-        self._check(self.lib.mpvss_modp_group_verify_many(self.ctx, grp.handle, space, arr, count, int(hash_threads), verdicts, pd),
-                    "group_verify_many")
+        self._check(fn(self.ctx, *args, verdicts, pd), name)
         raw = bytes(kd)
         return [(bool(verdicts[i]), raw[32 * i:32 * i + 32]) for i in range(count)]
 
+    @staticmethod
+    def _secret_array(struct, unit: int, secrets: Sequence[dict], device: bool):
+        """(keep-alive list, array of `struct`) of a *_reconstruct_many call: positions are host memory in either space; the shares
+        are host bytes of `unit` bytes each (m = the positions' count, or the shares' without positions), or shares_ptr and m"""
+        keep, arr = [], (struct * max(len(secrets), 1))()
+        for i, s in enumerate(secrets):
+            positions = s.get("positions")
+            pos = (C.c_int64 * max(len(positions), 1))(*positions) if positions is not None else None
+            if device:
+                m, ks, ps = int(s["m"]), None, (C.c_void_p(s["shares_ptr"]) if s.get("shares_ptr") else None)
+            else:
+                shares = s.get("shares")
+                m = len(positions) if positions is not None else len(shares or b"") // unit
+                ks, ps = _buf(shares or None)
+            keep.append((pos, ks))
+            arr[i] = struct(C.cast(pos, C.c_void_p) if pos is not None else None, ps, m)
+        return keep, arr
+
+    def _reconstruct_many(self, fn, name: str, group, struct, unit: int, space: int, secrets: Sequence[dict], host_threads: int,
+                          want_masks: bool):
+        """fn(ctx, group, space, secrets, count, host_threads, status, gs, masks): [(status, G^s, mask)] in the order given"""
+        count = len(secrets)
+        keep, arr = self._secret_array(struct, unit, secrets, space == MPVSS_DEVICE)
+        status = (C.c_int * max(count, 1))()
+        kg, pg = _out(count * unit)
+        km, pm = _out(32 * count) if want_masks else (None, None)
+        self._check(fn(self.ctx, group, space, arr, count, int(host_threads), status, pg, pm), name)
+        gs = bytes(kg)
+        masks = bytes(km) if want_masks else None
+        return [(int(status[i]), gs[i * unit:(i + 1) * unit], masks[32 * i:32 * i + 32] if want_masks else None) for i in range(count)]
+
+    # ---- many boxes of a run-time group in one call ----------------------------------------------------------------------
     def group_verify_many(self, grp: "ModpGroup", boxes: Sequence[dict], hash_threads: int = 0):
         """boxes: dicts with commitments, positions, pubkeys, shares, responses, challenge (host bytes; None: a null pointer) and,
         in place of pubkeys, keyset (a GroupKeySet) with key_offset.  Returns [(verdict, digest)] in box order: what
@@ -859,7 +898,8 @@ class Engine:
             keep.append((pos, bufs, ks))
             arr[i] = GroupBox(bufs[0][1], len(b.get("commitments") or b"") // EB, C.cast(pos, C.c_void_p), bufs[1][1], bufs[2][1],
                               bufs[3][1], n, bufs[4][1], ks.handle if ks is not None else None, int(b.get("key_offset", 0)))
-        return self._group_verify_many(grp, MPVSS_HOST, arr, len(boxes), hash_threads)
+        return self._verify_many(self.lib.mpvss_modp_group_verify_many, "group_verify_many",
+                                 (grp.handle, MPVSS_HOST, arr, len(boxes), int(hash_threads)))
 
     def group_verify_many_device(self, grp: "ModpGroup", boxes: Sequence[dict], hash_threads: int = 0):
         """the same with every array of a box in HBM: dicts with commitments_ptr, t, positions_ptr (int64), pubkeys_ptr,
@@ -872,13 +912,13 @@ class Engine:
             ptr = lambda k: C.c_void_p(b[k]) if b.get(k) else None
             arr[i] = GroupBox(ptr("commitments_ptr"), int(b["t"]), ptr("positions_ptr"), ptr("pubkeys_ptr"), ptr("shares_ptr"),
                               ptr("responses_ptr"), int(b["n"]), pc, ks.handle if ks is not None else None, int(b.get("key_offset", 0)))
-        return self._group_verify_many(grp, MPVSS_DEVICE, arr, len(boxes), hash_threads)
+        return self._verify_many(self.lib.mpvss_modp_group_verify_many, "group_verify_many",
+                                 (grp.handle, MPVSS_DEVICE, arr, len(boxes), int(hash_threads)))
 
     def group_verify_many_stats(self) -> dict:
         """since the context was created: grouped passes, boxes that went through them, boxes that took the one-box path"""
-        g, b, s = C.c_ulonglong(0), C.c_ulonglong(0), C.c_ulonglong(0)
-        self._check(self.lib.mpvss_modp_group_verify_many_stats(self.ctx, C.byref(g), C.byref(b), C.byref(s)), "group_verify_many_stats")
-        return {"groups": int(g.value), "grouped_boxes": int(b.value), "single_boxes": int(s.value)}
+        return self._three_counters(self.lib.mpvss_modp_group_verify_many_stats, "group_verify_many_stats",
+                                    ("groups", "grouped_boxes", "single_boxes"))
 
     def group_deal_keyset(self, grp: "ModpGroup", coeffs: bytes, positions: Sequence[int], keyset: "GroupKeySet", key_offset: int,
                           witnesses: bytes) -> dict:
@@ -926,52 +966,24 @@ class Engine:
         return self._group_reconstruct(grp, MPVSS_DEVICE, positions, C.c_void_p(shares_dev_ptr), m, want_mask)
 
     # ---- many secrets of a run-time group in one call ----------------------------------------------------------------------
-    def _group_reconstruct_many(self, grp: "ModpGroup", space: int, arr, count: int, host_threads: int, want_masks: bool):
-        EB = grp.elem_bytes
-        status = (C.c_int * max(count, 1))()
-        kg, pg = _out(count * EB)
-        km, pm = _out(32 * count) if want_masks else (None, None)
-        self._check(self.lib.mpvss_modp_group_reconstruct_many(self.ctx, grp.handle, space, arr, count, int(host_threads), status, pg,
-                                                               pm), "group_reconstruct_many")
-        gs = bytes(kg)
-        masks = bytes(km) if want_masks else None
-        return [(int(status[i]), gs[i * EB:(i + 1) * EB], masks[32 * i:32 * i + 32] if want_masks else None) for i in range(count)]
-
     def group_reconstruct_many(self, grp: "ModpGroup", secrets: Sequence[dict], host_threads: int = 0, want_masks: bool = True):
         """secrets: dicts with positions (a sequence of int) and shares (host bytes); None: a null pointer.  Returns
         [(status, G^s, mask)] in the order given: for status 0 what group_reconstruct gives secret by secret, the Lagrange
         coefficients computed once per distinct position list and small secrets travelling in groups; a refused secret has
         status -1, zeros for G^s and a mask of zeros."""
-        EB = grp.elem_bytes
-        keep, arr = [], (GroupSecret * max(len(secrets), 1))()
-        for i, s in enumerate(secrets):
-            positions, shares = s.get("positions"), s.get("shares")
-            m = len(positions) if positions is not None else len(shares or b"") // EB
-            pos = (C.c_int64 * max(m, 1))(*positions) if positions is not None else None
-            ks, ps = _buf(shares or None)
-            keep.append((pos, ks))
-            arr[i] = GroupSecret(C.cast(pos, C.c_void_p) if pos is not None else None, ps, m)
-        return self._group_reconstruct_many(grp, MPVSS_HOST, arr, len(secrets), host_threads, want_masks)
+        return self._reconstruct_many(self.lib.mpvss_modp_group_reconstruct_many, "group_reconstruct_many", grp.handle, GroupSecret,
+                                      grp.elem_bytes, MPVSS_HOST, secrets, host_threads, want_masks)
 
     def group_reconstruct_many_device(self, grp: "ModpGroup", secrets: Sequence[dict], host_threads: int = 0, want_masks: bool = True):
         """the same with the shares of every secret in HBM ([m][elem_bytes] bytes, left unchanged): dicts with positions (host),
         shares_ptr and m"""
-        keep, arr = [], (GroupSecret * max(len(secrets), 1))()
-        for i, s in enumerate(secrets):
-            positions = s.get("positions")
-            m = int(s["m"])
-            pos = (C.c_int64 * max(len(positions), 1))(*positions) if positions is not None else None
-            keep.append(pos)
-            arr[i] = GroupSecret(C.cast(pos, C.c_void_p) if pos is not None else None,
-                                 C.c_void_p(s["shares_ptr"]) if s.get("shares_ptr") else None, m)
-        return self._group_reconstruct_many(grp, MPVSS_DEVICE, arr, len(secrets), host_threads, want_masks)
+        return self._reconstruct_many(self.lib.mpvss_modp_group_reconstruct_many, "group_reconstruct_many", grp.handle, GroupSecret,
+                                      grp.elem_bytes, MPVSS_DEVICE, secrets, host_threads, want_masks)
 
     def group_reconstruct_many_stats(self) -> dict:
         """since the context was created: grouped passes, secrets that went through them, secrets that took the one-secret path"""
-        p, g, s = C.c_ulonglong(0), C.c_ulonglong(0), C.c_ulonglong(0)
-        self._check(self.lib.mpvss_modp_group_reconstruct_many_stats(self.ctx, C.byref(p), C.byref(g), C.byref(s)),
-                    "group_reconstruct_many_stats")
-        return {"passes": int(p.value), "grouped_secrets": int(g.value), "single_secrets": int(s.value)}
+        return self._three_counters(self.lib.mpvss_modp_group_reconstruct_many_stats, "group_reconstruct_many_stats",
+                                    ("passes", "grouped_secrets", "single_secrets"))
 
     # ---- sharded verification (one engine per GPU; see mpvss_rs_amd/sharding.py)
     def verify_block_compute(self, commitments: bytes, positions: Sequence[int], pubkeys: bytes, shares: bytes,
@@ -1227,52 +1239,24 @@ class Engine:
         return self._reconstruct(group, MPVSS_DEVICE, positions, C.c_void_p(shares_dev_ptr), m, want_mask)
 
     # ---- many secrets of a curve group in one call -------------------------------------------------------------------------
-    def _ec_reconstruct_many(self, group: int, space: int, arr, count: int, host_threads: int, want_masks: bool):
-        L = EC_ENC[group]
-        status = (C.c_int * max(count, 1))()
-        kg, pg = _out(count * L)
-        km, pm = _out(32 * count) if want_masks else (None, None)
-        self._check(self.lib.mpvss_ec_reconstruct_many(self.ctx, group, space, arr, count, int(host_threads), status, pg, pm),
-                    "ec_reconstruct_many")
-        gs = bytes(kg)
-        masks = bytes(km) if want_masks else None
-        return [(int(status[i]), gs[i * L:(i + 1) * L], masks[32 * i:32 * i + 32] if want_masks else None) for i in range(count)]
-
     def ec_reconstruct_many(self, group: int, secrets: Sequence[dict], host_threads: int = 0, want_masks: bool = True):
         """secrets: dicts with positions (a sequence of int) and shares (host bytes); None: a null pointer.  Returns
         [(status, G^s, mask)] in the order given: for status 0 what ec_reconstruct gives secret by secret, the Lagrange
         coefficients computed once per distinct position list and small secrets travelling in groups; a refused secret has
         status -1, zeros for G^s and a mask of zeros."""
-        L = EC_ENC[group]
-        keep, arr = [], (EcSecret * max(len(secrets), 1))()
-        for i, s in enumerate(secrets):
-            positions, shares = s.get("positions"), s.get("shares")
-            m = len(positions) if positions is not None else len(shares or b"") // L
-            pos = (C.c_int64 * max(m, 1))(*positions) if positions is not None else None
-            ks, ps = _buf(shares or None)
-            keep.append((pos, ks))
-            arr[i] = EcSecret(C.cast(pos, C.c_void_p) if pos is not None else None, ps, m)
-        return self._ec_reconstruct_many(group, MPVSS_HOST, arr, len(secrets), host_threads, want_masks)
+        return self._reconstruct_many(self.lib.mpvss_ec_reconstruct_many, "ec_reconstruct_many", group, EcSecret, EC_ENC[group], MPVSS_HOST,
+                                      secrets, host_threads, want_masks)
 
     def ec_reconstruct_many_device(self, group: int, secrets: Sequence[dict], host_threads: int = 0, want_masks: bool = True):
         """the same with the encoded shares of every secret in HBM (left unchanged): dicts with positions (host), shares_ptr
         and m"""
-        keep, arr = [], (EcSecret * max(len(secrets), 1))()
-        for i, s in enumerate(secrets):
-            positions = s.get("positions")
-            m = int(s["m"])
-            pos = (C.c_int64 * max(len(positions), 1))(*positions) if positions is not None else None
-            keep.append(pos)
-            arr[i] = EcSecret(C.cast(pos, C.c_void_p) if pos is not None else None,
-                              C.c_void_p(s["shares_ptr"]) if s.get("shares_ptr") else None, m)
-        return self._ec_reconstruct_many(group, MPVSS_DEVICE, arr, len(secrets), host_threads, want_masks)
+        return self._reconstruct_many(self.lib.mpvss_ec_reconstruct_many, "ec_reconstruct_many", group, EcSecret, EC_ENC[group], MPVSS_DEVICE,
+                                      secrets, host_threads, want_masks)
 
     def ec_reconstruct_many_stats(self) -> dict:
         """since the context was created: grouped passes, secrets that went through them, secrets that took the one-secret path"""
-        p, g, s = C.c_ulonglong(0), C.c_ulonglong(0), C.c_ulonglong(0)
-        self._check(self.lib.mpvss_ec_reconstruct_many_stats(self.ctx, C.byref(p), C.byref(g), C.byref(s)),
-                    "ec_reconstruct_many_stats")
-        return {"passes": int(p.value), "grouped_secrets": int(g.value), "single_secrets": int(s.value)}
+        return self._three_counters(self.lib.mpvss_ec_reconstruct_many_stats, "ec_reconstruct_many_stats",
+                                    ("passes", "grouped_secrets", "single_secrets"))
 
     def ec_batch_exp_generator(self, group: int, scalars: bytes) -> bytes:
         n = len(scalars) // 32
@@ -1295,14 +1279,6 @@ class Engine:
         self._check(self.lib.mpvss_ec_verify_block_absorb(self.ctx, ps, None, None, None), "ec_verify_block_absorb")
         return bytes(ks)
 
-    def _ec_verify_many(self, group: int, space: int, arr, count: int, depth: int, hash_threads: int):
-        verdicts = (C.c_int * max(count, 1))()
-        kd, pd = _out(32 * count)
-        self._check(self.lib.mpvss_ec_verify_many(self.ctx, group, space, arr, count, depth, hash_threads, verdicts, pd),
-                    "ec_verify_many")
-        raw = bytes(kd)
-        return [(bool(verdicts[i]), raw[32 * i:32 * i + 32]) for i in range(count)]
-
     def ec_verify_many(self, group: int, boxes: Sequence[dict], depth: int = 6, hash_threads: int = 3):
         """boxes: dicts with commitments, positions, pubkeys, shares, responses, challenge (host bytes; None for one of the
         byte arrays: a null pointer).  Returns [(verdict, digest)] in box order.  Runs of small boxes travel as one dense
@@ -1316,7 +1292,8 @@ class Engine:
             keep.append((pos, bufs))
             arr[i] = EcBox(bufs[0][1], len(b["commitments"] or b"") // e, C.cast(pos, C.c_void_p), bufs[1][1], bufs[2][1],
                            bufs[3][1], n, bufs[4][1])
-        return self._ec_verify_many(group, MPVSS_HOST, arr, len(boxes), depth, hash_threads)
+        return self._verify_many(self.lib.mpvss_ec_verify_many, "ec_verify_many",
+                                 (group, MPVSS_HOST, arr, len(boxes), depth, hash_threads))
 
     def ec_verify_many_device(self, group: int, boxes: Sequence[dict], depth: int = 6, hash_threads: int = 3):
         """the same with every box's arrays in HBM (left unchanged): dicts with commitments_ptr, t, positions_ptr, pubkeys_ptr,
@@ -1328,7 +1305,8 @@ class Engine:
             ptr = [C.c_void_p(b[k]) if b.get(k) else None for k in ("commitments_ptr", "positions_ptr", "pubkeys_ptr", "shares_ptr",
                                                                      "responses_ptr")]
             arr[i] = EcBox(ptr[0], int(b["t"]), ptr[1], ptr[2], ptr[3], ptr[4], int(b["n"]), pc)
-        return self._ec_verify_many(group, MPVSS_DEVICE, arr, len(boxes), depth, hash_threads)
+        return self._verify_many(self.lib.mpvss_ec_verify_many, "ec_verify_many",
+                                 (group, MPVSS_DEVICE, arr, len(boxes), depth, hash_threads))
 
     def set_ec_box_groups(self, mode: int) -> None:
         """mpvss_ctx_set_ec_box_groups: runs of small boxes of ec_verify_many as one dense batch -- 0 every box on its own,
@@ -1337,9 +1315,8 @@ class Engine:
 
     def ec_verify_many_stats(self) -> dict:
         """since the context was created: grouped passes, boxes they verified, boxes verified through a slot of their own"""
-        p, g, s = C.c_ulonglong(0), C.c_ulonglong(0), C.c_ulonglong(0)
-        self._check(self.lib.mpvss_ec_verify_many_stats(self.ctx, C.byref(p), C.byref(g), C.byref(s)), "ec_verify_many_stats")
-        return {"passes": int(p.value), "grouped_boxes": int(g.value), "single_boxes": int(s.value)}
+        return self._three_counters(self.lib.mpvss_ec_verify_many_stats, "ec_verify_many_stats",
+                                    ("passes", "grouped_boxes", "single_boxes"))
 
     def ec_batch_mul(self, group: int, a: bytes, b: bytes) -> bytes:
         n = len(a) // EC_ENC[group]

@@ -1119,7 +1119,7 @@ extern "C" int mpvss_ec_verify_distribution(mpvss_ctx* ctx, int group, int space
 // table builds, two or three multiplications, an addition and two encodes, about ten copies, two forks and an event wait: the
 // latency of a chain of narrow launches.  A run of such boxes travels instead as ONE concatenation through the launches of one
 // box, X by k_*_commit_eval_tiles (a tile = up to 64 shares of one box = one workgroup) and the DLEQ multiplications with a
-// challenge per share.  THE grouping decision is in mpvss_ec_verify_many below.
+// challenge per share.  Which boxes travel together: many::walk (host_many.h), called by mpvss_ec_verify_many below.
 // =====================================================================================================================
 namespace {
 
@@ -1127,8 +1127,6 @@ namespace {
 // forward differences or the X batches serve changes its path.  Derived, not measured.
 constexpr size_t EC_GROUP_BOX_MAX = 4096;
 constexpr size_t EC_TILE = 64;                     // shares per tile: one wave, one workgroup of the 64-lane curve kernels
-
-int rt_many_threads(int requested, size_t work, size_t per_thread);      // capi_scalar.inc
 
 // may this box travel in a run?  Judged on the host before anything is launched.
 bool ec_box_small(const EcInfo* gi, const mpvss_ec_box& b) {
@@ -1150,21 +1148,19 @@ int ec_many_run(mpvss_ctx* ctx, const EcInfo* gi, int space, const mpvss_ec_box*
   // the tables: tiles {box, first share, live count}, boxes {first commitment, t} (also the commitments' gather segments),
   // shares {first share, n} (the gather segments of the per-share arrays)
   std::vector<uint32_t> tab;
-  std::vector<size_t> first(B + 1), first_cm(B + 1);
+  std::vector<size_t> first(B + 1), first_cm(B + 1), counts(B);
   size_t S = 0, T = 0;
   for (size_t k = 0; k < B; ++k) {
     const mpvss_ec_box& b = boxes[lo + k];
     first[k] = S;
     first_cm[k] = T;
-    for (size_t off = 0; off < b.n; off += EC_TILE) {
-      const uint32_t tile[3] = {(uint32_t)k, (uint32_t)(S + off), (uint32_t)std::min(b.n - off, EC_TILE)};
-      tab.insert(tab.end(), tile, tile + 3);
-    }
+    counts[k] = b.n;
     S += b.n;
     T += b.t;
   }
   first[B] = S;
   first_cm[B] = T;
+  many::tile_table(counts.data(), B, EC_TILE, 3, tab);
   const size_t ntiles = tab.size() / 3;
   const size_t o_btab = tab.size();
   for (size_t k = 0; k < B; ++k) { tab.push_back((uint32_t)first_cm[k]); tab.push_back((uint32_t)boxes[lo + k].t); }
@@ -1185,10 +1181,7 @@ int ec_many_run(mpvss_ctx* ctx, const EcInfo* gi, int space, const mpvss_ec_box*
   spans_reset(ctx);
   RET_IF(ensure_pinned(ctx, off));
   uint8_t* pin = (uint8_t*)ctx->pin;
-  struct Drain {            // no copy out of (or into) the staging is pending when the pass ends, whichever way it ends
-    mpvss_ctx* c;
-    ~Drain() { (void)hipStreamSynchronize(c->stream); }
-  } drain{ctx};
+  StreamDrain drain{ctx};   // (the staging is the context's: nothing of this pass may be pending in it afterwards)
   memcpy(pin + p_tab, tab.data(), tab.size() * 4);
   const uint8_t** srcs = (const uint8_t**)(pin + p_tab + tab_bytes);      // [array][box]: positions, commitments, y, Y, r
   for (size_t k = 0; k < B; ++k) {
@@ -1274,7 +1267,7 @@ int ec_many_run(mpvss_ctx* ctx, const EcInfo* gi, int space, const mpvss_ec_box*
   struct Refusal { const char* what = nullptr; size_t i = 0; bool scalar = false; };
   std::vector<Refusal> refused(B);
   // automatic: one thread per 512 shares of the run; 1 .. 16, never sized by the machine
-  const size_t nth = std::min<size_t>((size_t)rt_many_threads(hash_threads, S, 512), B);
+  const size_t nth = std::min<size_t>((size_t)many::many_threads(hash_threads, S, 512), B);
   hsc::parallel_indices((unsigned)nth, [&](unsigned part) {
     for (size_t k = B * part / nth; k < B * (part + 1) / nth; ++k) {
       const mpvss_ec_box& b = boxes[lo + k];
@@ -1364,30 +1357,24 @@ extern "C" int mpvss_ec_verify_many(mpvss_ctx* ctx, int group, int space, const 
                                              digests32 ? digests32 + 32 * idx : nullptr);
         });
   };
-  // THE grouping decision: a run is a maximal stretch of consecutive small boxes (ec_box_small) that hold at most MAX_CHUNK shares
-  // and at most MAX_CHUNK commitments together.  A run of two or more boxes is one grouped pass; every other box -- a run of
-  // one, an empty, malformed or larger box -- goes through the pipeline, which is applied to the stretches between the passes
-  // (the X-batch look-ahead works inside a stretch).  `depth` means nothing inside a pass.
+  // The runs of many::walk: small boxes (ec_box_small) travel together, (n, t) against MAX_CHUNK shares and MAX_CHUNK commitments.
+  // A run of two or more boxes is one grouped pass; every other box -- a run of one, an empty, malformed or larger box -- stays
+  // where it is and goes through the pipeline, which is applied to the stretches between the passes (the X-batch look-ahead
+  // works inside a stretch).  Every box that is not small ends a run, so a run is the range [front, back].  `depth` means nothing
+  // inside a pass.
   int rc = MPVSS_OK;
   size_t stretch = 0;                                    // first box not yet handed to the pipeline or to a pass
-  for (size_t i = 0; mode == 1 && i < count && rc == MPVSS_OK;) {
-    if (!ec_box_small(gi, boxes[i])) { ++i; continue; }
-    size_t j = i, shares = 0, cms = 0;
-    while (j < count && ec_box_small(gi, boxes[j]) && shares + boxes[j].n <= MAX_CHUNK && cms + boxes[j].t <= MAX_CHUNK) {
-      shares += boxes[j].n;
-      cms += boxes[j].t;
-      ++j;
-    }
-    if (j - i >= 2) {
-      rc = pipeline(stretch, i);
-      if (rc == MPVSS_OK) {
-        std::lock_guard<std::mutex> lk(ctx->mu);
-        rc = ec_many_run(ctx, gi, space, boxes, i, j, hash_threads, verdicts, digests32);
-      }
-      stretch = j;
-    }
-    i = j;
-  }
+  if (mode == 1)
+    rc = many::walk(
+        count, MAX_CHUNK, MAX_CHUNK, [&](size_t i) { return ec_box_small(gi, boxes[i]) ? many::GROUPED : many::ALONE; },
+        [&](size_t i) { return many::Cost{boxes[i].n, boxes[i].t}; }, [](size_t, size_t) { return true; },
+        [](size_t) { return MPVSS_OK; },
+        [&](const std::vector<size_t>& run) -> int {
+          RET_IF(pipeline(stretch, run.front()));
+          stretch = run.back() + 1;
+          std::lock_guard<std::mutex> lk(ctx->mu);
+          return ec_many_run(ctx, gi, space, boxes, run.front(), run.back() + 1, hash_threads, verdicts, digests32);
+        });
   if (rc == MPVSS_OK) rc = pipeline(stretch, count);
   std::lock_guard<std::mutex> lk(ctx->mu);
   ctx->ec_many_single_boxes += finished.load();
@@ -1404,12 +1391,8 @@ extern "C" int mpvss_ctx_set_ec_box_groups(mpvss_ctx* ctx, int mode) {
 
 extern "C" int mpvss_ec_verify_many_stats(mpvss_ctx* ctx, unsigned long long* passes, unsigned long long* grouped_boxes,
                                           unsigned long long* single_boxes) {
-  if (!ctx) return MPVSS_E_INVALID;
-  std::lock_guard<std::mutex> lk(ctx->mu);
-  if (passes) *passes = ctx->ec_many_passes;
-  if (grouped_boxes) *grouped_boxes = ctx->ec_many_grouped_boxes;
-  if (single_boxes) *single_boxes = ctx->ec_many_single_boxes;
-  return MPVSS_OK;
+  return many_stats(ctx, &mpvss_ctx::ec_many_passes, &mpvss_ctx::ec_many_grouped_boxes, &mpvss_ctx::ec_many_single_boxes, passes,
+                    grouped_boxes, single_boxes);
 }
 
 // ---- verify_share, batched (participant.rs:1346-1371, 1789-1814) ---------------------------------------------

@@ -1953,7 +1953,7 @@ extern "C" int mpvss_modp_group_deal_keyset(mpvss_ctx* ctx, const mpvss_modp_gro
 // verifier tens to hundreds of small boxes for the same keys; one box per call is the latency of a chain of Montgomery products
 // on one or two waves.  Runs of small boxes therefore travel as ONE dense concatenation through the launches of one box:
 // k_rt_to_mont over all commitments, k_rt_commit_eval_tiles (a tile = up to RT_NUMS shares of one box = one workgroup), the
-// challenge of each box spread to its shares, then rt_dleq_dev with a per-share c.  THE grouping decision is rt_many_walk below.
+// challenge of each box spread to its shares, then rt_dleq_dev with a per-share c.  Which boxes travel together: many::walk (host_many.h).
 // =====================================================================================================================
 namespace {
 
@@ -2023,23 +2023,21 @@ int rt_many_run(mpvss_ctx* ctx, const mpvss_modp_group* grp, int space, const mp
   const mpvss_modp_group_keyset* ks = boxes[run[0]].keyset;
   // the tables: tiles {box, first share, live count, 0}, boxes {first commitment, t}, and with a key set the key of every share
   std::vector<uint32_t> tiles, btab(2 * B), key_of;
-  std::vector<size_t> first(B + 1);
+  std::vector<size_t> first(B + 1), counts(B);
   size_t S = 0, T = 0;
   for (size_t k = 0; k < B; ++k) {
     const mpvss_modp_group_box& b = boxes[run[k]];
     first[k] = S;
+    counts[k] = b.n;
     btab[2 * k] = (uint32_t)T;
     btab[2 * k + 1] = (uint32_t)b.t;
-    for (size_t off = 0; off < b.n; off += RT_TILE) {
-      const uint32_t tile[4] = {(uint32_t)k, (uint32_t)(S + off), (uint32_t)std::min(b.n - off, RT_TILE), 0};
-      tiles.insert(tiles.end(), tile, tile + 4);
-    }
     if (ks)
       for (size_t i = 0; i < b.n; ++i) key_of.push_back((uint32_t)(b.key_offset + i));
     S += b.n;
     T += b.t;
   }
   first[B] = S;
+  many::tile_table(counts.data(), B, RT_TILE, 4, tiles);
   const size_t ntiles = tiles.size() / 4;
   std::vector<uint8_t> ch(B * EB);
   for (size_t k = 0; k < B; ++k) memcpy(ch.data() + k * EB, boxes[run[k]].challenge_host, EB);
@@ -2048,10 +2046,7 @@ int rt_many_run(mpvss_ctx* ctx, const mpvss_modp_group* grp, int space, const mp
   std::vector<uint8_t> g_pos, g_cm, g_y, g_Y, g_r, hX, h1, h2, hYdev;
   std::vector<int64_t> pos_back;
   RtCall f(ctx, grp, space);
-  struct Drain {            // no copy out of (or into) the vectors above outlives them, whichever way the pass ends
-    mpvss_ctx* c;
-    ~Drain() { (void)hipStreamSynchronize(c->stream); }
-  } drain{ctx};
+  StreamDrain drain{ctx};
   RET_IF(f.begin());
   auto part = [&](const uint8_t* mpvss_modp_group_box::*arr, size_t mpvss_modp_group_box::*cnt, size_t unit) {
     return [&run, boxes, arr, cnt, unit](size_t k, const void** src, size_t* bytes) {
@@ -2113,8 +2108,10 @@ int rt_many_run(mpvss_ctx* ctx, const mpvss_modp_group* grp, int space, const mp
   }
   RET_IF(f.settle());
   // the boxes' transcripts are independent: box k hashes the shares first[k] .. first[k+1] of the concatenation
-  auto hash_boxes = [&](size_t k0, size_t k1) {
-    for (size_t k = k0; k < k1; ++k) {
+  // automatic: one thread per 512 shares of the run (half a megabyte of transcript and more), never sized by the machine
+  const size_t nth = std::min<size_t>((size_t)many::many_threads(hash_threads, S, 512), B);
+  hsc::parallel_indices((unsigned)nth, [&](unsigned slice) {
+    for (size_t k = B * slice / nth; k < B * (slice + 1) / nth; ++k) {
       mpvss::Sha256 h;
       frame_shares(h, hX.data(), Y, h1.data(), h2.data(), first[k], first[k + 1], EB);
       uint8_t digest[32], c[RT_EB_MAX];
@@ -2123,19 +2120,7 @@ int rt_many_run(mpvss_ctx* ctx, const mpvss_modp_group* grp, int space, const mp
       rt_hash_to_scalar(grp, digest, 32, c);
       verdicts[run[k]] = memcmp(c, boxes[run[k]].challenge_host, EB) == 0 ? 1 : 0;
     }
-  };
-  // automatic: one thread per 512 shares of the run (half a megabyte of transcript and more), never sized by the machine
-  size_t nth = hash_threads > 0 ? (size_t)hash_threads : std::max<size_t>(1, S / 512);
-  nth = std::min(std::min<size_t>(nth, 16), B);
-  if (nth <= 1) {
-    hash_boxes(0, B);
-  } else {
-    std::vector<std::thread> pool;
-    pool.reserve(nth - 1);
-    for (size_t i = 1; i < nth; ++i) pool.emplace_back(hash_boxes, B * i / nth, B * (i + 1) / nth);
-    hash_boxes(0, B / nth);
-    for (auto& th : pool) th.join();
-  }
+  });
   ++ctx->rt_many_groups;
   ctx->rt_many_grouped_boxes += B;
   return f.end();
@@ -2152,54 +2137,29 @@ extern "C" int mpvss_modp_group_verify_many(mpvss_ctx* ctx, const mpvss_modp_gro
   if (!boxes || !verdicts) return fail(ctx, MPVSS_E_INVALID, "group_verify_many: bad argument");
   for (size_t i = 0; i < count; ++i) verdicts[i] = 0;
   if (digests32) memset(digests32, 0, 32 * count);         // a malformed box has no transcript: verdict 0, digest zero
-  // THE grouping decision: a run is a maximal stretch of consecutive small boxes that take keys the same way (arrays, or one and
-  // the same key set) and hold at most MAX_CHUNK shares (and commitments) together.  Empty and malformed boxes are settled here
-  // and do not end a run; a run of one box takes the one-box path, like every box that fits no run.
-  std::vector<size_t> run;
-  size_t run_shares = 0, run_cms = 0;
-  auto flush = [&]() -> int {
-    int rc = MPVSS_OK;
-    if (run.size() == 1) {
-      const size_t i = run[0];
-      rc = rt_many_single(ctx, grp, space, boxes[i], &verdicts[i], digests32 ? digests32 + 32 * i : nullptr);
-      if (rc == MPVSS_OK) ++ctx->rt_many_single_boxes;
-    } else if (run.size() > 1) {
-      rc = rt_many_run(ctx, grp, space, boxes, run, hash_threads, verdicts, digests32);
-    }
-    run.clear();
-    run_shares = run_cms = 0;
-    return rc;
-  };
-  for (size_t i = 0; i < count; ++i) {
-    const mpvss_modp_group_box& b = boxes[i];
-    const RtBoxKind kind = rt_box_kind(ctx, grp, b);
-    if (kind == RT_BOX_MALFORMED) continue;
-    if (kind == RT_BOX_EMPTY) {                           // the empty transcript, on the host
-      RET_IF(rt_many_single(ctx, grp, space, b, &verdicts[i], digests32 ? digests32 + 32 * i : nullptr));
-      continue;
-    }
-    if (kind == RT_BOX_SINGLE) {
-      RET_IF(flush());
-      RET_IF(rt_many_single(ctx, grp, space, b, &verdicts[i], digests32 ? digests32 + 32 * i : nullptr));
-      ++ctx->rt_many_single_boxes;
-      continue;
-    }
-    if (!run.empty() && (boxes[run[0]].keyset != b.keyset || run_shares + b.n > MAX_CHUNK || run_cms + b.t > MAX_CHUNK)) RET_IF(flush());
-    run.push_back(i);
-    run_shares += b.n;
-    run_cms += b.t;
-  }
-  return flush();
+  // The runs of many::walk: small boxes that take keys the same way (arrays, or one and the same key set) travel together, (n, t)
+  // against MAX_CHUNK shares and MAX_CHUNK commitments.  Malformed boxes are settled above and empty ones on the host (the empty
+  // transcript); neither ends a run.  A run of one box takes the one-box path, like every box that fits no run.
+  return many::walk(
+      count, MAX_CHUNK, MAX_CHUNK,
+      [&](size_t i) {
+        const RtBoxKind kind = rt_box_kind(ctx, grp, boxes[i]);
+        return kind == RT_BOX_MALFORMED ? many::SKIP : kind == RT_BOX_EMPTY ? many::ASIDE : kind == RT_BOX_SINGLE ? many::ALONE : many::GROUPED;
+      },
+      [&](size_t i) { return many::Cost{boxes[i].n, boxes[i].t}; },
+      [&](size_t first, size_t i) { return boxes[first].keyset == boxes[i].keyset; },
+      [&](size_t i) -> int {
+        RET_IF(rt_many_single(ctx, grp, space, boxes[i], &verdicts[i], digests32 ? digests32 + 32 * i : nullptr));
+        if (boxes[i].n > 0) ++ctx->rt_many_single_boxes;        // (an empty box ran nothing)
+        return MPVSS_OK;
+      },
+      [&](const std::vector<size_t>& run) { return rt_many_run(ctx, grp, space, boxes, run, hash_threads, verdicts, digests32); });
 }
 
 extern "C" int mpvss_modp_group_verify_many_stats(mpvss_ctx* ctx, unsigned long long* groups, unsigned long long* grouped_boxes,
                                                   unsigned long long* single_boxes) {
-  if (!ctx) return MPVSS_E_INVALID;
-  std::lock_guard<std::mutex> lk(ctx->mu);
-  if (groups) *groups = ctx->rt_many_groups;
-  if (grouped_boxes) *grouped_boxes = ctx->rt_many_grouped_boxes;
-  if (single_boxes) *single_boxes = ctx->rt_many_single_boxes;
-  return MPVSS_OK;
+  return many_stats(ctx, &mpvss_ctx::rt_many_groups, &mpvss_ctx::rt_many_grouped_boxes, &mpvss_ctx::rt_many_single_boxes, groups,
+                    grouped_boxes, single_boxes);
 }
 
 // =====================================================================================================================
@@ -2208,28 +2168,17 @@ extern "C" int mpvss_modp_group_verify_many_stats(mpvss_ctx* ctx, unsigned long 
 // call is the latency of a chain of Montgomery products plus ceil(log2 m) rounds of the pairwise product, on one or two waves,
 // and the same m Lagrange coefficients computed again by every call.  Here the coefficients are computed once per distinct
 // position list, and runs of secrets travel as ONE dense concatenation of shares through the launches of one secret, the
-// pairwise rounds replaced by one k_rt_product_segments launch (one workgroup per secret).  THE grouping decision is in
-// mpvss_modp_group_reconstruct_many below.
+// pairwise rounds replaced by one k_rt_product_segments launch (one workgroup per secret).  The plan of the position lists and the
+// walk that forms the passes: many::plan_secrets, many::walk_secrets (host_many.h).
 // =====================================================================================================================
 namespace {
 
-enum RtSecretKind { RT_SECRET_REFUSED, RT_SECRET_GROUPED, RT_SECRET_SINGLE };
-
-// what the host knows of a secret before anything is launched: its kind, and where its exponents and signs start in the call's
-// arrays (the coefficients of its position list; npos for a secret that computes its own)
-struct RtSecretPlan {
-  RtSecretKind kind = RT_SECRET_REFUSED;
-  size_t coef = (size_t)-1;
-};
-
-// (host threads of a call: rt_many_threads, capi_scalar.inc -- shared with mpvss_ec_reconstruct_many)
-
-// a grouped pass: the secrets run[0 .. B) (indices into `secrets`, all RT_SECRET_GROUPED), shares in all <= MAX_CHUNK.  The
+// a grouped pass: the secrets run[0 .. B) (indices into `secrets`, all many::SECRET_GROUPED), shares in all <= MAX_CHUNK.  The
 // launches of one secret over the concatenation, then one k_rt_product_segments launch and one settle.  A secret with a share that
 // is 0 mod q under a negative coefficient is refused here (the one copy back of a pass in device space shows it): its powers run
 // with the others, its result is dropped.
 int rt_reconstruct_pass(mpvss_ctx* ctx, const mpvss_modp_group* grp, int space, const mpvss_modp_group_secret* secrets,
-                        const std::vector<size_t>& run, const std::vector<RtSecretPlan>& plan, const uint8_t* exps, const char* negs,
+                        const std::vector<size_t>& run, const std::vector<many::SecretPlan>& plan, const uint8_t* exps, const char* negs,
                         int host_threads, int* status, uint8_t* gs_out, uint8_t* masks_out32) {
   const size_t B = run.size(), EB = grp->eb;
   std::vector<uint32_t> segs(2 * B);                                // {first factor, m} of every secret
@@ -2246,10 +2195,7 @@ int rt_reconstruct_pass(mpvss_ctx* ctx, const mpvss_modp_group* grp, int space, 
   std::vector<uint8_t> g_sh, g_exp(S * EB), h_sh, h_gs;
   for (size_t k = 0; k < B; ++k) memcpy(g_exp.data() + first[k] * EB, exps + plan[run[k]].coef * EB, secrets[run[k]].m * EB);
   RtCall f(ctx, grp, space);
-  struct Drain {            // no copy out of (or into) the vectors above outlives them, whichever way the pass ends
-    mpvss_ctx* c;
-    ~Drain() { (void)hipStreamSynchronize(c->stream); }
-  } drain{ctx};
+  StreamDrain drain{ctx};
   RET_IF(f.begin());
   RET_IF(rt_run_gather(ctx, space, B, S * EB, ctx->rt_in[0], g_sh, [&](size_t k, const void** src, size_t* bytes) {
     *src = secrets[run[k]].shares;
@@ -2287,7 +2233,7 @@ int rt_reconstruct_pass(mpvss_ctx* ctx, const mpvss_modp_group* grp, int space, 
                                                  dG, f.dc, ctx->stream));                              // one product per secret
   f.to_host(dG, B, h_gs);
   RET_IF(f.settle());
-  hsc::parallel_for(B, rt_many_threads(host_threads, B, 256), [&](size_t lo, size_t hi) {
+  hsc::parallel_for(B, many::many_threads(host_threads, B, 256), [&](size_t lo, size_t hi) {
     for (size_t k = lo; k < hi; ++k) {
       if (refused[k]) continue;
       const size_t i = run[k];
@@ -2321,58 +2267,19 @@ extern "C" int mpvss_modp_group_reconstruct_many(mpvss_ctx* ctx, const mpvss_mod
   memset(gs_out, 0, count * EB);
   if (masks_out32) memset(masks_out32, 0, 32 * count);
 
-  // the arguments of every secret, as the one-secret call judges them; then the Lagrange exponents ONCE per distinct position
-  // list -- the sequences equal element by element: a permuted list is another list, coefficients belong to indices -- of the
-  // secrets that may travel in a pass (a secret too long for one computes its own on the one-secret path)
-  std::vector<RtSecretPlan> plan(count);
-  std::map<std::vector<int64_t>, size_t> lists;          // position list -> its index
-  std::vector<const int64_t*> list_pos;
-  std::vector<size_t> list_m, list_first, list_of(count, (size_t)-1);
-  size_t coefs = 0;
-  for (size_t i = 0; i < count; ++i) {
-    const mpvss_modp_group_secret& s = secrets[i];
-    if (!s.positions_host || !s.shares || s.m == 0 || s.m > 0x7fffffff) continue;
-    bool ok = true;
-    for (size_t k = 0; k < s.m && ok; ++k) ok = s.positions_host[k] >= 1;
-    if (!ok) continue;
-    if (s.m > RT_GROUP_BOX_MAX || s.m > MAX_CHUNK) {
-      plan[i].kind = RT_SECRET_SINGLE;
-      continue;
-    }
-    plan[i].kind = RT_SECRET_GROUPED;
-    const auto it = lists.emplace(std::vector<int64_t>(s.positions_host, s.positions_host + s.m), list_pos.size());
-    if (it.second) {
-      list_pos.push_back(s.positions_host);
-      list_m.push_back(s.m);
-      list_first.push_back(coefs);
-      coefs += s.m;
-    }
-    list_of[i] = it.first->second;
-  }
-  lists.clear();
-  std::vector<uint8_t> exps(coefs * EB);
-  std::vector<char> negs(coefs, 0), coef_ok(coefs, 0);
-  // a coefficient costs m small products and one inversion at the modulus' width: a thread per 64 of them when the library chooses
-  hsc::parallel_for(coefs, rt_many_threads(host_threads, coefs, 64), [&](size_t lo, size_t hi) {
-    size_t l = std::upper_bound(list_first.begin(), list_first.end(), lo) - list_first.begin() - 1;
-    for (size_t c = lo; c < hi; ++c) {
-      while (l + 1 < list_first.size() && list_first[l + 1] <= c) ++l;
-      coef_ok[c] = rt_lagrange_exponent(grp, list_pos[l], list_m[l], c - list_first[l], exps.data() + c * EB, &negs[c]) ? 1 : 0;
-    }
-  });
-  for (size_t i = 0; i < count; ++i) {
-    if (plan[i].kind != RT_SECRET_GROUPED) continue;
-    const size_t l = list_of[i];
-    plan[i].coef = list_first[l];
-    // duplicate positions, or a denominator without inverse (an even (q-1)/2 among the causes): refused
-    if (std::find(coef_ok.begin() + list_first[l], coef_ok.begin() + list_first[l] + list_m[l], 0) != coef_ok.begin() + list_first[l] + list_m[l])
-      plan[i].kind = RT_SECRET_REFUSED;
-  }
-
-  // THE grouping decision: a pass is a maximal stretch of consecutive grouped secrets that hold at most MAX_CHUNK shares together,
-  // cut only at secret boundaries.  Refused secrets are settled above and do not end a pass; a pass of one secret takes the
-  // one-secret path, like every secret too long for a pass.  A code of the one-secret path other than MPVSS_E_INVALID (which
-  // refuses that secret alone) ends the call.
+  // the Lagrange exponents and their signs ONCE per distinct position list (a list without them has duplicate positions, or a
+  // denominator without inverse -- an even (q-1)/2 among the causes: its secrets are refused)
+  std::vector<uint8_t> exps;
+  std::vector<char> negs;
+  const std::vector<many::SecretPlan> plan =
+      many::plan_secrets(secrets, count, RT_GROUP_BOX_MAX, MAX_CHUNK, host_threads,
+                         [&](size_t coefs) {
+                           exps.resize(coefs * EB);
+                           negs.assign(coefs, 0);
+                         },
+                         [&](const int64_t* pos, size_t m, size_t j, size_t c) { return rt_lagrange_exponent(grp, pos, m, j, exps.data() + c * EB, &negs[c]); })
+          .secret;
+  // A code of the one-secret path other than MPVSS_E_INVALID (which refuses that secret alone) ends the call.
   auto single = [&](size_t i) -> int {
     const mpvss_modp_group_secret& s = secrets[i];
     const bool pre = plan[i].coef != (size_t)-1;
@@ -2385,36 +2292,13 @@ extern "C" int mpvss_modp_group_reconstruct_many(mpvss_ctx* ctx, const mpvss_mod
     ++ctx->rt_rec_single_secrets;
     return MPVSS_OK;
   };
-  std::vector<size_t> run;
-  size_t run_shares = 0;
-  auto flush = [&]() -> int {
-    int rc = MPVSS_OK;
-    if (run.size() == 1) rc = single(run[0]);
-    else if (run.size() > 1) rc = rt_reconstruct_pass(ctx, grp, space, secrets, run, plan, exps.data(), negs.data(), host_threads, status, gs_out, masks_out32);
-    run.clear();
-    run_shares = 0;
-    return rc;
-  };
-  for (size_t i = 0; i < count; ++i) {
-    if (plan[i].kind == RT_SECRET_REFUSED) continue;
-    if (plan[i].kind == RT_SECRET_SINGLE) {
-      RET_IF(flush());
-      RET_IF(single(i));
-      continue;
-    }
-    if (!run.empty() && run_shares + secrets[i].m > MAX_CHUNK) RET_IF(flush());
-    run.push_back(i);
-    run_shares += secrets[i].m;
-  }
-  return flush();
+  return many::walk_secrets(secrets, plan, MAX_CHUNK, single, [&](const std::vector<size_t>& run) {
+    return rt_reconstruct_pass(ctx, grp, space, secrets, run, plan, exps.data(), negs.data(), host_threads, status, gs_out, masks_out32);
+  });
 }
 
 extern "C" int mpvss_modp_group_reconstruct_many_stats(mpvss_ctx* ctx, unsigned long long* passes, unsigned long long* grouped_secrets,
                                                        unsigned long long* single_secrets) {
-  if (!ctx) return MPVSS_E_INVALID;
-  std::lock_guard<std::mutex> lk(ctx->mu);
-  if (passes) *passes = ctx->rt_rec_passes;
-  if (grouped_secrets) *grouped_secrets = ctx->rt_rec_grouped_secrets;
-  if (single_secrets) *single_secrets = ctx->rt_rec_single_secrets;
-  return MPVSS_OK;
+  return many_stats(ctx, &mpvss_ctx::rt_rec_passes, &mpvss_ctx::rt_rec_grouped_secrets, &mpvss_ctx::rt_rec_single_secrets, passes,
+                    grouped_secrets, single_secrets);
 }

@@ -49,12 +49,6 @@ int host_threads(int requested) {
   const unsigned hc = std::thread::hardware_concurrency();
   return hc == 0 ? 1 : (hc > 16 ? 16 : (int)hc);
 }
-// host threads of a many-secrets call (mpvss_modp_group_reconstruct_many, mpvss_ec_reconstruct_many): what the caller asked for, or
-// one per `per_thread` items of work; 1 .. 16, never the machine's count
-int rt_many_threads(int requested, size_t work, size_t per_thread) {
-  const size_t nth = requested > 0 ? (size_t)requested : work / per_thread;
-  return (int)std::min<size_t>(std::max<size_t>(nth, 1), 16);
-}
 
 // generic bodies over (N limbs, byte width, endianness); Mod: hsc::Modulus<N>, or hsc::ModulusRt for N = 32
 template <int N, class Mod>
@@ -834,28 +828,19 @@ extern "C" int mpvss_ec_reconstruct(mpvss_ctx* ctx, int group, int space, const 
 // a quadratic Lagrange loop on one host thread, two synchronisations and three launches of one partial workgroup each; here the
 // coefficients are computed once per distinct position list on the call's host threads, and runs of secrets travel as ONE dense
 // concatenation of shares through the launches of one secret, the fold replaced by one k_*_sum_segments launch (one wave per
-// secret).  THE grouping decision is in mpvss_ec_reconstruct_many below.
+// secret).  The plan of the position lists and the walk that forms the passes: many::plan_secrets, many::walk_secrets (host_many.h).
 // =====================================================================================================================
 namespace {
 
 // shares of one secret that may travel in a pass (the project's RT_GROUP_BOX_MAX; DESIGN section 13 has the measurement it rests on)
 constexpr size_t EC_GROUP_SECRET_MAX = 16384;
 
-enum EcSecretKind { EC_SECRET_REFUSED, EC_SECRET_GROUPED, EC_SECRET_SINGLE };
-
-// what the host knows of a secret before anything is launched: its kind, and where the scalars of its position list start in the
-// call's array (npos for a secret that computes its own)
-struct EcSecretPlan {
-  EcSecretKind kind = EC_SECRET_REFUSED;
-  size_t coef = (size_t)-1;
-};
-
-// a grouped pass: the secrets run[0 .. B) (indices into `secrets`, all EC_SECRET_GROUPED), S <= MAX_CHUNK shares in all.  The
+// a grouped pass: the secrets run[0 .. B) (indices into `secrets`, all many::SECRET_GROUPED), S <= MAX_CHUNK shares in all.  The
 // launches of one secret over the concatenation -- the S factors are never encoded -- then one sum per secret into B dense points,
 // one encode of those and one synchronisation.  A secret with a share that is no valid encoding is refused here: its sum ran with
 // the others and is dropped.
 int ec_reconstruct_pass(mpvss_ctx* ctx, const EcInfo* gi, EcWork& w, int space, const mpvss_ec_secret* secrets,
-                        const std::vector<size_t>& run, const std::vector<EcSecretPlan>& plan, const uint8_t* scalars, int host_threads,
+                        const std::vector<size_t>& run, const std::vector<many::SecretPlan>& plan, const uint8_t* scalars, int host_threads,
                         int* status, uint8_t* gs_out, uint8_t* masks_out32) {
   const int group = gi->group;
   const size_t B = run.size(), L = gi->enc;
@@ -869,10 +854,7 @@ int ec_reconstruct_pass(mpvss_ctx* ctx, const EcInfo* gi, EcWork& w, int space, 
   // host sources of asynchronous copies and the results read back: declared before the guard, whose way out drains the stream
   std::vector<uint8_t> g_sh, g_k(S * 32), h_enc(B * L), h_ok(S);
   std::vector<const uint8_t*> srcs;
-  struct Drain {            // no copy out of (or into) the vectors above outlives them, whichever way the pass ends
-    mpvss_ctx* c;
-    ~Drain() { (void)hipStreamSynchronize(c->stream); }
-  } drain{ctx};
+  StreamDrain drain{ctx};
   spans_reset(ctx);
   for (size_t k = 0; k < B; ++k) memcpy(g_k.data() + (size_t)segs[2 * k] * 32, scalars + plan[run[k]].coef * 32, secrets[run[k]].m * 32);
   RET_IF(ensure(ctx, w.a, S * L));
@@ -911,7 +893,7 @@ int ec_reconstruct_pass(mpvss_ctx* ctx, const EcInfo* gi, EcWork& w, int space, 
     refused[k] = std::find(ok, ok + segs[2 * k + 1], 0) != ok + segs[2 * k + 1];
     if (!refused[k]) ++good;
   }
-  hsc::parallel_for(B, rt_many_threads(host_threads, B, 256), [&](size_t lo, size_t hi) {
+  hsc::parallel_for(B, many::many_threads(host_threads, B, 256), [&](size_t lo, size_t hi) {
     for (size_t k = lo; k < hi; ++k) {
       if (refused[k]) continue;
       const size_t i = run[k];
@@ -940,57 +922,13 @@ extern "C" int mpvss_ec_reconstruct_many(mpvss_ctx* ctx, int group, int space, c
   memset(gs_out, 0, count * L);
   if (masks_out32) memset(masks_out32, 0, 32 * count);
 
-  // the arguments of every secret, as the one-secret call judges them; then the Lagrange scalars ONCE per distinct position list
-  // -- the sequences equal element by element: a permuted list is another list, coefficients belong to indices -- of the secrets
-  // that may travel in a pass (a secret too long for one computes its own on the one-secret path)
-  std::vector<EcSecretPlan> plan(count);
-  std::map<std::vector<int64_t>, size_t> lists;          // position list -> its index
-  std::vector<const int64_t*> list_pos;
-  std::vector<size_t> list_m, list_first, list_of(count, (size_t)-1);
-  size_t coefs = 0;
-  for (size_t i = 0; i < count; ++i) {
-    const mpvss_ec_secret& s = secrets[i];
-    if (!s.positions_host || !s.shares || s.m == 0 || s.m > 0x7fffffff) continue;
-    bool ok = true;
-    for (size_t k = 0; k < s.m && ok; ++k) ok = s.positions_host[k] >= 1;
-    if (!ok) continue;
-    if (s.m > EC_GROUP_SECRET_MAX || s.m > MAX_CHUNK) {
-      plan[i].kind = EC_SECRET_SINGLE;
-      continue;
-    }
-    plan[i].kind = EC_SECRET_GROUPED;
-    const auto it = lists.emplace(std::vector<int64_t>(s.positions_host, s.positions_host + s.m), list_pos.size());
-    if (it.second) {
-      list_pos.push_back(s.positions_host);
-      list_m.push_back(s.m);
-      list_first.push_back(coefs);
-      coefs += s.m;
-    }
-    list_of[i] = it.first->second;
-  }
-  lists.clear();
-  std::vector<uint8_t> scalars(coefs * 32);
-  std::vector<char> coef_ok(coefs, 0);
-  // a coefficient costs 2 m small products and one inversion in the 256-bit field: a thread per 64 of them when the library chooses
-  hsc::parallel_for(coefs, rt_many_threads(host_threads, coefs, 64), [&](size_t lo, size_t hi) {
-    size_t l = std::upper_bound(list_first.begin(), list_first.end(), lo) - list_first.begin() - 1;
-    for (size_t c = lo; c < hi; ++c) {
-      while (l + 1 < list_first.size() && list_first[l + 1] <= c) ++l;
-      coef_ok[c] = ec_lagrange_scalar(gi, list_pos[l], list_m[l], c - list_first[l], scalars.data() + c * 32) ? 1 : 0;
-    }
-  });
-  for (size_t i = 0; i < count; ++i) {
-    if (plan[i].kind != EC_SECRET_GROUPED) continue;
-    const size_t l = list_of[i];
-    plan[i].coef = list_first[l];
-    const auto first = coef_ok.begin() + list_first[l], last = first + list_m[l];
-    if (std::find(first, last, 0) != last) plan[i].kind = EC_SECRET_REFUSED;                  // duplicate positions
-  }
-
-  // THE grouping decision: a pass is a maximal stretch of consecutive grouped secrets (at most EC_GROUP_SECRET_MAX shares each) that
-  // hold at most MAX_CHUNK shares together, cut only at secret boundaries.  Refused secrets are settled above and do not end a pass;
-  // a pass of one secret takes the one-secret path, like every secret too long for a pass.  A code of the one-secret path other
-  // than MPVSS_E_INVALID (which refuses that secret alone) ends the call.
+  // the Lagrange scalars ONCE per distinct position list (a list without them has duplicate positions: its secrets are refused)
+  std::vector<uint8_t> scalars;
+  const std::vector<many::SecretPlan> plan =
+      many::plan_secrets(secrets, count, EC_GROUP_SECRET_MAX, MAX_CHUNK, host_threads, [&](size_t coefs) { scalars.resize(coefs * 32); },
+                         [&](const int64_t* pos, size_t m, size_t j, size_t c) { return ec_lagrange_scalar(gi, pos, m, j, scalars.data() + c * 32); })
+          .secret;
+  // A code of the one-secret path other than MPVSS_E_INVALID (which refuses that secret alone) ends the call.
   auto single = [&](size_t i) -> int {
     const mpvss_ec_secret& s = secrets[i];
     spans_reset(ctx);
@@ -1007,36 +945,13 @@ extern "C" int mpvss_ec_reconstruct_many(mpvss_ctx* ctx, int group, int space, c
     ++ctx->ec_rec_single_secrets;
     return MPVSS_OK;
   };
-  std::vector<size_t> run;
-  size_t run_shares = 0;
-  auto flush = [&]() -> int {
-    int rc = MPVSS_OK;
-    if (run.size() == 1) rc = single(run[0]);
-    else if (run.size() > 1) rc = ec_reconstruct_pass(ctx, gi, w, space, secrets, run, plan, scalars.data(), host_threads, status, gs_out, masks_out32);
-    run.clear();
-    run_shares = 0;
-    return rc;
-  };
-  for (size_t i = 0; i < count; ++i) {
-    if (plan[i].kind == EC_SECRET_REFUSED) continue;
-    if (plan[i].kind == EC_SECRET_SINGLE) {
-      RET_IF(flush());
-      RET_IF(single(i));
-      continue;
-    }
-    if (!run.empty() && run_shares + secrets[i].m > MAX_CHUNK) RET_IF(flush());
-    run.push_back(i);
-    run_shares += secrets[i].m;
-  }
-  return flush();
+  return many::walk_secrets(secrets, plan, MAX_CHUNK, single, [&](const std::vector<size_t>& run) {
+    return ec_reconstruct_pass(ctx, gi, w, space, secrets, run, plan, scalars.data(), host_threads, status, gs_out, masks_out32);
+  });
 }
 
 extern "C" int mpvss_ec_reconstruct_many_stats(mpvss_ctx* ctx, unsigned long long* passes, unsigned long long* grouped_secrets,
                                                unsigned long long* single_secrets) {
-  if (!ctx) return MPVSS_E_INVALID;
-  std::lock_guard<std::mutex> lk(ctx->mu);
-  if (passes) *passes = ctx->ec_rec_passes;
-  if (grouped_secrets) *grouped_secrets = ctx->ec_rec_grouped_secrets;
-  if (single_secrets) *single_secrets = ctx->ec_rec_single_secrets;
-  return MPVSS_OK;
+  return many_stats(ctx, &mpvss_ctx::ec_rec_passes, &mpvss_ctx::ec_rec_grouped_secrets, &mpvss_ctx::ec_rec_single_secrets, passes,
+                    grouped_secrets, single_secrets);
 }

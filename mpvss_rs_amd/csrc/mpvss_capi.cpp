@@ -21,6 +21,7 @@
 #include <thread>
 #include <vector>
 
+#include "host_many.h"
 #include "host_modq.h"
 #include "host_scalar.h"
 #include "modp_kernels.h"
@@ -434,6 +435,25 @@ int fail(mpvss_ctx* ctx, int code, const char* what, hipError_t e = hipSuccess) 
     int rc_ = (x);            \
     if (rc_ != 0) return rc_; \
   } while (0)
+
+// the way out of a dense pass of a *_many call: no copy out of (or into) the host buffers declared before it is pending when the
+// pass ends, whichever way it ends
+struct StreamDrain {
+  mpvss_ctx* c;
+  ~StreamDrain() { (void)hipStreamSynchronize(c->stream); }
+};
+
+// the body of the four *_many_stats getters: three counters of the context, copied out under its lock
+typedef unsigned long long mpvss_ctx::*ManyCounter;
+int many_stats(mpvss_ctx* ctx, ManyCounter a, ManyCounter b, ManyCounter c, unsigned long long* a_out, unsigned long long* b_out,
+               unsigned long long* c_out) {
+  if (!ctx) return MPVSS_E_INVALID;
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  if (a_out) *a_out = ctx->*a;
+  if (b_out) *b_out = ctx->*b;
+  if (c_out) *c_out = ctx->*c;
+  return MPVSS_OK;
+}
 
 int ensure(mpvss_ctx* ctx, DevBuf& b, size_t bytes) {
   if (bytes <= b.cap) return 0;
