@@ -550,6 +550,26 @@ int mpvss_ec_reconstruct_many(mpvss_ctx* ctx, int group, int space, const mpvss_
 int mpvss_ec_reconstruct_many_stats(mpvss_ctx* ctx, unsigned long long* passes, unsigned long long* grouped_secrets,
                                     unsigned long long* single_secrets);
 
+/* Where mpvss_ec_reconstruct and mpvss_ec_reconstruct_many compute the Lagrange coefficients lambda_i = prod_{j != i} x_j / (x_j - x_i)
+ * mod the group order (participant.rs:1518-1557, 1955-2002): mode 0 on the host as before, 2 on the device (k_ec_lagrange: one
+ * coefficient per lane, one launch for all distinct position lists of a call, the scalars never cross the bus) whenever the lists
+ * allow it -- no list of more than 2^20 positions, fewer than 2^31 positions in all -- and 1, the default, on the device when the work
+ * of the call (the sum of m^2 over its distinct lists; m^2 of a lone secret) reaches a measured size ("Lagrange
+ * coefficients on the device, curve groups"; profiles/ec_lagrange_device.txt).  A coefficient is one element of a prime field, so
+ * the results of all four reconstruct entry points are the same bytes under every mode.  Returns the mode before; no context, or
+ * another value, is MPVSS_E_INVALID. */
+int mpvss_ctx_set_ec_lagrange(mpvss_ctx* ctx, int mode);
+/* The kernel on its own: scalars_out_host[32 i .. 32 i + 31] = the scalar share i of a secret at these positions is multiplied by,
+ * lambda_i mod the order ("order - |lambda_i|" for a negative coefficient) in the group's scalar byte order (secp256k1 big-endian,
+ * ristretto255 little-endian), computed where the context's mode says.  Refusals are those of mpvss_ec_reconstruct: a NULL pointer,
+ * m == 0, m above 0x7fffffff, a position below 1, duplicate positions are MPVSS_E_INVALID and leave the output untouched; an unknown
+ * group is MPVSS_E_UNSUPPORTED.  Synchronous, under the context lock. */
+int mpvss_ec_lagrange_scalars(mpvss_ctx* ctx, int group, const int64_t* positions_host, size_t m, uint8_t* scalars_out_host);
+/* Position lists whose coefficients were computed on the device / on the host since the context was created, by any of the three
+ * calls above (a list shared by several secrets of one call counts once; refused lists are in neither count; both curves count
+ * together).  Either pointer may be NULL; no context is MPVSS_E_INVALID. */
+int mpvss_ec_lagrange_stats(mpvss_ctx* ctx, unsigned long long* device_lists, unsigned long long* host_lists);
+
 /* ---- flat wire format of a DistributionSharesBox ("MPVSSBX1") ---------------------------------------------------------
  * The reference keeps a box as three HashMap<Vec<u8>, _> (src/sharebox.rs:74-86) and defines no serialisation.  This
  * format is the boundary's own layout -- rows in `publickeys` order (the order src/participant.rs:408-448 iterates in),
@@ -876,7 +896,7 @@ void mpvss_modp_hash_to_scalar(const uint8_t* data, size_t len, uint8_t out256[2
  * measured with hipEvents on the stream each kernel was launched on, summed per kind:
  *   0 = the X path (k_modp_commit_eval and, for consecutive positions, the forward-difference kernels),
  *   1 = k_modp_comb_dual_exp (a1), 2 = table builds, 3 = k_modp_dual_exp (a2, batch_exp),
- *   4 = the scalar-ring kernels of a run-time group (k_rt_modq_*).
+ *   4 = the scalar-ring kernels of a run-time group (k_rt_modq_*), and k_ec_lagrange of the curve groups.
  * Kernels of different kinds may overlap in time (two streams), so the sums can exceed the wall time.
  * mpvss_last_kernel_launches gives the number of launches behind each sum.  Negative when unavailable. */
 double mpvss_last_kernel_ms(const mpvss_ctx* ctx, int kernel_id);

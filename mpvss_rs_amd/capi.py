@@ -67,6 +67,7 @@ EXPORTED_SYMBOLS = (
     "mpvss_modp_group_verify_many", "mpvss_modp_group_verify_many_stats",
     "mpvss_modp_group_reconstruct_many", "mpvss_modp_group_reconstruct_many_stats",
     "mpvss_ec_reconstruct_many", "mpvss_ec_reconstruct_many_stats",
+    "mpvss_ctx_set_ec_lagrange", "mpvss_ec_lagrange_scalars", "mpvss_ec_lagrange_stats",
     "mpvss_ctx_set_ec_box_groups", "mpvss_ec_verify_many_stats",
 )
 
@@ -232,6 +233,10 @@ def load_library() -> C.CDLL:
     lib.mpvss_ec_reconstruct_many.argtypes = [vp, ci, ci, C.POINTER(EcSecret), sz, ci, C.POINTER(ci), u8p, u8p]
     lib.mpvss_ec_reconstruct_many_stats.argtypes = [vp, C.POINTER(C.c_ulonglong), C.POINTER(C.c_ulonglong),
                                                     C.POINTER(C.c_ulonglong)]
+    if hasattr(lib, "mpvss_ec_lagrange_scalars"):       # (an A/B library of an older commit, MPVSS_HIP_LIB, does without the three)
+        lib.mpvss_ctx_set_ec_lagrange.argtypes = [vp, ci]
+        lib.mpvss_ec_lagrange_scalars.argtypes = [vp, ci, vp, sz, vp]
+        lib.mpvss_ec_lagrange_stats.argtypes = [vp, C.POINTER(C.c_ulonglong), C.POINTER(C.c_ulonglong)]
     lib.mpvss_ec_verify_block_compute.argtypes = [vp, ci, ci, u8p, sz, i64p, u8p, u8p, u8p, sz, u8p]
     lib.mpvss_ec_verify_block_absorb.argtypes = [vp, u8p, u8p, u8p, u8p]
     lib.mpvss_ec_transcript_absorb.argtypes = [ci, u8p, u8p, sz]
@@ -1257,6 +1262,30 @@ class Engine:
         """since the context was created: grouped passes, secrets that went through them, secrets that took the one-secret path"""
         return self._three_counters(self.lib.mpvss_ec_reconstruct_many_stats, "ec_reconstruct_many_stats",
                                     ("passes", "grouped_secrets", "single_secrets"))
+
+    # ---- where the Lagrange coefficients of reconstruct are computed, and the kernel on its own ---------------------------------
+    def set_ec_lagrange(self, mode: int) -> int:
+        """mpvss_ctx_set_ec_lagrange: where ec_reconstruct / ec_reconstruct_many compute their Lagrange coefficients -- 0 on the
+        host, 1 automatic, 2 on the device whenever the lists allow it.  Returns the mode before."""
+        before = self.lib.mpvss_ctx_set_ec_lagrange(self.ctx, int(mode))
+        if before < 0:
+            self._check(before, "set_ec_lagrange")
+        return before
+
+    def ec_lagrange_scalars(self, group: int, positions: Sequence[int]) -> bytes:
+        """the len(positions) scalars a share is multiplied by in ec_reconstruct, 32 bytes each in the group's scalar byte order,
+        computed where the context's mode says (set_ec_lagrange)"""
+        m = len(positions)
+        pos = (C.c_int64 * max(m, 1))(*positions)
+        ko, po = _out(32 * m)
+        self._check(self.lib.mpvss_ec_lagrange_scalars(self.ctx, group, C.cast(pos, C.c_void_p), m, po), "ec_lagrange_scalars")
+        return bytes(ko)[: 32 * m]
+
+    def ec_lagrange_stats(self) -> dict:
+        """position lists whose coefficients were computed on the device / on the host since the context was created"""
+        d, h = C.c_ulonglong(0), C.c_ulonglong(0)
+        self._check(self.lib.mpvss_ec_lagrange_stats(self.ctx, C.byref(d), C.byref(h)), "ec_lagrange_stats")
+        return {"device": int(d.value), "host": int(h.value)}
 
     def ec_batch_exp_generator(self, group: int, scalars: bytes) -> bytes:
         n = len(scalars) // 32

@@ -772,10 +772,54 @@ void ec_secret_mask(const EcInfo* gi, const uint8_t* gs, uint8_t* mask_out32) {
   hsc::to_bytes<4>(mask_out32, x, true);
 }
 
-// one secret under the context lock (mpvss_ec_reconstruct, and the one-secret path of mpvss_ec_reconstruct_many).  scalars_pre: the
-// m scalars of ec_lagrange_scalar when the caller has them already (computed with the call's other position lists), else null.
+// ---- the same scalars on the device (DESIGN section 13, "Lagrange coefficients on the device, curve groups") --------------------
+// One list longer than this keeps the host path: its one launch would run for seconds on a shared machine.  Nobody has measured
+// that size; the value is a guess at "seconds", not a crossover.
+constexpr size_t EC_LAGRANGE_DEVICE_MAX_M = (size_t)1 << 20;
+// Mode 1 of mpvss_ctx_set_ec_lagrange takes the device for a call whose work -- the sum of m^2 over its distinct position lists, m^2
+// of a lone secret -- is at least this.  Set from tools/ec_reconstruct_many.py --lagrange against a build of the parent commit
+// (profiles/ec_lagrange_device.txt): the smallest measured work from which the device is not slower than the parent beyond the
+// spread of the parent's three runs, on both curves and in both spaces.  That is 200 secrets of 34 shares with a list each,
+// 200 x 34^2 (2.0 against 2.9 ms); every measured shape above it is faster on the device (60 x 1024 over one list 3.3 against
+// 5.1 ms, with a list each 3.5 against 170 ms), the three below it -- 9, 1 156 and 3 600 -- are 0.5 to 0.7 ms slower: the
+// launch costs the latency of one Fermat inversion whatever its size.  Nothing between 3 600 and 231 200 is measured: automatic
+// stays on the host there.
+constexpr double EC_LAGRANGE_DEVICE_MIN_WORK = 200.0 * 34 * 34;
+
+bool ec_lagrange_on_device(const mpvss_ctx* ctx, double work, size_t longest, size_t coefs) {
+  // (tile rows hold positions' and coefficients' indices in 32 bits)
+  if (ctx->ec_lagrange_mode == 0 || longest > EC_LAGRANGE_DEVICE_MAX_M || coefs > 0x7fffffffu) return false;
+  return ctx->ec_lagrange_mode == 2 || work >= EC_LAGRANGE_DEVICE_MIN_WORK;
+}
+// duplicates by sorting a copy, O(m log m): what the quadratic host loop finds on its way
+bool ec_positions_distinct(const int64_t* pos, size_t m) {
+  std::vector<int64_t> s(pos, pos + m);
+  std::sort(s.begin(), s.end());
+  return std::adjacent_find(s.begin(), s.end()) == s.end();
+}
+// `total` positions (the launch's lists back to back) and the tile rows up, then ONE k_ec_lagrange launch into out_dev (32 bytes
+// per position).  The copies are asynchronous: positions and tiles stay alive until the caller has drained the stream.
+int ec_lagrange_dev(mpvss_ctx* ctx, const EcInfo* gi, DevBuf& pos_buf, DevBuf& tile_buf, const int64_t* positions, size_t total,
+                    const std::vector<uint32_t>& tiles, uint8_t* out_dev) {
+  RET_IF(ensure(ctx, pos_buf, total * 8));
+  RET_IF(ensure(ctx, tile_buf, tiles.size() * 4));
+  HIPCHK(ctx, hipMemcpyAsync(pos_buf.p, positions, total * 8, hipMemcpyHostToDevice, ctx->stream));
+  HIPCHK(ctx, hipMemcpyAsync(tile_buf.p, tiles.data(), tiles.size() * 4, hipMemcpyHostToDevice, ctx->stream));
+  TIMED_LAUNCH(ctx, 4, ec_lagrange_launch(gi->group, (const int64_t*)pos_buf.p, (const uint32_t*)tile_buf.p, (int)(tiles.size() / 4),
+                                          out_dev, ctx->stream));
+  return MPVSS_OK;
+}
+struct StreamDrainIf {          // StreamDrain for a path that is only sometimes asynchronous
+  mpvss_ctx* c;
+  bool on = false;
+  ~StreamDrainIf() { if (on) (void)hipStreamSynchronize(c->stream); }
+};
+
+// one secret under the context lock (mpvss_ec_reconstruct, and the one-secret path of mpvss_ec_reconstruct_many).  The m scalars of
+// ec_lagrange_scalar when the caller has them already (computed with the call's other position lists): scalars_pre in host memory
+// or scalars_dev in device memory; else both null, and they are computed here, on the host or on the device.
 int ec_reconstruct_locked(mpvss_ctx* ctx, const EcInfo* gi, EcWork& w, int space, const int64_t* positions_host, const uint8_t* shares,
-                          size_t m, uint8_t* gs_out, uint8_t* mask_out32, const uint8_t* scalars_pre) {
+                          size_t m, uint8_t* gs_out, uint8_t* mask_out32, const uint8_t* scalars_pre, const uint8_t* scalars_dev = nullptr) {
   const int group = gi->group;
   if (!positions_host || !shares || m == 0 || !gs_out || m > 0x7fffffff) return fail(ctx, MPVSS_E_INVALID, "ec_reconstruct: bad argument");
   // a box's positions are 1..n (participant.rs:1127, 1600); the coefficient of a position <= 0 would multiply `j as u64` into
@@ -784,24 +828,41 @@ int ec_reconstruct_locked(mpvss_ctx* ctx, const EcInfo* gi, EcWork& w, int space
     if (positions_host[i] < 1) return fail(ctx, MPVSS_E_INVALID, "ec_reconstruct: positions must be >= 1");
   // lambda * S, negated for a negative coefficient (participant.rs:1546-1555)
   std::vector<uint8_t> ks;
-  if (!scalars_pre) {
-    ks.resize(m * 32);
-    for (size_t i = 0; i < m; ++i)
-      if (!ec_lagrange_scalar(gi, positions_host, m, i, ks.data() + i * 32)) return fail(ctx, MPVSS_E_INVALID, "ec_reconstruct: duplicate positions");
-    scalars_pre = ks.data();
+  std::vector<uint32_t> tiles;
+  StreamDrainIf drain{ctx, scalars_dev != nullptr};          // (after the host sources of the device path's copies)
+  const uint8_t* dK = scalars_dev;
+  if (!scalars_pre && !scalars_dev) {
+    if (ec_lagrange_on_device(ctx, (double)m * (double)m, m, m)) {
+      if (!ec_positions_distinct(positions_host, m)) return fail(ctx, MPVSS_E_INVALID, "ec_reconstruct: duplicate positions");
+      ec::lagrange_tiles(0, m, tiles);
+      RET_IF(ensure(ctx, w.d, m * 32));
+      drain.on = true;
+      RET_IF(ec_lagrange_dev(ctx, gi, w.lag_pos, w.lag_tiles, positions_host, m, tiles, (uint8_t*)w.d.p));   // straight into ec_dual's scalars
+      dK = (const uint8_t*)w.d.p;
+      ++ctx->ec_lagrange_dev_lists;
+    } else {
+      ks.resize(m * 32);
+      for (size_t i = 0; i < m; ++i)
+        if (!ec_lagrange_scalar(gi, positions_host, m, i, ks.data() + i * 32)) return fail(ctx, MPVSS_E_INVALID, "ec_reconstruct: duplicate positions");
+      scalars_pre = ks.data();
+      ++ctx->ec_lagrange_host_lists;
+    }
   }
   const void* dS;
   RET_IF(stage_in(ctx, space, shares, m * gi->enc, w.a, &dS));
-  RET_IF(ensure(ctx, w.d, m * 32));
-  HIPCHK(ctx, hipMemcpyAsync(w.d.p, scalars_pre, m * 32, hipMemcpyHostToDevice, ctx->stream));
-  HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+  if (!dK) {
+    RET_IF(ensure(ctx, w.d, m * 32));
+    HIPCHK(ctx, hipMemcpyAsync(w.d.p, scalars_pre, m * 32, hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    dK = (const uint8_t*)w.d.p;
+  }
   RET_IF(ensure(ctx, w.ok, m > 4096 ? m : 4096));
   RET_IF(ensure(ctx, w.o1, (m + 1) * gi->enc));
   EcBase b1;
   b1.enc = (const uint8_t*)dS;
   b1.enc_stride = gi->enc;
   uint8_t* dF = (uint8_t*)w.o1.p;
-  RET_IF(ec_dual(ctx, gi, b1, (const uint8_t*)w.d.p, 32, nullptr, nullptr, 0, m, w.tab1, w.tab2, w.p1, dF, (uint8_t*)w.ok.p, nullptr));
+  RET_IF(ec_dual(ctx, gi, b1, dK, 32, nullptr, nullptr, 0, m, w.tab1, w.tab2, w.p1, dF, (uint8_t*)w.ok.p, nullptr));
   // sum of the m factors (fold with Group::mul, participant.rs:1489-1492): one workgroup over the internal points
   LAUNCHCHK(ctx, ec_launch_sum(group, (const uint32_t*)w.p1.p, (int)m, (uint32_t*)w.p1.p, ctx->stream));
   LAUNCHCHK(ctx, ec_launch_encode(group, (const uint32_t*)w.p1.p, 1, dF, ctx->stream));
@@ -840,8 +901,8 @@ constexpr size_t EC_GROUP_SECRET_MAX = 16384;
 // one encode of those and one synchronisation.  A secret with a share that is no valid encoding is refused here: its sum ran with
 // the others and is dropped.
 int ec_reconstruct_pass(mpvss_ctx* ctx, const EcInfo* gi, EcWork& w, int space, const mpvss_ec_secret* secrets,
-                        const std::vector<size_t>& run, const std::vector<many::SecretPlan>& plan, const uint8_t* scalars, int host_threads,
-                        int* status, uint8_t* gs_out, uint8_t* masks_out32) {
+                        const std::vector<size_t>& run, const std::vector<many::SecretPlan>& plan, const uint8_t* scalars,
+                        const uint8_t* scalars_dev, int host_threads, int* status, uint8_t* gs_out, uint8_t* masks_out32) {
   const int group = gi->group;
   const size_t B = run.size(), L = gi->enc;
   std::vector<uint32_t> segs(2 * B);                                // {first factor, m} of every secret
@@ -852,11 +913,12 @@ int ec_reconstruct_pass(mpvss_ctx* ctx, const EcInfo* gi, EcWork& w, int space, 
     S += secrets[run[k]].m;
   }
   // host sources of asynchronous copies and the results read back: declared before the guard, whose way out drains the stream
-  std::vector<uint8_t> g_sh, g_k(S * 32), h_enc(B * L), h_ok(S);
-  std::vector<const uint8_t*> srcs;
+  std::vector<uint8_t> g_sh, g_k(scalars_dev ? 0 : S * 32), h_enc(B * L), h_ok(S);
+  std::vector<const uint8_t*> srcs, ksrcs;
   StreamDrain drain{ctx};
   spans_reset(ctx);
-  for (size_t k = 0; k < B; ++k) memcpy(g_k.data() + (size_t)segs[2 * k] * 32, scalars + plan[run[k]].coef * 32, secrets[run[k]].m * 32);
+  if (!scalars_dev)
+    for (size_t k = 0; k < B; ++k) memcpy(g_k.data() + (size_t)segs[2 * k] * 32, scalars + plan[run[k]].coef * 32, secrets[run[k]].m * 32);
   RET_IF(ensure(ctx, w.a, S * L));
   RET_IF(ensure(ctx, w.b, segs.size() * 4));
   RET_IF(ensure(ctx, w.d, S * 32));
@@ -876,7 +938,15 @@ int ec_reconstruct_pass(mpvss_ctx* ctx, const EcInfo* gi, EcWork& w, int space, 
     LAUNCHCHK(ctx, ec_launch_gather_segments((const uint8_t* const*)w.c.p, (const uint32_t*)w.b.p, (int)B, (uint32_t)L, (uint8_t*)w.a.p,
                                              ctx->stream));
   }
-  HIPCHK(ctx, hipMemcpyAsync(w.d.p, g_k.data(), S * 32, hipMemcpyHostToDevice, ctx->stream));
+  if (scalars_dev) {        // the coefficients never left the device: the same gather, from the call's coefficient buffer
+    ksrcs.resize(B);
+    for (size_t k = 0; k < B; ++k) ksrcs[k] = scalars_dev + plan[run[k]].coef * 32;
+    RET_IF(ensure(ctx, w.lag_src, B * sizeof(const uint8_t*)));
+    HIPCHK(ctx, hipMemcpyAsync(w.lag_src.p, ksrcs.data(), B * sizeof(const uint8_t*), hipMemcpyHostToDevice, ctx->stream));
+    LAUNCHCHK(ctx, ec_launch_gather_segments((const uint8_t* const*)w.lag_src.p, (const uint32_t*)w.b.p, (int)B, 32, (uint8_t*)w.d.p, ctx->stream));
+  } else {
+    HIPCHK(ctx, hipMemcpyAsync(w.d.p, g_k.data(), S * 32, hipMemcpyHostToDevice, ctx->stream));
+  }
   EcBase b1;
   b1.enc = (const uint8_t*)w.a.p;
   b1.enc_stride = L;
@@ -922,19 +992,63 @@ extern "C" int mpvss_ec_reconstruct_many(mpvss_ctx* ctx, int group, int space, c
   memset(gs_out, 0, count * L);
   if (masks_out32) memset(masks_out32, 0, 32 * count);
 
-  // the Lagrange scalars ONCE per distinct position list (a list without them has duplicate positions: its secrets are refused)
+  // the Lagrange scalars ONCE per distinct position list (a list without them has duplicate positions: its secrets are refused):
+  // on the host threads of the call, or by ONE k_ec_lagrange launch over all lists into a buffer the passes gather from
+  many::SecretPlans lists = many::plan_lists(secrets, count, EC_GROUP_SECRET_MAX, MAX_CHUNK);
+  double work = 0;
+  for (const size_t lm : lists.list_m) work += (double)lm * (double)lm;
+  const bool on_device = !lists.list_m.empty() &&
+                         ec_lagrange_on_device(ctx, work, *std::max_element(lists.list_m.begin(), lists.list_m.end()), lists.coefs);
   std::vector<uint8_t> scalars;
-  const std::vector<many::SecretPlan> plan =
-      many::plan_secrets(secrets, count, EC_GROUP_SECRET_MAX, MAX_CHUNK, host_threads, [&](size_t coefs) { scalars.resize(coefs * 32); },
-                         [&](const int64_t* pos, size_t m, size_t j, size_t c) { return ec_lagrange_scalar(gi, pos, m, j, scalars.data() + c * 32); })
-          .secret;
+  std::vector<int64_t> all_pos;                               // host sources of the launch's copies: before the guard
+  std::vector<uint32_t> tiles;
+  StreamDrainIf drain{ctx, on_device};
+  const uint8_t* scalars_dev = nullptr;
+  ctx->call_spans.spans.clear();
+  ctx->call_spans.ev_used = 0;
+  if (on_device) {
+    std::vector<char> list_ok(lists.list_m.size(), 0);
+    hsc::parallel_for(list_ok.size(), many::many_threads(host_threads, lists.coefs, 4096), [&](size_t lo, size_t hi) {
+      for (size_t l = lo; l < hi; ++l) list_ok[l] = ec_positions_distinct(lists.list_pos[l], lists.list_m[l]) ? 1 : 0;
+    });
+    many::plan_settle(lists, list_ok);
+    all_pos.resize(lists.coefs);
+    size_t good = 0;
+    for (size_t l = 0; l < list_ok.size(); ++l) {             // coefficient c belongs to position c; a refused list has no tile
+      memcpy(all_pos.data() + lists.list_first[l], lists.list_pos[l], lists.list_m[l] * 8);
+      if (!list_ok[l]) continue;
+      ec::lagrange_tiles(lists.list_first[l], lists.list_m[l], tiles);
+      ++good;
+    }
+    if (good) {
+      RET_IF(ensure(ctx, w.lag_coef, lists.coefs * 32));
+      ctx->sp = &ctx->call_spans;
+      const int rc = ec_lagrange_dev(ctx, gi, w.lag_call_pos, w.lag_call_tiles, all_pos.data(), lists.coefs, tiles, (uint8_t*)w.lag_coef.p);
+      ctx->sp = &ctx->main_spans;
+      RET_IF(rc);
+      ctx->ec_lagrange_dev_lists += good;
+    }
+    scalars_dev = (const uint8_t*)w.lag_coef.p;
+  } else {
+    many::plan_host_coefficients(lists, host_threads, [&](size_t coefs) { scalars.resize(coefs * 32); },
+                                 [&](const int64_t* pos, size_t m, size_t j, size_t c) { return ec_lagrange_scalar(gi, pos, m, j, scalars.data() + c * 32); });
+    std::vector<char> counted(lists.list_m.size(), 0);
+    for (size_t i = 0; i < count; ++i)
+      if (lists.secret[i].kind == many::SECRET_GROUPED && !counted[lists.list_of[i]]) {
+        counted[lists.list_of[i]] = 1;
+        ++ctx->ec_lagrange_host_lists;
+      }
+  }
+  const std::vector<many::SecretPlan>& plan = lists.secret;
   // A code of the one-secret path other than MPVSS_E_INVALID (which refuses that secret alone) ends the call.
   auto single = [&](size_t i) -> int {
     const mpvss_ec_secret& s = secrets[i];
     spans_reset(ctx);
+    const bool pre = plan[i].coef != (size_t)-1;             // a run of one: its list's scalars are there already
     const int rc = ec_reconstruct_locked(ctx, gi, w, space, s.positions_host, s.shares, s.m, gs_out + i * L,
                                          masks_out32 ? masks_out32 + 32 * i : nullptr,
-                                         plan[i].coef != (size_t)-1 ? scalars.data() + plan[i].coef * 32 : nullptr);
+                                         pre && !scalars_dev ? scalars.data() + plan[i].coef * 32 : nullptr,
+                                         pre && scalars_dev ? scalars_dev + plan[i].coef * 32 : nullptr);
     if (rc == MPVSS_E_INVALID) {                            // (nothing of a refused secret stays in its outputs)
       memset(gs_out + i * L, 0, L);
       if (masks_out32) memset(masks_out32 + 32 * i, 0, 32);
@@ -945,13 +1059,65 @@ extern "C" int mpvss_ec_reconstruct_many(mpvss_ctx* ctx, int group, int space, c
     ++ctx->ec_rec_single_secrets;
     return MPVSS_OK;
   };
-  return many::walk_secrets(secrets, plan, MAX_CHUNK, single, [&](const std::vector<size_t>& run) {
-    return ec_reconstruct_pass(ctx, gi, w, space, secrets, run, plan, scalars.data(), host_threads, status, gs_out, masks_out32);
-  });
+  RET_IF(many::walk_secrets(secrets, plan, MAX_CHUNK, single, [&](const std::vector<size_t>& run) {
+    return ec_reconstruct_pass(ctx, gi, w, space, secrets, run, plan, scalars.data(), scalars_dev, host_threads, status, gs_out, masks_out32);
+  }));
+  if (!ctx->call_spans.spans.empty()) {                       // the coefficient launch among the kernel times of the call's last pass
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    float ms = 0;
+    HIPCHK(ctx, hipEventElapsedTime(&ms, ctx->call_spans.spans[0].a, ctx->call_spans.spans[0].b));
+    ctx->kernel_ms[4] = ms;
+    ctx->kernel_launches[4] = 1;
+  }
+  return MPVSS_OK;
 }
 
 extern "C" int mpvss_ec_reconstruct_many_stats(mpvss_ctx* ctx, unsigned long long* passes, unsigned long long* grouped_secrets,
                                                unsigned long long* single_secrets) {
   return many_stats(ctx, &mpvss_ctx::ec_rec_passes, &mpvss_ctx::ec_rec_grouped_secrets, &mpvss_ctx::ec_rec_single_secrets, passes,
                     grouped_secrets, single_secrets);
+}
+
+// ---- where the Lagrange coefficients of the curve groups are computed, and the kernel on its own ---------------------------------
+extern "C" int mpvss_ctx_set_ec_lagrange(mpvss_ctx* ctx, int mode) {
+  if (!ctx) return MPVSS_E_INVALID;
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  if (mode < 0 || mode > 2) return fail(ctx, MPVSS_E_INVALID, "set_ec_lagrange: mode is 0, 1 or 2");
+  const int before = ctx->ec_lagrange_mode;
+  ctx->ec_lagrange_mode = mode;
+  return before;
+}
+
+extern "C" int mpvss_ec_lagrange_stats(mpvss_ctx* ctx, unsigned long long* device_lists, unsigned long long* host_lists) {
+  if (!ctx) return MPVSS_E_INVALID;
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  if (device_lists) *device_lists = ctx->ec_lagrange_dev_lists;
+  if (host_lists) *host_lists = ctx->ec_lagrange_host_lists;
+  return MPVSS_OK;
+}
+
+extern "C" int mpvss_ec_lagrange_scalars(mpvss_ctx* ctx, int group, const int64_t* positions_host, size_t m, uint8_t* scalars_out_host) {
+  EC_PROLOGUE("ec_lagrange_scalars");
+  if (!positions_host || !scalars_out_host || m == 0 || m > 0x7fffffff) return fail(ctx, MPVSS_E_INVALID, "ec_lagrange_scalars: bad argument");
+  for (size_t i = 0; i < m; ++i)
+    if (positions_host[i] < 1) return fail(ctx, MPVSS_E_INVALID, "ec_lagrange_scalars: positions must be >= 1");
+  std::vector<uint8_t> ks(m * 32);                           // the output stays untouched by a refused call
+  std::vector<uint32_t> tiles;
+  StreamDrainIf drain{ctx};
+  if (ec_lagrange_on_device(ctx, (double)m * (double)m, m, m)) {
+    if (!ec_positions_distinct(positions_host, m)) return fail(ctx, MPVSS_E_INVALID, "ec_lagrange_scalars: duplicate positions");
+    ec::lagrange_tiles(0, m, tiles);
+    RET_IF(ensure(ctx, w.d, m * 32));
+    drain.on = true;
+    RET_IF(ec_lagrange_dev(ctx, gi, w.lag_pos, w.lag_tiles, positions_host, m, tiles, (uint8_t*)w.d.p));
+    HIPCHK(ctx, hipMemcpyAsync(ks.data(), w.d.p, m * 32, hipMemcpyDeviceToHost, ctx->stream));
+    RET_IF(spans_collect(ctx));
+    ++ctx->ec_lagrange_dev_lists;
+  } else {
+    for (size_t i = 0; i < m; ++i)
+      if (!ec_lagrange_scalar(gi, positions_host, m, i, ks.data() + i * 32)) return fail(ctx, MPVSS_E_INVALID, "ec_lagrange_scalars: duplicate positions");
+    ++ctx->ec_lagrange_host_lists;
+  }
+  memcpy(scalars_out_host, ks.data(), m * 32);
+  return MPVSS_OK;
 }

@@ -82,25 +82,20 @@ struct SecretPlans {
   std::vector<size_t> list_of;           // per secret: the index of its position list (npos unless it was judged GROUPED)
   std::vector<size_t> list_first;        // per distinct list: its first coefficient; lists lie back to back
   std::vector<size_t> list_m;            // per distinct list: its length
+  std::vector<const int64_t*> list_pos;  // per distinct list: its positions (the caller's memory, of the first secret that has it)
   size_t coefs = 0;                      // coefficients in all
 };
 
-// The arguments of every secret (Secret: positions_host, shares, m), as the one-secret call judges them; then the Lagrange
-// coefficients ONCE per distinct position list -- the sequences equal element by element: a permuted list is another list,
-// coefficients belong to indices -- of the secrets that may travel in a pass.  A secret of more than cap_each or cap_run shares
-// is SINGLE: too long for a pass, it computes its own coefficients on the one-secret path.
-//   sized(coefs): called once, before any coefficient, so that the caller can size its arrays
-//   coefficient(positions, m, j, c) -> bool: coefficient j of a list into the caller's slot c; false: the list has none (duplicate
-//     positions, a denominator without inverse), and every secret of that list is refused.  Called on
-//     many_threads(host_threads, coefs, 64) threads, every (list, j) exactly once.
-template <class Secret, class Sized, class Coefficient>
-SecretPlans plan_secrets(const Secret* secrets, size_t count, size_t cap_each, size_t cap_run, int host_threads, Sized sized,
-                         Coefficient coefficient) {
+// The arguments of every secret (Secret: positions_host, shares, m), as the one-secret call judges them, and the distinct position
+// lists -- the sequences equal element by element: a permuted list is another list, coefficients belong to indices -- of the
+// secrets that may travel in a pass.  A secret of more than cap_each or cap_run shares is SINGLE: too long for a pass, it computes
+// its own coefficients on the one-secret path.  Every GROUPED secret still awaits the verdict on its list: plan_settle.
+template <class Secret>
+SecretPlans plan_lists(const Secret* secrets, size_t count, size_t cap_each, size_t cap_run) {
   SecretPlans p;
   p.secret.resize(count);
   p.list_of.assign(count, (size_t)-1);
   std::map<std::vector<int64_t>, size_t> lists;          // position list -> its index
-  std::vector<const int64_t*> list_pos;
   for (size_t i = 0; i < count; ++i) {
     const Secret& s = secrets[i];
     if (!s.positions_host || !s.shares || s.m == 0 || s.m > 0x7fffffff) continue;
@@ -112,16 +107,36 @@ SecretPlans plan_secrets(const Secret* secrets, size_t count, size_t cap_each, s
       continue;
     }
     p.secret[i].kind = SECRET_GROUPED;
-    const auto it = lists.emplace(std::vector<int64_t>(s.positions_host, s.positions_host + s.m), list_pos.size());
+    const auto it = lists.emplace(std::vector<int64_t>(s.positions_host, s.positions_host + s.m), p.list_pos.size());
     if (it.second) {
-      list_pos.push_back(s.positions_host);
+      p.list_pos.push_back(s.positions_host);
       p.list_m.push_back(s.m);
       p.list_first.push_back(p.coefs);
       p.coefs += s.m;
     }
     p.list_of[i] = it.first->second;
   }
-  lists.clear();
+  return p;
+}
+
+// the verdict on the lists: every GROUPED secret learns where its coefficients start, and is refused when its list has none
+// (list_ok[l] == 0: duplicate positions, a denominator without inverse)
+inline void plan_settle(SecretPlans& p, const std::vector<char>& list_ok) {
+  for (size_t i = 0; i < p.secret.size(); ++i) {
+    if (p.secret[i].kind != SECRET_GROUPED) continue;
+    const size_t l = p.list_of[i];
+    p.secret[i].coef = p.list_first[l];
+    if (!list_ok[l]) p.secret[i].kind = SECRET_REFUSED;
+  }
+}
+
+// The Lagrange coefficients ONCE per distinct position list of a plan_lists plan on the host, then plan_settle.
+//   sized(coefs): called once, before any coefficient, so that the caller can size its arrays
+//   coefficient(positions, m, j, c) -> bool: coefficient j of a list into the caller's slot c; false: the list has none (duplicate
+//     positions, a denominator without inverse), and every secret of that list is refused.  Called on
+//     many_threads(host_threads, coefs, 64) threads, every (list, j) exactly once.
+template <class Sized, class Coefficient>
+void plan_host_coefficients(SecretPlans& p, int host_threads, Sized sized, Coefficient coefficient) {
   sized(p.coefs);
   std::vector<char> coef_ok(p.coefs, 0);
   // a coefficient costs m small products and one inversion at the modulus' width: a thread per 64 of them when the library chooses
@@ -129,16 +144,23 @@ SecretPlans plan_secrets(const Secret* secrets, size_t count, size_t cap_each, s
     size_t l = std::upper_bound(p.list_first.begin(), p.list_first.end(), lo) - p.list_first.begin() - 1;
     for (size_t c = lo; c < hi; ++c) {
       while (l + 1 < p.list_first.size() && p.list_first[l + 1] <= c) ++l;
-      coef_ok[c] = coefficient(list_pos[l], p.list_m[l], c - p.list_first[l], c) ? 1 : 0;
+      coef_ok[c] = coefficient(p.list_pos[l], p.list_m[l], c - p.list_first[l], c) ? 1 : 0;
     }
   });
-  for (size_t i = 0; i < count; ++i) {
-    if (p.secret[i].kind != SECRET_GROUPED) continue;
-    const size_t l = p.list_of[i];
-    p.secret[i].coef = p.list_first[l];
+  std::vector<char> list_ok(p.list_m.size(), 0);
+  for (size_t l = 0; l < list_ok.size(); ++l) {
     const auto first = coef_ok.begin() + p.list_first[l], last = first + p.list_m[l];
-    if (std::find(first, last, 0) != last) p.secret[i].kind = SECRET_REFUSED;
+    list_ok[l] = std::find(first, last, 0) == last;
   }
+  plan_settle(p, list_ok);
+}
+
+// plan_lists and plan_host_coefficients: the whole plan of a call whose coefficients are the host's
+template <class Secret, class Sized, class Coefficient>
+SecretPlans plan_secrets(const Secret* secrets, size_t count, size_t cap_each, size_t cap_run, int host_threads, Sized sized,
+                         Coefficient coefficient) {
+  SecretPlans p = plan_lists(secrets, count, cap_each, cap_run);
+  plan_host_coefficients(p, host_threads, sized, coefficient);
   return p;
 }
 

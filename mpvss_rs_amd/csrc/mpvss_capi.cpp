@@ -28,6 +28,7 @@
 #include "modp_rt_kernels.h"
 #include "sha256.h"
 #include "verdict_kernels.h"
+#include "ec_lagrange.h"
 
 namespace {
 
@@ -69,9 +70,11 @@ struct EcWork {   // device workspace of the elliptic-curve entry points (one pe
   DevBuf flags;                  // ints: [0] forward-difference gate, [1] first bad response, [2] first bad challenge
   DevBuf pg;                     // r G of a lone block, computed beside the X path (a1 = r G + c X is then one table multiplication and an addition)
   DevBuf hand, wtab;             // hand-over space of the quad-lane stepping pipeline, window tables of its seed kernel (a box that has the chip to itself)
+  DevBuf lag_pos, lag_tiles;     // k_ec_lagrange of one secret: its positions and its tile table
+  DevBuf lag_call_pos, lag_call_tiles, lag_coef, lag_src;   // ... of a reconstruct_many call: all distinct lists, their coefficients, the passes' source pointers
   std::vector<DevBuf*> all() {
     return {&a, &b, &c, &d, &e, &pos, &cm, &cmenc, &x, &o1, &o2, &ok, &gen, &chal, &pts, &fdst, &tab1, &tab2, &tab3, &p1, &p2,
-            &flags, &hand, &wtab, &pg};
+            &flags, &hand, &wtab, &pg, &lag_pos, &lag_tiles, &lag_call_pos, &lag_call_tiles, &lag_coef, &lag_src};
   }
 };
 
@@ -162,8 +165,8 @@ struct mpvss_ctx {
   void* pin = nullptr;
   size_t pin_cap = 0;
   hipEvent_t ev[2] = {nullptr, nullptr};
-  // 0 X path, 1 comb_dual_exp (a1), 2 table builds, 3 dual_exp (a2 / exp), 4 the scalar-ring kernels of a run-time group,
-  // 5 the per-share hash of a run-time group (k_rt_share_verdict)
+  // 0 X path, 1 comb_dual_exp (a1), 2 table builds, 3 dual_exp (a2 / exp), 4 the scalar-ring kernels of a run-time group and
+  // k_ec_lagrange of the curve groups, 5 the per-share hash of a run-time group (k_rt_share_verdict)
   double kernel_ms[6] = {-1, -1, -1, -1, -1, -1};
   int kernel_launches[6] = {0, 0, 0, 0, 0, 0};
   struct Span { int id; hipEvent_t a, b; };
@@ -173,6 +176,7 @@ struct mpvss_ctx {
     size_t ev_used = 0;
   };
   SpanSet main_spans;
+  SpanSet call_spans;          // the one k_ec_lagrange launch of an mpvss_ec_reconstruct_many call: its passes reset main_spans
   SpanSet* sp = &main_spans;   // where TIMED_LAUNCH records
   // Up to NSLOT verify blocks may be in flight (compute of block k+1.. is enqueued before block k is absorbed):
   // each has its own pinned staging, timing events and completion event.
@@ -345,6 +349,8 @@ struct mpvss_ctx {
   EcWork ecwork;
   // mpvss_ec_reconstruct_many_stats (capi_scalar.inc), both curves together
   unsigned long long ec_rec_passes = 0, ec_rec_grouped_secrets = 0, ec_rec_single_secrets = 0;
+  int ec_lagrange_mode = 1;                      // mpvss_ctx_set_ec_lagrange
+  unsigned long long ec_lagrange_dev_lists = 0, ec_lagrange_host_lists = 0;   // position lists (mpvss_ec_lagrange_stats)
   // mpvss_ec_verify_many (capi_ec.inc): runs of small boxes as one dense batch (mpvss_ctx_set_ec_box_groups: 0 never, 1 automatic),
   // and mpvss_ec_verify_many_stats, both curves together
   int ec_box_groups = EC_BOX_GROUPS_DEFAULT;
@@ -943,6 +949,7 @@ extern "C" void mpvss_ctx_destroy(mpvss_ctx* ctx) {
   if (ctx->ct.stream) { (void)hipStreamSynchronize(ctx->ct.stream); (void)hipStreamDestroy(ctx->ct.stream); }
   if (ctx->ct.ready) (void)hipEventDestroy(ctx->ct.ready);
   for (hipEvent_t e : ctx->main_spans.ev_pool) (void)hipEventDestroy(e);
+  for (hipEvent_t e : ctx->call_spans.ev_pool) (void)hipEventDestroy(e);
   for (auto& sl : ctx->slot) {
     if (sl.pin) (void)hipHostFree(sl.pin);
     if (sl.done) (void)hipEventDestroy(sl.done);

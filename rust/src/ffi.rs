@@ -267,6 +267,9 @@ unsafe extern "C" {
                                      host_threads: c_int, status: *mut c_int, gs_out: *mut u8, masks_out32: *mut u8) -> c_int;
     pub fn mpvss_ec_reconstruct_many_stats(ctx: *mut mpvss_ctx, passes: *mut c_ulonglong, grouped_secrets: *mut c_ulonglong,
                                            single_secrets: *mut c_ulonglong) -> c_int;
+    pub fn mpvss_ctx_set_ec_lagrange(ctx: *mut mpvss_ctx, mode: c_int) -> c_int;
+    pub fn mpvss_ec_lagrange_scalars(ctx: *mut mpvss_ctx, group: c_int, positions_host: *const i64, m: usize, scalars_out_host: *mut u8) -> c_int;
+    pub fn mpvss_ec_lagrange_stats(ctx: *mut mpvss_ctx, device_lists: *mut c_ulonglong, host_lists: *mut c_ulonglong) -> c_int;
     // ---- wire format
     pub fn mpvss_box_wire_size(group: c_int, n: usize, t: usize, u_len: usize) -> usize;
     pub fn mpvss_box_serialize(group: c_int, commitments: *const u8, t: usize, positions: *const i64, pubkeys: *const u8, shares: *const u8,

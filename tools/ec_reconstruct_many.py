@@ -6,9 +6,16 @@ repetitions stands beside it.  The results of the two sides are compared before 
 the same position list for all its secrets and once with a list of its own for each, so that the share of the Lagrange cache shows.
 
     python tools/ec_reconstruct_many.py > profiles/ec_reconstruct_many.txt
-    python tools/ec_reconstruct_many.py --curves secp256k1 --shapes 3 --spaces host --lists equal   (a part of the table: shape 3 is 8 x 16384)"""
+    python tools/ec_reconstruct_many.py --curves secp256k1 --shapes 3 --spaces host --lists equal   (a part of the table: shape 3 is 8 x 16384)
+
+--lagrange {host,device,auto} sets where the Lagrange coefficients are computed (mpvss_ctx_set_ec_lagrange; a library of an older
+commit, MPVSS_HIP_LIB, has no such switch and is reported as "parent").  --no-loop leaves the loop of one-secret calls out -- at
+16384 shares with a list per secret it takes minutes on the host -- and prints a digest of the call's results instead, so that
+runs of different builds and modes can be compared line by line (profiles/ec_lagrange_device.txt).  Shapes 4 to 7 are 60 x 4096
+and ONE secret of 1024, 4096 and 16384 shares: a call of one secret is the one-secret path, mpvss_ec_reconstruct."""
 import argparse
 import ctypes as C
+import hashlib
 import os
 import random
 import statistics
@@ -21,7 +28,7 @@ import torch  # noqa: E402
 from mpvss_rs_amd import Engine, capi  # noqa: E402
 
 REPS = 3
-SHAPES = ((400, 3), (200, 34), (60, 1024), (8, 16384))       # secrets, m
+SHAPES = ((400, 3), (200, 34), (60, 1024), (8, 16384), (60, 4096), (1, 1024), (1, 4096), (1, 16384))       # secrets, m
 POOL = 16384 + 512                                           # shares made per curve; a secret takes m consecutive ones
 GID = {"secp256k1": capi.GROUP_SECP256K1, "ristretto255": capi.GROUP_RISTRETTO255}
 ORDER = {"secp256k1": 0xFFFFFFFFFFFFFFFFFFFFFFFFFFFFFFFEBAAEDCE6AF48A03BBFD25E8CD0364141,
@@ -32,9 +39,16 @@ ap.add_argument("--curves", default="secp256k1,ristretto255")
 ap.add_argument("--shapes", default="0,1,2")
 ap.add_argument("--spaces", default="host,device")
 ap.add_argument("--lists", default="equal,distinct")
+ap.add_argument("--lagrange", choices=("host", "device", "auto"), default=None)
+ap.add_argument("--no-loop", action="store_true")
 args = ap.parse_args()
 
 eng = Engine(0)
+HAS_MODE = hasattr(eng.lib, "mpvss_ec_lagrange_scalars")
+MODE = (args.lagrange or "auto") if HAS_MODE else "parent"
+if HAS_MODE and args.lagrange:
+    eng.set_ec_lagrange(("host", "auto", "device").index(args.lagrange))
+eng.lib.mpvss_last_kernel_ms.restype = C.c_double
 
 
 def timed(fn):
@@ -50,7 +64,9 @@ def timed(fn):
 
 
 print(f"# {torch.cuda.get_device_name(0)}; median of {REPS} after one warm-up; ms for all secrets of the call; loop_min / loop_max: the spread of the loop's {REPS} runs")
-print("# curve        secrets     m space  lists      loop_ms  loop_min  loop_max   many_ms  speedup  passes grouped single", flush=True)
+print("# lagrange: where the coefficients are computed; dev_l / host_l: position lists per call computed on either side; k_ms: k_ec_lagrange's own time in the last call (hipEvents)")
+print("# curve        secrets     m space  lists      loop_ms  loop_min  loop_max   many_ms  many_min  many_max  speedup  passes grouped single lagrange  dev_l host_l    k_ms  digest",
+      flush=True)
 for curve in args.curves.split(","):
     group, L = GID[curve], capi.EC_ENC[GID[curve]]
     rng = random.Random(curve)
@@ -85,15 +101,23 @@ for curve in args.curves.split(","):
 
                 print(f"  {curve} {K} x {m} {lists}: many, then loop", file=sys.stderr, flush=True)
                 s0 = eng.ec_reconstruct_many_stats()
-                t_many, _, _ = timed(many)
+                l0 = eng.ec_lagrange_stats() if HAS_MODE else dict(device=0, host=0)
+                t_many, many_lo, many_hi = timed(many)
+                k_ms = eng.lib.mpvss_last_kernel_ms(eng.ctx, 4)
                 s1 = eng.ec_reconstruct_many_stats()
-                t_loop, lo, hi = timed(loop)
-                assert list(st) == [0] * K and bytes(g_many) == bytes(g_loop) and bytes(m_many) == bytes(m_loop)
-                assert len({bytes(g_many)[L * i:L * i + L] for i in range(K)}) > 1
+                l1 = eng.ec_lagrange_stats() if HAS_MODE else dict(device=0, host=0)
+                assert list(st) == [0] * K
+                if args.no_loop:
+                    t_loop = lo = hi = float("nan")
+                else:
+                    t_loop, lo, hi = timed(loop)
+                    assert bytes(g_many) == bytes(g_loop) and bytes(m_many) == bytes(m_loop)
+                assert K == 1 or len({bytes(g_many)[L * i:L * i + L] for i in range(K)}) > 1
                 calls = REPS + 1
                 print(f"  {curve:12s} {K:7d} {m:5d} {'host' if space == capi.MPVSS_HOST else 'device':6s} {lists:8s} "
-                      f"{t_loop:9.2f} {lo:9.2f} {hi:9.2f} {t_many:9.2f} {t_loop / t_many:8.2f} {(s1['passes'] - s0['passes']) // calls:7d} "
+                      f"{t_loop:9.2f} {lo:9.2f} {hi:9.2f} {t_many:9.2f} {many_lo:9.2f} {many_hi:9.2f} {t_loop / t_many:8.2f} {(s1['passes'] - s0['passes']) // calls:7d} "
                       f"{(s1['grouped_secrets'] - s0['grouped_secrets']) // calls:7d} "
-                      f"{(s1['single_secrets'] - s0['single_secrets']) // calls:6d}", flush=True)
+                      f"{(s1['single_secrets'] - s0['single_secrets']) // calls:6d} {MODE:8s} {(l1['device'] - l0['device']) // calls:6d} "
+                      f"{(l1['host'] - l0['host']) // calls:6d} {k_ms:7.3f}  {hashlib.sha256(bytes(g_many) + bytes(m_many)).hexdigest()[:16]}", flush=True)
     assert dev_pool.cpu().numpy().tobytes() == pool, "the share pool in HBM changed"
 eng.close()
