@@ -454,6 +454,62 @@ int mpvss_ec_deal_compute(mpvss_ctx* ctx, int group, const uint8_t* coeffs_host,
 int mpvss_ec_deal(mpvss_ctx* ctx, int group, const uint8_t* coeffs_host, size_t t, const int64_t* positions_host,
                   const uint8_t* pubkeys_host, const uint8_t* witnesses_host, size_t n, uint8_t* x_out, uint8_t* y_out,
                   uint8_t* a1_out, uint8_t* a2_out, uint8_t* digest32_out, uint8_t* challenge_out32, uint8_t* r_out);
+
+/* Key sets of a curve group.  The dealer's Y_i = P(i) y_i and a2_i = w_i y_i are multiples of long-lived public keys.  A key
+ * set holds, for each of n keys, the fixed-base comb the context keeps for the generator: rows[key][w][i] = (i + 1) 16^w y_key,
+ * w < 65, i < 8, packed affine entries of 64 (secp256k1) / 96 (ristretto255) bytes -- 33 280 / 49 920 bytes per key plus one
+ * mark byte, mpvss_ec_keyset_bytes_per_key; 65 536 keys take 2.2 / 3.3 GB.  Over the rows k y is 65 mixed additions and no
+ * doublings, against 128 doublings + about 66 additions (secp256k1, endomorphism) or 256 + 64 (ristretto255) over a table built
+ * per call; the key's decode (a field square root) and table build disappear from every call.
+ * KEYS: canonical encodings of 33 / 32 bytes.  One invalid encoding refuses the whole create with MPVSS_E_INVALID, the smallest
+ * bad index named by mpvss_last_error, *out = NULL.  The identity (33 / 32 zero bytes) is a valid key: it has no affine form
+ * on secp256k1, so the set marks such a key and every multiple of it comes out as the identity.
+ * OWNERSHIP: a set belongs to the context that built it, remembers its curve and never changes.  destroy synchronises the
+ * set's context first (a block enqueued by mpvss_ec_deal_compute_keyset may still read the rows) and frees the set on its own
+ * context whichever context is named (both arguments may be null); a set is destroyed before its context.
+ * ERRORS: MPVSS_E_INVALID for a set of another context or of the other curve, for key_offset + n beyond the set, for a scalar
+ * that is not below the group order (its index named) and for create with n == 0 or a null pointer; an allocation that fails is
+ * MPVSS_E_NOMEM and leaves the context usable.  n == 0 behaves as in the calls that take the keys as an array.
+ * RESULTS are byte-identical to those calls -- mpvss_ec_batch_exp, a2 of mpvss_ec_dleq_commitments, mpvss_ec_deal_compute
+ * followed by mpvss_ec_distribute_absorb, mpvss_ec_deal with digest, challenge and responses -- with pubkeys = the keys
+ * key_offset .. key_offset + n - 1 of the set.  The rows hold public values only and are not wiped; P(i), the witnesses and
+ * the coefficients are wiped exactly as in those calls.
+ * Not offered: verify_distribution, verify_many and distribute over a key set (a2 = r y + c Y of the verifier still needs the
+ * doublings for the fresh Y); a key cache behind the calls that take a key array; a half-size secp256k1 set through the
+ * endomorphism (33 windows, the entries of phi(y) by one product with beta) -- the follow-up if memory matters; any automatic
+ * routing: the caller builds the set and names it. */
+typedef struct mpvss_ec_keyset mpvss_ec_keyset;
+/* bytes of one key in a set of this curve: its rows and its mark; host only; 0 for an unknown group */
+size_t mpvss_ec_keyset_bytes_per_key(int group);
+/* pubkeys: n encodings in `space`; the build is 256 doublings per key and, per window, 4 doublings, 3 additions and ONE field
+ * inversion for the eight entries */
+int mpvss_ec_keyset_create(mpvss_ctx* ctx, int group, int space, const uint8_t* pubkeys, size_t n, mpvss_ec_keyset** out);
+void mpvss_ec_keyset_destroy(mpvss_ctx* ctx, mpvss_ec_keyset* keyset);
+/* device bytes of the set; host only; 0 for no set */
+size_t mpvss_ec_keyset_bytes(const mpvss_ec_keyset* keyset);
+/* out1[i] = e1[i] y_(key_offset+i), out2[i] = e2[i] y_(key_offset+i): two scalar sets in one launch; e2 and out2 may both be
+ * NULL (one power).  Scalars: 32 bytes each in the group's byte order, in `space`, as the outputs */
+int mpvss_ec_keyset_twin_exp(mpvss_ctx* ctx, int group, int space, const mpvss_ec_keyset* keyset, size_t key_offset,
+                             const uint8_t* e1, const uint8_t* e2, size_t n, uint8_t* out1, uint8_t* out2);
+/* out[i] = e1[i] y_(key_offset+i) + e2[i] h2[i]; h2 == NULL: the first term alone.  e2: n scalars in `space` when
+ * e2_per_share, else ONE scalar in host memory for every share (as c of mpvss_ec_dleq_commitments).  The shape of the
+ * verifier's a2, as a building block: the walk, the one-table window kernel for h2, an addition, the encode */
+int mpvss_ec_keyset_dual_exp(mpvss_ctx* ctx, int group, int space, const mpvss_ec_keyset* keyset, size_t key_offset,
+                             const uint8_t* e1, const uint8_t* h2, const uint8_t* e2, int e2_per_share, size_t n, uint8_t* out);
+/* mpvss_ec_deal_compute with (keyset, key_offset) in place of pubkeys_dev; absorbed by mpvss_ec_distribute_absorb */
+int mpvss_ec_deal_compute_keyset(mpvss_ctx* ctx, int group, const uint8_t* coeffs_host, size_t t, const int64_t* positions_dev,
+                                 const mpvss_ec_keyset* keyset, size_t key_offset, const uint8_t* witnesses_dev, size_t n,
+                                 uint8_t* p_dev_out, uint8_t* x_dev_out, uint8_t* y_dev_out, uint8_t* a1_dev_out,
+                                 uint8_t* a2_dev_out);
+/* mpvss_ec_deal with (keyset, key_offset) in place of pubkeys_host: no key upload, decode or table build */
+int mpvss_ec_deal_keyset(mpvss_ctx* ctx, int group, const uint8_t* coeffs_host, size_t t, const int64_t* positions_host,
+                         const mpvss_ec_keyset* keyset, size_t key_offset, const uint8_t* witnesses_host, size_t n, uint8_t* x_out,
+                         uint8_t* y_out, uint8_t* a1_out, uint8_t* a2_out, uint8_t* digest32_out, uint8_t* challenge_out32,
+                         uint8_t* r_out);
+/* since the context was created, both curves together: the keys whose rows were built, and the multiples k y computed by a walk
+ * over rows (two per share of a dealer's block or a twin call with e2, one otherwise); either pointer may be NULL */
+int mpvss_ec_keyset_stats(mpvss_ctx* ctx, unsigned long long* keys_built, unsigned long long* powers_from_rows);
+
 /* Group::hash_to_scalar(data), host only; out32 in the group's scalar byte order */
 int mpvss_ec_hash_to_scalar(int group, const uint8_t* data, size_t len, uint8_t out32[32]);
 

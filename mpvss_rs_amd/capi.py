@@ -69,6 +69,9 @@ EXPORTED_SYMBOLS = (
     "mpvss_ec_reconstruct_many", "mpvss_ec_reconstruct_many_stats",
     "mpvss_ctx_set_ec_lagrange", "mpvss_ec_lagrange_scalars", "mpvss_ec_lagrange_stats",
     "mpvss_ctx_set_ec_box_groups", "mpvss_ec_verify_many_stats",
+    "mpvss_ec_keyset_bytes_per_key", "mpvss_ec_keyset_create", "mpvss_ec_keyset_destroy", "mpvss_ec_keyset_bytes",
+    "mpvss_ec_keyset_twin_exp", "mpvss_ec_keyset_dual_exp", "mpvss_ec_deal_compute_keyset", "mpvss_ec_deal_keyset",
+    "mpvss_ec_keyset_stats",
 )
 
 GROUP_SECP256K1 = 1
@@ -208,6 +211,18 @@ def load_library() -> C.CDLL:
     lib.mpvss_ec_dleq_responses_device.argtypes = [vp, ci, vp, vp, u8p, sz, vp]
     lib.mpvss_ec_deal_compute.argtypes = [vp, ci, u8p, sz, vp, vp, vp, sz, vp, vp, vp, vp, vp]
     lib.mpvss_ec_deal.argtypes = [vp, ci, u8p, sz, i64p, u8p, u8p, sz, u8p, u8p, u8p, u8p, u8p, u8p, u8p]
+    lib.mpvss_ec_keyset_bytes_per_key.argtypes = [ci]
+    lib.mpvss_ec_keyset_bytes_per_key.restype = sz
+    lib.mpvss_ec_keyset_create.argtypes = [vp, ci, ci, vp, sz, C.POINTER(vp)]
+    lib.mpvss_ec_keyset_destroy.argtypes = [vp, vp]
+    lib.mpvss_ec_keyset_destroy.restype = None
+    lib.mpvss_ec_keyset_bytes.argtypes = [vp]
+    lib.mpvss_ec_keyset_bytes.restype = sz
+    lib.mpvss_ec_keyset_twin_exp.argtypes = [vp, ci, ci, vp, sz, u8p, u8p, sz, u8p, u8p]
+    lib.mpvss_ec_keyset_dual_exp.argtypes = [vp, ci, ci, vp, sz, u8p, u8p, u8p, ci, sz, u8p]
+    lib.mpvss_ec_deal_compute_keyset.argtypes = [vp, ci, u8p, sz, vp, vp, sz, vp, sz, vp, vp, vp, vp, vp]
+    lib.mpvss_ec_deal_keyset.argtypes = [vp, ci, u8p, sz, i64p, vp, sz, u8p, sz, u8p, u8p, u8p, u8p, u8p, u8p, u8p]
+    lib.mpvss_ec_keyset_stats.argtypes = [vp, C.POINTER(C.c_ulonglong), C.POINTER(C.c_ulonglong)]
     lib.mpvss_ec_hash_to_scalar.argtypes = [ci, u8p, sz, u8p]
     lib.mpvss_ec_batch_exp_generator.argtypes = [vp, ci, ci, u8p, sz, u8p]
     lib.mpvss_box_wire_size.argtypes = [ci, sz, sz, sz]
@@ -346,6 +361,29 @@ class GroupKeySet:
     def close(self) -> None:
         if self.handle:
             self.engine.lib.mpvss_modp_group_keyset_destroy(self.engine.ctx, self.handle)
+            self.handle = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+
+class EcKeySet:
+    """The per-key combs of registered public keys of a curve group on one Engine's context (mpvss_ec_keyset_create): immutable;
+    close() synchronises the context and frees the device memory."""
+
+    def __init__(self, engine, group, handle, n):
+        self.engine, self.group, self.handle, self.n = engine, group, handle, n
+
+    @property
+    def nbytes(self) -> int:
+        return int(self.engine.lib.mpvss_ec_keyset_bytes(self.handle)) if self.handle else 0
+
+    def close(self) -> None:
+        if self.handle:
+            self.engine.lib.mpvss_ec_keyset_destroy(self.engine.ctx, self.handle)
             self.handle = None
 
     def __enter__(self):
@@ -1459,6 +1497,90 @@ class Engine:
         call, outputs = self.ec_deal_call(group, coeffs, positions, pubkeys, witnesses)
         call()
         return outputs()
+
+    # ---- key sets of a curve group (include/mpvss_hip.h, "Key sets of a curve group")
+    def ec_keyset_bytes_per_key(self, group: int) -> int:
+        return int(self.lib.mpvss_ec_keyset_bytes_per_key(group))
+
+    def ec_keyset_create(self, group: int, pubkeys: bytes) -> "EcKeySet":
+        """the per-key combs of n public keys (canonical encodings); one invalid key refuses the whole call"""
+        n = len(pubkeys) // EC_ENC[group]
+        kk, pk = _buf(pubkeys)
+        h = C.c_void_p()
+        self._check(self.lib.mpvss_ec_keyset_create(self.ctx, group, MPVSS_HOST, pk, n, C.byref(h)), "ec_keyset_create")
+        return EcKeySet(self, group, h, n)
+
+    def ec_keyset_create_device(self, group: int, pubkeys_dev_ptr: int, n: int) -> "EcKeySet":
+        """the same from n encodings in device memory"""
+        h = C.c_void_p()
+        self._check(self.lib.mpvss_ec_keyset_create(self.ctx, group, MPVSS_DEVICE, C.c_void_p(pubkeys_dev_ptr), int(n), C.byref(h)),
+                    "ec_keyset_create")
+        return EcKeySet(self, group, h, int(n))
+
+    def ec_keyset_twin_exp(self, group: int, keyset: "EcKeySet", key_offset: int, e1: bytes, e2: Optional[bytes] = None):
+        """(e1[i] y_(key_offset+i), e2[i] y_(key_offset+i)) over the set's rows; e2 None: (the first, None)"""
+        n, L = len(e1) // 32, EC_ENC[group]
+        k = [_buf(e1), _buf(e2)]
+        o1, p1 = _out(n * L)
+        o2, p2 = _out(n * L) if e2 is not None else (None, None)
+        self._check(self.lib.mpvss_ec_keyset_twin_exp(self.ctx, group, MPVSS_HOST, keyset.handle, int(key_offset), k[0][1], k[1][1], n,
+                                                      p1, p2), "ec_keyset_twin_exp")
+        return bytes(o1)[: n * L], (bytes(o2)[: n * L] if e2 is not None else None)
+
+    def ec_keyset_dual_exp(self, group: int, keyset: "EcKeySet", key_offset: int, e1: bytes, h2: Optional[bytes] = None,
+                           e2: Optional[bytes] = None, e2_per_share: bool = True) -> bytes:
+        """e1[i] y_(key_offset+i) + e2[i] h2[i] (h2 None: the first term alone); e2: n scalars, or ONE when not e2_per_share"""
+        n, L = len(e1) // 32, EC_ENC[group]
+        k = [_buf(e1), _buf(h2), _buf(e2)]
+        ko, po = _out(n * L)
+        self._check(self.lib.mpvss_ec_keyset_dual_exp(self.ctx, group, MPVSS_HOST, keyset.handle, int(key_offset), k[0][1], k[1][1],
+                                                      k[2][1], int(e2_per_share), n, po), "ec_keyset_dual_exp")
+        return bytes(ko)[: n * L]
+
+    def ec_deal_compute_keyset(self, group: int, coeffs: bytes, positions_dev_ptr: int, keyset: "EcKeySet", key_offset: int,
+                               witnesses_dev_ptr: int, n: int, p_dev_out_ptr: int) -> None:
+        """ec_deal_compute to registered keys: Y and a2 from the set's rows, same outputs (absorb with ec_distribute_absorb)"""
+        kc, pc = _buf(coeffs)
+        self._check(self.lib.mpvss_ec_deal_compute_keyset(self.ctx, group, pc, len(coeffs) // 32, positions_dev_ptr, keyset.handle,
+                                                          int(key_offset), witnesses_dev_ptr, n, p_dev_out_ptr, None, None, None, None),
+                    "ec_deal_compute_keyset")
+
+    def ec_deal_keyset_call(self, group: int, coeffs: bytes, positions: Sequence[int], keyset: "EcKeySet", key_offset: int,
+                            witnesses: bytes, optional_outputs: bool = True):
+        """(call, outputs) for mpvss_ec_deal_keyset over ctypes buffers made once (see ec_deal_call); optional_outputs False passes
+        NULL for X, a1, a2, digest and challenge"""
+        n = len(positions)
+        L = EC_ENC[group]
+        pos = (C.c_int64 * max(n, 1))(*positions)
+        k = [_buf(b) for b in (coeffs, witnesses)]
+        outs = [_out(n * L) if (optional_outputs or i == 1) else (None, None) for i in range(4)]
+        kr, pr = _out(n * 32)
+        kd, pd = _out(32) if optional_outputs else (None, None)
+        kc, pc = _out(32) if optional_outputs else (None, None)
+        t = len(coeffs) // 32
+
+        def call():
+            self._check(self.lib.mpvss_ec_deal_keyset(self.ctx, group, k[0][1], t, pos, keyset.handle, int(key_offset), k[1][1], n,
+                                                      outs[0][1], outs[1][1], outs[2][1], outs[3][1], pd, pc, pr), "ec_deal_keyset")
+
+        def outputs():
+            X, Y, a1, a2 = (bytes(o[0])[: n * L] if o[0] is not None else None for o in outs)
+            return {"X": X, "Y": Y, "a1": a1, "a2": a2, "digest": bytes(kd)[:32] if kd is not None else None,
+                    "challenge": bytes(kc)[:32] if kc is not None else None, "responses": bytes(kr)[: n * 32]}
+        return call, outputs
+
+    def ec_deal_keyset(self, group: int, coeffs: bytes, positions: Sequence[int], keyset: "EcKeySet", key_offset: int,
+                       witnesses: bytes, optional_outputs: bool = True) -> dict:
+        """ec_deal to registered keys: the whole box in one call, no key upload"""
+        call, outputs = self.ec_deal_keyset_call(group, coeffs, positions, keyset, key_offset, witnesses, optional_outputs)
+        call()
+        return outputs()
+
+    def ec_keyset_stats(self):
+        """(keys whose rows were built, multiples computed by a walk over rows) since the context was created"""
+        a, b = C.c_ulonglong(0), C.c_ulonglong(0)
+        self._check(self.lib.mpvss_ec_keyset_stats(self.ctx, C.byref(a), C.byref(b)), "ec_keyset_stats")
+        return int(a.value), int(b.value)
 
     def ec_distribute_absorb(self, group: int, state: bytes, n: int):
         """(state, X, Y, a1, a2) of the oldest dealer block"""

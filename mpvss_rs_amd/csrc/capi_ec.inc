@@ -7,6 +7,17 @@
 #include "ec_kernels.h"
 #include "sha512.h"
 
+// A key set of a curve group (include/mpvss_hip.h, "Key sets of a curve group"): the per-key combs of n public keys on the
+// device (ec_launch_keyset_build) and a mark per key that is the identity.  It belongs to the context that built it, remembers
+// its curve and never changes after create.  The rows hold public values only and are not wiped.
+struct mpvss_ec_keyset {
+  mpvss_ctx* ctx = nullptr;
+  int group = 0;
+  size_t n = 0;
+  uint32_t* rows = nullptr;      // [n][65][8][packed affine words]
+  uint8_t* marks = nullptr;      // [n]: 1 = the key is the identity
+};
+
 namespace {
 
 struct EcInfo {
@@ -232,6 +243,29 @@ int ec_dual(mpvss_ctx* ctx, const EcInfo* gi, const EcBase& b1, const uint8_t* k
                                           ctx->stream));
   // (out_enc == null: the caller goes on with the internal points in pout and nobody reads the encodings -- a reconstruct pass)
   if (out_enc != nullptr) TIMED_LAUNCH(ctx, 3, ec_launch_encode(group, (const uint32_t*)pout.p, (int)n, out_enc, ctx->stream));
+  return 0;
+}
+
+// One byte per key beside its rows: the identity mark.
+constexpr size_t EC_KEYSET_MARK_BYTES = 1;
+
+// The one admission of a key set to a call (context lock held): built by this context, for this curve, and holding the keys
+// key_offset .. key_offset + n - 1.  Why not, or null when the set is admitted.
+const char* ec_keyset_refusal(const mpvss_ctx* ctx, int group, const mpvss_ec_keyset* ks, size_t key_offset, size_t n) {
+  if (!ks) return "key set: none given";
+  if (ks->ctx != ctx) return "key set: built by another context";
+  if (ks->group != group) return "key set: built for the other curve";
+  if (key_offset > ks->n || n > ks->n - key_offset) return "key set: key_offset + n is beyond the set";
+  return nullptr;
+}
+
+// out1[x] = k1[x] * y_(first + x) and (k2 != null) out2[x] = k2[x] * y_(first + x), x < n, in internal coordinates on
+// ctx->stream: one walk over the rows, both scalar sets in one launch.  The counter feeds mpvss_ec_keyset_stats.
+int ec_keyset_walk(mpvss_ctx* ctx, const mpvss_ec_keyset* ks, size_t first, const uint8_t* k1, const uint8_t* k2, size_t n,
+                   uint32_t* out1, uint32_t* out2) {
+  TIMED_LAUNCH(ctx, 1, ec_launch_keyset_walk(ks->group, ks->rows + first * ec_keyset_row_words(ks->group), ks->marks + first, k1, k2,
+                                             (int)n, out1, out2, ctx->stream));
+  ctx->ec_ks_powers += (k2 != nullptr ? 2 : 1) * (unsigned long long)n;
   return 0;
 }
 
@@ -824,16 +858,21 @@ struct EcDealPoly {
 int ec_distribute_compute_locked(mpvss_ctx* ctx, int group, int space, const uint8_t* commitments, size_t t,
                                  const int64_t* positions, const uint8_t* pubkeys, const uint8_t* p_values,
                                  const uint8_t* witnesses, size_t n, uint8_t* x_dev_out, uint8_t* y_dev_out,
-                                 uint8_t* a1_dev_out, uint8_t* a2_dev_out, const EcDealPoly* poly = nullptr) {
+                                 uint8_t* a1_dev_out, uint8_t* a2_dev_out, const EcDealPoly* poly = nullptr,
+                                 const mpvss_ec_keyset* keyset = nullptr, size_t key_offset = 0) {
   const EcInfo* gi = ec_info(group);
   if (!gi) return fail(ctx, MPVSS_E_UNSUPPORTED, "ec_distribute: unknown group");
+  // keyset != null: the keys key_offset .. key_offset + n - 1 of the set stand for pubkeys (admitted by the caller): Y and a2 by
+  // one walk over their rows -- no key staging, decode or table build
+  if (keyset && space != MPVSS_DEVICE) return fail(ctx, MPVSS_E_INVALID, "ec_distribute: a key set takes device buffers");
   if (poly) {
     if (space != MPVSS_DEVICE || commitments || (!poly->coeffs_host && !poly->coeffs_dev) || !poly->positions_dev || !poly->p_dev_out ||
         poly->t == 0 || poly->t > 0x7fffffff)
       return fail(ctx, MPVSS_E_INVALID, "ec_deal: bad argument (device buffers, t >= 1)");
     p_values = poly->p_dev_out;
   }
-  if (n > 0 && (!pubkeys || !p_values || !witnesses || n > 0x7fffffff || (commitments && (!positions || t == 0 || t > 0x7fffffff))))
+  if (n > 0 && ((!pubkeys && !keyset) || !p_values || !witnesses || n > 0x7fffffff ||
+                (commitments && (!positions || t == 0 || t > 0x7fffffff))))
     return fail(ctx, MPVSS_E_INVALID, "ec_distribute: bad argument");
   if (!commitments) t = 0;      // (threshold > n is the whole box's business -- mpvss_ec_distribute checks it; a block may be smaller)
   BlockEnqueue be(ctx, 2, n, "ec_distribute");
@@ -890,8 +929,8 @@ int ec_distribute_compute_locked(mpvss_ctx* ctx, int group, int space, const uin
   HIPCHK(ctx, hipMemcpyAsync(flags + 1, st.flags + 1, 8, hipMemcpyHostToDevice, ctx->stream));
   HIPCHK(ctx, hipMemsetAsync(ok, 1, okn, ctx->stream));          // the flags nobody writes here count as valid
   if (commitments) RET_IF(ec_stage_commitments_async(ctx, gi, w, space, commitments, t, ok));
-  const void *dy, *dp, *dw;
-  RET_IF(stage_in(ctx, space, pubkeys, n * L, w.a, &dy));
+  const void *dy = nullptr, *dp, *dw;
+  if (!keyset) RET_IF(stage_in(ctx, space, pubkeys, n * L, w.a, &dy));
   RET_IF(stage_in(ctx, space, p_values, n * 32, w.d, &dp));
   RET_IF(stage_in(ctx, space, witnesses, n * 32, w.e, &dw));
   LAUNCHCHK(ctx, verdict_launch_check_scalars(group, (const uint8_t*)dp, (int)n, flags + 1, ctx->stream));
@@ -913,11 +952,22 @@ int ec_distribute_compute_locked(mpvss_ctx* ctx, int group, int space, const uin
   } else {
     RET_IF(ec_dual(ctx, gi, bg, (const uint8_t*)dp, 32, nullptr, nullptr, 0, n, w.tab2, w.tab2, w.p1, dX, nullptr, nullptr));   // X = p * G
   }
-  // the table of y_i serves both Y = p * y (participant.rs:1190) and a2 = w * y (dleq.rs:214-216)
-  RET_IF(ec_dual(ctx, gi, by, (const uint8_t*)dp, 32, nullptr, nullptr, 0, n, w.tab1, w.tab2, w.p1, dY, ok + t, nullptr));
-  RET_IF(ec_dual(ctx, gi, bg, (const uint8_t*)dw, 32, nullptr, nullptr, 0, n, w.tab2, w.tab2, w.p1, d1, nullptr, nullptr));     // a1 = w * G
-  by.table = (const uint32_t*)w.tab1.p;
-  RET_IF(ec_dual(ctx, gi, by, (const uint8_t*)dw, 32, nullptr, nullptr, 0, n, w.tab1, w.tab2, w.p2, d2, nullptr, nullptr));     // a2 = w * y
+  if (keyset) {
+    // Y = p * y and a2 = w * y from the rows of y_i: one walk, two encodes (the key flags count as valid: create checked the keys)
+    const size_t pts_bytes = n * (size_t)ec_point_words(group) * 4;
+    RET_IF(ensure(ctx, w.p1, pts_bytes));
+    RET_IF(ensure(ctx, w.p2, pts_bytes));
+    RET_IF(ec_keyset_walk(ctx, keyset, key_offset, (const uint8_t*)dp, (const uint8_t*)dw, n, (uint32_t*)w.p1.p, (uint32_t*)w.p2.p));
+    TIMED_LAUNCH(ctx, 3, ec_launch_encode(group, (const uint32_t*)w.p1.p, (int)n, dY, ctx->stream));
+    TIMED_LAUNCH(ctx, 3, ec_launch_encode(group, (const uint32_t*)w.p2.p, (int)n, d2, ctx->stream));
+    RET_IF(ec_dual(ctx, gi, bg, (const uint8_t*)dw, 32, nullptr, nullptr, 0, n, w.tab2, w.tab2, w.p1, d1, nullptr, nullptr));   // a1 = w * G
+  } else {
+    // the table of y_i serves both Y = p * y (participant.rs:1190) and a2 = w * y (dleq.rs:214-216)
+    RET_IF(ec_dual(ctx, gi, by, (const uint8_t*)dp, 32, nullptr, nullptr, 0, n, w.tab1, w.tab2, w.p1, dY, ok + t, nullptr));
+    RET_IF(ec_dual(ctx, gi, bg, (const uint8_t*)dw, 32, nullptr, nullptr, 0, n, w.tab2, w.tab2, w.p1, d1, nullptr, nullptr));   // a1 = w * G
+    by.table = (const uint32_t*)w.tab1.p;
+    RET_IF(ec_dual(ctx, gi, by, (const uint8_t*)dw, 32, nullptr, nullptr, 0, n, w.tab1, w.tab2, w.p2, d2, nullptr, nullptr));   // a2 = w * y
+  }
   HIPCHK(ctx, hipMemcpyAsync(st.X, dX, n * L, hipMemcpyDeviceToHost, ctx->stream));
   HIPCHK(ctx, hipMemcpyAsync(st.Y, dY, n * L, hipMemcpyDeviceToHost, ctx->stream));
   HIPCHK(ctx, hipMemcpyAsync(st.a1, d1, n * L, hipMemcpyDeviceToHost, ctx->stream));
@@ -967,15 +1017,17 @@ extern "C" int mpvss_ec_deal_compute(mpvss_ctx* ctx, int group, const uint8_t* c
 // The dealer of participant.rs:1094-1274 / 1573-1717 in ONE call from host buffers: P(i), X_i = P(i) G, Y_i = P(i) y_i, a1, a2,
 // the transcript digest, the challenge c = hash_to_scalar(digest) and the responses r_i = w_i - P(i) c.  Inputs and
 // intermediate secrets in the deal's own buffers (a set per deal in flight from the context's pool), P(i) and the witnesses zeroed at the end.
-extern "C" int mpvss_ec_deal(mpvss_ctx* ctx, int group, const uint8_t* coeffs_host, size_t t, const int64_t* positions_host,
-                             const uint8_t* pubkeys_host, const uint8_t* witnesses_host, size_t n, uint8_t* x_out, uint8_t* y_out,
-                             uint8_t* a1_out, uint8_t* a2_out, uint8_t* digest32_out, uint8_t* challenge_out32, uint8_t* r_out) {
-  if (!ctx) return MPVSS_E_INVALID;
-  std::unique_lock<std::mutex> lk(ctx->mu);
+// The keys: a host array (mpvss_ec_deal), or the keys key_offset .. of a key set admitted by the caller (mpvss_ec_deal_keyset: no
+// key upload).  Context lock held on entry and on return.
+namespace {
+int ec_deal_locked(mpvss_ctx* ctx, std::unique_lock<std::mutex>& lk, int group, const uint8_t* coeffs_host, size_t t,
+                   const int64_t* positions_host, const uint8_t* pubkeys_host, const mpvss_ec_keyset* keyset, size_t key_offset,
+                   const uint8_t* witnesses_host, size_t n, uint8_t* x_out, uint8_t* y_out, uint8_t* a1_out, uint8_t* a2_out,
+                   uint8_t* digest32_out, uint8_t* challenge_out32, uint8_t* r_out) {
   const EcInfo* gi = ec_info(group);
   if (!gi) return fail(ctx, MPVSS_E_UNSUPPORTED, "ec_deal: unknown group");
-  if (n == 0 || !coeffs_host || !positions_host || !pubkeys_host || !witnesses_host || !y_out || !r_out || t == 0 || t > 0x7fffffff ||
-      n > 0x7fffffff)
+  if (n == 0 || !coeffs_host || !positions_host || (!pubkeys_host && !keyset) || !witnesses_host || !y_out || !r_out || t == 0 ||
+      t > 0x7fffffff || n > 0x7fffffff)
     return fail(ctx, MPVSS_E_INVALID, "ec_deal: bad argument (t >= 1, 1 <= n < 2^31)");
   if (t > n) return fail(ctx, MPVSS_E_INVALID, "ec_deal: threshold > number of public keys (participant.rs:1100)");
   HIPCHK(ctx, hipSetDevice(ctx->device));
@@ -1000,21 +1052,22 @@ extern "C" int mpvss_ec_deal(mpvss_ctx* ctx, int group, const uint8_t* coeffs_ho
   const auto t_d0 = std::chrono::steady_clock::now();
   double t_marks[4] = {0, 0, 0, 0};
   auto dmark = [&](int k) { t_marks[k] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_d0).count(); };
-  RET_IF(ensure(ctx, d.keys, n * L));
+  if (!keyset) RET_IF(ensure(ctx, d.keys, n * L));
   for (DevBuf* b : {&d.p, &d.w, &d.r}) RET_IF(ensure(ctx, *b, n * 32));
   RET_IF(ensure(ctx, d.pos, n * 8));
   RET_IF(ensure(ctx, d.coef, t * 32));
   RET_IF(ensure(ctx, d.c, 32));
   HIPCHK(ctx, hipMemcpyAsync(d.coef.p, coeffs_host, t * 32, hipMemcpyHostToDevice, ctx->stream));
-  HIPCHK(ctx, hipMemcpyAsync(d.keys.p, pubkeys_host, n * L, hipMemcpyHostToDevice, ctx->stream));
+  if (!keyset) HIPCHK(ctx, hipMemcpyAsync(d.keys.p, pubkeys_host, n * L, hipMemcpyHostToDevice, ctx->stream));
   HIPCHK(ctx, hipMemcpyAsync(d.w.p, witnesses_host, n * 32, hipMemcpyHostToDevice, ctx->stream));
   HIPCHK(ctx, hipMemcpyAsync(d.pos.p, positions_host, n * 8, hipMemcpyHostToDevice, ctx->stream));
   HIPCHK(ctx, hipStreamSynchronize(ctx->stream));            // the block's own streams read them next
   dmark(0);
   const EcDealPoly poly{nullptr, t, (const int64_t*)d.pos.p, (uint8_t*)d.p.p, (const uint8_t*)d.coef.p};
   RET_IF(wait_for_room(ctx, lk));
-  RET_IF(ec_distribute_compute_locked(ctx, group, MPVSS_DEVICE, nullptr, 0, nullptr, (const uint8_t*)d.keys.p, (const uint8_t*)d.p.p,
-                                      (const uint8_t*)d.w.p, n, nullptr, nullptr, nullptr, nullptr, &poly));
+  RET_IF(ec_distribute_compute_locked(ctx, group, MPVSS_DEVICE, nullptr, 0, nullptr, keyset ? nullptr : (const uint8_t*)d.keys.p,
+                                      (const uint8_t*)d.p.p, (const uint8_t*)d.w.p, n, nullptr, nullptr, nullptr, nullptr, &poly, keyset,
+                                      key_offset));
   const unsigned long long blk = ctx->own_last(1);
   dmark(1);
   uint8_t state[MPVSS_TRANSCRIPT_STATE_BYTES];
@@ -1041,6 +1094,212 @@ extern "C" int mpvss_ec_deal(mpvss_ctx* ctx, int group, const uint8_t* coeffs_ho
             "(pipeline: wait %.1f, hash %.1f)\n", group, n, t, t_marks[0], t_marks[1] - t_marks[0], t_marks[2] - t_marks[1], t_marks[3] - t_marks[2],
             ctx->pstats.wait_ms, ctx->pstats.hash_ms);
   return MPVSS_OK;
+}
+}  // namespace
+
+extern "C" int mpvss_ec_deal(mpvss_ctx* ctx, int group, const uint8_t* coeffs_host, size_t t, const int64_t* positions_host,
+                             const uint8_t* pubkeys_host, const uint8_t* witnesses_host, size_t n, uint8_t* x_out, uint8_t* y_out,
+                             uint8_t* a1_out, uint8_t* a2_out, uint8_t* digest32_out, uint8_t* challenge_out32, uint8_t* r_out) {
+  if (!ctx) return MPVSS_E_INVALID;
+  std::unique_lock<std::mutex> lk(ctx->mu);
+  return ec_deal_locked(ctx, lk, group, coeffs_host, t, positions_host, pubkeys_host, nullptr, 0, witnesses_host, n, x_out, y_out, a1_out,
+                        a2_out, digest32_out, challenge_out32, r_out);
+}
+
+// =====================================================================================================================
+// Key sets of a curve group (DESIGN section 13, "Key sets, curve groups"): the per-key combs of long-lived public keys, built
+// once, and the calls that multiply those keys over them -- Y_i = P(i) y_i and a2_i = w_i y_i of the dealer, and the stand-alone
+// multiples.  A set is explicit: the caller built it and names it, so nothing here decides by a threshold.
+// =====================================================================================================================
+extern "C" size_t mpvss_ec_keyset_bytes_per_key(int group) {
+  return ec_info(group) ? ec_keyset_row_words(group) * 4 + EC_KEYSET_MARK_BYTES : 0;
+}
+
+extern "C" size_t mpvss_ec_keyset_bytes(const mpvss_ec_keyset* ks) {
+  return ks ? ks->n * (ec_keyset_row_words(ks->group) * 4 + EC_KEYSET_MARK_BYTES) : 0;
+}
+
+extern "C" int mpvss_ec_keyset_create(mpvss_ctx* ctx, int group, int space, const uint8_t* pubkeys, size_t n, mpvss_ec_keyset** out) {
+  if (out) *out = nullptr;
+  EC_PROLOGUE("ec_keyset_create");
+  if (!out || !pubkeys || n == 0 || n > 0x7fffffff) return fail(ctx, MPVSS_E_INVALID, "ec_keyset_create: bad argument (n >= 1)");
+  mpvss_ec_keyset* ks = new (std::nothrow) mpvss_ec_keyset();
+  if (!ks) return fail(ctx, MPVSS_E_NOMEM, "ec_keyset_create: no memory for the handle");
+  ks->ctx = ctx;
+  ks->group = group;
+  ks->n = n;
+  const int rc = [&]() -> int {
+    const size_t row_words = ec_keyset_row_words(group);
+    hipError_t e = hipMalloc((void**)&ks->rows, n * row_words * 4);
+    if (e == hipSuccess) e = hipMalloc((void**)&ks->marks, n * EC_KEYSET_MARK_BYTES);
+    if (e != hipSuccess) {
+      (void)hipGetLastError();       // the runtime's last-error slot is sticky: the next launcher must not see this
+      return fail(ctx, MPVSS_E_NOMEM, "ec_keyset_create: hipMalloc(rows)", e);
+    }
+    // a chunk's launches work on at most 2^16 keys (and never more than MPVSS_MAX_CHUNK): keys x 65 windows fits the
+    // launcher's int with room, and the staging buffer of host keys stays at 2 MB
+    const size_t step = std::min(MAX_CHUNK, (size_t)1 << 16);
+    RET_IF(ensure(ctx, w.ok, std::max(step, (size_t)4096)));
+    std::vector<uint8_t> okh(std::min(step, n));
+    for (size_t off = 0; off < n; off += step) {
+      const size_t cnt = std::min(n - off, step);
+      const void* dk;
+      RET_IF(stage_in(ctx, space, pubkeys + off * gi->enc, cnt * gi->enc, w.a, &dk));
+      TIMED_LAUNCH(ctx, 2, ec_launch_keyset_build(group, (const uint8_t*)dk, (int)cnt, ks->rows + off * row_words, (uint8_t*)w.ok.p,
+                                                  ks->marks + off, ctx->stream));
+      // the chunk's validity flags; the wait also frees the staging buffer for the next chunk
+      HIPCHK(ctx, hipMemcpyAsync(okh.data(), w.ok.p, cnt, hipMemcpyDeviceToHost, ctx->stream));
+      HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+      for (size_t i = 0; i < cnt; ++i)
+        if (!okh[i]) return ec_report_bad_element(ctx, "ec_keyset_create: public keys", off + i);      // chunks in order: the smallest bad index
+    }
+    return spans_collect(ctx);
+  }();
+  if (rc != MPVSS_OK) {
+    (void)hipStreamSynchronize(ctx->stream);
+    if (ks->rows) (void)hipFree(ks->rows);
+    if (ks->marks) (void)hipFree(ks->marks);
+    delete ks;
+    return rc;
+  }
+  ctx->ec_ks_keys_built += n;
+  *out = ks;
+  return MPVSS_OK;
+}
+
+// A block enqueued by mpvss_ec_deal_compute_keyset may still read the rows: every stream of the set's context is drained first.
+extern "C" void mpvss_ec_keyset_destroy(mpvss_ctx* ctx, mpvss_ec_keyset* ks) {
+  if (!ks) return;
+  mpvss_ctx* const owner = ks->ctx;          // the set is freed on its own context's device whichever context is named
+  (void)ctx;
+  (void)mpvss_ctx_synchronize(owner);
+  std::lock_guard<std::mutex> lk(owner->mu);
+  if (hipSetDevice(owner->device) == hipSuccess) {
+    if (ks->rows) (void)hipFree(ks->rows);
+    if (ks->marks) (void)hipFree(ks->marks);
+  }
+  delete ks;
+}
+
+extern "C" int mpvss_ec_keyset_stats(mpvss_ctx* ctx, unsigned long long* keys_built, unsigned long long* powers_from_rows) {
+  if (!ctx) return MPVSS_E_INVALID;
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  if (keys_built) *keys_built = ctx->ec_ks_keys_built;
+  if (powers_from_rows) *powers_from_rows = ctx->ec_ks_powers;
+  return MPVSS_OK;
+}
+
+extern "C" int mpvss_ec_keyset_twin_exp(mpvss_ctx* ctx, int group, int space, const mpvss_ec_keyset* keyset, size_t key_offset,
+                                        const uint8_t* e1, const uint8_t* e2, size_t n, uint8_t* out1, uint8_t* out2) {
+  EC_PROLOGUE("ec_keyset_twin_exp");
+  if (const char* why = ec_keyset_refusal(ctx, group, keyset, key_offset, n)) return fail(ctx, MPVSS_E_INVALID, why);
+  if (n == 0) return MPVSS_OK;
+  if (!e1 || !out1 || (e2 == nullptr) != (out2 == nullptr) || n > 0x7fffffff)
+    return fail(ctx, MPVSS_E_INVALID, "ec_keyset_twin_exp: bad argument (e2 and out2 are given together)");
+  RET_IF(ec_check_scalars(ctx, gi, space, e1, n, "ec_keyset_twin_exp e1"));
+  if (e2) RET_IF(ec_check_scalars(ctx, gi, space, e2, n, "ec_keyset_twin_exp e2"));
+  const size_t L = gi->enc, pw = (size_t)ec_point_words(group);
+  // chunks of at most MPVSS_MAX_CHUNK shares, as the run-time groups' calls chunk: the workspace stays bounded whatever n is
+  const size_t step = MAX_CHUNK;
+  for (size_t off = 0; off < n; off += step) {
+    const size_t cnt = std::min(n - off, step);
+    const void *d1, *d2 = nullptr;
+    RET_IF(stage_in(ctx, space, e1 + off * 32, cnt * 32, w.d, &d1));
+    if (e2) RET_IF(stage_in(ctx, space, e2 + off * 32, cnt * 32, w.e, &d2));
+    uint8_t *o1 = out1 + off * L, *o2 = e2 ? out2 + off * L : nullptr;
+    if (space == MPVSS_HOST) {
+      RET_IF(ensure(ctx, w.o1, cnt * L)); o1 = (uint8_t*)w.o1.p;
+      if (e2) { RET_IF(ensure(ctx, w.o2, cnt * L)); o2 = (uint8_t*)w.o2.p; }
+    }
+    RET_IF(ensure(ctx, w.p1, cnt * pw * 4));
+    if (e2) RET_IF(ensure(ctx, w.p2, cnt * pw * 4));
+    RET_IF(ec_keyset_walk(ctx, keyset, key_offset + off, (const uint8_t*)d1, (const uint8_t*)d2, cnt, (uint32_t*)w.p1.p,
+                          e2 ? (uint32_t*)w.p2.p : nullptr));
+    TIMED_LAUNCH(ctx, 3, ec_launch_encode(group, (const uint32_t*)w.p1.p, (int)cnt, o1, ctx->stream));
+    if (e2) TIMED_LAUNCH(ctx, 3, ec_launch_encode(group, (const uint32_t*)w.p2.p, (int)cnt, o2, ctx->stream));
+    if (space == MPVSS_HOST) {
+      RET_IF(copy_out(ctx, space, out1 + off * L, o1, cnt * L));
+      if (e2) RET_IF(copy_out(ctx, space, out2 + off * L, o2, cnt * L));
+    }
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));        // the staging buffers are reused by the next chunk
+  }
+  RET_IF(spans_collect(ctx));
+  return MPVSS_OK;
+}
+
+extern "C" int mpvss_ec_keyset_dual_exp(mpvss_ctx* ctx, int group, int space, const mpvss_ec_keyset* keyset, size_t key_offset,
+                                        const uint8_t* e1, const uint8_t* h2, const uint8_t* e2, int e2_per_share, size_t n,
+                                        uint8_t* out) {
+  EC_PROLOGUE("ec_keyset_dual_exp");
+  if (const char* why = ec_keyset_refusal(ctx, group, keyset, key_offset, n)) return fail(ctx, MPVSS_E_INVALID, why);
+  if (n == 0) return MPVSS_OK;
+  if (!e1 || !out || (h2 && !e2) || n > 0x7fffffff) return fail(ctx, MPVSS_E_INVALID, "ec_keyset_dual_exp: bad argument");
+  RET_IF(ec_check_scalars(ctx, gi, space, e1, n, "ec_keyset_dual_exp e1"));
+  if (h2) RET_IF(ec_check_scalars(ctx, gi, e2_per_share ? space : MPVSS_HOST, e2, e2_per_share ? n : 1, "ec_keyset_dual_exp e2"));
+  const size_t L = gi->enc, pw = (size_t)ec_point_words(group);
+  const void* dshared = nullptr;
+  if (h2 && !e2_per_share) RET_IF(stage_in(ctx, MPVSS_HOST, e2, 32, w.chal, &dshared));      // host bytes, as c of ec_dleq_commitments
+  const size_t step = MAX_CHUNK;
+  RET_IF(ensure(ctx, w.ok, std::max(std::min(n, step), (size_t)4096)));
+  for (size_t off = 0; off < n; off += step) {
+    const size_t cnt = std::min(n - off, step);
+    const void *d1, *dh = nullptr, *d2 = dshared;
+    RET_IF(stage_in(ctx, space, e1 + off * 32, cnt * 32, w.d, &d1));
+    if (h2) RET_IF(stage_in(ctx, space, h2 + off * L, cnt * L, w.c, &dh));
+    if (h2 && e2_per_share) RET_IF(stage_in(ctx, space, e2 + off * 32, cnt * 32, w.e, &d2));
+    uint8_t* o = out + off * L;
+    if (space == MPVSS_HOST) { RET_IF(ensure(ctx, w.o1, cnt * L)); o = (uint8_t*)w.o1.p; }
+    RET_IF(ensure(ctx, w.p1, cnt * pw * 4));
+    RET_IF(ec_keyset_walk(ctx, keyset, key_offset + off, (const uint8_t*)d1, nullptr, cnt, (uint32_t*)w.p1.p, nullptr));
+    if (h2) {
+      // e2 * h2 by the one-table window kernel (the result stays in internal coordinates), then one addition
+      EcBase bh;
+      bh.enc = (const uint8_t*)dh;
+      bh.enc_stride = L;
+      RET_IF(ec_dual(ctx, gi, bh, (const uint8_t*)d2, e2_per_share ? 32 : 0, nullptr, nullptr, 0, cnt, w.tab1, w.tab2, w.p2, nullptr,
+                     (uint8_t*)w.ok.p, nullptr));
+      LAUNCHCHK(ctx, ec_launch_add_pts(group, (const uint32_t*)w.p1.p, (const uint32_t*)w.p2.p, (int)cnt, (uint32_t*)w.p1.p, ctx->stream));
+    }
+    TIMED_LAUNCH(ctx, 3, ec_launch_encode(group, (const uint32_t*)w.p1.p, (int)cnt, o, ctx->stream));
+    if (space == MPVSS_HOST) RET_IF(copy_out(ctx, space, out + off * L, o, cnt * L));
+    if (h2) {
+      std::vector<uint8_t> okh(cnt);
+      HIPCHK(ctx, hipMemcpyAsync(okh.data(), w.ok.p, cnt, hipMemcpyDeviceToHost, ctx->stream));
+      HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+      for (size_t i = 0; i < cnt; ++i)
+        if (!okh[i]) return ec_report_bad_element(ctx, "ec_keyset_dual_exp h2", off + i);
+    } else {
+      HIPCHK(ctx, hipStreamSynchronize(ctx->stream));      // the staging buffers are reused by the next chunk
+    }
+  }
+  RET_IF(spans_collect(ctx));
+  return MPVSS_OK;
+}
+
+extern "C" int mpvss_ec_deal_compute_keyset(mpvss_ctx* ctx, int group, const uint8_t* coeffs_host, size_t t, const int64_t* positions_dev,
+                                            const mpvss_ec_keyset* keyset, size_t key_offset, const uint8_t* witnesses_dev, size_t n,
+                                            uint8_t* p_dev_out, uint8_t* x_dev_out, uint8_t* y_dev_out, uint8_t* a1_dev_out,
+                                            uint8_t* a2_dev_out) {
+  if (!ctx) return MPVSS_E_INVALID;
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  if (!ec_info(group)) return fail(ctx, MPVSS_E_UNSUPPORTED, "ec_deal_compute_keyset: unknown group");
+  if (const char* why = ec_keyset_refusal(ctx, group, keyset, key_offset, n)) return fail(ctx, MPVSS_E_INVALID, why);
+  if (n == 0) return fail(ctx, MPVSS_E_INVALID, "ec_deal_compute_keyset: no shares");
+  const EcDealPoly poly{coeffs_host, t, positions_dev, p_dev_out};
+  return ec_distribute_compute_locked(ctx, group, MPVSS_DEVICE, nullptr, 0, nullptr, nullptr, p_dev_out, witnesses_dev, n, x_dev_out,
+                                      y_dev_out, a1_dev_out, a2_dev_out, &poly, keyset, key_offset);
+}
+
+extern "C" int mpvss_ec_deal_keyset(mpvss_ctx* ctx, int group, const uint8_t* coeffs_host, size_t t, const int64_t* positions_host,
+                                    const mpvss_ec_keyset* keyset, size_t key_offset, const uint8_t* witnesses_host, size_t n,
+                                    uint8_t* x_out, uint8_t* y_out, uint8_t* a1_out, uint8_t* a2_out, uint8_t* digest32_out,
+                                    uint8_t* challenge_out32, uint8_t* r_out) {
+  if (!ctx) return MPVSS_E_INVALID;
+  std::unique_lock<std::mutex> lk(ctx->mu);
+  if (!ec_info(group)) return fail(ctx, MPVSS_E_UNSUPPORTED, "ec_deal_keyset: unknown group");
+  if (const char* why = ec_keyset_refusal(ctx, group, keyset, key_offset, n)) return fail(ctx, MPVSS_E_INVALID, why);
+  return ec_deal_locked(ctx, lk, group, coeffs_host, t, positions_host, nullptr, keyset, key_offset, witnesses_host, n, x_out, y_out, a1_out,
+                        a2_out, digest32_out, challenge_out32, r_out);
 }
 
 // a block of a curve group taken by mpvss_block_claim (several threads absorb -- wait for and hash -- blocks side by side and each

@@ -78,6 +78,13 @@ int ec_launch_sum_segments(int group, const uint32_t* pts, const uint32_t* segs,
 /* dst[segs[2 b] * len ..] = the segs[2 b + 1] * len bytes at src[b] (src: `count` device pointers in device memory) */
 int ec_launch_gather_segments(const uint8_t* const* src, const uint32_t* segs, int count, uint32_t len, uint8_t* dst, hipStream_t s);
 int ec_launch_encode_gated(int group, const uint32_t* pts, int count, uint8_t* enc, const int* gate, hipStream_t s);
+/* key sets (ec_keyset_kernels.hip): rows [count][65][8][packed affine words] = (i + 1) 16^w y of `count` encoded keys, ok[x] =
+ * the key decodes, marks[x] = it is the identity (count * 65 must fit an int); the walk: out1[x] = k1[x] y_x and, k2 != null,
+ * out2[x] = k2[x] y_x in internal coordinates, rows / marks those of the first key, scalars 32 bytes apart */
+size_t ec_keyset_row_words(int group);
+int ec_launch_keyset_build(int group, const uint8_t* enc, int count, uint32_t* rows, uint8_t* ok, uint8_t* marks, hipStream_t s);
+int ec_launch_keyset_walk(int group, const uint32_t* rows, const uint8_t* marks, const uint8_t* k1, const uint8_t* k2, int count,
+                          uint32_t* out1, uint32_t* out2, hipStream_t s);
 #ifdef __cplusplus
 }
 #endif

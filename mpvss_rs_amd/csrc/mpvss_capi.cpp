@@ -337,6 +337,7 @@ struct mpvss_ctx {
   // blocks whose X went through the forward-difference path / of those, blocks that fell back to Horner's rule on
   // the device (positions not consecutive, an X that is 0 mod q, a pipeline stage that gave up)
   unsigned long long fd_blocks = 0, fd_fallbacks = 0;
+  unsigned long long ec_ks_keys_built = 0, ec_ks_powers = 0;     // mpvss_ec_keyset_stats
   DevBuf ec_comb[2];             // fixed-base combs of the curve groups' generators (built on first use)
   bool ec_comb_ready[2] = {false, false};
   // host-side accounting of the block pipeline (mpvss_pipeline_stats_get): sums over absorbed blocks

@@ -35,6 +35,11 @@ pub struct mpvss_modp_group {
 pub struct mpvss_modp_group_keyset {
     _private: [u8; 0],
 }
+/// the per-key combs of registered public keys of a curve group (mpvss_ec_keyset_create): owned by one context
+#[repr(C)]
+pub struct mpvss_ec_keyset {
+    _private: [u8; 0],
+}
 #[repr(C)]
 pub struct mpvss_modp_box {
     pub commitments: *const u8,
@@ -238,6 +243,25 @@ unsafe extern "C" {
     pub fn mpvss_ec_deal(ctx: *mut mpvss_ctx, group: c_int, coeffs_host: *const u8, t: usize, positions_host: *const i64,
                          pubkeys_host: *const u8, witnesses_host: *const u8, n: usize, x_out: *mut u8, y_out: *mut u8,
                          a1_out: *mut u8, a2_out: *mut u8, digest32_out: *mut u8, challenge_out32: *mut u8, r_out: *mut u8) -> c_int;
+    // ---- key sets of a curve group
+    pub fn mpvss_ec_keyset_bytes_per_key(group: c_int) -> usize;
+    pub fn mpvss_ec_keyset_create(ctx: *mut mpvss_ctx, group: c_int, space: c_int, pubkeys: *const u8, n: usize,
+                                  out: *mut *mut mpvss_ec_keyset) -> c_int;
+    pub fn mpvss_ec_keyset_destroy(ctx: *mut mpvss_ctx, keyset: *mut mpvss_ec_keyset);
+    pub fn mpvss_ec_keyset_bytes(keyset: *const mpvss_ec_keyset) -> usize;
+    pub fn mpvss_ec_keyset_twin_exp(ctx: *mut mpvss_ctx, group: c_int, space: c_int, keyset: *const mpvss_ec_keyset, key_offset: usize,
+                                    e1: *const u8, e2: *const u8, n: usize, out1: *mut u8, out2: *mut u8) -> c_int;
+    pub fn mpvss_ec_keyset_dual_exp(ctx: *mut mpvss_ctx, group: c_int, space: c_int, keyset: *const mpvss_ec_keyset, key_offset: usize,
+                                    e1: *const u8, h2: *const u8, e2: *const u8, e2_per_share: c_int, n: usize, out: *mut u8) -> c_int;
+    pub fn mpvss_ec_deal_compute_keyset(ctx: *mut mpvss_ctx, group: c_int, coeffs_host: *const u8, t: usize, positions_dev: *const i64,
+                                        keyset: *const mpvss_ec_keyset, key_offset: usize, witnesses_dev: *const u8, n: usize,
+                                        p_dev_out: *mut u8, x_dev_out: *mut u8, y_dev_out: *mut u8, a1_dev_out: *mut u8,
+                                        a2_dev_out: *mut u8) -> c_int;
+    pub fn mpvss_ec_deal_keyset(ctx: *mut mpvss_ctx, group: c_int, coeffs_host: *const u8, t: usize, positions_host: *const i64,
+                                keyset: *const mpvss_ec_keyset, key_offset: usize, witnesses_host: *const u8, n: usize, x_out: *mut u8,
+                                y_out: *mut u8, a1_out: *mut u8, a2_out: *mut u8, digest32_out: *mut u8, challenge_out32: *mut u8,
+                                r_out: *mut u8) -> c_int;
+    pub fn mpvss_ec_keyset_stats(ctx: *mut mpvss_ctx, keys_built: *mut c_ulonglong, powers_from_rows: *mut c_ulonglong) -> c_int;
     pub fn mpvss_ec_hash_to_scalar(group: c_int, data: *const u8, len: usize, out32: *mut u8) -> c_int;
     // ---- extract_secret_share, batched
     pub fn mpvss_modp_extract_shares(ctx: *mut mpvss_ctx, space: c_int, pk: *const u8, y: *const u8, xinv: *const u8, w: *const u8, n: usize,
