@@ -79,7 +79,9 @@ struct F {
     add(r, a, b);
     carry(r);
   }
-  // r = a - b  (b limbs < 2^29 - 2^26), carried
+  // r = a - b, carried.  b[i] <= subpad(i) (2^29 - 8, limb 0 a little less: ec_consts.h), so that no limb goes below zero,
+  // and a[i] + subpad(i) - b[i] < 2^31 (carry's input); neg the same with a = 0.  Every caller (ec_curves.h, ec_quad.h,
+  // ec_keyset.h) has both a and b below 2^28 + 2^13, a sum of two products; tests/test_ec_repr_host.py goes to the bounds.
   static EC_HD void sub(Fe& r, const Fe& a, const Fe& b) {
 #pragma unroll
     for (int i = 0; i < 10; ++i) r.v[i] = a.v[i] + PrimeConsts<P>::subpad(i) - b.v[i];
@@ -90,7 +92,9 @@ struct F {
     for (int i = 0; i < 10; ++i) r.v[i] = PrimeConsts<P>::subpad(i) - a.v[i];
     carry(r);
   }
-  // r = a * k for a small constant k (< 2^6), carried
+  // r = a * k for a small constant k (< 2^6), carried.  In: ANY 32-bit limbs -- the chain is 64 bits wide, x < 63 * 2^32 + 2^12,
+  // so t <= 4032 and t * R0 < 2^26; the largest a caller feeds is OctSecp::add's (2^27 + 2^12) + 2 (2^29 - 8) > 2^30 with
+  // k <= 21.  Out: v[0] < 2^27, v[1] < 2^26 + 2^22, others < 2^26.
   static EC_HD void mul_small(Fe& r, const Fe& a, u32 k) {
     u64 c = 0;
 #pragma unroll
@@ -165,7 +169,10 @@ struct F {
     reduce_columns(r, c);
   }
 
-  // r = a * b + c * d with one reduction (limbs up to 2^28.5: 20 products of 2^57 fit a 64-bit column with room for the folds)
+  // r = a * b + c * d with one reduction.  With limb bounds A, B, C, D of the four factors: A B + C D <= (2^64 - 2^43) / 10
+  // ~ 2^60.67 -- a column holds at most 10 products of each pair, and the folds of reduce_columns add less than 2^43 to it
+  // (pieces < 2^26 times R0 < 2^14 or R1 <= 2^10, six of them and the wrap-around).  All four below 2^29.8 is enough;
+  // QuadSecp::add's largest pair is (2^27 + 2^29) 2^28 + 2^27 2^27 ~ 2^57.4.  Out: the class of reduce_columns.
   static EC_HD void mul2(Fe& r, const Fe& a, const Fe& b, const Fe& c2, const Fe& d) {
     u64 c[20];
 #pragma unroll

@@ -29,7 +29,8 @@
 // additions were inlined one after the other.  So (a) everything here is branch-free, lane-dependent choices are selects, and
 // (b) the operand of every cross-lane move passes through an empty `asm volatile` first, which makes it opaque.
 // tests: tests/ec_quad_unit.hip through tests/test_gpu_ec_fd.py (addition, negation + addition against the one-lane formulas:
-// doublings, P + (-P), the identity on either side); the stepping and table pipelines against Horner's rule and the oracle.
+// doublings, P + (-P), the identity on either side); the stepping and table pipelines against Horner's rule and the oracle;
+// its raw mode through tests/test_gpu_ec_quad_repr.py (operands with saturated limbs in every position, non-canonical identities).
 #pragma once
 #include "ec_curves.h"
 
@@ -190,9 +191,9 @@ struct QuadSecp {
     fe_quad_perm<1, 2, 0, 1>(mn, m);
     Fp::add(zz, m, mn);
 #pragma unroll
-    for (int i = 0; i < 10; ++i) mm.v[i] = m.v[i] + PrimeConsts<PrimeSecp>::subpad(i) - mn.v[i];     // (a factor of mul2: no carry, < 2^30)
+    for (int i = 0; i < 10; ++i) mm.v[i] = m.v[i] + PrimeConsts<PrimeSecp>::subpad(i) - mn.v[i];     // (a factor of mul2: no carry, < 2^27 + 2^29; its partner zz < 2^28, the other pair < 2^27 each: within mul2's A B + C D budget)
 #pragma unroll
-    for (int i = 0; i < 10; ++i) ncrk.v[i] = PrimeConsts<PrimeSecp>::subpad(i) - crk.v[i];      // (no carry: a factor of mul2, limbs < 2^30)
+    for (int i = 0; i < 10; ++i) ncrk.v[i] = PrimeConsts<PrimeSecp>::subpad(i) - crk.v[i];      // (no carry: a factor of mul2, limbs < 2^29; its partner crk < 2^27)
     fe_select(s1, mm, m, c == 1);
     fe_select(s1, ncrk, s1, c == 2);
     // publish S0 = crk, S1, S2 = zz; fetch A, B, C, D by (lane of the quad, slot)
@@ -330,7 +331,7 @@ struct OctSecp {
       for (int i = 0; i < 10; ++i) {
         const u32 pad = PrimeConsts<PrimeSecp>::subpad(i);
         const u32 bt = negB ? pad - B.v[i] : B.v[i];
-        x.v[i] = A.v[i] + (bt & mB) + ((pad - Cc.v[i]) & mC);      // < 2^27.1 + 2^29 + 2^29
+        x.v[i] = A.v[i] + (bt & mB) + ((pad - Cc.v[i]) & mC);      // < 2^27.1 + 2^29 + 2^29: above 2^30, mul_small takes any 32-bit limb
       }
     }
     Fp::mul_small(mid, x, K);

@@ -48,8 +48,9 @@ def load_shim():
     """tests/ec_host_shim.cpp as a shared library (built as tests/test_ec_host.py builds it)"""
     lib = os.path.join(HERE, "_build", "libec_host.so")
     src = os.path.join(HERE, "ec_host_shim.cpp")
-    deps = [src] + [os.path.join(HERE, "..", "mpvss_rs_amd", "csrc", f)
-                    for f in ("ec_field.h", "ec_curves.h", "ec_consts.h", "ec_glv.h", "ec_scalar.h")]
+    deps = [src, os.path.join(HERE, "ec_repr_ops.h")] + \
+        [os.path.join(HERE, "..", "mpvss_rs_amd", "csrc", f)
+         for f in ("ec_field.h", "ec_curves.h", "ec_consts.h", "ec_glv.h", "ec_scalar.h", "ec_keyset.h")]
     os.makedirs(os.path.dirname(lib), exist_ok=True)
     if not os.path.exists(lib) or any(os.path.getmtime(d) > os.path.getmtime(lib) for d in deps):
         tmp = "%s.%d" % (lib, os.getpid())

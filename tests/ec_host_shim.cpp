@@ -2,6 +2,7 @@
 // Test infrastructure: compiled by tests/test_ec_host.py with g++, never shipped.
 #include "../mpvss_rs_amd/csrc/ec_curves.h"
 #include "../mpvss_rs_amd/csrc/ec_glv.h"
+#include "ec_repr_ops.h"
 
 using namespace ec;
 
@@ -127,6 +128,31 @@ static int t_dual_win_glv(const uint8_t* p1, const uint8_t* k1, const uint8_t* p
   return 0;
 }
 
+template <class Fp>
+static uint32_t t_fe_repr(int op, const uint32_t* a10, const uint32_t* b10, const uint32_t* c10, const uint32_t* d10,
+                          uint32_t k, uint32_t* limbs10, uint8_t* out32) {
+  Fe a, b, c, d, r;
+  for (int i = 0; i < 10; ++i) { a.v[i] = a10[i]; b.v[i] = b10[i]; c.v[i] = c10[i]; d.v[i] = d10[i]; }
+  if (op == 8) return Fp::is_zero(a);
+  if (op == 9) return Fp::equal(a, b);
+  if (op == 10) return Fp::is_odd(a);
+  switch (op) {
+    case 0: Fp::sub(r, a, b); break;
+    case 1: Fp::neg(r, a); break;
+    case 2: Fp::add(r, a, b); Fp::carry(r); break;
+    case 3: Fp::addc(r, a, b); break;
+    case 4: r = a; Fp::carry(r); break;
+    case 5: Fp::mul_small(r, a, k); break;
+    case 6: Fp::mul2(r, a, b, c, d); break;
+    default: r = a; Fp::canon(r); break;
+  }
+  uint32_t top = 0;
+  for (int i = 0; i < 10; ++i) { limbs10[i] = r.v[i]; top = r.v[i] > top ? r.v[i] : top; }
+  if (op != 7) Fp::canon(r);
+  Fp::to_le32(out32, r);
+  return top;
+}
+
 extern "C" {
 int ec_dual_win_glv(const uint8_t* p1, const uint8_t* k1, const uint8_t* p2, const uint8_t* k2, uint8_t* out) {
   return t_dual_win_glv(p1, k1, p2, k2, out);
@@ -210,6 +236,25 @@ uint32_t fe_limb_op(int curve, int op, const uint32_t* a10, const uint32_t* b10,
     Fp::canon(r); Fp::to_le32(out, r);
   }
   return top;
+}
+// every other field operation on RAW limbs (tests/test_ec_repr_host.py; the operands are at the stated limb bounds):
+//   0 sub(a, b)  1 neg(a)  2 add(a, b) then carry  3 addc(a, b)  4 carry(a)  5 mul_small(a, k)  6 mul2(a, b, c, d)
+//   7 canon(a)   8 is_zero(a)  9 equal(a, b)  10 is_odd(a)
+// ops 0..6: the result's limbs as the operation leaves them -> limbs10, its canonical bytes -> out32, returns the largest limb;
+// op 7: the limbs canon leaves -> limbs10 and those very limbs through to_le32 -> out32;  ops 8..10: returns the boolean
+uint32_t fe_repr_op(int curve, int op, const uint32_t* a10, const uint32_t* b10, const uint32_t* c10, const uint32_t* d10,
+                    uint32_t k, uint32_t* limbs10, uint8_t* out32) {
+  return curve == 0 ? t_fe_repr<F<PrimeSecp>>(op, a10, b10, c10, d10, k, limbs10, out32)
+                    : t_fe_repr<F<PrimeEd>>(op, a10, b10, c10, d10, k, limbs10, out32);
+}
+// the one-lane point operations on raw limb words (tests/ec_repr_ops.h): REPR_SLOTS encodings per pair
+int ec_repr_pair(int curve, const uint32_t* p, const uint32_t* q, uint8_t* out) {
+  if (curve == 0) repr_pair<Secp>(p, q, out); else repr_pair<Ristretto>(p, q, out);
+  return REPR_SLOTS;
+}
+int secp_repr_batch8(const uint32_t* pts, uint8_t* out) {
+  repr_batch8(pts, out);
+  return 0;
 }
 int fe_op(int curve, int op, const uint8_t* a32, const uint8_t* b32, uint8_t* out) {
   Fe a, b, r;

@@ -18,7 +18,8 @@ LIB = os.path.join(HERE, "_build", "libec_host.so")
 def shim():
     os.makedirs(os.path.dirname(LIB), exist_ok=True)
     src = os.path.join(HERE, "ec_host_shim.cpp")
-    deps = [src] + [os.path.join(HERE, "..", "mpvss_rs_amd", "csrc", f) for f in ("ec_field.h", "ec_curves.h", "ec_consts.h", "ec_glv.h", "ec_scalar.h")]
+    deps = [src, os.path.join(HERE, "ec_repr_ops.h")] + \
+        [os.path.join(HERE, "..", "mpvss_rs_amd", "csrc", f) for f in ("ec_field.h", "ec_curves.h", "ec_consts.h", "ec_glv.h", "ec_scalar.h", "ec_keyset.h")]
     if not os.path.exists(LIB) or any(os.path.getmtime(d) > os.path.getmtime(LIB) for d in deps):
         subprocess.check_call(["g++", "-O1", "-std=c++17", "-shared", "-fPIC", src, "-o", LIB])
     return C.CDLL(LIB)
