@@ -1205,6 +1205,8 @@ int pair_mask();     // which kernels take the pair layout (below)
 // X path 68.5 -> 47.7 ms at (65536, 256), profiles/r06_commit_eval_alone.txt).  NOT inside a verifier's block: there the box is
 // bound by the sum of its work, the wider layout costs 1.3x the issue slots per seed, and the call gets slower (148 against 122 ms,
 // profiles/r06_lone_box_schedule_ab.txt).
+// (The t first-level seeds of a box AMONG OTHERS take the row layout whatever x_alone says: there the box is bound by the length of its
+// X path's chain, below.)
 // direct: Horner for every share whatever the positions are (a one-box call of up to ROW_MAX_NUMBERS shares, below).
 int eval_x(mpvss_ctx* ctx, size_t t, const int64_t* dpos, const int64_t* hpos, size_t cnt, uint8_t* dX, size_t boxes = 1,
            size_t box_positions = 0, bool x_alone = false, bool direct = false) {
@@ -1256,14 +1258,19 @@ int eval_x(mpvss_ctx* ctx, size_t t, const int64_t* dpos, const int64_t* hpos, s
   // seeds of all chains together are the S*t consecutive positions from S*w0 (Horner, and outputs at the same time).
   // The seed launch is latency-bound (2048 seeds are an eighth of a wave per SIMD), so fewer seeds would not finish
   // sooner; more chains shorten the stepping but cost Horner work.
-  // measured optima on MI355X: chains of about 8192 members (n=65536: 8 chains for t = 16..256), fewer when the
+  // measured optima on MI355X: chains of about 8192 members (raised to 16 chains below for t <= 256), fewer when the
   // seeds are dear (t = 512: 4), never longer than 16384 members (n=131072, t=1024: 8)
   int S = (int)std::max<size_t>(std::max<size_t>(std::min<size_t>(2048 / t, cnt / 8192), cnt / 16384), 4);
   // a call that has the GPU to itself: more, shorter chains -- the extra seeds are one wide launch on an idle chip, the
   // stepping (the serial part) shrinks in proportion
+  // ... and a box among others of at least 65536 shares: its X path is a chain of dependent launches that holds one hardware queue
+  // from its first kernel to a1, and the boxes in flight share GPU_MAX_HW_QUEUES of them, so a box cannot come sooner than its
+  // chain's span over the queues (profiles/x_chain_trace_parent.txt: 4 queues, 4 X paths open, 207 ms / 3.4 = 61 ms per box).
+  // With the stride-1 seeding chain stepping both ways (below) 16 chains are 2 175 + 2 175 serial steps instead of 8 chains'
+  // 1 151 + 4 223, for about 25 products per share more (profiles/x_chain_ab.txt).
   const int S_pipelined = S;
   constexpr int lone_chains = 16;     // measured: 8 -> 109 ms per box, 16 -> 96.5, 32 -> 104, 64 -> 115
-  if (lone_chains > S && !ctx->busy_with_others() && t <= 256) S = lone_chains;
+  if (lone_chains > S && (!ctx->busy_with_others() || cnt >= 65536) && t <= 256) S = lone_chains;
   const int s_max = (int)(cnt / (4 * t));      // cnt >= 16 t, so at least 4
   if (S > s_max) S = s_max;
   if (S < 1) S = 1;
@@ -1272,7 +1279,7 @@ int eval_x(mpvss_ctx* ctx, size_t t, const int64_t* dpos, const int64_t* hpos, s
   const size_t seed0 = (size_t)S * w0;    // index of the first seed position
   const int m0 = (int)(S * t);
   // Two-level seeding (MPVSS_FD_L1, default on): Horner's rule -- about 7 000 products per seed at (65536, 256) -- only
-  // for the first t of the S*t seed positions; a stride-1 forward-difference chain built from those t values steps
+  // for the middle t of the S*t seed positions; a stride-1 forward-difference chain built from those t values steps
   // through the remaining (S-1)*t seed positions at t products each.  Same values (uniqueness of the group element);
   // 180 products per share fewer at (65536, 256), for about 15 ms more latency of the box's chain.
   // tests only: one pipeline stage gives up and the flag falls -- 1 / 2: a stage of the stepping pipelines, 3: of the
@@ -1372,9 +1379,9 @@ int eval_x(mpvss_ctx* ctx, size_t t, const int64_t* dpos, const int64_t* hpos, s
   // strides from one box of the group to the next, in 32-bit words
   const size_t bx_xm = cnt * MODP_L, bx_state = (size_t)2 * m0 * MODP_L, bx_hand_t = (hand_t + hand_t1) / 4, bx_hand_s = (hand_s + hand_s1) / 4;
   // the seeds of the group's boxes side by side (one simultaneous inversion for all of them); a lone box's are already
-  auto seeds_together = [&](int per_box) -> const uint32_t* {
-    if (B == 1) return xseed;
-    if (modp_launch_gather_rows(xseed, bx_xm, (size_t)per_box * MODP_L, B, (uint32_t*)w.fd_gather.p, ctx->stream) != 0) return nullptr;
+  auto seeds_together = [&](const uint32_t* first, int per_box) -> const uint32_t* {
+    if (B == 1) return first;
+    if (modp_launch_gather_rows(first, bx_xm, (size_t)per_box * MODP_L, B, (uint32_t*)w.fd_gather.p, ctx->stream) != 0) return nullptr;
     return (const uint32_t*)w.fd_gather.p;
   };
   w.root[0].one = 1;     // pinned: the copy below is asynchronous and reads it in stream order
@@ -1385,16 +1392,25 @@ int eval_x(mpvss_ctx* ctx, size_t t, const int64_t* dpos, const int64_t* hpos, s
   HIPCHK(ctx, hipMemsetAsync(w.fd_hand_s.p, 0, boxes * (hand_s + hand_s1), ctx->stream));
   // seeds: X at the S*t positions from seed0, kept in Montgomery form
   if (two_level) {
-    LAUNCHCHK(ctx, modp_launch_commit_eval_boxes((const uint32_t*)w.cm.p, (int)t, dpos + seed0, box_positions, (int)t, B, xseed, nullptr,
-                                                 cnt, flag, 1, ctx->consts, ctx->stream));
-    const uint32_t* seeds1 = seeds_together((int)t);
+    // The t Horner positions sit in the MIDDLE of the seed window (w1 .. w1 + t - 1 of its m0), as the seeds of a strided chain
+    // sit in the middle of the chain: the stride-1 chain then steps forward and backward at once, max(m0 - 1 - w1, w1 + t - 1)
+    // serial steps instead of m0 - 1 (S = 8, t = 256: 1 151 instead of 2 047), for the t - 1 table-advancing steps of the
+    // backward pipeline (t (t - 1) products per box).  m0 == t never gets here (S > 1), and w1 == 0 would be forward only.
+    const int w1 = (m0 - (int)t) / 2;
+    uint32_t* xseed1 = xseed + (size_t)w1 * MODP_L;
+    // The t seeds are 16 waves of the quad layout whose latency is the whole cost (about 5 600 dependent operations): the row layout
+    // does an operation in 3.5 instead of 5.7 us, and its 1.3x issue slots on t seeds are 0.4 % of the box
+    // (48 -> 30 ms of the chain under load, profiles/x_chain_trace_new.txt).
+    LAUNCHCHK(ctx, modp_launch_commit_eval_row_boxes((const uint32_t*)w.cm.p, (int)t, dpos + seed0 + w1, box_positions, (int)t, B, xseed1, cnt,
+                                                     flag, 1, ctx->consts, ctx->stream, 1));
+    const uint32_t* seeds1 = seeds_together(xseed1, (int)t);
     if (!seeds1) return fail(ctx, MPVSS_E_DEVICE, "eval_x: gather launch");
     RET_IF(invert_batch(seeds1, B * (int)t, (uint32_t*)w.fd_xinv.p, &w.root[1]));
-    // one chain of stride 1 over the seed window: tables from its first t values, then m0 - 1 steps forward
-    LAUNCHCHK(ctx, modp_launch_fd_table_boxes(xseed, bx_xm, (const uint32_t*)w.fd_xinv.p, t * MODP_L, 1, (int)t, state_fwd, state_bwd,
+    // one chain of stride 1 over the seed window: tables from those t values, then both ways to the window's ends
+    LAUNCHCHK(ctx, modp_launch_fd_table_boxes(xseed1, bx_xm, (const uint32_t*)w.fd_xinv.p, t * MODP_L, 1, (int)t, state_fwd, state_bwd,
                                               bx_state, (uint32_t*)((uint8_t*)w.fd_hand_t.p + hand_t), bx_hand_t, B, flag, 0,
                                               ctx->consts, ctx->stream));
-    LAUNCHCHK(ctx, launch_step(state_fwd, state_bwd, bx_state, 1, (int)t, 0, m0, m0, xseed, bx_xm,
+    LAUNCHCHK(ctx, launch_step(state_fwd, state_bwd, bx_state, 1, (int)t, w1, m0, m0, xseed, bx_xm,
                                (uint32_t*)((uint8_t*)w.fd_hand_s.p + hand_s), bx_hand_s, inject_fault == 3 ? 1 : 0));
   } else if (x_alone && !ctx->busy_with_others()) {
     LAUNCHCHK(ctx, modp_launch_commit_eval_row_boxes((const uint32_t*)w.cm.p, (int)t, dpos + seed0, box_positions, m0, B, xseed, cnt, flag, 1,
@@ -1403,7 +1419,7 @@ int eval_x(mpvss_ctx* ctx, size_t t, const int64_t* dpos, const int64_t* hpos, s
     LAUNCHCHK(ctx, modp_launch_commit_eval_boxes((const uint32_t*)w.cm.p, (int)t, dpos + seed0, box_positions, m0, B, xseed, nullptr,
                                                  cnt, flag, 1, ctx->consts, ctx->stream));
   }
-  const uint32_t* seeds2 = seeds_together(m0);
+  const uint32_t* seeds2 = seeds_together(xseed, m0);
   if (!seeds2) return fail(ctx, MPVSS_E_DEVICE, "eval_x: gather launch");
   RET_IF(invert_batch(seeds2, B * m0, (uint32_t*)w.fd_xinv.p, &w.root[0]));
   // difference tables, stepping, conversion -- all gated on flag == 1.  Both kernels are pipelines of single-wave
