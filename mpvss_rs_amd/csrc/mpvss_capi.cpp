@@ -145,6 +145,8 @@ struct mpvss_ctx {
     hipStream_t sa = nullptr, sb = nullptr;  // stream pair: sb runs a2 beside the serial phases of the X path on sa
     hipEvent_t ev_fork = nullptr, ev_gr = nullptr;
     hipEvent_t ev_a2 = nullptr;
+    hipEvent_t ev_x = nullptr;               // block slots: recorded on sa behind the last kernel of the X path of a box among others,
+                                             // whose tail sb runs (verify_block_compute_locked)
     bool ready = false;
     std::vector<DevBuf*> all() {
       return {&in_a, &in_b, &in_c, &in_d, &in_e, &pos, &cm, &xbe, &out1, &out2, &tab1, &tab2, &tabg, &cbuf, &fd_flag,
@@ -843,6 +845,7 @@ int work_init(mpvss_ctx* ctx, mpvss_ctx::Work& w, hipStream_t main_stream) {
     // (the X path on CUs of its own -- CU-masked streams -- was measured and is 2.2x slower: profiles/r04_cu_partition_ab.txt)
     HIPCHK(ctx, hipStreamCreateWithPriority(&w.sa, hipStreamNonBlocking, ctx->prio_high));
     HIPCHK(ctx, hipStreamCreateWithPriority(&w.sb, hipStreamNonBlocking, ctx->prio_low));
+    HIPCHK(ctx, hipEventCreateWithFlags(&w.ev_x, hipEventDisableTiming));
   }
   for (hipEvent_t* e : {&w.ev_fork, &w.ev_gr})
     HIPCHK(ctx, hipEventCreateWithFlags(e, hipEventDisableTiming));
@@ -860,6 +863,7 @@ void work_destroy(mpvss_ctx::Work& w, bool owns_sa) {
   for (hipEvent_t e : {w.ev_fork, w.ev_gr})
     if (e) (void)hipEventDestroy(e);
   if (w.ev_a2) (void)hipEventDestroy(w.ev_a2);
+  if (w.ev_x) (void)hipEventDestroy(w.ev_x);
   if (w.root) (void)hipHostFree(w.root);
   if (w.sb) (void)hipStreamDestroy(w.sb);
   if (w.sa && owns_sa) (void)hipStreamDestroy(w.sa);
@@ -1731,8 +1735,10 @@ struct BlockEnqueue {
     }
     return 0;
   }
-  int commit() {
-    HIPCHK(ctx, hipEventRecord(sl.done, ctx->stream));
+  // last: the stream that everything of the block is behind (null: the slot's stream A, as every block but a verifier's box that
+  // closes on another stream has it)
+  int commit(hipStream_t last = nullptr) {
+    HIPCHK(ctx, hipEventRecord(sl.done, last ? last : ctx->stream));
     sl.busy = true;
     sl.enqueue_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     ctx->commit_head(sl);
@@ -1966,6 +1972,7 @@ int verify_block_compute_locked(mpvss_ctx* ctx, int space, const uint8_t* commit
   HIPCHK(ctx, hipMemcpyAsync(ctx->w->in_e.p, sl.work.root->challenge, EB, hipMemcpyHostToDevice, ctx->stream));
   const void* dchal = ctx->w->in_e.p;
   const int c_windows = fits_256_bits(challenge_host) ? 64 : 512;
+  hipStream_t last = nullptr;                // the stream that ended the block's last chunk: `done` goes there
   for (size_t off = 0; off < n; off += MAX_CHUNK) {
     const size_t cnt = (n - off < MAX_CHUNK) ? n - off : MAX_CHUNK;
     const int64_t* dpos;
@@ -1996,6 +2003,7 @@ int verify_block_compute_locked(mpvss_ctx* ctx, int space, const uint8_t* commit
     uint8_t* da1 = (uint8_t*)ctx->w->out1.p;
     uint8_t* da2 = (uint8_t*)ctx->w->out2.p;
     sl.work.fd_used = false;
+    hipStream_t closing = ctx->stream;       // the stream that ends this chunk: stream A, or the slot's closing stream (below)
     const int64_t* hp = space == MPVSS_HOST ? hpos + off : nullptr;
     // A one-box call of up to ROW_MAX_NUMBERS shares (BASELINE config C2 and everything the reference's tests and examples use) is the
     // latency of its chains, not work: Horner for every share ((t - 1) x 26 operations on the row layout) is shorter than the
@@ -2089,8 +2097,27 @@ int verify_block_compute_locked(mpvss_ctx* ctx, int space, const uint8_t* commit
       // row-layout seeds pay: 122.8 -> 103.5 ms per lone call, profiles/r06_lone_key_cache.txt; without key tables they lose, eval_x)
       RET_IF(eval_x(ctx, t, dpos, hp, cnt, dX, 1, 0, use_keys));
       mark(3);
+      // A box among others hands its TAIL to sb here, behind g^r: X's table, a1, the output copies and the slot's `done` need nothing
+      // of the chain, but enqueued on stream A they hold A's hardware queue -- a1's wide launch trickles in as a2 waves retire, and
+      // the ev_a2 wait stalls at the queue's head -- while the next box's Horner seeds wait behind them in that queue
+      // (profiles/closing_stream_ab.txt; a third stream of the middle priority for the tail, and from_mont moved with it, measured
+      // no better).  Nothing of this box follows ev_x on A.  A box that has the chip to itself keeps everything on A: its tail is
+      // the end of its critical path.  Workspaces that cross the two streams, and what orders each write before its read:
+      //   xbe (X)        from_mont or the gated Horner fall-back, on A     -> ev_x -> X's table and the copy of X
+      //   fd_flag        the X path's kernels, on A                        -> ev_x -> the copy of the chunk's flag
+      //   in_b (Y)       staged on A ahead of the fork                     -> ev_fork (and ev_x) -> the copy of Y
+      //   gr_m, csched, out2 (a2), tab3, out1 (a1): written and read on sb alone, in stream order
+      // The slot's next occupant: `done` is behind everything on sb, ev_x behind everything on A, the host waits for `done` before
+      // it gives the slot away, and fork_side_stream orders the occupant's sb behind its A.
+      if (ctx->busy_with_others()) {
+        closing = ctx->w->sb;
+        HIPCHK(ctx, hipEventRecord(ctx->w->ev_x, ctx->stream));
+        HIPCHK(ctx, hipStreamWaitEvent(closing, ctx->w->ev_x, 0));
+      }
+      const bool join_sb = closing != ctx->w->sb;      // (sb itself is behind its own g^r and a2)
       // a1 = g^r * X^c: once X is known only X^c and one product remain
       {
+        SwapStream sw(ctx, closing);
         const uint32_t* tx;
         if (dsched) {
           RET_IF(ensure(ctx, ctx->w->tab3, cnt * TABW * 4));
@@ -2099,7 +2126,7 @@ int verify_block_compute_locked(mpvss_ctx* ctx, int space, const uint8_t* commit
         } else {
           RET_IF(number_tables(ctx, dX, cnt, ctx->w->tab3, &tx));
         }
-        HIPCHK(ctx, hipStreamWaitEvent(ctx->stream, ctx->w->ev_gr, 0));
+        if (join_sb) HIPCHK(ctx, hipStreamWaitEvent(ctx->stream, ctx->w->ev_gr, 0));
         if (dsched && pair_a1)
           TIMED_LAUNCH(ctx, 1, modp_launch_sched_exp_mul_pair(tx, TABW, dsched, (const uint32_t*)ctx->w->gr_m.p, (int)cnt, da1, ctx->consts,
                                                               ctx->pair_tables, ctx->stream));
@@ -2111,7 +2138,7 @@ int verify_block_compute_locked(mpvss_ctx* ctx, int space, const uint8_t* commit
                                                                c_windows, (int)cnt, da1, 2, (uint32_t*)ctx->w->gr_m.p,
                                                                comb_bits_of(ctx, cg), ctx->consts, ctx->stream));
       }
-      HIPCHK(ctx, hipStreamWaitEvent(ctx->stream, ctx->w->ev_a2, 0));
+      if (join_sb) HIPCHK(ctx, hipStreamWaitEvent(closing, ctx->w->ev_a2, 0));
     } else if (ctx->w->sb) {
       // A small box, or positions that are not consecutive: a2_i = y_i^r_i * Y_i^c (dleq.rs:79-81) needs nothing of X -- it runs on
       // the slot's second stream beside X_i (participant.rs:423-434) and a1_i = g^r_i * X_i^c (dleq.rs:75-77; X's table in tab3: a2
@@ -2144,20 +2171,22 @@ int verify_block_compute_locked(mpvss_ctx* ctx, int space, const uint8_t* commit
       RET_IF(dleq_side(ctx, nullptr, (const uint8_t*)dy, (const uint8_t*)dY, (const uint8_t*)dr, (const uint8_t*)dchal,
                        0, c_windows, cnt, da2));
     }
-    HIPCHK(ctx, hipMemcpyAsync(hX + off * EB, dX, cnt * EB, hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(ctx, hipMemcpyAsync(hY + off * EB, dY, cnt * EB, hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(ctx, hipMemcpyAsync(h1 + off * EB, da1, cnt * EB, hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(ctx, hipMemcpyAsync(h2 + off * EB, da2, cnt * EB, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipMemcpyAsync(hX + off * EB, dX, cnt * EB, hipMemcpyDeviceToHost, closing));
+    HIPCHK(ctx, hipMemcpyAsync(hY + off * EB, dY, cnt * EB, hipMemcpyDeviceToHost, closing));
+    HIPCHK(ctx, hipMemcpyAsync(h1 + off * EB, da1, cnt * EB, hipMemcpyDeviceToHost, closing));
+    HIPCHK(ctx, hipMemcpyAsync(h2 + off * EB, da2, cnt * EB, hipMemcpyDeviceToHost, closing));
     if (sl.work.fd_used) {     // the device's decision for this chunk (1 = forward differences held, 0 = fell back)
       sl.fd_used = true;
       if (sl.fd_chunks < FLAGS)
-        HIPCHK(ctx, hipMemcpyAsync(hflags + sl.fd_chunks, sl.work.fd_flag.p, 4, hipMemcpyDeviceToHost, ctx->stream));
+        HIPCHK(ctx, hipMemcpyAsync(hflags + sl.fd_chunks, sl.work.fd_flag.p, 4, hipMemcpyDeviceToHost, closing));
       ++sl.fd_chunks;
     }
-    if (off + MAX_CHUNK < n) HIPCHK(ctx, hipStreamSynchronize(ctx->stream));   // device buffers are reused
+    // device buffers are reused: the closing stream is behind the chunk's work on all of the slot's streams
+    if (off + MAX_CHUNK < n) HIPCHK(ctx, hipStreamSynchronize(closing));
+    last = closing;
   }
   mark(4);
-  RET_IF(be.commit());
+  RET_IF(be.commit(last));
   if (trace_enq && sl.enqueue_ms > 3.0)
     fprintf(stderr, "[mpvss] slow enqueue %.1f ms: staging %.1f | commitments %.1f | tables+a2+g^r %.1f | X path %.1f | a1+copies %.1f | "
             "event %.1f\n", sl.enqueue_ms, marks[0], marks[1] - marks[0], marks[2] - marks[1], marks[3] - marks[2],
