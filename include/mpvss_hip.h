@@ -653,14 +653,14 @@ int mpvss_box_parse(const uint8_t* buf, size_t len, mpvss_box_view* view);
 int mpvss_box_verify_wire(mpvss_ctx* ctx, const uint8_t* buf, size_t len, int* verdict, uint8_t* digest32_out);
 
 /* ---- MODP groups of a run-time modulus (ModpGroup::init, src/groups/modp.rs:72-84) ---------------------------
- * A group handle holds an odd modulus q of at most 3072 bits -- ModpGroup::init(length).modulus() or any other -- and
+ * A group handle holds an odd modulus q of at most 4096 bits -- ModpGroup::init(length).modulus() or any other -- and
  * what the kernels need of it (Montgomery constants, the width: 5, 9 or 18 limbs of 29 bits per lane, the smallest with
- * bits(q) <= 29 * 4 * limbs - 2, or 27 for a wide handle).  Creating it is host work only (no GPU, no context); it is
+ * bits(q) <= 29 * 4 * limbs - 2, or 27 for a 384-byte handle and 36 for a 512-byte one).  Creating it is host work only (no GPU, no context); it is
  * immutable afterwards and may be used from any number of contexts and threads at once.
  * ELEMENT SIZE: every element, scalar and exponent that a mpvss_modp_group_* entry point reads or writes is a big-endian
  * value of mpvss_modp_group_elem_bytes(handle) bytes, and arrays of them have that stride: 256 (MPVSS_MODP_BYTES) for a
- * handle of mpvss_modp_group_create, 384 for a wide handle of mpvss_modp_group_create_wide (moduli of 2049 .. 3072 bits, RFC
- * 3526 group 15 among them).  Parameter names and comments below that say 256 mean that size.  Inputs need not be reduced (a value >= q gives what BigInt::modpow / (a * b) % q give, modp.rs:154-156
+ * handle of mpvss_modp_group_create; 384 (moduli of 2049 .. 3072 bits, RFC 3526 group 15 among them) or 512 (moduli of 3073 ..
+ * 4096 bits, RFC 3526 group 16 among them) for a handle of mpvss_modp_group_create_wide.  Parameter names and comments below that say 256 mean that size.  Inputs need not be reduced (a value >= q gives what BigInt::modpow / (a * b) % q give, modp.rs:154-156
  * validates nothing), outputs are canonical (< q).  The group's generators are those of ModpGroup: G = 2, g = G^2 = 4.
  * Protocol parity is specified for safe primes, which is what ModpGroup::init yields; for another odd q the calls return
  * without fault and are deterministic.
@@ -672,17 +672,19 @@ int mpvss_box_verify_wire(mpvss_ctx* ctx, const uint8_t* buf, size_t len, int* v
  * below), the boxes of a whole round verified in one call ("Many boxes in one call" below) and the secrets of a whole round
  * reconstructed in one call ("Many secrets in one call" below).  Not offered for a
  * run-time group: the block / pipeline forms, the wire format, and the overlap of one run's hashing with the next run's GPU
- * work; moduli above 3072 bits are refused
- * with MPVSS_E_INVALID (4096 bits would overflow the product's 64-bit column accumulators). */
+ * work; moduli above 4096 bits are refused
+ * with MPVSS_E_INVALID (a 512-byte handle's product carries each 64-bit column accumulator once more per lane than the narrower
+ * ones, DESIGN section 13, "Handles of 512 bytes"; its rates are unmeasured). */
 typedef struct mpvss_modp_group mpvss_modp_group;
 /* q_be: q_len big-endian bytes (leading zeros allowed).  MPVSS_E_INVALID for an even q, q < 5 or q >= 2^2048. */
 int mpvss_modp_group_create(const uint8_t* q_be, size_t q_len, mpvss_modp_group** out);
 /* The same with the element size chosen: elem_bytes 256 is mpvss_modp_group_create itself; 384 takes an odd q of 2049 .. 3072
- * bits and gives a wide handle, which always runs at 27 limbs per lane (a narrower q with 384 is MPVSS_E_INVALID: the 256-byte
- * handle serves it).  Any other elem_bytes is MPVSS_E_INVALID. */
+ * bits and gives a handle that always runs at 27 limbs per lane; 512 takes an odd q of 3073 .. 4096 bits and gives a handle
+ * that always runs at 36 limbs per lane.  A narrower q with 384 or 512 is MPVSS_E_INVALID: the next smaller handle serves it.
+ * Any other elem_bytes is MPVSS_E_INVALID.  Everything a 256-byte handle can do, a 384- and a 512-byte handle can do. */
 int mpvss_modp_group_create_wide(const uint8_t* q_be, size_t q_len, size_t elem_bytes, mpvss_modp_group** out);
 void mpvss_modp_group_destroy(mpvss_modp_group* grp);
-/* bit length of q, the limbs per lane of the width the kernels run at (5, 9, 18 or 27), and the element size (256 or 384) */
+/* bit length of q, the limbs per lane of the width the kernels run at (5, 9, 18, 27 or 36), and the element size (256, 384 or 512) */
 int mpvss_modp_group_bits(const mpvss_modp_group* grp);
 int mpvss_modp_group_limbs_per_lane(const mpvss_modp_group* grp);
 int mpvss_modp_group_elem_bytes(const mpvss_modp_group* grp);

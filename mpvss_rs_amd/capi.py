@@ -397,7 +397,8 @@ class ModpGroup:
     """Handle of a run-time MODP group, host only -- the counterpart of the reference's ModpGroup::init(length)
     (src/groups/modp.rs:72-84).  ModpGroup(q): any odd modulus q of at most 2048 bits, 256-byte elements and scalars
     (mpvss_modp_group_create).  ModpGroup(q, elem_bytes=384): an odd q of 2049 .. 3072 bits (RFC 3526 group 15), 384-byte
-    elements and scalars (mpvss_modp_group_create_wide).  Every group_* call packs and unpacks at `elem_bytes`.  Usable with
+    elements and scalars; ModpGroup(q, elem_bytes=512): an odd q of 3073 .. 4096 bits (RFC 3526 group 16), 512-byte elements
+    and scalars (both mpvss_modp_group_create_wide; a q that a narrower handle serves is refused).  Every group_* call packs and unpacks at `elem_bytes`.  Usable with
     every Engine."""
 
     def __init__(self, q: int, elem_bytes: int = EB):

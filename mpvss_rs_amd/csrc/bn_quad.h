@@ -81,7 +81,7 @@ __device__ __forceinline__ Lane make_lane() {
 }
 
 // r = a * b * R^-1 (mod N), R = 2^(29 * 4 K); result almost normalised and < 2N when a, b < 2N.
-//   a     : this lane's K limbs of the first operand (registers); K = 18 for a 2048-bit number, bn_quad_rt.h adds 5 and 9
+//   a     : this lane's K limbs of the first operand (registers); K = 18 for a 2048-bit number, bn_quad_rt.h adds 5, 9, 27 and 36
 //   b     : LDS pointer to the limbs of the second operand of THIS number (a slot of at least 4 K words)
 //   n     : this lane's K limbs of the modulus (registers)
 //   N0INV : -N^-1 mod 2^29 when the modulus is a compile-time one; 1 for the RFC 3526 prime (N = -1 mod 2^64), the multiply
@@ -135,6 +135,17 @@ __device__ __forceinline__ void mont_mul(u32 (&r)[K], const u32 (&a)[K], const u
       const u32 m = quad_bcast0((u32)T[rr] * (N0INV != N0INV_RUNTIME ? N0INV : n0inv)) & ln.mask28;
 #pragma unroll
       for (int k = 0; k < K; ++k) T[(k + rr) % K] += (u64)m * n[k];
+      // K > 27 (bn_quad_rt.h, 36 limbs per lane): 2 K products pass 2^64, so a column is also carried half way down the lane.
+      // The column at local position K / 2 moves its upper bits into the column above it (same weight) and keeps its low
+      // W bits: between two carries a column then collects at most 36 products and two carry-ins in a product, and in a
+      // squaring, whose doubled limbs fall unevenly over a column's life, at most 54 products' worth -- the bound of K = 27
+      // (tests/test_modp_rt_4096_model.py).  In-lane, compile-time indices under the full unroll; no narrower instantiation
+      // sees it.
+      if constexpr (K > 27) {
+        const u64 mid = T[(K / 2 + rr) % K];
+        T[(K / 2 + 1 + rr) % K] += mid >> W;
+        T[(K / 2 + rr) % K] = (u64)((u32)mid & MASK);
+      }
       // Every lane moves the upper bits of its lowest column into its next column (same weight) and hands the
       // low 28 bits to the lane below, whose fresh top column they become; lane 0's lowest column is 0 mod 2^W
       // by construction and retires.  No lane-dependent arithmetic: one shift, one 64-bit add, one v_and_b32_dpp.
@@ -161,7 +172,7 @@ __device__ __forceinline__ void mont_mul(u32 (&r)[K], const u32 (&a)[K], const u
     r[k] = (u32)v & MASK;
     c = v >> W;
   }
-  // pass 2: hand the lane's carry-out (< 2^37) to the next lane, one more local step
+  // pass 2: hand the lane's carry-out (< 2^37, at K = 36 too: tests/test_modp_rt_4096_model.py) to the next lane, one more local step
   const u32 cl = quad_from_prev((u32)c) & ln.not_low;
   const u32 ch = quad_from_prev((u32)(c >> 32)) & ln.not_low;
   const u64 v = (u64)r[0] + (((u64)ch << 32) | cl);

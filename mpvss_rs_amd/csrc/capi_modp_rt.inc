@@ -10,7 +10,7 @@
 // rt_fd_positions_ok, rt_twin_dev, rt_fixed_base_dev, rt_scalar_on_device, rt_share_hash_on_device, rt_product_tree, the grouping of small boxes in
 // mpvss_modp_group_verify_many and that of secrets in mpvss_modp_group_reconstruct_many) are single places of their own.
 
-constexpr size_t RT_EB_MAX = FRAME_EB_MAX;     // the widest element / scalar of a handle (mpvss_modp_group_create_wide): 384 bytes
+constexpr size_t RT_EB_MAX = FRAME_EB_MAX;     // the widest element / scalar of a handle (mpvss_modp_group_create_wide): 512 bytes
 
 // q, q - 1 and (q-1)/2 for the host-side scalar ring (host_scalar.h) at NW 64-bit words
 template <int NW_>
@@ -29,13 +29,14 @@ struct mpvss_modp_group {
   uint8_t subR_be[RT_EB_MAX];// R mod q' = 2^(29 L) mod q', eb bytes big-endian (has_q): takes a coefficient into Montgomery form
   int bits = 0;
   int lpl = 0;
-  size_t eb = 0;             // bytes of every element, scalar and exponent of this handle on the ABI: 256, or 384 (wide)
+  size_t eb = 0;             // bytes of every element, scalar and exponent of this handle on the ABI: 256, 384 or 512
   uint8_t sub_be[RT_EB_MAX]; // (q-1)/2 big-endian, eb bytes: hash_to_scalar's modulus (modp.rs:142-148)
   uint8_t g_be[RT_EB_MAX];   // subgroup generator 4 (modp.rs:65-66 for any q >= 5)
   uint8_t G_be[RT_EB_MAX];   // main generator 2
   uint8_t q_be[RT_EB_MAX];
   RtRings<32> r32;           // the rings of a 256-byte handle ...
-  RtRings<48> r48;           // ... and of a 384-byte one (the other stays unset)
+  RtRings<48> r48;           // ... of a 384-byte one ...
+  RtRings<64> r64;           // ... and of a 512-byte one (the other two stay unset)
 };
 
 // A key set of a run-time group (include/mpvss_hip.h, "Key sets of a run-time group"): the rows of n public keys on the device
@@ -52,15 +53,15 @@ struct mpvss_modp_group_keyset {
 
 namespace {
 
-// fn(rings) with the handle's own rings: RT_NW(rings), 32 or 48 words, is a compile-time constant inside fn
+// fn(rings) with the handle's own rings: RT_NW(rings), 32, 48 or 64 words, is a compile-time constant inside fn
 #define RT_NW(R) std::decay_t<decltype(R)>::NW
 template <class Fn>
 auto rt_rings(const mpvss_modp_group* grp, Fn fn) {
-  return grp->eb == RT_EB_MAX ? fn(grp->r48) : fn(grp->r32);
+  return grp->eb == 512 ? fn(grp->r64) : grp->eb == 384 ? fn(grp->r48) : fn(grp->r32);
 }
 
-// ---- host big integers: little-endian 32-bit words, fixed capacity (2 q < 2^3074) ------------------------------
-constexpr int RTW = 98;
+// ---- host big integers: little-endian 32-bit words, fixed capacity (2 q < 2^4098) ------------------------------
+constexpr int RTW = 130;
 typedef uint32_t RtNum[RTW];
 
 void rt_from_be(RtNum x, const uint8_t* be, size_t len) {
@@ -111,7 +112,7 @@ void rt_limbs(const RtNum x, uint32_t* limbs, int L) {
 }
 
 // width of a modulus of a 256-byte handle: the smallest of 5, 9, 18 limbs per lane with bits <= 29 L - 2 (R > 4 N).  A
-// 384-byte handle always runs at 27.
+// 384-byte handle always runs at 27, a 512-byte one at 36.
 int rt_lpl_for_bits(int bits) {
   for (int lpl : {5, 9, 18})
     if (bits <= 29 * 4 * lpl - 2) return lpl;
@@ -719,11 +720,12 @@ extern "C" int mpvss_modp_group_create_wide(const uint8_t* q_be, size_t q_len, s
   if (!out) return MPVSS_E_INVALID;
   *out = nullptr;
   if (elem_bytes == MPVSS_MODP_BYTES) return mpvss_modp_group_create(q_be, q_len, out);
-  if (elem_bytes != RT_EB_MAX) return MPVSS_E_INVALID;
+  if (elem_bytes != 384 && elem_bytes != 512) return MPVSS_E_INVALID;
   RtNum q;
-  const int bits = rt_parse_modulus(q_be, q_len, RT_EB_MAX, q);
-  if (bits <= 8 * MPVSS_MODP_BYTES) return MPVSS_E_INVALID;                // a 256-byte handle serves it (or q is no modulus)
-  return rt_group_build<48>(q, bits, RT_EB_MAX, 27, &mpvss_modp_group::r48, out);
+  const int bits = rt_parse_modulus(q_be, q_len, elem_bytes, q);
+  if (bits <= 8 * ((int)elem_bytes - 128)) return MPVSS_E_INVALID;         // the next narrower handle serves it (or q is no modulus)
+  if (elem_bytes == 512) return rt_group_build<64>(q, bits, 512, 36, &mpvss_modp_group::r64, out);
+  return rt_group_build<48>(q, bits, 384, 27, &mpvss_modp_group::r48, out);
 }
 
 extern "C" void mpvss_modp_group_destroy(mpvss_modp_group* grp) { delete grp; }
@@ -1110,8 +1112,9 @@ const char* const RT_NO_Q = "no device scalar ring for this group: (q-1)/2 must 
 
 // Shares per k_rt_twin_exp launch: 4096 waves, more than the chip holds at once, and it bounds the bucket scratch the context
 // keeps at 2 x 15 x 65536 numbers (540 MiB at 18 limbs per lane, 270 MiB at 9, 150 MiB at 5) whatever MAX_CHUNK is.  At 27
-// limbs per lane a share's buckets are 12 960 bytes: 32768 shares (2048 waves, 405 MiB) keep the same ceiling.
-size_t rt_twin_launch(int lpl) { return lpl == 27 ? 32768 : 65536; }
+// limbs per lane a share's buckets are 12 960 bytes: 32768 shares (2048 waves, 405 MiB) keep the same ceiling.  At 36 they
+// are 17 280 bytes: 24576 shares (1536 waves) are the same 405 MiB.
+size_t rt_twin_launch(int lpl) { return lpl == 36 ? 24576 : lpl == 27 ? 32768 : 65536; }
 
 // out1 = B^e1, out2 = B^e2 for cnt shares (device pointers, one chunk).  Large batches: k_rt_twin_exp over bucket scratch of
 // the context, of which the frame's wipe zeroes what the call used; small ones, two left-to-right exponent sets over the bases' tables

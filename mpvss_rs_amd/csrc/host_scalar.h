@@ -175,7 +175,7 @@ struct Modulus {
 // itself, 3 .. 64 CAP bits).  Same interface as Modulus<CAP> -- every operand and result is an array of CAP limbs, zero above
 // the modulus' own `n` limbs -- so that the byte-level bodies of capi_scalar.inc serve both; the loops run over n limbs.
 // The division is the same Knuth D; no Montgomery form (q - 1 is even).  CAP = 32 for a group of 256-byte scalars
-// (ModulusRt), 48 for one of 384-byte scalars.
+// (ModulusRt), 48 for one of 384-byte scalars, 64 for one of 512-byte scalars.
 template <int CAP_>
 struct ModulusRtN {
   static constexpr int CAP = CAP_;

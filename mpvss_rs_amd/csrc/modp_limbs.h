@@ -32,7 +32,7 @@ struct ModpConsts {
 };
 
 // limb j (W bits at bit offset W j) of an EB-byte big-endian integer; 0 above bit 8 EB - 1.  EB = 256 on every ABI but that
-// of a wide run-time group (bn_quad_rt.h, 384 bytes).
+// of the wider run-time groups (bn_quad_rt.h, 384 and 512 bytes).
 template <int EB>
 LIMBS_HD u32 be_limb(const uint8_t* __restrict__ be, int j) {
   const int o = W * j;

@@ -1,12 +1,12 @@
 // Internal launch interface between the C-ABI layer (capi_modp_rt.inc) and the kernels of a run-time MODP group
-// (modp_rt_kernels.hip, modp_rt_kernels_wide.hip, bn_quad_rt.h).  Every array of limbs holds numbers of L = 4 lpl limbs,
+// (modp_rt_kernels.hip, modp_rt_kernels_wide.hip, modp_rt_kernels_4096.hip, bn_quad_rt.h).  Every array of limbs holds numbers of L = 4 lpl limbs,
 // stride L words; every element, scalar and exponent is a big-endian value of EB = modp_rt_elem_bytes(lpl) bytes, stride EB.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stddef.h>
 #include <stdint.h>
 
-#define MODP_RT_MAX_LIMBS 108
+#define MODP_RT_MAX_LIMBS 144
 
 /* device image of a group's constants (built by the host from the modulus alone) */
 typedef struct modp_rt_consts {
@@ -15,15 +15,16 @@ typedef struct modp_rt_consts {
   uint32_t one_m[MODP_RT_MAX_LIMBS];  /* R mod N (Montgomery one) */
   uint32_t one[MODP_RT_MAX_LIMBS];    /* plain 1 (leaves the Montgomery domain) */
   uint32_t n0inv;                     /* -N^-1 mod 2^29 */
-  uint32_t lpl;                       /* limbs per lane: 5, 9, 18 or 27 */
+  uint32_t lpl;                       /* limbs per lane: 5, 9, 18, 27 or 36 */
   uint32_t qm1_lo, qm1_hi;            /* q - 1 when it is below 2^64 (positions are reduced by it), else 0 */
 } modp_rt_consts;
 
 /* Forward differences (k_rt_fd_chain): the largest t a width's workgroup holds -- one level per DPP quad, 16 waves of at most
- * 128 registers at 5 / 9 / 18 limbs per lane, 8 waves of at most 256 at 27 -- and the one place that cuts n consecutive
+ * 128 registers at 5 / 9 / 18 limbs per lane, 8 waves of at most 256 at 27, 4 waves (one per SIMD) at 36 -- and the
+ * one place that cuts n consecutive
  * positions into S chains (host and device): chain c is [first, first + len), len >= t when n / S >= t; its t seeds start at
  * first + (len - t) / 2. */
-#define MODP_RT_FD_MAX_T(lpl) ((lpl) == 27 ? 128 : 256)
+#define MODP_RT_FD_MAX_T(lpl) ((lpl) == 36 ? 64 : (lpl) == 27 ? 128 : 256)
 static inline __host__ __device__ void modp_rt_fd_chain(int n, int S, int c, int* first, int* len) {
   const long long a = (long long)c * n / S, b = (long long)(c + 1) * n / S;
   *first = (int)a;
@@ -37,7 +38,7 @@ extern "C" {
 int modp_rt_fd_max_t(int lpl);
 /* HBM scratch of modp_rt_launch_fd_chains: one number per level, chain and direction */
 size_t modp_rt_fd_park_bytes(int lpl, int t, int S);
-/* bytes of an element / scalar / exponent of a width (256; 384 at 27 limbs per lane), -1 for no width */
+/* bytes of an element / scalar / exponent of a width (256; 384 at 27 limbs per lane, 512 at 36), -1 for no width */
 int modp_rt_elem_bytes(int lpl);
 /* IN_ROWS of a width (rows of the long product that takes an EB-byte input) */
 int modp_rt_in_rows(int lpl);
@@ -49,6 +50,9 @@ size_t modp_rt_keyset_bytes(int lpl, size_t count);
 #include "modp_rt_launchers.h"
 #undef MODP_RT_FN
 #define MODP_RT_FN(name) modp_rt27_##name
+#include "modp_rt_launchers.h"
+#undef MODP_RT_FN
+#define MODP_RT_FN(name) modp_rt36_##name
 #include "modp_rt_launchers.h"
 #undef MODP_RT_FN
 /* c_out[first + i] = c_box[box] (eb bytes each, eb a multiple of 4) for the live shares i of every tile of

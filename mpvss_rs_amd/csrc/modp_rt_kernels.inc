@@ -1,8 +1,9 @@
 // Kernel templates and launchers of a run-time MODP group: ModpGroup::init(length) of the reference
-// (src/groups/modp.rs:72-84) -- any odd modulus q of at most 3072 bits, chosen when the program runs.  Included by the
-// two translation units that instantiate them: modp_rt_kernels.hip (5, 9 and 18 limbs per lane, groups of 256-byte
-// elements) and modp_rt_kernels_wide.hip (27 limbs per lane, groups of 384-byte elements), each of which defines
-// RT_FN, RT_DISPATCH, RT_DISPATCH_FN and RT_ELSEWHERE first.  A third unit, modp_rt_fd_kernels.hip (RT_FD_ONLY), holds nothing but
+// (src/groups/modp.rs:72-84) -- any odd modulus q of at most 4096 bits, chosen when the program runs.  Included by the
+// three translation units that instantiate them: modp_rt_kernels.hip (5, 9 and 18 limbs per lane, groups of 256-byte
+// elements), modp_rt_kernels_wide.hip (27 limbs per lane, groups of 384-byte elements) and modp_rt_kernels_4096.hip (36 limbs
+// per lane, groups of 512-byte elements), each of which defines
+// RT_FN, RT_DISPATCH, RT_DISPATCH_FN and RT_ELSEWHERE first.  One more unit, modp_rt_fd_kernels.hip (RT_FD_ONLY), holds nothing but
 // k_rt_fd_chain at 5, 9 and 18 limbs per lane, which modp_rt_kernels.hip reaches through RT_FD_ELSEWHERE.
 //
 //   ModpGroup::exp / ::mul                       (src/groups/modp.rs:122-132)      k_rt_dual_exp, k_rt_mul
@@ -19,8 +20,8 @@
 // product is bn::mont_mul at the widths of bn_quad_rt.h, n0inv a run-time value.
 //
 // Cost follows the operands: the exponent loops run over the wave's largest exponent (4-bit windows), Horner's squarings
-// over the wave's largest reduced position.  Inputs are big-endian values of Width::EB bytes (256, or 384 at the wide
-// width) of any size: they enter a width by one long product (bnrt::Width::IN_ROWS rows), which reduces them mod q on
+// over the wave's largest reduced position.  Inputs are big-endian values of Width::EB bytes (256; 384 at 27 limbs per lane,
+// 512 at 36) of any size: they enter a width by one long product (bnrt::Width::IN_ROWS rows), which reduces them mod q on
 // the way into Montgomery form.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -34,11 +35,12 @@ using namespace bnrt;
 namespace {
 
 // occupancy of each width: the 18-limb product wants 3 waves per SIMD like the group-14 kernels (135 VGPRs); the
-// narrower ones fit more, the 27-limb one (54 accumulator registers) two
+// narrower ones fit more, the 27-limb one (54 accumulator registers) two, the 36-limb one (72) one
 template <int LPL> struct Occ { static constexpr int waves = 3; };
 template <> struct Occ<9> { static constexpr int waves = 4; };
 template <> struct Occ<5> { static constexpr int waves = 6; };
 template <> struct Occ<27> { static constexpr int waves = 2; };
+template <> struct Occ<36> { static constexpr int waves = 1; };
 
 // a = in R mod N (< 2N) for any EB-byte input: the input's 29-bit limbs go to the LDS slot (IN_ROWS of them), and one
 // long product with kin = 2^(29 (IN_ROWS + L)) mod N gives in kin 2^(-29 IN_ROWS) = in R, below N + kin in / 2^(29 IN_ROWS) < 2N.
@@ -1200,10 +1202,13 @@ __global__ void RT_KERNEL(LPL) k_rt_modq_poly_eval(const u32* __restrict__ coef_
 }
 
 // ---------------------------------------------------------------------------------------
-// launchers: RT_FN names them (modp_rt_launch_* here or modp_rt27_launch_* in the wide unit), RT_DISPATCH launches the
-// instance of a width this unit holds, RT_ELSEWHERE hands a width of the other unit over to it
+// launchers: RT_FN names them (modp_rt_launch_* here, modp_rt27_launch_* in the wide unit, modp_rt36_launch_* in the 4096-bit one), RT_DISPATCH launches the
+// instance of a width this unit holds, RT_ELSEWHERE hands a width of another unit over to it
 // ---------------------------------------------------------------------------------------
 static inline int rt_grid(int count) { return (count + RT_NUMS - 1) / RT_NUMS; }
+// rows of a width's comb and of one key of a key set (Width::COMB_ROWS, Width::KS_ROWS follow EB alone)
+static inline int rt_comb_rows(int lpl) { return lpl == 36 ? Width<36>::COMB_ROWS : lpl == 27 ? Width<27>::COMB_ROWS : Width<18>::COMB_ROWS; }
+static inline int rt_ks_rows(int lpl) { return lpl == 36 ? Width<36>::KS_ROWS : lpl == 27 ? Width<27>::KS_ROWS : Width<18>::KS_ROWS; }
 
 #ifdef RT_WIDTH_FREE
 // ---------------------------------------------------------------------------------------
@@ -1259,7 +1264,7 @@ extern "C" int RT_FN(launch_dual_exp)(int lpl, const uint32_t* tab1, size_t tab1
 extern "C" int RT_FN(launch_comb_build)(int lpl, const uint8_t* base_be, uint32_t* comb, const modp_rt_consts* cs, hipStream_t s) {
   RT_ELSEWHERE(launch_comb_build, lpl, base_be, comb, cs, s);
   RT_DISPATCH(lpl, k_rt_comb_bases, dim3(1), dim3(64), 0, s, base_be, comb, cs);
-  RT_DISPATCH(lpl, k_rt_comb_rows, dim3(rt_grid(lpl == 27 ? Width<27>::COMB_ROWS : Width<18>::COMB_ROWS)), dim3(64), 0, s, comb, cs);
+  RT_DISPATCH(lpl, k_rt_comb_rows, dim3(rt_grid(rt_comb_rows(lpl))), dim3(64), 0, s, comb, cs);
   return (int)hipGetLastError();
 }
 
@@ -1283,7 +1288,7 @@ extern "C" int RT_FN(launch_exp_sets)(int lpl, const uint32_t* tab, size_t tab_s
 extern "C" int RT_FN(launch_keyset_build)(int lpl, const uint8_t* keys_be, int count, uint32_t* ks, const modp_rt_consts* cs, hipStream_t s) {
   RT_ELSEWHERE(launch_keyset_build, lpl, keys_be, count, ks, cs, s);
   if (count <= 0) return 0;
-  const int nrows = count * (lpl == 27 ? Width<27>::KS_ROWS : Width<18>::KS_ROWS);
+  const int nrows = count * rt_ks_rows(lpl);
   RT_DISPATCH(lpl, k_rt_keyset_bases, dim3(rt_grid(count)), dim3(64), 0, s, keys_be, count, ks, cs);
   RT_DISPATCH(lpl, k_rt_keyset_rows, dim3(rt_grid(nrows)), dim3(64), 0, s, ks, nrows, cs);
   return (int)hipGetLastError();

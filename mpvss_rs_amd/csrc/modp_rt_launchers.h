@@ -1,6 +1,6 @@
 // The launchers of a run-time MODP group, named by MODP_RT_FN: modp_rt_launch_* (modp_rt_kernels.h; every width) and, for
-// modp_rt_kernels.hip alone, modp_rt27_launch_* (modp_rt_kernels_wide.hip; 27 limbs per lane only).  No include guard: it
-// is included once per name.
+// modp_rt_kernels.hip alone, modp_rt27_launch_* (modp_rt_kernels_wide.hip; 27 limbs per lane only) and modp_rt36_launch_*
+// (modp_rt_kernels_4096.hip; 36 only).  No include guard: it is included once per name.
 /* out_m[x] = in[x] R mod N (< 2N), any EB-byte big-endian input */
 int MODP_RT_FN(launch_to_mont)(int lpl, const uint8_t* in_be, int count, uint32_t* out_m, const modp_rt_consts* cs, hipStream_t s);
 /* tab[x][d] = base[x]^d R mod N, d < 16 (base_stride 0: one base for every x) */
@@ -12,7 +12,7 @@ int MODP_RT_FN(launch_dual_exp)(int lpl, const uint32_t* tab1, size_t tab1_strid
                             const uint8_t* e1, size_t e1_stride, const uint8_t* e2, size_t e2_stride, int count, uint8_t* out,
                             const modp_rt_consts* cs, hipStream_t s);
 /* fixed-base comb of one base shared by every share: comb[k][d] = base^(d 16^k) R mod N, k < 2 EB, d < 16 --
-   modp_rt_comb_bytes(lpl) bytes (5.06 MiB at 27 limbs per lane, 2.25 MiB at 18, 1.125 MiB at 9, 640 KiB at 5).  The base is an
+   modp_rt_comb_bytes(lpl) bytes (9.0 MiB at 36 limbs per lane, 5.06 MiB at 27, 2.25 MiB at 18, 1.125 MiB at 9, 640 KiB at 5).  The base is an
    EB-byte value of any size on the device. */
 int MODP_RT_FN(launch_comb_build)(int lpl, const uint8_t* base_be, uint32_t* comb, const modp_rt_consts* cs, hipStream_t s);
 /* out[x] = base^e1[x] * B2[x]^e2[x] mod q, canonical: e1 over the comb with no squarings, e2 left to right over B2's 16-entry

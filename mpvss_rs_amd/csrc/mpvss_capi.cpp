@@ -607,9 +607,9 @@ struct Timed {
     RET_IF(span_end((ctx)));            \
   } while (0)
 
-// The widest element the transcript helpers frame: a 384-byte handle of a run-time group (capi_modp_rt.inc).  The helpers take the
+// The widest element the transcript helpers frame: a 512-byte handle of a run-time group (capi_modp_rt.inc).  The helpers take the
 // element size as a trailing parameter; the group-14 call sites leave it at EB.
-constexpr size_t FRAME_EB_MAX = 384;
+constexpr size_t FRAME_EB_MAX = 512;
 
 // minimal-length big-endian view of an eb-byte element (modp.rs:150-152: zero -> one 0x00 byte)
 inline void frame_update(mpvss::Sha256& h, const uint8_t* e, size_t eb = EB) {

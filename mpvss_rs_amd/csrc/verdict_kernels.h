@@ -13,7 +13,7 @@ int verdict_launch_modp(const uint8_t* h1, const uint8_t* h2, const uint8_t* a1,
  * share-box proof (hash_to_scalar of the transcript digest, participant.rs:329-343; the mod (q-1)/2 is the identity) */
 int verdict_launch_modp_challenge(const uint8_t* h1, const uint8_t* h2, const uint8_t* a1, const uint8_t* a2, int count,
                                   uint8_t* c_out32, hipStream_t s);
-/* the same for a run-time MODP group at its element size eb (256 or 384), all arrays [count][eb]; no reduction mod (q-1)/2 (the
+/* the same for a run-time MODP group at its element size eb (256, 384 or 512), all arrays [count][eb]; no reduction mod (q-1)/2 (the
  * caller admits handles with (q-1)/2 >= 2^256 only).  c_out null: verdict[i] = (c_i == the hash, zero-extended to eb bytes);
  * c_out given: the hash itself, c_out_stride (32 or eb) big-endian bytes per share, zero-extended on the left; c, verdict unused */
 int verdict_launch_rt(int eb, const uint8_t* h1, const uint8_t* h2, const uint8_t* a1, const uint8_t* a2, const uint8_t* c, int count,

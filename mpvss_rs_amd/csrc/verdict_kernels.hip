@@ -315,7 +315,7 @@ k_modp_share_verdict(const uint8_t* __restrict__ h1, const uint8_t* __restrict__
 }
 
 // ---- MODP groups of a run-time modulus (capi_modp_rt.inc) ----------------------------------------------------------
-// K7 at the handle's element size EB (256, or 384 for a wide handle): one lane per share, four EB-byte elements at stride EB
+// K7 at the handle's element size EB (256, 384 or 512): one lane per share, four EB-byte elements at stride EB
 // hashed as given, c' = int_BE(SHA256(SHA256(transcript))).  The kernel does NOT reduce c' mod (q-1)/2: the host admits a handle
 // only when (q-1)/2 >= 2^256 (mpvss_modp_group_has_device_share_hash), where the reduction is the identity.
 //   c_out == null  verdict[i] = 1 iff the EB-byte big-endian c_i has its leading EB - 32 bytes zero and its last 32 equal to c'
@@ -485,15 +485,16 @@ extern "C" int verdict_launch_modp_challenge(const uint8_t* h1, const uint8_t* h
                      (uint8_t*)nullptr, c_out32);
   return (int)hipGetLastError();
 }
-// c_out null: verdicts against c; otherwise challenges at c_out_stride (32 or eb) bytes per share.  eb: 256 or 384
+// c_out null: verdicts against c; otherwise challenges at c_out_stride (32 or eb) bytes per share.  eb: 256, 384 or 512
 extern "C" int verdict_launch_rt(int eb, const uint8_t* h1, const uint8_t* h2, const uint8_t* a1, const uint8_t* a2, const uint8_t* c,
                                  int count, uint8_t* verdict, uint8_t* c_out, int c_out_stride, hipStream_t s) {
   if (count <= 0) return 0;
-  if ((eb != 256 && eb != 384) || (c_out ? (c_out_stride != 32 && c_out_stride != eb) : (c == nullptr || verdict == nullptr)))
+  if ((eb != 256 && eb != 384 && eb != 512) || (c_out ? (c_out_stride != 32 && c_out_stride != eb) : (c == nullptr || verdict == nullptr)))
     return (int)hipErrorInvalidValue;
   const dim3 grid((count + 63) / 64), block(64);
   if (eb == 256) hipLaunchKernelGGL(k_rt_share_verdict<256>, grid, block, 0, s, h1, h2, a1, a2, c, count, verdict, c_out, c_out_stride);
-  else hipLaunchKernelGGL(k_rt_share_verdict<384>, grid, block, 0, s, h1, h2, a1, a2, c, count, verdict, c_out, c_out_stride);
+  else if (eb == 384) hipLaunchKernelGGL(k_rt_share_verdict<384>, grid, block, 0, s, h1, h2, a1, a2, c, count, verdict, c_out, c_out_stride);
+  else hipLaunchKernelGGL(k_rt_share_verdict<512>, grid, block, 0, s, h1, h2, a1, a2, c, count, verdict, c_out, c_out_stride);
   return (int)hipGetLastError();
 }
 extern "C" int verdict_launch_ec(int group,const uint8_t* h1, const uint8_t* h2, const uint8_t* a1, const uint8_t* a2,

@@ -303,6 +303,8 @@ unsafe extern "C" {
     pub fn mpvss_box_verify_wire(ctx: *mut mpvss_ctx, buf: *const u8, len: usize, verdict: *mut c_int, digest32_out: *mut u8) -> c_int;
     // ---- MODP groups of a run-time modulus (ModpGroup::init)
     pub fn mpvss_modp_group_create(q_be: *const u8, q_len: usize, out: *mut *mut mpvss_modp_group) -> c_int;
+    /// elem_bytes 256: mpvss_modp_group_create; 384: an odd q of 2049 .. 3072 bits (RFC 3526 group 15); 512: an odd q of 3073 .. 4096
+    /// bits (RFC 3526 group 16).  Every mpvss_modp_group_* call then reads and writes values of mpvss_modp_group_elem_bytes bytes.
     pub fn mpvss_modp_group_create_wide(q_be: *const u8, q_len: usize, elem_bytes: usize, out: *mut *mut mpvss_modp_group) -> c_int;
     pub fn mpvss_modp_group_destroy(grp: *mut mpvss_modp_group);
     pub fn mpvss_modp_group_bits(grp: *const mpvss_modp_group) -> c_int;

@@ -50,7 +50,8 @@ impl HipModpGroup {
     /// `ModpGroup::init(length)` (modp.rs:72-84): the reference generates the safe prime (num_primes, its own choice of
     /// prime), the engine runs the group's exp / mul and the whole protocol of crate::batch on the GPU -- distribute_secret,
     /// verify_distribution_shares, extract_secret_shares, verify_shares and reconstruct (only verify_many stays with group 14).  Moduli above
-    /// 2048 bits have no GPU path and there is no CPU fallback: `init(length > 2048)` panics.
+    /// 2048 bits have no GPU path in this crate, which packs 256-byte values (the C ABI's 384- and 512-byte handles of
+    /// mpvss_modp_group_create_wide cover 2049 .. 4096 bits), and there is no CPU fallback: `init(length > 2048)` panics.
     pub fn init(length: u32) -> Arc<Self> {
         assert!(length <= 2048, "HipModpGroup::init({length}): the MI355X engine covers MODP groups of at most 2048 bits and has no CPU fallback");
         let reference = mpvss_rs::groups::ModpGroup::init(length);

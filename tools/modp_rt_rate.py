@@ -64,6 +64,9 @@ measurement.  Usage: python tools/modp_rt_rate.py [--quick] [--reps 3] [--legs r
               arrays in device memory (group_verify_shares, 2048 bits, n = 65536; torch tensors); --share-hash-wide: the one 3072-bit
               row, both calls at n = 16384.  --share-hash-parts parent: the library under test as it is (every share hashed on the
               host before this path existed); mode2: mpvss_ctx_set_rt_share_hash(2), with the time of the hash launches (timer 5).
+  w4096       (--legs w4096) 4096 bits (512-byte handle) beside 3072 bits (384-byte handle) in one session: kernels alone for
+              group_batch_exp and whole group_verify_distribution calls (t = 64) at n = 1024 and 65536, and their ratios beside the
+              count-derived 2.37; recorded in profiles/modp_rt_4096_rate.txt, no gate.
   --share-hash --ab PARENT  fresh processes of a built checkout of the parent commit and of this build under mode 2 take turns,
               best of the rounds, into profiles/modp_rt_share_hash_rate.txt.  rt_share_hash_min_shares is the smallest measured n
               from which mode 2's whole call is no slower than the parent's at every larger measured n (1 if that holds
@@ -683,11 +686,45 @@ def ab_fd(a):
             f.write(json.dumps(row) + "\n")
 
 
+def w4096_leg(eng, a, rng):
+    """4096 bits (512-byte handle, 36 limbs per lane) beside 3072 bits (384 bytes, 27) in one session: kernels alone for
+    group_batch_exp with full-width exponents, and whole group_verify_distribution calls (t = 64, challenge of 256 bits), at
+    n = 1024 and 65536.  The last rows hold the ratios beside the count-derived expectation, (144/108)^2 x 4/3 = 2.37 per
+    full-width exponentiation at equal occupancy -- which it is not: 1 wave per SIMD at 36 limbs per lane, 2 at 27."""
+    import modp_rt_4096_helpers as XH
+    import modp_rt_wide_helpers as WH
+    sizes = [256, 1024] if a.quick else [1024, 65536]
+    t = 64
+    groups = [(3072, ModpGroup(WH.group15(), elem_bytes=WH.EB), WH.EB), (4096, ModpGroup(XH.group16(), elem_bytes=XH.EB), XH.EB)]
+    rb = lambda n, bits, eb: b"".join(rng.getrandbits(bits).to_bytes(eb, "big") for _ in range(n))
+    exp_ms, ver_s = {}, {}
+    for bits, grp, eb in groups:
+        for n in sizes:
+            B, E = rb(n, bits, eb), rb(n, bits, eb)
+            s = best(lambda: eng.group_batch_exp(grp, B, E), a.reps)
+            kms = kernel_ms(eng)
+            exp_ms[bits, n] = kms
+            print(json.dumps({"what": "group_batch_exp", "bits": bits, "limbs_per_lane": grp.limbs_per_lane, "elem_bytes": eb, "n": n,
+                              "s": round(s, 4), "kernel_ms": kms, "kernel_exps_per_s": round(n / (kms / 1e3))}), flush=True)
+            cm, pos = rb(t, bits, eb), list(range(1, n + 1))
+            y, Y, r = rb(n, bits, eb), rb(n, bits, eb), rb(n, bits, eb)
+            c = rng.getrandbits(256).to_bytes(eb, "big")
+            s = best(lambda: eng.group_verify_distribution(grp, cm, pos, y, Y, r, c), a.reps)
+            ver_s[bits, n] = s
+            print(json.dumps({"what": "group_verify_distribution", "bits": bits, "elem_bytes": eb, "n": n, "t": t, "s": round(s, 4),
+                              "share_verifications_per_s": round(n / s), "kernel_ms": kernel_ms(eng)}), flush=True)
+    for n in sizes:
+        print(json.dumps({"what": "4096_over_3072", "n": n, "batch_exp_kernel_ms_ratio": round(exp_ms[4096, n] / exp_ms[3072, n], 2),
+                          "verify_distribution_s_ratio": round(ver_s[4096, n] / ver_s[3072, n], 2),
+                          "expected_per_exponentiation_at_equal_occupancy": round((144 / 108) ** 2 * 4 / 3, 2),
+                          "waves_per_simd": {"3072": 2, "4096": 1}}), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--quick", action="store_true", help="smaller shapes (a check of the tool, not a measurement)")
-    ap.add_argument("--legs", default="rates", help="comma-separated: rates (batch_exp, verify), twin, deal")
+    ap.add_argument("--legs", default="rates", help="comma-separated: rates (batch_exp, verify), twin, deal, w4096 (4096 beside 3072 bits)")
     ap.add_argument("--twin-parts", default="call,baseline", help="of the twin leg: call (batch_twin_exp), baseline (two batch_exp)")
     ap.add_argument("--comb", action="store_true", help="the fixed-base comb: alone, the comb leg; with --ab, its interleaved A/B")
     ap.add_argument("--comb-parts", default="comb", help="of the comb leg: parent (g^w inside group_deal), comb (cold and warm)")
@@ -745,6 +782,8 @@ def main():
         keyset_leg(eng, a, rng)
     if "share_hash" in legs:
         share_hash_leg(eng, a, rng)
+    if "w4096" in legs:
+        w4096_leg(eng, a, rng)
     if "rates" not in legs:
         eng.close()
         return
