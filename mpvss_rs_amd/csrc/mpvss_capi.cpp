@@ -21,6 +21,7 @@
 #include <thread>
 #include <vector>
 
+#include "host_fd_plan.h"
 #include "host_many.h"
 #include "host_modq.h"
 #include "host_scalar.h"
@@ -141,7 +142,6 @@ struct mpvss_ctx {
       uint16_t csched[160];                  // pinned: sliding-window schedule of that challenge (sliding_schedule)
     };
     RootJob* root = nullptr;
-    bool fd_used = false;                    // eval_x took the forward-difference path in the call being enqueued
     hipStream_t sa = nullptr, sb = nullptr;  // stream pair: sb runs a2 beside the serial phases of the X path on sa
     hipEvent_t ev_fork = nullptr, ev_gr = nullptr;
     hipEvent_t ev_a2 = nullptr;
@@ -792,7 +792,7 @@ int copy_out(mpvss_ctx* ctx, int space, void* dst, const void* dev_src, size_t b
 // operations: it takes the row layout (16 lanes per number, modp_row_kernels.hip: 3.5 instead of 5.7 us per operation of a wave that has
 // its SIMD to itself; ModpGroup::exp of 16 numbers 14.5 -> 7.4 ms, profiles/r06_small_box_latency.txt) up to one wave per SIMD, larger
 // ones the quad layout's throughput.
-constexpr size_t ROW_MAX_NUMBERS = 4096;
+constexpr size_t ROW_MAX_NUMBERS = fdplan::ROW_MAX_NUMBERS;
 int dual_exp_any(mpvss_ctx* ctx, const uint32_t* t1, size_t s1, const uint32_t* t2, size_t s2, const uint8_t* e1, const uint8_t* e2,
                  size_t e2_stride, int e2_windows, size_t cnt, uint8_t* out, const uint8_t* e1b = nullptr, const uint8_t* e2b = nullptr,
                  uint8_t* outb = nullptr) {
@@ -1182,206 +1182,139 @@ bool all_units_mod_q(const uint8_t* y, size_t n) {
   return true;
 }
 
-// are the n positions consecutive from a start in [0, 2^61)?  (what the forward differences of either group family step through;
-// n == 0: no)
-bool positions_consecutive(const int64_t* hpos, size_t n) {
-  if (n == 0 || hpos[0] < 0 || hpos[0] >= ((int64_t)1 << 61)) return false;
-  for (size_t i = 1; i < n; ++i)
-    if (hpos[i] != hpos[0] + (int64_t)i) return false;
-  return true;
-}
+using fdplan::positions_consecutive;      // (the curve groups' forward differences step through the same positions)
 
-// does the forward-difference path apply to this run of shares?  (host-side part of the decision)
-bool fd_applies(size_t t, const int64_t* hpos, size_t cnt) {
-  static const int fd_on = fd_env("MPVSS_FD", 1);
-  static const size_t min_shares = (size_t)fd_env("MPVSS_FD_MIN_SHARES", 4096);
-  constexpr size_t max_t = 1024;
-  bool fd = fd_on && t >= 16 && t <= max_t && cnt >= 16 * t && cnt >= min_shares;
-  // host positions: decide here; device positions are checked by a kernel
-  return fd && (hpos == nullptr || positions_consecutive(hpos, cnt));
-}
-
-// boxes > 1: a GROUP of same-shaped boxes in one set of launches -- box b has its commitments at w.cm + b * t rows, its `cnt`
-// positions at dpos + b * box_positions (0: the boxes share one array) and its X at dX + b * cnt rows; one flag for the group.
 int pair_mask();     // which kernels take the pair layout (below)
-// x_alone: nothing of the caller runs beside this X path (the stand-alone mpvss_modp_commit_eval): its Horner seeds then take the
-// row-layout kernel (modp_row_kernels.hip: 16 lanes per seed, 1024 waves instead of 256 -- the seed launch 52 -> 28 ms, the whole
-// X path 68.5 -> 47.7 ms at (65536, 256), profiles/r06_commit_eval_alone.txt).  NOT inside a verifier's block: there the box is
-// bound by the sum of its work, the wider layout costs 1.3x the issue slots per seed, and the call gets slower (148 against 122 ms,
-// profiles/r06_lone_box_schedule_ab.txt).
-// (The t first-level seeds of a box AMONG OTHERS take the row layout whatever x_alone says: there the box is bound by the length of its
-// X path's chain, below.)
-// direct: Horner for every share whatever the positions are (a one-box call of up to ROW_MAX_NUMBERS shares, below).
-int eval_x(mpvss_ctx* ctx, size_t t, const int64_t* dpos, const int64_t* hpos, size_t cnt, uint8_t* dX, size_t boxes = 1,
-           size_t box_positions = 0, bool x_alone = false, bool direct = false) {
-  const int B = (int)boxes;
-  // The stepping kernels on the pair layout (MPVSS_PAIR bit 5) from MPVSS_FD_PAIR_MIN_T commitments: stages of 32 levels, 122
-  // instead of 191 issue slots per product, but half as many waves with longer steps.  Measured (profiles/r03_fd_pair_ab.txt):
-  // one GPU's slice of C5 (131072, 1024), where the stepping is a third of the work, 0.60 -> 0.69 M share verifications/s;
-  // the headline shape (t = 256) within noise, if anything slower (1.08 against 1.11 M): its X path is latency, not issue.
-  static const size_t pair_min_t = (size_t)fd_env("MPVSS_FD_PAIR_MIN_T", 512);
-  const bool step_pair = (pair_mask() & 32) != 0 && t >= pair_min_t;
-  auto launch_step = [&](const uint32_t* sf, const uint32_t* sb, size_t bx_st, int chains, int tt, int w0_, int clen, int cnt_, uint32_t* xm_,
-                         size_t bx_xm_, uint32_t* hand_, size_t bx_hand_, int fault) -> int {
-    // MPVSS_FD_TILE (with the pair-layout stepping): the stepping as wide launches over the anti-diagonals of the (stage, block of
-    // MPVSS_FD_TILE_STEPS steps) grid instead of a pipeline of persistent stages -- no wave waits for another one.  0: never,
-    // 1: when other blocks are in flight (a lone call keeps the pipeline: its latency is shorter), 2: always.
-    static const int tile_mode = fd_env("MPVSS_FD_TILE", 0), tile_steps = fd_env("MPVSS_FD_TILE_STEPS", 64);
-    if (step_pair && fault == 0 && (tile_mode >= 2 || (tile_mode == 1 && ctx->busy_with_others())))
-      return modp_launch_fd_step_pair_tiled_boxes(const_cast<uint32_t*>(sf), const_cast<uint32_t*>(sb), bx_st, chains, tt, w0_, clen, cnt_, xm_,
-                                                  bx_xm_, hand_, bx_hand_, B, (const int*)ctx->w->fd_flag.p, tile_steps, ctx->consts,
-                                                  ctx->pair_tables, ctx->stream);
-    if (step_pair)
-      return modp_launch_fd_step_pair_boxes(sf, sb, bx_st, chains, tt, w0_, clen, cnt_, xm_, bx_xm_, hand_, bx_hand_, B, (int*)ctx->w->fd_flag.p,
-                                            fault, ctx->consts, ctx->pair_tables, ctx->stream);
-    return modp_launch_fd_step_boxes(sf, sb, bx_st, chains, tt, w0_, clen, cnt_, xm_, bx_xm_, hand_, bx_hand_, B, (int*)ctx->w->fd_flag.p, fault,
-                                     ctx->consts, ctx->stream);
-  };
-  const bool fd = !direct && fd_applies(t, hpos, cnt);
-  if (!fd && B == 1 && cnt <= ROW_MAX_NUMBERS) {
-    // a small box is the latency of one share's Horner chain ((t - 1) x about 26 operations): the row layout's kernel, 3.5 instead of
-    // 5.7 us per operation (Montgomery limbs out, converted by k_modp_from_mont)
-    RET_IF(ensure(ctx, ctx->w->fd_xm, cnt * MODP_L * 4));
-    uint32_t* xm_small = (uint32_t*)ctx->w->fd_xm.p;
-    TIMED_LAUNCH(ctx, 0, modp_launch_commit_eval_row_boxes((const uint32_t*)ctx->w->cm.p, (int)t, dpos, 0, (int)cnt, 1, xm_small, cnt, nullptr, 0,
-                                                           ctx->consts, ctx->stream, 0));
-    LAUNCHCHK(ctx, modp_launch_from_mont(xm_small, (int)cnt, dX, nullptr, ctx->consts, ctx->stream));
-    return 0;
-  }
-  if (!fd) {
-    if (B > 1)
-      TIMED_LAUNCH(ctx, 0, modp_launch_commit_eval_boxes((const uint32_t*)ctx->w->cm.p, (int)t, dpos, box_positions, (int)cnt, B,
-                                                         nullptr, dX, cnt, nullptr, 0, ctx->consts, ctx->stream));
-    else
-    TIMED_LAUNCH(ctx, 0, modp_launch_commit_eval((const uint32_t*)ctx->w->cm.p, (int)t, dpos, (int)cnt, nullptr, dX,
-                                                 ctx->consts, ctx->stream));
-    return 0;
-  }
-  // number of chains S.  Chain c owns the positions c, c+S, c+2S, .. (index j inside the chain); its seeds are the t
-  // indices w0 .. w0+t-1 in the MIDDLE of the chain, from which one pipeline steps forward and one backward: the
-  // seeds of all chains together are the S*t consecutive positions from S*w0 (Horner, and outputs at the same time).
-  // The seed launch is latency-bound (2048 seeds are an eighth of a wave per SIMD), so fewer seeds would not finish
-  // sooner; more chains shorten the stepping but cost Horner work.
-  // measured optima on MI355X: chains of about 8192 members (raised to 16 chains below for t <= 256), fewer when the
-  // seeds are dear (t = 512: 4), never longer than 16384 members (n=131072, t=1024: 8)
-  int S = (int)std::max<size_t>(std::max<size_t>(std::min<size_t>(2048 / t, cnt / 8192), cnt / 16384), 4);
-  // a call that has the GPU to itself: more, shorter chains -- the extra seeds are one wide launch on an idle chip, the
-  // stepping (the serial part) shrinks in proportion
-  // ... and a box among others of at least 65536 shares: its X path is a chain of dependent launches that holds one hardware queue
-  // from its first kernel to a1, and the boxes in flight share GPU_MAX_HW_QUEUES of them, so a box cannot come sooner than its
-  // chain's span over the queues (profiles/x_chain_trace_parent.txt: 4 queues, 4 X paths open, 207 ms / 3.4 = 61 ms per box).
-  // With the stride-1 seeding chain stepping both ways (below) 16 chains are 2 175 + 2 175 serial steps instead of 8 chains'
-  // 1 151 + 4 223, for about 25 products per share more (profiles/x_chain_ab.txt).
-  const int S_pipelined = S;
-  constexpr int lone_chains = 16;     // measured: 8 -> 109 ms per box, 16 -> 96.5, 32 -> 104, 64 -> 115
-  if (lone_chains > S && (!ctx->busy_with_others() || cnt >= 65536) && t <= 256) S = lone_chains;
-  const int s_max = (int)(cnt / (4 * t));      // cnt >= 16 t, so at least 4
-  if (S > s_max) S = s_max;
-  if (S < 1) S = 1;
-  const int chain_len = (int)((cnt + S - 1) / S);
-  const int w0 = (chain_len - (int)t) / 2;
-  const size_t seed0 = (size_t)S * w0;    // index of the first seed position
-  const int m0 = (int)(S * t);
-  // Two-level seeding (MPVSS_FD_L1, default on): Horner's rule -- about 7 000 products per seed at (65536, 256) -- only
-  // for the middle t of the S*t seed positions; a stride-1 forward-difference chain built from those t values steps
-  // through the remaining (S-1)*t seed positions at t products each.  Same values (uniqueness of the group element);
-  // 180 products per share fewer at (65536, 256), for about 15 ms more latency of the box's chain.
-  // tests only: one pipeline stage gives up and the flag falls -- 1 / 2: a stage of the stepping pipelines, 3: of the
-  // stride-1 seeding chain, 4: of the table pipeline
-  static const int inject_fault = fd_env("MPVSS_FD_TEST_FAULT", 0);
-  // MPVSS_FD_L1: 0 never, 1 (default) when other blocks are in flight, 2 always.  The second level saves 180 products per
-  // share and costs a serial chain (about 15 ms of a lone box's latency): a call that has the GPU to itself keeps the
-  // wide Horner launch for all S*t seeds.
-  static const int two_level_env = fd_env("MPVSS_FD_L1", 1);
-  const bool two_level = S > 1 && (two_level_env >= 2 || (two_level_env == 1 && ctx->busy_with_others()));
-  // product tree of the simultaneous inversion: level l turns ms[l] numbers into ms[l+1] group totals
-  constexpr int G = 16;
-  auto tree_sizes = [&](int m) {
-    std::vector<int> ms{m};
-    while (ms.back() > 1) ms.push_back((ms.back() + G - 1) / G);
-    return ms;
-  };
 
+// what the environment says about the X path's plan (host_fd_plan.h), read once per process
+const fdplan::Knobs& fd_knobs() {
+  static const fdplan::Knobs knobs = [] {
+    fdplan::Knobs k;
+    k.fd = fd_env("MPVSS_FD", k.fd);
+    k.min_shares = (size_t)fd_env("MPVSS_FD_MIN_SHARES", (int)k.min_shares);
+    k.pair_min_t = (size_t)fd_env("MPVSS_FD_PAIR_MIN_T", (int)k.pair_min_t);
+    k.pair_step = (pair_mask() & 32) != 0;
+    k.tile = fd_env("MPVSS_FD_TILE", k.tile);
+    k.tile_steps = fd_env("MPVSS_FD_TILE_STEPS", k.tile_steps);
+    k.l1 = fd_env("MPVSS_FD_L1", k.l1);
+    k.test_fault = fd_env("MPVSS_FD_TEST_FAULT", k.test_fault);
+    return k;
+  }();
+  return knobs;
+}
+
+// THE plan of a chunk's X path: what the context knows (are other blocks in flight?) is read here, once
+fdplan::Plan x_plan(const mpvss_ctx* ctx, size_t t, size_t cnt, const int64_t* hpos, size_t boxes = 1, bool x_alone = false,
+                    bool direct = false) {
+  return fdplan::plan(fd_knobs(), t, cnt, boxes, ctx->busy_with_others(), x_alone, direct, hpos);
+}
+
+// one stepping launch of the forward differences, by the kernel the plan names
+int launch_fd_step(mpvss_ctx* ctx, const fdplan::Plan& p, fdplan::Step kernel, const uint32_t* sf, const uint32_t* sb, size_t bx_state,
+                   int chains, int w0, int chain_len, int cnt, uint32_t* xm, size_t bx_xm, uint32_t* hand, size_t bx_hand, int fault) {
+  const int B = (int)p.boxes, t = (int)p.t;
+  int* flag = (int*)ctx->w->fd_flag.p;
+  if (kernel == fdplan::STEP_PAIR_TILED)
+    return modp_launch_fd_step_pair_tiled_boxes(const_cast<uint32_t*>(sf), const_cast<uint32_t*>(sb), bx_state, chains, t, w0, chain_len, cnt,
+                                                xm, bx_xm, hand, bx_hand, B, flag, p.tile_steps, ctx->consts, ctx->pair_tables, ctx->stream);
+  if (kernel == fdplan::STEP_PAIR)
+    return modp_launch_fd_step_pair_boxes(sf, sb, bx_state, chains, t, w0, chain_len, cnt, xm, bx_xm, hand, bx_hand, B, flag, fault,
+                                          ctx->consts, ctx->pair_tables, ctx->stream);
+  return modp_launch_fd_step_boxes(sf, sb, bx_state, chains, t, w0, chain_len, cnt, xm, bx_xm, hand, bx_hand, B, flag, fault, ctx->consts,
+                                   ctx->stream);
+}
+
+// inverses of the m Montgomery-form numbers at `in` into `inv_out`: Montgomery's trick on the device (3 products per number), the
+// single inversion of the root on the host, in stream order (no host synchronisation).  A root that is 0 mod q (some X is 0: a
+// commitment was) clears the flag.  `job`: pinned mailbox of the host callback.
+int fd_invert_batch(mpvss_ctx* ctx, const uint32_t* in, size_t m, uint32_t* inv_out, mpvss_ctx::Work::RootJob* job) {
   mpvss_ctx::Work& w = *ctx->w;
-  w.fd_used = true;
-  RET_IF(ensure(ctx, w.fd_flag, 64));
-  RET_IF(ensure(ctx, w.fd_root, 4 * EB));
-  RET_IF(ensure(ctx, w.fd_xm, boxes * cnt * MODP_L * 4));
-  // The configuration (chains, seeding levels) depends on whether other blocks are in flight, and a slot sees both
-  // over its life: the buffers are sized for the largest of them at once -- growing one later means hipFree, which
-  // waits for the device (58-87 ms inside the enqueue of a timed box, measured with MPVSS_TRACE_ENQUEUE).
-  struct FdBytes { size_t xinv = 0, pre = 0, tot = 0, state = 0, hand_t = 0, hand_s = 0; } need_b;
-  {
-    const int s_cap = (int)(cnt / (4 * t)) < 1 ? 1 : (int)(cnt / (4 * t));
-    int cands[3] = {S, std::min(S_pipelined, s_cap), (t <= 256 && lone_chains > 0) ? std::min(lone_chains, s_cap) : S};
-    for (int c = 0; c < 3; ++c) {
-      const int Sc = cands[c] < 1 ? 1 : cands[c];
-      const int m0c = (int)(Sc * t), clc = (int)((cnt + Sc - 1) / Sc);
-      const std::vector<int> msc = tree_sizes(m0c * B);
-      size_t prec = 0, totc = 0;
-      for (size_t l = 0; l + 1 < msc.size(); ++l) prec += (size_t)msc[l];
-      for (size_t l = 1; l < msc.size(); ++l) totc += (size_t)msc[l];
-      const size_t l1t = Sc > 1 ? modp_fd_table_hand_words(1, (int)t) * 4 : 0;
-      const size_t l1s = Sc > 1 ? modp_fd_step_hand_words(1, (int)t, m0c) * 4 : 0;
-      need_b.xinv = std::max(need_b.xinv, boxes * m0c * MODP_L * 4);
-      need_b.pre = std::max(need_b.pre, prec * MODP_L * 4);
-      need_b.tot = std::max(need_b.tot, totc * MODP_L * 4);
-      need_b.state = std::max(need_b.state, boxes * 2 * m0c * MODP_L * 4);
-      need_b.hand_t = std::max(need_b.hand_t, boxes * (modp_fd_table_hand_words(Sc, (int)t) * 4 + l1t));
-      need_b.hand_s = std::max(need_b.hand_s, boxes * (modp_fd_step_hand_words(Sc, (int)t, clc) * 4 + l1s));
-    }
-  }
-  RET_IF(ensure(ctx, w.fd_xinv, need_b.xinv));
-  RET_IF(ensure(ctx, w.fd_pre, need_b.pre));
-  RET_IF(ensure(ctx, w.fd_tot, need_b.tot));
-  RET_IF(ensure(ctx, w.fd_totinv, need_b.tot));
-  RET_IF(ensure(ctx, w.fd_state, need_b.state));
-  if (B > 1) RET_IF(ensure(ctx, w.fd_gather, need_b.xinv));
-  if (!w.root) return fail(ctx, MPVSS_E_DEVICE, "eval_x: workspace not initialised");
+  const fdplan::InvTree tr = fdplan::tree(m);
+  const int nlev = (int)tr.levels(), G = (int)fdplan::InvTree::G;
   int* flag = (int*)w.fd_flag.p;
   int* dok = flag + 1;
   uint8_t* root_be = (uint8_t*)w.fd_root.p;
   uint8_t* rootinv_be = root_be + EB;
-  uint32_t* xm = (uint32_t*)w.fd_xm.p;
-  uint32_t* xseed = xm + seed0 * MODP_L;
-  uint32_t* state_fwd = (uint32_t*)w.fd_state.p;
-  uint32_t* state_bwd = state_fwd + (size_t)m0 * MODP_L;
-  // inverses of the m Montgomery-form numbers at `in` into `inv_out`: Montgomery's trick on the device (3 products per
-  // number), the single inversion of the root on the host, in stream order (no host synchronisation).  A root that
-  // is 0 mod q (some X is 0: a commitment was) clears the flag.  `job`: pinned mailbox of the host callback.
-  auto invert_batch = [&](const uint32_t* in, int m, uint32_t* inv_out, mpvss_ctx::Work::RootJob* job) -> int {
-    const std::vector<int> ms = tree_sizes(m);
-    const int nlev = (int)ms.size() - 1;
-    std::vector<size_t> pre_off(nlev + 1, 0), tot_off(nlev + 1, 0);
-    size_t po = 0, to = 0;
-    for (int l = 0; l < nlev; ++l) { pre_off[l] = po; po += (size_t)ms[l]; }
-    for (int l = 1; l <= nlev; ++l) { tot_off[l] = to; to += (size_t)ms[l]; }
-    auto level_in = [&](int l) { return l == 0 ? in : (const uint32_t*)w.fd_tot.p + tot_off[l] * MODP_L; };
-    auto level_out = [&](int l) { return (uint32_t*)w.fd_tot.p + tot_off[l] * MODP_L; };
-    auto level_inv = [&](int l) { return l == 0 ? inv_out : (uint32_t*)w.fd_totinv.p + tot_off[l] * MODP_L; };
-    for (int l = 0; l < nlev; ++l)
-      LAUNCHCHK(ctx, modp_launch_binv_up(level_in(l), ms[l], G, (uint32_t*)w.fd_pre.p + pre_off[l] * MODP_L, level_out(l + 1),
-                                         flag, ctx->consts, ctx->stream));
-    LAUNCHCHK(ctx, modp_launch_from_mont(level_in(nlev), 1, root_be, flag, ctx->consts, ctx->stream));
-    HIPCHK(ctx, hipMemcpyAsync(job->in_be, root_be, EB, hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(ctx, hipLaunchHostFunc(ctx->stream, invert_root_on_host, job));
-    HIPCHK(ctx, hipMemcpyAsync(rootinv_be, job->out_be, EB, hipMemcpyHostToDevice, ctx->stream));
-    HIPCHK(ctx, hipMemcpyAsync(dok, &job->ok, sizeof(int), hipMemcpyHostToDevice, ctx->stream));
-    LAUNCHCHK(ctx, modp_launch_fd_apply_ok(dok, flag, ctx->stream));
-    LAUNCHCHK(ctx, modp_launch_to_mont(rootinv_be, level_inv(nlev), 1, ctx->consts, ctx->stream));
-    for (int l = nlev - 1; l >= 0; --l)
-      LAUNCHCHK(ctx, modp_launch_binv_down(level_in(l), (const uint32_t*)w.fd_pre.p + pre_off[l] * MODP_L, level_inv(l + 1),
-                                           ms[l], G, level_inv(l), flag, ctx->consts, ctx->stream));
+  auto pre = [&](int l) { return (uint32_t*)w.fd_pre.p + tr.pre_off[l] * MODP_L; };
+  auto level_out = [&](int l) { return (uint32_t*)w.fd_tot.p + tr.tot_off[l] * MODP_L; };
+  auto level_in = [&](int l) { return l == 0 ? in : (const uint32_t*)level_out(l); };
+  auto level_inv = [&](int l) { return l == 0 ? inv_out : (uint32_t*)w.fd_totinv.p + tr.tot_off[l] * MODP_L; };
+  for (int l = 0; l < nlev; ++l)
+    LAUNCHCHK(ctx, modp_launch_binv_up(level_in(l), (int)tr.ms[l], G, pre(l), level_out(l + 1), flag, ctx->consts, ctx->stream));
+  LAUNCHCHK(ctx, modp_launch_from_mont(level_in(nlev), 1, root_be, flag, ctx->consts, ctx->stream));
+  HIPCHK(ctx, hipMemcpyAsync(job->in_be, root_be, EB, hipMemcpyDeviceToHost, ctx->stream));
+  HIPCHK(ctx, hipLaunchHostFunc(ctx->stream, invert_root_on_host, job));
+  HIPCHK(ctx, hipMemcpyAsync(rootinv_be, job->out_be, EB, hipMemcpyHostToDevice, ctx->stream));
+  HIPCHK(ctx, hipMemcpyAsync(dok, &job->ok, sizeof(int), hipMemcpyHostToDevice, ctx->stream));
+  LAUNCHCHK(ctx, modp_launch_fd_apply_ok(dok, flag, ctx->stream));
+  LAUNCHCHK(ctx, modp_launch_to_mont(rootinv_be, level_inv(nlev), 1, ctx->consts, ctx->stream));
+  for (int l = nlev - 1; l >= 0; --l)
+    LAUNCHCHK(ctx, modp_launch_binv_down(level_in(l), pre(l), level_inv(l + 1), (int)tr.ms[l], G, level_inv(l), flag, ctx->consts,
+                                         ctx->stream));
+  return 0;
+}
+
+// Enqueues the X path that plan p (x_plan above) describes: the plan decides, this function ensures the buffers and launches.
+// boxes > 1: a GROUP of same-shaped boxes in one set of launches -- box b has its commitments at w.cm + b * t rows, its `cnt`
+// positions at dpos + b * box_positions (0: the boxes share one array) and its X at dX + b * cnt rows; one flag for the group.
+// x_alone (of the plan): nothing of the caller runs beside this X path (the stand-alone mpvss_modp_commit_eval): its Horner seeds
+// then take the row-layout kernel (modp_row_kernels.hip: 16 lanes per seed, 1024 waves instead of 256 -- the seed launch 52 -> 28 ms,
+// the whole X path 68.5 -> 47.7 ms at (65536, 256), profiles/r06_commit_eval_alone.txt).  NOT inside a verifier's block: there the
+// box is bound by the sum of its work, the wider layout costs 1.3x the issue slots per seed, and the call gets slower (148 against
+// 122 ms, profiles/r06_lone_box_schedule_ab.txt).
+int eval_x(mpvss_ctx* ctx, const fdplan::Plan& p, const int64_t* dpos, size_t box_positions, uint8_t* dX) {
+  const int B = (int)p.boxes, t = (int)p.t, cnt = (int)p.cnt;
+  mpvss_ctx::Work& w = *ctx->w;
+  if (p.path == fdplan::HORNER_ROW) {      // (Montgomery limbs out, converted by k_modp_from_mont)
+    RET_IF(ensure(ctx, w.fd_xm, p.cnt * MODP_L * 4));
+    uint32_t* xm_small = (uint32_t*)w.fd_xm.p;
+    TIMED_LAUNCH(ctx, 0, modp_launch_commit_eval_row_boxes((const uint32_t*)w.cm.p, t, dpos, 0, cnt, 1, xm_small, p.cnt, nullptr, 0,
+                                                           ctx->consts, ctx->stream, 0));
+    LAUNCHCHK(ctx, modp_launch_from_mont(xm_small, cnt, dX, nullptr, ctx->consts, ctx->stream));
     return 0;
-  };
-  // handoff buffers of the pipelined kernels (zeroed per call): [tables L2][stepping L2][tables L1][stepping L1]
-  const size_t hand_t = modp_fd_table_hand_words(S, (int)t) * 4, hand_s = modp_fd_step_hand_words(S, (int)t, chain_len) * 4;
-  const size_t hand_t1 = two_level ? modp_fd_table_hand_words(1, (int)t) * 4 : 0;
-  const size_t hand_s1 = two_level ? modp_fd_step_hand_words(1, (int)t, m0) * 4 : 0;
-  RET_IF(ensure(ctx, w.fd_hand_t, std::max(need_b.hand_t, boxes * (hand_t + hand_t1))));
-  RET_IF(ensure(ctx, w.fd_hand_s, std::max(need_b.hand_s, boxes * (hand_s + hand_s1))));
+  }
+  if (p.path == fdplan::HORNER) {
+    if (B > 1)
+      TIMED_LAUNCH(ctx, 0, modp_launch_commit_eval_boxes((const uint32_t*)w.cm.p, t, dpos, box_positions, cnt, B, nullptr, dX, p.cnt,
+                                                         nullptr, 0, ctx->consts, ctx->stream));
+    else
+      TIMED_LAUNCH(ctx, 0, modp_launch_commit_eval((const uint32_t*)w.cm.p, t, dpos, cnt, nullptr, dX, ctx->consts, ctx->stream));
+    return 0;
+  }
+  const fdplan::Bytes b = fdplan::sized(
+      fd_knobs(), p, [](size_t chains, size_t tt) { return modp_fd_table_hand_words((int)chains, (int)tt); },
+      [](size_t chains, size_t tt, size_t len) { return modp_fd_step_hand_words((int)chains, (int)tt, (int)len); });
+  RET_IF(ensure(ctx, w.fd_flag, 64));
+  RET_IF(ensure(ctx, w.fd_root, 4 * EB));
+  RET_IF(ensure(ctx, w.fd_xm, b.xm));
+  RET_IF(ensure(ctx, w.fd_xinv, b.xinv));
+  RET_IF(ensure(ctx, w.fd_pre, b.pre));
+  RET_IF(ensure(ctx, w.fd_tot, b.tot));
+  RET_IF(ensure(ctx, w.fd_totinv, b.tot));
+  RET_IF(ensure(ctx, w.fd_state, b.state));
+  if (B > 1) RET_IF(ensure(ctx, w.fd_gather, b.gather));
+  if (!w.root) return fail(ctx, MPVSS_E_DEVICE, "eval_x: workspace not initialised");
+  RET_IF(ensure(ctx, w.fd_hand_t, b.hand_t));
+  RET_IF(ensure(ctx, w.fd_hand_s, b.hand_s));
+  const int S = (int)p.S, m0 = (int)p.m0;
+  int* flag = (int*)w.fd_flag.p;
+  const uint32_t* cm = (const uint32_t*)w.cm.p;
+  uint32_t* xinv = (uint32_t*)w.fd_xinv.p;
+  uint32_t* xm = (uint32_t*)w.fd_xm.p;
+  uint32_t* xseed = xm + p.seed0 * MODP_L;
+  uint32_t* state_fwd = (uint32_t*)w.fd_state.p;
+  uint32_t* state_bwd = state_fwd + p.m0 * MODP_L;
+  // hand-over buffers of the pipelined kernels (zeroed per call), level 2's part of a box first, then level 1's
+  uint32_t *hand_t2 = (uint32_t*)w.fd_hand_t.p, *hand_t1 = (uint32_t*)((uint8_t*)w.fd_hand_t.p + b.hand_t1_off);
+  uint32_t *hand_s2 = (uint32_t*)w.fd_hand_s.p, *hand_s1 = (uint32_t*)((uint8_t*)w.fd_hand_s.p + b.hand_s1_off);
   // strides from one box of the group to the next, in 32-bit words
-  const size_t bx_xm = cnt * MODP_L, bx_state = (size_t)2 * m0 * MODP_L, bx_hand_t = (hand_t + hand_t1) / 4, bx_hand_s = (hand_s + hand_s1) / 4;
+  const size_t bx_xm = p.cnt * MODP_L, bx_state = 2 * p.m0 * MODP_L, bx_hand_t = b.box_hand_t / 4, bx_hand_s = b.box_hand_s / 4;
+  // Horner's rule at `count` positions of every box, kept in Montgomery form, by the kernel the plan names for the seeding level
+  auto horner_seeds = [&](fdplan::Seeds kernel, const int64_t* pos, int count, uint32_t* out) -> int {
+    if (kernel == fdplan::SEEDS_ROW)
+      return modp_launch_commit_eval_row_boxes(cm, t, pos, box_positions, count, B, out, p.cnt, flag, 1, ctx->consts, ctx->stream, 1);
+    return modp_launch_commit_eval_boxes(cm, t, pos, box_positions, count, B, out, nullptr, p.cnt, flag, 1, ctx->consts, ctx->stream);
+  };
   // the seeds of the group's boxes side by side (one simultaneous inversion for all of them); a lone box's are already
   auto seeds_together = [&](const uint32_t* first, int per_box) -> const uint32_t* {
     if (B == 1) return first;
@@ -1391,52 +1324,38 @@ int eval_x(mpvss_ctx* ctx, size_t t, const int64_t* dpos, const int64_t* hpos, s
   w.root[0].one = 1;     // pinned: the copy below is asynchronous and reads it in stream order
   HIPCHK(ctx, hipMemcpyAsync(flag, &w.root[0].one, sizeof(int), hipMemcpyHostToDevice, ctx->stream));
   RET_IF(span_begin(ctx, 0));
-  if (!hpos) LAUNCHCHK(ctx, modp_launch_fd_check_positions_boxes(dpos, box_positions, (int)cnt, box_positions ? B : 1, flag, ctx->stream));
-  HIPCHK(ctx, hipMemsetAsync(w.fd_hand_t.p, 0, boxes * (hand_t + hand_t1), ctx->stream));
-  HIPCHK(ctx, hipMemsetAsync(w.fd_hand_s.p, 0, boxes * (hand_s + hand_s1), ctx->stream));
-  // seeds: X at the S*t positions from seed0, kept in Montgomery form
-  if (two_level) {
-    // The t Horner positions sit in the MIDDLE of the seed window (w1 .. w1 + t - 1 of its m0), as the seeds of a strided chain
-    // sit in the middle of the chain: the stride-1 chain then steps forward and backward at once, max(m0 - 1 - w1, w1 + t - 1)
-    // serial steps instead of m0 - 1 (S = 8, t = 256: 1 151 instead of 2 047), for the t - 1 table-advancing steps of the
-    // backward pipeline (t (t - 1) products per box).  m0 == t never gets here (S > 1), and w1 == 0 would be forward only.
-    const int w1 = (m0 - (int)t) / 2;
-    uint32_t* xseed1 = xseed + (size_t)w1 * MODP_L;
-    // The t seeds are 16 waves of the quad layout whose latency is the whole cost (about 5 600 dependent operations): the row layout
-    // does an operation in 3.5 instead of 5.7 us, and its 1.3x issue slots on t seeds are 0.4 % of the box
-    // (48 -> 30 ms of the chain under load, profiles/x_chain_trace_new.txt).
-    LAUNCHCHK(ctx, modp_launch_commit_eval_row_boxes((const uint32_t*)w.cm.p, (int)t, dpos + seed0 + w1, box_positions, (int)t, B, xseed1, cnt,
-                                                     flag, 1, ctx->consts, ctx->stream, 1));
-    const uint32_t* seeds1 = seeds_together(xseed1, (int)t);
+  if (p.device_positions)
+    LAUNCHCHK(ctx, modp_launch_fd_check_positions_boxes(dpos, box_positions, cnt, box_positions ? B : 1, flag, ctx->stream));
+  HIPCHK(ctx, hipMemsetAsync(w.fd_hand_t.p, 0, p.boxes * b.box_hand_t, ctx->stream));
+  HIPCHK(ctx, hipMemsetAsync(w.fd_hand_s.p, 0, p.boxes * b.box_hand_s, ctx->stream));
+  // seeds: X at the S t positions from seed0, kept in Montgomery form
+  if (p.two_level) {
+    // Horner's rule at the t middle positions of the seed window; one chain of stride 1 over the window: tables from those t
+    // values, then both ways to the window's ends
+    uint32_t* xseed1 = xseed + p.w1 * MODP_L;
+    LAUNCHCHK(ctx, horner_seeds(p.seeds1, dpos + p.seed0 + p.w1, t, xseed1));
+    const uint32_t* seeds1 = seeds_together(xseed1, t);
     if (!seeds1) return fail(ctx, MPVSS_E_DEVICE, "eval_x: gather launch");
-    RET_IF(invert_batch(seeds1, B * (int)t, (uint32_t*)w.fd_xinv.p, &w.root[1]));
-    // one chain of stride 1 over the seed window: tables from those t values, then both ways to the window's ends
-    LAUNCHCHK(ctx, modp_launch_fd_table_boxes(xseed1, bx_xm, (const uint32_t*)w.fd_xinv.p, t * MODP_L, 1, (int)t, state_fwd, state_bwd,
-                                              bx_state, (uint32_t*)((uint8_t*)w.fd_hand_t.p + hand_t), bx_hand_t, B, flag, 0,
-                                              ctx->consts, ctx->stream));
-    LAUNCHCHK(ctx, launch_step(state_fwd, state_bwd, bx_state, 1, (int)t, w1, m0, m0, xseed, bx_xm,
-                               (uint32_t*)((uint8_t*)w.fd_hand_s.p + hand_s), bx_hand_s, inject_fault == 3 ? 1 : 0));
-  } else if (x_alone && !ctx->busy_with_others()) {
-    LAUNCHCHK(ctx, modp_launch_commit_eval_row_boxes((const uint32_t*)w.cm.p, (int)t, dpos + seed0, box_positions, m0, B, xseed, cnt, flag, 1,
-                                                     ctx->consts, ctx->stream, 1));
+    RET_IF(fd_invert_batch(ctx, seeds1, p.boxes * p.t, xinv, &w.root[1]));
+    LAUNCHCHK(ctx, modp_launch_fd_table_boxes(xseed1, bx_xm, xinv, p.t * MODP_L, 1, t, state_fwd, state_bwd, bx_state, hand_t1, bx_hand_t,
+                                              B, flag, p.fault_table1, ctx->consts, ctx->stream));
+    LAUNCHCHK(ctx, launch_fd_step(ctx, p, p.step1, state_fwd, state_bwd, bx_state, 1, (int)p.w1, m0, m0, xseed, bx_xm, hand_s1, bx_hand_s,
+                                  p.fault_step1));
   } else {
-    LAUNCHCHK(ctx, modp_launch_commit_eval_boxes((const uint32_t*)w.cm.p, (int)t, dpos + seed0, box_positions, m0, B, xseed, nullptr,
-                                                 cnt, flag, 1, ctx->consts, ctx->stream));
+    LAUNCHCHK(ctx, horner_seeds(p.seeds2, dpos + p.seed0, m0, xseed));
   }
   const uint32_t* seeds2 = seeds_together(xseed, m0);
   if (!seeds2) return fail(ctx, MPVSS_E_DEVICE, "eval_x: gather launch");
-  RET_IF(invert_batch(seeds2, B * m0, (uint32_t*)w.fd_xinv.p, &w.root[0]));
+  RET_IF(fd_invert_batch(ctx, seeds2, p.boxes * p.m0, xinv, &w.root[0]));
   // difference tables, stepping, conversion -- all gated on flag == 1.  Both kernels are pipelines of single-wave
   // stages that hand numbers down through zeroed buffers (see modp_kernels.hip).
-  LAUNCHCHK(ctx, modp_launch_fd_table_boxes(xseed, bx_xm, (const uint32_t*)w.fd_xinv.p, (size_t)m0 * MODP_L, S, (int)t, state_fwd,
-                                            state_bwd, bx_state, (uint32_t*)w.fd_hand_t.p, bx_hand_t, B, flag, inject_fault, ctx->consts,
-                                            ctx->stream));
-  LAUNCHCHK(ctx, launch_step(state_fwd, state_bwd, bx_state, S, (int)t, w0, chain_len, (int)cnt, xm, bx_xm, (uint32_t*)w.fd_hand_s.p,
-                             bx_hand_s, inject_fault));
-  LAUNCHCHK(ctx, modp_launch_from_mont(xm, B * (int)cnt, dX, flag, ctx->consts, ctx->stream));
+  LAUNCHCHK(ctx, modp_launch_fd_table_boxes(xseed, bx_xm, xinv, p.m0 * MODP_L, S, t, state_fwd, state_bwd, bx_state, hand_t2, bx_hand_t, B,
+                                            flag, p.fault_table2, ctx->consts, ctx->stream));
+  LAUNCHCHK(ctx, launch_fd_step(ctx, p, p.step2, state_fwd, state_bwd, bx_state, S, (int)p.w0, (int)p.chain_len, cnt, xm, bx_xm, hand_s2,
+                                bx_hand_s, p.fault_step2));
+  LAUNCHCHK(ctx, modp_launch_from_mont(xm, B * cnt, dX, flag, ctx->consts, ctx->stream));
   // fallback: plain Horner when the flag was cleared
-  LAUNCHCHK(ctx, modp_launch_commit_eval_boxes((const uint32_t*)w.cm.p, (int)t, dpos, box_positions, (int)cnt, B, nullptr, dX, cnt, flag,
-                                               0, ctx->consts, ctx->stream));
+  LAUNCHCHK(ctx, modp_launch_commit_eval_boxes(cm, t, dpos, box_positions, cnt, B, nullptr, dX, p.cnt, flag, 0, ctx->consts, ctx->stream));
   RET_IF(span_end(ctx));
   return 0;
 }
@@ -1460,7 +1379,7 @@ extern "C" int mpvss_modp_commit_eval(mpvss_ctx* ctx, int space, const uint8_t* 
     RET_IF(ensure(ctx, ctx->w->xbe, n * EB));
     dout = (uint8_t*)ctx->w->xbe.p;
   }
-  RET_IF(eval_x(ctx, t, dpos, space == MPVSS_HOST ? positions : nullptr, n, dout, 1, 0, true));
+  RET_IF(eval_x(ctx, x_plan(ctx, t, n, space == MPVSS_HOST ? positions : nullptr, 1, true), dpos, 0, dout));
   if (space == MPVSS_HOST) RET_IF(copy_out(ctx, space, x_out, dout, n * EB));
   RET_IF(spans_collect(ctx));
   return MPVSS_OK;
@@ -1717,7 +1636,6 @@ struct BlockEnqueue {
     stream0 = ctx->stream;
     stream_b0 = ctx->stream_b;
     ctx->w = &sl.work;
-    sl.work.fd_used = false;
     ctx->stream = sl.work.sa;
     ctx->stream_b = sl.work.sb;
     ctx->sp = &sl.spans;
@@ -2002,7 +1920,6 @@ int verify_block_compute_locked(mpvss_ctx* ctx, int space, const uint8_t* commit
     uint8_t* dX = (uint8_t*)ctx->w->xbe.p;
     uint8_t* da1 = (uint8_t*)ctx->w->out1.p;
     uint8_t* da2 = (uint8_t*)ctx->w->out2.p;
-    sl.work.fd_used = false;
     hipStream_t closing = ctx->stream;       // the stream that ends this chunk: stream A, or the slot's closing stream (below)
     const int64_t* hp = space == MPVSS_HOST ? hpos + off : nullptr;
     // A one-box call of up to ROW_MAX_NUMBERS shares (BASELINE config C2 and everything the reference's tests and examples use) is the
@@ -2012,11 +1929,17 @@ int verify_block_compute_locked(mpvss_ctx* ctx, int space, const uint8_t* commit
     // set: the tests' way to reach the forward-difference path at small sizes, honoured.)
     static const bool fd_min_default = getenv("MPVSS_FD_MIN_SHARES") == nullptr;
     const bool small_direct = fd_min_default && n <= ROW_MAX_NUMBERS && !ctx->crowded();
-    if (ctx->w->sb && !small_direct && fd_applies(t, hp, cnt)) {
+    const bool use_keys = ks && c_windows == 64;
+    // THE decision on this chunk's X path, taken once: the branches below follow it.
+    // (registered keys: a2 is a quarter of its usual work, so a box that has the chip to itself is its X path's latency -- there the
+    // row-layout seeds pay: 122.8 -> 103.5 ms per lone call, profiles/r06_lone_key_cache.txt; without key tables they lose, eval_x)
+    // (a workspace without its second stream keeps what it always did: neither the row-layout seeds nor the direct path)
+    const bool side = ctx->w->sb != nullptr;
+    const fdplan::Plan xp = x_plan(ctx, t, cnt, hp, 1, use_keys && side, small_direct && side);
+    if (side && xp.fd) {
       // The forward-difference X path is a chain of latency-bound launches that occupy few wave slots (seeds,
       // inversion tree, difference tables, stepping) and runs on the block slot's high-priority stream.  a2 = y^r Y^c
       // and g^r do not depend on X: they run beside it on the slot's low-priority stream.
-      const bool use_keys = ks && c_windows == 64;
       // (a challenge of 0 has no sliding-window schedule: such a box keeps the plain kernels, and its tab1 is allocated here, in
       //  front of the fork, like everybody's)
       bool c_nonzero = false;
@@ -2093,9 +2016,7 @@ int verify_block_compute_locked(mpvss_ctx* ctx, int space, const uint8_t* commit
         HIPCHK(ctx, hipEventRecord(ctx->w->ev_gr, ctx->stream));
       }
       mark(2);
-      // (registered keys: a2 is a quarter of its usual work, so a box that has the chip to itself is its X path's latency -- there the
-      // row-layout seeds pay: 122.8 -> 103.5 ms per lone call, profiles/r06_lone_key_cache.txt; without key tables they lose, eval_x)
-      RET_IF(eval_x(ctx, t, dpos, hp, cnt, dX, 1, 0, use_keys));
+      RET_IF(eval_x(ctx, xp, dpos, 0, dX));
       mark(3);
       // A box among others hands its TAIL to sb here, behind g^r: X's table, a1, the output copies and the slot's `done` need nothing
       // of the chain, but enqueued on stream A they hold A's hardware queue -- a1's wide launch trickles in as a2 waves retire, and
@@ -2160,12 +2081,12 @@ int verify_block_compute_locked(mpvss_ctx* ctx, int space, const uint8_t* commit
         }
         HIPCHK(ctx, hipEventRecord(ctx->w->ev_a2, ctx->stream));
       }
-      RET_IF(eval_x(ctx, t, dpos, hp, cnt, dX, 1, 0, false, small_direct));
+      RET_IF(eval_x(ctx, xp, dpos, 0, dX));
       RET_IF(dleq_side(ctx, nullptr, nullptr, dX, (const uint8_t*)dr, (const uint8_t*)dchal, 0, c_windows, cnt, da1, cg, &ctx->w->tab3));
       HIPCHK(ctx, hipStreamWaitEvent(ctx->stream, ctx->w->ev_a2, 0));
     } else {
       // X_i                                                  participant.rs:423-434
-      RET_IF(eval_x(ctx, t, dpos, hp, cnt, dX));
+      RET_IF(eval_x(ctx, xp, dpos, 0, dX));
       // a1_i = g^r_i * X_i^c, a2_i = y_i^r_i * Y_i^c           dleq.rs:66-84
       RET_IF(dleq_side(ctx, nullptr, nullptr, dX, (const uint8_t*)dr, (const uint8_t*)dchal, 0, c_windows, cnt, da1, cg));
       RET_IF(dleq_side(ctx, nullptr, (const uint8_t*)dy, (const uint8_t*)dY, (const uint8_t*)dr, (const uint8_t*)dchal,
@@ -2175,7 +2096,7 @@ int verify_block_compute_locked(mpvss_ctx* ctx, int space, const uint8_t* commit
     HIPCHK(ctx, hipMemcpyAsync(hY + off * EB, dY, cnt * EB, hipMemcpyDeviceToHost, closing));
     HIPCHK(ctx, hipMemcpyAsync(h1 + off * EB, da1, cnt * EB, hipMemcpyDeviceToHost, closing));
     HIPCHK(ctx, hipMemcpyAsync(h2 + off * EB, da2, cnt * EB, hipMemcpyDeviceToHost, closing));
-    if (sl.work.fd_used) {     // the device's decision for this chunk (1 = forward differences held, 0 = fell back)
+    if (xp.fd) {     // the device's decision for this chunk (1 = forward differences held, 0 = fell back)
       sl.fd_used = true;
       if (sl.fd_chunks < FLAGS)
         HIPCHK(ctx, hipMemcpyAsync(hflags + sl.fd_chunks, sl.work.fd_flag.p, 4, hipMemcpyDeviceToHost, closing));
@@ -2317,7 +2238,8 @@ int verify_group_compute_locked(mpvss_ctx* ctx, int space, const mpvss_modp_box*
     RET_IF(launch_comb_gr_mont(ctx, cg, (pair_mask() & 4) != 0, dr, dchal, N, (uint32_t*)w.gr_m.p));
     HIPCHK(ctx, hipEventRecord(w.ev_gr, ctx->stream));
   }
-  RET_IF(eval_x(ctx, t, dpos, nullptr, n, dX, B, n));
+  const fdplan::Plan xp = x_plan(ctx, t, n, nullptr, B);
+  RET_IF(eval_x(ctx, xp, dpos, n, dX));
   {
     const uint32_t* tx;
     RET_IF(number_tables(ctx, dX, N, w.tab3, &tx));
@@ -2330,7 +2252,7 @@ int verify_group_compute_locked(mpvss_ctx* ctx, int space, const mpvss_modp_box*
   HIPCHK(ctx, hipMemcpyAsync(hY, dY, N * EB, hipMemcpyDeviceToHost, ctx->stream));
   HIPCHK(ctx, hipMemcpyAsync(h1, da1, N * EB, hipMemcpyDeviceToHost, ctx->stream));
   HIPCHK(ctx, hipMemcpyAsync(h2, da2, N * EB, hipMemcpyDeviceToHost, ctx->stream));
-  if (w.fd_used) {
+  if (xp.fd) {
     sl.fd_used = true;
     HIPCHK(ctx, hipMemcpyAsync(hflags, w.fd_flag.p, 4, hipMemcpyDeviceToHost, ctx->stream));
     sl.fd_chunks = 1;
@@ -3569,9 +3491,9 @@ int distribute_block_compute_locked(mpvss_ctx* ctx, int space, const uint8_t* co
         HIPCHK(ctx, hipMemcpyAsync(hpos + off, dpos, cnt * 8, hipMemcpyDeviceToHost, ctx->stream));
         sl.check_positions = true;
       }
-      sl.work.fd_used = false;
-      RET_IF(eval_x(ctx, t, dpos, space == MPVSS_HOST ? hpos + off : nullptr, cnt, dX));          // :207-215
-      if (sl.work.fd_used) {
+      const fdplan::Plan xp = x_plan(ctx, t, cnt, space == MPVSS_HOST ? hpos + off : nullptr);
+      RET_IF(eval_x(ctx, xp, dpos, 0, dX));          // :207-215
+      if (xp.fd) {
         sl.fd_used = true;
         if (sl.fd_chunks < FLAGS)
           HIPCHK(ctx, hipMemcpyAsync(hflags + sl.fd_chunks, sl.work.fd_flag.p, 4, hipMemcpyDeviceToHost, ctx->stream));

@@ -1,4 +1,4 @@
-"""Exact integer model of the two-level seeding of the forward-difference X path (eval_x in mpvss_capi.cpp, k_modp_fd_table and
+"""Exact integer model of the two-level seeding of the forward-difference X path (fdplan::plan in host_fd_plan.h, k_modp_fd_table and
 k_modp_fd_step in modp_kernels.hip) over a small safe prime: Horner's rule at the t MIDDLE positions of the seed window, the
 difference table of those t values, and the stride-1 chain stepping forward and backward from them to the window's ends.
 
@@ -16,7 +16,8 @@ ORDER = P - 1                 # the commitments' exponents live mod P - 1, as th
 
 
 def host_plan(t, n, busy=True):
-    """S, chain_len, w0, seed0, m0, w1 as eval_x computes them (16 chains for t <= 256: a call that has the GPU to itself, and a box
+    """S, chain_len, w0, seed0, m0, w1 as the X path's plan has them (fdplan::plan in mpvss_rs_amd/csrc/host_fd_plan.h, which
+    tests/test_fd_plan_host.py holds to this transcription; 16 chains for t <= 256: a call that has the GPU to itself, and a box
     among others from 65536 shares)"""
     S = max(max(min(2048 // t, n // 8192), n // 16384), 4)
     if (not busy or n >= 65536) and t <= 256:
