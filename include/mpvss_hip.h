@@ -941,6 +941,34 @@ int mpvss_modp_group_reconstruct_many(mpvss_ctx* ctx, const mpvss_modp_group* gr
 int mpvss_modp_group_reconstruct_many_stats(mpvss_ctx* ctx, unsigned long long* passes, unsigned long long* grouped_secrets,
                                             unsigned long long* single_secrets);
 
+/* Where mpvss_modp_group_reconstruct and mpvss_modp_group_reconstruct_many compute the Lagrange exponents of a position list,
+ * |lambda_i| = prod_{j != i} x_j / |x_j - x_i| mod (q-1)/2 written as the exponent of share i (participant.rs:526-561): mode 0 on
+ * the host as before; 2 on the device whenever the list is admitted -- the handle has the device scalar ring
+ * (mpvss_modp_group_has_device_scalar), no list of more than 16384 positions, fewer than 2^31 positions in all --; 1, the
+ * default, on the device when the work of the call (the sum of m^2 over its distinct lists; m^2 of a lone secret) reaches a
+ * measured size: 60 x 32^2 = 61 440 up to 2048 bits, 60 x 1024^2 at the 384- and 512-byte handles ("Lagrange
+ * exponents on the device"; profiles/modp_rt_lagrange_device.txt).  On the device k_rt_lagrange_terms forms numerator and denominator
+ * of every coefficient (one DPP quad each, a tile of up to 16 coefficients of one list per workgroup), the denominators are
+ * inverted by Fermat's power through the group's own table and exponentiation kernels, and k_rt_lagrange_finish checks
+ * den * den^-1 = 1 and stores the exponent; a list with a failed check -- a denominator that is 0 mod a small (q-1)/2, a composite
+ * (q-1)/2 -- is computed again, whole, by the host path, which decides between a value (the fraction in lowest terms) and a
+ * refusal.  Every exponent is the host's byte for byte, so the results of all reconstruct entry points are the same bytes under
+ * every mode.  Returns the mode before; no context, or another value, is MPVSS_E_INVALID. */
+int mpvss_ctx_set_rt_lagrange(mpvss_ctx* ctx, int mode);
+/* The exponents on their own: exps_out_host[i eb .. i eb + eb - 1] (eb = mpvss_modp_group_elem_bytes, big-endian) = the exponent
+ * share i of a secret at these positions is raised to: |lambda_i| mod (q-1)/2, or (q-1) - |lambda_i| for a negative coefficient
+ * of nonzero magnitude; computed where the context's mode says.  Refusals are those of mpvss_modp_group_reconstruct: a NULL pointer,
+ * m == 0, m above 0x7fffffff, a position below 1, duplicate positions, a coefficient whose reduced denominator has no inverse mod
+ * (q-1)/2 are MPVSS_E_INVALID and leave the output untouched.  Synchronous, under the context lock. */
+int mpvss_modp_group_lagrange_exponents(mpvss_ctx* ctx, const mpvss_modp_group* grp, const int64_t* positions_host, size_t m,
+                                        uint8_t* exps_out_host);
+/* Position lists whose exponents were computed on the device / on the host since the context was created, by any of the three
+ * calls above, and fallback_lists, the lists tried on the device and done again on the host (they are counted in host_lists too,
+ * not in device_lists).  A list shared by several secrets of one call counts once; refused lists are in none of the counts.  Any
+ * pointer may be NULL; no context is MPVSS_E_INVALID. */
+int mpvss_modp_group_lagrange_stats(mpvss_ctx* ctx, unsigned long long* device_lists, unsigned long long* host_lists,
+                                    unsigned long long* fallback_lists);
+
 /* ---- hashing helpers (host only; Group::hash_to_scalar, src/groups/modp.rs:142-148) ------ */
 
 /* out32 = SHA-256(data) */
@@ -954,7 +982,8 @@ void mpvss_modp_hash_to_scalar(const uint8_t* data, size_t len, uint8_t out256[2
  * measured with hipEvents on the stream each kernel was launched on, summed per kind:
  *   0 = the X path (k_modp_commit_eval and, for consecutive positions, the forward-difference kernels),
  *   1 = k_modp_comb_dual_exp (a1), 2 = table builds, 3 = k_modp_dual_exp (a2, batch_exp),
- *   4 = the scalar-ring kernels of a run-time group (k_rt_modq_*), and k_ec_lagrange of the curve groups.
+ *   4 = the scalar-ring kernels of a run-time group (k_rt_modq_*), the launches of its Lagrange exponents (k_rt_lagrange_terms, the
+ *       denominators' tables and powers, k_rt_lagrange_finish), and k_ec_lagrange of the curve groups.
  * Kernels of different kinds may overlap in time (two streams), so the sums can exceed the wall time.
  * mpvss_last_kernel_launches gives the number of launches behind each sum.  Negative when unavailable. */
 double mpvss_last_kernel_ms(const mpvss_ctx* ctx, int kernel_id);

@@ -66,6 +66,7 @@ EXPORTED_SYMBOLS = (
     "mpvss_modp_group_verify_distribution_keyset", "mpvss_modp_group_deal_keyset",
     "mpvss_modp_group_verify_many", "mpvss_modp_group_verify_many_stats",
     "mpvss_modp_group_reconstruct_many", "mpvss_modp_group_reconstruct_many_stats",
+    "mpvss_ctx_set_rt_lagrange", "mpvss_modp_group_lagrange_exponents", "mpvss_modp_group_lagrange_stats",
     "mpvss_ec_reconstruct_many", "mpvss_ec_reconstruct_many_stats",
     "mpvss_ctx_set_ec_lagrange", "mpvss_ec_lagrange_scalars", "mpvss_ec_lagrange_stats",
     "mpvss_ctx_set_ec_box_groups", "mpvss_ec_verify_many_stats",
@@ -331,6 +332,11 @@ def load_library() -> C.CDLL:
     lib.mpvss_modp_group_reconstruct_many.argtypes = [vp, vp, ci, C.POINTER(GroupSecret), sz, ci, C.POINTER(ci), u8p, u8p]
     lib.mpvss_modp_group_reconstruct_many_stats.argtypes = [vp, C.POINTER(C.c_ulonglong), C.POINTER(C.c_ulonglong),
                                                             C.POINTER(C.c_ulonglong)]
+    if hasattr(lib, "mpvss_modp_group_lagrange_exponents"):   # (an A/B library of an older commit, MPVSS_HIP_LIB, does without the three)
+        lib.mpvss_ctx_set_rt_lagrange.argtypes = [vp, ci]
+        lib.mpvss_modp_group_lagrange_exponents.argtypes = [vp, vp, vp, sz, vp]
+        lib.mpvss_modp_group_lagrange_stats.argtypes = [vp, C.POINTER(C.c_ulonglong), C.POINTER(C.c_ulonglong),
+                                                        C.POINTER(C.c_ulonglong)]
     return lib
 
 
@@ -1028,6 +1034,30 @@ class Engine:
         """since the context was created: grouped passes, secrets that went through them, secrets that took the one-secret path"""
         return self._three_counters(self.lib.mpvss_modp_group_reconstruct_many_stats, "group_reconstruct_many_stats",
                                     ("passes", "grouped_secrets", "single_secrets"))
+
+    # ---- where the Lagrange exponents of a run-time group are computed, and the device path on its own -------------------------
+    def set_rt_lagrange(self, mode: int) -> int:
+        """mpvss_ctx_set_rt_lagrange: where group_reconstruct / group_reconstruct_many compute their Lagrange exponents -- 0 on the
+        host, 1 automatic, 2 on the device whenever the list is admitted.  Returns the mode before."""
+        before = self.lib.mpvss_ctx_set_rt_lagrange(self.ctx, int(mode))
+        if before < 0:
+            self._check(before, "set_rt_lagrange")
+        return before
+
+    def group_lagrange_exponents(self, grp: "ModpGroup", positions: Sequence[int]) -> bytes:
+        """the len(positions) exponents a share is raised to in group_reconstruct, elem_bytes each, big-endian, computed where the
+        context's mode says (set_rt_lagrange)"""
+        m = len(positions)
+        pos = (C.c_int64 * max(m, 1))(*positions)
+        ko, po = _out(grp.elem_bytes * m)
+        self._check(self.lib.mpvss_modp_group_lagrange_exponents(self.ctx, grp.handle, C.cast(pos, C.c_void_p), m, po),
+                    "group_lagrange_exponents")
+        return bytes(ko)[: grp.elem_bytes * m]
+
+    def group_lagrange_stats(self) -> dict:
+        """position lists whose exponents were computed on the device / on the host since the context was created, and those tried
+        on the device and done again on the host (counted under host too)"""
+        return self._three_counters(self.lib.mpvss_modp_group_lagrange_stats, "group_lagrange_stats", ("device", "host", "fallback"))
 
     # ---- sharded verification (one engine per GPU; see mpvss_rs_amd/sharding.py)
     def verify_block_compute(self, commitments: bytes, positions: Sequence[int], pubkeys: bytes, shares: bytes,

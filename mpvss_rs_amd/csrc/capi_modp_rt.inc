@@ -27,6 +27,7 @@ struct mpvss_modp_group {
   bool has_sh = false;       // (q-1)/2 >= 2^256, i.e. bits >= 258: hash_to_scalar is the identity on a SHA-256 output, so the per-share
                              // DLEQ hash may run on the device (k_rt_share_verdict does not reduce)
   uint8_t subR_be[RT_EB_MAX];// R mod q' = 2^(29 L) mod q', eb bytes big-endian (has_q): takes a coefficient into Montgomery form
+  uint8_t subm2_be[RT_EB_MAX];// q' - 2, eb bytes big-endian (has_q): Fermat's exponent of an inverse mod q' (rt_lagrange_dev)
   int bits = 0;
   int lpl = 0;
   size_t eb = 0;             // bytes of every element, scalar and exponent of this handle on the ABI: 256, 384 or 512
@@ -674,6 +675,7 @@ int rt_group_build(const RtNum q, int bits, size_t eb, int lpl, RtRings<NW> mpvs
   // the constants of q' for the device-side scalar ring: q' odd (q = 3 mod 4) and q' >= 3 (q >= 7) -- every safe prime above 5
   memset(&g->cq, 0, sizeof(g->cq));
   memset(g->subR_be, 0, sizeof(g->subR_be));
+  memset(g->subm2_be, 0, sizeof(g->subm2_be));
   g->has_q = (q[0] & 3) == 3 && (bits > 3 || q[0] >= 7);
   g->has_sh = bits >= 258;                       // q odd: (q-1)/2 >= 2^256  <=>  q >= 2^257 + 1  <=>  bits(q) >= 258
   if (g->has_q) {
@@ -683,6 +685,14 @@ int rt_group_build(const RtNum q, int bits, size_t eb, int lpl, RtRings<NW> mpvs
     rt_pow2_mod<NW>(k, 29 * L, R.sub);
     rt_limbs(k, g->cq.one_m, L);
     rt_to_be(k, g->subR_be, eb);
+    RtNum m2;                                    // q' - 2 (q' >= 3)
+    memcpy(m2, sub, sizeof(RtNum));
+    for (int i = 0, borrow = 2; i < RTW && borrow; ++i) {
+      const uint32_t before = m2[i];
+      m2[i] -= (uint32_t)borrow;
+      borrow = before < (uint32_t)borrow ? 1 : 0;
+    }
+    rt_to_be(m2, g->subm2_be, eb);
     g->cq.one[0] = 1;
     uint32_t qinv = sub[0];
     for (int i = 0; i < 5; ++i) qinv *= 2u - sub[0] * qinv;
@@ -1558,6 +1568,152 @@ bool rt_lagrange_exponent(const mpvss_modp_group* grp, const int64_t* positions,
   });
 }
 
+// ---- the same exponents on the device (DESIGN section 13, "Lagrange exponents on the device") -----------------------------------
+// A list longer than this keeps the host path: at these widths a launch at the curve groups' 2^20 would run for minutes.  Nobody
+// has measured above it.
+constexpr size_t RT_LAGRANGE_DEVICE_MAX_M = 16384;
+// Mode 1 of mpvss_ctx_set_rt_lagrange takes the device for a call whose work -- the sum of m^2 over its distinct position lists,
+// m^2 of a lone secret -- is at least this: the smallest measured work from which, at every measured shape at or above it and at
+// every measured width, the median of mode 2 lies below the minimum of mode 0 (tools/modp_rt_reconstruct_many.py --lagrange against
+// a build of the parent commit, fresh processes, profiles/modp_rt_lagrange_device.txt).  At 1024 and 2048 bits that is 60 secrets
+// of 32 shares with a list each, 60 x 32^2 (6.6 against 12.3 ms, 31.5 against 31.8 ms); every measured shape above it is faster on
+// the device (60 x 1024 with a list each 25 against 814 ms and 119 against 1 499 ms, one secret of 16 384 shares 89 ms against
+// 3.6 s), the four below it -- 9, 1 024, 1 156 and 3 600 -- are slower by the latency of one Fermat power, 3 and 15 ms.  At 3072
+// and 4096 bits only 60 x 1024 with a list each is measured (346 ms against 2.9 s, 892 ms against 4.6 s): automatic starts there.
+// Nothing between 3 600 and 61 440 is measured, nor anything below 1024 bits: automatic stays on the host below the figure.
+double rt_lagrange_min_work(int lpl) { return lpl > 18 ? 60.0 * 1024 * 1024 : 60.0 * 32 * 32; }
+
+// THE launch decision of the Lagrange exponents: `work` as above, the longest list and the coefficients of the call
+bool rt_lagrange_on_device(const mpvss_ctx* ctx, const mpvss_modp_group* grp, double work, size_t longest, size_t coefs) {
+  // (tile rows hold positions' and coefficients' indices in 32 bits)
+  if (ctx->rt_lagrange_mode == 0 || !grp->has_q || longest > RT_LAGRANGE_DEVICE_MAX_M || coefs >= 0x80000000u) return false;
+  return ctx->rt_lagrange_mode == 2 || work >= rt_lagrange_min_work(grp->lpl);
+}
+
+// The signs of a list's coefficients: lambda_i is negative for an odd number of positions below x_i, the parity of the rank of x_i
+// in the sorted list.  False: duplicate positions (what the quadratic host loop finds on its way).
+bool rt_lagrange_signs(const int64_t* pos, size_t m, char* neg) {
+  std::vector<std::pair<int64_t, size_t>> s(m);
+  for (size_t i = 0; i < m; ++i) s[i] = {pos[i], i};
+  std::sort(s.begin(), s.end());
+  for (size_t r = 0; r + 1 < m; ++r)
+    if (s[r].first == s[r + 1].first) return false;
+  for (size_t r = 0; r < m; ++r) neg[s[r].second] = (char)(r & 1);
+  return true;
+}
+
+constexpr size_t RT_LAGRANGE_TILE = 16;            // RT_NUMS of modp_rt_kernels.inc: coefficients of a tile, slots of a workgroup
+
+// a list of a launch: where it starts in the launch's positions (and coefficients), its length, its positions
+struct RtLagrangeList {
+  size_t first, m;
+  const int64_t* pos;
+};
+
+// The exponents of the admitted lists `lists` (positions >= 1 and pairwise different, signs in negs) of a launch whose `total`
+// positions lie back to back in all_pos: exps_dev[c] (EB bytes) for coefficient c = position c.  The frame has begun with the
+// constants of q'.  Tiles travel in chunks of at most MAX_CHUNK slots, 16 per tile, over the context's workspaces: numerators and
+// denominators in rt_tab1, the denominators' bytes and inverses in rt_out[1] and rt_out[2], their tables in rt_tab2 --
+// k_rt_lagrange_terms, k_rt_table, k_rt_dual_exp with q' - 2 at stride 0, k_rt_lagrange_finish, all timed as kind 4.  A list with
+// a failed flag (a denominator without Fermat inverse: 0 mod a small q', or a composite q') is recomputed WHOLE by
+// rt_lagrange_exponent, which decides between a value and a refusal (list_ok[l] = 0); its exponents are uploaded into its slice.
+// Counts the lists.  Synchronous: the stream is drained on every way out, so all_pos and negs need not outlive the call.
+int rt_lagrange_dev(RtCall& f, DevBuf& pos_buf, DevBuf& tile_buf, DevBuf& neg_buf, const int64_t* all_pos, const char* negs, size_t total,
+                    const std::vector<RtLagrangeList>& lists, uint8_t* exps_dev, std::vector<char>& list_ok) {
+  mpvss_ctx* ctx = f.ctx;
+  const mpvss_modp_group* grp = f.grp;
+  const size_t EB = grp->eb, L = rt_L(grp);
+  std::vector<uint32_t> tiles;
+  std::vector<uint8_t> flags(total, 1), redo;
+  StreamDrain drain{ctx};
+  for (const RtLagrangeList& l : lists)
+    for (size_t off = 0; off < l.m; off += RT_LAGRANGE_TILE) {
+      const uint32_t row[4] = {(uint32_t)l.first, (uint32_t)l.m, (uint32_t)(l.first + off), (uint32_t)std::min(l.m - off, RT_LAGRANGE_TILE)};
+      tiles.insert(tiles.end(), row, row + 4);
+    }
+  const size_t ntiles = tiles.size() / 4;
+  if (ntiles == 0) return MPVSS_OK;
+  const size_t chunk_tiles = std::min(ntiles, std::max<size_t>(MAX_CHUNK / RT_LAGRANGE_TILE, 1)), slots = chunk_tiles * RT_LAGRANGE_TILE;
+  RET_IF(ensure(ctx, pos_buf, total * 8));
+  RET_IF(ensure(ctx, tile_buf, tiles.size() * 4));
+  RET_IF(ensure(ctx, neg_buf, total));
+  RET_IF(ensure(ctx, ctx->rt_lag_flags, total));
+  RET_IF(ensure(ctx, ctx->rt_lag_e, EB));
+  RET_IF(ensure(ctx, ctx->rt_tab1, 2 * slots * L * 4));
+  RET_IF(ensure(ctx, ctx->rt_tab2, slots * 16 * L * 4));
+  RET_IF(ensure(ctx, ctx->rt_out[1], slots * EB));
+  RET_IF(ensure(ctx, ctx->rt_out[2], slots * EB));
+  HIPCHK(ctx, hipMemcpyAsync(pos_buf.p, all_pos, total * 8, hipMemcpyHostToDevice, ctx->stream));
+  HIPCHK(ctx, hipMemcpyAsync(tile_buf.p, tiles.data(), tiles.size() * 4, hipMemcpyHostToDevice, ctx->stream));
+  HIPCHK(ctx, hipMemcpyAsync(neg_buf.p, negs, total, hipMemcpyHostToDevice, ctx->stream));
+  HIPCHK(ctx, hipMemcpyAsync(ctx->rt_lag_e.p, grp->subm2_be, EB, hipMemcpyHostToDevice, ctx->stream));
+  uint32_t* num_m = (uint32_t*)ctx->rt_tab1.p;
+  uint32_t* den_m = num_m + slots * L;
+  uint32_t* tab = (uint32_t*)ctx->rt_tab2.p;
+  uint8_t* den_be = (uint8_t*)ctx->rt_out[1].p;
+  uint8_t* dinv_be = (uint8_t*)ctx->rt_out[2].p;
+  for (size_t t0 = 0; t0 < ntiles; t0 += chunk_tiles) {
+    const int nt = (int)std::min(chunk_tiles, ntiles - t0), ns = nt * (int)RT_LAGRANGE_TILE;
+    const uint32_t* rows = (const uint32_t*)tile_buf.p + 4 * t0;
+    TIMED_LAUNCH(ctx, 4, modp_rt_launch_lagrange_terms(grp->lpl, (const int64_t*)pos_buf.p, rows, nt, num_m, den_m, den_be, f.dcq, ctx->stream));
+    TIMED_LAUNCH(ctx, 4, modp_rt_launch_table(grp->lpl, den_be, EB, ns, tab, f.dcq, ctx->stream));
+    TIMED_LAUNCH(ctx, 4, modp_rt_launch_dual_exp(grp->lpl, tab, 16 * L, nullptr, 0, (const uint8_t*)ctx->rt_lag_e.p, 0, nullptr, 0, ns, dinv_be,
+                                                 f.dcq, ctx->stream));                                  // den^(q'-2)
+    TIMED_LAUNCH(ctx, 4, modp_rt_launch_lagrange_finish(grp->lpl, rows, nt, num_m, den_m, dinv_be, (const uint8_t*)neg_buf.p, exps_dev,
+                                                        (uint8_t*)ctx->rt_lag_flags.p, f.dcq, ctx->stream));
+  }
+  for (const RtLagrangeList& l : lists)                  // (only the slices of the launch's lists were written)
+    HIPCHK(ctx, hipMemcpyAsync(flags.data() + l.first, (const uint8_t*)ctx->rt_lag_flags.p + l.first, l.m, hipMemcpyDeviceToHost, ctx->stream));
+  HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+  for (size_t k = 0; k < lists.size(); ++k) {
+    const RtLagrangeList& l = lists[k];
+    const uint8_t* fl = flags.data() + l.first;
+    if (std::find(fl, fl + l.m, 0) == fl + l.m) {
+      ++ctx->rt_lagrange_dev_lists;
+      continue;
+    }
+    redo.resize(l.m * EB);
+    char sign;
+    bool ok = true;
+    for (size_t i = 0; i < l.m && ok; ++i) ok = rt_lagrange_exponent(grp, l.pos, l.m, i, redo.data() + i * EB, &sign);
+    list_ok[k] = ok ? 1 : 0;
+    if (!ok) continue;
+    HIPCHK(ctx, hipMemcpyAsync(exps_dev + l.first * EB, redo.data(), l.m * EB, hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));       // (redo is filled again by the next such list)
+    ++ctx->rt_lagrange_fallback_lists;
+    ++ctx->rt_lagrange_host_lists;
+  }
+  return MPVSS_OK;
+}
+
+const char* const RT_NO_LAGRANGE = "group_reconstruct: duplicate positions, or a Lagrange coefficient whose denominator in lowest terms has no inverse mod (q-1)/2";
+
+// the m exponents and signs of one list computed here, on the host (into exps_own) or on the device (into rt_in[1], which
+// k_rt_dual_exp reads its exponents from: *exps_dev)
+int rt_lagrange_one(RtCall& f, const int64_t* positions_host, size_t m, std::vector<uint8_t>& exps_own, std::vector<char>& neg_own,
+                    const uint8_t** exps_dev) {
+  mpvss_ctx* ctx = f.ctx;
+  const size_t EB = f.grp->eb;
+  neg_own.assign(m, 0);
+  if (rt_lagrange_on_device(ctx, f.grp, (double)m * (double)m, m, m)) {
+    if (!rt_lagrange_signs(positions_host, m, neg_own.data())) return fail(ctx, MPVSS_E_INVALID, RT_NO_LAGRANGE);
+    RET_IF(f.begin(RtCall::SubQ));
+    uint8_t* dE = f.work(ctx->rt_in[1], m);
+    RET_IF(f.rc);
+    std::vector<char> list_ok(1, 1);
+    RET_IF(rt_lagrange_dev(f, ctx->rt_lag_pos, ctx->rt_lag_tiles, ctx->rt_lag_neg, positions_host, neg_own.data(), m,
+                           {RtLagrangeList{0, m, positions_host}}, dE, list_ok));
+    if (!list_ok[0]) return fail(ctx, MPVSS_E_INVALID, RT_NO_LAGRANGE);
+    *exps_dev = dE;
+    return MPVSS_OK;
+  }
+  exps_own.resize(m * EB);
+  for (size_t i = 0; i < m; ++i)
+    if (!rt_lagrange_exponent(f.grp, positions_host, m, i, exps_own.data() + i * EB, &neg_own[i])) return fail(ctx, MPVSS_E_INVALID, RT_NO_LAGRANGE);
+  ++ctx->rt_lagrange_host_lists;
+  return MPVSS_OK;
+}
+
 // int_BE(SHA256(element_to_bytes(G^s))) mod q (participant.rs:512-515): the reduction matters for q below 2^256
 void rt_secret_mask(const mpvss_modp_group* grp, const uint8_t* gs, uint8_t* mask_out32) {
   const size_t EB = grp->eb;
@@ -1582,9 +1738,11 @@ void rt_secret_mask(const mpvss_modp_group* grp, const uint8_t* gs, uint8_t* mas
 // lowest terms before its denominator is inverted (:546-553), which matters only for a (q-1)/2 small enough to divide a position
 // or a difference of two: lagrange_at_zero does so where the raw denominator has no inverse.
 // The body of mpvss_modp_group_reconstruct (context lock held, the group checked).  exps_pre / neg_pre: the m exponents and signs
-// when the caller has them already (mpvss_modp_group_reconstruct_many computed them with the call's other position lists).
+// when the caller has them already (mpvss_modp_group_reconstruct_many computed them with the call's other position lists), the
+// exponents in host memory (exps_pre) or in device memory (exps_dev); else they are computed here, on the host or on the device.
 int rt_reconstruct_locked(mpvss_ctx* ctx, const mpvss_modp_group* grp, int space, const int64_t* positions_host, const uint8_t* shares,
-                          size_t m, uint8_t* gs_out256, uint8_t* mask_out32, const uint8_t* exps_pre, const char* neg_pre) {
+                          size_t m, uint8_t* gs_out256, uint8_t* mask_out32, const uint8_t* exps_pre, const char* neg_pre,
+                          const uint8_t* exps_dev = nullptr) {
   const size_t EB = grp->eb;
   if (!positions_host || !shares || m == 0 || !gs_out256 || m > 0x7fffffff)
     return fail(ctx, MPVSS_E_INVALID, "group_reconstruct: bad argument");
@@ -1594,15 +1752,9 @@ int rt_reconstruct_locked(mpvss_ctx* ctx, const mpvss_modp_group* grp, int space
   std::vector<uint8_t> exps_own, hs;
   RtCall f(ctx, grp, space);
   RET_IF(f.begin());
-  if (!exps_pre) {
-    neg_own.assign(m, 0);
-    exps_own.resize(m * EB);
-    for (size_t i = 0; i < m; ++i)
-      if (!rt_lagrange_exponent(grp, positions_host, m, i, exps_own.data() + i * EB, &neg_own[i]))
-        return fail(ctx, MPVSS_E_INVALID, "group_reconstruct: duplicate positions, or a Lagrange coefficient whose denominator in lowest terms has no inverse mod (q-1)/2");
-  }
+  if (!exps_pre && !exps_dev) RET_IF(rt_lagrange_one(f, positions_host, m, exps_own, neg_own, &exps_dev));
   const uint8_t* exps = exps_pre ? exps_pre : exps_own.data();
-  const char* neg = exps_pre ? neg_pre : neg_own.data();
+  const char* neg = neg_pre ? neg_pre : neg_own.data();
   // a share that is 0 mod q has no inverse: the reference returns None when its coefficient is negative (:551-553)
   const uint8_t* S = f.host_view(shares, 0, m, hs);
   RET_IF(f.host_ready());
@@ -1610,7 +1762,7 @@ int rt_reconstruct_locked(mpvss_ctx* ctx, const mpvss_modp_group* grp, int space
     if (neg[i] && rt_zero_mod_q(grp, S + i * EB))
       return fail(ctx, MPVSS_E_INVALID, "group_reconstruct: a share is 0 mod q and has no inverse");
   const uint8_t* dS = f.in(shares, 0, m, ctx->rt_in[0], RtCall::Public);
-  const uint8_t* dE = f.in_host(exps, m, ctx->rt_in[1], RtCall::Public);
+  const uint8_t* dE = exps_dev ? exps_dev : f.in_host(exps, m, ctx->rt_in[1], RtCall::Public);
   uint8_t* dF = f.work(ctx->rt_out[0], m);
   RET_IF(f.rc);
   const uint32_t* tb;
@@ -2181,8 +2333,8 @@ namespace {
 // is 0 mod q under a negative coefficient is refused here (the one copy back of a pass in device space shows it): its powers run
 // with the others, its result is dropped.
 int rt_reconstruct_pass(mpvss_ctx* ctx, const mpvss_modp_group* grp, int space, const mpvss_modp_group_secret* secrets,
-                        const std::vector<size_t>& run, const std::vector<many::SecretPlan>& plan, const uint8_t* exps, const char* negs,
-                        int host_threads, int* status, uint8_t* gs_out, uint8_t* masks_out32) {
+                        const std::vector<size_t>& run, const std::vector<many::SecretPlan>& plan, const uint8_t* exps,
+                        const uint8_t* exps_dev, const char* negs, int host_threads, int* status, uint8_t* gs_out, uint8_t* masks_out32) {
   const size_t B = run.size(), EB = grp->eb;
   std::vector<uint32_t> segs(2 * B);                                // {first factor, m} of every secret
   std::vector<size_t> first(B + 1);
@@ -2195,8 +2347,9 @@ int rt_reconstruct_pass(mpvss_ctx* ctx, const mpvss_modp_group* grp, int space, 
   }
   first[B] = S;
   // host sources of asynchronous copies and the results read back: declared before the frame, whose way out drains the stream
-  std::vector<uint8_t> g_sh, g_exp(S * EB), h_sh, h_gs;
-  for (size_t k = 0; k < B; ++k) memcpy(g_exp.data() + first[k] * EB, exps + plan[run[k]].coef * EB, secrets[run[k]].m * EB);
+  std::vector<uint8_t> g_sh, g_exp(exps_dev ? 0 : S * EB), h_sh, h_gs;
+  if (!exps_dev)
+    for (size_t k = 0; k < B; ++k) memcpy(g_exp.data() + first[k] * EB, exps + plan[run[k]].coef * EB, secrets[run[k]].m * EB);
   RtCall f(ctx, grp, space);
   StreamDrain drain{ctx};
   RET_IF(f.begin());
@@ -2220,10 +2373,15 @@ int rt_reconstruct_pass(mpvss_ctx* ctx, const mpvss_modp_group* grp, int space, 
       if (neg[i] && rt_zero_mod_q(grp, Sv + (first[k] + i) * EB)) refused[k] = 1;
     if (!refused[k]) ++good;
   }
-  const uint8_t* dE = f.in_host(g_exp.data(), S, ctx->rt_in[1], RtCall::Public);
+  // the exponents: the host's, or gathered device to device from the call's coefficient buffer, one copy per secret
+  const uint8_t* dE = exps_dev ? f.work(ctx->rt_in[1], S) : f.in_host(g_exp.data(), S, ctx->rt_in[1], RtCall::Public);
   uint8_t* dF = f.work(ctx->rt_out[0], S);
   uint8_t* dG = f.work(ctx->rt_out[1], B);
   RET_IF(f.rc);
+  if (exps_dev)
+    for (size_t k = 0; k < B; ++k)
+      HIPCHK(ctx, hipMemcpyAsync((uint8_t*)ctx->rt_in[1].p + first[k] * EB, exps_dev + plan[run[k]].coef * EB, secrets[run[k]].m * EB,
+                                 hipMemcpyDeviceToDevice, ctx->stream));
   RET_IF(ensure(ctx, ctx->rt_run_boxes, segs.size() * 4));
   HIPCHK(ctx, hipMemcpyAsync(ctx->rt_run_boxes.p, segs.data(), segs.size() * 4, hipMemcpyHostToDevice, ctx->stream));
   RET_IF(ensure(ctx, ctx->rt_tab1, S * rt_L(grp) * 4));
@@ -2271,33 +2429,133 @@ extern "C" int mpvss_modp_group_reconstruct_many(mpvss_ctx* ctx, const mpvss_mod
   if (masks_out32) memset(masks_out32, 0, 32 * count);
 
   // the Lagrange exponents and their signs ONCE per distinct position list (a list without them has duplicate positions, or a
-  // denominator without inverse -- an even (q-1)/2 among the causes: its secrets are refused)
+  // denominator without inverse -- an even (q-1)/2 among the causes: its secrets are refused): on the host threads of the call, or
+  // by ONE pass of launches over all lists into a buffer of the context that the passes gather from
+  many::SecretPlans lists = many::plan_lists(secrets, count, RT_GROUP_BOX_MAX, MAX_CHUNK);
+  double work = 0;
+  for (const size_t lm : lists.list_m) work += (double)lm * (double)lm;
+  const bool on_device = !lists.list_m.empty() &&
+                         rt_lagrange_on_device(ctx, grp, work, *std::max_element(lists.list_m.begin(), lists.list_m.end()), lists.coefs);
   std::vector<uint8_t> exps;
   std::vector<char> negs;
-  const std::vector<many::SecretPlan> plan =
-      many::plan_secrets(secrets, count, RT_GROUP_BOX_MAX, MAX_CHUNK, host_threads,
-                         [&](size_t coefs) {
-                           exps.resize(coefs * EB);
-                           negs.assign(coefs, 0);
-                         },
-                         [&](const int64_t* pos, size_t m, size_t j, size_t c) { return rt_lagrange_exponent(grp, pos, m, j, exps.data() + c * EB, &negs[c]); })
-          .secret;
+  const uint8_t* exps_dev = nullptr;
+  ctx->call_spans.spans.clear();
+  ctx->call_spans.ev_used = 0;
+  if (on_device) {
+    negs.assign(lists.coefs, 0);
+    std::vector<char> list_ok(lists.list_m.size(), 0);
+    hsc::parallel_for(list_ok.size(), many::many_threads(host_threads, lists.coefs, 4096), [&](size_t lo, size_t hi) {
+      for (size_t l = lo; l < hi; ++l)
+        list_ok[l] = rt_lagrange_signs(lists.list_pos[l], lists.list_m[l], negs.data() + lists.list_first[l]) ? 1 : 0;
+    });
+    std::vector<int64_t> all_pos(lists.coefs);               // coefficient c belongs to position c; a refused list has no tile
+    std::vector<RtLagrangeList> admitted;
+    std::vector<size_t> admitted_l;
+    for (size_t l = 0; l < list_ok.size(); ++l) {
+      memcpy(all_pos.data() + lists.list_first[l], lists.list_pos[l], lists.list_m[l] * 8);
+      if (!list_ok[l]) continue;
+      admitted.push_back(RtLagrangeList{lists.list_first[l], lists.list_m[l], lists.list_pos[l]});
+      admitted_l.push_back(l);
+    }
+    if (!admitted.empty()) {
+      struct SpanGuard {                                     // the launches' spans outlive the passes, which reset the main ones
+        mpvss_ctx* c;
+        ~SpanGuard() { c->sp = &c->main_spans; }
+      } guard{ctx};
+      ctx->sp = &ctx->call_spans;
+      RtCall f(ctx, grp, space);
+      RET_IF(f.begin(RtCall::SubQ));
+      RET_IF(ensure(ctx, ctx->rt_lag_call_exp, lists.coefs * EB));
+      std::vector<char> ok(admitted.size(), 1);
+      RET_IF(rt_lagrange_dev(f, ctx->rt_lag_call_pos, ctx->rt_lag_call_tiles, ctx->rt_lag_call_neg, all_pos.data(), negs.data(), lists.coefs,
+                             admitted, (uint8_t*)ctx->rt_lag_call_exp.p, ok));
+      for (size_t k = 0; k < ok.size(); ++k) list_ok[admitted_l[k]] = ok[k];
+    }
+    many::plan_settle(lists, list_ok);
+    exps_dev = (const uint8_t*)ctx->rt_lag_call_exp.p;
+  } else {
+    many::plan_host_coefficients(lists, host_threads,
+                                 [&](size_t coefs) {
+                                   exps.resize(coefs * EB);
+                                   negs.assign(coefs, 0);
+                                 },
+                                 [&](const int64_t* pos, size_t m, size_t j, size_t c) { return rt_lagrange_exponent(grp, pos, m, j, exps.data() + c * EB, &negs[c]); });
+    std::vector<char> counted(lists.list_m.size(), 0);
+    for (size_t i = 0; i < count; ++i)
+      if (lists.secret[i].kind == many::SECRET_GROUPED && !counted[lists.list_of[i]]) {
+        counted[lists.list_of[i]] = 1;
+        ++ctx->rt_lagrange_host_lists;
+      }
+  }
+  const std::vector<many::SecretPlan>& plan = lists.secret;
   // A code of the one-secret path other than MPVSS_E_INVALID (which refuses that secret alone) ends the call.
   auto single = [&](size_t i) -> int {
     const mpvss_modp_group_secret& s = secrets[i];
-    const bool pre = plan[i].coef != (size_t)-1;
+    const bool pre = plan[i].coef != (size_t)-1;             // a run of one: its list's exponents are there already
     const int rc = rt_reconstruct_locked(ctx, grp, space, s.positions_host, s.shares, s.m, gs_out + i * EB,
-                                         masks_out32 ? masks_out32 + 32 * i : nullptr, pre ? exps.data() + plan[i].coef * EB : nullptr,
-                                         pre ? negs.data() + plan[i].coef : nullptr);
+                                         masks_out32 ? masks_out32 + 32 * i : nullptr,
+                                         pre && !exps_dev ? exps.data() + plan[i].coef * EB : nullptr, pre ? negs.data() + plan[i].coef : nullptr,
+                                         pre && exps_dev ? exps_dev + plan[i].coef * EB : nullptr);
     if (rc == MPVSS_E_INVALID) return MPVSS_OK;
     RET_IF(rc);
     status[i] = MPVSS_OK;
     ++ctx->rt_rec_single_secrets;
     return MPVSS_OK;
   };
-  return many::walk_secrets(secrets, plan, MAX_CHUNK, single, [&](const std::vector<size_t>& run) {
-    return rt_reconstruct_pass(ctx, grp, space, secrets, run, plan, exps.data(), negs.data(), host_threads, status, gs_out, masks_out32);
-  });
+  RET_IF(many::walk_secrets(secrets, plan, MAX_CHUNK, single, [&](const std::vector<size_t>& run) {
+    return rt_reconstruct_pass(ctx, grp, space, secrets, run, plan, exps.data(), exps_dev, negs.data(), host_threads, status, gs_out, masks_out32);
+  }));
+  if (!ctx->call_spans.spans.empty()) {                       // the coefficient launches among the kernel times of the call's last pass
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    double sum = 0;
+    for (auto& sp : ctx->call_spans.spans) {
+      float ms = 0;
+      HIPCHK(ctx, hipEventElapsedTime(&ms, sp.a, sp.b));
+      sum += ms;
+    }
+    ctx->kernel_ms[4] = (ctx->kernel_ms[4] > 0 ? ctx->kernel_ms[4] : 0) + sum;
+    ctx->kernel_launches[4] += (int)ctx->call_spans.spans.size();
+  }
+  return MPVSS_OK;
+}
+
+// ---- where the Lagrange exponents of a run-time group are computed, and the device path on its own ------------------------------
+extern "C" int mpvss_ctx_set_rt_lagrange(mpvss_ctx* ctx, int mode) {
+  if (!ctx) return MPVSS_E_INVALID;
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  if (mode < 0 || mode > 2) return fail(ctx, MPVSS_E_INVALID, "set_rt_lagrange: mode is 0, 1 or 2");
+  const int before = ctx->rt_lagrange_mode;
+  ctx->rt_lagrange_mode = mode;
+  return before;
+}
+
+extern "C" int mpvss_modp_group_lagrange_stats(mpvss_ctx* ctx, unsigned long long* device_lists, unsigned long long* host_lists,
+                                               unsigned long long* fallback_lists) {
+  return many_stats(ctx, &mpvss_ctx::rt_lagrange_dev_lists, &mpvss_ctx::rt_lagrange_host_lists, &mpvss_ctx::rt_lagrange_fallback_lists,
+                    device_lists, host_lists, fallback_lists);
+}
+
+extern "C" int mpvss_modp_group_lagrange_exponents(mpvss_ctx* ctx, const mpvss_modp_group* grp, const int64_t* positions_host, size_t m,
+                                                   uint8_t* exps_out_host) {
+  if (!ctx) return MPVSS_E_INVALID;
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  if (rt_bad_group(grp)) return fail(ctx, MPVSS_E_INVALID, "group_lagrange_exponents: no group");
+  if (!positions_host || !exps_out_host || m == 0 || m > 0x7fffffff) return fail(ctx, MPVSS_E_INVALID, "group_reconstruct: bad argument");
+  for (size_t i = 0; i < m; ++i)
+    if (positions_host[i] < 1) return fail(ctx, MPVSS_E_INVALID, "group_reconstruct: positions must be >= 1 (util.rs:47-64)");
+  std::vector<char> neg;
+  std::vector<uint8_t> exps;                                 // the output stays untouched by a refused call
+  RtCall f(ctx, grp, MPVSS_HOST);
+  RET_IF(f.begin(0));
+  const uint8_t* exps_dev = nullptr;
+  RET_IF(rt_lagrange_one(f, positions_host, m, exps, neg, &exps_dev));
+  if (exps_dev) {
+    f.to_host(exps_dev, m, exps);
+    RET_IF(f.settle());
+  }
+  RET_IF(f.end());
+  memcpy(exps_out_host, exps.data(), m * grp->eb);
+  return MPVSS_OK;
 }
 
 extern "C" int mpvss_modp_group_reconstruct_many_stats(mpvss_ctx* ctx, unsigned long long* passes, unsigned long long* grouped_secrets,

@@ -31,6 +31,9 @@ static inline __host__ __device__ void modp_rt_fd_chain(int n, int S, int c, int
   *len = (int)(b - a);
 }
 
+/* k_rt_lagrange_terms: steps of a position list staged through LDS at a time (one position more than steps) */
+#define MODP_RT_LAGRANGE_STAGE 256
+
 #ifdef __cplusplus
 extern "C" {
 #endif

@@ -1201,6 +1201,156 @@ __global__ void RT_KERNEL(LPL) k_rt_modq_poly_eval(const u32* __restrict__ coef_
   store_canonical_lift<LPL>(out_be + (size_t)x * EB, acc, slot, cs, ln, live, (pos & 1) ? par_odd : par_even);
 }
 
+// =======================================================================================
+// The Lagrange exponents of reconstruct on the device (capi_modp_rt.inc, "Lagrange exponents on the device"): for a list of m
+// positions, |lambda_i| = prod_{j != i} x_j / prod_{j != i} |x_j - x_i| mod q', written as the exponent the host writes
+// (rt_lagrange_exponent).  `cs` is the image of the constants of q' throughout.  Three steps, all on tiles of up to RT_NUMS
+// coefficients of ONE list (rows {the list's first position, m, the tile's first coefficient, live quads}; workgroup w of a launch
+// serves row w and owns the slots 16 w .. 16 w + 15 of the launch's work arrays, dead quads included):
+//   k_rt_lagrange_terms   numerator and denominator of every coefficient, the denominator also as canonical bytes;
+//   k_rt_table + k_rt_dual_exp with the one exponent q' - 2 over those bytes: den^(q'-2), the inverse when q' is prime (Fermat);
+//   k_rt_lagrange_finish  checks den den^-1 = 1, forms the magnitude and stores the exponent.
+// Bounds, the cancellation and the product counts: tests/test_modp_rt_lagrange_model.py.
+// =======================================================================================
+
+// Quad i starts both accumulators from R mod q' and takes m - 1 steps: step j multiplies x_jj into the numerator and |x_jj - x_i|
+// into the denominator, jj = j for j < i and j + 1 from there on (its own index is skipped, every quad of the wave takes the same
+// number of steps).  A factor is below 2^63: three 29-bit limbs in an operand of LPL limbs, one quarter product
+// (bn::mont_mul<.., OUTER = 1>) -- acc <- acc f 2^(-29 LPL), below q' + 2 q' 2^87 / 2^(29 LPL) < 2 q'.  Both accumulators carry
+// the same stray 2^(-29 LPL (m-1)): it cancels in the quotient.  The list's positions pass through LDS MODP_RT_LAGRANGE_STAGE
+// steps at a time (one position more than steps: the shifted index); nothing at or past first + m is read.  Loop bounds and
+// barriers are wave-uniform; a dead quad works on the tile's last live coefficient and writes a slot nobody reads back.
+template <int LPL>
+__global__ void RT_KERNEL(LPL) k_rt_lagrange_terms(const int64_t* __restrict__ positions, const uint4* __restrict__ tiles,
+                                                   u32* __restrict__ num_m, u32* __restrict__ den_m, uint8_t* __restrict__ den_be,
+                                                   const modp_rt_consts* __restrict__ cs) {
+  constexpr int L = Width<LPL>::L, SLOT = Width<LPL>::SLOT, EB = Width<LPL>::EB, STAGE = MODP_RT_LAGRANGE_STAGE;
+  static_assert(2 * LPL + LPL + 1 <= SLOT, "two operands of LPL limbs (and the prefetched word after each) in one slot");
+  __shared__ __attribute__((aligned(16))) u32 lds[RT_NUMS * SLOT];
+  __shared__ int64_t stage[STAGE + 1];
+  const Lane ln = make_lane();
+  const uint4 tile = tiles[blockIdx.x];
+  const u32 first = tile.x, m = tile.y, live = tile.w;
+  const int quad = threadIdx.x >> 2;
+  const u32 i = tile.z - first + ((u32)quad < live ? (u32)quad : live - 1);      // this quad's index in its list, < m
+  const size_t sl = (size_t)blockIdx.x * RT_NUMS + quad;
+  u32* slot = lds + quad * SLOT;
+  u32* opn = slot;
+  u32* opd = slot + 2 * LPL;
+  const u32 n0inv = cs->n0inv;
+  const u64 xi = (u64)positions[(size_t)first + i];
+  u32 n[LPL], num[LPL], den[LPL];
+  load_lane_limbs<LPL>(n, cs->n, ln);
+#pragma unroll
+  for (int k = 0; k < LPL; ++k) num[k] = 0;
+  slot_store<LPL>(slot, num, ln);                        // limbs 3 .. LPL of both operands stay 0
+  load_lane_limbs<LPL>(num, cs->one_m, ln);
+#pragma unroll
+  for (int k = 0; k < LPL; ++k) den[k] = num[k];
+  const u32 steps = m - 1;
+  for (u32 base = 0; base < steps; base += STAGE) {
+    const u32 cnt = steps - base < (u32)STAGE ? steps - base : (u32)STAGE;
+    for (u32 k = threadIdx.x; k <= cnt; k += 64) stage[k] = positions[(size_t)first + base + k];   // base + cnt <= m - 1
+    __syncthreads();
+#pragma nounroll
+    for (u32 k = 0; k < cnt; ++k) {
+      const u64 xj = (u64)stage[k + (base + k >= i ? 1u : 0u)];
+      u64 d = xj - xi;                                   // |x_j - x_i| < 2^63: both lie in [1, 2^63)
+      if ((int64_t)d < 0) d = 0 - d;
+      if (ln.q < 3) {
+        opn[ln.q] = (u32)(xj >> (W * ln.q)) & MASK;
+        opd[ln.q] = (u32)(d >> (W * ln.q)) & MASK;
+      }
+      __builtin_amdgcn_wave_barrier();
+      mont_mul<N0INV_RUNTIME, false, 1>(num, num, opn, n, ln, n0inv);
+      mont_mul<N0INV_RUNTIME, false, 1>(den, den, opd, n, ln, n0inv);
+      __builtin_amdgcn_wave_barrier();
+    }
+    __syncthreads();
+  }
+  store_lane_limbs<LPL>(num_m + sl * L, num, ln);
+  store_lane_limbs<LPL>(den_m + sl * L, den, ln);
+  store_canonical<LPL>(den_be + sl * EB, den, slot, cs, ln, true);
+}
+
+// store_canonical_lift with a sign instead of a parity: the residue mag in [0, q') leaves as the exponent the host writes, mag
+// itself, or (q - 1) - mag = 2 q' - mag for a negative coefficient of nonzero magnitude (the residue -mag mod q', plus q')
+template <int LPL>
+__device__ __forceinline__ void store_canonical_signed(uint8_t* __restrict__ out, const u32 (&a)[LPL], u32* slot,
+                                                       const modp_rt_consts* __restrict__ cs, const Lane& ln, bool write, bool negative) {
+  constexpr int L = Width<LPL>::L, EB = Width<LPL>::EB, WPL = EB / 16;
+  slot_store<LPL>(slot, a, ln);
+  __builtin_amdgcn_wave_barrier();
+  if (ln.q == 0) {
+    limbs::slot_canonicalize<L>(slot, cs->n);
+    u32 any = 0;
+#pragma nounroll
+    for (int j = 0; j < L; ++j) any |= slot[j];
+    if (negative && any) {
+      int64_t c = 0;
+#pragma nounroll
+      for (int j = 0; j < L; ++j) {
+        const int64_t t = 2 * (int64_t)cs->n[j] - (int64_t)slot[j] + c;
+        slot[j] = (u32)t & MASK;
+        c = t >> W;
+      }
+    }
+  }
+  __builtin_amdgcn_wave_barrier();
+  if (write) {
+    u32* out32 = reinterpret_cast<u32*>(out);
+#pragma unroll
+    for (int i = 0; i < WPL; ++i) {
+      const int wd = (int)ln.q * WPL + i;
+      out32[4 * WPL - 1 - wd] = __builtin_bswap32(limbs::slot_word32<L, EB>(slot, wd));
+    }
+  }
+  __builtin_amdgcn_wave_barrier();
+}
+
+// exps[c] and flags[c] of every live coefficient c of the tiles from the work arrays of k_rt_lagrange_terms and dinv = den^(q'-2):
+// dinv R by the entry product, then den dinv (the check) and num dinv (the magnitude; the stray power has cancelled), both out of
+// the Montgomery domain.  flags[c] = 1 iff den dinv is 1 mod q': then dinv IS the inverse, whatever q' is; a denominator that is 0
+// mod a small q', or a composite q' where Fermat's power is no inverse, gives 0 and the host recomputes the list.  1 entry
+// product + 2.  neg[c]: the sign of coefficient c (host: the parity of the rank of x_i in its sorted list).
+template <int LPL>
+__global__ void RT_KERNEL(LPL) k_rt_lagrange_finish(const uint4* __restrict__ tiles, const u32* __restrict__ num_m,
+                                                    const u32* __restrict__ den_m, const uint8_t* __restrict__ dinv_be,
+                                                    const uint8_t* __restrict__ neg, uint8_t* __restrict__ exps, uint8_t* __restrict__ flags,
+                                                    const modp_rt_consts* __restrict__ cs) {
+  constexpr int L = Width<LPL>::L, SLOT = Width<LPL>::SLOT, EB = Width<LPL>::EB;
+  __shared__ __attribute__((aligned(16))) u32 lds[RT_NUMS * SLOT];
+  const Lane ln = make_lane();
+  const uint4 tile = tiles[blockIdx.x];
+  const int quad = threadIdx.x >> 2;
+  const bool live = (u32)quad < tile.w;
+  const size_t c = (size_t)tile.z + (live ? (u32)quad : tile.w - 1);
+  const size_t sl = (size_t)blockIdx.x * RT_NUMS + quad;
+  u32* slot = lds + quad * SLOT;
+  const u32 n0inv = cs->n0inv;
+  u32 n[LPL], acc[LPL], v[LPL];
+  load_lane_limbs<LPL>(n, cs->n, ln);
+  to_mont_in<LPL>(v, slot, dinv_be + sl * EB, cs, n, n0inv, ln);
+  slot_store<LPL>(slot, v, ln);
+  load_lane_limbs<LPL>(acc, den_m + sl * L, ln);
+  load_lane_limbs<LPL>(v, num_m + sl * L, ln);
+  __builtin_amdgcn_wave_barrier();
+  mont_mul<N0INV_RUNTIME>(acc, acc, slot, n, ln, n0inv);           // den dinv
+  mont_mul<N0INV_RUNTIME>(v, v, slot, n, ln, n0inv);               // num dinv
+  __builtin_amdgcn_wave_barrier();
+  slot_store<LPL>(slot, acc, ln);
+  __builtin_amdgcn_wave_barrier();
+  if (ln.q == 0) {
+    limbs::slot_canonicalize<L>(slot, cs->n);
+    u32 rest = slot[0] ^ 1u;
+#pragma nounroll
+    for (int j = 1; j < L; ++j) rest |= slot[j];
+    if (live) flags[c] = rest == 0 ? 1 : 0;
+  }
+  __builtin_amdgcn_wave_barrier();
+  store_canonical_signed<LPL>(exps + c * EB, v, slot, cs, ln, live, neg[c] != 0);
+}
+
 // ---------------------------------------------------------------------------------------
 // launchers: RT_FN names them (modp_rt_launch_* here, modp_rt27_launch_* in the wide unit, modp_rt36_launch_* in the 4096-bit one), RT_DISPATCH launches the
 // instance of a width this unit holds, RT_ELSEWHERE hands a width of another unit over to it
@@ -1428,6 +1578,25 @@ extern "C" int RT_FN(launch_modq_poly_eval)(int lpl, const uint32_t* coef_m, int
   RT_ELSEWHERE(launch_modq_poly_eval, lpl, coef_m, t, positions, count, par_even, par_odd, out_be, csq, s);
   if (count <= 0 || t <= 0) return 0;
   RT_DISPATCH(lpl, k_rt_modq_poly_eval, dim3(rt_grid(count)), dim3(64), 0, s, coef_m, t, positions, count, par_even, par_odd, out_be, csq);
+  return (int)hipGetLastError();
+}
+
+extern "C" int RT_FN(launch_lagrange_terms)(int lpl, const int64_t* positions, const uint32_t* tiles, int ntiles, uint32_t* num_m,
+                                            uint32_t* den_m, uint8_t* den_be, const modp_rt_consts* csq, hipStream_t s) {
+  RT_ELSEWHERE(launch_lagrange_terms, lpl, positions, tiles, ntiles, num_m, den_m, den_be, csq, s);
+  if (ntiles <= 0) return 0;
+  RT_DISPATCH(lpl, k_rt_lagrange_terms, dim3(ntiles), dim3(64), 0, s, positions, reinterpret_cast<const uint4*>(tiles), num_m, den_m, den_be,
+              csq);
+  return (int)hipGetLastError();
+}
+
+extern "C" int RT_FN(launch_lagrange_finish)(int lpl, const uint32_t* tiles, int ntiles, const uint32_t* num_m, const uint32_t* den_m,
+                                             const uint8_t* dinv_be, const uint8_t* neg, uint8_t* exps, uint8_t* flags,
+                                             const modp_rt_consts* csq, hipStream_t s) {
+  RT_ELSEWHERE(launch_lagrange_finish, lpl, tiles, ntiles, num_m, den_m, dinv_be, neg, exps, flags, csq, s);
+  if (ntiles <= 0) return 0;
+  RT_DISPATCH(lpl, k_rt_lagrange_finish, dim3(ntiles), dim3(64), 0, s, reinterpret_cast<const uint4*>(tiles), num_m, den_m, dinv_be, neg,
+              exps, flags, csq);
   return (int)hipGetLastError();
 }
 #endif  // RT_FD_ONLY

@@ -77,3 +77,14 @@ int MODP_RT_FN(launch_modq_responses)(int lpl, const uint8_t* w_be, const uint8_
    parity of P at even / odd positions */
 int MODP_RT_FN(launch_modq_poly_eval)(int lpl, const uint32_t* coef_m, int t, const int64_t* positions, int count, int par_even, int par_odd,
                                   uint8_t* out_be, const modp_rt_consts* csq, hipStream_t s);
+/* The Lagrange exponents of reconstruct (csq as above).  positions: the launch's position lists back to back; tiles [ntiles][4] words
+   {the list's first position, m, the tile's first coefficient, live coefficients (1 .. 16)} on the device, a tile inside one list.
+   Workgroup w owns the slots 16 w .. 16 w + 15 of the work arrays: num_m, den_m [16 ntiles][L] limbs below 2 q' (the products of
+   the x_j and of the |x_j - x_i|, both times the same power of two), den_be the denominators as canonical EB bytes */
+int MODP_RT_FN(launch_lagrange_terms)(int lpl, const int64_t* positions, const uint32_t* tiles, int ntiles, uint32_t* num_m, uint32_t* den_m,
+                                  uint8_t* den_be, const modp_rt_consts* csq, hipStream_t s);
+/* exps[c] (EB bytes) and flags[c] of every live coefficient c of the tiles from those work arrays and dinv_be = den^(q'-2) (canonical
+   EB bytes per slot): flags[c] = 1 iff den dinv = 1 mod q'; exps[c] = num dinv mod q', or 2 q' minus that when neg[c] and it is not 0 */
+int MODP_RT_FN(launch_lagrange_finish)(int lpl, const uint32_t* tiles, int ntiles, const uint32_t* num_m, const uint32_t* den_m,
+                                   const uint8_t* dinv_be, const uint8_t* neg, uint8_t* exps, uint8_t* flags, const modp_rt_consts* csq,
+                                   hipStream_t s);

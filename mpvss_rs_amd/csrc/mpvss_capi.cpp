@@ -387,12 +387,20 @@ struct mpvss_ctx {
   unsigned long long rt_many_groups = 0, rt_many_grouped_boxes = 0, rt_many_single_boxes = 0;   // mpvss_modp_group_verify_many_stats
   // mpvss_modp_group_reconstruct_many_stats (a pass keeps its segment table in rt_run_boxes)
   unsigned long long rt_rec_passes = 0, rt_rec_grouped_secrets = 0, rt_rec_single_secrets = 0;
+  // the Lagrange exponents of reconstruct on the device (capi_modp_rt.inc, "Lagrange exponents on the device"): positions, tile
+  // table and signs of one launch, Fermat's exponent, the flags; the _call buffers are those of a whole
+  // mpvss_modp_group_reconstruct_many call, whose one-secret paths use the others meanwhile.  Nothing here is secret.
+  DevBuf rt_lag_pos, rt_lag_tiles, rt_lag_neg, rt_lag_e, rt_lag_flags, rt_lag_call_pos, rt_lag_call_tiles, rt_lag_call_neg, rt_lag_call_exp;
+  int rt_lagrange_mode = 1;                      // mpvss_ctx_set_rt_lagrange
+  unsigned long long rt_lagrange_dev_lists = 0, rt_lagrange_host_lists = 0, rt_lagrange_fallback_lists = 0;   // mpvss_modp_group_lagrange_stats
   std::vector<DevBuf*> rt_all() {
     return {&rt_consts, &rt_in[0], &rt_in[1], &rt_in[2], &rt_in[3], &rt_in[4], &rt_in[5], &rt_out[0], &rt_out[1], &rt_out[2],
             &rt_tab1, &rt_tab2, &rt_tabg, &rt_cm, &rt_small[0], &rt_small[1], &rt_out_y, &rt_buckets,
             &rt_fd_inv, &rt_cm_inv, &rt_fd_pos, &rt_fd_seeds, &rt_fd_x, &rt_fd_park,
             &rt_consts_q, &rt_sc_coef, &rt_sc_p, &rt_sc_w, &rt_sc_c, &rt_sc_r, &rt_sh_verdict, &rt_sh_c32,
             &rt_run_tiles, &rt_run_boxes, &rt_run_keyof, &rt_run_ch, &rt_run_pos,
+            &rt_lag_pos, &rt_lag_tiles, &rt_lag_neg, &rt_lag_e, &rt_lag_flags, &rt_lag_call_pos, &rt_lag_call_tiles, &rt_lag_call_neg,
+            &rt_lag_call_exp,
             &rt_comb[0].buf, &rt_comb[1].buf, &rt_comb[2].buf, &rt_comb[3].buf};
   }
   // fixed-base combs of run-time groups (rt_comb_for, capi_modp_rt.inc), used under `mu`: keyed by the bytes (q, base) -- a handle

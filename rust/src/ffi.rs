@@ -404,6 +404,11 @@ unsafe extern "C" {
                                              status: *mut c_int, gs_out: *mut u8, masks_out32: *mut u8) -> c_int;
     pub fn mpvss_modp_group_reconstruct_many_stats(ctx: *mut mpvss_ctx, passes: *mut c_ulonglong, grouped_secrets: *mut c_ulonglong,
                                                    single_secrets: *mut c_ulonglong) -> c_int;
+    pub fn mpvss_ctx_set_rt_lagrange(ctx: *mut mpvss_ctx, mode: c_int) -> c_int;
+    pub fn mpvss_modp_group_lagrange_exponents(ctx: *mut mpvss_ctx, grp: *const mpvss_modp_group, positions_host: *const i64, m: usize,
+                                               exps_out_host: *mut u8) -> c_int;
+    pub fn mpvss_modp_group_lagrange_stats(ctx: *mut mpvss_ctx, device_lists: *mut c_ulonglong, host_lists: *mut c_ulonglong,
+                                           fallback_lists: *mut c_ulonglong) -> c_int;
     // ---- hashing helpers
     pub fn mpvss_sha256(data: *const u8, len: usize, out32: *mut u8);
     pub fn mpvss_modp_hash_to_scalar(data: *const u8, len: usize, out256: *mut u8);
