@@ -224,9 +224,9 @@ int mpvss_modp_keyset_create(mpvss_ctx* ctx, int space, const uint8_t* pubkeys, 
 int mpvss_ctx_set_key_cache(mpvss_ctx* ctx, int min_boxes);
 /* Call tables (ON by default, threshold 3): when at least `min_boxes` large boxes of one mpvss_modp_verify_many /
  * mpvss_modp_verify_many_chained call present the same DEVICE-resident key array (same pointer, same n; boxes without a key set,
- * 16 384 < n <= one chunk, challenge of at most 256 bits), the library builds two rows of 64 powers per key once for the call
- * (36 KB per key, 2.4 GB for 65 536 keys; on a low-priority stream, beside the first boxes' X paths) and those boxes' a2 = y^r Y^c
- * takes them: half of the squarings under y^r, no window table of y per box.  Same bytes, verdicts and digests.  The buffer stays
+ * 16 384 < n <= one chunk, challenge of at most 256 bits), the library builds eight rows of 32 powers per key once for the call
+ * (72 KB per key, 4.8 GB for 65 536 keys; on a low-priority stream, beside the first boxes' X paths) and those boxes' a2 = y^r Y^c
+ * takes them: 255 of the 2 046 squarings under y^r, no window table of y per box.  Same bytes, verdicts and digests.  The buffer stays
  * with the context between calls; it is freed when the feature is switched off, when a workspace allocation runs out of memory and
  * with the context.  Any failure costs speed, not the call.  min_boxes: 0 switches the feature off, >= 2 sets the threshold;
  * returns the previous value (negative: error).  MPVSS_CALL_TABLES=0 in the environment: off for every context of the process.

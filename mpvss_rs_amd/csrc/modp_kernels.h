@@ -123,7 +123,7 @@ int modp_launch_keyset_twin_exp_pair(const uint32_t* ks, const uint8_t* e1, cons
 /* a2 = y^r Y^c against a registered key's table, pair layout (same table and program as modp_launch_keyset_dual_exp) */
 int modp_launch_keyset_dual_exp_pair(const uint32_t* ks, const uint32_t* tab2, const uint8_t* r, const uint8_t* c, int count, uint8_t* out,
                                      const void* cs, const void* pair_tables, hipStream_t s);
-/* call tables (modp_pair_kernels.hip): two rows of 64 entries per key, rows[x][j][d] = y_x^(d 2^(1024 j)), built once per verify_many
+/* call tables (modp_pair_kernels.hip): eight rows of 32 entries per key, rows[x][j][d] = y_x^(d 2^(256 j)), built once per verify_many
  * call; a2 = y^r Y^c against them with the operands of modp_launch_dual_exp_w6_pair in place of y's window table */
 size_t modp_call_rows_words_per_key(void);
 int modp_launch_call_rows_build(const uint8_t* pk_be, int count, uint32_t* tab, const void* cs, const void* pair_tables,

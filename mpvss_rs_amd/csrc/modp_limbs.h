@@ -49,7 +49,7 @@ LIMBS_HD u32 be256_limb(const uint8_t* __restrict__ be, int j) { return be_limb<
 
 // Geometry of a rows-by-windows table of one base y: table[j][d] = y^(d 2^(B j)), j < R rows of B bits, d < 2^W -- y^e for a
 // 2048-bit e is then the product over the rows of R B-bit exponentiations that share one chain of TOP squarings.  The registered
-// key tables are RowGeom<8, 256, 7>, the call tables RowGeom<2, 1024, 6>; every kernel that builds or reads such a table takes
+// key tables are RowGeom<8, 256, 7>, the call tables RowGeom<8, 256, 5>; every kernel that builds or reads such a table takes
 // its sizes and its digits from here.
 template <int R_, int B_, int W_>
 struct RowGeom {

@@ -564,6 +564,7 @@ __device__ __forceinline__ void rows_dual_exp_pair(const u32* __restrict__ rows,
                                                    const ModpConsts* __restrict__ cs, PairCtx& pc) {
   constexpr int R = G::R, WIN = G::WIN;
   static_assert(G::B >= 256, "a row is at least as wide as the 256-bit challenge");
+  static_assert(!SCHED || G::TOP >= 255, "a window of the 256-bit challenge's schedule may lie at weight 255: the chain must start there");
   const PairLane& pl = pc.pl;
   auto digit = [&](int j, int w) -> u32 { return G::digit(r_be + (size_t)pc.x * 256, j, w); };
   u32 acc[LP];
@@ -661,20 +662,25 @@ k_modp_keyset_twin_exp_pair(const u32* __restrict__ ks, size_t key_words, const 
 // ---------------------------------------------------------------------------------------
 // Call tables: the dealers' boxes of ONE verify_many call are boxes for the same participants, and in a2 = y^r * Y^c (dleq.rs:79-81)
 // both the window table of y and the 2 046 squarings under y^r depend on the key alone.  R rows per key,
-//   rows[x][j][d] = y_x^(d 2^(B j)),   d < 64,  j < R,  B = 2048 / R      (limbs::RowGeom<R, B, 6>),
+//   rows[x][j][d] = y_x^(d 2^(B j)),   d < 2^WIN,  j < R,  B = 2048 / R      (limbs::RowGeom<R, B, WIN>),
 // built once per call, turn y^r into the product of R exponentiations with B-bit exponents that share ONE chain of squarings:
-// 6 (NWIN - 1) squarings and R NWIN - 1 row products instead of 2 046 and 341, NWIN = ceil(B / 6), through rows_dual_exp_pair above.
-//   R = 2 (the instance in use): 1 020 squarings + 341 row products, 36 KB per key;   R = 4: 510 + 343, 72 KB per key
-// The exact integer model with the operation counts: tests/test_call_tables_model.py.
+// TOP = WIN (NWIN - 1) squarings and R NWIN - 1 row products instead of 2 046 and 341, NWIN = ceil(B / WIN), through
+// rows_dual_exp_pair above.  Y^c needs 252 .. 255 squarings of its own (c has 256 bits), so rows of 256 bits are where this ends:
+//   R = 8, WIN = 5 (the instance in use): 255 squarings + 415 row products, 72 KB per key
+//   (before: R = 2, WIN = 6: 1 020 + 341, 36 KB per key)
+// Five-bit windows, not six: the schedule of c has windows whose lowest bit lies anywhere up to weight 255, and the program takes
+// none above TOP.  WIN = 5 gives NWIN = 52 and TOP = 255 (the top window of a row is one bit wide); WIN = 6 gives TOP = 252 and
+// would drop the top window of c = 2^255 -- rows_dual_exp_pair refuses to compile that.
+// The exact integer model with the operation counts: tests/test_call_rows8_model.py (tests/test_call_tables_model.py: R = 2, 4).
 // ---------------------------------------------------------------------------------------
 namespace {
-using CallGeom = limbs::RowGeom<2, 1024, 6>;
+using CallGeom = limbs::RowGeom<8, 256, 5>;
 }  // namespace
 
 extern "C" __global__ void __launch_bounds__(64 * PAIR_WAVES) PAIR_OCC_ATTR
-k_modp_rows2_dual_exp_pair(const u32* __restrict__ rows, const u32* __restrict__ tab2, const uint8_t* __restrict__ r_be,
-                           const uint8_t* __restrict__ c_all, size_t c_stride, int count, uint8_t* __restrict__ out_be,
-                           const ModpConsts* __restrict__ cs, const uint16_t* __restrict__ c_sched, const Tables* __restrict__ gtab) {
+k_modp_call_rows_dual_exp_pair(const u32* __restrict__ rows, const u32* __restrict__ tab2, const uint8_t* __restrict__ r_be,
+                               const uint8_t* __restrict__ c_all, size_t c_stride, int count, uint8_t* __restrict__ out_be,
+                               const ModpConsts* __restrict__ cs, const uint16_t* __restrict__ c_sched, const Tables* __restrict__ gtab) {
   PAIR_KERNEL_PROLOGUE(gtab, count)
   rows_dual_exp_pair<CallGeom, true>(rows, (size_t)CallGeom::KEY_WORDS, tab2, r_be, c_all, c_stride, c_sched, out_be, cs, pc);
 }
@@ -721,8 +727,8 @@ __device__ __forceinline__ void rows_build_pair(const uint8_t* __restrict__ pk_b
 }  // namespace
 
 extern "C" __global__ void __launch_bounds__(64 * PAIR_WAVES)
-k_modp_rows2_build_pair(const uint8_t* __restrict__ pk_be, int count, u32* __restrict__ rows, const ModpConsts* __restrict__ cs,
-                        const Tables* __restrict__ gtab) {
+k_modp_call_rows_build_pair(const uint8_t* __restrict__ pk_be, int count, u32* __restrict__ rows, const ModpConsts* __restrict__ cs,
+                            const Tables* __restrict__ gtab) {
   PAIR_KERNEL_PROLOGUE(gtab, count)
   rows_build_pair<CallGeom>(pk_be, rows, cs, pc);
 }
@@ -1164,14 +1170,15 @@ extern "C" int modp_launch_keyset_dual_exp_pair(const uint32_t* ks, const uint32
   return (int)hipGetLastError();
 }
 
-// (R = 4 -- 510 squarings, 72 KB per key -- was built and measured beside R = 2: faster on average, but not by more than the spread
-//  between runs of one build, profiles/call_tables_ab.txt; the smaller table and the shorter build stay)
+// (R = 4 -- 510 squarings, 72 KB per key -- was measured beside R = 2 while the X path's chain was the bound: faster on average, but not
+//  by more than the spread between runs of one build, profiles/call_tables_ab.txt.  R = 8 at the same 72 KB, with the chain shortened:
+//  its lowest run clears R = 2's highest, profiles/call_rows8_ab.txt)
 extern "C" size_t modp_call_rows_words_per_key() { return (size_t)CallGeom::KEY_WORDS; }
 
 extern "C" int modp_launch_call_rows_build(const uint8_t* pk_be, int count, uint32_t* tab, const void* cs, const void* pair_tables,
                                            hipStream_t s) {
   if (count <= 0) return 0;
-  hipLaunchKernelGGL(k_modp_rows2_build_pair, dim3(pair_grid(count)), dim3(64 * PAIR_WAVES), 0, s, pk_be, count, tab,
+  hipLaunchKernelGGL(k_modp_call_rows_build_pair, dim3(pair_grid(count)), dim3(64 * PAIR_WAVES), 0, s, pk_be, count, tab,
                      (const ModpConsts*)cs, (const Tables*)pair_tables);
   return (int)hipGetLastError();
 }
@@ -1180,7 +1187,7 @@ extern "C" int modp_launch_call_rows_dual_exp(const uint32_t* tab, const uint32_
                                               const uint16_t* c_sched, int count, uint8_t* out, const void* cs, const void* pair_tables,
                                               hipStream_t s) {
   if (count <= 0) return 0;
-  hipLaunchKernelGGL(k_modp_rows2_dual_exp_pair, dim3(pair_grid(count)), dim3(64 * PAIR_WAVES), 0, s, tab, tab2, r, c, c_stride, count, out,
+  hipLaunchKernelGGL(k_modp_call_rows_dual_exp_pair, dim3(pair_grid(count)), dim3(64 * PAIR_WAVES), 0, s, tab, tab2, r, c, c_stride, count, out,
                      (const ModpConsts*)cs, c_sched, (const Tables*)pair_tables);
   return (int)hipGetLastError();
 }

@@ -243,11 +243,11 @@ struct mpvss_ctx {
   }
   // Call tables (mpvss_ctx_set_call_tables, on by default): a few rows per key, rows[key][j][d] = y^(d 2^(B j)), for the key array that
   // at least `call_tables_min` large boxes of ONE verify_many call share, built on a low-priority stream of the call while the first
-  // boxes' X paths run; those boxes' a2 waits for `ready` and takes modp_launch_call_rows_dual_exp: half of the
-  // squarings under y^r and no window table of y per box.  One buffer per context, kept between calls (hipMalloc of gigabytes has
+  // boxes' X paths run; those boxes' a2 waits for `ready` and takes modp_launch_call_rows_dual_exp: 255 of the
+  // 2 046 squarings under y^r and no window table of y per box.  One buffer per context, kept between calls (hipMalloc of gigabytes has
   // been measured at up to 1 s), owned by one call at a time (`in_use`); a call that finds it taken goes the plain way.
   struct CallTables {
-    void* buf = nullptr;           // [n][2][64][72] words
+    void* buf = nullptr;           // [n][8][32][72] words (modp_call_rows_words_per_key: 72 KB per key, 4.8 GB for 65 536 keys)
     size_t cap = 0;
     hipStream_t stream = nullptr;
     hipEvent_t ready = nullptr;
@@ -2002,7 +2002,7 @@ int verify_block_compute_locked(mpvss_ctx* ctx, int space, const uint8_t* commit
             TIMED_LAUNCH(ctx, 3, modp_launch_keyset_dual_exp(kt, t2p, (const uint8_t*)dr, (const uint8_t*)dchal, (int)cnt, da2,
                                                              ctx->consts, ctx->stream));
         } else if (rows_ok) {
-          // the call's rows of these keys: no window table of y, half of the squarings; the build runs on the call's own stream
+          // the call's rows of these keys: no window table of y, an eighth of the squarings; the build runs on the call's own stream
           HIPCHK(ctx, hipStreamWaitEvent(ctx->stream, call_rows->ready, 0));
           TIMED_LAUNCH(ctx, 3, modp_launch_call_rows_dual_exp(call_rows->rows, t2p, (const uint8_t*)dr, (const uint8_t*)dchal, 0,
                                                               dsched, (int)cnt, da2, ctx->consts, ctx->pair_tables, ctx->stream));

@@ -36,7 +36,7 @@ def load(path):
 
 
 def is_a1(nm):
-    """a1 = g^r X^c: the comb kernel, or the pair layout's scheduled power times g^r (a2's kernels are rows2_ / w6 / keyset ones)"""
+    """a1 = g^r X^c: the comb kernel, or the pair layout's scheduled power times g^r (a2's kernels are call_rows_ / w6 / keyset ones)"""
     return "comb_dual_exp" in nm or "exp_mul" in nm
 
 
