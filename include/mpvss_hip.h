@@ -969,6 +969,26 @@ int mpvss_modp_group_lagrange_exponents(mpvss_ctx* ctx, const mpvss_modp_group* 
 int mpvss_modp_group_lagrange_stats(mpvss_ctx* ctx, unsigned long long* device_lists, unsigned long long* host_lists,
                                     unsigned long long* fallback_lists);
 
+/* The row layout for small calls of a run-time group.  The quad layout (4 lanes per number, 16 numbers per wave) is sized for a
+ * full chip; a call of a handful to a few thousand numbers is the latency of ONE number's chain of 2 000 to 5 000 Montgomery
+ * operations.  On the row layout (16 lanes per number, 4 numbers per wave; 5 / 7 / 9 limbs per lane instead of 18 / 27 / 36) about a third
+ * of the instructions lie on that chain.  It exists for the handles at 18, 27 and 36 limbs per lane (moduli of 1043 .. 4096 bits) and
+ * for the launches of k_rt_dual_exp, k_rt_exp_sets and k_rt_comb_exp: every mpvss_modp_group_* call that reaches one of them --
+ * batch_exp, batch_exp_fixed_base, the small path of batch_twin_exp, dleq_commitments, verify_distribution, verify_shares, deal,
+ * distribute, extract_shares, reconstruct, the Lagrange inverses, and the grouped runs of verify_many / reconstruct_many by their total
+ * share count.  Results are the same bytes under every mode.
+ * mode 0 = never (the default); 1 = automatic: launches of at most mpvss_modp_group_row_max_shares numbers; 2 = whenever the handle
+ * has the layout, at any count.  Returns the mode before; no context, or another value, is MPVSS_E_INVALID.
+ * Not on the row layout: the key-set kernels, X_i (commit_eval, forward differences), the shared-squarings twin kernel, handles at 5 /
+ * 9 limbs per lane, the pair / MFMA layout; the run-time calls stay on one stream ("Row layout for small calls"). */
+int mpvss_ctx_set_rt_row(mpvss_ctx* ctx, int mode);
+/* Numbers of one launch up to which mode 1 takes the row layout: 4096 -- four numbers per wave on 1 024 SIMDs, one wave per SIMD, the
+ * derivation group 14 uses, not a measurement -- or 0 for a handle at 5 or 9 limbs per lane and for no group. */
+int mpvss_modp_group_row_max_shares(const mpvss_modp_group* grp);
+/* Launches through the three routed sites since the context was created, by the layout they took.  Either pointer may be NULL; no
+ * context is MPVSS_E_INVALID. */
+int mpvss_modp_group_row_stats(mpvss_ctx* ctx, unsigned long long* row_launches, unsigned long long* quad_launches);
+
 /* ---- hashing helpers (host only; Group::hash_to_scalar, src/groups/modp.rs:142-148) ------ */
 
 /* out32 = SHA-256(data) */

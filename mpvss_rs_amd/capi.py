@@ -67,6 +67,7 @@ EXPORTED_SYMBOLS = (
     "mpvss_modp_group_verify_many", "mpvss_modp_group_verify_many_stats",
     "mpvss_modp_group_reconstruct_many", "mpvss_modp_group_reconstruct_many_stats",
     "mpvss_ctx_set_rt_lagrange", "mpvss_modp_group_lagrange_exponents", "mpvss_modp_group_lagrange_stats",
+    "mpvss_ctx_set_rt_row", "mpvss_modp_group_row_max_shares", "mpvss_modp_group_row_stats",
     "mpvss_ec_reconstruct_many", "mpvss_ec_reconstruct_many_stats",
     "mpvss_ctx_set_ec_lagrange", "mpvss_ec_lagrange_scalars", "mpvss_ec_lagrange_stats",
     "mpvss_ctx_set_ec_box_groups", "mpvss_ec_verify_many_stats",
@@ -337,6 +338,10 @@ def load_library() -> C.CDLL:
         lib.mpvss_modp_group_lagrange_exponents.argtypes = [vp, vp, vp, sz, vp]
         lib.mpvss_modp_group_lagrange_stats.argtypes = [vp, C.POINTER(C.c_ulonglong), C.POINTER(C.c_ulonglong),
                                                         C.POINTER(C.c_ulonglong)]
+    if hasattr(lib, "mpvss_ctx_set_rt_row"):                   # (likewise)
+        lib.mpvss_ctx_set_rt_row.argtypes = [vp, ci]
+        lib.mpvss_modp_group_row_max_shares.argtypes = [vp]
+        lib.mpvss_modp_group_row_stats.argtypes = [vp, C.POINTER(C.c_ulonglong), C.POINTER(C.c_ulonglong)]
     return lib
 
 
@@ -1058,6 +1063,26 @@ class Engine:
         """position lists whose exponents were computed on the device / on the host since the context was created, and those tried
         on the device and done again on the host (counted under host too)"""
         return self._three_counters(self.lib.mpvss_modp_group_lagrange_stats, "group_lagrange_stats", ("device", "host", "fallback"))
+
+    # ---- the row layout for small calls of a run-time group ------------------------------------------------------------------
+    def set_rt_row(self, mode: int) -> int:
+        """mpvss_ctx_set_rt_row: which layout the launches of k_rt_dual_exp / k_rt_exp_sets / k_rt_comb_exp of a handle at 18 / 27 /
+        36 limbs per lane take -- 0 the quad layout always (the default), 1 the row layout up to group_row_max_shares numbers, 2 the
+        row layout at any count.  Returns the mode before."""
+        before = self.lib.mpvss_ctx_set_rt_row(self.ctx, int(mode))
+        if before < 0:
+            self._check(before, "set_rt_row")
+        return before
+
+    def group_row_max_shares(self, grp: "ModpGroup") -> int:
+        """numbers of one launch up to which mode 1 takes the row layout; 0: the handle has no row layout"""
+        return int(self.lib.mpvss_modp_group_row_max_shares(grp.handle))
+
+    def group_row_stats(self) -> dict:
+        """launches through the routed sites since the context was created, by the layout they took"""
+        row, quad = C.c_ulonglong(0), C.c_ulonglong(0)
+        self._check(self.lib.mpvss_modp_group_row_stats(self.ctx, C.byref(row), C.byref(quad)), "group_row_stats")
+        return {"row": int(row.value), "quad": int(quad.value)}
 
     # ---- sharded verification (one engine per GPU; see mpvss_rs_amd/sharding.py)
     def verify_block_compute(self, commitments: bytes, positions: Sequence[int], pubkeys: bytes, shares: bytes,

@@ -379,6 +379,66 @@ int rt_comb_for(mpvss_ctx* ctx, const mpvss_modp_group* grp, const modp_rt_const
   return 0;
 }
 
+// ---- Row layout for small calls (DESIGN section 13, "Row layout for small calls") ------------------------------------------------
+// The three launches whose program exists on the row layout (modp_rt_row_kernels.hip: 16 lanes per number) go through these
+// wrappers, which decide once per launch: the row kernel when the context's mode allows it (mpvss_ctx_set_rt_row), the handle
+// runs at 18 / 27 / 36 limbs per lane and the count fits; the quad launch otherwise, exactly as before.  The row kernel stores
+// Montgomery limbs into rt_row_m (results only), modp_rt_launch_from_mont turns them into the caller's bytes; both are timed under
+// the timer of the launch they replace.
+// Numbers of one launch up to which mode 1 takes the row layout: four numbers per wave on 1 024 SIMDs, one wave per SIMD -- the
+// derivation of group 14's ROW_MAX_NUMBERS, not a measurement; 0: the width has no row layout.
+size_t rt_row_max_shares(int lpl) { return (lpl == 18 || lpl == 27 || lpl == 36) ? 4096 : 0; }
+
+bool rt_row_takes(mpvss_ctx* ctx, const mpvss_modp_group* grp, size_t cnt) {
+  const size_t most = rt_row_max_shares(grp->lpl);
+  const bool row = most != 0 && (ctx->rt_row_mode == 2 || (ctx->rt_row_mode == 1 && cnt <= most));
+  ++(row ? ctx->rt_row_launches : ctx->rt_quad_launches);
+  return row;
+}
+
+int rt_dual_exp_any(mpvss_ctx* ctx, const mpvss_modp_group* grp, int timer, const uint32_t* tab1, size_t tab1_stride, const uint32_t* tab2,
+                    size_t tab2_stride, const uint8_t* e1, size_t e1_stride, const uint8_t* e2, size_t e2_stride, size_t cnt, uint8_t* out,
+                    const modp_rt_consts* dc) {
+  if (!rt_row_takes(ctx, grp, cnt)) {
+    TIMED_LAUNCH(ctx, timer, modp_rt_launch_dual_exp(grp->lpl, tab1, tab1_stride, tab2, tab2_stride, e1, e1_stride, e2, e2_stride, (int)cnt,
+                                                     out, dc, ctx->stream));
+    return 0;
+  }
+  RET_IF(ensure(ctx, ctx->rt_row_m, cnt * rt_L(grp) * 4));
+  uint32_t* rm = (uint32_t*)ctx->rt_row_m.p;
+  TIMED_LAUNCH(ctx, timer, modp_rt_row_launch_dual_exp(grp->lpl, tab1, tab1_stride, tab2, tab2_stride, e1, e1_stride, e2, e2_stride, (int)cnt,
+                                                       rm, dc, ctx->stream));
+  TIMED_LAUNCH(ctx, timer, modp_rt_launch_from_mont(grp->lpl, rm, (int)cnt, out, dc, ctx->stream));
+  return 0;
+}
+
+int rt_exp_sets_any(mpvss_ctx* ctx, const mpvss_modp_group* grp, int timer, const uint32_t* tab, size_t tab_stride, const uint8_t* e1,
+                    const uint8_t* e2, size_t cnt, uint8_t* out1, uint8_t* out2, const modp_rt_consts* dc) {
+  if (!rt_row_takes(ctx, grp, cnt)) {
+    TIMED_LAUNCH(ctx, timer, modp_rt_launch_exp_sets(grp->lpl, tab, tab_stride, e1, e2, (int)cnt, out1, out2, dc, ctx->stream));
+    return 0;
+  }
+  RET_IF(ensure(ctx, ctx->rt_row_m, 2 * cnt * rt_L(grp) * 4));
+  uint32_t* rm = (uint32_t*)ctx->rt_row_m.p;
+  TIMED_LAUNCH(ctx, timer, modp_rt_row_launch_exp_sets(grp->lpl, tab, tab_stride, e1, e2, (int)cnt, rm, dc, ctx->stream));
+  TIMED_LAUNCH(ctx, timer, modp_rt_launch_from_mont(grp->lpl, rm, (int)cnt, out1, dc, ctx->stream));
+  TIMED_LAUNCH(ctx, timer, modp_rt_launch_from_mont(grp->lpl, rm + cnt * rt_L(grp), (int)cnt, out2, dc, ctx->stream));
+  return 0;
+}
+
+int rt_comb_exp_any(mpvss_ctx* ctx, const mpvss_modp_group* grp, int timer, const uint32_t* comb, const uint32_t* tab2, size_t tab2_stride,
+                    const uint8_t* e1, const uint8_t* e2, size_t e2_stride, size_t cnt, uint8_t* out, const modp_rt_consts* dc) {
+  if (!rt_row_takes(ctx, grp, cnt)) {
+    TIMED_LAUNCH(ctx, timer, modp_rt_launch_comb_exp(grp->lpl, comb, tab2, tab2_stride, e1, e2, e2_stride, (int)cnt, out, dc, ctx->stream));
+    return 0;
+  }
+  RET_IF(ensure(ctx, ctx->rt_row_m, cnt * rt_L(grp) * 4));
+  uint32_t* rm = (uint32_t*)ctx->rt_row_m.p;
+  TIMED_LAUNCH(ctx, timer, modp_rt_row_launch_comb_exp(grp->lpl, comb, tab2, tab2_stride, e1, e2, e2_stride, (int)cnt, rm, dc, ctx->stream));
+  TIMED_LAUNCH(ctx, timer, modp_rt_launch_from_mont(grp->lpl, rm, (int)cnt, out, dc, ctx->stream));
+  return 0;
+}
+
 // a1 = g1^r h1^c and a2 = g2^r h2^c for cnt shares (device pointers but g1: one shared base in host bytes; c stride 0 = shared);
 // g2: the second proof's bases as bytes, or (g2 null) g2_rows: the rows of a key set from the chunk's first key on -- or, with
 // g2_key_of, from the set's first key on, share i taking key g2_key_of[i] (device; a run of boxes of mpvss_modp_group_verify_many)
@@ -391,19 +451,19 @@ int rt_dleq_dev(mpvss_ctx* ctx, const mpvss_modp_group* grp, const modp_rt_const
     RET_IF(rt_comb_for(ctx, grp, dc, g1_host, cnt, false, &tg));
     RET_IF(rt_tables(ctx, grp, dc, h1, EB, cnt, ctx->rt_tab1, &t1));
     if (tg) {
-      TIMED_LAUNCH(ctx, 1, modp_rt_launch_comb_exp(grp->lpl, tg, t1, TW, r, c, c_stride, (int)cnt, a1, dc, ctx->stream));
+      RET_IF(rt_comb_exp_any(ctx, grp, 1, tg, t1, TW, r, c, c_stride, cnt, a1, dc));
     } else {
       const uint8_t* dg1;
       RET_IF(rt_stage_small(ctx, grp, g1_host, ctx->rt_small[0], &dg1));
       RET_IF(rt_tables(ctx, grp, dc, dg1, 0, 1, ctx->rt_tabg, &tg));
-      TIMED_LAUNCH(ctx, 1, modp_rt_launch_dual_exp(grp->lpl, tg, 0, t1, TW, r, EB, c, c_stride, (int)cnt, a1, dc, ctx->stream));
+      RET_IF(rt_dual_exp_any(ctx, grp, 1, tg, 0, t1, TW, r, EB, c, c_stride, cnt, a1, dc));
     }
   }
   if (a2) {
     RET_IF(rt_tables(ctx, grp, dc, h2, EB, cnt, ctx->rt_tab2, &t2));
     if (g2) {
       RET_IF(rt_tables(ctx, grp, dc, g2, EB, cnt, ctx->rt_tab1, &t1));
-      TIMED_LAUNCH(ctx, 3, modp_rt_launch_dual_exp(grp->lpl, t1, TW, t2, TW, r, EB, c, c_stride, (int)cnt, a2, dc, ctx->stream));
+      RET_IF(rt_dual_exp_any(ctx, grp, 3, t1, TW, t2, TW, r, EB, c, c_stride, cnt, a2, dc));
     } else if (g2_key_of) {
       TIMED_LAUNCH(ctx, 3, modp_rt_launch_keyset_exp_idx(grp->lpl, g2_rows, g2_key_of, t2, TW, r, c, c_stride, (int)cnt, a2, dc, ctx->stream));
     } else {
@@ -768,8 +828,7 @@ extern "C" int mpvss_modp_group_batch_exp(mpvss_ctx* ctx, const mpvss_modp_group
     RET_IF(f.rc);
     const uint32_t* t1;
     RET_IF(rt_tables(ctx, grp, f.dc, db, f.EB, cnt, ctx->rt_tab1, &t1));
-    TIMED_LAUNCH(ctx, 3, modp_rt_launch_dual_exp(grp->lpl, t1, 16 * rt_L(grp), nullptr, 0, de, f.EB, nullptr, 0, (int)cnt, dout, f.dc,
-                                                 ctx->stream));
+    RET_IF(rt_dual_exp_any(ctx, grp, 3, t1, 16 * rt_L(grp), nullptr, 0, de, f.EB, nullptr, 0, cnt, dout, f.dc));
     return 0;
   }));
   return f.end();
@@ -1147,7 +1206,7 @@ int rt_twin_dev(RtCall& f, const uint8_t* bases, const uint8_t* e1, const uint8_
   }
   const uint32_t* tb;
   RET_IF(rt_tables(ctx, grp, dc, bases, EB, cnt, ctx->rt_tab1, &tb));
-  TIMED_LAUNCH(ctx, 3, modp_rt_launch_exp_sets(grp->lpl, tb, 16 * rt_L(grp), e1, e2, (int)cnt, out1, out2, dc, ctx->stream));
+  RET_IF(rt_exp_sets_any(ctx, grp, 3, tb, 16 * rt_L(grp), e1, e2, cnt, out1, out2, dc));
   return 0;
 }
 
@@ -1159,14 +1218,14 @@ int rt_fixed_base_dev(mpvss_ctx* ctx, const mpvss_modp_group* grp, const modp_rt
   const uint32_t* comb;
   RET_IF(rt_comb_for(ctx, grp, dc, base_host, cnt, false, &comb));
   if (comb) {
-    TIMED_LAUNCH(ctx, timer, modp_rt_launch_comb_exp(grp->lpl, comb, nullptr, 0, e, nullptr, 0, (int)cnt, out, dc, ctx->stream));
+    RET_IF(rt_comb_exp_any(ctx, grp, timer, comb, nullptr, 0, e, nullptr, 0, cnt, out, dc));
     return 0;
   }
   const uint8_t* db;
   RET_IF(rt_stage_small(ctx, grp, base_host, ctx->rt_small[0], &db));
   const uint32_t* tg;
   RET_IF(rt_tables(ctx, grp, dc, db, 0, 1, ctx->rt_tabg, &tg));
-  TIMED_LAUNCH(ctx, timer, modp_rt_launch_dual_exp(grp->lpl, tg, 0, nullptr, 0, e, EB, nullptr, 0, (int)cnt, out, dc, ctx->stream));
+  RET_IF(rt_dual_exp_any(ctx, grp, timer, tg, 0, nullptr, 0, e, EB, nullptr, 0, cnt, out, dc));
   return 0;
 }
 
@@ -1520,11 +1579,9 @@ extern "C" int mpvss_modp_group_extract_shares(mpvss_ctx* ctx, const mpvss_modp_
     } else {
       const uint32_t* tb;
       RET_IF(rt_tables(ctx, grp, f.dc, dy, EB, cnt, ctx->rt_tab1, &tb));                               // S = Y^(1/x), :310-314
-      TIMED_LAUNCH(ctx, 3, modp_rt_launch_dual_exp(grp->lpl, tb, 16 * rt_L(grp), nullptr, 0, dxi, EB, nullptr, 0, (int)cnt, dS, f.dc,
-                                                   ctx->stream));
+      RET_IF(rt_dual_exp_any(ctx, grp, 3, tb, 16 * rt_L(grp), nullptr, 0, dxi, EB, nullptr, 0, cnt, dS, f.dc));
       RET_IF(rt_tables(ctx, grp, f.dc, dS, EB, cnt, ctx->rt_tab2, &tb));                               // a2 = S^w
-      TIMED_LAUNCH(ctx, 3, modp_rt_launch_dual_exp(grp->lpl, tb, 16 * rt_L(grp), nullptr, 0, dw, EB, nullptr, 0, (int)cnt, d2, f.dc,
-                                                   ctx->stream));
+      RET_IF(rt_dual_exp_any(ctx, grp, 3, tb, 16 * rt_L(grp), nullptr, 0, dw, EB, nullptr, 0, cnt, d2, f.dc));
     }
     RET_IF(rt_fixed_base_dev(ctx, grp, f.dc, grp->G_be, dw, cnt, d1, 1));                              // a1 = G^w
     if (hdev) {                                                  // :329-343; S goes out by settle(), the challenges as 32 bytes each
@@ -1657,8 +1714,7 @@ int rt_lagrange_dev(RtCall& f, DevBuf& pos_buf, DevBuf& tile_buf, DevBuf& neg_bu
     const uint32_t* rows = (const uint32_t*)tile_buf.p + 4 * t0;
     TIMED_LAUNCH(ctx, 4, modp_rt_launch_lagrange_terms(grp->lpl, (const int64_t*)pos_buf.p, rows, nt, num_m, den_m, den_be, f.dcq, ctx->stream));
     TIMED_LAUNCH(ctx, 4, modp_rt_launch_table(grp->lpl, den_be, EB, ns, tab, f.dcq, ctx->stream));
-    TIMED_LAUNCH(ctx, 4, modp_rt_launch_dual_exp(grp->lpl, tab, 16 * L, nullptr, 0, (const uint8_t*)ctx->rt_lag_e.p, 0, nullptr, 0, ns, dinv_be,
-                                                 f.dcq, ctx->stream));                                  // den^(q'-2)
+    RET_IF(rt_dual_exp_any(ctx, grp, 4, tab, 16 * L, nullptr, 0, (const uint8_t*)ctx->rt_lag_e.p, 0, nullptr, 0, ns, dinv_be, f.dcq));   // den^(q'-2)
     TIMED_LAUNCH(ctx, 4, modp_rt_launch_lagrange_finish(grp->lpl, rows, nt, num_m, den_m, dinv_be, (const uint8_t*)neg_buf.p, exps_dev,
                                                         (uint8_t*)ctx->rt_lag_flags.p, f.dcq, ctx->stream));
   }
@@ -1767,8 +1823,7 @@ int rt_reconstruct_locked(mpvss_ctx* ctx, const mpvss_modp_group* grp, int space
   RET_IF(f.rc);
   const uint32_t* tb;
   RET_IF(rt_tables(ctx, grp, f.dc, dS, EB, m, ctx->rt_tab2, &tb));
-  TIMED_LAUNCH(ctx, 3, modp_rt_launch_dual_exp(grp->lpl, tb, 16 * rt_L(grp), nullptr, 0, dE, EB, nullptr, 0, (int)m, dF, f.dc,
-                                               ctx->stream));                                          // S_i^lambda_i
+  RET_IF(rt_dual_exp_any(ctx, grp, 3, tb, 16 * rt_L(grp), nullptr, 0, dE, EB, nullptr, 0, m, dF, f.dc));   // S_i^lambda_i
   RET_IF(rt_product_tree(ctx, grp, f.dc, dF, m));                                                      // fold with mul, :503-505
   std::vector<uint8_t> gs;
   f.to_host(dF, 1, gs);
@@ -2387,8 +2442,7 @@ int rt_reconstruct_pass(mpvss_ctx* ctx, const mpvss_modp_group* grp, int space, 
   RET_IF(ensure(ctx, ctx->rt_tab1, S * rt_L(grp) * 4));
   const uint32_t* tb;
   RET_IF(rt_tables(ctx, grp, f.dc, dS, EB, S, ctx->rt_tab2, &tb));
-  TIMED_LAUNCH(ctx, 3, modp_rt_launch_dual_exp(grp->lpl, tb, 16 * rt_L(grp), nullptr, 0, dE, EB, nullptr, 0, (int)S, dF, f.dc,
-                                               ctx->stream));                                          // S_i^lambda_i, every secret
+  RET_IF(rt_dual_exp_any(ctx, grp, 3, tb, 16 * rt_L(grp), nullptr, 0, dE, EB, nullptr, 0, S, dF, f.dc));   // S_i^lambda_i, every secret
   LAUNCHCHK(ctx, modp_rt_launch_to_mont(grp->lpl, dF, (int)S, (uint32_t*)ctx->rt_tab1.p, f.dc, ctx->stream));
   LAUNCHCHK(ctx, modp_rt_launch_product_segments(grp->lpl, (const uint32_t*)ctx->rt_tab1.p, (const uint32_t*)ctx->rt_run_boxes.p, (int)B,
                                                  dG, f.dc, ctx->stream));                              // one product per secret
@@ -2555,6 +2609,26 @@ extern "C" int mpvss_modp_group_lagrange_exponents(mpvss_ctx* ctx, const mpvss_m
   }
   RET_IF(f.end());
   memcpy(exps_out_host, exps.data(), m * grp->eb);
+  return MPVSS_OK;
+}
+
+// ---- the row layout for small calls: mode, the automatic bound of a handle, launches through the wrappers ----------------------------
+extern "C" int mpvss_ctx_set_rt_row(mpvss_ctx* ctx, int mode) {
+  if (!ctx) return MPVSS_E_INVALID;
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  if (mode < 0 || mode > 2) return fail(ctx, MPVSS_E_INVALID, "set_rt_row: mode is 0, 1 or 2");
+  const int before = ctx->rt_row_mode;
+  ctx->rt_row_mode = mode;
+  return before;
+}
+
+extern "C" int mpvss_modp_group_row_max_shares(const mpvss_modp_group* grp) { return rt_bad_group(grp) ? 0 : (int)rt_row_max_shares(grp->lpl); }
+
+extern "C" int mpvss_modp_group_row_stats(mpvss_ctx* ctx, unsigned long long* row_launches, unsigned long long* quad_launches) {
+  if (!ctx) return MPVSS_E_INVALID;
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  if (row_launches) *row_launches = ctx->rt_row_launches;
+  if (quad_launches) *quad_launches = ctx->rt_quad_launches;
   return MPVSS_OK;
 }
 

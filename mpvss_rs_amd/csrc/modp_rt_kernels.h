@@ -64,6 +64,18 @@ int modp_rt_launch_spread_challenge(const uint8_t* c_box, const uint32_t* tiles,
 /* modp_rt_fd_kernels.hip: modp_rt_launch_fd_chains at 5, 9 and 18 limbs per lane */
 int modp_rtfd_launch_fd_chains(int lpl, const uint32_t* seeds_m, int t, int n, int S, uint32_t* x_m, uint32_t* park,
                                const modp_rt_consts* cs, hipStream_t s);
+/* modp_rt_row_kernels.hip: the row layout (bn_row_rt.h, 16 lanes per number) for small calls at 18, 27 and 36 limbs per lane --
+ * any other lpl is hipErrorInvalidValue.  The argument lists of modp_rt_launch_dual_exp, _exp_sets and _comb_exp with a work
+ * buffer in place of the results: out_m[x] = the result in Montgomery limbs below 2N, L words each (exp_sets: 2 count numbers,
+ * the second set behind the first), which modp_rt_launch_from_mont turns into canonical bytes.  Not here: row variants of the
+ * key-set, commit_eval, twin_exp and fd_chain kernels, handles at 5 / 9 limbs per lane, the pair layout. */
+int modp_rt_row_launch_dual_exp(int lpl, const uint32_t* tab1, size_t tab1_stride, const uint32_t* tab2, size_t tab2_stride,
+                                const uint8_t* e1, size_t e1_stride, const uint8_t* e2, size_t e2_stride, int count, uint32_t* out_m,
+                                const modp_rt_consts* cs, hipStream_t s);
+int modp_rt_row_launch_exp_sets(int lpl, const uint32_t* tab, size_t tab_stride, const uint8_t* e1, const uint8_t* e2, int count,
+                                uint32_t* out_m, const modp_rt_consts* cs, hipStream_t s);
+int modp_rt_row_launch_comb_exp(int lpl, const uint32_t* comb, const uint32_t* tab2, size_t tab2_stride, const uint8_t* e1,
+                                const uint8_t* e2, size_t e2_stride, int count, uint32_t* out_m, const modp_rt_consts* cs, hipStream_t s);
 #ifdef __cplusplus
 }
 #endif

@@ -393,6 +393,11 @@ struct mpvss_ctx {
   DevBuf rt_lag_pos, rt_lag_tiles, rt_lag_neg, rt_lag_e, rt_lag_flags, rt_lag_call_pos, rt_lag_call_tiles, rt_lag_call_neg, rt_lag_call_exp;
   int rt_lagrange_mode = 1;                      // mpvss_ctx_set_rt_lagrange
   unsigned long long rt_lagrange_dev_lists = 0, rt_lagrange_host_lists = 0, rt_lagrange_fallback_lists = 0;   // mpvss_modp_group_lagrange_stats
+  // the row layout for small calls (rt_dual_exp_any / rt_exp_sets_any / rt_comb_exp_any, capi_modp_rt.inc): results in Montgomery
+  // limbs between the row kernel and modp_rt_launch_from_mont -- results only, never a secret
+  DevBuf rt_row_m;
+  int rt_row_mode = 0;                           // mpvss_ctx_set_rt_row
+  unsigned long long rt_row_launches = 0, rt_quad_launches = 0;   // mpvss_modp_group_row_stats
   std::vector<DevBuf*> rt_all() {
     return {&rt_consts, &rt_in[0], &rt_in[1], &rt_in[2], &rt_in[3], &rt_in[4], &rt_in[5], &rt_out[0], &rt_out[1], &rt_out[2],
             &rt_tab1, &rt_tab2, &rt_tabg, &rt_cm, &rt_small[0], &rt_small[1], &rt_out_y, &rt_buckets,
@@ -400,7 +405,7 @@ struct mpvss_ctx {
             &rt_consts_q, &rt_sc_coef, &rt_sc_p, &rt_sc_w, &rt_sc_c, &rt_sc_r, &rt_sh_verdict, &rt_sh_c32,
             &rt_run_tiles, &rt_run_boxes, &rt_run_keyof, &rt_run_ch, &rt_run_pos,
             &rt_lag_pos, &rt_lag_tiles, &rt_lag_neg, &rt_lag_e, &rt_lag_flags, &rt_lag_call_pos, &rt_lag_call_tiles, &rt_lag_call_neg,
-            &rt_lag_call_exp,
+            &rt_lag_call_exp, &rt_row_m,
             &rt_comb[0].buf, &rt_comb[1].buf, &rt_comb[2].buf, &rt_comb[3].buf};
   }
   // fixed-base combs of run-time groups (rt_comb_for, capi_modp_rt.inc), used under `mu`: keyed by the bytes (q, base) -- a handle

@@ -409,6 +409,9 @@ unsafe extern "C" {
                                                exps_out_host: *mut u8) -> c_int;
     pub fn mpvss_modp_group_lagrange_stats(ctx: *mut mpvss_ctx, device_lists: *mut c_ulonglong, host_lists: *mut c_ulonglong,
                                            fallback_lists: *mut c_ulonglong) -> c_int;
+    pub fn mpvss_ctx_set_rt_row(ctx: *mut mpvss_ctx, mode: c_int) -> c_int;
+    pub fn mpvss_modp_group_row_max_shares(grp: *const mpvss_modp_group) -> c_int;
+    pub fn mpvss_modp_group_row_stats(ctx: *mut mpvss_ctx, row_launches: *mut c_ulonglong, quad_launches: *mut c_ulonglong) -> c_int;
     // ---- hashing helpers
     pub fn mpvss_sha256(data: *const u8, len: usize, out32: *mut u8);
     pub fn mpvss_modp_hash_to_scalar(data: *const u8, len: usize, out256: *mut u8);

@@ -22,6 +22,11 @@
               twin kernel beats the sets at every measured n above, and the gate is twin against PARENT's two batch_exp calls
               at n = 65536.  Then the deal leg runs under the default library.  All lines go to profiles/modp_rt_deal_rate.txt.
 
+  row         (--row) the row layout for small calls (mpvss_ctx_set_rt_row): modes 0 and 2 of the loaded library in turns on one
+              warm context, results compared first, median of 5 -- kernels alone (timer 3) of group_batch_exp with full-width
+              exponents at 2048 / 3072 / 4096 bits and n = 1 .. 16384, and whole one-box calls (verify_distribution, deal,
+              extract_shares, verify_shares) at (5, 3) and (64, 22).  Written to profiles/modp_rt_row_rate.txt.
+
   comb        (--comb, or --legs comb) the fixed-base power g^e of a run-time group, kernels alone (mpvss_last_kernel_ms), at
               n = 1 .. 65536 for 1024 and 2048 bits.  --comb-parts parent: the launch a caller had before the comb -- a1_i = g^w_i
               inside mpvss_modp_group_deal (t = 1), timer 1: the 16-entry table of g and the left-to-right kernel.  --comb-parts
@@ -720,6 +725,81 @@ def w4096_leg(eng, a, rng):
                           "waves_per_simd": {"3072": 2, "4096": 1}}), flush=True)
 
 
+def row_leg(eng, a, rng):
+    """The row layout for small calls (mpvss_ctx_set_rt_row) against the quad layout, modes 0 and 2 of the same library taking turns on
+    one warm context (group_prepare done): (1) kernels alone (timer 3) of group_batch_exp with full-width exponents at 2048 / 3072 /
+    4096 bits, (2) whole one-box calls at (5, 3) and (64, 22).  Median of --reps (5) after a warm-up of both modes; the results of both
+    modes are compared before anything is timed."""
+    import statistics
+    import modp_rt_4096_helpers as XH
+    import modp_rt_wide_helpers as WH
+    sizes = [1, 64, 1024] if a.quick else [1, 64, 1024, 4096, 8192, 16384]
+    shapes = [(5, 3)] if a.quick else [(5, 3), (64, 22)]
+    reps = max(a.reps, 5)
+    groups = [(2048, H.rfc_prime(2048), 256), (3072, WH.group15(), WH.EB), (4096, XH.group16(), XH.EB)]
+    cat = lambda vals, eb: b"".join(v.to_bytes(eb, "big") for v in vals)
+    lines = []
+
+    def emit(row):
+        lines.append(row)
+        print(json.dumps(row), flush=True)
+
+    def turns(call, figure):
+        """{mode: median of figure() after call()} with the modes taking turns; call() gives equal results under both"""
+        got = {}
+        for mode in (0, 2):
+            eng.set_rt_row(mode)
+            got[mode] = call()
+        assert got[0] == got[2], "the two layouts disagree"
+        vals = {0: [], 2: []}
+        for _ in range(reps):
+            for mode in (0, 2):
+                eng.set_rt_row(mode)
+                t0 = time.perf_counter()
+                call()
+                vals[mode].append(figure(t0))
+        eng.set_rt_row(0)
+        return {m: statistics.median(v) for m, v in vals.items()}
+
+    for bits, q, eb in groups:
+        grp = ModpGroup(q, elem_bytes=eb) if eb != 256 else ModpGroup(q)
+        eng.group_prepare(grp)
+        rb = lambda n: b"".join(rng.getrandbits(bits).to_bytes(eb, "big") for _ in range(n))
+        for n in sizes:
+            B, E = rb(n), rb(n)
+            med = turns(lambda: eng.group_batch_exp(grp, B, E), lambda t0: max(0.0, eng.kernel_ms(3)))
+            emit({"what": "group_batch_exp_kernels", "bits": bits, "limbs_per_lane": grp.limbs_per_lane, "n": n,
+                              "quad_kernel_ms": round(med[0], 3), "row_kernel_ms": round(med[2], 3),
+                              "row_over_quad": round(med[2] / med[0], 3)})
+        for n, t in shapes:
+            pos = list(range(1, n + 1))
+            privs = [rng.randrange(3, q - 1) | 1 for _ in range(n)]
+            xinv = cat([pow(k, -1, q - 1) for k in privs], eb)
+            pks = eng.group_batch_exp_fixed_base(grp, cat([2], eb), cat(privs, eb))
+            coeffs, ws, w2 = rb(t), rb(n), rb(n)
+            cm = eng.group_batch_exp_fixed_base(grp, cat([4], eb), coeffs)
+            box = eng.group_deal(grp, coeffs, pos, pks, ws)
+            S, Cs = eng.group_extract_shares(grp, pks, box["Y"], xinv, w2)
+            R = capi.group_dleq_responses(grp, w2, cat(privs, eb), Cs)
+            calls = {
+                "group_verify_distribution": lambda: eng.group_verify_distribution(grp, cm, pos, pks, box["Y"], box["responses"], box["challenge"]),
+                "group_deal": lambda: eng.group_deal(grp, coeffs, pos, pks, ws),
+                "group_extract_shares": lambda: eng.group_extract_shares(grp, pks, box["Y"], xinv, w2),
+                "group_verify_shares": lambda: bytes(eng.group_verify_shares(grp, pks, S, box["Y"], Cs, R)),
+            }
+            for what, call in calls.items():
+                med = turns(call, lambda t0: (time.perf_counter() - t0) * 1e3)
+                emit({"what": what, "bits": bits, "n": n, "t": t, "quad_ms": round(med[0], 3), "row_ms": round(med[2], 3),
+                                  "row_over_quad": round(med[2] / med[0], 3)})
+        grp.close()
+    with open(a.out, "w") as f:
+        f.write("# tools/modp_rt_rate.py --row: set_rt_row modes 0 (quad layout) and 2 (row layout) of one library in turns on one warm\n"
+                "# context, median of %d after a warm-up of both; kernel_ms = timer 3 of group_batch_exp, full-width exponents; *_ms of the\n"
+                "# one-box calls = wall time of the whole call from host buffers\n" % reps)
+        for row in lines:
+            f.write(json.dumps(row) + "\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=3)
@@ -740,6 +820,7 @@ def main():
     ap.add_argument("--share-hash", action="store_true", help="the per-share hash on the device: alone, the share-hash leg; with --ab, its interleaved A/B")
     ap.add_argument("--share-hash-parts", default="mode2", help="of the share-hash leg: parent (the library under test as it is), mode2 (set_rt_share_hash(2))")
     ap.add_argument("--share-hash-wide", action="store_true", help="of the share-hash leg: the one 3072-bit row, n = 16384")
+    ap.add_argument("--row", action="store_true", help="the row layout for small calls: modes 0 and 2 of set_rt_row in turns (profiles/modp_rt_row_rate.txt)")
     ap.add_argument("--package-root", default=None, help="import mpvss_rs_amd (bindings and library) from this checkout")
     ap.add_argument("--ab", default=None, metavar="PARENT", help="the interleaved A/B against a built checkout of the parent commit")
     ap.add_argument("--rounds", type=int, default=2, help="of --ab: how often the three processes take turns")
@@ -748,7 +829,7 @@ def main():
     ap.add_argument("--out", default=None, help="of --ab: the file written (profiles/modp_rt_deal_rate.txt, or _comb_rate.txt)")
     a = ap.parse_args()
     if a.out is None:
-        a.out = os.path.join(ROOT, "profiles", "modp_rt_share_hash_rate.txt" if a.share_hash else "modp_rt_keyset_rate.txt" if a.keyset else "modp_rt_scalar_rate.txt" if a.scalar else "modp_rt_fd_rate.txt" if a.fd else "modp_rt_comb_rate.txt" if a.comb else "modp_rt_deal_rate.txt")
+        a.out = os.path.join(ROOT, "profiles", "modp_rt_row_rate.txt" if a.row else "modp_rt_share_hash_rate.txt" if a.share_hash else "modp_rt_keyset_rate.txt" if a.keyset else "modp_rt_scalar_rate.txt" if a.scalar else "modp_rt_fd_rate.txt" if a.fd else "modp_rt_comb_rate.txt" if a.comb else "modp_rt_deal_rate.txt")
     if a.ab:
         return ab_share_hash(a) if a.share_hash else ab_keyset(a) if a.keyset else ab_scalar(a) if a.scalar else ab_fd(a) if a.fd else ab_comb(a) if a.comb else ab(a)
     if a.comb:
@@ -759,6 +840,8 @@ def main():
         a.legs = "scalar"
     if a.keyset:
         a.legs = "keyset"
+    if a.row:
+        a.legs = "row"
     if a.share_hash:
         a.legs = "share_hash"
         import torch  # noqa: F401  (its own HIP runtime must be loaded before the library's, for the device-space row)
@@ -784,6 +867,8 @@ def main():
         share_hash_leg(eng, a, rng)
     if "w4096" in legs:
         w4096_leg(eng, a, rng)
+    if "row" in legs:
+        row_leg(eng, a, rng)
     if "rates" not in legs:
         eng.close()
         return
